@@ -29,6 +29,11 @@ the 1.5 MB gradient all-reduce of train mode.  ONE JSON line on rank 0.
                   single_episode_eager_step_episodes_per_sec (same schedule) or `value`
 Extra fields: single_episode_eager_step_episodes_per_sec (E = 1, eager: the reference's own schedule),
 single_episode_graph_step_episodes_per_sec (the same as one captured hipGraph) and eval_forward_episodes_per_sec.
+  --dump-outputs DIR -- after the headline's timed steps, what its LAST step handed its caller, as DIR/<name>.npy (rank 0;
+                  float32, float64 for integers and float64 results; at most 64 MB, larger arrays as a fixed seeded sample):
+                  train: per-episode loss / lp_loss / contrast_loss / logits / metrics and the model state after the
+                  optimiser step (state.<name>); eval: per-episode logits and loss.  Inputs and weights are seeded, so
+                  two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -192,7 +197,11 @@ def main():
     ap.add_argument("--roofline-kernel", default="auto", help="entry point to price (auto = the one taking most time)")
     ap.add_argument("--steady-steps", type=int, default=150,
                     help="train mode: optimiser steps from the initial weights before the headline is timed (0 = headline on fresh weights)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -251,6 +260,7 @@ def main():
     cg_acc = [0, 0, 0]    # CG iterations of the forward solves: sum, systems, max
     invalid = []          # reasons why a timed leg does not count (every episode must have a converged, exact head)
     redone_notes = []
+    last_eval = []        # eval legs: the (logits, loss) pairs the last step's launches returned
 
     def head_flags():
         hb = model._head[1]
@@ -275,8 +285,7 @@ def main():
     def eval_step(i):
         model.eval()
         runner.begin_step()
-        for b in pool_batches[i & 1]:
-            runner.eval_batch(b)
+        last_eval[:] = [runner.eval_batch(b) for b in pool_batches[i & 1]]
         bad, ovf, its, mx = runner.step_status()
         cg_acc[0] += its; cg_acc[1] += E; cg_acc[2] = max(cg_acc[2], mx)
         if bad or ovf:
@@ -286,7 +295,8 @@ def main():
         model.eval()
         sx, sy, qx, qy = pool[i % n_pool][:4]
         with torch.no_grad():
-            model(sx, sy, qx, qy)
+            logits, loss = model(sx, sy, qx, qy)
+        last_eval[:] = [(logits.unsqueeze(0), loss.view(1))]
         lp_flags.append(head_flags())
 
     def timed(step_fn, steps, warmup):
@@ -338,6 +348,7 @@ def main():
             extra["fresh_weights"] = fresh
         else:
             elapsed, cg = el_f, cg_f
+        dumped = headline_outputs(model, trainer, last_eval, train) if args.dump_outputs else None
         E = Eeff
         if batched and not args.no_extras:
             n_e = max(args.steps, 16)
@@ -369,6 +380,7 @@ def main():
         else:
             E = 1
             elapsed, cg = timed(eval_step_eager, args.steps, args.warmup)
+        dumped = headline_outputs(model, trainer, last_eval, train) if args.dump_outputs else None
     cg_mean, cg_max = cg
 
     # roofline leg: ONE more step of the headline kind with a HIP event pair (torch's current stream = the launch stream)
@@ -576,11 +588,49 @@ def main():
         "train_steps_redone": {"count": getattr(trainer, "n_redone", 0) if trainer is not None else 0, "notes": redone_notes},
     }
     out.update(extra)
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     if not out["valid"]:
         print("bench.py: WARNING, the line below is flagged invalid: %s" % "; ".join(invalid), file=sys.stderr)
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def headline_outputs(model, trainer, last_eval, train):
+    """{name: host tensor} of what the headline's last timed step handed its caller.  Copied at once: the legs after it
+    step the model again and replay the same buffers."""
+    if train:  # DPTrainer.last_outputs: (loss, lp_loss, contrast_loss, logits (n_q, C, N), metrics (4,)) per episode
+        outs = trainer.last_outputs
+        got = {name: torch.stack([o[j] for o in outs]).cpu()
+               for j, name in enumerate(("loss", "lp_loss", "contrast_loss", "logits", "metrics"))}
+        got.update(("state." + k, v.detach().cpu()) for k, v in model.state_dict().items())
+        return got
+    return {"logits": torch.cat([o[0] for o in last_eval]).cpu(), "loss": torch.cat([o[1].view(-1) for o in last_eval]).cpu()}
+
+
+def dump_outputs(out_dir, arrays, budget=60 << 20):  # (60 MiB of data + .npy headers: under 64 MB however counted)
+    """DIR/<name>.npy: float32 stays float32, everything else is stored as float64.  If the whole exceeds `budget` bytes,
+    every array above 1 MB keeps the same fraction of its elements, drawn with a fixed seed (flattened, in index order)."""
+    import numpy as np
+    arrs = {}
+    for k, v in arrays.items():
+        a = v.numpy()
+        arrs[k] = a if a.dtype == np.float32 else a.astype(np.float64)
+    big = [k for k, a in arrs.items() if a.nbytes > (1 << 20)]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        room = budget - sum(a.nbytes for k, a in arrs.items() if k not in big)
+        frac = room / float(sum(arrs[k].nbytes for k in big))
+        for k in big:
+            a = arrs[k].reshape(-1)
+            keep = np.sort(np.random.RandomState(0).choice(a.size, int(a.size * frac), replace=False))
+            arrs[k] = a[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    print("bench.py: %d array(s), %.1f MB written to %s%s" % (len(arrs), sum(a.nbytes for a in arrs.values()) / 2 ** 20, out_dir,
+          " (sampled: %s)" % ", ".join(big) if total > budget else ""), file=sys.stderr)
 
 
 def cpu_baseline(S, cfg, workload, extra, train, batched):

@@ -7,7 +7,13 @@ there), and the interpreter that has torch has no h5py.  `write_episode` / `read
 nothing but h5py and print, so their two function definitions are taken out of the file with `ast` and compiled on
 their own with `h5 = h5py`: the code that writes the fixture is the reference's, unmodified.  The episode is
 deterministic (numpy RandomState below; the test regenerates it).  `--check FILE` reads FILE with the reference's
-read_episode and prints a digest (tests/test_episode_h5.py hands it files written by r3dfsseg_amd/h5lite.py).
+read_episode and prints a digest.
+
+    python oracle/gen_golden_h5.py --h5lite                  # the interpreter with torch (no h5py needed)
+
+writes tests/golden/episode_h5lite.h5: the seed-9 episode written by r3dfsseg_amd/h5lite.py.  Hand it to `--check`
+once: the digest it prints must be tests/test_episode_h5.py's digest of that episode.  The test then compares a fresh
+h5lite write with this file byte for byte (modification times aside), so it needs neither h5py nor the reference.
 """
 import ast
 import hashlib
@@ -49,6 +55,13 @@ def digest(arrays):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--h5lite"]:
+        sys.path.insert(0, ROOT)
+        from r3dfsseg_amd import episode_io as EIO, h5lite
+        out = os.path.join(ROOT, "tests", "golden", "episode_h5lite.h5")
+        h5lite.write_datasets(out, [(n, np.asarray(a, dtype=dt)) for (n, dt), a in zip(EIO.EPISODE_FIELDS, episode(seed=9))])
+        print(out, os.path.getsize(out))
+        sys.exit(0)
     write_episode, read_episode = reference_functions()
     if len(sys.argv) == 3 and sys.argv[1] == "--check":
         print(digest(read_episode(sys.argv[2])))
