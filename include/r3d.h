@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 const char* r3d_last_error_string(void);
-int r3d_abi_version(void); /* 4 (round 4: r3d_edge_stats1 + esum, r3d_edgeconv_bwd + zwin, esum) */
+int r3d_abi_version(void); /* 5: r3d_knn_topk_batched takes one workspace (r3d_knn_ws_words) */
 /* Arithmetic of the GEMM-shaped kernels that decide no index (self-attention forward / backward, r3d_pointwise_conv*,
  * r3d_gemm_tn): 0 = fp32 matrix core (v_mfma_f32_32x32x2_f32), 1 = every fp32 operand cut into three bf16 pieces, six
  * v_mfma_f32_32x32x16_bf16 per product block accumulated in fp32 (fp32-level accuracy at 2.67x the matrix rate;
@@ -81,30 +81,25 @@ long r3d_knn_norm_ws_words(int B, int N);  /* floats of norm_ws: B*N norms + per
 int r3d_knn_topk(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
                  const int32_t* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out, float* score_out,
                  int32_t* status, void* stream);
-/* the same with a scratch of r3d_knn_split_ws_words(B, N, k) floats: for k > 32 with status != NULL and so few query
- * tiles that even twice as many workgroups fit the chip in one round (2 B ceil(N/32) <= 256), the candidate axis is
- * dealt to two workgroups per tile and their sorted lists are merged -- same result, bit for bit */
-long r3d_knn_split_ws_words(int B, int N, int k);
-int r3d_knn_topk_split(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                       const int32_t* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out, float* score_out,
-                       int32_t* status, float* split_ws, long split_ws_words, void* stream);
-
 /* B point sets with their own valid counts: set b has n_valid_dev[b * n_valid_stride] rows (the graph nodes of B episodes'
- * label-propagation systems, each at its capacity N).  status: ONE word for the batch. */
+ * label-propagation systems, each at its capacity N).  status: ONE word for the batch.
+ * ws: one scratch of r3d_knn_ws_words(B, N, C, k, flags) floats, 16-byte aligned; flags bit 0 = status is given, bit 1 =
+ * x_cm is given.  The library places in it what the path it selects needs: the squared norms, per-tile overflow flags,
+ * the channel-major copy, the two partial lists per row when the large-k kernel splits its candidate axis (so few query
+ * tiles that even twice as many workgroups fit the chip in one round), and the bf16 pieces of the points (C % 64 == 0,
+ * needs x): the streamed kernels then run their THRESHOLD pass -- which only needs a lower bound of every score -- on the
+ * bf16 matrix core, and for k <= 32 (x 16-byte aligned, ldx % 4 == 0) their second pass as a bf16 FILTER: a candidate
+ * whose score's upper bound reaches the threshold is kept, and only the kept ones (~k + 10 per query) get their exact
+ * score -- the fp32 fmaf chain in channel order, bit for bit the accumulation of the all-pairs fp32 pass it replaces.
+ * Indices and scores are the same bits on every path. */
+long r3d_knn_ws_words(int B, int N, int C, int k, int flags);
 int r3d_knn_topk_batched(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                         const int32_t* n_valid_dev, int n_valid_stride, float* norm_ws, float* cm_ws, int32_t* idx_out,
-                         float* score_out, int32_t* status, float* split_ws, long split_ws_words, float* bf_ws,
-                         long bf_ws_words, void* stream);
-/* bf_ws: optional scratch of r3d_knn_bf_ws_words(B, N, C) floats (needs x and C % 64 == 0): the streamed kernels then run
- * their THRESHOLD pass -- which only needs a lower bound of every score -- on the bf16 matrix core, and (x 16-byte aligned,
- * ldx % 4 == 0) their second pass as a bf16 FILTER: a candidate whose score's upper bound reaches the threshold is kept,
- * and only the kept ones (~k + 10 per query) get their exact score -- the fp32 fmaf chain in channel order, bit for bit
- * the accumulation of the all-pairs fp32 pass it replaces.  Indices and scores are bit-identical with and without bf_ws. */
-long r3d_knn_bf_ws_words(int B, int N, int C);
-/* test / A-B utility: 0 keeps the threshold pass on the fp32 core even when bf_ws is given (same results).  Returns the
+                         const int32_t* n_valid_dev, int n_valid_stride, float* ws, long ws_words, int32_t* idx_out,
+                         float* score_out, int32_t* status, void* stream);
+/* test / A-B utility: 0 keeps the threshold pass on the fp32 core (same results).  Returns the
  * previous setting. */
 int r3d_debug_set_knn_bf16_threshold(int on);
-/* the same for the second pass: 0 keeps it the all-pairs fp32 pass (same results) */
+/* the same for the second pass: <= 0 keeps it the all-pairs fp32 pass, > 0 the bf16 filter where it applies (same results) */
 int r3d_debug_set_knn_bf16_filter(int on);
 /* 1: launches captured into a hipGraph may use their stream's packed-weight scratch of the bf16 x 3 point-wise GEMM (it
  * must exist already: run the sequence eagerly on that stream first).  The caller promises that the captured graph is the

@@ -29,8 +29,6 @@ _SIGS = {
     "r3d_copy_cols": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_f]),
     "r3d_sqnorm": (c_i, [c_f, c_l, c_l, c_i, c_f, c_f]),
     "r3d_knn_topk": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-    "r3d_knn_split_ws_words": (c_l, [c_i, c_i, c_i]),
-    "r3d_knn_topk_split": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_f]),
     "r3d_pointwise_conv": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_f, c_i, c_f, c_l, c_f]),
     "r3d_edgeconv_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_f]),
     "r3d_attention_ws_words": (c_l, [c_i, c_i]),
@@ -90,9 +88,8 @@ _SIGS = {
     "r3d_miou_accumulate": (c_i, [c_f, c_f, c_l, c_f, c_i, c_i, c_f, c_f]),
     "r3d_query_logits_ce": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
     # ---- ABI version 3: segments (training encoder) and batches of episodes (head)
-    "r3d_knn_topk_batched": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_f, c_l,
-                                   c_f]),
-    "r3d_knn_bf_ws_words": (c_l, [c_i, c_i, c_i]),
+    "r3d_knn_topk_batched": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_l, c_f, c_f, c_f, c_f]),
+    "r3d_knn_ws_words": (c_l, [c_i, c_i, c_i, c_i, c_i]),
     "r3d_debug_set_knn_bf16_threshold": (c_i, [c_i]),
     "r3d_debug_set_knn_bf16_filter": (c_i, [c_i]),
     "r3d_set_wpack_in_capture": (c_i, [c_i]),
@@ -135,7 +132,7 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(r3d_[a-z0-9_]+)\s*\(", txt)))
 
 
-ABI_VERSION = 4  # include/r3d.h; 4 (round 4): r3d_edge_stats1(+esum), r3d_edgeconv_bwd(+zwin, esum)
+ABI_VERSION = 5  # include/r3d.h; 5: r3d_knn_topk_batched takes one workspace of r3d_knn_ws_words floats
 
 
 def load():

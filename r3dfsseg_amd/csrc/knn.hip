@@ -1386,16 +1386,6 @@ __global__ __launch_bounds__(256) void r3d_knn_merge_kernel(const int* __restric
     }
 }
 
-static size_t knn_append_lds_bytes(int C, int waves, int cap, int top, int kch = 32, bool bfa = false) {
-  const int nch = (C + 2 * kch - 1) / (2 * kch);
-  const size_t a = 32 * (size_t)(nch * 2 * kch + 4);  // (row stride + 1 for the fp32 passes, + 4 for the filter form)
-  size_t g = 32 * (size_t)(top * waves * 32 + 1);
-  if (bfa) g = ((g + 3) & ~(size_t)3) + 32 * (size_t)(2 * nch * 64 + 8) / 2 + 64;  // + the query rows' bf16 pieces, bound terms
-  const size_t bsz = 2 * 32 * (size_t)cap;
-  return sizeof(float) * (a + (g > bsz ? g : bsz));
-}
-static size_t knn_big_lds_bytes(int C, bool bfa = false) { return knn_append_lds_bytes(C, 8, 384, 2, 32, bfa); }
-
 // bf16 pieces of the points for the bf16 passes of r3d_knn_append_kernel<..., BFA = true>, per set [piece][chunk of 8
 // channels][point][8] (chunk-major: see the kernel's staging loop for why),
 // Cp = C rounded up to 64 (zeros), cut from the point MINUS its set's mean: hi = the top 16 bits of the value, lo = the top
@@ -1480,27 +1470,25 @@ __global__ __launch_bounds__(256) void r3d_knn_cnorm_kernel(const float* __restr
   s += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x140, 0xF, 0xF, true));  // row_mirror
   if (sub == 0 && m < rows) cnorm[m] = s;
 }
-// A/B switch (tests, tools): 0 = the threshold pass stays on the fp32 core even when bf_ws is given.  Same results.
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  knn_plan decides, from the shape and what the caller hands over, which kernels a call runs and the scratch
+// they need; r3d_knn_ws_words sizes the workspace from that decision and r3d_knn_topk_batched carves it the same way.
+// ---------------------------------------------------------------------------------------------------------------------
+// A/B switch (tests, tools): 0 = the threshold pass stays on the fp32 core.  Same results.
 static int g_knn_bf16_threshold = getenv("R3D_KNN_FP32_THRESHOLD") ? 0 : 1;
 // ... and: 0 = pass B stays the all-pairs fp32 pass (no bf16 filter + exact scores of the survivors).  Same results.
+// (The filter runs in the k <= 32 configuration only.  In the k > 32 one it loses -- 230 survivors per query, each a row
+// gather the L1 serves one line look-up at a time: measured 6.9 ms against 5.6 ms per 32 graphs of 4 396 nodes.)
 static int g_knn_bf16_filter = getenv("R3D_KNN_FP32_PASS_B") ? 0 : 1;
-// (2: also in the k > 32 configuration, where it loses -- 230 survivors per query, each a row gather the L1 serves one line
-// look-up at a time: measured 6.9 ms against 5.6 ms per 32 graphs of 4 396 nodes; kept for tests and tools/knnbench)
 extern "C" int r3d_debug_set_knn_bf16_filter(int on) {
   const int old = g_knn_bf16_filter;
-  g_knn_bf16_filter = on < 0 ? 0 : on > 2 ? 2 : on;
+  g_knn_bf16_filter = on > 0 ? 1 : 0;
   return old;
 }
 extern "C" int r3d_debug_set_knn_bf16_threshold(int on) {
   const int old = g_knn_bf16_threshold;
   g_knn_bf16_threshold = on ? 1 : 0;
   return old;
-}
-// floats of bf_ws (r3d_knn_topk_batched): the packed pieces, 4 bytes per point and (padded) channel
-// (pieces B N Cp | means B Cp | centred squared norms B N)
-extern "C" long r3d_knn_bf_ws_words(int B, int N, int C) {
-  const long Cp = ((long)C + 63) / 64 * 64;
-  return (long)B * N * Cp + (long)B * Cp + (long)B * N + 64;
 }
 #ifndef KM_WAVES  // mid configuration (overridable for tools/knnbench sweeps)
 #define KM_WAVES 4
@@ -1512,57 +1500,20 @@ extern "C" long r3d_knn_bf_ws_words(int B, int N, int C) {
                      // 277 us per call against 306 (no sampling), 324 (1/4, 192 slots) and 841 (1/8: repairs)
 #endif
 
+// dynamic LDS of r3d_knn_append_kernel<waves, cap, top, kch, ..., bfa, ...>
+static size_t knn_append_lds_bytes(int C, int waves, int cap, int top, int kch, bool bfa) {
+  const int nch = (C + 2 * kch - 1) / (2 * kch);
+  const size_t a = 32 * (size_t)(nch * 2 * kch + 4);  // (row stride + 1 for the fp32 passes, + 4 for the filter form)
+  size_t g = 32 * (size_t)(top * waves * 32 + 1);
+  if (bfa) g = ((g + 3) & ~(size_t)3) + 32 * (size_t)(2 * nch * 64 + 8) / 2 + 64;  // + the query rows' bf16 pieces, bound terms
+  const size_t bsz = 2 * 32 * (size_t)cap;
+  return sizeof(float) * (a + (g > bsz ? g : bsz));
+}
+// dynamic LDS of r3d_knn_topk_kernel
 static size_t knn_lds_bytes(int C) {
   const int Cp = (C + 1) & ~1;
   return sizeof(float) * ((size_t)KNN_Q * (Cp + 1) + (size_t)KNN_CH * (KNN_SLAB + 1) +
                           (size_t)KNN_Q * (KNN_CH + 1) + KNN_Q);
-}
-
-// launch one instance of the append-and-rank kernel (raising its dynamic-LDS limit once per instance)
-template <int WAVES, int CAP, int TOP, int KCH, int SAMPLE, bool FULLC, int SMODE, bool BFA = false, bool BFB = false>
-static int knn_append_launch_mode(dim3 grid, size_t lds, hipStream_t st, const float* xT, long ldT, int N, int C, int k,
-                                  const int* n_valid_dev, int n_valid_stride, const float* nrm, int* idx_out, float* score_out, int* status,
-                                  int* tile_flags, int nsplit = 1, int* idx_tmp = nullptr, float* sc_tmp = nullptr,
-                                  const unsigned short* xpk = nullptr, const float* cnorm = nullptr, const float* xpm = nullptr,
-                                  long ldx = 0) {
-  static size_t attr = 0;
-  if (lds > attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SMODE, BFA, BFB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    R3D_REQUIRE(e == hipSuccess, "r3d_knn_topk: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-    attr = lds;
-  }
-  hipLaunchKernelGGL((r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SMODE, BFA, BFB>), grid, dim3(64 * WAVES), lds, st,
-                     xT, ldT, N, C, k, SMODE, n_valid_dev, n_valid_stride, nrm, idx_out, score_out, status, tile_flags, nsplit,
-                     idx_tmp, sc_tmp, xpk, cnorm, xpm, ldx);
-  return R3D_OK;
-}
-// the same with the threshold pass on the bf16 matrix core (xpk: r3d_knn_pack_bf_kernel's output)
-// xpm != nullptr: the filter pass on the bf16 core as well, exact scores for the survivors alone (BFB)
-template <int WAVES, int CAP, int TOP, int SAMPLE>
-static int knn_append_launch_bfa(dim3 grid, size_t lds, hipStream_t st, const float* xT, long ldT, int N, int C, int k, int mode,
-                                 const int* n_valid_dev, int n_valid_stride, const float* nrm, int* idx_out, float* score_out,
-                                 int* status, int* tile_flags, const unsigned short* xpk, const float* cnorm,
-                                 const float* xpm = nullptr, long ldx = 0) {
-#define KB_GO(SM, FB)                                                                                                            \
-  knn_append_launch_mode<WAVES, CAP, TOP, 32, SAMPLE, true, SM, true, FB>(grid, lds, st, xT, ldT, N, C, k, n_valid_dev, n_valid_stride, \
-                                                                          nrm, idx_out, score_out, status, tile_flags, 1, nullptr,   \
-                                                                          nullptr, xpk, cnorm, xpm, ldx)
-  if (xpm) return mode == R3D_SCORE_DGCNN ? KB_GO(R3D_SCORE_DGCNN, true) : KB_GO(R3D_SCORE_L2, true);
-  return mode == R3D_SCORE_DGCNN ? KB_GO(R3D_SCORE_DGCNN, false) : KB_GO(R3D_SCORE_L2, false);
-#undef KB_GO
-}
-template <int WAVES, int CAP, int TOP, int KCH, int SAMPLE, bool FULLC>
-static int knn_append_launch(dim3 grid, size_t lds, hipStream_t st, const float* xT, long ldT, int N, int C, int k, int mode,
-                             const int* n_valid_dev, int n_valid_stride, const float* nrm, int* idx_out, float* score_out, int* status,
-                             int* tile_flags, int nsplit = 1, int* idx_tmp = nullptr, float* sc_tmp = nullptr) {
-  return mode == R3D_SCORE_DGCNN
-             ? knn_append_launch_mode<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, R3D_SCORE_DGCNN>(grid, lds, st, xT, ldT, N, C, k, n_valid_dev, n_valid_stride,
-                                                                                            nrm, idx_out, score_out, status, tile_flags,
-                                                                                            nsplit, idx_tmp, sc_tmp)
-             : knn_append_launch_mode<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, R3D_SCORE_L2>(grid, lds, st, xT, ldT, N, C, k, n_valid_dev, n_valid_stride, nrm,
-                                                                                         idx_out, score_out, status, tile_flags, nsplit,
-                                                                                         idx_tmp, sc_tmp);
 }
 
 extern "C" int r3d_sqnorm(const float* x, long ldx, long rows, int C, float* out, void* stream) {
@@ -1578,8 +1529,224 @@ extern "C" int r3d_pm_to_cm_pitched(const float* in, long ld, int B, int C, int 
 // row pitch of the internal channel-major copies: N + 32 floats, so that consecutive channels of
 // one point do not sit a power-of-two stride apart (same L2 channel for every load of a chain)
 extern "C" long r3d_cm_pitch(int N) { return (long)((N + 31) / 32) * 32 + 32; }
-// floats of norm_ws: the squared norms (B*N) + one overflow flag per 32-row tile (k <= 32 path) + padding
+// floats of r3d_knn_topk's norm_ws: the squared norms (B*N) + one overflow flag per 32-row tile (k <= 32 path) + padding
 extern "C" long r3d_knn_norm_ws_words(int B, int N) { return (long)B * N + (long)B * ((N + 31) / 32) + 64; }
+
+enum KnnPath {
+  KNN_STREAMED_SMALL,  // k <= 32, C <= 64: append-and-rank, mid configuration; overflowed tiles redone by the two-pass kernel
+  KNN_STREAMED_LARGE,  // k > 32 with a status word: append-and-rank, big configuration; overflow -> *status bit 0
+  KNN_INSERTION,       // everything else: the sorted-insertion kernel
+};
+struct KnnPlan {
+  KnnPath path;
+  bool few;    // (small) fewer row tiles than CUs: 8 waves per tile instead of 4
+  bool split;  // (large) the candidate axis dealt to two workgroups per tile, their lists merged
+  bool bf;     // bf16 pieces of the points: the threshold pass (and in the small path the filter) on the bf16 matrix core
+  // the workspace, floats from its start; each part begins on a 64-float boundary (pieces, means: 16-byte vector reads)
+  long norms, tile_flags, xcm, pieces, mean, cnorm, split_idx, split_sc, words;
+};
+// extras: the split lists and the bf16 pieces may be placed in the workspace (not by r3d_knn_topk, whose scratch is two
+// fixed buffers)
+static KnnPlan knn_plan(int B, int N, int C, int k, bool status, bool x_cm, bool extras) {
+  KnnPlan p = {};
+  const long tiles = ((long)N + 31) / 32;
+  if (k <= 32 && C <= 64) {
+    p.path = KNN_STREAMED_SMALL;
+    // (the 2 query clouds of a training episode: 128 tiles; each wave's chain of sub-tiles is half as long with 8 waves)
+    p.few = tiles * B <= 256;
+    p.bf = extras && C % 64 == 0 && !p.few;
+  } else if (status && knn_append_lds_bytes(C, 8, 384, 2, 32, false) <= 160 * 1024) {
+    p.path = KNN_STREAMED_LARGE;
+    // two workgroups per query tile when BOTH halves of every tile still fit the chip in one round (the kernel's
+    // 123 KB of LDS admit one workgroup per CU: at workload S, 138 tiles -> 276 workgroups ran as two rounds, 489 us
+    // against 412 us unsplit) and every half still holds >= 2 k candidates
+    p.split = extras && 2 * tiles * B <= 256 && N >= 4L * k;
+    p.bf = extras && !p.split && C % 64 == 0 && knn_append_lds_bytes(C, 8, 384, 2, 32, true) <= 160 * 1024;
+  } else {
+    p.path = KNN_INSERTION;
+  }
+  long at = 0;
+  auto part = [&](long words) {
+    const long o = at;
+    at += (words + 63) / 64 * 64;
+    return o;
+  };
+  p.norms = part((long)B * N);
+  p.tile_flags = part(p.path == KNN_STREAMED_SMALL ? B * tiles : 0);
+  p.xcm = part(p.path != KNN_INSERTION && !x_cm ? (long)B * C * r3d_cm_pitch(N) : 0);
+  p.pieces = part(p.bf ? (long)B * N * C : 0);  // two bf16 pieces per coordinate (C % 64 == 0)
+  p.mean = part(p.bf ? (long)B * C : 0);
+  p.cnorm = part(p.bf ? (long)B * N : 0);
+  p.split_idx = part(p.split ? 2L * B * N * k : 0);
+  p.split_sc = part(p.split ? 2L * B * N * k : 0);
+  p.words = at;
+  return p;
+}
+
+extern "C" long r3d_knn_ws_words(int B, int N, int C, int k, int flags) {
+  return knn_plan(B, N, C, k, flags & 1, flags & 2, true).words;
+}
+
+// one call's operands and scratch, as the kernels take them (xT: the streamed kernels' channel-major operand)
+struct KnnCall {
+  const float* x; long ldx; const float* xT; long ldT;
+  int B, N, C, k, mode; const int* n_dev; int n_stride; int32_t* idx; float* sc; hipStream_t st;
+  float *norms; int* tile_flags; float* cm; unsigned short* pieces; float *mean, *cnorm; int* split_idx; float* split_sc;
+};
+
+// launch one configuration of the append-and-rank kernel (raising its dynamic-LDS limit once per instantiation);
+// nsplit = grid.z
+template <int WAVES, int CAP, int TOP, int KCH, int SAMPLE, bool FULLC, bool BFA = false, bool BFB = false>
+static int knn_append_launch(const KnnCall& c, dim3 grid, int* status, int* tile_flags) {
+  const size_t lds = knn_append_lds_bytes(c.C, WAVES, CAP, TOP, KCH, BFA);
+  auto go = [&](auto smode) {
+    constexpr int SM = decltype(smode)::value;
+    static size_t attr = 0;
+    if (lds > attr) {
+      hipError_t e = hipFuncSetAttribute((const void*)r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SM, BFA, BFB>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      R3D_REQUIRE(e == hipSuccess, "r3d_knn_topk: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
+      attr = lds;
+    }
+    hipLaunchKernelGGL((r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SM, BFA, BFB>), grid, dim3(64 * WAVES), lds,
+                       c.st, c.xT, c.ldT, c.N, c.C, c.k, SM, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, status, tile_flags,
+                       (int)grid.z, c.split_idx, c.split_sc, BFA ? c.pieces : nullptr, BFA ? c.cnorm : nullptr,
+                       BFB ? c.x : nullptr, c.ldx);
+    return R3D_OK;
+  };
+  return c.mode == R3D_SCORE_DGCNN ? go(std::integral_constant<int, R3D_SCORE_DGCNN>())
+                                   : go(std::integral_constant<int, R3D_SCORE_L2>());
+}
+
+// launch the sorted-insertion kernel
+template <int R>
+static void knn_insertion_launch(const KnnCall& c, size_t lds) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)r3d_knn_topk_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(r3d_knn_topk_kernel<R>, dim3(r3d_cdiv(c.N, KNN_Q), c.B), dim3(256), lds, c.st, c.x, c.ldx, c.N, c.C,
+                     c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc);
+}
+
+// the streamed kernels' channel-major operand (x_cm as given, or a copy of x into c.cm) and its squared norms
+static int knn_cm_operand(KnnCall& c, const float* x_cm) {
+  c.xT = x_cm;
+  c.ldT = c.N;
+  if (!x_cm) {
+    R3D_REQUIRE(c.cm && c.x, "r3d_knn_topk: need x_cm or (x and cm_ws)");
+    c.ldT = r3d_cm_pitch(c.N);
+    int rc = r3d_pm_to_cm_pitched(c.x, c.ldx, c.B, c.C, c.N, c.cm, c.ldT, c.st);
+    if (rc) return rc;
+    c.xT = c.cm;
+  }
+  hipLaunchKernelGGL(r3d_sqnorm_cm_kernel, dim3(r3d_cdiv(c.N, 256), c.B), dim3(256), 0, c.st, c.xT, c.ldT, c.C, c.N, c.norms);
+  return R3D_OK;
+}
+
+// the bf16 pieces, their set means and centred squared norms, from the point-major rows (C % 64 == 0)
+static void knn_pack_bf(const KnnCall& c) {
+  const long rows = (long)c.B * c.N;
+  hipLaunchKernelGGL(r3d_knn_mean_kernel, dim3(c.C / 64, c.B), dim3(1024), 0, c.st, c.x, c.ldx, c.N, c.C, c.n_dev, c.n_stride,
+                     c.C, c.mean);
+  hipLaunchKernelGGL(r3d_knn_pack_bf_kernel, dim3(r3d_cdiv(rows * (c.C / 8), 256)), dim3(256), 0, c.st, c.x, c.ldx, rows, c.N,
+                     c.C, c.C, c.mean, c.pieces);
+  hipLaunchKernelGGL(r3d_knn_cnorm_kernel, dim3(r3d_cdiv(rows, 16)), dim3(256), 0, c.st, c.x, c.ldx, rows, c.N, c.C, c.C,
+                     c.mean, c.cnorm);
+}
+
+// scratch: ws (r3d_knn_topk_batched: split lists and bf16 pieces allowed) or else r3d_knn_topk's norm_ws and cm_ws
+static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
+                         const int* n_valid_dev, int n_valid_stride, float* ws, long ws_words, float* norm_ws, float* cm_ws,
+                         int32_t* idx_out, float* score_out, int32_t* status, void* stream) {
+  R3D_REQUIRE((x || x_cm) && (ws || norm_ws) && idx_out, "r3d_knn_topk: null pointer");
+  R3D_REQUIRE(B > 0 && N > 0 && C > 0 && (!x || ldx >= C), "r3d_knn_topk: bad shape B=%d N=%d C=%d ldx=%ld", B, N, C, ldx);
+  R3D_REQUIRE(k > 0 && k <= N && k <= 256, "r3d_knn_topk: unsupported k=%d (need 1..min(N,256))", k);
+  R3D_REQUIRE(mode == R3D_SCORE_DGCNN || mode == R3D_SCORE_L2, "r3d_knn_topk: unknown mode %d", mode);
+  const KnnPlan p = knn_plan(B, N, C, k, status, x_cm, ws);
+  KnnCall c = {x, ldx, nullptr, 0, B, N, C, k, mode, n_valid_dev, n_valid_stride, idx_out, score_out, (hipStream_t)stream};
+  if (ws) {
+    R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_words >= p.words,
+                "r3d_knn_topk_batched: ws must be 16-byte aligned and hold r3d_knn_ws_words = %ld floats (got %ld)", p.words,
+                ws_words);
+    c.norms = ws + p.norms;
+    c.tile_flags = (int*)(ws + p.tile_flags);
+    c.cm = ws + p.xcm;
+    c.pieces = (unsigned short*)(ws + p.pieces);
+    c.mean = ws + p.mean;
+    c.cnorm = ws + p.cnorm;
+    c.split_idx = (int*)(ws + p.split_idx);
+    c.split_sc = ws + p.split_sc;
+  } else {
+    c.norms = norm_ws;
+    c.tile_flags = (int*)(norm_ws + (long)B * N);  // r3d_knn_norm_ws_words reserves B ceil(N/32) words here
+    c.cm = cm_ws;
+  }
+  if (p.path == KNN_INSERTION) {
+    R3D_REQUIRE(c.x, "r3d_knn_topk: the insertion kernel needs the point-major matrix");
+    const size_t lds = knn_lds_bytes(c.C);
+    R3D_REQUIRE(lds <= 160 * 1024, "r3d_knn_topk: C=%d needs %zu B of LDS (> 160 KiB)", c.C, lds);
+    int rc = r3d_sqnorm(c.x, c.ldx, (long)c.B * c.N, c.C, c.norms, c.st);
+    if (rc) return rc;
+    if (c.k <= 64) knn_insertion_launch<1>(c, lds);
+    else if (c.k <= 128) knn_insertion_launch<2>(c, lds);
+    else knn_insertion_launch<4>(c, lds);
+    R3D_LAUNCH_CHECK("r3d_knn_topk");
+    return R3D_OK;
+  }
+  int rc = knn_cm_operand(c, x_cm);
+  if (rc) return rc;
+  const bool bfa = p.bf && g_knn_bf16_threshold && c.x;  // the pieces are cut from the point-major rows
+  const dim3 grid(r3d_cdiv(c.N, 32), c.B);
+  if (p.path == KNN_STREAMED_SMALL) {
+    // append-and-rank (mid configuration); tiles whose survivor buffer overflowed are redone by the exact
+    // two-pass kernel in the same stream -- no host round trip, never a wrong result
+    r3d_zero_words(c.tile_flags, (long)c.B * grid.x, c.st);
+    if (c.C <= 16) {
+      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
+                 : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
+    } else if (bfa) {
+      knn_pack_bf(c);
+      // the filter on the bf16 core as well: exact scores come from the point-major rows, read as 16-byte vectors; its
+      // survivor bitmap, 32 words per sub-tile, sits in the index buffer's 32 KM_CAP words.  (With the filter the threshold
+      // pass visits EVERY sub-tile: a tighter threshold means fewer survivors, and their exact scores cost more than the
+      // half pass saved -- 3.30 against 3.63 ms per 384 clouds.)
+      const bool filter = g_knn_bf16_filter && (c.ldx & 3) == 0 && ((uintptr_t)c.x & 15) == 0 && grid.x <= KM_CAP;
+      rc = filter ? knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, 1, true, true, true>(c, grid, nullptr, c.tile_flags)
+                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true, true>(c, grid, nullptr, c.tile_flags);
+    } else if (c.C % 64 == 0) {
+      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags)
+                 : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags);
+    } else {
+      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
+                 : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(c.C <= 16 ? r3d_knn_small_kernel<8> : r3d_knn_small_kernel<32>, grid, dim3(256), 0, c.st, c.xT, c.ldT, c.N,
+                       c.C, c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, (const int*)c.tile_flags);
+    R3D_LAUNCH_CHECK("r3d_knn_topk(small)");
+    return R3D_OK;
+  }
+  // large k; *status bit 0 reports survivor-buffer overflow (the caller re-runs with status == NULL, which selects the
+  // insertion kernel)
+  r3d_zero_words(status, 1, c.st);
+  const dim3 gb(grid.x, c.B, p.split ? 2 : 1);
+  if (bfa) {
+    knn_pack_bf(c);
+    rc = knn_append_launch<8, 384, 2, 32, 1, true, true>(c, gb, status, nullptr);
+  } else if (c.C % 64 == 0) {
+    rc = knn_append_launch<8, 384, 2, 32, 1, true>(c, gb, status, nullptr);
+  } else {
+    rc = knn_append_launch<8, 384, 2, 32, 1, false>(c, gb, status, nullptr);
+  }
+  if (rc) return rc;
+  if (p.split)
+    hipLaunchKernelGGL(r3d_knn_merge_kernel, dim3(r3d_cdiv((long)c.B * c.N, 4)), dim3(256), 0, c.st, c.split_idx, c.split_sc, 2,
+                       (long)c.B * c.N, c.k, c.n_dev, c.n_stride, c.N, c.idx, c.sc);
+  R3D_LAUNCH_CHECK("r3d_knn_topk(big)");
+  return R3D_OK;
+}
 
 // x: (B*N, ldx) point-major fp32; norm_ws: r3d_knn_norm_ws_words(B, N) fp32 scratch; idx_out: (B, N, k) int32;
 // score_out: optional (B, N, k) fp32; n_valid_dev: optional device int, rows >= *n are
@@ -1590,197 +1757,20 @@ extern "C" long r3d_knn_norm_ws_words(int B, int N) { return (long)B * N + (long
 // status: optional device int.  With k > 32 a non-NULL status selects the append-and-rank
 // kernel; bit 0 set afterwards = its survivor buffer overflowed and the result is unusable
 // (re-run with status == NULL for the insertion kernel).
-// floats of split_ws for r3d_knn_topk_split (two partial top-k lists per row: indices and scores)
-extern "C" long r3d_knn_split_ws_words(int B, int N, int k) { return 4L * B * N * k + 64; }
-
-static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                         const int* n_valid_dev, int n_valid_stride, float* norm_ws, float* cm_ws, int32_t* idx_out,
-                         float* score_out, int32_t* status, float* split_ws, long split_ws_words, float* bf_ws,
-                         long bf_ws_words, void* stream);
-
 extern "C" int r3d_knn_topk(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
                             const int* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out,
                             float* score_out, int32_t* status, void* stream) {
-  return knn_topk_impl(x, ldx, x_cm, B, N, C, k, mode, n_valid_dev, 0, norm_ws, cm_ws, idx_out, score_out, status, nullptr, 0,
-                       nullptr, 0, stream);
-}
-
-// r3d_knn_topk with an optional scratch for the large-k streamed kernel: when the query tiles alone cannot fill the
-// chip even when doubled (2 B ceil(N / 32) <= 256 workgroups) and split_ws holds r3d_knn_split_ws_words(B, N, k) floats, the candidate
-// axis is split over two workgroups per tile and the two sorted lists are merged by a second small kernel.
-extern "C" int r3d_knn_topk_split(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                                  const int* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out,
-                                  float* score_out, int32_t* status, float* split_ws, long split_ws_words, void* stream) {
-  return knn_topk_impl(x, ldx, x_cm, B, N, C, k, mode, n_valid_dev, 0, norm_ws, cm_ws, idx_out, score_out, status, split_ws,
-                       split_ws_words, nullptr, 0, stream);
+  return knn_topk_impl(x, ldx, x_cm, B, N, C, k, mode, n_valid_dev, 0, nullptr, 0, norm_ws, cm_ws, idx_out, score_out, status,
+                       stream);
 }
 
 // The same over a batch of B point sets with their OWN valid counts: set b has n_valid_dev[b * n_valid_stride] rows (the
 // graph nodes of B episodes' label-propagation systems, each at its capacity N).  status: ONE word for the batch (bit 0:
-// some set's survivor buffer overflowed).
-// bf_ws (optional, r3d_knn_bf_ws_words(B, N, C) floats, needs x): lets the streamed kernels run their THRESHOLD pass on
-// the bf16 matrix core (a lower bound of every score; the pass that emits neighbours and scores stays fp32, results are
-// bit-identical with and without it).
+// some set's survivor buffer overflowed).  ws: r3d_knn_ws_words(B, N, C, k, flags) floats, 16-byte aligned.
 extern "C" int r3d_knn_topk_batched(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                                    const int* n_valid_dev, int n_valid_stride, float* norm_ws, float* cm_ws,
-                                    int32_t* idx_out, float* score_out, int32_t* status, float* split_ws,
-                                    long split_ws_words, float* bf_ws, long bf_ws_words, void* stream) {
+                                    const int* n_valid_dev, int n_valid_stride, float* ws, long ws_words, int32_t* idx_out,
+                                    float* score_out, int32_t* status, void* stream) {
   R3D_REQUIRE(n_valid_stride >= 0, "r3d_knn_topk_batched: negative stride");
-  return knn_topk_impl(x, ldx, x_cm, B, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws, cm_ws, idx_out, score_out, status,
-                       split_ws, split_ws_words, bf_ws, bf_ws_words, stream);
-}
-
-static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
-                         const int* n_valid_dev, int n_valid_stride, float* norm_ws, float* cm_ws, int32_t* idx_out,
-                         float* score_out, int32_t* status, float* split_ws, long split_ws_words, float* bf_ws,
-                         long bf_ws_words, void* stream) {
-  R3D_REQUIRE((x || x_cm) && norm_ws && idx_out, "r3d_knn_topk: null pointer");
-  // the threshold pass on the bf16 core: whole 64-channel chunks, the packed pieces from the point-major matrix
-  const bool bfa = g_knn_bf16_threshold && bf_ws && x && C % 64 == 0 && bf_ws_words >= r3d_knn_bf_ws_words(B, N, C) &&
-                   ((uintptr_t)bf_ws & 15) == 0;
-  // the filter pass on it as well: exact scores come from the point-major rows, read as 16-byte vectors
-  const float* xpm = bfa && g_knn_bf16_filter && (ldx & 3) == 0 && ((uintptr_t)x & 15) == 0 ? x : nullptr;
-  float* bf_mean = bf_ws ? bf_ws + (long)B * N * C : nullptr;  // (C == Cp here)
-  float* bf_cnorm = bf_ws ? bf_mean + (long)B * C : nullptr;
-  auto pack_bf = [&]() {
-    hipStream_t s_ = (hipStream_t)stream;
-    hipLaunchKernelGGL(r3d_knn_mean_kernel, dim3(C / 64, B), dim3(1024), 0, s_, x, ldx, N, C, n_valid_dev, n_valid_stride, C, bf_mean);
-    const long chunks = (long)B * N * (C / 8);
-    hipLaunchKernelGGL(r3d_knn_pack_bf_kernel, dim3(r3d_cdiv(chunks, 256)), dim3(256), 0, s_, x, ldx, (long)B * N, N, C, C, bf_mean,
-                       (unsigned short*)bf_ws);
-    hipLaunchKernelGGL(r3d_knn_cnorm_kernel, dim3(r3d_cdiv((long)B * N, 16)), dim3(256), 0, s_, x, ldx, (long)B * N, N, C, C, bf_mean,
-                       bf_cnorm);
-  };
-  R3D_REQUIRE(B > 0 && N > 0 && C > 0 && (!x || ldx >= C), "r3d_knn_topk: bad shape B=%d N=%d C=%d ldx=%ld", B, N, C, ldx);
-  R3D_REQUIRE(k > 0 && k <= N && k <= 256, "r3d_knn_topk: unsupported k=%d (need 1..min(N,256))", k);
-  R3D_REQUIRE(mode == R3D_SCORE_DGCNN || mode == R3D_SCORE_L2, "r3d_knn_topk: unknown mode %d", mode);
-  hipStream_t st = (hipStream_t)stream;
-  if (k <= 32 && C <= 64) {
-    const float* xT = x_cm;
-    long ldT = N;
-    if (!xT) {
-      R3D_REQUIRE(cm_ws && x, "r3d_knn_topk: need x_cm or (x and cm_ws)");
-      ldT = r3d_cm_pitch(N);
-      int rc = r3d_pm_to_cm_pitched(x, ldx, B, C, N, cm_ws, ldT, stream);
-      if (rc) return rc;
-      xT = cm_ws;
-    }
-    hipLaunchKernelGGL(r3d_sqnorm_cm_kernel, dim3(r3d_cdiv(N, 256), B), dim3(256), 0, st, xT, ldT, C, N, norm_ws);
-    dim3 g2(r3d_cdiv(N, 32), B);
-    static const bool two_pass_only = getenv("R3D_KNN_TWO_PASS") != nullptr;  // A/B switch for tools/knnbench
-    int* tile_flags = (int*)(norm_ws + (long)B * N);  // r3d_knn_norm_ws_words reserves B * ceil(N/32) words here
-    if (two_pass_only) {
-      if (C <= 16)
-        hipLaunchKernelGGL(r3d_knn_small_kernel<8>, g2, dim3(256), 0, st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws,
-                           idx_out, score_out, (const int*)nullptr);
-      else
-        hipLaunchKernelGGL(r3d_knn_small_kernel<32>, g2, dim3(256), 0, st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws,
-                           idx_out, score_out, (const int*)nullptr);
-    } else {
-      // append-and-rank (mid configuration); tiles whose survivor buffer overflowed are redone by the exact
-      // sorted-insertion kernel in the same stream -- no host round trip, never a wrong result
-      r3d_zero_words(tile_flags, (long)B * g2.x, st);
-      // fewer row tiles than CUs (the 2 query clouds of a training episode: 128 tiles): 8 waves per tile instead of 4,
-      // each wave's chain of sub-tiles is half as long
-      const bool few = (long)g2.x * B <= 256;
-      const size_t lds = knn_append_lds_bytes(C, few ? 8 : KM_WAVES, KM_CAP, KM_TOP, C <= 16 ? 8 : 32);
-      int rc;
-#define KM_LAUNCH(WAVES, KCH, FULLC)                                                                                       \
-  knn_append_launch<WAVES, KM_CAP, KM_TOP, KCH, KM_SAMPLE, FULLC>(g2, lds, st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws, \
-                                                                  idx_out, score_out, nullptr, tile_flags)
-      if (C <= 16) {
-        rc = few ? KM_LAUNCH(8, 8, false) : KM_LAUNCH(KM_WAVES, 8, false);
-        if (rc) return rc;
-        hipLaunchKernelGGL(r3d_knn_small_kernel<8>, g2, dim3(256), 0, st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws,
-                           idx_out, score_out, (const int*)tile_flags);
-      } else {
-        if (C % 64 == 0 && bfa && !few) {
-          pack_bf();
-          // (with the filter on the bf16 core the threshold pass visits EVERY sub-tile: a tighter threshold means fewer
-          // survivors, and their exact scores cost more than the half pass saved -- 3.30 against 3.63 ms per 384 clouds)
-          // (the filter's survivor bitmap, 32 words per sub-tile, sits in the index buffer's 32 KM_CAP words)
-          const float* xpm_f = (r3d_cdiv(N, 32) <= KM_CAP) ? xpm : nullptr;
-          rc = xpm_f ? knn_append_launch_bfa<KM_WAVES, KM_CAP, KM_TOP, 1>(
-                         g2, knn_append_lds_bytes(C, KM_WAVES, KM_CAP, KM_TOP, 32, true), st, xT, ldT, N, C, k, mode, n_valid_dev,
-                         n_valid_stride, norm_ws, idx_out, score_out, nullptr, tile_flags, (const unsigned short*)bf_ws, bf_cnorm, xpm_f, ldx)
-                   : knn_append_launch_bfa<KM_WAVES, KM_CAP, KM_TOP, KM_SAMPLE>(
-                         g2, knn_append_lds_bytes(C, KM_WAVES, KM_CAP, KM_TOP, 32, true), st, xT, ldT, N, C, k, mode, n_valid_dev,
-                         n_valid_stride, norm_ws, idx_out, score_out, nullptr, tile_flags, (const unsigned short*)bf_ws, bf_cnorm, nullptr, 0);
-        } else if (C % 64 == 0) rc = few ? KM_LAUNCH(8, 32, true) : KM_LAUNCH(KM_WAVES, 32, true);
-        else rc = few ? KM_LAUNCH(8, 32, false) : KM_LAUNCH(KM_WAVES, 32, false);
-        if (rc) return rc;
-        hipLaunchKernelGGL(r3d_knn_small_kernel<32>, g2, dim3(256), 0, st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride, norm_ws,
-                           idx_out, score_out, (const int*)tile_flags);
-      }
-#undef KM_LAUNCH
-    }
-    R3D_LAUNCH_CHECK("r3d_knn_topk(small)");
-    return R3D_OK;
-  }
-  if (status && k <= 256 && knn_big_lds_bytes(C) <= 160 * 1024) {
-    // fast path for large k; *status bit 0 reports survivor-buffer overflow (caller re-runs with
-    // status == NULL, which selects the insertion kernel below)
-    const float* xT = x_cm;
-    long ldT = N;
-    if (!xT) {
-      R3D_REQUIRE(cm_ws && x, "r3d_knn_topk: need x_cm or (x and cm_ws)");
-      ldT = r3d_cm_pitch(N);
-      int rc = r3d_pm_to_cm_pitched(x, ldx, B, C, N, cm_ws, ldT, stream);
-      if (rc) return rc;
-      xT = cm_ws;
-    }
-    hipLaunchKernelGGL(r3d_sqnorm_cm_kernel, dim3(r3d_cdiv(N, 256), B), dim3(256), 0, st, xT, ldT, C, N, norm_ws);
-    r3d_zero_words(status, 1, st);
-    {
-      const int tiles = r3d_cdiv(N, 32);
-      // two workgroups per query tile when BOTH halves of every tile still fit the chip in one round (the kernel's
-      // 123 KB of LDS admit one workgroup per CU: at workload S, 138 tiles -> 276 workgroups ran as two rounds, 489 us
-      // against 412 us unsplit) and every half still holds >= 2 k candidates
-      const bool split = split_ws && 2L * tiles * B <= 256 && N >= 4 * k && split_ws_words >= r3d_knn_split_ws_words(B, N, k);
-      const int nsplit = split ? 2 : 1;
-      const dim3 gb(tiles, B, nsplit);
-      int* idx_tmp = (int*)split_ws;
-      float* sc_tmp = split_ws ? split_ws + 2L * B * N * k : nullptr;
-      const bool bfa_big = bfa && nsplit == 1 && knn_big_lds_bytes(C, true) <= 160 * 1024;
-      if (bfa_big) pack_bf();
-      const int rc = bfa_big
-                         ? knn_append_launch_bfa<8, 384, 2, 1>(gb, knn_big_lds_bytes(C, true), st, xT, ldT, N, C, k, mode, n_valid_dev,
-                                                               n_valid_stride, norm_ws, idx_out, score_out, status, nullptr,
-                                                               (const unsigned short*)bf_ws, bf_cnorm, g_knn_bf16_filter > 1 ? xpm : nullptr, ldx)
-                     : C % 64 == 0
-                         ? knn_append_launch<8, 384, 2, 32, 1, true>(gb, knn_big_lds_bytes(C), st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride,
-                                                                     norm_ws, idx_out, score_out, status, nullptr, nsplit, idx_tmp, sc_tmp)
-                         : knn_append_launch<8, 384, 2, 32, 1, false>(gb, knn_big_lds_bytes(C), st, xT, ldT, N, C, k, mode, n_valid_dev, n_valid_stride,
-                                                                      norm_ws, idx_out, score_out, status, nullptr, nsplit, idx_tmp, sc_tmp);
-      if (rc) return rc;
-      if (split)
-        hipLaunchKernelGGL(r3d_knn_merge_kernel, dim3(r3d_cdiv((long)B * N, 4)), dim3(256), 0, st, idx_tmp, sc_tmp, 2,
-                           (long)B * N, k, n_valid_dev, n_valid_stride, N, idx_out, score_out);
-    }
-    R3D_LAUNCH_CHECK("r3d_knn_topk(big)");
-    return R3D_OK;
-  }
-  R3D_REQUIRE(x, "r3d_knn_topk: the insertion kernel needs the point-major matrix");
-  const size_t lds = knn_lds_bytes(C);
-  R3D_REQUIRE(lds <= 160 * 1024, "r3d_knn_topk: C=%d needs %zu B of LDS (> 160 KiB)", C, lds);
-  int rc = r3d_sqnorm(x, ldx, (long)B * N, C, norm_ws, stream);
-  if (rc) return rc;
-  dim3 grid(r3d_cdiv(N, KNN_Q), B), block(256);
-#define KNN_LAUNCH(RR)                                                                           \
-  do {                                                                                           \
-    static bool attr_set = false;                                                                \
-    if (!attr_set) {                                                                             \
-      hipFuncSetAttribute((const void*)r3d_knn_topk_kernel<RR>,                                  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
-      attr_set = true;                                                                           \
-    }                                                                                            \
-    hipLaunchKernelGGL(r3d_knn_topk_kernel<RR>, grid, block, lds, st, x, ldx, N, C, k, mode,     \
-                       n_valid_dev, n_valid_stride, norm_ws, idx_out, score_out);                \
-  } while (0)
-  if (k <= 64) KNN_LAUNCH(1);
-  else if (k <= 128) KNN_LAUNCH(2);
-  else KNN_LAUNCH(4);
-#undef KNN_LAUNCH
-  R3D_LAUNCH_CHECK("r3d_knn_topk");
-  return R3D_OK;
+  return knn_topk_impl(x, ldx, x_cm, B, N, C, k, mode, n_valid_dev, n_valid_stride, ws, ws_words, nullptr, nullptr, idx_out,
+                       score_out, status, stream);
 }

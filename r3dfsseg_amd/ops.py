@@ -183,41 +183,25 @@ def copy_cols(src, dst):
 def knn(x_pm, B, N, k, mode=SCORE_DGCNN, n_valid=None, return_scores=False, x_cm=None, status=None, n_valid_stride=0):
     """x_pm (B*N, C) -> idx (B, N, k) int32, best first.  x_cm: optional (B, C, N) channel-major
     copy of the same points (saves the internal transpose of the streamed k <= 32 kernel).
-    n_valid (device int32) with n_valid_stride > 0: set b has n_valid[b * n_valid_stride] valid rows."""
+    n_valid (device int32) with n_valid_stride > 0: set b has n_valid[b * n_valid_stride] valid rows.
+    status (device int32, k > 32): selects the large-k streamed kernel; bit 0 set afterwards = overflow, redo with None."""
     M, ld = _rows(x_pm)
     C = x_pm.shape[1]
     assert M == B * N
+    if x_cm is not None:
+        assert x_cm.is_contiguous() and x_cm.shape == (B, C, N) and x_cm.dtype == torch.float32
+    if status is not None:
+        assert status.dtype == torch.int32
+    lib = _lib.load()
     dev = x_pm.device
-    norm = torch.empty(_lib.load().r3d_knn_norm_ws_words(B, N), device=dev, dtype=torch.float32)
+    # one scratch; the library decides which kernels run and what they need in it
+    words = lib.r3d_knn_ws_words(B, N, C, k, (status is not None) | (x_cm is not None) << 1)
+    ws = torch.empty(words, device=dev, dtype=torch.float32)
     idx = torch.empty(B, N, k, device=dev, dtype=torch.int32)
     sc = torch.empty(B, N, k, device=dev, dtype=torch.float32) if return_scores else None
-    cm_ws = None
-    if k <= 32 and C <= 64:
-        if x_cm is None:
-            cm_ws = torch.empty(B * C * _lib.load().r3d_cm_pitch(N), device=dev, dtype=torch.float32)
-        else:
-            assert x_cm.is_contiguous() and x_cm.shape == (B, C, N) and x_cm.dtype == torch.float32
-    elif status is not None:  # large-k streamed kernel (status bit 0 = overflow -> redo with status=None)
-        assert status.dtype == torch.int32
-        if x_cm is None:
-            cm_ws = torch.empty(B * C * _lib.load().r3d_cm_pitch(N), device=dev, dtype=torch.float32)
-    else:
-        x_cm = None
-    lib = _lib.load()
-    split_ws, split_words = None, 0
-    if k > 32 and status is not None and 2 * B * ((N + 31) // 32) <= 256:  # the large-k kernel may split the candidate axis
-        split_words = lib.r3d_knn_split_ws_words(B, N, k)
-        split_ws = torch.empty(split_words, device=dev, dtype=torch.float32)
-    # scratch for the bf16 pieces of the points: the streamed kernels' threshold pass then runs on the bf16 matrix core
-    # (a lower bound is all it needs; neighbours and scores come from the fp32 pass: same bits either way)
-    bf_ws, bf_words = None, 0
-    if C % 64 == 0 and (k <= 32 or status is not None):
-        bf_words = lib.r3d_knn_bf_ws_words(B, N, C)
-        bf_ws = torch.empty(bf_words, device=dev, dtype=torch.float32)
     with _timed("knn_topk_l2" if mode == SCORE_L2 else "knn_topk"):
-        _lib.check(lib.r3d_knn_topk_batched(_p(x_pm), ld, _p(x_cm), B, N, C, k, mode, _p(n_valid), n_valid_stride, _p(norm),
-                                            _p(cm_ws), _p(idx), _p(sc), _p(status), _p(split_ws), split_words, _p(bf_ws),
-                                            bf_words, _st()))
+        _lib.check(lib.r3d_knn_topk_batched(_p(x_pm), ld, _p(x_cm), B, N, C, k, mode, _p(n_valid), n_valid_stride, _p(ws), words,
+                                            _p(idx), _p(sc), _p(status), _st()))
     return (idx, sc) if return_scores else idx
 
 

@@ -11,7 +11,7 @@ import torch
 from r3dfsseg_amd import _lib, synthetic as S
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_of_abi_5_exports_every_declared_symbol():
     from r3dfsseg_amd import build
     path = build.build()
     assert os.path.exists(path)
@@ -22,24 +22,25 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert set(_lib._SIGS) == set(declared), set(_lib._SIGS) ^ set(declared)
     lib.r3d_abi_version.restype = ctypes.c_int
-    assert lib.r3d_abi_version() == 4
+    assert lib.r3d_abi_version() == 5
     lib.r3d_head_desc_words.restype = ctypes.c_int
     assert lib.r3d_head_desc_words() == 32
     lib.r3d_lp_ws_words.restype = ctypes.c_long
     assert lib.r3d_lp_ws_words(4396, 201) > 0
 
 
-def test_loading_a_library_of_another_abi_version_is_refused(monkeypatch):
-    """A stale libr3d_hip.so would be called with this package's argument lists (round 4 added arguments to two entry
-    points): load() compares r3d_abi_version() with the version the bindings were written for and says how to rebuild."""
+def test_loading_a_library_of_another_abi_version_than_5_is_refused(monkeypatch):
+    """A stale libr3d_hip.so would be called with this package's argument lists (ABI 5 replaced the four scratch buffers of
+    r3d_knn_topk_batched with one workspace): load() compares r3d_abi_version() with the version the bindings were written
+    for and says how to rebuild."""
     from r3dfsseg_amd import build
     build.build()
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="C ABI version 4.*rebuild"):
+    with pytest.raises(RuntimeError, match="C ABI version 5.*rebuild"):
         _lib.load()
-    monkeypatch.setattr(_lib, "ABI_VERSION", 4)
-    assert _lib.load().r3d_abi_version() == 4
+    monkeypatch.setattr(_lib, "ABI_VERSION", 5)
+    assert _lib.load().r3d_abi_version() == 5
 
 
 def test_binding_signatures_match_the_header():
