@@ -345,6 +345,16 @@ int r3d_attention_bwd_ep(const float* qkv, long ld, int B, int N, const float* O
                          const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, float q_scale,
                          float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
 
+/* the _ep calls at head width D in {32, 64, 96, 128} (the reference's --output_dim; D = 64 is the calls above): qkv holds
+ * q / sqrt(D) | k | v at columns 0 | D | 2D (ld >= 3D), out / O / dO D columns, dqkv (ldd >= 3D).  Any other D is refused
+ * (R3D_ERR_ARG) before a launch; r3d_attention_ws_words_ep_d returns -1 for it. */
+long r3d_attention_ws_words_ep_d(int B, int N, int seed_group, int D);
+int r3d_attention_fwd_train_ep_d(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
+                                 unsigned seed, const unsigned* seed_dev, int seed_group, int D, float* ws, void* stream);
+int r3d_attention_bwd_ep_d(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
+                           const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, int D,
+                           float q_scale, float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
+
 /* head backward (reference: autograd through models/mpti.py:488-512,571).  r3d_ce_grad -> G = dL/dZ (scaled by the
  * device scalar *gscale); r3d_label_propagate_bwd: adjoint CG solve on the graph r3d_label_propagate left in ws,
  * then gradients w.r.t. the node features; r3d_head_prototypes_bwd: cluster-mean / query-row backward. */

@@ -103,6 +103,10 @@ _SIGS = {
     "r3d_attention_ws_words_ep": (c_l, [c_i, c_i, c_i]),
     "r3d_attention_fwd_train_ep": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_f, c_f]),
     "r3d_attention_bwd_ep": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_fl, c_f, c_l, c_f, c_i, c_f]),
+    "r3d_attention_ws_words_ep_d": (c_l, [c_i, c_i, c_i, c_i]),
+    "r3d_attention_fwd_train_ep_d": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_i, c_f, c_f]),
+    "r3d_attention_bwd_ep_d": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_i, c_fl, c_f, c_l, c_f, c_i,
+                                     c_f]),
     "r3d_head_prototypes_batched": (c_i, [c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_l, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i,
                                           c_f, c_l, c_l, c_f, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l, c_l, c_i, c_f]),
     "r3d_head_prototypes_bwd_batched": (c_i, [c_i, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l,

@@ -162,15 +162,32 @@ class DGCNN(nn.Module):
         return outs[0], out
 
 
+# head widths the attention kernels are built for (csrc/attention.hip: a template over D)
+ATTENTION_WIDTHS = (32, 64, 96, 128)
+# the transductive heads carry node features of at most 256 channels, a multiple of 4 (csrc/head_graph.hip, head_proto.hip)
+FEAT_DIM_MAX = 256
+
+
+def check_output_dim(output_dim, use_attention, feat_dim):
+    """Raises NotImplementedError, naming what is supported, for an --output_dim the kernels are not built for."""
+    if use_attention and output_dim not in ATTENTION_WIDTHS:
+        raise NotImplementedError("output_dim = %d: the attention kernels are built for output_dim in %s"
+                                  % (output_dim, ATTENTION_WIDTHS))
+    if output_dim <= 0 or output_dim % 4 or feat_dim > FEAT_DIM_MAX:
+        raise NotImplementedError("output_dim = %d: the linear mapper needs output_dim %% 4 == 0 and a feature width "
+                                  "64 + output_dim + base_widths[-1] = %d <= %d" % (output_dim, feat_dim, FEAT_DIM_MAX))
+
+
 class SelfAttention(nn.Module):
-    """Single-head point self-attention (attention.py:10-48)."""
+    """Single-head point self-attention (attention.py:10-48), head width out_channel in ATTENTION_WIDTHS."""
 
     def __init__(self, in_channel, out_channel=None, attn_dropout=0.1):
         super().__init__()
         self.in_channel = in_channel
         self.out_channel = out_channel if out_channel is not None else in_channel
-        if self.out_channel != 64:
-            raise NotImplementedError("the attention kernel is built for out_channel = 64")
+        if self.out_channel not in ATTENTION_WIDTHS:
+            raise NotImplementedError("the attention kernels are built for out_channel in %s, not %d"
+                                      % (ATTENTION_WIDTHS, self.out_channel))
         self.temperature = self.out_channel ** 0.5
         self.q_map = nn.Conv1d(in_channel, self.out_channel, 1, bias=False)
         self.k_map = nn.Conv1d(in_channel, self.out_channel, 1, bias=False)
@@ -185,7 +202,9 @@ class SelfAttention(nn.Module):
         with torch.no_grad():
             W = torch.cat([m.weight.reshape(self.out_channel, -1) for m in (self.q_map, self.k_map, self.v_map)], 0).contiguous()
             scale = torch.ones(3 * self.out_channel, device=W.device)
-            scale[: self.out_channel] = 1.0 / self.temperature  # q / sqrt(d), exact for d = 64
+            # q / sqrt(d) as q * fp32(1 / sqrt(d)) in the GEMM epilogue: exact for d = 64, within an ulp of the
+            # reference's division at 32, 96, 128
+            scale[: self.out_channel] = 1.0 / self.temperature
             f = _refresh(self._folded[1] if self._folded is not None else None, (W, scale))
         self._folded = (key, f)
         return self._folded[1]
@@ -201,7 +220,7 @@ class SelfAttention(nn.Module):
 
     def forward(self, x):
         B, _, N = x.shape
-        out = torch.empty(B * N, 64, device=x.device, dtype=torch.float32)
+        out = torch.empty(B * N, self.out_channel, device=x.device, dtype=torch.float32)
         self.forward_pm(ops.cm_to_pm(x), B, N, out)
         return ops.pm_to_cm(out, B, N)
 

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .dgcnn import DGCNN, BaseLearner, SelfAttention
+from .dgcnn import DGCNN, BaseLearner, SelfAttention, check_output_dim
 
 
 class EpisodeSlot:
@@ -41,15 +41,16 @@ class MPTI_SelfAtten(nn.Module):
         if self.n_classes > 8:
             raise NotImplementedError("the head kernels carry at most 8 classes (n_way <= 7): two planes of 4 label columns")
 
+        self.output_dim = args.output_dim
+        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
+        check_output_dim(self.output_dim, self.use_attention, self.feat_dim)
+
         self.encoder = DGCNN(args.edgeconv_widths, args.dgcnn_mlp_widths, args.pc_in_dim, k=args.dgcnn_k)
         self.base_learner = BaseLearner(args.dgcnn_mlp_widths[-1], args.base_widths)
         if self.use_attention:
             self.att_learner = SelfAttention(args.dgcnn_mlp_widths[-1], args.output_dim)
         else:
-            if args.output_dim != 64:
-                raise NotImplementedError("output_dim must be 64")
             self.linear_mapper = nn.Conv1d(args.dgcnn_mlp_widths[-1], args.output_dim, 1, bias=False)
-        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
         self.shot_seed = getattr(args, "shot_seed", 1)
         self.proj = nn.Linear(self.feat_dim, 128)
         # solver knobs of the sparse label propagation (no reference counterpart: the reference
@@ -84,15 +85,15 @@ class MPTI_SelfAtten(nn.Module):
             self._trace.setdefault("idx", []).append(self.encoder.trace)
             self._trace.setdefault("cat", []).append(cat)
             self.encoder.trace = None
-        d1 = 64
+        d1, od = 64, self.output_dim
         feat = torch.empty(B * N, self.feat_dim, device=x_pm.device, dtype=torch.float32)
         ops.copy_cols(cat[:, :d1], feat[:, :d1])
         if self.use_attention:
-            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + 64], group=group)
+            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od], group=group)
         else:
-            W = self.linear_mapper.weight.reshape(64, -1).contiguous()
-            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + 64])
-        self.base_learner.forward_pm(level2, feat[:, d1 + 64:])
+            W = self.linear_mapper.weight.reshape(od, -1).contiguous()
+            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
+        self.base_learner.forward_pm(level2, feat[:, d1 + od:])
         return feat
 
     def getFeatures(self, x):

@@ -235,17 +235,22 @@ def edgeconv(PQ, idx, W2, s2, t2, out, B, N, want_argmax=False):
 
 
 def attention(qkv, B, N, out, want_lse=False, group=0):
-    """Inference attention of B clouds.  group > 0: the clouds are a batch of episodes of `group` clouds each; the
-    key-axis split (and with it every output bit) is then the one of a single episode."""
+    """Inference attention of B clouds, head width D = out.shape[1] (qkv: q | k | v, 3 D columns).  group > 0: the clouds
+    are a batch of episodes of `group` clouds each; the key-axis split (and with it every output bit) is then the one of a
+    single episode."""
     M, ld = _rows(qkv)
     M2, ldo = _rows(out)
-    assert M == B * N and M2 == M and qkv.shape[1] == 192 and out.shape[1] == 64
+    D = out.shape[1]
+    assert M == B * N and M2 == M and qkv.shape[1] == 3 * D
     lib = _lib.load()
     lse = torch.empty(M, device=qkv.device, dtype=torch.float32)
-    ws = torch.empty(lib.r3d_attention_ws_words_ep(B, N, group), device=qkv.device, dtype=torch.float32)
+    words = lib.r3d_attention_ws_words_ep_d(B, N, group, D)
+    if words < 0:
+        raise NotImplementedError("attention head width %d: the kernels are built for 32, 64, 96, 128" % D)
+    ws = torch.empty(words, device=qkv.device, dtype=torch.float32)
     with _timed("attention"):
-        _lib.check(lib.r3d_attention_fwd_train_ep(_p(qkv), ld, B, N, _p(out), ldo, _p(lse), 0.0, ctypes.c_uint(0), None, group,
-                                                  _p(ws), _st()))
+        _lib.check(lib.r3d_attention_fwd_train_ep_d(_p(qkv), ld, B, N, _p(out), ldo, _p(lse), 0.0, ctypes.c_uint(0), None,
+                                                    group, D, _p(ws), _st()))
     return lse if want_lse else None
 
 

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .dgcnn import DGCNN, BaseLearner, SelfAttention
+from .dgcnn import DGCNN, BaseLearner, SelfAttention, check_output_dim
 
 
 class ProtoNet(nn.Module):
@@ -19,26 +19,29 @@ class ProtoNet(nn.Module):
         self.use_attention = args.use_attention
         if self.n_way > 7:
             raise NotImplementedError("n_way <= 7 (the head kernels carry at most 8 classes)")
+        self.output_dim = args.output_dim
+        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
+        check_output_dim(self.output_dim, self.use_attention, self.feat_dim)
         self.encoder = DGCNN(args.edgeconv_widths, args.dgcnn_mlp_widths, args.pc_in_dim, k=args.dgcnn_k)
         self.base_learner = BaseLearner(args.dgcnn_mlp_widths[-1], args.base_widths)
         if self.use_attention:
             self.att_learner = SelfAttention(args.dgcnn_mlp_widths[-1], args.output_dim)
         else:
             self.linear_mapper = nn.Conv1d(args.dgcnn_mlp_widths[-1], args.output_dim, 1, bias=False)
-        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
 
     def getFeatures_pm(self, x):
         B, _, N = x.shape
         x_pm, x_cm = ops.input_layouts(x)
         cat, level2 = self.encoder.forward_pm(x_pm, B, N, x_cm=x_cm)
         feat = torch.empty(B * N, self.feat_dim, device=x.device, dtype=torch.float32)
-        ops.copy_cols(cat[:, :64], feat[:, :64])
+        d1, od = 64, self.output_dim
+        ops.copy_cols(cat[:, :d1], feat[:, :d1])
         if self.use_attention:
-            self.att_learner.forward_pm(level2, B, N, feat[:, 64:128])
+            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od])
         else:
-            W = self.linear_mapper.weight.reshape(64, -1).contiguous()
-            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, 64:128])
-        self.base_learner.forward_pm(level2, feat[:, 128:])
+            W = self.linear_mapper.weight.reshape(od, -1).contiguous()
+            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
+        self.base_learner.forward_pm(level2, feat[:, d1 + od:])
         return feat
 
     def getFeatures(self, x):

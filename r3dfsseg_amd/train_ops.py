@@ -322,7 +322,8 @@ def edgeconv_train_bwd(saved, dout, B, N, dx_acc):
 
 # ----------------------------------------------------------------------------- encoder
 class EncoderTrainFn(torch.autograd.Function):
-    """getFeatures in training mode.  forward(x (B,C_in,N), model, seed, *params) -> feat (B*N, 192).
+    """getFeatures in training mode.  forward(x (B,C_in,N), model, seed, *params) -> feat (B*N, feat_dim):
+    [level1 (64) | attention (output_dim) | base].  Training needs the attention (model.att_learner).
 
     ``ctx.seg`` (ops.SegLayout, set by the caller before forward; default: the B clouds are one getFeatures call) says
     which clouds are which episode's support / query call.  The two getFeatures calls of every episode of the batch
@@ -359,23 +360,24 @@ class EncoderTrainFn(torch.autograd.Function):
             mlp_saved.append(sv)
         level2 = h
         feat = torch.empty(M, model.feat_dim, device=dev, dtype=torch.float32)
+        od = att.out_channel  # head width: feat columns [64, 64 + od), qkv (M, 3 od)
         ops.copy_cols(cat[:, :64], feat[:, :64])
         hb, base_saved = level2, []
         for i, seq in enumerate(base.convs):
             last = i == base.num_convs - 1
             W = seq[0].weight
             hb, sv = conv_bn_fwd(hb, W.reshape(W.shape[0], -1).contiguous(), seq[1], ops.ACT_NONE if last else ops.ACT_RELU,
-                                 bias=seq[0].bias, out=feat[:, 128:] if last else None, seg=seg)
+                                 bias=seq[0].bias, out=feat[:, 64 + od:] if last else None, seg=seg)
             base_saved.append(sv)
         Wqkv, qscale = att._fold()
         qkv = ops.pointwise_conv(level2, Wqkv, qscale, None, ops.ACT_NONE)
         lse = torch.empty(M, device=dev, dtype=torch.float32)
         p_drop = float(att.dropout.p)
-        aws = _f(lib.r3d_attention_ws_words_ep(B, N, seg.clouds), dev)
+        aws = _f(lib.r3d_attention_ws_words_ep_d(B, N, seg.clouds, od), dev)
         with _timed("attention"):
-            _lib.check(lib.r3d_attention_fwd_train_ep(_p(qkv), 192, B, N, _p(feat[:, 64:128]), feat.stride(0), _p(lse), p_drop,
-                                                      ctypes.c_uint(seed & 0xffffffff), _p(model._slot.seed_dev), seg.clouds,
-                                                      _p(aws), _st()))
+            _lib.check(lib.r3d_attention_fwd_train_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0), _p(lse),
+                                                        p_drop, ctypes.c_uint(seed & 0xffffffff), _p(model._slot.seed_dev),
+                                                        seg.clouds, od, _p(aws), _st()))
         ctx.model, ctx.dims, ctx.seed_dev, ctx.seg = model, (B, N, seed, p_drop), model._slot.seed_dev, seg
         model._dbg_idx = [sv[1] for sv in ec_saved]  # neighbour lists of this pass (parity tests inject them into the oracle)
         if getattr(model, "_trace", None) is not None:  # one entry per getFeatures call
@@ -403,8 +405,9 @@ class EncoderTrainFn(torch.autograd.Function):
                 dict.__setitem__(self, id(k), v)
         g = _G()
         dlevel2 = torch.zeros(M, level2.shape[1], device=dev, dtype=torch.float32)
+        od = att.out_channel
         # --- BaseLearner (mpti.py:35-40)
-        d = dfeat[:, 128:]
+        d = dfeat[:, 64 + od:]
         for i in reversed(range(base.num_convs)):
             seq = base.convs[i]
             dW, dg, db, dbias, dX = conv_bn_bwd(base_saved[i], d, want_dx=True, dx_acc=dlevel2 if i == 0 else None)
@@ -413,16 +416,16 @@ class EncoderTrainFn(torch.autograd.Function):
             g[seq[1].weight], g[seq[1].bias] = dg, db
             d = dX
         # --- SelfAttention (attention.py:39-46)
-        dqkv = torch.empty(M, 192, device=dev, dtype=torch.float32)
+        dqkv = torch.empty(M, 3 * od, device=dev, dtype=torch.float32)
         with _timed("attention_bwd"):  # the forward's workspace, kept since: its packed q | k | v pieces are reused
-            _lib.check(lib.r3d_attention_bwd_ep(_p(qkv), 192, B, N, _p(feat[:, 64:128]), feat.stride(0), _p(dfeat[:, 64:128]),
-                                                dfeat.stride(0), _p(lse), p_drop, ctypes.c_uint(seed & 0xffffffff),
-                                                _p(ctx.seed_dev), seg.clouds, 1.0 / att.temperature, _p(dqkv), 192, _p(aws), 1,
-                                                _st()))
+            _lib.check(lib.r3d_attention_bwd_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0),
+                                                  _p(dfeat[:, 64:64 + od]), dfeat.stride(0), _p(lse), p_drop,
+                                                  ctypes.c_uint(seed & 0xffffffff), _p(ctx.seed_dev), seg.clouds, od,
+                                                  1.0 / att.temperature, _p(dqkv), 3 * od, _p(aws), 1, _st()))
         dWqkv = gemm_tn(dqkv, level2)
         for k, m in enumerate((att.q_map, att.k_map, att.v_map)):
-            g[m.weight] = dWqkv[64 * k:64 * (k + 1)].reshape(m.weight.shape)
-        Wraw = torch.cat([m.weight.reshape(64, -1) for m in (att.q_map, att.k_map, att.v_map)], 0)
+            g[m.weight] = dWqkv[od * k:od * (k + 1)].reshape(m.weight.shape)
+        Wraw = torch.cat([m.weight.reshape(od, -1) for m in (att.q_map, att.k_map, att.v_map)], 0)
         conv_acc(dqkv, Wraw.t().contiguous(), dlevel2)
         # --- point MLP (dgcnn.py:121-122)
         dcat = torch.zeros(M, cat.shape[1], device=dev, dtype=torch.float32)
@@ -451,7 +454,7 @@ def encoder_params(model):
 
 
 def get_features_train(model, x, seed, seg=None):
-    """feat (B*N, 192) with gradient edges to the encoder / base / attention parameters.  `seg` (ops.SegLayout with
+    """feat (B*N, feat_dim) with gradient edges to the encoder / base / attention parameters.  `seg` (ops.SegLayout with
     E = 1, Q > 0): x holds the support clouds followed by the query clouds of an episode and the two getFeatures
     results are returned (see EncoderTrainFn)."""
     params = encoder_params(model)
