@@ -14,21 +14,25 @@ BASELINE.json configs[4]'s 256-episode batch over 8 GPUs; each episode is config
                           launches, one episode at a time (the reference's schedule).
 Episodes are independent: ranks take disjoint episodes (weak scaling); the only collective is
 the 1.5 MB gradient all-reduce of train mode.  ONE JSON line on rank 0.
+A plain run does only what the headline needs: set-up, the W warm-up and K timed steps (in train mode with the
+conditioning steps of --steady-steps between them), --dump-outputs, the JSON line.  --full adds every other leg after
+the headline: the single-episode and eval legs, the roofline leg and the CPU baseline (the fields marked [full] below).
   value        -- STEADY STATE: K timed steps after --steady-steps optimiser steps from the synthetic initial weights
                   (the label-propagation systems get harder as the encoder separates the classes: CG iterations
                   roughly double within 150 steps; the reference trains 40 000 episodes, mpti_train_noise.py:182).
                   `fresh_weights` is the same measurement over the first K steps after W warm-up steps.
-  roofline     -- the kernel with the most device time in a live batched step, timed with HIP events on the launch
+  roofline     -- [full] the kernel with the most device time in a live batched step, timed with HIP events on the launch
                   stream (one event pair per entry-point call; batched launches do not overlap) and priced with its
                   ALGORITHMIC work.  When that entry point is the label propagation, the CG
                   iteration (its two kernels, all systems of the batch per launch) is measured on its own.
-  rooflines    -- every entry point of the batched step against both ceilings, same timing
-  cpu_baseline -- the CPU oracle (a port of the reference path) on this box's host cores: EVAL FORWARD (1 warm-up,
+  rooflines    -- [full] every entry point of the batched step against both ceilings, same timing (also
+                  roofline_cg_iteration, entry_point_ms_per_step, step_fp32_equiv_tflops)
+  cpu_baseline -- [full] the CPU oracle (a port of the reference path) on this box's host cores: EVAL FORWARD (1 warm-up,
                   min / median of 5) to be compared with eval_forward_episodes_per_sec, and a TRAIN STEP (forward,
                   backward through the dense inverse, Adam; 1 warm-up, median of 3) to be compared with
                   single_episode_eager_step_episodes_per_sec (same schedule) or `value`
-Extra fields: single_episode_eager_step_episodes_per_sec (E = 1, eager: the reference's own schedule),
-single_episode_graph_step_episodes_per_sec (the same as one captured hipGraph) and eval_forward_episodes_per_sec.
+[full] extra fields of train mode: single_episode_eager_step_episodes_per_sec (E = 1, eager: the reference's own
+schedule), single_episode_graph_step_episodes_per_sec (the same as one captured hipGraph) and eval_forward_episodes_per_sec.
   --dump-outputs DIR -- after the headline's timed steps, what its LAST step handed its caller, as DIR/<name>.npy (rank 0;
                   float32, float64 for integers and float64 results; at most 64 MB, larger arrays as a fixed seeded sample):
                   train: per-episode loss / lp_loss / contrast_loss / logits / metrics and the model state after the
@@ -190,8 +194,10 @@ def main():
     ap.add_argument("--batch", type=int, default=None,
                     help="episodes per launch sequence (default: all of the rank's episodes; 0 = one episode at a time, eager)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-episode and eval legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the single-episode and eval legs, the roofline leg and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the single-episode and eval legs (profiling runs)")
     ap.add_argument("--no-batch-graph", action="store_true",
                     help="launch the batched training step eagerly instead of replaying its captured hipGraph (A/B; same results)")
     ap.add_argument("--roofline-kernel", default="auto", help="entry point to price (auto = the one taking most time)")
@@ -350,7 +356,7 @@ def main():
             elapsed, cg = el_f, cg_f
         dumped = headline_outputs(model, trainer, last_eval, train) if args.dump_outputs else None
         E = Eeff
-        if batched and not args.no_extras:
+        if args.full and batched and not args.no_extras:
             n_e = max(args.steps, 16)
             el1, _ = timed(train_step_eager, n_e, 3)
             extra["single_episode_eager_step_episodes_per_sec"] = n_e * world / el1
@@ -383,24 +389,25 @@ def main():
         dumped = headline_outputs(model, trainer, last_eval, train) if args.dump_outputs else None
     cg_mean, cg_max = cg
 
-    # roofline leg: ONE more step of the headline kind with a HIP event pair (torch's current stream = the launch stream)
-    # around every entry-point call; batched launches run one after the other, so the pairs do not overlap
-    step_fn = (train_step if batched else train_step_eager) if train else (eval_step if batched else eval_step_eager)
-    n_roof = 2
-    timer = ops.KernelTimer(OPS, repeat=0)
-    ops.set_timer(timer)
-    if trainer is not None:
-        graph_mode, trainer.batch_graph = trainer.batch_graph, False  # the event pairs sit around eager entry-point calls
-        ops.set_timer(None)
-        step_fn(0)  # (the eager launch path's first step after the graph replays: allocations, lazily set attributes)
+    if args.full:
+        # roofline leg: ONE more step of the headline kind with a HIP event pair (torch's current stream = the launch stream)
+        # around every entry-point call; batched launches run one after the other, so the pairs do not overlap
+        step_fn = (train_step if batched else train_step_eager) if train else (eval_step if batched else eval_step_eager)
+        n_roof = 2
+        timer = ops.KernelTimer(OPS, repeat=0)
         ops.set_timer(timer)
-    for i in range(n_roof):
-        step_fn(i)
-    if trainer is not None:
-        trainer.batch_graph = graph_mode
-    ops.set_timer(None)
-    timer.close()
-    ksum_all = timer.summary()
+        if trainer is not None:
+            graph_mode, trainer.batch_graph = trainer.batch_graph, False  # the event pairs sit around eager entry-point calls
+            ops.set_timer(None)
+            step_fn(0)  # (the eager launch path's first step after the graph replays: allocations, lazily set attributes)
+            ops.set_timer(timer)
+        for i in range(n_roof):
+            step_fn(i)
+        if trainer is not None:
+            trainer.batch_graph = graph_mode
+        ops.set_timer(None)
+        timer.close()
+        ksum_all = timer.summary()
 
     n_invalid = torch.tensor([float(len(invalid))], device=dev)
     if dist is not None:
@@ -412,146 +419,147 @@ def main():
 
     N = cfg["pc_npts"]
     B = cfg["n_way"] * cfg["k_shot"] + cfg["n_way"] * cfg.get("n_queries", 1)
-    hb = model._head[1]
-    n_nodes = int(hb.desc.view(-1, 32)[0, ops.HD_N_NODES].item())
-    per_step_ms = {k: v["total_ms"] / n_roof for k, v in ksum_all.items() if v["launches"]}
-    calls_per_step = {k: v["launches"] / n_roof for k, v in ksum_all.items() if v["launches"]}
-    mode_name = "train" if train else "eval"
-    prof, prof_name = committed_profile(args.workload, mode_name)
-    pmc, pmc_name = committed_traffic(args.workload, mode_name)
-    kern = args.roofline_kernel
-    if kern == "auto":  # the entry point with the most device time in the live step above
-        kern = max(per_step_ms, key=per_step_ms.get)
-    roof = None
-    cg_roof = None
-    if True:
-        # The label propagation is graph build + CG; its dominant kernels are the two of one CG iteration, which serve
-        # every system of the batch.  Their time is measured live: the same solves with 8 and with 40 forced iterations
-        # (tol = 0), HIP events on the launch stream, difference / 32.
-        nbr = ops.knn_nodes(hb)
+    if args.full:  # the roofline leg's report and the CPU baseline
+        hb = model._head[1]
+        n_nodes = int(hb.desc.view(-1, 32)[0, ops.HD_N_NODES].item())
+        per_step_ms = {k: v["total_ms"] / n_roof for k, v in ksum_all.items() if v["launches"]}
+        calls_per_step = {k: v["launches"] / n_roof for k, v in ksum_all.items() if v["launches"]}
+        mode_name = "train" if train else "eval"
+        prof, prof_name = committed_profile(args.workload, mode_name)
+        pmc, pmc_name = committed_traffic(args.workload, mode_name)
+        kern = args.roofline_kernel
+        if kern == "auto":  # the entry point with the most device time in the live step above
+            kern = max(per_step_ms, key=per_step_ms.get)
+        roof = None
+        cg_roof = None
+        if True:
+            # The label propagation is graph build + CG; its dominant kernels are the two of one CG iteration, which serve
+            # every system of the batch.  Their time is measured live: the same solves with 8 and with 40 forced iterations
+            # (tol = 0), HIP events on the launch stream, difference / 32.
+            nbr = ops.knn_nodes(hb)
 
-        def solve_ms(iters, reps=4):
-            ops.label_propagate(hb, nbr, model.sigma, 0.99, iters, 0.0)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
+            def solve_ms(iters, reps=4):
                 ops.label_propagate(hb, nbr, model.sigma, 0.99, iters, 0.0)
-            b.record()
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / reps
-        t_iter = (solve_ms(40) - solve_ms(8)) / 32.0 * 1e-3
-        nnz = sum(int(hb.csr(e)[1][-1].item()) for e in range(hb.E))
-        nodes_tot = int(hb.desc.view(-1, 32)[:, ops.HD_N_NODES].sum().item())
-        by = cg_iteration_bytes(nnz, nodes_tot)
-        fl = nnz * 2.0 * 4 + nodes_tot * 4 * (12.0 + 4 * CG_M)
-        # (batches of >= 8 systems run the LDS-resident SpMV, smaller ones the row-per-wave form: same bits)
-        cg_names = ("r3d_cg_spmv_lds_kernel" if hb.E * ((hb.n_cap + 127) // 128) >= 256 else "r3d_cg_spmv_kernel",
-                    "r3d_cg_update_kernel")
-        traffic = rocprof_us = None
-        if pmc is not None and all(k in pmc for k in cg_names):
-            traffic = 1024.0 * sum(FETCH_SIZE_WIDE_READ_FACTOR * pmc[k]["fetch_kb_per_launch"] + pmc[k]["write_kb_per_launch"]
-                                   for k in cg_names)
-        if prof is not None:
-            us = [v[2] for k, v in prof.items() if k.split("(")[0] in cg_names]
-            rocprof_us = sum(us) if len(us) == 2 else None
-        cg_roof = dict(kernel="%s + %s (one iteration of the two-level CG of the label propagation, %d systems per launch, "
-                           "graphs of the weights at the time of measurement: hub rows grow with training; entry points "
-                           "label_propagate / label_propagate_bwd)" % (cg_names + (hb.E,)),
-                    bound="hbm", achieved=by / t_iter / 1e9, peak=HBM_PEAK_GBS, unit="GB/s", frac=by / t_iter / 1e9 / HBM_PEAK_GBS,
-                    traffic=traffic, avg_launch_ms=t_iter * 1e3, algorithmic_mb_per_launch=by / 1e6,
-                    algorithmic_gflop_per_launch=fl / 1e9, csr_nnz=nnz, nodes=nodes_tot, systems_per_launch=hb.E,
-                    iterations_per_episode=cg_mean * (2 if train else 1), rocprofv3_kernel_us=rocprof_us,
-                    frac_kernel_time_only=(by / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rocprof_us else None,
-                    rocprofv3_summary=prof_name, pmc_summary=pmc_name,
-                    note=("avg_launch_ms is event-measured over back-to-back launches (pair of kernels); rocprofv3_kernel_us is "
-                          "the pair's in-kernel time from the committed --kernel-trace summary of this workload (null when none "
-                          "is committed); traffic = %.0f x FETCH_SIZE + WRITE_SIZE of the pair from the committed PMC passes "
-                          "(the guide's gfx950 correction for wide coalesced reads)" % FETCH_SIZE_WIDE_READ_FACTOR))
-    if kern in ("label_propagate", "label_propagate_bwd"):
-        roof = cg_roof
-    if roof is None:
-        fl, by, bound, launches = algorithmic_work(kern, cfg, n_nodes, cg_mean, train)
-        fl, by = fl * E, by * E                       # the step's work of this entry point
-        calls = calls_per_step[kern]
-        t_launch = per_step_ms[kern] * 1e-3 / calls
-        bx3_now = _lib_arith() == 1 and kern in BX3_OPS
-        if bound == "mfma":
-            # bf16 x 3 entry points: fp32-EQUIVALENT flops against the fp32-equivalent matrix peak of that arithmetic
-            # (six bf16 MFMA products per fp32 product: dense bf16 peak / 6)
-            ach, peak, unit = fl / calls / t_launch / 1e12, (BF16_MFMA_PEAK_TF / 6.0 if bx3_now else F32_MFMA_PEAK_TF), "TFLOP/s"
-        else:
-            ach, peak, unit = by / calls / t_launch / 1e9, HBM_PEAK_GBS, "GB/s"
-        traffic = rocprof_us = rocprof_ms_step = frac_kernel = None
-        main = MAIN_KERNEL.get(kern, kern)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    ops.label_propagate(hb, nbr, model.sigma, 0.99, iters, 0.0)
+                b.record()
+                torch.cuda.synchronize()
+                return a.elapsed_time(b) / reps
+            t_iter = (solve_ms(40) - solve_ms(8)) / 32.0 * 1e-3
+            nnz = sum(int(hb.csr(e)[1][-1].item()) for e in range(hb.E))
+            nodes_tot = int(hb.desc.view(-1, 32)[:, ops.HD_N_NODES].sum().item())
+            by = cg_iteration_bytes(nnz, nodes_tot)
+            fl = nnz * 2.0 * 4 + nodes_tot * 4 * (12.0 + 4 * CG_M)
+            # (batches of >= 8 systems run the LDS-resident SpMV, smaller ones the row-per-wave form: same bits)
+            cg_names = ("r3d_cg_spmv_lds_kernel" if hb.E * ((hb.n_cap + 127) // 128) >= 256 else "r3d_cg_spmv_kernel",
+                        "r3d_cg_update_kernel")
+            traffic = rocprof_us = None
+            if pmc is not None and all(k in pmc for k in cg_names):
+                traffic = 1024.0 * sum(FETCH_SIZE_WIDE_READ_FACTOR * pmc[k]["fetch_kb_per_launch"] + pmc[k]["write_kb_per_launch"]
+                                       for k in cg_names)
+            if prof is not None:
+                us = [v[2] for k, v in prof.items() if k.split("(")[0] in cg_names]
+                rocprof_us = sum(us) if len(us) == 2 else None
+            cg_roof = dict(kernel="%s + %s (one iteration of the two-level CG of the label propagation, %d systems per launch, "
+                               "graphs of the weights at the time of measurement: hub rows grow with training; entry points "
+                               "label_propagate / label_propagate_bwd)" % (cg_names + (hb.E,)),
+                        bound="hbm", achieved=by / t_iter / 1e9, peak=HBM_PEAK_GBS, unit="GB/s", frac=by / t_iter / 1e9 / HBM_PEAK_GBS,
+                        traffic=traffic, avg_launch_ms=t_iter * 1e3, algorithmic_mb_per_launch=by / 1e6,
+                        algorithmic_gflop_per_launch=fl / 1e9, csr_nnz=nnz, nodes=nodes_tot, systems_per_launch=hb.E,
+                        iterations_per_episode=cg_mean * (2 if train else 1), rocprofv3_kernel_us=rocprof_us,
+                        frac_kernel_time_only=(by / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rocprof_us else None,
+                        rocprofv3_summary=prof_name, pmc_summary=pmc_name,
+                        note=("avg_launch_ms is event-measured over back-to-back launches (pair of kernels); rocprofv3_kernel_us is "
+                              "the pair's in-kernel time from the committed --kernel-trace summary of this workload (null when none "
+                              "is committed); traffic = %.0f x FETCH_SIZE + WRITE_SIZE of the pair from the committed PMC passes "
+                              "(the guide's gfx950 correction for wide coalesced reads)" % FETCH_SIZE_WIDE_READ_FACTOR))
+        if kern in ("label_propagate", "label_propagate_bwd"):
+            roof = cg_roof
+        if roof is None:
+            fl, by, bound, launches = algorithmic_work(kern, cfg, n_nodes, cg_mean, train)
+            fl, by = fl * E, by * E                       # the step's work of this entry point
+            calls = calls_per_step[kern]
+            t_launch = per_step_ms[kern] * 1e-3 / calls
+            bx3_now = _lib_arith() == 1 and kern in BX3_OPS
+            if bound == "mfma":
+                # bf16 x 3 entry points: fp32-EQUIVALENT flops against the fp32-equivalent matrix peak of that arithmetic
+                # (six bf16 MFMA products per fp32 product: dense bf16 peak / 6)
+                ach, peak, unit = fl / calls / t_launch / 1e12, (BF16_MFMA_PEAK_TF / 6.0 if bx3_now else F32_MFMA_PEAK_TF), "TFLOP/s"
+            else:
+                ach, peak, unit = by / calls / t_launch / 1e9, HBM_PEAK_GBS, "GB/s"
+            traffic = rocprof_us = rocprof_ms_step = frac_kernel = None
+            main = MAIN_KERNEL.get(kern, kern)
 
-        def base(name):  # "void r3d_x_kernel<5>(float const*, ..." -> "r3d_x_kernel"
-            return name.split("(")[0].split("<")[0].replace("void ", "").strip()
-        # the two kNN entry points run instances of ONE kernel template: told apart by their template arguments
-        by_template = {"knn_topk": ("r3d_knn_append_kernel<4, 128, 1,",), "knn_topk_l2": ("r3d_knn_append_kernel<8, 384, 2,",)}
+            def base(name):  # "void r3d_x_kernel<5>(float const*, ..." -> "r3d_x_kernel"
+                return name.split("(")[0].split("<")[0].replace("void ", "").strip()
+            # the two kNN entry points run instances of ONE kernel template: told apart by their template arguments
+            by_template = {"knn_topk": ("r3d_knn_append_kernel<4, 128, 1,",), "knn_topk_l2": ("r3d_knn_append_kernel<8, 384, 2,",)}
 
-        def mine(name):
-            if kern in by_template:
-                return name.replace("void ", "").startswith(by_template[kern])
-            return bool(base(name)) and base(name) in main
-        if pmc is not None:
-            hit = [v for k, v in pmc.items() if mine(k)]
-            if hit:  # the SUM over the named kernels (one launch of each per call of the entry point)
-                traffic = 1024.0 * sum(FETCH_SIZE_WIDE_READ_FACTOR * v["fetch_kb_per_launch"] + v["write_kb_per_launch"] for v in hit)
-        if prof is not None:
-            hits = [v for k, v in prof.items() if k != "_steps" and mine(k)]
-            if hits:
-                rocprof_us = max(v[2] for v in hits)  # average duration of the entry point's longest kernel
-                if prof.get("_steps"):
-                    # the entry point's main kernels in the committed kernel trace of the same workload and schedule: their
-                    # time per step, and the roofline fraction from kernel time alone (no helper kernels, no launch gaps)
-                    rocprof_ms_step = sum(v[1] for v in hits) / prof["_steps"]
-                    frac_kernel = (fl / (rocprof_ms_step * 1e-3) / 1e12 / peak) if bound == "mfma" else \
-                        (by / (rocprof_ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS)
-        useful = None
-        if kern + "_useful" in ("edgeconv_bwd_useful",):  # flops the math needs (recompute excluded) over the same time
-            fu = algorithmic_work(kern + "_useful", cfg, n_nodes, cg_mean, train)[0] * E
-            useful = fu / calls / t_launch / 1e12 / peak
-        roof = dict(kernel="%s (entry point %s, %d episodes per launch)" % (main, kern, E), bound=bound, achieved=ach, peak=peak,
-                    unit=unit, frac=ach / peak, useful_frac=useful if useful is not None else ach / peak,
-                    peak_note=("fp32-equivalent peak of the bf16 x 3 arithmetic: 2500 TFLOP/s dense bf16 / 6 products per fp32 "
-                               "product" if (bound == "mfma" and bx3_now) else None), traffic=traffic, avg_launch_ms=t_launch * 1e3, launches_per_step=calls,
-                    algorithmic_gflop_per_launch=fl / calls / 1e9, algorithmic_mb_per_launch=by / calls / 1e6,
-                    hbm_gbs=by / calls / t_launch / 1e9, fp32_tflops=fl / calls / t_launch / 1e12,
-                    rocprofv3_kernel_us=rocprof_us, rocprofv3_main_kernels_ms_per_step=rocprof_ms_step,
-                    event_ms_per_step=per_step_ms[kern], frac_kernel_time_only=frac_kernel,
-                    rocprofv3_summary=prof_name, pmc_summary=pmc_name,
-                    note="one HIP event pair per entry-point call on the launch stream (launches of the batched step do not "
-                         "overlap; the pair includes the entry point's small helper kernels); traffic = %.0f x FETCH_SIZE + "
-                         "WRITE_SIZE of the main kernel from the committed PMC passes" % FETCH_SIZE_WIDE_READ_FACTOR)
-    # every entry point against both ceilings (north_star: HBM GB/s for kNN / EdgeConv, MFMA utilisation for attention)
-    from r3dfsseg_amd import _lib as _l0
-    bx3_attention = _l0.load().r3d_get_matrix_arith() == 1
-    rooflines = {"_note": "HIP event pairs around every entry-point call of a live step (%d episodes per launch): hbm_gbs is "
-                          "algorithmic bytes / device time, not HBM traffic" % E}
-    for op, ms in per_step_ms.items():
-        f_, b_, bnd, _ = algorithmic_work(op, cfg, n_nodes, cg_mean, train)
-        f_, b_ = f_ * E, b_ * E
-        sec = ms * 1e-3
-        rooflines[op] = dict(bound=bnd, ms_per_step=round(ms, 4), calls_per_step=calls_per_step[op],
-                             hbm_gbs=round(b_ / sec / 1e9, 1), frac_hbm=round(b_ / sec / 1e9 / HBM_PEAK_GBS, 4),
-                             fp32_tflops=round(f_ / sec / 1e12, 2), frac_mfma=round(f_ / sec / 1e12 / F32_MFMA_PEAK_TF, 4))
-        if op in BX3_OPS and bx3_attention:
-            # six bf16 MFMA products per fp32 product: the matrix-core work actually issued, against the dense bf16 peak
-            rooflines[op].update(matrix_arith="bf16 x 3", bf16_tflops_issued=round(6 * f_ / sec / 1e12, 1),
-                                 frac_mfma=round(6 * f_ / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
-                                 frac_mfma_note="issued bf16 MFMA flops (6 per fp32 product) / 2500 TFLOP/s dense bf16 peak; "
-                                                "fp32_tflops is the useful fp32-equivalent rate")
-    breakdown = {k: round(v, 4) for k, v in sorted(per_step_ms.items(), key=lambda kv: -kv[1])}
-    # the whole step: useful fp32-equivalent flops of every matrix-shaped entry point (recomputes excluded) over the step time
-    step_flops = 0.0
-    for op in per_step_ms:
-        f_u = algorithmic_work(op + "_useful" if op == "edgeconv_bwd" else op, cfg, n_nodes, cg_mean, train)
-        if f_u[2] == "mfma":
-            step_flops += f_u[0] * E
+            def mine(name):
+                if kern in by_template:
+                    return name.replace("void ", "").startswith(by_template[kern])
+                return bool(base(name)) and base(name) in main
+            if pmc is not None:
+                hit = [v for k, v in pmc.items() if mine(k)]
+                if hit:  # the SUM over the named kernels (one launch of each per call of the entry point)
+                    traffic = 1024.0 * sum(FETCH_SIZE_WIDE_READ_FACTOR * v["fetch_kb_per_launch"] + v["write_kb_per_launch"] for v in hit)
+            if prof is not None:
+                hits = [v for k, v in prof.items() if k != "_steps" and mine(k)]
+                if hits:
+                    rocprof_us = max(v[2] for v in hits)  # average duration of the entry point's longest kernel
+                    if prof.get("_steps"):
+                        # the entry point's main kernels in the committed kernel trace of the same workload and schedule: their
+                        # time per step, and the roofline fraction from kernel time alone (no helper kernels, no launch gaps)
+                        rocprof_ms_step = sum(v[1] for v in hits) / prof["_steps"]
+                        frac_kernel = (fl / (rocprof_ms_step * 1e-3) / 1e12 / peak) if bound == "mfma" else \
+                            (by / (rocprof_ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS)
+            useful = None
+            if kern + "_useful" in ("edgeconv_bwd_useful",):  # flops the math needs (recompute excluded) over the same time
+                fu = algorithmic_work(kern + "_useful", cfg, n_nodes, cg_mean, train)[0] * E
+                useful = fu / calls / t_launch / 1e12 / peak
+            roof = dict(kernel="%s (entry point %s, %d episodes per launch)" % (main, kern, E), bound=bound, achieved=ach, peak=peak,
+                        unit=unit, frac=ach / peak, useful_frac=useful if useful is not None else ach / peak,
+                        peak_note=("fp32-equivalent peak of the bf16 x 3 arithmetic: 2500 TFLOP/s dense bf16 / 6 products per fp32 "
+                                   "product" if (bound == "mfma" and bx3_now) else None), traffic=traffic, avg_launch_ms=t_launch * 1e3, launches_per_step=calls,
+                        algorithmic_gflop_per_launch=fl / calls / 1e9, algorithmic_mb_per_launch=by / calls / 1e6,
+                        hbm_gbs=by / calls / t_launch / 1e9, fp32_tflops=fl / calls / t_launch / 1e12,
+                        rocprofv3_kernel_us=rocprof_us, rocprofv3_main_kernels_ms_per_step=rocprof_ms_step,
+                        event_ms_per_step=per_step_ms[kern], frac_kernel_time_only=frac_kernel,
+                        rocprofv3_summary=prof_name, pmc_summary=pmc_name,
+                        note="one HIP event pair per entry-point call on the launch stream (launches of the batched step do not "
+                             "overlap; the pair includes the entry point's small helper kernels); traffic = %.0f x FETCH_SIZE + "
+                             "WRITE_SIZE of the main kernel from the committed PMC passes" % FETCH_SIZE_WIDE_READ_FACTOR)
+        # every entry point against both ceilings (north_star: HBM GB/s for kNN / EdgeConv, MFMA utilisation for attention)
+        from r3dfsseg_amd import _lib as _l0
+        bx3_attention = _l0.load().r3d_get_matrix_arith() == 1
+        rooflines = {"_note": "HIP event pairs around every entry-point call of a live step (%d episodes per launch): hbm_gbs is "
+                              "algorithmic bytes / device time, not HBM traffic" % E}
+        for op, ms in per_step_ms.items():
+            f_, b_, bnd, _ = algorithmic_work(op, cfg, n_nodes, cg_mean, train)
+            f_, b_ = f_ * E, b_ * E
+            sec = ms * 1e-3
+            rooflines[op] = dict(bound=bnd, ms_per_step=round(ms, 4), calls_per_step=calls_per_step[op],
+                                 hbm_gbs=round(b_ / sec / 1e9, 1), frac_hbm=round(b_ / sec / 1e9 / HBM_PEAK_GBS, 4),
+                                 fp32_tflops=round(f_ / sec / 1e12, 2), frac_mfma=round(f_ / sec / 1e12 / F32_MFMA_PEAK_TF, 4))
+            if op in BX3_OPS and bx3_attention:
+                # six bf16 MFMA products per fp32 product: the matrix-core work actually issued, against the dense bf16 peak
+                rooflines[op].update(matrix_arith="bf16 x 3", bf16_tflops_issued=round(6 * f_ / sec / 1e12, 1),
+                                     frac_mfma=round(6 * f_ / sec / 1e12 / BF16_MFMA_PEAK_TF, 4),
+                                     frac_mfma_note="issued bf16 MFMA flops (6 per fp32 product) / 2500 TFLOP/s dense bf16 peak; "
+                                                    "fp32_tflops is the useful fp32-equivalent rate")
+        breakdown = {k: round(v, 4) for k, v in sorted(per_step_ms.items(), key=lambda kv: -kv[1])}
+        # the whole step: useful fp32-equivalent flops of every matrix-shaped entry point (recomputes excluded) over the step time
+        step_flops = 0.0
+        for op in per_step_ms:
+            f_u = algorithmic_work(op + "_useful" if op == "edgeconv_bwd" else op, cfg, n_nodes, cg_mean, train)
+            if f_u[2] == "mfma":
+                step_flops += f_u[0] * E
 
-    cpu = None
-    if not args.no_cpu_baseline and world == 1:
-        cpu = cpu_baseline(S, cfg, args.workload, extra, train, batched)
+        cpu = None
+        if not args.no_cpu_baseline and world == 1:
+            cpu = cpu_baseline(S, cfg, args.workload, extra, train, batched)
 
     eps = args.steps * E * world / elapsed
     from r3dfsseg_amd import _lib as _l
@@ -579,14 +587,15 @@ def main():
             "optimiser_steps_before_timing": (steps_done - args.steps) if train else 0,
             "launch": ("one captured hipGraph per step (batched.BatchGraph: the batch's ~450 launches frozen; same kernels, "
                        "bit-identical results)" if (train and batched and trainer.batch_graph) else "eager launches")},
-        "valid": int(n_invalid.item()) == 0, "invalid": invalid,
-        "roofline": roof, "roofline_cg_iteration": cg_roof, "rooflines": rooflines, "cpu_baseline": cpu,
-        "entry_point_ms_per_step": breakdown,
-        "step_fp32_equiv_tflops": step_flops / (elapsed / args.steps) / 1e12,
+        "valid": int(n_invalid.item()) == 0, "invalid": invalid, "full": args.full,
         "rccl_world_size": (dist.get_world_size() if dist is not None else 1),
         "lp_cg_iterations": {"mean": cg_mean, "max": cg_max},
         "train_steps_redone": {"count": getattr(trainer, "n_redone", 0) if trainer is not None else 0, "notes": redone_notes},
     }
+    if args.full:
+        out.update({"roofline": roof, "roofline_cg_iteration": cg_roof, "rooflines": rooflines, "cpu_baseline": cpu,
+                    "entry_point_ms_per_step": breakdown,
+                    "step_fp32_equiv_tflops": step_flops / (elapsed / args.steps) / 1e12})
     out.update(extra)
     if dumped is not None:
         dump_outputs(args.dump_outputs, dumped)
