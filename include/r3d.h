@@ -426,6 +426,25 @@ int r3d_protonet_head(const float* sfeat, long ldf, const float* qfeat, long ldq
                       int n_way, int k_shot, int N, int n_query_pts, int method, float scaler, float* Z, float* ws,
                       void* stream);
 
+/* ---- ProtoNet head in training mode (reference: models/protonet.py:295-349 and autograd through it; the loop
+ * models/proto_learner.py:55-67 intends) ------------------------------------------------
+ * n_ep episodes per call: episode e's support / query rows start e * feat_ep_rows rows behind sfeat / qfeat, its masks are
+ * entry e of support_y (n_ep, S, N).  Z / dZ: (n_ep * n_query_pts, 4), episode after episode; more than 3 ways: two planes
+ * (2, n_ep * n_query_pts, 4), classes 4..7 in plane 1 (r3d_query_logits_ce_batched / r3d_ce_grad_batched with z_ep_rows =
+ * n_cap = n_query_pts).  The forward splits the rows of a support cloud over workgroups (its Z agrees with
+ * r3d_protonet_head's to rounding, not bit for bit) and leaves pooled means, per-shot counts, prototypes and their norms
+ * in ws; the backward needs ws as the forward left it and the same shape arguments.  It WRITES dsfeat (S*N rows) and
+ * dqfeat (n_query_pts rows) of every episode, e * dfeat_ep_rows rows further on for episode e: both may point into one
+ * gradient matrix over [support rows | query rows].  Every reduction is deterministic (no floating-point atomics).
+ * 1 <= n_way <= 7, D <= 256; ws: r3d_protonet_head_train_ws_words(...) floats (-1: unsupported shape), 16-byte aligned. */
+long r3d_protonet_head_train_ws_words(int n_ep, int n_way, int k_shot, int N, int n_query_pts, int D);
+int r3d_protonet_head_train_fwd(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows, int D,
+                                const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts, int method,
+                                float scaler, float* Z, float* ws, long ws_words, void* stream);
+int r3d_protonet_head_bwd(int n_ep, const float* qfeat, long ldq, long feat_ep_rows, int D, const int32_t* support_y, int n_way,
+                          int k_shot, int N, int n_query_pts, int method, float scaler, const float* dZ, float* dsfeat,
+                          long ldds, float* dqfeat, long lddq, long dfeat_ep_rows, float* ws, long ws_words, void* stream);
+
 /* ---- mIoU accumulator (eval_noise.py:23-72): hist (3, n_classes) uint64 = GT | predicted | TP */
 int r3d_miou_accumulate(const int32_t* pred, const int64_t* gt, long n, const int32_t* lut, int n_lut, int n_classes,
                         uint64_t* hist, void* stream);

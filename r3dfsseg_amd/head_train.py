@@ -94,13 +94,7 @@ def mpti_train_forward(model, support_x, support_y, query_x, query_y, gt_support
     query_acc_original, clean_ratio_LP_avg, clean_ratio_original_avg."""
     from . import contrast
     S, N = model.n_way * model.k_shot, model.n_points
-    slot = model._slot
-    if slot.seed_dev is not None:  # captured launch sequence: the seed advances in device memory
-        slot.seed_dev.add_(2)
-        seed = 0
-    else:
-        model._drop_seed = getattr(model, "_drop_seed", 0) + 2
-        seed = model._drop_seed
+    seed = T.next_dropout_seed(model)  # (captured launch sequence: the seed advances in device memory)
     sx = support_x.reshape(S, model.in_channels, N)
     # two getFeatures calls, each with its own BatchNorm batch statistics (mpti.py:434,436), through one launch sequence
     # over the S + Q clouds

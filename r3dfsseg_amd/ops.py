@@ -441,6 +441,56 @@ def protonet_head(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scale
     return Z
 
 
+_PROTO_METHODS = {"cosine": 0, "euclidean": 1}
+
+
+def _proto_method(method):
+    if method not in _PROTO_METHODS:
+        raise NotImplementedError('Error! Distance computation method (%s) is unknown!' % method)
+    return _PROTO_METHODS[method]
+
+
+def protonet_head_train(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0, n_ep=1, feat_ep_rows=0,
+                        n_query_pts=None):
+    """Training forward of the ProtoNet head -> (Z, ws): the similarity rows of protonet_head (n_ep > 1: (n_ep * n_query_pts, 4)
+    per plane, episode after episode) and the scratch protonet_head_bwd needs.  sfeat_pm / qfeat_pm: the support / query rows
+    of episode 0 (views into ONE feature matrix in which episode e's rows start feat_ep_rows rows further on)."""
+    _, ldf = _rows(sfeat_pm)
+    Mq, ldq = _rows(qfeat_pm)
+    n_pts = Mq if n_query_pts is None else n_query_pts
+    code = _proto_method(method)
+    D = sfeat_pm.shape[1]
+    sy = support_y.reshape(n_ep * n_way * k_shot, N).to(torch.int32).contiguous()
+    dev = sfeat_pm.device
+    lib = _lib.load()
+    words = lib.r3d_protonet_head_train_ws_words(n_ep, n_way, k_shot, N, n_pts, D)
+    if words < 0:
+        raise NotImplementedError("ProtoNet head: 1 <= n_way <= 7 and feature width <= 256 (n_way=%d, D=%d)" % (n_way, D))
+    ws = torch.empty(words, device=dev, dtype=torch.float32)
+    Z = torch.empty((1 if n_way <= 3 else 2) * n_ep * n_pts, 4, device=dev, dtype=torch.float32)  # (planes of 4 classes)
+    _lib.check(lib.r3d_protonet_head_train_fwd(n_ep, _p(sfeat_pm), ldf, _p(qfeat_pm), ldq, feat_ep_rows, D, _p(sy), n_way, k_shot,
+                                               N, n_pts, code, float(scaler), _p(Z), _p(ws), words, _st()))
+    return Z, ws
+
+
+def protonet_head_bwd(qfeat_pm, support_y, n_way, k_shot, N, method, dZ, ws, dsfeat, dqfeat, scaler=10.0, n_ep=1,
+                      feat_ep_rows=0, dfeat_ep_rows=0, n_query_pts=None):
+    """Backward of protonet_head_train: dZ (the layout of Z) -> dsfeat (S*N rows), dqfeat (n_query_pts rows), WRITTEN into the
+    given 2-D views (their own leading dimensions; episode e dfeat_ep_rows rows further on in both)."""
+    Mq, ldq = _rows(qfeat_pm)
+    _, ldds = _rows(dsfeat)
+    _, lddq = _rows(dqfeat)
+    n_pts = Mq if n_query_pts is None else n_query_pts
+    D = qfeat_pm.shape[1]
+    assert dsfeat.shape[1] == D and dqfeat.shape[1] == D and dZ.dtype == torch.float32 and dZ.is_contiguous()
+    assert dZ.numel() == (1 if n_way <= 3 else 2) * n_ep * n_pts * 4
+    sy = support_y.reshape(n_ep * n_way * k_shot, N).to(torch.int32).contiguous()
+    _lib.check(_lib.load().r3d_protonet_head_bwd(n_ep, _p(qfeat_pm), ldq, feat_ep_rows, D, _p(sy), n_way, k_shot, N, n_pts,
+                                                 _proto_method(method), float(scaler), _p(dZ), _p(dsfeat), ldds, _p(dqfeat),
+                                                 lddq, dfeat_ep_rows, _p(ws), ws.numel(), _st()))
+    return dsfeat, dqfeat
+
+
 def logits_ce_from_rows(Z, n_q, N, n_classes, labels):
     """Z (n_q*N, 4) -- (2, n_q*N, 4) for more than 4 classes -- -> logits (n_q, n_classes, N), CE loss, argmax."""
     dev = Z.device

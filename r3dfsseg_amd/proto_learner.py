@@ -1,5 +1,5 @@
-"""Host-side mirror of the reference's models/proto_learner.py::ProtoLearner (test path; the
-reference's own train() cannot run, see SURVEY.md "facts that contradict")."""
+"""Host-side mirror of the reference's models/proto_learner.py::ProtoLearner: test(), and the training loop train()
+plainly intends (forward, zero_grad, backward, optimizer.step, lr_scheduler.step)."""
 import torch
 from torch import optim
 
@@ -34,7 +34,27 @@ class ProtoLearner(object):
             raise ValueError('Wrong GMMLearner mode (%s)! Option:train/test' % mode)
 
     def train(self, data, logger):
-        raise NotImplementedError("the reference's ProtoLearner.train is broken (proto_learner.py:57)")
+        """One optimisation step on one episode (models/proto_learner.py:55-67): model.train(), forward, zero_grad,
+        loss.backward(), optimizer.step(), lr_scheduler.step().  Returns ``(loss, accuracy)``: the loss of the forward on the
+        pre-step weights and the arg-max accuracy of that forward over all query points, background included.  These are the
+        two values ProtoNet.forward can supply; the four further names in the reference's return statement
+        (proto_learner.py:69: clean_ratio, size_ratio, query_acc_LP, query_acc_original) have no source in it.
+
+        data: the 8-entry list of proto_learner.py:54 or the 11-tensor training layout (synthetic.make_episode(train=True),
+        the reference's training collate); only the first four entries are used:
+        support_x (n_way, k_shot, in_channels, num_points), support_y (n_way, k_shot, num_points),
+        query_x (n_queries, in_channels, num_points), query_y (n_queries, num_points)."""
+        support_x, support_y, query_x, query_y = (t.cuda() for t in data[:4])
+        self.model.train()
+        query_logits, loss = self.model(support_x, support_y, query_x, query_y)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        self.lr_scheduler.step()
+        query_pred = query_logits.argmax(dim=1)
+        correct = torch.eq(query_pred, query_y).sum().item()  # including background class
+        accuracy = correct / (query_y.shape[0] * query_y.shape[1])
+        return loss, accuracy
 
     def test(self, data, sampled_classes, step=None, path=None):
         [support_x, support_y, query_x, query_y, _, _, gt_support_y] = data

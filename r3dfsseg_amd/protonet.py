@@ -1,11 +1,13 @@
 """Host-side mirror of the reference's models/protonet.py::ProtoNet (lines 39-58, 245-354):
 same constructor and forward() signature; encoder / attention / base learner run on the HIP
-kernels, the head is r3d_protonet_head."""
+kernels, the head is r3d_protonet_head (evaluation) or r3d_protonet_head_train_fwd / r3d_protonet_head_bwd
+(a module in .train() mode: protonet_train.py)."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from .dgcnn import DGCNN, BaseLearner, SelfAttention, check_output_dim
+from .mpti import EpisodeSlot
 
 
 class ProtoNet(nn.Module):
@@ -28,6 +30,9 @@ class ProtoNet(nn.Module):
             self.att_learner = SelfAttention(args.dgcnn_mlp_widths[-1], args.output_dim)
         else:
             self.linear_mapper = nn.Conv1d(args.dgcnn_mlp_widths[-1], args.output_dim, 1, bias=False)
+        self._slot = EpisodeSlot(0)  # what train_ops.EncoderTrainFn reads: the device word behind the dropout seed
+        # parity tests set this to a dict; a training forward then leaves its neighbour lists and features in it
+        self._trace = None
 
     def getFeatures_pm(self, x):
         B, _, N = x.shape
@@ -50,9 +55,15 @@ class ProtoNet(nn.Module):
 
     def forward(self, support_x, support_y, query_x, query_y, support_c=None, query_c=None, train=False,
                 gt_support_y=None, gt_query_y=None, logger=None):
-        if train or self.training:
-            raise NotImplementedError("ProtoLearner.train is broken in the reference itself "
-                                      "(proto_learner.py:57 unpacks 6 values from a forward that returns 2)")
+        if train and not self.training:
+            raise NotImplementedError("train=True needs model.train(): the training kernels use batch-statistics "
+                                      "BatchNorm and attention dropout (models/mpti_learner.py:58-63)")
+        if self.training:  # the reference's forward under model.train(): the same pair, the loss carries the graph
+            if not self.use_attention:
+                raise NotImplementedError("training with use_attention=False (the linear mapper) is not built: the training "
+                                          "encoder (train_ops.EncoderTrainFn) needs the attention learner")
+            from . import protonet_train
+            return protonet_train.protonet_train_forward(self, support_x, support_y, query_x, query_y)
         S, N = self.n_way * self.k_shot, self.n_points
         n_q = query_x.shape[0]
         sx = support_x.reshape(S, self.in_channels, N)

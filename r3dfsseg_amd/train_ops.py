@@ -453,6 +453,31 @@ def encoder_params(model):
     return ps
 
 
+def _adjacent_rows(a, b):
+    """The matrix whose rows are a's followed by b's when both are views of exactly that (one contiguous 2-D tensor), else None."""
+    base = a._base
+    if base is None or base is not b._base or base.dim() != 2 or not base.is_contiguous():
+        return None
+    if not (a.is_contiguous() and b.is_contiguous() and a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[1] == base.shape[1]):
+        return None
+    if base.shape[0] != a.shape[0] + b.shape[0] or a.data_ptr() != base.data_ptr():
+        return None
+    if b.data_ptr() != base.data_ptr() + a.numel() * a.element_size():
+        return None
+    return base
+
+
+def next_dropout_seed(model):
+    """The attention-dropout seed of a model's next training forward (two getFeatures calls: the seed advances by 2).  A
+    launch sequence frozen in a graph advances the slot's device word instead and the host value stays 0."""
+    slot = model._slot
+    if slot.seed_dev is not None:
+        slot.seed_dev.add_(2)
+        return 0
+    model._drop_seed = getattr(model, "_drop_seed", 0) + 2
+    return model._drop_seed
+
+
 def get_features_train(model, x, seed, seg=None):
     """feat (B*N, feat_dim) with gradient edges to the encoder / base / attention parameters.  `seg` (ops.SegLayout with
     E = 1, Q > 0): x holds the support clouds followed by the query clouds of an episode and the two getFeatures
@@ -477,7 +502,9 @@ def get_features_train(model, x, seed, seg=None):
             if len(dfeats) == 2:
                 dfeats = [d if d is not None else torch.zeros(sh, device=ctx.saved[3].device, dtype=torch.float32)
                           for d, sh in zip(dfeats, ctx.seg_shapes)]
-                dfeat = torch.cat(dfeats, 0)
+                dfeat = _adjacent_rows(*dfeats)  # a head that wrote both into one matrix: no copy
+                if dfeat is None:
+                    dfeat = torch.cat(dfeats, 0)
             else:
                 dfeat = dfeats[0]
             out = EncoderTrainFn.backward(ctx, dfeat)
