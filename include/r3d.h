@@ -426,6 +426,21 @@ int r3d_protonet_head(const float* sfeat, long ldf, const float* qfeat, long ldq
                       int n_way, int k_shot, int N, int n_query_pts, int method, float scaler, float* Z, float* ws,
                       void* stream);
 
+/* The same head for n_ep episodes in one launch pair (shots x episodes, query tiles x episodes).  Layout conventions of
+ * r3d_protonet_head_train_fwd below: sfeat / qfeat point at episode 0's support / query rows inside one feature matrix,
+ * episode e starts feat_ep_rows rows further on; support_y (n_ep, S, N); Z (n_ep * n_query_pts, 4) per plane, plane 1
+ * (classes 4..7) n_ep * n_query_pts rows further on when n_way > 3 (r3d_query_logits_ce_batched with z_ep_rows =
+ * n_query_pts).  Per episode the result is bit for bit r3d_protonet_head's on that episode alone.  1 <= n_way <= 7,
+ * D <= 256, n_ep <= 65535; ws: r3d_protonet_head_ws_words(...) floats (< 0: unsupported shape), 16-byte aligned. */
+long r3d_protonet_head_ws_words(int n_ep, int n_way, int k_shot);
+int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows, int D,
+                              const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts, int method,
+                              float scaler, float* Z, float* ws, long ws_words, void* stream);
+/* correct (n_ep) int32 = per episode #{pred == label}: pred (n_ep, n_pts) int32 as r3d_query_logits_ce_batched writes it,
+ * labels (n_ep, n_pts) int64.  One host read then serves the accuracy of a whole batch. */
+int r3d_count_correct_batched(int n_ep, const int32_t* pred, const int64_t* labels, long n_pts, int32_t* correct,
+                              void* stream);
+
 /* ---- ProtoNet head in training mode (reference: models/protonet.py:295-349 and autograd through it; the loop
  * models/proto_learner.py:55-67 intends) ------------------------------------------------
  * n_ep episodes per call: episode e's support / query rows start e * feat_ep_rows rows behind sfeat / qfeat, its masks are

@@ -85,6 +85,9 @@ _SIGS = {
     "r3d_clean_ws_words": (c_l, [c_i, c_i]),
     "r3d_clean_shot_detect": (c_i, [c_f, c_l, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     "r3d_protonet_head": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_f]),
+    "r3d_protonet_head_ws_words": (c_l, [c_i, c_i, c_i]),
+    "r3d_protonet_head_batched": (c_i, [c_i, c_f, c_l, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f]),
+    "r3d_count_correct_batched": (c_i, [c_i, c_f, c_f, c_l, c_f, c_f]),
     "r3d_protonet_head_train_ws_words": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "r3d_protonet_head_train_fwd": (c_i, [c_i, c_f, c_l, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f]),
     "r3d_protonet_head_bwd": (c_i, [c_i, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f, c_l, c_l, c_f,

@@ -216,11 +216,12 @@ __global__ __launch_bounds__(256) void r3d_proto_pool_kernel(const float* __rest
   }
 }
 
-// prototypes (getPrototype) + per-point similarity (calculateSimilarity) -> Z rows (n_q*N, 4)
-__global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restrict__ pooled, int n_way, int k_shot,
-                                                            const float* __restrict__ qfeat, long ldq, int D, int n_pts,
-                                                            int method /*0 cosine, 1 euclidean*/, float scaler,
-                                                            float4* __restrict__ Zq, float4* __restrict__ Zq2 /* classes 4..7 */) {
+// prototypes (getPrototype) + per-point similarity (calculateSimilarity) -> Z rows (n_q*N, 4).  Workgroup `blk` of `nblk`
+// takes every nblk-th group of 4 query points, one wave per point: a point's arithmetic does not depend on the grid.
+static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ pooled, int n_way, int k_shot,
+                                                    const float* __restrict__ qfeat, long ldq, int D, int n_pts, int method,
+                                                    float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2, int blk,
+                                                    int nblk) {
   __shared__ float proto[8][AH_DMAX];
   __shared__ float pnorm[8];
   const int tid = threadIdx.x;
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restr
   }
   __syncthreads();
   const int lane = tid & 63, w = tid >> 6;
-  for (int p = blockIdx.x * 4 + w; p < n_pts; p += gridDim.x * 4) {  // one wave per query point
+  for (int p = blk * 4 + w; p < n_pts; p += nblk * 4) {  // one wave per query point
     const float* q = qfeat + (long)p * ldq;
     float dot[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qq = 0.f, dd[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int c = lane; c < D; c += 64) {
@@ -271,6 +272,81 @@ __global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restr
     if (lane == 0) Zq[p] = make_float4(out[0], out[1], out[2], out[3]);
     if (lane == 0 && Zq2) Zq2[p] = make_float4(out[4], out[5], out[6], out[7]);
   }
+}
+
+__global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restrict__ pooled, int n_way, int k_shot,
+                                                            const float* __restrict__ qfeat, long ldq, int D, int n_pts,
+                                                            int method /*0 cosine, 1 euclidean*/, float scaler,
+                                                            float4* __restrict__ Zq, float4* __restrict__ Zq2 /* classes 4..7 */) {
+  ah_proto_sim(pooled, n_way, k_shot, qfeat, ldq, D, n_pts, method, scaler, Zq, Zq2, blockIdx.x, gridDim.x);
+}
+
+// ---- the same head for a batch of episodes: grid axis y is the episode in both kernels ------------------------------------
+// Pooling: r3d_proto_pool_kernel's two chains per channel, row after row in its order with its operations -- bit for bit its
+// sums -- with the loads of 8 rows in flight instead of one.  grid (S, n_ep); pooled: episode e at + e * S * 2 * 256.
+__global__ __launch_bounds__(256) void r3d_proto_pool_ep_kernel(const float* __restrict__ feat, long ldf, long feat_ep_rows,
+                                                                int D, const int* __restrict__ support_y, int N,
+                                                                float* __restrict__ pooled) {
+  const int shot = blockIdx.x, S = gridDim.x, tid = threadIdx.x;
+  const long ep = blockIdx.y;
+  if (tid >= D) return;
+  const int* my = support_y + (ep * S + shot) * N;
+  const float* f = feat + (ep * feat_ep_rows + (long)shot * N) * ldf + tid;  // rows are read coalesced across the D threads
+  float fg = 0.f, bg = 0.f;
+  int nfg = 0;
+  int p = 0;
+  for (; p + 8 <= N; p += 8) {
+    float v[8];
+    int m[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      v[u] = f[(long)(p + u) * ldf];
+      m[u] = my[p + u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      fg += v[u] * (float)m[u];
+      bg += v[u] * (float)(m[u] == 0);
+      nfg += m[u];
+    }
+  }
+  for (; p < N; ++p) {
+    const float v = f[(long)p * ldf];
+    const int m = my[p];
+    fg += v * (float)m;
+    bg += v * (float)(m == 0);
+    nfg += m;
+  }
+  float* out = pooled + (ep * S + shot) * 2 * AH_DMAX;
+  // getMaskedFeatures: sum(feat * mask) / (mask.sum() + 1e-5)
+  out[tid] = fg / ((float)nfg + 1e-5f);
+  out[AH_DMAX + tid] = bg / ((float)(N - nfg) + 1e-5f);
+}
+
+// grid (query tiles, n_ep)
+__global__ __launch_bounds__(256) void r3d_proto_sim_ep_kernel(const float* __restrict__ pooled, int n_way, int k_shot,
+                                                               const float* __restrict__ qfeat, long ldq, long feat_ep_rows,
+                                                               int D, int n_pts, int method, float scaler,
+                                                               float4* __restrict__ Zq, float4* __restrict__ Zq2) {
+  const long ep = blockIdx.y;
+  ah_proto_sim(pooled + ep * n_way * k_shot * 2 * AH_DMAX, n_way, k_shot, qfeat + ep * feat_ep_rows * ldq, ldq, D, n_pts, method,
+               scaler, Zq + ep * n_pts, Zq2 ? Zq2 + ep * n_pts : nullptr, blockIdx.x, gridDim.x);
+}
+
+// correct[e] = #{pred == label} over the n_pts query points of episode e (integers: any order gives the same count).  grid (n_ep)
+__global__ __launch_bounds__(256) void r3d_count_correct_kernel(const int* __restrict__ pred, const long long* __restrict__ labels,
+                                                                long n_pts, int* __restrict__ correct) {
+  __shared__ int part[4];
+  const int tid = threadIdx.x;
+  const int* pr = pred + (long)blockIdx.x * n_pts;
+  const long long* lb = labels + (long)blockIdx.x * n_pts;
+  int c = 0;
+  for (long i = tid; i < n_pts; i += 256) c += (long long)pr[i] == lb[i] ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((tid & 63) == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) correct[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
 // ---------------------------------------------------------------------------
@@ -341,6 +417,56 @@ extern "C" int r3d_protonet_head(const float* sfeat, long ldf, const float* qfea
   hipLaunchKernelGGL(r3d_proto_sim_kernel, dim3(256), dim3(256), 0, st, ws, n_way, k_shot, qfeat, ldq, D, n_query_pts,
                      method, scaler, (float4*)Z, n_way > 3 ? (float4*)Z + n_query_pts : nullptr);
   R3D_LAUNCH_CHECK("r3d_protonet_head");
+  return R3D_OK;
+}
+
+// The evaluation head for n_ep episodes in ONE launch pair: per episode bit for bit what r3d_protonet_head gives for it alone
+// (the pooled sums walk a shot's rows in the same order; a query point's arithmetic is the same function).  sfeat / qfeat:
+// episode 0's support / query rows inside one feature matrix, episode e feat_ep_rows rows further on; support_y (n_ep, S, N);
+// Z (n_ep * n_query_pts, 4) per plane, plane 1 (classes 4..7) n_ep * n_query_pts rows further on when n_way > 3.
+extern "C" long r3d_protonet_head_ws_words(int n_ep, int n_way, int k_shot) {
+  if (n_ep < 1 || n_ep > 65535 || n_way < 1 || n_way > 7 || k_shot < 1 || (long)n_way * k_shot > 65535) return -1;
+  return (long)n_ep * n_way * k_shot * 2 * AH_DMAX;
+}
+extern "C" int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows,
+                                         int D, const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts,
+                                         int method, float scaler, float* Z, float* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(sfeat && qfeat && support_y && Z && ws, "r3d_protonet_head_batched: null pointer");
+  R3D_REQUIRE(n_way >= 1 && n_way <= 7 && D >= 1 && D <= AH_DMAX && k_shot >= 1 && (long)n_way * k_shot <= 65535 && N >= 1 &&
+                  n_query_pts >= 1 && ldf >= D && ldq >= D,
+              "r3d_protonet_head_batched: unsupported shape n_way=%d k_shot=%d N=%d D=%d", n_way, k_shot, N, D);
+  if (method != 0 && method != 1) {
+    // the reference raises NotImplementedError for anything but cosine / euclidean (protonet.py:347)
+    r3d_set_error("Error! Distance computation method (%d) is unknown!", method);
+    return R3D_ERR_UNSUPPORTED;
+  }
+  const int S = n_way * k_shot;
+  R3D_REQUIRE(n_ep >= 1 && n_ep <= 65535 && (n_ep == 1 || feat_ep_rows >= (long)S * N),
+              "r3d_protonet_head_batched: %d episodes, %ld rows between them", n_ep, feat_ep_rows);
+  const long need = r3d_protonet_head_ws_words(n_ep, n_way, k_shot);
+  R3D_REQUIRE(ws_words >= need, "r3d_protonet_head_batched: workspace of %ld words is shorter than r3d_protonet_head_ws_words = %ld",
+              ws_words, need);
+  R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)Z & 15) == 0, "r3d_protonet_head_batched: ws and Z must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(r3d_proto_pool_ep_kernel, dim3(S, n_ep), dim3(256), 0, st, sfeat, ldf, feat_ep_rows, D, support_y, N, ws);
+  // ~2048 workgroups over the batch (8 per CU), 256 for one episode as r3d_protonet_head: every workgroup builds the
+  // prototypes of its episode again, so few episodes get many tiles and many episodes few
+  const int gx = min(r3d_cdiv(n_query_pts, 4), max(32, min(256, 2048 / n_ep)));
+  hipLaunchKernelGGL(r3d_proto_sim_ep_kernel, dim3(gx, n_ep), dim3(256), 0, st, ws, n_way, k_shot, qfeat, ldq, feat_ep_rows, D,
+                     n_query_pts, method, scaler, (float4*)Z, n_way > 3 ? (float4*)Z + (long)n_ep * n_query_pts : nullptr);
+  R3D_LAUNCH_CHECK("r3d_protonet_head_batched");
+  return R3D_OK;
+}
+
+// correct (n_ep) int32: per episode the number of query points whose arg-max (pred (n_ep, n_pts) int32, as
+// r3d_query_logits_ce_batched writes it) equals the label (n_ep, n_pts) int64
+extern "C" int r3d_count_correct_batched(int n_ep, const int32_t* pred, const int64_t* labels, long n_pts, int32_t* correct,
+                                         void* stream) {
+  R3D_REQUIRE(pred && labels && correct, "r3d_count_correct_batched: null pointer");
+  R3D_REQUIRE(n_ep >= 1 && n_pts >= 1 && n_pts < 0x7fffffffL, "r3d_count_correct_batched: %d episodes of %ld points", n_ep, n_pts);
+  hipLaunchKernelGGL(r3d_count_correct_kernel, dim3(n_ep), dim3(256), 0, (hipStream_t)stream, pred, (const long long*)labels,
+                     n_pts, correct);
+  R3D_LAUNCH_CHECK("r3d_count_correct_batched");
   return R3D_OK;
 }
 

@@ -125,13 +125,7 @@ def explicit_train_batch(model, batch, grad_sink, loss_weight=0.1):
     S, N = model.n_way * model.k_shot, model.n_points
     Q = batch.query_x.shape[1]
     with torch.no_grad():
-        slot = model._slot
-        if slot.seed_dev is not None:
-            slot.seed_dev.add_(2 * E)
-            seed = 2 - 2 * E  # episode e draws seed_dev + 2 - 2 E + 2 e: the values E single-episode sequences would
-        else:
-            seed = getattr(model, "_drop_seed", 0) + 2
-            model._drop_seed = seed + 2 * (E - 1)
+        seed = T.next_dropout_seeds(model, E)  # episode e draws what the e-th of E single-episode sequences would
         params = T.encoder_params(model)
         cs, cc, ch = (SimpleNamespace(param_list=params) for _ in range(3))
         seg = SegLayout(E, S, Q, N)

@@ -450,6 +450,26 @@ def _proto_method(method):
     return _PROTO_METHODS[method]
 
 
+def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, n_ep, feat_ep_rows, n_query_pts, scaler=10.0):
+    """protonet_head for n_ep episodes in one launch pair: Z (n_ep * n_query_pts, 4) per plane, episode after episode, per
+    episode bit for bit protonet_head's rows.  sfeat_pm / qfeat_pm: the support / query rows of episode 0 (views into ONE
+    feature matrix in which episode e's rows start feat_ep_rows rows further on)."""
+    _, ldf = _rows(sfeat_pm)
+    _, ldq = _rows(qfeat_pm)
+    code = _proto_method(method)
+    sy = support_y.reshape(n_ep * n_way * k_shot, N).to(torch.int32).contiguous()
+    dev = sfeat_pm.device
+    lib = _lib.load()
+    words = lib.r3d_protonet_head_ws_words(n_ep, n_way, k_shot)
+    if words < 0:
+        raise NotImplementedError("ProtoNet head: 1 <= n_way <= 7, 1 <= episodes <= 65535 (n_way=%d, episodes=%d)" % (n_way, n_ep))
+    ws = torch.empty(words, device=dev, dtype=torch.float32)
+    Z = torch.empty((1 if n_way <= 3 else 2) * n_ep * n_query_pts, 4, device=dev, dtype=torch.float32)  # (planes of 4 classes)
+    _lib.check(lib.r3d_protonet_head_batched(n_ep, _p(sfeat_pm), ldf, _p(qfeat_pm), ldq, feat_ep_rows, sfeat_pm.shape[1], _p(sy),
+                                             n_way, k_shot, N, n_query_pts, code, float(scaler), _p(Z), _p(ws), words, _st()))
+    return Z
+
+
 def protonet_head_train(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0, n_ep=1, feat_ep_rows=0,
                         n_query_pts=None):
     """Training forward of the ProtoNet head -> (Z, ws): the similarity rows of protonet_head (n_ep > 1: (n_ep * n_query_pts, 4)
@@ -501,6 +521,32 @@ def logits_ce_from_rows(Z, n_q, N, n_classes, labels):
     _lib.check(_lib.load().r3d_query_logits_ce_batched(1, _p(Z), n_q * N, _p(zero), 0, n_q, N, n_classes, _p(labels),
                                                        _p(logits), _p(loss.view(1)), _p(pred), _st()))
     return logits, loss, pred
+
+
+def logits_ce_from_rows_batched(Z, E, n_q, N, n_classes, labels):
+    """logits_ce_from_rows for E episodes: Z (E * n_q*N, 4) per plane -> logits (E, n_q, n_classes, N), loss (E,) -- each the
+    mean over ITS episode's query points --, pred (E, n_q, N) int32."""
+    dev = Z.device
+    zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
+    logits = torch.empty(E, n_q, n_classes, N, device=dev, dtype=torch.float32)
+    loss = torch.empty(E, device=dev, dtype=torch.float32)
+    pred = torch.empty(E, n_q, N, device=dev, dtype=torch.int32)
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == E * n_q * N
+    _lib.check(_lib.load().r3d_query_logits_ce_batched(E, _p(Z), n_q * N, _p(zero), 0, n_q, N, n_classes, _p(labels), _p(logits),
+                                                       _p(loss), _p(pred), _st()))
+    return logits, loss, pred
+
+
+def count_correct(pred, labels):
+    """pred (E, ...) int32, labels (E, ...) int64 -> (E,) int32 on the device: per episode the number of points with
+    pred == label (one host read then serves a whole batch's accuracies)."""
+    E = pred.shape[0]
+    assert pred.dtype == torch.int32 and labels.dtype == torch.int64 and pred.is_contiguous() and labels.is_contiguous()
+    assert pred.numel() == labels.numel()
+    correct = torch.empty(E, device=pred.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_count_correct_batched(E, _p(pred), _p(labels), pred.numel() // E, _p(correct), _st()))
+    return correct
 
 
 def miou_accumulate(pred, gt, lut, hist):

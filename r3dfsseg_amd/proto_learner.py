@@ -1,5 +1,7 @@
 """Host-side mirror of the reference's models/proto_learner.py::ProtoLearner: test(), and the training loop train()
-plainly intends (forward, zero_grad, backward, optimizer.step, lr_scheduler.step)."""
+plainly intends (forward, zero_grad, backward, optimizer.step, lr_scheduler.step).  train_batch() / test_batch() are this
+build's additions: E episodes of one shape per call through ONE launch sequence (protonet_train.explicit_train_batch,
+ProtoNet.forward_episodes), as MPTILearner_V3.train_batch / test_batch."""
 import torch
 from torch import optim
 
@@ -10,6 +12,7 @@ from .protonet import ProtoNet
 class ProtoLearner(object):
     def __init__(self, args, mode='train'):
         self.model = ProtoNet(args)
+        self._batch_trainer = None  # protonet_train.ProtoBatchTrainer behind train_batch
         if not torch.cuda.is_available():
             raise RuntimeError("ProtoLearner needs an MI355X: the forward pass has no CPU path")
         self.model.cuda()
@@ -55,6 +58,53 @@ class ProtoLearner(object):
         correct = torch.eq(query_pred, query_y).sum().item()  # including background class
         accuracy = correct / (query_y.shape[0] * query_y.shape[1])
         return loss, accuracy
+
+    @staticmethod
+    def _batch(datas):
+        """A list of episodes (the first four tensors of each are used) -> batch.EpisodeBatch on the device."""
+        from .batch import EpisodeBatch
+        if isinstance(datas, EpisodeBatch):
+            return datas
+        if len(datas) == 0:
+            raise ValueError("an empty list of episodes: a batch is at least one episode")
+        eps = [[t.cuda() for t in d[:4]] for d in datas]
+        for e, ep in enumerate(eps[1:], 1):
+            for i, (a, b) in enumerate(zip(eps[0], ep)):
+                if a.shape != b.shape:
+                    raise ValueError("a batch is E episodes of ONE shape: tensor %d of episode %d is %s, of episode 0 %s"
+                                     % (i, e, tuple(b.shape), tuple(a.shape)))
+        return EpisodeBatch.from_episodes(eps)
+
+    def train_batch(self, datas, logger):
+        """E episodes per optimiser step: ``datas`` is a list of what train() takes, all of one shape.  The E episodes go
+        through ONE launch sequence (protonet_train.explicit_train_batch), their gradients are averaged -- over all ranks'
+        episodes when torch.distributed is initialised: one flat all-reduce -- and there is ONE optimizer.step() and ONE
+        lr_scheduler.step().  Returns a list with train()'s ``(loss, accuracy)`` for every episode: per episode what
+        train() computes for it from the same weights and the same dropout seed.  May be interleaved with train() and
+        test*() in any order (protonet_train.ProtoBatchTrainer says how the gradients stay apart)."""
+        from .protonet_train import ProtoBatchTrainer
+        b = self._batch(datas)
+        if not self.model.use_attention:
+            raise NotImplementedError("training with use_attention=False (the linear mapper) is not built: the training "
+                                      "encoder (train_ops.EncoderTrainFn) needs the attention learner")
+        if self._batch_trainer is None:
+            self._batch_trainer = ProtoBatchTrainer(self)
+        loss, _, _, correct = self._batch_trainer.step(b)
+        n = b.query_y.shape[1] * b.query_y.shape[2]
+        return [(loss[e], c / n) for e, c in enumerate(correct.tolist())]  # (the step's one host read)
+
+    def test_batch(self, datas, sampled_classes=None):
+        """test() for E episodes of one shape in ONE launch sequence (ProtoNet.forward_episodes): a list of
+        (pred (n_q, N), loss, accuracy), per episode what test() returns for it."""
+        from . import dist as D
+        b = self._batch(datas)
+        self.model.eval()
+        D.warn_rank_local_stats(self.model, 'evaluation')
+        with torch.no_grad():
+            _, loss, pred, correct = self.model.forward_episodes(b)
+            pred = pred.to(torch.int64)
+        n = b.query_y.shape[1] * b.query_y.shape[2]
+        return [(pred[e], loss[e], c / n) for e, c in enumerate(correct.tolist())]  # (the batch's one host read)
 
     def test(self, data, sampled_classes, step=None, path=None):
         [support_x, support_y, query_x, query_y, _, _, gt_support_y] = data

@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's models/protonet.py::ProtoNet (lines 39-58, 245-354):
 same constructor and forward() signature; encoder / attention / base learner run on the HIP
-kernels, the head is r3d_protonet_head (evaluation) or r3d_protonet_head_train_fwd / r3d_protonet_head_bwd
-(a module in .train() mode: protonet_train.py)."""
+kernels, the head is r3d_protonet_head (evaluation; r3d_protonet_head_batched for a batch of episodes: forward_episodes)
+or r3d_protonet_head_train_fwd / r3d_protonet_head_bwd (a module in .train() mode: protonet_train.py)."""
 import torch
 import torch.nn as nn
 
@@ -34,7 +34,9 @@ class ProtoNet(nn.Module):
         # parity tests set this to a dict; a training forward then leaves its neighbour lists and features in it
         self._trace = None
 
-    def getFeatures_pm(self, x):
+    def getFeatures_pm(self, x, group=0):
+        """group > 0: x is a batch of episodes of `group` clouds each (the attention then splits its key axis as for one
+        episode)."""
         B, _, N = x.shape
         x_pm, x_cm = ops.input_layouts(x)
         cat, level2 = self.encoder.forward_pm(x_pm, B, N, x_cm=x_cm)
@@ -42,7 +44,7 @@ class ProtoNet(nn.Module):
         d1, od = 64, self.output_dim
         ops.copy_cols(cat[:, :d1], feat[:, :d1])
         if self.use_attention:
-            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od])
+            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od], group=group)
         else:
             W = self.linear_mapper.weight.reshape(od, -1).contiguous()
             ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
@@ -72,3 +74,20 @@ class ProtoNet(nn.Module):
         labels = query_y.to(torch.int64).contiguous() if query_y is not None else None
         logits, loss, _ = ops.logits_ce_from_rows(Z, n_q, N, self.n_way + 1, labels)
         return logits, loss
+
+    def forward_episodes(self, batch):
+        """Inference forward of the E episodes of `batch` (batch.EpisodeBatch) in ONE launch sequence: eval-mode BatchNorm
+        uses running statistics, so all clouds of all episodes share one encoder pass; then the batched head and the
+        batched loss kernel.  Returns (logits (E, n_q, n_way + 1, N), loss (E,), pred (E, n_q, N) int32, correct (E,) int32):
+        per episode what forward() gives for it."""
+        if self.training:
+            raise NotImplementedError("forward_episodes is the inference path; training batches go through "
+                                      "protonet_train.explicit_train_batch")
+        E = batch.E
+        S, N = self.n_way * self.k_shot, self.n_points
+        n_q = batch.query_x.shape[1]
+        feat = self.getFeatures_pm(batch.x_all.reshape(E * (S + n_q), self.in_channels, N), group=S + n_q)
+        Z = ops.protonet_head_batched(feat, feat[S * N:], batch.support_y, self.n_way, self.k_shot, N, self.dist_method, E,
+                                      (S + n_q) * N, n_q * N)
+        logits, loss, pred = ops.logits_ce_from_rows_batched(Z, E, n_q, N, self.n_way + 1, batch.query_y)
+        return logits, loss, pred, ops.count_correct(pred, batch.query_y)

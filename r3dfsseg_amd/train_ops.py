@@ -478,6 +478,18 @@ def next_dropout_seed(model):
     return model._drop_seed
 
 
+def next_dropout_seeds(model, E):
+    """The seed argument of ONE launch sequence over E episodes (EncoderTrainFn: episode e draws seed + 2 e) such that
+    episode e gets the seed the e-th of E consecutive next_dropout_seed() calls would hand it."""
+    slot = model._slot
+    if slot.seed_dev is not None:
+        slot.seed_dev.add_(2 * E)
+        return 2 - 2 * E  # episode e draws seed_dev + 2 - 2 E + 2 e
+    seed = getattr(model, "_drop_seed", 0) + 2
+    model._drop_seed = seed + 2 * (E - 1)
+    return seed
+
+
 def get_features_train(model, x, seed, seg=None):
     """feat (B*N, feat_dim) with gradient edges to the encoder / base / attention parameters.  `seg` (ops.SegLayout with
     E = 1, Q > 0): x holds the support clouds followed by the query clouds of an episode and the two getFeatures
