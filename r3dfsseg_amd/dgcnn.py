@@ -1,4 +1,5 @@
-"""Host-side mirror of the reference's models/dgcnn.py + models/attention.py + BaseLearner.
+"""Host-side mirror of the reference's models/dgcnn.py + models/attention.py + BaseLearner, and FewShotFeatures: what the two
+few-shot models (mpti.MPTI_SelfAtten, protonet.ProtoNet) share around them.
 
 Same class names, constructor arguments and state-dict keys as the reference
 (models/dgcnn.py:45-127, models/attention.py:10-48, models/mpti.py:18-40) so reference
@@ -266,3 +267,75 @@ class BaseLearner(nn.Module):
         out = torch.empty(B * N, self.convs[-1][0].weight.shape[0], device=x.device, dtype=torch.float32)
         self.forward_pm(ops.cm_to_pm(x), out)
         return ops.pm_to_cm(out, B, N)
+
+
+class EpisodeSlot:
+    """State owned by ONE in-flight episode: its head buffers, the device word behind the attention-dropout seed
+    and its CG launch budget.  Eager calls use the model's default slot; episode_graph.EpisodeGraphs gives every
+    captured hipGraph its own slot so that several episodes can be in flight on separate HIP streams.  (ProtoNet uses
+    the seed word only: it is what train_ops.EncoderTrainFn reads.)"""
+
+    def __init__(self, sid=0):
+        self.id = sid
+        self.heads = {}
+        self.last = None            # (key, HeadBuffers) of the latest forward through this slot
+        self.seed_dev = None        # int32 device word added to the dropout seed (None: host-side counter)
+        self.fixed_budget = None    # CG launches per solve when the launch sequence is frozen in a graph
+        self.fps_one_launch = True  # persistent one-launch FPS (needs its grid co-resident, see head_proto.hip)
+
+
+class FewShotFeatures(nn.Module):
+    """What MPTI_SelfAtten and ProtoNet share: the episode shape, the feature extractor's parameter containers and
+    getFeatures (models/mpti.py:579-595, models/protonet.py:277-293).  The submodules are registered in the reference's
+    order -- encoder, base_learner, att_learner or linear_mapper; a subclass adds its own after this constructor --
+    because gradient sinks, dist.FlatGradBucket and the optimiser groups are laid out by model.parameters()."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.n_way = args.n_way
+        self.k_shot = args.k_shot
+        self.in_channels = args.pc_in_dim
+        self.n_points = args.pc_npts
+        self.use_attention = args.use_attention
+        if self.n_way > 7:
+            raise NotImplementedError("the head kernels carry at most 8 classes (n_way <= 7): two planes of 4 label columns")
+        self.output_dim = args.output_dim
+        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
+        check_output_dim(self.output_dim, self.use_attention, self.feat_dim)
+        self.encoder = DGCNN(args.edgeconv_widths, args.dgcnn_mlp_widths, args.pc_in_dim, k=args.dgcnn_k)
+        self.base_learner = BaseLearner(args.dgcnn_mlp_widths[-1], args.base_widths)
+        if self.use_attention:
+            self.att_learner = SelfAttention(args.dgcnn_mlp_widths[-1], args.output_dim)
+        else:
+            self.linear_mapper = nn.Conv1d(args.dgcnn_mlp_widths[-1], args.output_dim, 1, bias=False)
+        self._slot = EpisodeSlot(0)
+        # parity tests set this to a dict; a forward then leaves its index decisions and intermediate tensors in it
+        # (neighbour lists per encoder pass and layer, max-pool winners, features; MPTI: shot flags, 201-NN lists)
+        self._trace = None
+
+    def getFeatures_pm(self, x, group=0):
+        """x (B, C_in, N) -> point-major features (B*N, feat_dim): [level1 | att | base].  group > 0: x is a batch of episodes
+        of `group` clouds each (the attention then splits its key axis as for one episode: batch-independent bits)."""
+        B, _, N = x.shape
+        x_pm, x_cm = ops.input_layouts(x)  # point-major views (the collate's) as they lie: no transpose kernel
+        self.encoder.trace = [] if self._trace is not None else None
+        cat, level2 = self.encoder.forward_pm(x_pm, B, N, x_cm=x_cm)
+        if self._trace is not None:
+            self._trace.setdefault("idx", []).append(self.encoder.trace)
+            self._trace.setdefault("cat", []).append(cat)
+            self.encoder.trace = None
+        d1, od = 64, self.output_dim
+        feat = torch.empty(B * N, self.feat_dim, device=x_pm.device, dtype=torch.float32)
+        ops.copy_cols(cat[:, :d1], feat[:, :d1])
+        if self.use_attention:
+            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od], group=group)
+        else:
+            W = self.linear_mapper.weight.reshape(od, -1).contiguous()
+            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
+        self.base_learner.forward_pm(level2, feat[:, d1 + od:])
+        return feat
+
+    def getFeatures(self, x):
+        """Reference signature: (B, C_in, L) -> (B, C_out, L)."""
+        B, _, N = x.shape
+        return ops.pm_to_cm(self.getFeatures_pm(x), B, N)

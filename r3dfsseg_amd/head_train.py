@@ -52,11 +52,8 @@ class HeadLPFn(torch.autograd.Function):
         dev = hb.Z.device
         N, D = model.n_points, model.feat_dim
         S = model.n_way * model.k_shot
-        gs = gloss.reshape(-1)[:1].to(torch.float32).contiguous()  # (the step's loss is the SUM over episodes: one scale)
         pl = E * hb.n_cap  # rows of one plane of label columns (ops.HeadBuffers: two planes for more than 3 ways)
-        G = torch.empty(hb.planes * pl, 4, device=dev, dtype=torch.float32)
-        _lib.check(lib.r3d_ce_grad_batched(E, _p(hb.Z), _p(hb.n_proto_ptr()), 32, hb.n_cap, n_q * N, model.n_classes, _p(labels),
-                                           _p(gs), _p(G), _st()))
+        G = ops.ce_grad(hb.Z, hb.n_proto_ptr(), 32, E, hb.n_cap, n_q * N, model.n_classes, labels, gloss)
         lam = torch.empty(pl, 4, device=dev, dtype=torch.float32)
         dnodes = torch.empty(pl, D, device=dev, dtype=torch.float32)
         budget = int(min(model.lp_max_iter, ctx.budget + max(4, ctx.budget // 4)))
@@ -122,18 +119,10 @@ def explicit_train_batch(model, batch, grad_sink, loss_weight=0.1):
     metrics (E, 4), lp_loss (E,), contrast_loss (E,))."""
     from . import contrast
     E = batch.E
-    S, N = model.n_way * model.k_shot, model.n_points
-    Q = batch.query_x.shape[1]
-    with torch.no_grad():
-        seed = T.next_dropout_seeds(model, E)  # episode e draws what the e-th of E single-episode sequences would
-        params = T.encoder_params(model)
-        cs, cc, ch = (SimpleNamespace(param_list=params) for _ in range(3))
-        seg = SegLayout(E, S, Q, N)
-        cs.seg = seg
-        feat = T.EncoderTrainFn.forward(cs, batch.x_all.view(E * (S + Q), model.in_channels, N), model, seed)
-        sfeat, qfeat = feat, feat[S * N:]
-        cc.E = ch.E = E
-        cc.ep_rows = ch.ep_rows = seg.ep_rows
+
+    def head(feat, seg):
+        sfeat, qfeat = feat, feat[seg.rows_a:]
+        cc, ch = (SimpleNamespace(E=E, ep_rows=seg.ep_rows) for _ in range(2))
         closs = contrast.ContrastFn.forward(cc, sfeat, model.proj.weight, model.proj.bias, model, batch.support_y,
                                             batch.support_flag)
         lploss = HeadLPFn.forward(ch, sfeat, qfeat, model, batch.support_y, batch.query_y)
@@ -146,19 +135,11 @@ def explicit_train_batch(model, batch, grad_sink, loss_weight=0.1):
         dfeat_c, dWp, dbp = contrast.ContrastFn.backward(cc, one * loss_weight)[:3]
         HeadLPFn.backward(ch, one)
         dfeat = ch.dfeat_full  # per episode (support rows | query rows), the layout of `feat`
-        assert dfeat.shape[0] == feat.shape[0]
         dfeat.add_(dfeat_c)  # (the contrast gradient has the batch's layout too: zero on the query rows)
-        grads = T.EncoderTrainFn.backward(cs, dfeat)[3:]
-        index = {id(p): i for i, p in enumerate(q for q in model.parameters() if q.requires_grad)}
-        dst, src = [], []
-        for p, g in zip(params, grads):
-            if g is not None:
-                dst.append(grad_sink[index[id(p)]])
-                src.append(g.reshape(p.shape))
-        dst += [grad_sink[index[id(model.proj.weight)]], grad_sink[index[id(model.proj.bias)]]]
-        src += [dWp, dbp]
-        torch._foreach_add_(dst, src)
-    n_q = batch.query_x.shape[1]
+        return (loss, logits, metrics, lploss, closs), dfeat, [(model.proj.weight, dWp), (model.proj.bias, dbp)]
+
+    loss, logits, metrics, lploss, closs = T.explicit_encoder_step(model, batch, grad_sink, head)
+    n_q, N = batch.query_x.shape[1], model.n_points
     return (loss.reshape(E), logits.reshape(E, n_q, model.n_classes, N), metrics, lploss.reshape(E), closs.reshape(E))
 
 

@@ -1,9 +1,15 @@
 """Device-side mIoU accumulator replacing the per-point python triple loop of
 eval_noise.py:23-72 (evaluate_metric): TP / GT / P histograms per test class, mean IoU over the
-foreground classes only (eval_noise.py:70)."""
+foreground classes only (eval_noise.py:70); and the learners' per-episode accuracy."""
 import torch
 
 from . import ops
+
+
+def point_accuracy(pred, query_y):
+    """Fraction of the query points (n_q, N) of one episode with pred == label, background included
+    (models/mpti_learner.py:75-76).  A host read: the caller's synchronisation point."""
+    return torch.eq(pred, query_y).sum().item() / (query_y.shape[0] * query_y.shape[1])
 
 
 class MIoUAccumulator:

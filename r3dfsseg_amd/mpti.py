@@ -9,48 +9,16 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .dgcnn import DGCNN, BaseLearner, SelfAttention, check_output_dim
+from .dgcnn import EpisodeSlot, FewShotFeatures  # noqa: F401  (EpisodeSlot: batched.py and episode_graph.py import it from here)
 
 
-class EpisodeSlot:
-    """State owned by ONE in-flight episode: its head buffers, the device word behind the attention-dropout seed
-    and its CG launch budget.  Eager calls use the model's default slot; episode_graph.EpisodeGraphs gives every
-    captured hipGraph its own slot so that several episodes can be in flight on separate HIP streams."""
-
-    def __init__(self, sid=0):
-        self.id = sid
-        self.heads = {}
-        self.last = None            # (key, HeadBuffers) of the latest forward through this slot
-        self.seed_dev = None        # int32 device word added to the dropout seed (None: host-side counter)
-        self.fixed_budget = None    # CG launches per solve when the launch sequence is frozen in a graph
-        self.fps_one_launch = True  # persistent one-launch FPS (needs its grid co-resident, see head_proto.hip)
-
-
-class MPTI_SelfAtten(nn.Module):
+class MPTI_SelfAtten(FewShotFeatures):
     def __init__(self, args):
-        super().__init__()
-        self.n_way = args.n_way
-        self.k_shot = args.k_shot
-        self.in_channels = args.pc_in_dim
-        self.n_points = args.pc_npts
-        self.use_attention = args.use_attention
+        super().__init__(args)
         self.n_subprototypes = args.n_subprototypes
         self.k_connect = args.k_connect
         self.sigma = args.sigma
         self.n_classes = self.n_way + 1
-        if self.n_classes > 8:
-            raise NotImplementedError("the head kernels carry at most 8 classes (n_way <= 7): two planes of 4 label columns")
-
-        self.output_dim = args.output_dim
-        self.feat_dim = args.edgeconv_widths[0][-1] + args.output_dim + args.base_widths[-1]
-        check_output_dim(self.output_dim, self.use_attention, self.feat_dim)
-
-        self.encoder = DGCNN(args.edgeconv_widths, args.dgcnn_mlp_widths, args.pc_in_dim, k=args.dgcnn_k)
-        self.base_learner = BaseLearner(args.dgcnn_mlp_widths[-1], args.base_widths)
-        if self.use_attention:
-            self.att_learner = SelfAttention(args.dgcnn_mlp_widths[-1], args.output_dim)
-        else:
-            self.linear_mapper = nn.Conv1d(args.dgcnn_mlp_widths[-1], args.output_dim, 1, bias=False)
         self.shot_seed = getattr(args, "shot_seed", 1)
         self.proj = nn.Linear(self.feat_dim, 128)
         # solver knobs of the sparse label propagation (no reference counterpart: the reference
@@ -58,7 +26,6 @@ class MPTI_SelfAtten(nn.Module):
         self.lp_max_iter = getattr(args, "lp_max_iter", 200)
         self.lp_tol = getattr(args, "lp_tol", 1e-6)
         self.shot_level_clean_ratio = 0
-        self._slot = EpisodeSlot(0)
         # CG launch budget: iterations are enqueued without knowing when the solver converges
         # (no host sync in forward).  The budget follows the iteration count observed on earlier
         # episodes (read back asynchronously); callers that synchronise anyway (learner.test)
@@ -66,40 +33,9 @@ class MPTI_SelfAtten(nn.Module):
         self._lp_budget = min(32, self.lp_max_iter)
         self._lp_probe = None
         self._lp_force = False  # True: the conservative schedule (full CG budget, exact 201-NN kernel, FPS per round)
-        # parity tests set this to a dict; forward() then leaves its index decisions and intermediate tensors in it
-        # (neighbour lists per encoder pass and layer, max-pool winners, features, shot flags, 201-NN lists)
-        self._trace = None
         # parity tests only: callable (nbr (E, n_cap, k + 1) int32) -> nbr that replaces rows of the device's own 201-NN
         # lists (the reference's choice on its near-tie rows, tests/test_gpu_golden_head.py); None in every product path
         self.nbr_patch = None
-
-    # ------------------------------------------------------------------ features (mpti.py:579-595)
-    def getFeatures_pm(self, x, group=0):
-        """x (B, C_in, N) -> point-major features (B*N, feat_dim): [level1 | att | base].  group > 0: x is a batch of episodes
-        of `group` clouds each (the attention then splits its key axis as for one episode: batch-independent bits)."""
-        B, _, N = x.shape
-        x_pm, x_cm = ops.input_layouts(x)  # point-major views (the collate's) as they lie: no transpose kernel
-        self.encoder.trace = [] if self._trace is not None else None
-        cat, level2 = self.encoder.forward_pm(x_pm, B, N, x_cm=x_cm)
-        if self._trace is not None:
-            self._trace.setdefault("idx", []).append(self.encoder.trace)
-            self._trace.setdefault("cat", []).append(cat)
-            self.encoder.trace = None
-        d1, od = 64, self.output_dim
-        feat = torch.empty(B * N, self.feat_dim, device=x_pm.device, dtype=torch.float32)
-        ops.copy_cols(cat[:, :d1], feat[:, :d1])
-        if self.use_attention:
-            self.att_learner.forward_pm(level2, B, N, feat[:, d1:d1 + od], group=group)
-        else:
-            W = self.linear_mapper.weight.reshape(od, -1).contiguous()
-            ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
-        self.base_learner.forward_pm(level2, feat[:, d1 + od:])
-        return feat
-
-    def getFeatures(self, x):
-        """Reference signature: (B, C_in, L) -> (B, C_out, L)."""
-        B, _, N = x.shape
-        return ops.pm_to_cm(self.getFeatures_pm(x), B, N)
 
     # ------------------------------------------------------------------ head buffers
     @property

@@ -18,6 +18,7 @@ import torch
 from torch import optim
 
 from .checkpoint_util import load_model_checkpoint, load_pretrain_checkpoint
+from .metrics import point_accuracy
 from .mpti import MPTI_SelfAtten
 
 
@@ -74,9 +75,7 @@ class MPTILearner_V3(object):
         if self._trainer.redone:  # the conservative eager pass ran instead: its results live in the eager buffers
             return self._tuple_from_eager(loss, data)
         lp, con, m0, m1, m2, m3 = sl.parts.unbind(0)
-        query_y = data[3]
-        correct = torch.eq(sl.logits.argmax(dim=1), query_y).sum().item()  # the step's host sync (mpti_learner.py:75)
-        accuracy = correct / (query_y.shape[0] * query_y.shape[1])
+        accuracy = point_accuracy(sl.logits.argmax(dim=1), data[3])  # the step's host sync (mpti_learner.py:75)
         if logger is not None:
             v = sl.parts[2:].tolist()
             logger.cprint('after label propagation: QUERY prediction acc: {:.3f}, original_acc: {:.3f}'.format(v[0], v[1]))
@@ -85,9 +84,7 @@ class MPTILearner_V3(object):
 
     def _tuple_from_eager(self, loss, data):
         m = self.model
-        query_y = data[3]
-        correct = torch.eq(m._train_logits.argmax(dim=1), query_y).sum().item()
-        accuracy = correct / (query_y.shape[0] * query_y.shape[1])
+        accuracy = point_accuracy(m._train_logits.argmax(dim=1), data[3])
         lp, con, metrics = m._last_train_parts
         return (loss, lp, con, accuracy) + tuple(metrics)
 
@@ -126,8 +123,7 @@ class MPTILearner_V3(object):
         self.optimizer.step()
         self.lr_scheduler.step()
         query_pred = query_logits.argmax(dim=1)  # == softmax(dim=1).argmax(dim=1), mpti_learner.py:74
-        correct = torch.eq(query_pred, query_y).sum().item()
-        accuracy = correct / (query_y.shape[0] * query_y.shape[1])
+        accuracy = point_accuracy(query_pred, query_y)
         return (loss, lp_loss, contrastive_loss, accuracy, query_acc_LP, query_acc_original, clean_ratio_LP_avg,
                 original_clean_ratio)
 
@@ -196,9 +192,7 @@ class MPTILearner_V3(object):
         if bad or overflow:
             return None                          # the eager path below redoes the episode on the conservative schedule
         pred = sl.logits.argmax(dim=1)
-        query_y = data[3]
-        correct = torch.eq(pred, query_y).sum().item()
-        return pred, loss.clone(), correct / (query_y.shape[0] * query_y.shape[1])
+        return pred, loss.clone(), point_accuracy(pred, data[3])
 
     def test(self, data, sampled_classes, step=None, path=None, eval=False):
         if self.episode_graphs:
@@ -214,14 +208,13 @@ class MPTILearner_V3(object):
                                       sampled_classes=sampled_classes, step=step, path=path, support_flag=None,
                                       eval=eval)
             pred = logits.argmax(dim=1)
-            correct = torch.eq(pred, query_y).sum().item()
+            accuracy = point_accuracy(pred, query_y)
             if not self.model.lp_converged():  # CG launch budget too small for this episode: redo in full
                 logits, loss = self.model(support_x, support_y, query_x, query_y, gt_support_y=gt_support_y,
                                           sampled_classes=sampled_classes, step=step, path=path,
                                           support_flag=None, eval=eval, lp_iters=self.model.lp_max_iter)
                 pred = logits.argmax(dim=1)
-                correct = torch.eq(pred, query_y).sum().item()
+                accuracy = point_accuracy(pred, query_y)
                 if not self.model.lp_converged():
                     raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
-            accuracy = correct / (query_y.shape[0] * query_y.shape[1])
         return pred, loss, accuracy

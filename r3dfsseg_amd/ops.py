@@ -387,21 +387,41 @@ def graph_weights_verify(hb, sigma):
     return bad
 
 
-def query_logits_ce(hb, n_q, n_classes, labels):
-    """labels (E, n_q, N) int64 or None -> logits (E, n_q, n_classes, N), loss (E,), pred (E, n_q, N) int32 (E = 1: without
-    the episode axis)."""
-    dev = hb.Z.device
-    E = hb.E
-    logits = torch.empty(E, n_q, n_classes, hb.N, device=dev, dtype=torch.float32)
+def logits_ce(Z, z_ep_rows, n_proto_ptr, desc_stride, E, n_q, N, n_classes, labels):
+    """Z rows -> logits (E, n_q, n_classes, N), loss (E,) -- each the mean over ITS episode's query points --, pred (E, n_q, N)
+    int32 (the arg-max).  Z: planes of 4 class columns with z_ep_rows rows per episode, of which the first
+    n_proto_ptr[e * desc_stride] are not query rows; labels (E, n_q, N) int64, or None: logits and arg-max only."""
+    dev = Z.device
+    logits = torch.empty(E, n_q, n_classes, N, device=dev, dtype=torch.float32)
     loss = torch.empty(E, device=dev, dtype=torch.float32)
-    pred = torch.empty(E, n_q, hb.N, device=dev, dtype=torch.int32)
+    pred = torch.empty(E, n_q, N, device=dev, dtype=torch.int32)
     if labels is not None:
-        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == E * n_q * hb.N
-    _lib.check(_lib.load().r3d_query_logits_ce_batched(E, _p(hb.Z), hb.n_cap, _p(hb.n_proto_ptr()), 32, n_q, hb.N, n_classes,
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == E * n_q * N
+    _lib.check(_lib.load().r3d_query_logits_ce_batched(E, _p(Z), z_ep_rows, _p(n_proto_ptr), desc_stride, n_q, N, n_classes,
                                                        _p(labels), _p(logits), _p(loss), _p(pred), _st()))
-    if E == 1:  # the single-episode shapes: (n_q, n_classes, N), 0-d, (n_q, N)
-        return logits[0], loss[0], pred[0]
     return logits, loss, pred
+
+
+def query_logits_ce(hb, n_q, n_classes, labels):
+    """logits_ce of the label-propagation result in hb (E = 1: without the episode axis, the loss 0-d)."""
+    out = logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), 32, hb.E, n_q, hb.N, n_classes, labels)
+    return tuple(t[0] for t in out) if hb.E == 1 else out
+
+
+def logits_ce_from_rows(Z, E, n_q, N, n_classes, labels):
+    """logits_ce of similarity rows that are query rows only (the ProtoNet heads): Z (E * n_q*N, 4) per plane."""
+    zero = torch.zeros(1, device=Z.device, dtype=torch.int32)  # (no prototype rows in front of the query rows)
+    return logits_ce(Z, n_q * N, zero, 0, E, n_q, N, n_classes, labels)
+
+
+def ce_grad(Z, n_proto_ptr, desc_stride, E, n_cap, n_query_pts, n_classes, labels, gscale):
+    """Backward of logits_ce's loss -> G, the layout of Z (n_cap rows per episode and plane).  gscale (its first element is
+    used) scales every episode alike: the step's loss is the SUM of the episodes' losses."""
+    gs = gscale.reshape(-1)[:1].to(torch.float32).contiguous()
+    G = torch.empty_like(Z)
+    _lib.check(_lib.load().r3d_ce_grad_batched(E, _p(Z), _p(n_proto_ptr), desc_stride, n_cap, n_query_pts, n_classes, _p(labels),
+                                               _p(gs), _p(G), _st()))
+    return G
 
 
 def clean_shot_detect(sfeat_pm, support_x, support_y, n_way, k_shot, N, want_debug=False, E=1, feat_ep_rows=0):
@@ -425,22 +445,6 @@ def clean_shot_detect(sfeat_pm, support_x, support_y, n_way, k_shot, N, want_deb
     return (keep, dbg) if want_debug else keep
 
 
-def protonet_head(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0):
-    """Similarity rows (n_q*N, 4) of the ProtoNet head; method 'cosine' | 'euclidean'."""
-    M, ldf = _rows(sfeat_pm)
-    Mq, ldq = _rows(qfeat_pm)
-    codes = {"cosine": 0, "euclidean": 1}
-    if method not in codes:
-        raise NotImplementedError('Error! Distance computation method (%s) is unknown!' % method)
-    sy = support_y.reshape(n_way * k_shot, N).to(torch.int32).contiguous()
-    dev = sfeat_pm.device
-    Z = torch.empty((1 if n_way <= 3 else 2) * Mq, 4, device=dev, dtype=torch.float32)  # (planes of 4 classes)
-    ws = torch.empty(n_way * k_shot * 2 * 256, device=dev, dtype=torch.float32)
-    _lib.check(_lib.load().r3d_protonet_head(_p(sfeat_pm), ldf, _p(qfeat_pm), ldq, sfeat_pm.shape[1], _p(sy), n_way,
-                                             k_shot, N, Mq, codes[method], float(scaler), _p(Z), _p(ws), _st()))
-    return Z
-
-
 _PROTO_METHODS = {"cosine": 0, "euclidean": 1}
 
 
@@ -448,6 +452,22 @@ def _proto_method(method):
     if method not in _PROTO_METHODS:
         raise NotImplementedError('Error! Distance computation method (%s) is unknown!' % method)
     return _PROTO_METHODS[method]
+
+
+def protonet_head(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0):
+    """Similarity rows (n_q*N, 4) of the ProtoNet head; method 'cosine' | 'euclidean'.  The library's single-episode entry
+    point: no model calls it (ProtoNet runs protonet_head_batched, one episode included); the tests hold the batched and
+    the training head to it bit for bit."""
+    M, ldf = _rows(sfeat_pm)
+    Mq, ldq = _rows(qfeat_pm)
+    code = _proto_method(method)
+    sy = support_y.reshape(n_way * k_shot, N).to(torch.int32).contiguous()
+    dev = sfeat_pm.device
+    Z = torch.empty((1 if n_way <= 3 else 2) * Mq, 4, device=dev, dtype=torch.float32)  # (planes of 4 classes)
+    ws = torch.empty(n_way * k_shot * 2 * 256, device=dev, dtype=torch.float32)
+    _lib.check(_lib.load().r3d_protonet_head(_p(sfeat_pm), ldf, _p(qfeat_pm), ldq, sfeat_pm.shape[1], _p(sy), n_way,
+                                             k_shot, N, Mq, code, float(scaler), _p(Z), _p(ws), _st()))
+    return Z
 
 
 def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, n_ep, feat_ep_rows, n_query_pts, scaler=10.0):
@@ -509,33 +529,6 @@ def protonet_head_bwd(qfeat_pm, support_y, n_way, k_shot, N, method, dZ, ws, dsf
                                                  _proto_method(method), float(scaler), _p(dZ), _p(dsfeat), ldds, _p(dqfeat),
                                                  lddq, dfeat_ep_rows, _p(ws), ws.numel(), _st()))
     return dsfeat, dqfeat
-
-
-def logits_ce_from_rows(Z, n_q, N, n_classes, labels):
-    """Z (n_q*N, 4) -- (2, n_q*N, 4) for more than 4 classes -- -> logits (n_q, n_classes, N), CE loss, argmax."""
-    dev = Z.device
-    zero = torch.zeros(1, device=dev, dtype=torch.int32)
-    logits = torch.empty(n_q, n_classes, N, device=dev, dtype=torch.float32)
-    loss = torch.empty((), device=dev, dtype=torch.float32)
-    pred = torch.empty(n_q, N, device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().r3d_query_logits_ce_batched(1, _p(Z), n_q * N, _p(zero), 0, n_q, N, n_classes, _p(labels),
-                                                       _p(logits), _p(loss.view(1)), _p(pred), _st()))
-    return logits, loss, pred
-
-
-def logits_ce_from_rows_batched(Z, E, n_q, N, n_classes, labels):
-    """logits_ce_from_rows for E episodes: Z (E * n_q*N, 4) per plane -> logits (E, n_q, n_classes, N), loss (E,) -- each the
-    mean over ITS episode's query points --, pred (E, n_q, N) int32."""
-    dev = Z.device
-    zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
-    logits = torch.empty(E, n_q, n_classes, N, device=dev, dtype=torch.float32)
-    loss = torch.empty(E, device=dev, dtype=torch.float32)
-    pred = torch.empty(E, n_q, N, device=dev, dtype=torch.int32)
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == E * n_q * N
-    _lib.check(_lib.load().r3d_query_logits_ce_batched(E, _p(Z), n_q * N, _p(zero), 0, n_q, N, n_classes, _p(labels), _p(logits),
-                                                       _p(loss), _p(pred), _st()))
-    return logits, loss, pred
 
 
 def count_correct(pred, labels):

@@ -6,6 +6,7 @@ import torch
 from torch import optim
 
 from .checkpoint_util import load_model_checkpoint, load_pretrain_checkpoint
+from .metrics import point_accuracy
 from .protonet import ProtoNet
 
 
@@ -54,10 +55,7 @@ class ProtoLearner(object):
         loss.backward()
         self.optimizer.step()
         self.lr_scheduler.step()
-        query_pred = query_logits.argmax(dim=1)
-        correct = torch.eq(query_pred, query_y).sum().item()  # including background class
-        accuracy = correct / (query_y.shape[0] * query_y.shape[1])
-        return loss, accuracy
+        return loss, point_accuracy(query_logits.argmax(dim=1), query_y)
 
     @staticmethod
     def _batch(datas):
@@ -112,6 +110,4 @@ class ProtoLearner(object):
         with torch.no_grad():
             logits, loss = self.model(support_x, support_y, query_x, query_y)
             pred = logits.argmax(dim=1)
-            correct = torch.eq(pred, query_y).sum().item()
-            accuracy = correct / (query_y.shape[0] * query_y.shape[1])
-        return pred, loss, accuracy
+        return pred, loss, point_accuracy(pred, query_y)

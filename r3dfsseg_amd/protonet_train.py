@@ -1,46 +1,57 @@
 """Training-mode forward of ProtoNet (reference models/protonet.py:245-275 under model.train()) and the autograd edge of its
 head.  Compute lives in libr3d_hip.so (csrc/protonet_train.hip); this file orders launches: one episode under autograd
 (protonet_train_forward), or the E episodes of an optimiser step as ONE launch sequence without the autograd engine
-(explicit_train_batch, ProtoBatchTrainer)."""
+(explicit_train_batch, ProtoBatchTrainer).  Both run the same head, ProtoHeadFn: one episode is a batch of one."""
 from types import SimpleNamespace
 
 import torch
 
-from . import _lib, ops, train_ops as T
-from .ops import SegLayout, _p, _st
+from . import ops, train_ops as T
+from .ops import SegLayout
 
 
 class ProtoHeadFn(torch.autograd.Function):
-    """(sfeat, qfeat) -> cross-entropy loss of the prototype similarities; leaves logits / arg-max in model._train_logits /
-    model._train_pred.  backward writes both feature gradients into ONE (S*N + n_q*N, D) matrix, support rows first -- the
-    layout train_ops.EncoderTrainFn.backward consumes -- and returns its two row ranges."""
+    """(sfeat, qfeat) -> cross-entropy loss (E,) of the prototype similarities, each the mean over ITS episode's query
+    points; leaves logits / arg-max in model._train_logits / model._train_pred (E = 1: all without the episode axis).
+
+    sfeat / qfeat: the support / query rows of episode 0; with ``ctx.E > 1`` (set by the caller) they are views into ONE
+    feature matrix in which episode e's rows start ``ctx.ep_rows`` rows further on.  backward writes both feature
+    gradients into ONE (E (S*N + n_q*N), D) matrix, per episode support rows then query rows -- the layout
+    train_ops.EncoderTrainFn.backward consumes --, leaves it in ``ctx.dfeat_full`` and returns it whole (E > 1) or as its
+    two row ranges."""
 
     @staticmethod
     def forward(ctx, sfeat, qfeat, model, support_y, query_y):
+        E = getattr(ctx, "E", 1)
+        ep_rows = getattr(ctx, "ep_rows", 0)
         N = model.n_points
         n_q = query_y.shape[-2]
-        Z, ws = ops.protonet_head_train(sfeat, qfeat, support_y, model.n_way, model.k_shot, N, model.dist_method)
-        labels = query_y.reshape(n_q, N).to(torch.int64).contiguous()
-        logits, loss, pred = ops.logits_ce_from_rows(Z, n_q, N, model.n_way + 1, labels)
-        ctx.model, ctx.Z, ctx.ws, ctx.labels, ctx.n_q = model, Z, ws, labels, n_q
+        Z, ws = ops.protonet_head_train(sfeat, qfeat, support_y, model.n_way, model.k_shot, N, model.dist_method, n_ep=E,
+                                        feat_ep_rows=ep_rows, n_query_pts=n_q * N)
+        labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous()
+        logits, loss, pred = ops.logits_ce_from_rows(Z, E, n_q, N, model.n_way + 1, labels)
+        if E == 1:
+            logits, loss, pred = logits[0], loss[0], pred[0]
+        ctx.model, ctx.Z, ctx.ws, ctx.labels, ctx.n_q, ctx.E, ctx.ep_rows = model, Z, ws, labels, n_q, E, ep_rows
         ctx.qfeat, ctx.support_y = qfeat, support_y
         model._train_logits, model._train_pred = logits, pred
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        model, Z, n_q = ctx.model, ctx.Z, ctx.n_q
+        model, Z, n_q, E, ep_rows = ctx.model, ctx.Z, ctx.n_q, ctx.E, ctx.ep_rows
         dev = Z.device
         N, D = model.n_points, model.feat_dim
         S = model.n_way * model.k_shot
-        gs = gloss.reshape(-1)[:1].to(torch.float32).contiguous()
         zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
-        G = torch.empty_like(Z)
-        _lib.check(_lib.load().r3d_ce_grad_batched(1, _p(Z), _p(zero), 0, n_q * N, n_q * N, model.n_way + 1, _p(ctx.labels), _p(gs),
-                                                   _p(G), _st()))
-        dfeat = torch.empty((S + n_q) * N, D, device=dev, dtype=torch.float32)
-        ops.protonet_head_bwd(ctx.qfeat, ctx.support_y, model.n_way, model.k_shot, N, model.dist_method, G, ctx.ws,
-                              dfeat[:S * N], dfeat[S * N:])
+        G = ops.ce_grad(Z, zero, 0, E, n_q * N, n_q * N, model.n_way + 1, ctx.labels, gloss)
+        assert E == 1 or ep_rows == (S + n_q) * N
+        dfeat = torch.empty(E * (S + n_q) * N, D, device=dev, dtype=torch.float32)
+        ops.protonet_head_bwd(ctx.qfeat, ctx.support_y, model.n_way, model.k_shot, N, model.dist_method, G, ctx.ws, dfeat,
+                              dfeat[S * N:], n_ep=E, feat_ep_rows=ep_rows, dfeat_ep_rows=ep_rows, n_query_pts=n_q * N)
+        ctx.dfeat_full = dfeat  # (explicit_train_batch takes the whole buffer)
+        if E > 1:
+            return dfeat, None, None, None, None
         return dfeat[:S * N], dfeat[S * N:], None, None, None
 
 
@@ -63,45 +74,24 @@ def protonet_train_forward(model, support_x, support_y, query_x, query_y):
 
 def explicit_train_batch(model, batch, grad_sink):
     """Forward + backward of the E episodes of `batch` (batch.EpisodeBatch) as ONE fixed launch sequence without the
-    autograd engine (as head_train.explicit_train_batch for MPTI): training encoder over all E (S + Q) clouds with BatchNorm
-    batch statistics per episode and getFeatures call, the head kernels with n_ep = E, one cross entropy per episode (the
-    mean over ITS query points) with a unit upstream gradient each, and every parameter gradient -- summed over the E
-    episodes where it is produced -- ADDED into grad_sink[i] (views in the order of model.parameters(), requires_grad
-    only).  Per episode the same kernels and results as protonet_train_forward + loss.backward(), episode after episode.
+    autograd engine (train_ops.explicit_encoder_step, as head_train.explicit_train_batch for MPTI): training encoder over
+    all E (S + Q) clouds with BatchNorm batch statistics per episode and getFeatures call, the head kernels with n_ep = E,
+    one cross entropy per episode (the mean over ITS query points) with a unit upstream gradient each, and every parameter
+    gradient -- summed over the E episodes where it is produced -- ADDED into grad_sink[i].  Per episode the same kernels
+    and results as protonet_train_forward + loss.backward(), episode after episode.
     Returns (loss (E,), logits (E, n_q, n_way + 1, N), pred (E, n_q, N) int32, correct (E,) int32)."""
-    E = batch.E
-    S, N, D = model.n_way * model.k_shot, model.n_points, model.feat_dim
+    E, N = batch.E, model.n_points
     Q = batch.query_x.shape[1]
-    n_pts, C = Q * N, model.n_way + 1
-    with torch.no_grad():
-        seed = T.next_dropout_seeds(model, E)
-        params = T.encoder_params(model)
-        ctx = SimpleNamespace(param_list=params)
-        seg = ctx.seg = SegLayout(E, S, Q, N)
-        feat = T.EncoderTrainFn.forward(ctx, batch.x_all.view(E * (S + Q), model.in_channels, N), model, seed)
-        sfeat, qfeat = feat, feat[S * N:]
-        Z, ws = ops.protonet_head_train(sfeat, qfeat, batch.support_y, model.n_way, model.k_shot, N, model.dist_method, n_ep=E,
-                                        feat_ep_rows=seg.ep_rows, n_query_pts=n_pts)
-        logits, loss, pred = ops.logits_ce_from_rows_batched(Z, E, Q, N, C, batch.query_y)
+
+    def head(feat, seg):
+        ctx = SimpleNamespace(E=E, ep_rows=seg.ep_rows)
+        loss = ProtoHeadFn.forward(ctx, feat, feat[seg.rows_a:], model, batch.support_y, batch.query_y).reshape(E)
+        logits, pred = model._train_logits.reshape(E, Q, model.n_way + 1, N), model._train_pred.reshape(E, Q, N)
         correct = ops.count_correct(pred, batch.query_y)
-        # ---- backward, in dependency order
-        dev = feat.device
-        one = torch.ones(1, device=dev, dtype=torch.float32)  # d(step loss) / d(loss_e) = 1 for every episode
-        zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
-        G = torch.empty_like(Z)
-        _lib.check(_lib.load().r3d_ce_grad_batched(E, _p(Z), _p(zero), 0, n_pts, n_pts, C, _p(batch.query_y), _p(one), _p(G), _st()))
-        dfeat = torch.empty(E * seg.ep_rows, D, device=dev, dtype=torch.float32)  # the layout of `feat`
-        ops.protonet_head_bwd(qfeat, batch.support_y, model.n_way, model.k_shot, N, model.dist_method, G, ws, dfeat, dfeat[S * N:],
-                              n_ep=E, feat_ep_rows=seg.ep_rows, dfeat_ep_rows=seg.ep_rows, n_query_pts=n_pts)
-        grads = T.EncoderTrainFn.backward(ctx, dfeat)[3:]
-        index = {id(p): i for i, p in enumerate(q for q in model.parameters() if q.requires_grad)}
-        dst, src = [], []
-        for p, g in zip(params, grads):
-            if g is not None:
-                dst.append(grad_sink[index[id(p)]])
-                src.append(g.reshape(p.shape))
-        torch._foreach_add_(dst, src)
-    return loss, logits, pred, correct
+        ProtoHeadFn.backward(ctx, torch.ones((), device=feat.device))  # d(step loss) / d(loss_e) = 1 for every episode
+        return (loss, logits, pred, correct), ctx.dfeat_full, []
+
+    return T.explicit_encoder_step(model, batch, grad_sink, head)
 
 
 class ProtoBatchTrainer:

@@ -14,6 +14,7 @@ segment's statistics, and with them every per-episode result of the forward pass
 the episode runs alone or inside a batch (the kernels partition their reductions by the segment, not by the batch).
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
@@ -523,6 +524,36 @@ def get_features_train(model, x, seed, seg=None):
             return (None,) + out[3:]
 
     return _Fn.apply(x, *params)
+
+
+def explicit_encoder_step(model, batch, grad_sink, head):
+    """Forward + backward of the E episodes of `batch` (batch.EpisodeBatch) as ONE fixed launch sequence without the
+    autograd engine: EncoderTrainFn's forward half runs with a plain namespace as its ctx, then the model's head, then
+    the backward half, and every parameter gradient -- summed over the E episodes where it is produced -- is ADDED into
+    grad_sink[i] (views in the order of model.parameters(), requires_grad only).
+
+    head(feat, seg) -> (outputs, dfeat, extra): everything between the two halves.  feat (E (S + Q) N, feat_dim) per episode
+    (support rows | query rows), seg its ops.SegLayout; dfeat = d(step loss) / d(feat) in the same layout; extra a list of
+    (parameter, gradient) of the head's own parameters.  Returns `outputs`."""
+    E = batch.E
+    S, N = model.n_way * model.k_shot, model.n_points
+    Q = batch.query_x.shape[1]
+    with torch.no_grad():
+        seed = next_dropout_seeds(model, E)  # episode e draws what the e-th of E single-episode sequences would
+        params = encoder_params(model)
+        ctx = SimpleNamespace(param_list=params, seg=SegLayout(E, S, Q, N))
+        feat = EncoderTrainFn.forward(ctx, batch.x_all.view(E * (S + Q), model.in_channels, N), model, seed)
+        outputs, dfeat, extra = head(feat, ctx.seg)
+        assert dfeat.shape[0] == feat.shape[0]
+        grads = EncoderTrainFn.backward(ctx, dfeat)[3:]
+        index = {id(p): i for i, p in enumerate(q for q in model.parameters() if q.requires_grad)}
+        dst, src = [], []
+        for p, g in list(zip(params, grads)) + extra:
+            if g is not None:
+                dst.append(grad_sink[index[id(p)]])
+                src.append(g.reshape(p.shape))
+        torch._foreach_add_(dst, src)
+    return outputs
 
 
 def mpti_train_forward(model, support_x, support_y, query_x, query_y, gt_support_y, gt_query_y, logger, support_flag):

@@ -79,6 +79,29 @@ def test_partial_state_dict_is_non_strict(tmp_path):
     assert m.checkpoint_meta["unexpected"] == ["some.other.head"]
 
 
+@pytest.mark.parametrize("use_attention", [True, False])
+def test_parameter_order_of_both_models(use_attention):
+    """Gradient sinks, dist.FlatGradBucket and the optimiser groups are laid out by model.parameters(), and reference
+    checkpoints by the state-dict names: encoder, base_learner, att_learner or linear_mapper, then MPTI's proj."""
+    from itertools import groupby
+
+    from r3dfsseg_amd.mpti import MPTI_SelfAtten
+    from r3dfsseg_amd.protonet import ProtoNet
+    cfg = S.make_cfg(use_attention=use_attention)
+    head = ("att_learner", 3) if use_attention else ("linear_mapper", 1)
+    last = "att_learner.v_map.weight" if use_attention else "linear_mapper.weight"
+    for cls, tail, n_par, n_keys in ((MPTI_SelfAtten, [("proj", 2)], 34 + head[1], 64 + head[1]),
+                                     (ProtoNet, [], 32 + head[1], 62 + head[1])):
+        m = cls(SimpleNamespace(**cfg))
+        names = [n for n, _ in m.named_parameters()]
+        keys = list(m.state_dict())
+        assert [(k, len(list(g))) for k, g in groupby(n.split(".")[0] for n in names)] == \
+            [("encoder", 24), ("base_learner", 8), head] + tail
+        assert len(names) == n_par and len(keys) == n_keys
+        assert names[0] == keys[0] == "encoder.edge_convs.0.layer.0.weight"
+        assert names[-1] == keys[-1] == ("proj.bias" if tail else last)
+
+
 @pytest.mark.gpu
 def test_learner_from_checkpoint_matches_direct_load_and_graphs_follow(tmp_path):
     from r3dfsseg_amd.episode_graph import EpisodeGraphs
