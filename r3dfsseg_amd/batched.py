@@ -83,12 +83,8 @@ class EpisodeBatchRunner:
         m = self.model
         m._lp_force = False
         self.rec_index.fill_(2 * self.n_done)
-        saved = T.bn_recorder
-        T.bn_recorder = self.bn_records
-        try:
+        with T.recording(self.bn_records):
             out = explicit_train_batch(m, batch, grad_sink, loss_weight)
-        finally:
-            T.bn_recorder = saved
         self._count(backward=True)
         self.n_done += batch.E
         return out
@@ -144,7 +140,7 @@ class BatchGraph:
         self.slot = slot
         self.stream = torch.cuda.Stream()
         lib = _lib.load()
-        saved_slot, saved_rec = m._slot, T.bn_recorder
+        saved_slot = m._slot
         buffers = {k: v.clone() for k, v in m.named_buffers()}  # warm-up passes must not count in the running statistics
         sink_backup = [g.clone() for g in grad_sink]
         counters_backup = runner.counters.clone()
@@ -152,21 +148,21 @@ class BatchGraph:
         try:
             m._slot = slot
             m._lp_force = False
-            T.bn_recorder = runner.bn_records
-            cur = torch.cuda.current_stream()
-            self.stream.wait_stream(cur)
-            with torch.cuda.stream(self.stream):
-                for _ in range(2):  # eager warm-up on the capture stream: allocations, head buffers, the W scratch
+            with T.recording(runner.bn_records):
+                cur = torch.cuda.current_stream()
+                self.stream.wait_stream(cur)
+                with torch.cuda.stream(self.stream):
+                    for _ in range(2):  # eager warm-up on the capture stream: allocations, head buffers, the W scratch
+                        self._once(grad_sink, loss_weight)
+                cur.wait_stream(self.stream)
+                torch.cuda.synchronize()
+                self.graph = torch.cuda.CUDAGraph(keep_graph=True)
+                with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
                     self._once(grad_sink, loss_weight)
-            cur.wait_stream(self.stream)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
-                self._once(grad_sink, loss_weight)
-            self.graph.instantiate()
+                self.graph.instantiate()
         finally:
             lib.r3d_set_wpack_in_capture(old)
-            m._slot, T.bn_recorder = saved_slot, saved_rec
+            m._slot = saved_slot
         with torch.no_grad():
             for k, v in m.named_buffers():
                 v.copy_(buffers[k])

@@ -273,7 +273,7 @@ class EpisodeSlot:
     """State owned by ONE in-flight episode: its head buffers, the device word behind the attention-dropout seed
     and its CG launch budget.  Eager calls use the model's default slot; episode_graph.EpisodeGraphs gives every
     captured hipGraph its own slot so that several episodes can be in flight on separate HIP streams.  (ProtoNet uses
-    the seed word only: it is what train_ops.EncoderTrainFn reads.)"""
+    the seed word only: it is what train_ops.encoder_forward reads.)"""
 
     def __init__(self, sid=0):
         self.id = sid

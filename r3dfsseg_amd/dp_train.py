@@ -175,15 +175,12 @@ class DPTrainer:
             for lp_iters in ((self.model.lp_max_iter,) if conservative else (None, self.model.lp_max_iter)):
                 keep = self.bucket.flat.clone() if lp_iters is None and total is not None else None
                 rec.index_dev.fill_(2 * n_kept)  # (a discarded attempt's records are overwritten by the attempt that is kept)
-                saved, T.bn_recorder = T.bn_recorder, rec
-                try:
+                with T.recording(rec):
                     out = self.model(support_x, support_y, query_x, query_y, gt_support_y=gt_support_y,
                                      gt_query_y=gt_query_y, train=True, logger=logger, support_flag=support_flag,
                                      lp_iters=lp_iters)
                     loss = out[1] + 0.1 * out[2]  # mpti_learner.py:66
                     loss.backward()               # accumulates into the bucket views
-                finally:
-                    T.bn_recorder = saved
                 if self.model.lp_converged(backward=True):
                     break
                 if lp_iters is None:              # drop the inexact gradient again, then the conservative schedule

@@ -106,9 +106,9 @@ class MPTI_SelfAtten(FewShotFeatures):
             if not self.training:
                 raise NotImplementedError("train=True needs model.train(): the training kernels use batch-statistics "
                                           "BatchNorm and attention dropout (models/mpti_learner.py:58-63)")
-            from . import train_ops
-            return train_ops.mpti_train_forward(self, support_x, support_y, query_x, query_y, gt_support_y,
-                                                gt_query_y, logger, support_flag)
+            from . import head_train
+            return head_train.mpti_train_forward(self, support_x, support_y, query_x, query_y, gt_support_y,
+                                                 gt_query_y, logger, support_flag)
         if self.training:
             raise NotImplementedError("train=False on a model in .train() mode (batch-statistics BatchNorm in an "
                                       "inference forward) is not built; call model.eval() first as "

@@ -83,10 +83,8 @@ class MPTILearner_V3(object):
         return (loss, lp.clone(), con.clone(), accuracy, m0.clone(), m1.clone(), m2.clone(), m3.clone())
 
     def _tuple_from_eager(self, loss, data):
-        m = self.model
-        accuracy = point_accuracy(m._train_logits.argmax(dim=1), data[3])
-        lp, con, metrics = m._last_train_parts
-        return (loss, lp, con, accuracy) + tuple(metrics)
+        _, lp, con, logits, metrics = self._trainer.last_outputs[0]
+        return (loss, lp, con, point_accuracy(logits.argmax(dim=1), data[3])) + tuple(metrics.unbind(0))
 
     def train(self, data, logger):
         if self.episode_graphs:

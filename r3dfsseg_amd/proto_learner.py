@@ -84,7 +84,7 @@ class ProtoLearner(object):
         b = self._batch(datas)
         if not self.model.use_attention:
             raise NotImplementedError("training with use_attention=False (the linear mapper) is not built: the training "
-                                      "encoder (train_ops.EncoderTrainFn) needs the attention learner")
+                                      "encoder (train_ops.encoder_forward) needs the attention learner")
         if self._batch_trainer is None:
             self._batch_trainer = ProtoBatchTrainer(self)
         loss, _, _, correct = self._batch_trainer.step(b)

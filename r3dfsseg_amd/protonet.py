@@ -21,7 +21,7 @@ class ProtoNet(FewShotFeatures):
         if self.training:  # the reference's forward under model.train(): the same pair, the loss carries the graph
             if not self.use_attention:
                 raise NotImplementedError("training with use_attention=False (the linear mapper) is not built: the training "
-                                          "encoder (train_ops.EncoderTrainFn) needs the attention learner")
+                                          "encoder (train_ops.encoder_forward) needs the attention learner")
             from . import protonet_train
             return protonet_train.protonet_train_forward(self, support_x, support_y, query_x, query_y)
         logits, loss, _ = self._forward_eval(support_x[None], support_y[None], query_x[None],

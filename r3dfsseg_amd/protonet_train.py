@@ -1,58 +1,61 @@
-"""Training-mode forward of ProtoNet (reference models/protonet.py:245-275 under model.train()) and the autograd edge of its
-head.  Compute lives in libr3d_hip.so (csrc/protonet_train.hip); this file orders launches: one episode under autograd
-(protonet_train_forward), or the E episodes of an optimiser step as ONE launch sequence without the autograd engine
-(explicit_train_batch, ProtoBatchTrainer).  Both run the same head, ProtoHeadFn: one episode is a batch of one."""
-from types import SimpleNamespace
+"""Training-mode forward of ProtoNet (reference models/protonet.py:245-275 under model.train()): its head as plain halves
+(proto_forward / proto_backward; compute in libr3d_hip.so, csrc/protonet_train.hip) and the two callers that order the
+launches: one episode under autograd (protonet_train_forward, through the adapter ProtoHeadFn), or the E episodes of an
+optimiser step as ONE launch sequence without the autograd engine (explicit_train_batch, ProtoBatchTrainer).  Both run
+the same halves: one episode is a batch of one."""
+from collections import namedtuple
 
 import torch
 
 from . import ops, train_ops as T
 from .ops import SegLayout
 
+ProtoSaved = namedtuple("ProtoSaved", "model Z ws labels n_q E ep_rows qfeat support_y")
+
+
+def proto_forward(model, sfeat, qfeat, support_y, query_y, E=1, ep_rows=0):
+    """(sfeat, qfeat) -> (loss (E,), logits (E, n_q, n_way + 1, N), pred (E, n_q, N) int32, saved): the cross entropy of the
+    prototype similarities, each the mean over ITS episode's query points, and their arg-max.  sfeat / qfeat: the support /
+    query rows of episode 0; episode e's rows start e * ep_rows rows further on in the same matrix."""
+    N = model.n_points
+    n_q = query_y.shape[-2]
+    Z, ws = ops.protonet_head_train(sfeat, qfeat, support_y, model.n_way, model.k_shot, N, model.dist_method, n_ep=E,
+                                    feat_ep_rows=ep_rows, n_query_pts=n_q * N)
+    labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous()
+    logits, loss, pred = ops.logits_ce_from_rows(Z, E, n_q, N, model.n_way + 1, labels)
+    return loss, logits, pred, ProtoSaved(model, Z, ws, labels, n_q, E, ep_rows, qfeat, support_y)
+
+
+def proto_backward(saved, gscale):
+    """d(gscale * sum_e loss[e]) / d(features) as ONE (E (S*N + n_q*N), D) matrix, per episode support rows then query
+    rows -- the layout train_ops.encoder_backward consumes."""
+    model, Z, ws, labels, n_q, E, ep_rows, qfeat, support_y = saved
+    dev = Z.device
+    N, D = model.n_points, model.feat_dim
+    S = model.n_way * model.k_shot
+    zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
+    G = ops.ce_grad(Z, zero, 0, E, n_q * N, n_q * N, model.n_way + 1, labels, gscale)
+    assert E == 1 or ep_rows == (S + n_q) * N
+    dfeat = torch.empty(E * (S + n_q) * N, D, device=dev, dtype=torch.float32)
+    ops.protonet_head_bwd(qfeat, support_y, model.n_way, model.k_shot, N, model.dist_method, G, ws, dfeat, dfeat[S * N:],
+                          n_ep=E, feat_ep_rows=ep_rows, dfeat_ep_rows=ep_rows, n_query_pts=n_q * N)
+    return dfeat
+
 
 class ProtoHeadFn(torch.autograd.Function):
-    """(sfeat, qfeat) -> cross-entropy loss (E,) of the prototype similarities, each the mean over ITS episode's query
-    points; leaves logits / arg-max in model._train_logits / model._train_pred (E = 1: all without the episode axis).
-
-    sfeat / qfeat: the support / query rows of episode 0; with ``ctx.E > 1`` (set by the caller) they are views into ONE
-    feature matrix in which episode e's rows start ``ctx.ep_rows`` rows further on.  backward writes both feature
-    gradients into ONE (E (S*N + n_q*N), D) matrix, per episode support rows then query rows -- the layout
-    train_ops.EncoderTrainFn.backward consumes --, leaves it in ``ctx.dfeat_full`` and returns it whole (E > 1) or as its
-    two row ranges."""
+    """The autograd adapter of proto_forward / proto_backward for ONE episode: (sfeat, qfeat) -> loss (0-d).  The logits,
+    which carry no gradient, wait in ``model._train_out`` for protonet_train_forward."""
 
     @staticmethod
     def forward(ctx, sfeat, qfeat, model, support_y, query_y):
-        E = getattr(ctx, "E", 1)
-        ep_rows = getattr(ctx, "ep_rows", 0)
-        N = model.n_points
-        n_q = query_y.shape[-2]
-        Z, ws = ops.protonet_head_train(sfeat, qfeat, support_y, model.n_way, model.k_shot, N, model.dist_method, n_ep=E,
-                                        feat_ep_rows=ep_rows, n_query_pts=n_q * N)
-        labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous()
-        logits, loss, pred = ops.logits_ce_from_rows(Z, E, n_q, N, model.n_way + 1, labels)
-        if E == 1:
-            logits, loss, pred = logits[0], loss[0], pred[0]
-        ctx.model, ctx.Z, ctx.ws, ctx.labels, ctx.n_q, ctx.E, ctx.ep_rows = model, Z, ws, labels, n_q, E, ep_rows
-        ctx.qfeat, ctx.support_y = qfeat, support_y
-        model._train_logits, model._train_pred = logits, pred
-        return loss
+        loss, logits, pred, ctx.saved = proto_forward(model, sfeat, qfeat, support_y, query_y)
+        model._train_out, ctx.rows = (logits[0], pred[0]), sfeat.shape[0]
+        return loss[0]
 
     @staticmethod
     def backward(ctx, gloss):
-        model, Z, n_q, E, ep_rows = ctx.model, ctx.Z, ctx.n_q, ctx.E, ctx.ep_rows
-        dev = Z.device
-        N, D = model.n_points, model.feat_dim
-        S = model.n_way * model.k_shot
-        zero = torch.zeros(1, device=dev, dtype=torch.int32)  # (no prototype rows in front of the query rows)
-        G = ops.ce_grad(Z, zero, 0, E, n_q * N, n_q * N, model.n_way + 1, ctx.labels, gloss)
-        assert E == 1 or ep_rows == (S + n_q) * N
-        dfeat = torch.empty(E * (S + n_q) * N, D, device=dev, dtype=torch.float32)
-        ops.protonet_head_bwd(ctx.qfeat, ctx.support_y, model.n_way, model.k_shot, N, model.dist_method, G, ctx.ws, dfeat,
-                              dfeat[S * N:], n_ep=E, feat_ep_rows=ep_rows, dfeat_ep_rows=ep_rows, n_query_pts=n_q * N)
-        ctx.dfeat_full = dfeat  # (explicit_train_batch takes the whole buffer)
-        if E > 1:
-            return dfeat, None, None, None, None
-        return dfeat[:S * N], dfeat[S * N:], None, None, None
+        dfeat = proto_backward(ctx.saved, gloss)
+        return dfeat[:ctx.rows], dfeat[ctx.rows:], None, None, None
 
 
 def protonet_train_forward(model, support_x, support_y, query_x, query_y):
@@ -69,7 +72,7 @@ def protonet_train_forward(model, support_x, support_y, query_x, query_y):
         qfeat.retain_grad()
         model._trace.update(sfeat=sfeat, qfeat=qfeat)
     loss = ProtoHeadFn.apply(sfeat, qfeat, model, support_y, query_y)
-    return model._train_logits, loss
+    return model._train_out[0], loss
 
 
 def explicit_train_batch(model, batch, grad_sink):
@@ -80,16 +83,12 @@ def explicit_train_batch(model, batch, grad_sink):
     gradient -- summed over the E episodes where it is produced -- ADDED into grad_sink[i].  Per episode the same kernels
     and results as protonet_train_forward + loss.backward(), episode after episode.
     Returns (loss (E,), logits (E, n_q, n_way + 1, N), pred (E, n_q, N) int32, correct (E,) int32)."""
-    E, N = batch.E, model.n_points
-    Q = batch.query_x.shape[1]
-
     def head(feat, seg):
-        ctx = SimpleNamespace(E=E, ep_rows=seg.ep_rows)
-        loss = ProtoHeadFn.forward(ctx, feat, feat[seg.rows_a:], model, batch.support_y, batch.query_y).reshape(E)
-        logits, pred = model._train_logits.reshape(E, Q, model.n_way + 1, N), model._train_pred.reshape(E, Q, N)
+        loss, logits, pred, saved = proto_forward(model, feat, feat[seg.rows_a:], batch.support_y, batch.query_y, batch.E,
+                                                  seg.ep_rows)
         correct = ops.count_correct(pred, batch.query_y)
-        ProtoHeadFn.backward(ctx, torch.ones((), device=feat.device))  # d(step loss) / d(loss_e) = 1 for every episode
-        return (loss, logits, pred, correct), ctx.dfeat_full, []
+        dfeat = proto_backward(saved, torch.ones((), device=feat.device))  # d(step loss) / d(loss_e) = 1 for every episode
+        return (loss, logits, pred, correct), dfeat, []
 
     return T.explicit_encoder_step(model, batch, grad_sink, head)
 
@@ -120,11 +119,8 @@ class ProtoBatchTrainer:
         assert batch.E <= self.max_episodes
         self.model.train()
         self.bucket.zero_()
-        saved, T.bn_recorder = T.bn_recorder, self.bn_records
-        try:
+        with T.recording(self.bn_records):
             out = explicit_train_batch(self.model, batch, self.views)
-        finally:
-            T.bn_recorder = saved
         self.bucket.all_reduce_mean(batch.E)
         # the running statistics move only now that the step is known to be applied, in the order E single calls would
         # move them: episode after episode, support call then query call

@@ -1,10 +1,12 @@
 """Training-mode launch orchestration (forward with batch-statistics BatchNorm + backward).
 
-Two torch.autograd.Function objects wrap the HIP kernels so that the reference's
-``loss.backward(); optimizer.step()`` (models/mpti_learner.py:68-70) works unchanged:
-``EncoderTrainFn`` (DGCNN + BaseLearner + SelfAttention, i.e. getFeatures, models/mpti.py:579-589)
-and, in head_train.py, the transductive head with its losses.  Nothing here computes: every tensor
-operation is a call into libr3d_hip.so; torch provides memory, the autograd graph edge and Adam.
+The training step is written as plain halves: ``encoder_forward`` / ``encoder_backward`` here (DGCNN + BaseLearner +
+SelfAttention, i.e. getFeatures, models/mpti.py:579-589) and a ``*_forward`` / ``*_backward`` pair per head in
+head_train.py, contrast.py and protonet_train.py.  Two callers run them: ``explicit_encoder_step`` calls the halves one
+after the other (the launch sequence the batched and captured paths freeze), and thin torch.autograd.Function adapters
+(``EncoderTrainFn`` here, one per head there) hang the same halves into the autograd graph of ONE episode so that the
+reference's ``loss.backward(); optimizer.step()`` (models/mpti_learner.py:68-70) works unchanged.  Nothing here computes:
+every tensor operation is a call into libr3d_hip.so; torch provides memory, the autograd graph edge and Adam.
 
 Everything works on a BATCH OF E EPISODES laid out as ops.SegLayout describes (E = 1: the reference's schedule, one
 episode per step): kNN, every GEMM, the attention and the edge passes are ONE launch over all E (S + Q) clouds, while
@@ -13,8 +15,9 @@ records the running statistics in the reference's order -- episode after episode
 segment's statistics, and with them every per-episode result of the forward pass, are bit for bit the same whether
 the episode runs alone or inside a batch (the kernels partition their reductions by the segment, not by the batch).
 """
+import contextlib
 import ctypes
-from types import SimpleNamespace
+from collections import namedtuple
 
 import torch
 
@@ -56,30 +59,30 @@ class BNRecorder:
                 bnmod.num_batches_tracked += 2 * n_episodes
 
 
-bn_recorder = None  # set by the owner of a deferred sequence (episode_graph.EpisodeGraphs, batched.EpisodeBatchRunner)
+bn_recorder = None  # the BNRecorder of the running launch sequence (recording(); episode_graph.EpisodeGraphs sets it at capture)
 
 
-class deferred_running_stats:
+@contextlib.contextmanager
+def recording(rec):
+    """``with recording(rec): <training forward>``: every BatchNorm call inside records its batch statistics in `rec`
+    (BNRecorder) instead of updating the running statistics; the recorder set before is back in place afterwards."""
+    global bn_recorder
+    saved, bn_recorder = bn_recorder, rec
+    try:
+        yield rec
+    finally:
+        bn_recorder = saved
+
+
+def deferred_running_stats(model):
     """``with deferred_running_stats(model) as rec: <training forward of ONE episode>`` records the episode's BatchNorm batch
     statistics instead of updating the running statistics; ``rec.apply(1)`` afterwards folds them in.  The eager
     one-episode schedule runs an attempt that may be discarded (CG launch budget, 201-NN overflow, FPS time-out) and
     redone on the conservative schedule: only the attempt that is kept may count in the running statistics."""
-
-    def __init__(self, model):
-        self.model = model
-
-    def __enter__(self):
-        global bn_recorder
-        rec = self.model.__dict__.get("_bn_rec1")
-        if rec is None:
-            rec = self.model.__dict__["_bn_rec1"] = BNRecorder(1, next(self.model.parameters()).device)
-        self.saved, bn_recorder = bn_recorder, rec
-        return rec
-
-    def __exit__(self, *exc):
-        global bn_recorder
-        bn_recorder = self.saved
-        return False
+    rec = model.__dict__.get("_bn_rec1")
+    if rec is None:
+        rec = model.__dict__["_bn_rec1"] = BNRecorder(1, next(model.parameters()).device)
+    return recording(rec)
 
 
 def _f(n, dev):
@@ -322,136 +325,130 @@ def edgeconv_train_bwd(saved, dout, B, N, dx_acc):
 
 
 # ----------------------------------------------------------------------------- encoder
-class EncoderTrainFn(torch.autograd.Function):
-    """getFeatures in training mode.  forward(x (B,C_in,N), model, seed, *params) -> feat (B*N, feat_dim):
-    [level1 (64) | attention (output_dim) | base].  Training needs the attention (model.att_learner).
+EncoderSaved = namedtuple("EncoderSaved", "model seg seed p_drop seed_dev ec mlp base cat level2 qkv lse feat aws")
 
-    ``ctx.seg`` (ops.SegLayout, set by the caller before forward; default: the B clouds are one getFeatures call) says
-    which clouds are which episode's support / query call.  The two getFeatures calls of every episode of the batch
-    (mpti.py:434,436) go through ONE launch sequence: kNN, every GEMM and the attention see all clouds in one grid,
-    every BatchNorm keeps the statistics of the calls apart (and updates / records them in the reference's order), the
-    attention dropout of episode e draws the mask of seed + 2 e, and backward returns the SUM of all calls' parameter
-    gradients."""
 
-    @staticmethod
-    def forward(ctx, x, model, seed, *params):
-        enc, base, att = model.encoder, model.base_learner, model.att_learner
-        lib = _lib.load()
-        B, _, N = x.shape
-        M = B * N
-        dev = x.device
-        seg = getattr(ctx, "seg", None)
-        if seg is None:
-            seg = SegLayout(1, B, 0, N)
-        assert seg.B == B and seg.N == N
-        x_pm, x_cm = ops.input_layouts(x)
-        cat = torch.empty(M, 64 * enc.n_edgeconv, device=dev, dtype=torch.float32)
-        inp, ec_saved = x_pm, []
-        for l in range(enc.n_edgeconv):
-            idx = ops.knn(inp, B, N, enc.k, x_cm=x_cm if l == 0 else None)
-            if enc.idx_patch is not None:  # parity tests only (dgcnn.DGCNN.idx_patch)
-                idx = enc.idx_patch(l, idx.view(B, N, enc.k)).view(idx.shape)
-            out = cat[:, 64 * l:64 * (l + 1)]
-            ec_saved.append(edgeconv_train_fwd(inp, idx, enc.edge_convs[l], B, N, out, seg))
-            inp = out
-        h, mlp_saved = cat, []
-        for jn in range(len(enc.conv.layer_dims)):
-            W = enc.conv.layer[3 * jn].weight
-            h, sv = conv_bn_fwd(h, W.reshape(W.shape[0], -1).contiguous(), enc.conv.layer[3 * jn + 1], ops.ACT_LRELU, seg=seg)
-            mlp_saved.append(sv)
-        level2 = h
-        feat = torch.empty(M, model.feat_dim, device=dev, dtype=torch.float32)
-        od = att.out_channel  # head width: feat columns [64, 64 + od), qkv (M, 3 od)
-        ops.copy_cols(cat[:, :64], feat[:, :64])
-        hb, base_saved = level2, []
-        for i, seq in enumerate(base.convs):
-            last = i == base.num_convs - 1
-            W = seq[0].weight
-            hb, sv = conv_bn_fwd(hb, W.reshape(W.shape[0], -1).contiguous(), seq[1], ops.ACT_NONE if last else ops.ACT_RELU,
-                                 bias=seq[0].bias, out=feat[:, 64 + od:] if last else None, seg=seg)
-            base_saved.append(sv)
-        Wqkv, qscale = att._fold()
-        qkv = ops.pointwise_conv(level2, Wqkv, qscale, None, ops.ACT_NONE)
-        lse = torch.empty(M, device=dev, dtype=torch.float32)
-        p_drop = float(att.dropout.p)
-        aws = _f(lib.r3d_attention_ws_words_ep_d(B, N, seg.clouds, od), dev)
-        with _timed("attention"):
-            _lib.check(lib.r3d_attention_fwd_train_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0), _p(lse),
-                                                        p_drop, ctypes.c_uint(seed & 0xffffffff), _p(model._slot.seed_dev),
-                                                        seg.clouds, od, _p(aws), _st()))
-        ctx.model, ctx.dims, ctx.seed_dev, ctx.seg = model, (B, N, seed, p_drop), model._slot.seed_dev, seg
-        model._dbg_idx = [sv[1] for sv in ec_saved]  # neighbour lists of this pass (parity tests inject them into the oracle)
-        if getattr(model, "_trace", None) is not None:  # one entry per getFeatures call
-            for e in range(seg.E):
-                for b0, Bs in ((e * seg.clouds, seg.S), (e * seg.clouds + seg.S, seg.Q)):
-                    if Bs:
-                        model._trace.setdefault("idx", []).append([sv[1][b0:b0 + Bs] for sv in ec_saved])
-                        model._trace.setdefault("argmax", []).append([sv[7][b0 * N:(b0 + Bs) * N] for sv in ec_saved])
-        ctx.saved = (ec_saved, mlp_saved, base_saved, cat, level2, Wqkv, qkv, lse, feat, aws)
-        return feat
+def encoder_forward(model, x, seed, seg=None):
+    """getFeatures in training mode: x (B, C_in, N) -> (feat (B*N, feat_dim), saved).  feat columns: [level1 (64) |
+    attention (output_dim) | base]; saved (EncoderSaved) is what encoder_backward needs.  Training needs the attention
+    (model.att_learner).
 
-    @staticmethod
-    def backward(ctx, dfeat):
-        model = ctx.model
-        enc, base, att = model.encoder, model.base_learner, model.att_learner
-        B, N, seed, p_drop = ctx.dims
-        seg = ctx.seg
-        ec_saved, mlp_saved, base_saved, cat, level2, Wqkv, qkv, lse, feat, aws = ctx.saved
-        lib = _lib.load()
-        dev = dfeat.device
-        M = B * N
-        dfeat = dfeat.contiguous()
-        class _G(dict):  # gradients keyed by parameter identity
-            def __setitem__(self, k, v):
-                dict.__setitem__(self, id(k), v)
-        g = _G()
-        dlevel2 = torch.zeros(M, level2.shape[1], device=dev, dtype=torch.float32)
-        od = att.out_channel
-        # --- BaseLearner (mpti.py:35-40)
-        d = dfeat[:, 64 + od:]
-        for i in reversed(range(base.num_convs)):
-            seq = base.convs[i]
-            dW, dg, db, dbias, dX = conv_bn_bwd(base_saved[i], d, want_dx=True, dx_acc=dlevel2 if i == 0 else None)
-            g[seq[0].weight] = dW.view_as(seq[0].weight)
-            g[seq[0].bias] = dbias
-            g[seq[1].weight], g[seq[1].bias] = dg, db
-            d = dX
-        # --- SelfAttention (attention.py:39-46)
-        dqkv = torch.empty(M, 3 * od, device=dev, dtype=torch.float32)
-        with _timed("attention_bwd"):  # the forward's workspace, kept since: its packed q | k | v pieces are reused
-            _lib.check(lib.r3d_attention_bwd_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0),
-                                                  _p(dfeat[:, 64:64 + od]), dfeat.stride(0), _p(lse), p_drop,
-                                                  ctypes.c_uint(seed & 0xffffffff), _p(ctx.seed_dev), seg.clouds, od,
-                                                  1.0 / att.temperature, _p(dqkv), 3 * od, _p(aws), 1, _st()))
-        dWqkv = gemm_tn(dqkv, level2)
-        for k, m in enumerate((att.q_map, att.k_map, att.v_map)):
-            g[m.weight] = dWqkv[od * k:od * (k + 1)].reshape(m.weight.shape)
-        Wraw = torch.cat([m.weight.reshape(od, -1) for m in (att.q_map, att.k_map, att.v_map)], 0)
-        conv_acc(dqkv, Wraw.t().contiguous(), dlevel2)
-        # --- point MLP (dgcnn.py:121-122)
-        dcat = torch.zeros(M, cat.shape[1], device=dev, dtype=torch.float32)
-        add_cols(dfeat[:, :64], dcat[:, :64])
-        d = dlevel2
-        for jn in reversed(range(len(mlp_saved))):
-            conv, bnm = enc.conv.layer[3 * jn], enc.conv.layer[3 * jn + 1]
-            dW, dg, db, _, dX = conv_bn_bwd(mlp_saved[jn], d, want_dx=True, dx_acc=dcat if jn == 0 else None)
-            g[conv.weight] = dW.view_as(conv.weight)
-            g[bnm.weight], g[bnm.bias] = dg, db
-            d = dX
-        # --- EdgeConv stack, last layer first (dgcnn.py:115-119)
-        for l in reversed(range(enc.n_edgeconv)):
-            ec = enc.edge_convs[l]
-            dx_acc = dcat[:, 64 * (l - 1):64 * l] if l > 0 else None
-            dW1, dg1, db1, dW2, dg2, db2 = edgeconv_train_bwd(ec_saved[l], dcat[:, 64 * l:64 * (l + 1)], B, N, dx_acc)
-            g[ec.layer[0].weight], g[ec.layer[1].weight], g[ec.layer[1].bias] = dW1, dg1, db1
-            g[ec.layer[3].weight], g[ec.layer[4].weight], g[ec.layer[4].bias] = dW2, dg2, db2
-        ctx.saved = None
-        return (None, None, None) + tuple(g.get(id(p)) for p in ctx.param_list)
+    `seg` (ops.SegLayout; None: the B clouds are one getFeatures call) says which clouds are which episode's support /
+    query call.  The two getFeatures calls of every episode of the batch (mpti.py:434,436) go through ONE launch
+    sequence: kNN, every GEMM and the attention see all clouds in one grid, every BatchNorm keeps the statistics of the
+    calls apart (and updates / records them in the reference's order), the attention dropout of episode e draws the mask
+    of seed + 2 e, and the backward returns the SUM of all calls' parameter gradients."""
+    enc, base, att = model.encoder, model.base_learner, model.att_learner
+    lib = _lib.load()
+    B, _, N = x.shape
+    M = B * N
+    dev = x.device
+    if seg is None:
+        seg = SegLayout(1, B, 0, N)
+    assert seg.B == B and seg.N == N
+    x_pm, x_cm = ops.input_layouts(x)
+    cat = torch.empty(M, 64 * enc.n_edgeconv, device=dev, dtype=torch.float32)
+    inp, ec_saved = x_pm, []
+    for l in range(enc.n_edgeconv):
+        idx = ops.knn(inp, B, N, enc.k, x_cm=x_cm if l == 0 else None)
+        if enc.idx_patch is not None:  # parity tests only (dgcnn.DGCNN.idx_patch)
+            idx = enc.idx_patch(l, idx.view(B, N, enc.k)).view(idx.shape)
+        out = cat[:, 64 * l:64 * (l + 1)]
+        ec_saved.append(edgeconv_train_fwd(inp, idx, enc.edge_convs[l], B, N, out, seg))
+        inp = out
+    h, mlp_saved = cat, []
+    for jn in range(len(enc.conv.layer_dims)):
+        W = enc.conv.layer[3 * jn].weight
+        h, sv = conv_bn_fwd(h, W.reshape(W.shape[0], -1).contiguous(), enc.conv.layer[3 * jn + 1], ops.ACT_LRELU, seg=seg)
+        mlp_saved.append(sv)
+    level2 = h
+    feat = torch.empty(M, model.feat_dim, device=dev, dtype=torch.float32)
+    od = att.out_channel  # head width: feat columns [64, 64 + od), qkv (M, 3 od)
+    ops.copy_cols(cat[:, :64], feat[:, :64])
+    hb, base_saved = level2, []
+    for i, seq in enumerate(base.convs):
+        last = i == base.num_convs - 1
+        W = seq[0].weight
+        hb, sv = conv_bn_fwd(hb, W.reshape(W.shape[0], -1).contiguous(), seq[1], ops.ACT_NONE if last else ops.ACT_RELU,
+                             bias=seq[0].bias, out=feat[:, 64 + od:] if last else None, seg=seg)
+        base_saved.append(sv)
+    Wqkv, qscale = att._fold()
+    qkv = ops.pointwise_conv(level2, Wqkv, qscale, None, ops.ACT_NONE)
+    lse = torch.empty(M, device=dev, dtype=torch.float32)
+    p_drop = float(att.dropout.p)
+    aws = _f(lib.r3d_attention_ws_words_ep_d(B, N, seg.clouds, od), dev)
+    with _timed("attention"):
+        _lib.check(lib.r3d_attention_fwd_train_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0), _p(lse),
+                                                    p_drop, ctypes.c_uint(seed & 0xffffffff), _p(model._slot.seed_dev),
+                                                    seg.clouds, od, _p(aws), _st()))
+    model._dbg_idx = [sv[1] for sv in ec_saved]  # neighbour lists of this pass (parity tests inject them into the oracle)
+    if getattr(model, "_trace", None) is not None:  # one entry per getFeatures call
+        for e in range(seg.E):
+            for b0, Bs in ((e * seg.clouds, seg.S), (e * seg.clouds + seg.S, seg.Q)):
+                if Bs:
+                    model._trace.setdefault("idx", []).append([sv[1][b0:b0 + Bs] for sv in ec_saved])
+                    model._trace.setdefault("argmax", []).append([sv[7][b0 * N:(b0 + Bs) * N] for sv in ec_saved])
+    return feat, EncoderSaved(model, seg, seed, p_drop, model._slot.seed_dev, ec_saved, mlp_saved, base_saved, cat, level2,
+                              qkv, lse, feat, aws)
+
+
+def encoder_backward(saved, dfeat):
+    """dfeat = d(loss) / d(feat), the layout of feat -> the gradients of encoder_params(model), in that order (None where
+    none is produced), summed over the getFeatures calls of the batch."""
+    model, seg = saved.model, saved.seg
+    enc, base, att = model.encoder, model.base_learner, model.att_learner
+    B, N, M = seg.B, seg.N, seg.M
+    ec_saved, mlp_saved, base_saved = saved.ec, saved.mlp, saved.base
+    cat, level2, qkv, lse, feat, aws = saved.cat, saved.level2, saved.qkv, saved.lse, saved.feat, saved.aws
+    lib = _lib.load()
+    dev = dfeat.device
+    dfeat = dfeat.contiguous()
+    g = {}  # gradients keyed by the module's own Parameter objects (a tensor hashes by identity)
+    dlevel2 = torch.zeros(M, level2.shape[1], device=dev, dtype=torch.float32)
+    od = att.out_channel
+    # --- BaseLearner (mpti.py:35-40)
+    d = dfeat[:, 64 + od:]
+    for i in reversed(range(base.num_convs)):
+        seq = base.convs[i]
+        dW, dg, db, dbias, dX = conv_bn_bwd(base_saved[i], d, want_dx=True, dx_acc=dlevel2 if i == 0 else None)
+        g[seq[0].weight] = dW.view_as(seq[0].weight)
+        g[seq[0].bias] = dbias
+        g[seq[1].weight], g[seq[1].bias] = dg, db
+        d = dX
+    # --- SelfAttention (attention.py:39-46)
+    dqkv = torch.empty(M, 3 * od, device=dev, dtype=torch.float32)
+    with _timed("attention_bwd"):  # the forward's workspace, kept since: its packed q | k | v pieces are reused
+        _lib.check(lib.r3d_attention_bwd_ep_d(_p(qkv), 3 * od, B, N, _p(feat[:, 64:64 + od]), feat.stride(0),
+                                              _p(dfeat[:, 64:64 + od]), dfeat.stride(0), _p(lse), saved.p_drop,
+                                              ctypes.c_uint(saved.seed & 0xffffffff), _p(saved.seed_dev), seg.clouds, od,
+                                              1.0 / att.temperature, _p(dqkv), 3 * od, _p(aws), 1, _st()))
+    dWqkv = gemm_tn(dqkv, level2)
+    for k, m in enumerate((att.q_map, att.k_map, att.v_map)):
+        g[m.weight] = dWqkv[od * k:od * (k + 1)].reshape(m.weight.shape)
+    Wraw = torch.cat([m.weight.reshape(od, -1) for m in (att.q_map, att.k_map, att.v_map)], 0)
+    conv_acc(dqkv, Wraw.t().contiguous(), dlevel2)
+    # --- point MLP (dgcnn.py:121-122)
+    dcat = torch.zeros(M, cat.shape[1], device=dev, dtype=torch.float32)
+    add_cols(dfeat[:, :64], dcat[:, :64])
+    d = dlevel2
+    for jn in reversed(range(len(mlp_saved))):
+        conv, bnm = enc.conv.layer[3 * jn], enc.conv.layer[3 * jn + 1]
+        dW, dg, db, _, dX = conv_bn_bwd(mlp_saved[jn], d, want_dx=True, dx_acc=dcat if jn == 0 else None)
+        g[conv.weight] = dW.view_as(conv.weight)
+        g[bnm.weight], g[bnm.bias] = dg, db
+        d = dX
+    # --- EdgeConv stack, last layer first (dgcnn.py:115-119)
+    for l in reversed(range(enc.n_edgeconv)):
+        ec = enc.edge_convs[l]
+        dx_acc = dcat[:, 64 * (l - 1):64 * l] if l > 0 else None
+        dW1, dg1, db1, dW2, dg2, db2 = edgeconv_train_bwd(ec_saved[l], dcat[:, 64 * l:64 * (l + 1)], B, N, dx_acc)
+        g[ec.layer[0].weight], g[ec.layer[1].weight], g[ec.layer[1].bias] = dW1, dg1, db1
+        g[ec.layer[3].weight], g[ec.layer[4].weight], g[ec.layer[4].bias] = dW2, dg2, db2
+    return [g.get(p) for p in encoder_params(model)]
 
 
 def encoder_params(model):
-    ps = list(model.encoder.parameters()) + list(model.base_learner.parameters()) + list(model.att_learner.parameters())
-    return ps
+    return list(model.encoder.parameters()) + list(model.base_learner.parameters()) + list(model.att_learner.parameters())
 
 
 def _adjacent_rows(a, b):
@@ -480,7 +477,7 @@ def next_dropout_seed(model):
 
 
 def next_dropout_seeds(model, E):
-    """The seed argument of ONE launch sequence over E episodes (EncoderTrainFn: episode e draws seed + 2 e) such that
+    """The seed argument of ONE launch sequence over E episodes (encoder_forward: episode e draws seed + 2 e) such that
     episode e gets the seed the e-th of E consecutive next_dropout_seed() calls would hand it."""
     slot = model._slot
     if slot.seed_dev is not None:
@@ -491,46 +488,45 @@ def next_dropout_seeds(model, E):
     return seed
 
 
+class EncoderTrainFn(torch.autograd.Function):
+    """The autograd adapter of encoder_forward / encoder_backward for ONE episode: apply(x, model, seed, seg,
+    *encoder_params(model)) -> feat, or, when seg.Q > 0, the two getFeatures results (support rows, query rows)."""
+
+    @staticmethod
+    def forward(ctx, x, model, seed, seg, *params):
+        feat, ctx.saved = encoder_forward(model, x, seed, seg)
+        if seg is None or seg.Q == 0:
+            return feat
+        assert seg.E == 1
+        return feat[:seg.rows_a], feat[seg.rows_a:]
+
+    @staticmethod
+    def backward(ctx, *dfeats):
+        saved, ctx.saved = ctx.saved, None
+        if len(dfeats) == 2:
+            rows, feat = (saved.seg.rows_a, saved.seg.rows_b), saved.feat
+            dfeats = [d if d is not None else torch.zeros(r, feat.shape[1], device=feat.device, dtype=torch.float32)
+                      for d, r in zip(dfeats, rows)]
+            dfeat = _adjacent_rows(*dfeats)  # a head that wrote both into one matrix: no copy
+            if dfeat is None:
+                dfeat = torch.cat(dfeats, 0)
+        else:
+            dfeat = dfeats[0]
+        return (None, None, None, None) + tuple(encoder_backward(saved, dfeat))
+
+
 def get_features_train(model, x, seed, seg=None):
     """feat (B*N, feat_dim) with gradient edges to the encoder / base / attention parameters.  `seg` (ops.SegLayout with
     E = 1, Q > 0): x holds the support clouds followed by the query clouds of an episode and the two getFeatures
     results are returned (see EncoderTrainFn)."""
-    params = encoder_params(model)
-
-    class _Fn(EncoderTrainFn):
-        @staticmethod
-        def forward(ctx, x, *ps):
-            ctx.param_list = params  # the module's own Parameter objects (gradient dict is keyed by identity)
-            ctx.seg = seg
-            feat = EncoderTrainFn.forward(ctx, x, model, seed, *ps)
-            if seg is None or seg.Q == 0:
-                return feat
-            assert seg.E == 1
-            rows = seg.rows_a
-            ctx.seg_shapes = ((rows, feat.shape[1]), (feat.shape[0] - rows, feat.shape[1]))
-            return feat[:rows], feat[rows:]  # the two getFeatures results
-
-        @staticmethod
-        def backward(ctx, *dfeats):
-            if len(dfeats) == 2:
-                dfeats = [d if d is not None else torch.zeros(sh, device=ctx.saved[3].device, dtype=torch.float32)
-                          for d, sh in zip(dfeats, ctx.seg_shapes)]
-                dfeat = _adjacent_rows(*dfeats)  # a head that wrote both into one matrix: no copy
-                if dfeat is None:
-                    dfeat = torch.cat(dfeats, 0)
-            else:
-                dfeat = dfeats[0]
-            out = EncoderTrainFn.backward(ctx, dfeat)
-            return (None,) + out[3:]
-
-    return _Fn.apply(x, *params)
+    return EncoderTrainFn.apply(x, model, seed, seg, *encoder_params(model))
 
 
 def explicit_encoder_step(model, batch, grad_sink, head):
     """Forward + backward of the E episodes of `batch` (batch.EpisodeBatch) as ONE fixed launch sequence without the
-    autograd engine: EncoderTrainFn's forward half runs with a plain namespace as its ctx, then the model's head, then
-    the backward half, and every parameter gradient -- summed over the E episodes where it is produced -- is ADDED into
-    grad_sink[i] (views in the order of model.parameters(), requires_grad only).
+    autograd engine: encoder_forward, then the model's head, then encoder_backward, and every parameter gradient --
+    summed over the E episodes where it is produced -- is ADDED into grad_sink[i] (views in the order of
+    model.parameters(), requires_grad only).
 
     head(feat, seg) -> (outputs, dfeat, extra): everything between the two halves.  feat (E (S + Q) N, feat_dim) per episode
     (support rows | query rows), seg its ops.SegLayout; dfeat = d(step loss) / d(feat) in the same layout; extra a list of
@@ -540,23 +536,16 @@ def explicit_encoder_step(model, batch, grad_sink, head):
     Q = batch.query_x.shape[1]
     with torch.no_grad():
         seed = next_dropout_seeds(model, E)  # episode e draws what the e-th of E single-episode sequences would
-        params = encoder_params(model)
-        ctx = SimpleNamespace(param_list=params, seg=SegLayout(E, S, Q, N))
-        feat = EncoderTrainFn.forward(ctx, batch.x_all.view(E * (S + Q), model.in_channels, N), model, seed)
-        outputs, dfeat, extra = head(feat, ctx.seg)
+        seg = SegLayout(E, S, Q, N)
+        feat, saved = encoder_forward(model, batch.x_all.view(E * (S + Q), model.in_channels, N), seed, seg)
+        outputs, dfeat, extra = head(feat, seg)
         assert dfeat.shape[0] == feat.shape[0]
-        grads = EncoderTrainFn.backward(ctx, dfeat)[3:]
+        grads = encoder_backward(saved, dfeat)
         index = {id(p): i for i, p in enumerate(q for q in model.parameters() if q.requires_grad)}
         dst, src = [], []
-        for p, g in list(zip(params, grads)) + extra:
+        for p, g in list(zip(encoder_params(model), grads)) + extra:
             if g is not None:
                 dst.append(grad_sink[index[id(p)]])
                 src.append(g.reshape(p.shape))
         torch._foreach_add_(dst, src)
     return outputs
-
-
-def mpti_train_forward(model, support_x, support_y, query_x, query_y, gt_support_y, gt_query_y, logger, support_flag):
-    from . import head_train
-    return head_train.mpti_train_forward(model, support_x, support_y, query_x, query_y, gt_support_y, gt_query_y, logger,
-                                         support_flag)

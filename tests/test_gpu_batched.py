@@ -111,12 +111,10 @@ def test_batched_features_are_bitwise_those_of_the_single_episode():
         T.update_running_stats = False
         try:
             for ep in eps:
-                c = SimpleNamespace(param_list=T.encoder_params(m), seg=SegLayout(1, Sn, Q, N))
                 x = torch.cat((ep[0].reshape(Sn, -1, N), ep[2]), 0)
-                singles.append(T.EncoderTrainFn.forward(c, x, m, 0).clone())
+                singles.append(T.encoder_forward(m, x, 0, SegLayout(1, Sn, Q, N))[0].clone())
             b = EpisodeBatch.from_episodes(eps)
-            c = SimpleNamespace(param_list=T.encoder_params(m), seg=SegLayout(3, Sn, Q, N))
-            feat = T.EncoderTrainFn.forward(c, b.x_all.view(3 * (Sn + Q), -1, N), m, 0)
+            feat = T.encoder_forward(m, b.x_all.view(3 * (Sn + Q), -1, N), 0, SegLayout(3, Sn, Q, N))[0]
         finally:
             T.update_running_stats = True
     rows = (Sn + Q) * N

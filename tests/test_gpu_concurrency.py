@@ -141,12 +141,10 @@ def test_training_kernels_are_not_disturbed_by_attention_on_another_stream():
 
     def victim():
         with torch.cuda.stream(sa), torch.no_grad():
-            c = SimpleNamespace(param_list=T.encoder_params(m), seg=SegLayout(1, Sn, B - Sn, N))
-            feat = T.EncoderTrainFn.forward(c, x_all, m, 11)
-            cc = SimpleNamespace()
-            closs = contrast.ContrastFn.forward(cc, feat[:Sn * N], m.proj.weight, m.proj.bias, m, ep[1], ep[10])
-            dc = contrast.ContrastFn.backward(cc, torch.ones((), device="cuda"))[:3]
-            grads = T.EncoderTrainFn.backward(c, R)[3:]
+            feat, saved = T.encoder_forward(m, x_all, 11, SegLayout(1, Sn, B - Sn, N))
+            closs, csaved = contrast.contrast_forward(m, feat[:Sn * N], m.proj.weight, m.proj.bias, ep[1], ep[10])
+            dc = contrast.contrast_backward(csaved, torch.ones((), device="cuda"), Sn * N)
+            grads = T.encoder_backward(saved, R)
             res = [feat.clone(), closs.clone()] + [g.clone() for g in dc] + [g.clone() for g in grads if g is not None]
         return res
 

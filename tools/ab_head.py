@@ -18,17 +18,14 @@ m.cuda().train()
 m.att_learner.dropout.p = 0.0
 Sn, N = cfg["n_way"] * cfg["k_shot"], cfg["pc_npts"]
 with torch.no_grad():
-    pass
-    c = SimpleNamespace(param_list=T.encoder_params(m))
-    sf = T.EncoderTrainFn.forward(c, ep[0].reshape(Sn, -1, N), m, 0).clone()
-    c = SimpleNamespace(param_list=T.encoder_params(m))
-    qf = T.EncoderTrainFn.forward(c, ep[2], m, 0).clone()
+    sf = T.encoder_forward(m, ep[0].reshape(Sn, -1, N), 0)[0].clone()
+    qf = T.encoder_forward(m, ep[2], 0)[0].clone()
     m._lp_force = True
 
     def run(sfeat, qfeat):
-        ch = SimpleNamespace()
-        loss = H.HeadLPFn.forward(ch, sfeat, qfeat, m, ep[1], ep[3])
-        dsf, dqf = H.HeadLPFn.backward(ch, torch.ones((), device="cuda"))[:2]
+        loss, _, _, saved = H.lp_forward(m, sfeat, qfeat, ep[1], ep[3])
+        dfeat = H.lp_backward(saved, torch.ones((), device="cuda"))
+        dsf, dqf = dfeat[:Sn * N], dfeat[Sn * N:]
         torch.cuda.synchronize()
         return loss.item(), dsf.clone(), dqf.clone(), m._head_buffers(qf.shape[0] // N, sf.device).stats_bwd.clone()
 
