@@ -16,7 +16,7 @@ running-statistics records (applied only when the step is kept), the per-step so
 forward over batches."""
 import torch
 
-from . import ops, train_ops as T
+from . import _lib, captured, ops, train_ops as T
 from .batch import EpisodeBatch
 from .head_train import explicit_train_batch
 
@@ -35,6 +35,7 @@ class EpisodeBatchRunner:
         self.counters = torch.zeros(4, device=dev, dtype=torch.int64)
         self._pinned = torch.zeros(4, dtype=torch.int64).pin_memory()
         self.n_done = 0  # episodes of the running step
+        self._graph = None  # BatchGraph of the last batch shape that went through train_batch_graph
 
     # ------------------------------------------------------------------ status
     def _count(self, backward):
@@ -63,11 +64,19 @@ class EpisodeBatchRunner:
 
     # ------------------------------------------------------------------ training
     def train_batch_graph(self, batch, grad_sink, loss_weight=0.1):
-        """train_batch through a captured hipGraph of the batch's shape (captured on first use; BatchGraph).  Same results."""
+        """train_batch through a captured hipGraph of the batch's shape (captured on first use; BatchGraph).  Same results.
+        A stack that cannot capture this sequence keeps launching it eagerly: ``_graph`` is None after such a call."""
         assert self.n_done + batch.E <= self.max_episodes
-        g = self.__dict__.get("_graph")
+        g = self._graph
         if g is None or not g.matches(batch):
-            g = self.__dict__["_graph"] = BatchGraph(self, batch, grad_sink, loss_weight)
+            try:
+                g = self._graph = BatchGraph(self, batch, grad_sink, loss_weight)
+            except Exception as exc:  # noqa: BLE001 -- whatever the capture ran into, the eager path is the same computation
+                import warnings
+                warnings.warn("batch graph capture failed (%r): the batched step stays on eager launches" % (exc,))
+                self._graph = None
+                torch.cuda.synchronize()
+                return self.train_batch(batch, grad_sink, loss_weight)
             self._graph_sink = [t.data_ptr() for t in grad_sink]
         assert self._graph_sink == [t.data_ptr() for t in grad_sink], "the captured batch writes into the sink it was captured with"
         self.rec_index.fill_(2 * self.n_done)
@@ -108,19 +117,16 @@ class BatchGraph:
     """The training launch sequence of ONE batch shape (head_train.explicit_train_batch: ~450 launches for 32 episodes)
     frozen into a hipGraph and replayed once per step: the same kernels with the same arguments in the same order, so the
     same results bit for bit (tests/test_gpu_batched.py), without ~450 host launch calls per step and without the queue
-    running dry behind the step's host wait (status words, Adam).  What a frozen sequence needs (as episode_graph.py):
+    running dry behind the step's host wait (status words, Adam).  What a frozen sequence needs (captured.py):
       * inputs live in static buffers (the step's episodes are copied in: 29 MB at workload S, 32 episodes);
       * the attention-dropout seed advances in device memory; BatchNorm statistics are recorded (the runner's records);
-      * the CG loops are captured with `lp_budget` iterations, of which only the first 1.5 x (slowly decaying maximum seen)
-        + 8 stay enabled (r3d_graph_set_lp_budget: disabled kernel nodes are empty); a step that needs more reports "not
-        converged" through the runner's counters like any other miss, and the trainer redoes it eagerly;
+      * the CG loops are captured with `lp_budget` iterations (captured.LpBudget); a step that needs more than are enabled
+        reports "not converged" through the runner's counters like any other miss, and the trainer redoes it eagerly;
       * the folded q | k | v matrix is refreshed in place before a replay (the graph holds its address);
       * the packed-weight scratch of the point-wise GEMM may be used by the captured launches (r3d_set_wpack_in_capture):
         this graph is the only user of its stream's scratch while it replays."""
 
     def __init__(self, runner, example, grad_sink, loss_weight=0.1, lp_budget=None):
-        import ctypes
-        from . import _lib
         from .mpti import EpisodeSlot
         self.runner, self.model = runner, runner.model
         m = self.model
@@ -131,9 +137,7 @@ class BatchGraph:
         self.batch = EpisodeBatch(self._clone_x(example.support_x), example.support_y.clone(), self._clone_x(example.query_x),
                                   example.query_y.clone(), clone(example.gt_support_y), clone(example.gt_query_y),
                                   clone(example.support_flag))
-        self.lp_budget = int(lp_budget if lp_budget is not None else min(m.lp_max_iter, 96))
-        self.active_budget = self.lp_budget
-        self._mx_decay = 0
+        self.budget = captured.LpBudget(lp_budget if lp_budget is not None else min(m.lp_max_iter, 96))
         slot = EpisodeSlot(7000 + self.E)
         slot.fixed_budget = self.lp_budget
         slot.seed_dev = torch.full((1,), 104729, device=dev, dtype=torch.int32)
@@ -141,38 +145,18 @@ class BatchGraph:
         self.stream = torch.cuda.Stream()
         lib = _lib.load()
         saved_slot = m._slot
-        buffers = {k: v.clone() for k, v in m.named_buffers()}  # warm-up passes must not count in the running statistics
-        sink_backup = [g.clone() for g in grad_sink]
-        counters_backup = runner.counters.clone()
-        old = lib.r3d_set_wpack_in_capture(1)
-        try:
-            m._slot = slot
-            m._lp_force = False
-            with T.recording(runner.bn_records):
-                cur = torch.cuda.current_stream()
-                self.stream.wait_stream(cur)
-                with torch.cuda.stream(self.stream):
-                    for _ in range(2):  # eager warm-up on the capture stream: allocations, head buffers, the W scratch
-                        self._once(grad_sink, loss_weight)
-                cur.wait_stream(self.stream)
-                torch.cuda.synchronize()
-                self.graph = torch.cuda.CUDAGraph(keep_graph=True)
-                with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
-                    self._once(grad_sink, loss_weight)
-                self.graph.instantiate()
-        finally:
-            lib.r3d_set_wpack_in_capture(old)
-            m._slot = saved_slot
-        with torch.no_grad():
-            for k, v in m.named_buffers():
-                v.copy_(buffers[k])
-            for g, b in zip(grad_sink, sink_backup):
-                g.copy_(b)
-            runner.counters.copy_(counters_backup)
-        n_cg = ctypes.c_int(0)
-        _lib.check(lib.r3d_graph_set_lp_budget(ctypes.c_void_p(self.graph.raw_cuda_graph()),
-                                               ctypes.c_void_p(self.graph.raw_cuda_graph_exec()), self.lp_budget, ctypes.byref(n_cg)))
-        assert n_cg.value > 0, "no CG nodes found in the captured batch"
+        with captured.preserved(m, list(grad_sink) + [runner.counters]):
+            old = lib.r3d_set_wpack_in_capture(1)
+            try:
+                m._slot = slot
+                m._lp_force = False
+                with T.recording(runner.bn_records):  # (the warm-up runs on the capture stream: the W scratch is per stream)
+                    self.graph = captured.capture(lambda: self._once(grad_sink, loss_weight), self.stream,
+                                                  capture_stream=self.stream)
+            finally:
+                lib.r3d_set_wpack_in_capture(old)
+                m._slot = saved_slot
+        self.set_lp_budget(self.lp_budget, force=True)  # (asserts that the capture holds CG nodes at all)
         torch.cuda.synchronize()
 
     @staticmethod
@@ -191,26 +175,15 @@ class BatchGraph:
                 and (batch.support_flag is None) == (b.support_flag is None)
                 and ops.is_point_major_view(batch.support_x) == ops.is_point_major_view(b.support_x))
 
-    def set_lp_budget(self, budget):
-        import ctypes
-        from . import _lib
-        budget = max(1, min(int(budget), self.lp_budget))
-        if budget == self.active_budget:
-            return
-        torch.cuda.current_stream().synchronize()  # never edit an executable graph that is in flight
-        _lib.check(_lib.load().r3d_graph_set_lp_budget(ctypes.c_void_p(self.graph.raw_cuda_graph()),
-                                                       ctypes.c_void_p(self.graph.raw_cuda_graph_exec()), budget, None))
-        self.active_budget = budget
+    lp_budget = property(lambda self: self.budget.captured)
+    active_budget = property(lambda self: self.budget.active)
+
+    def set_lp_budget(self, budget, force=False):
+        self.budget.apply([self.graph], budget, lambda _: torch.cuda.current_stream().synchronize(), force)
 
     def adapt(self, status):
         """The CG budget of the next replays from a finished step's (bad, overflow, iterations, max)."""
-        bad, _, _, mx = status
-        if bad:
-            self._mx_decay = max(self._mx_decay, mx)
-            self.set_lp_budget(self.lp_budget)
-        elif mx > 0:
-            self._mx_decay = max(mx, self._mx_decay - max(1, self._mx_decay // 16))
-            self.set_lp_budget(max(24, 8 * ((self._mx_decay + self._mx_decay // 2 + 8 + 7) // 8)))
+        self.set_lp_budget(self.budget.target(status[0], status[3]))
 
     def replay(self, batch):
         """One training pass of `batch` (same shapes as the example) on the current stream; returns what
@@ -236,5 +209,7 @@ class BatchGraph:
 
 
 def collate(episodes, batch_size):
-    """Episode lists (train or test layout) -> EpisodeBatch objects of up to batch_size episodes."""
+    """Episode lists (train or test layout) -> EpisodeBatch objects of up to batch_size episodes (ready ones pass through)."""
+    if episodes and isinstance(episodes[0], EpisodeBatch):
+        return episodes
     return [EpisodeBatch.from_episodes(episodes[i:i + batch_size]) for i in range(0, len(episodes), batch_size)]

@@ -41,10 +41,17 @@ class FlatGradBucket:
         dev = self.params[0].device
         self.store = torch.zeros(n + 2, dtype=torch.float32, device=dev)
         self.flat = self.store[:n]
-        off = 0
-        for p in self.params:  # p.grad becomes a view into the bucket
-            p.grad = self.flat[off:off + p.numel()].view_as(p)
+        self.views, off = [], 0  # one view per parameter, in parameter order: where every gradient of a step is written
+        for p in self.params:
+            self.views.append(self.flat[off:off + p.numel()].view_as(p))
             off += p.numel()
+        self.bind()
+
+    def bind(self):
+        """p.grad becomes the parameter's view into the bucket: before a backward() that is to accumulate here and before
+        the optimiser reads a step's gradient.  Nothing relies on .grad in between (others may re-point it)."""
+        for p, v in zip(self.params, self.views):
+            p.grad = v
 
     def zero_(self):
         self.flat.zero_()

@@ -54,116 +54,88 @@ class DPTrainer:
     def step(self, episodes, logger=None):
         """episodes: list of train-layout data lists (loader.py:1666-1671) local to this rank.
         Returns the mean (lp_loss + 0.1 contrast) over the local episodes as a device tensor.
-
+        Whatever the schedule: one pass over the local episodes, a redo if it reports a miss, reduce_and_step.
         Fails closed: the optimiser never steps on a gradient from an episode whose CG solves (forward or adjoint) ran
         out of launch budget, whose 201-NN survivor buffer overflowed or whose one-launch FPS timed out.  The status
         words are read after the local episodes and BEFORE the all-reduce (one host wait per step, ~0.3 % of a
         32-episode step); a miss makes this rank redo its episodes of the step on the conservative schedule (full
         budget, exact kernels).  Ranks decide locally: a rank's contribution to the all-reduce is an exact gradient or
-        nothing -- if the conservative schedule fails too, the rank says so in the bucket's failure slot, takes part in
-        the collective like everybody else, and EVERY rank raises after it (no rank is left blocked in an all-reduce)."""
+        nothing -- if the conservative schedule fails too (SolverMiss), the rank says so in the bucket's failure slot,
+        takes part in the collective like everybody else, and EVERY rank raises after it (no rank is left blocked in an
+        all-reduce).  That holds for SolverMiss alone: any other error -- a launch failure, a guard mismatch -- is not
+        recoverable and propagates at once, BEFORE the collective, on the rank that met it; a multi-rank job relies on its
+        launcher to tear the other ranks down."""
         self.model.train()
         self.redone = False
         if self.runner is not None:
-            from .batch import EpisodeBatch
             from .batched import collate
-            batches = episodes if (episodes and isinstance(episodes[0], EpisodeBatch)) else collate(episodes, self.batch_size)
-            n_local = sum(b.E for b in batches)
-            self.bucket.zero_()
-            self.runner.begin_step()
-            total = None
-            outs = []
-            use_graph = self.batch_graph and len(batches) == 1 and batches[0].E == self.batch_size
-            if use_graph and self.runner.__dict__.get("_graph") is None:
-                try:  # capture on first use; a stack that cannot capture this sequence keeps launching it eagerly
-                    from .batched import BatchGraph
-                    sink = [p.grad for p in self.bucket.params]
-                    self.runner._graph = BatchGraph(self.runner, batches[0], sink)
-                    self.runner._graph_sink = [t.data_ptr() for t in sink]
-                    self.bucket.zero_()
-                    self.runner.begin_step()
-                except Exception as exc:  # noqa: BLE001 -- whatever the capture ran into, the eager path is the same computation
-                    import warnings
-                    warnings.warn("batch graph capture failed (%r): the batched step stays on eager launches" % (exc,))
-                    self.batch_graph = use_graph = False
-                    torch.cuda.synchronize()
-                    self.bucket.zero_()
-                    self.runner.begin_step()
-            for b in batches:
-                o = (self.runner.train_batch_graph if use_graph else self.runner.train_batch)(b, [p.grad for p in self.bucket.params])
-                outs += [(o[0][e], o[3][e], o[4][e], o[1][e], o[2][e]) for e in range(b.E)]
-                loss = o[0].sum()
-                total = loss if total is None else total + loss
-            self.last_status = self.runner.step_status()
-            if use_graph:
-                self.runner._graph.adapt(self.last_status)
-            failed, apply_stats = None, self.runner.apply_running_stats
+            pass_fn, episodes = self._batched_pass, collate(episodes, self.batch_size)
+            n_local = sum(b.E for b in episodes)
+        else:
+            pass_fn = self._slots_pass if self.graphs is not None else self._eager_pass
+            n_local = len(episodes)
+        failed, total, outs, apply_stats = None, None, [], None
+        try:
+            total, outs, self.last_status, apply_stats = pass_fn(episodes, logger)
             if self.last_status[0] or self.last_status[1]:
-                eps = [b.episode(e) for b in batches for e in range(b.E)]
-                try:
-                    total, outs, apply_stats = self._eager_pass(eps, logger, conservative=True)
-                except SolverMiss as exc:
-                    failed, apply_stats = exc, None
                 self.redone = True
                 self.n_redone += 1
-            self.last_outputs = outs
-            # (the running statistics only move once the collective has said that no rank failed: an abandoned step leaves
-            # neither Adam nor the BatchNorm buffers touched)
-            self._reduce_and_step(n_local, failed, apply_stats)
-            return total / max(n_local, 1)
-        failed, apply_stats = None, None
-        self.last_outputs = []
-        try:
-            if self.graphs is not None:
-                total = self.graphs.run(episodes, apply_bn=False)
-                bad, overflow, _, _ = self.graphs.step_status()
-                self.n_steps += 1
-                if self.guard_every and self.graphs.n_slots > 1 and self.n_steps % self.guard_every == 0:
-                    wrong = self.graphs.verify_graph_weights()
-                    if wrong:
-                        raise RuntimeError("guard: %d label-propagation edge weights computed beside other streams' kernels "
-                                           "differ from their recomputation on the idle chip" % wrong)
-                if bad or overflow:
-                    self.redone = True
-                    self.n_redone += 1
-                    total, self.last_outputs, apply_stats = self._eager_pass(episodes, logger, conservative=True)
-                else:
-                    n_ep = len(episodes)
-                    apply_stats = lambda: self.graphs.apply_running_stats(n_ep)
-                    torch.sum(self.rows, 0, out=self.bucket.store)
-            else:
-                total, self.last_outputs, apply_stats = self._eager_pass(episodes, logger, conservative=False)
-        except SolverMiss as exc:  # (anything else -- a launch failure, a guard mismatch -- is not recoverable: it propagates)
-            failed, total, apply_stats = exc, torch.zeros((), device=self.bucket.store.device), None
-        self._reduce_and_step(len(episodes), failed, apply_stats)
-        return total / max(len(episodes), 1)
+                if self.runner is not None:
+                    episodes = [b.episode(e) for b in episodes for e in range(b.E)]
+                total, outs, _, apply_stats = self._eager_pass(episodes, logger, conservative=True)
+        except SolverMiss as exc:
+            failed, apply_stats = exc, None
+        self.last_outputs = outs
+        reduce_and_step(self.learner, self.bucket, n_local, failed, apply_stats)
+        return total / max(n_local, 1)
 
-    def _reduce_and_step(self, n_local, failed, apply_stats=None):
-        """The step's ONE collective (gradients + episode count + failure flag), then the BatchNorm running statistics of
-        the step's episodes and Adam -- or, if any rank could not produce an exact gradient, the same error on every rank
-        with neither touched."""
-        n_failed = self.bucket.all_reduce_mean(n_local, failed=failed is not None)
-        if n_failed:
-            raise RuntimeError("training step abandoned on all ranks: %d rank(s) could not solve their episodes exactly%s" % (
-                n_failed, (" (this rank: %s)" % failed) if failed is not None else "")) from failed
-        if apply_stats is not None:
-            apply_stats()
-            D.mark_rank_local_stats(self.model)
-        self.learner.optimizer.step()
-        self.learner.lr_scheduler.step()
+    def _batched_pass(self, batches, logger=None):
+        """Every batch through ONE launch sequence; a step of one batch of batch_size episodes replays it as a hipGraph."""
+        runner = self.runner
+        self.bucket.zero_()
+        runner.begin_step()
+        use_graph = self.batch_graph and len(batches) == 1 and batches[0].E == self.batch_size
+        run = runner.train_batch_graph if use_graph else runner.train_batch
+        total, outs = None, []
+        for b in batches:
+            o = run(b, self.bucket.views)
+            outs += [(o[0][e], o[3][e], o[4][e], o[1][e], o[2][e]) for e in range(b.E)]
+            loss = o[0].sum()
+            total = loss if total is None else total + loss
+        status = runner.step_status()
+        if use_graph and runner._graph is None:  # the capture failed (the runner has warned): eager launches from now on
+            self.batch_graph = False
+        elif use_graph:
+            runner._graph.adapt(status)
+        return total, outs, status, runner.apply_running_stats
+
+    def _slots_pass(self, episodes, logger=None):
+        """One captured hipGraph per episode, n_slots in flight; the slots' gradient rows are summed into the bucket."""
+        total = self.graphs.run(episodes, apply_bn=False)
+        status = self.graphs.step_status()
+        self.n_steps += 1
+        if self.guard_every and self.graphs.n_slots > 1 and self.n_steps % self.guard_every == 0:
+            wrong = self.graphs.verify_graph_weights()
+            if wrong:
+                raise RuntimeError("guard: %d label-propagation edge weights computed beside other streams' kernels "
+                                   "differ from their recomputation on the idle chip" % wrong)
+        if not (status[0] or status[1]):
+            torch.sum(self.rows, 0, out=self.bucket.store)
+        return total, [], status, (lambda: self.graphs.apply_running_stats(len(episodes)))
 
     def sync_running_stats(self):
         """Average the BatchNorm running statistics over the ranks (dist.sync_running_stats): call before an evaluation
         sweep or a checkpoint, so that every rank evaluates / saves the same model."""
         return D.sync_running_stats(self.model)
 
-    def _eager_pass(self, episodes, logger, conservative):
-        """Forward + backward of every episode into the bucket (parameter .grad tensors are views into it).  An attempt
+    def _eager_pass(self, episodes, logger=None, conservative=False):
+        """Forward + backward of every episode into the bucket (parameter .grad tensors are bound to its views).  An attempt
         on the adaptive schedule that misses (CG budget, 201-NN overflow, FPS time-out) is discarded -- its gradient AND
         its BatchNorm statistics -- and the episode is redone on the conservative schedule.  Returns (sum of the losses,
-        per-episode results, a callable that folds the kept attempts' BatchNorm statistics into the running buffers, episode
-        after episode: the caller runs it once the step is known to be kept)."""
+        per-episode results, the status of a pass without a miss (a miss here raises SolverMiss), a callable that folds the
+        kept attempts' BatchNorm statistics into the running buffers: the caller runs it once the step is kept)."""
         from . import train_ops as T
+        self.bucket.bind()
         self.bucket.zero_()
         total = None
         outs = []
@@ -192,5 +164,21 @@ class DPTrainer:
                 raise SolverMiss("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
             total = loss.detach() if total is None else total + loss.detach()
             outs.append((loss.detach(), out[1].detach(), out[2].detach(), out[0].detach(), torch.stack([torch.as_tensor(v, device=loss.device, dtype=torch.float32) for v in out[3:]])))
-        n = len(episodes)
-        return total, outs, (lambda: rec.apply(n))
+        return total, outs, (0, 0, 0, 0), (lambda: rec.apply(len(episodes)))
+
+
+def reduce_and_step(learner, bucket, n_local, failed=None, apply_stats=None):
+    """The tail of every optimiser step (DPTrainer, protonet_train.ProtoBatchTrainer): the step's ONE collective (gradients
+    + episode count + failure flag), then the BatchNorm running statistics of the step's episodes (apply_stats) and Adam
+    on the bucket -- or, if any rank could not produce an exact gradient (`failed`: this rank's SolverMiss), the same
+    error on every rank with neither touched: the running statistics only move once the collective has said so."""
+    n_failed = bucket.all_reduce_mean(n_local, failed=failed is not None)
+    if n_failed:
+        raise RuntimeError("training step abandoned on all ranks: %d rank(s) could not solve their episodes exactly%s" % (
+            n_failed, (" (this rank: %s)" % failed) if failed is not None else "")) from failed
+    if apply_stats is not None:
+        apply_stats()
+        D.mark_rank_local_stats(learner.model)
+    bucket.bind()  # whatever ran since this bucket was filled may have re-pointed .grad: Adam reads THIS step's gradient
+    learner.optimizer.step()
+    learner.lr_scheduler.step()

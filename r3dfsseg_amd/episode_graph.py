@@ -24,18 +24,15 @@ Frozen-sequence consequences, all checked or documented:
     slots would race) and the owner applies the records in episode order after the step -- bit for bit the running
     statistics of the reference's one-episode-at-a-time schedule (tests/test_gpu_graph.py).
 
-The CG launch budget is adaptive without re-capturing: launches after convergence return at once but still cost
-~2.5 us of queue time each, so ``run()`` reads -- one step late, through a pinned buffer, never blocking -- the largest
-iteration count seen and keeps only the CG kernel nodes of the first ``1.5 * max + 8`` iterations enabled
-(``r3d_graph_set_lp_budget``: a disabled node is an empty node).  A replay that needs more reports "not converged"
-through ``check()`` as before, and the budget returns to the captured maximum.
+The CG launch budget is adaptive without re-capturing (captured.LpBudget): launches after convergence return at once but
+still cost ~2.5 us of queue time each, so ``run()`` reads -- one step late, through a pinned buffer, never blocking --
+the largest iteration count seen.  A replay that needs more than is enabled reports "not converged" through ``check()``.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _lib, ops, train_ops
+from . import captured, ops, train_ops
 from .mpti import EpisodeSlot
 
 
@@ -58,36 +55,30 @@ class EpisodeGraphs:
             n = sum(p.numel() for p in self.params)
             self.grad_rows = grad_rows if grad_rows is not None else torch.zeros(n_slots, n, device=dev)
             assert self.grad_rows.shape[0] == n_slots and self.grad_rows.shape[1] >= n
-        if lp_budget is None:  # CG iterations frozen into the graph; the ones beyond the adaptive budget are disabled nodes
-            lp_budget = min(model.lp_max_iter, 200)
-        self.lp_budget = lp_budget          # CG iterations captured into every graph
-        self.active_budget = lp_budget      # ... of which this many are enabled
+        # CG iterations frozen into every graph, and how many of them are enabled
+        self.budget = captured.LpBudget(lp_budget if lp_budget is not None else min(model.lp_max_iter, 200))
         self.adaptive_budget = os.environ.get("R3D_FIXED_LP_BUDGET") is None
         # per slot, per run(): [not converged / FPS time-out, 201-NN overflow, CG iterations (sum), CG iterations (max)]
         self.counters = torch.zeros(n_slots, 4, device=dev, dtype=torch.int32)
         self._probes = []                   # (event, pinned copy of the counters) of the runs not yet accounted for
         self._probe_pool = [torch.zeros(n_slots, 4, dtype=torch.int32).pin_memory() for _ in range(4)]
         self._since_check = [0, 0, 0, 0]    # host totals since the last check(): bad, overflow, iterations, max
-        self._mx_decay = 0                  # slowly decaying maximum of the iteration counts (budget adaptation)
         self.slots = []
         self.ev_start = torch.cuda.Event()
         self.max_episodes = 256             # episodes of one run() the BatchNorm records are sized for
         self.bn_records = train_ops.BNRecorder(self.max_episodes, dev) if train else None
         saved_slot = model._slot
-        buffers = {k: v.clone() for k, v in model.named_buffers()}  # warm-up passes must not leak into BN statistics
         was_training = model.training
         model.train(train)
-        try:
-            for s in range(n_slots):
-                self.slots.append(self._capture(s, example, dev))
-        finally:
-            model._slot = saved_slot
-            train_ops.update_running_stats = True
-            train_ops.bn_recorder = None
-            model.train(was_training)
-        with torch.no_grad():
-            for k, v in model.named_buffers():
-                v.copy_(buffers[k])
+        with captured.preserved(model):
+            try:
+                for s in range(n_slots):
+                    self.slots.append(self._capture(s, example, dev))
+            finally:
+                model._slot = saved_slot
+                train_ops.update_running_stats = True
+                train_ops.bn_recorder = None
+                model.train(was_training)
         self.reset()
         self.counters.zero_()  # the warm-up and capture passes are not episodes of any step
         torch.cuda.synchronize()
@@ -149,42 +140,17 @@ class EpisodeGraphs:
         if self.train:
             self.bn_records.index_dev = sl.ep2
             train_ops.bn_recorder = self.bn_records
-        cur = torch.cuda.current_stream()
-        sl.stream.wait_stream(cur)
-        with torch.cuda.stream(sl.stream):
-            for _ in range(2):  # eager warm-up: allocations, head buffers, lazily initialised library state
-                self._run_once(sl)
-        cur.wait_stream(sl.stream)
-        torch.cuda.synchronize()
-        sl.graph = torch.cuda.CUDAGraph(keep_graph=True)  # the hipGraph_t stays: its nodes are enabled / disabled later
-        # thread-local capture mode: only this thread launches into the capture (no autograd engine threads in the
-        # explicit episode), while other threads -- e.g. the RCCL watchdog of torch.distributed polling its events --
-        # must stay free to call the HIP runtime
-        with torch.cuda.graph(sl.graph, capture_error_mode="thread_local"):
-            self._run_once(sl)
-        sl.graph.instantiate()
+        sl.graph = captured.capture(lambda: self._run_once(sl), sl.stream)
         return sl
 
     # ------------------------------------------------------------------ CG launch budget
+    lp_budget = property(lambda self: self.budget.captured)
+    active_budget = property(lambda self: self.budget.active)
+    budget_for = staticmethod(captured.LpBudget.budget_for)
+
     def set_lp_budget(self, budget):
         """Enable the CG kernel nodes of the first `budget` iterations in every slot's graph, disable the rest."""
-        budget = max(1, min(int(budget), self.lp_budget))
-        if budget == self.active_budget:
-            return
-        lib = _lib.load()
-        for sl in self.slots:
-            sl.stream.synchronize()  # never edit an executable graph that is in flight
-            n_cg = ctypes.c_int(0)
-            _lib.check(lib.r3d_graph_set_lp_budget(ctypes.c_void_p(sl.graph.raw_cuda_graph()),
-                                                   ctypes.c_void_p(sl.graph.raw_cuda_graph_exec()), budget, ctypes.byref(n_cg)))
-            assert n_cg.value > 0, "no CG nodes found in the captured episode"
-        self.active_budget = budget
-
-    @staticmethod
-    def budget_for(mx):
-        """Enabled CG iterations for an observed maximum of `mx`: half as many again plus 8, rounded up to 8, at least 24
-        (convergence is detected inside the last productive launch, so nothing extra is needed for the test itself)."""
-        return max(24, 8 * ((mx + mx // 2 + 8 + 7) // 8))
+        self.budget.apply([sl.graph for sl in self.slots], budget, lambda s: self.slots[s].stream.synchronize())
 
     def _account(self, c):
         """One finished run()'s counters (host copy): totals for check(), launch budget for the next runs."""
@@ -192,12 +158,7 @@ class EpisodeGraphs:
         t = self._since_check
         t[0] += bad; t[1] += ovf; t[2] += its; t[3] = max(t[3], mx)
         self._probe_pool.append(c)
-        if bad > 0:          # a replay did not converge: back to everything that was captured
-            self._mx_decay = max(self._mx_decay, mx)
-            self.set_lp_budget(self.lp_budget)
-        elif self.adaptive_budget and mx > 0:  # the budget follows a slowly decaying maximum, so it can shrink again
-            self._mx_decay = max(mx, self._mx_decay - max(1, self._mx_decay // 16))
-            self.set_lp_budget(self.budget_for(self._mx_decay))
+        self.set_lp_budget(self.budget.target(bad, mx, self.adaptive_budget))
         return bad, ovf, its, mx
 
     def _adapt_budget(self):

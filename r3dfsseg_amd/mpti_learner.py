@@ -105,8 +105,7 @@ class MPTILearner_V3(object):
                                                     bg_pcd_y=bg_pcd_y, support_c=support_c, support_flag=support_flag,
                                                     lp_iters=lp_iters)
                 loss = lp_loss + 0.1 * contrastive_loss
-                # (once a gradient bucket exists the parameters' .grad tensors are views into it: zero them in place)
-                self.optimizer.zero_grad(set_to_none=self._trainer is None)
+                self.optimizer.zero_grad()  # (its own gradients: the trainers bind .grad to their buckets at step time)
                 loss.backward()
             # the CG solves (forward and adjoint) run on a launch budget and the 201-NN / FPS fast paths can report
             # overflow / time-out: never step Adam on an inexact gradient.  One host read per step, where the

@@ -94,19 +94,15 @@ def explicit_train_batch(model, batch, grad_sink):
 
 
 class ProtoBatchTrainer:
-    """What ProtoLearner.train_batch needs around explicit_train_batch: ONE flat gradient bucket (dist.FlatGradBucket: a
-    single all-reduce carries the gradients and the episode count), the deferred BatchNorm running-statistics records and
-    the optimiser step on the mean gradient.
-
-    The parameters' .grad is bound to the bucket's views right before every optimiser step and not relied on in between:
-    ProtoLearner.train() may have run since (its zero_grad() sets .grad to None and its backward() allocates fresh
-    tensors), so a step here never reads another call's gradient and train() never writes into the bucket."""
+    """What ProtoLearner.train_batch needs around explicit_train_batch: ONE flat gradient bucket (dist.FlatGradBucket),
+    ProtoNet's deferred BatchNorm running-statistics records, and the tail every optimiser step shares
+    (dp_train.reduce_and_step: one all-reduce carries the gradients and the episode count; .grad is bound to the bucket's
+    views right before the optimiser step and not relied on in between, so ProtoLearner.train() may run in between)."""
 
     def __init__(self, learner, max_episodes=256):
         from . import dist as D
         self.learner, self.model = learner, learner.model
         self.bucket = D.FlatGradBucket(self.model.parameters())
-        self.views = [p.grad for p in self.bucket.params]
         dev = self.bucket.store.device
         self.max_episodes = max_episodes
         self.bn_records = T.BNRecorder(max_episodes, dev)
@@ -115,19 +111,12 @@ class ProtoBatchTrainer:
     def step(self, batch):
         """One optimiser step on the mean gradient of the batch's episodes (over all ranks' episodes when torch.distributed
         is initialised).  Returns explicit_train_batch's results."""
-        from . import dist as D
+        from .dp_train import reduce_and_step
         assert batch.E <= self.max_episodes
         self.model.train()
         self.bucket.zero_()
         with T.recording(self.bn_records):
-            out = explicit_train_batch(self.model, batch, self.views)
-        self.bucket.all_reduce_mean(batch.E)
-        # the running statistics move only now that the step is known to be applied, in the order E single calls would
-        # move them: episode after episode, support call then query call
-        self.bn_records.apply(batch.E)
-        D.mark_rank_local_stats(self.model)
-        for p, v in zip(self.bucket.params, self.views):
-            p.grad = v
-        self.learner.optimizer.step()
-        self.learner.lr_scheduler.step()
+            out = explicit_train_batch(self.model, batch, self.bucket.views)
+        # (the records apply as E single calls would move the statistics: episode after episode, support then query call)
+        reduce_and_step(self.learner, self.bucket, batch.E, apply_stats=lambda: self.bn_records.apply(batch.E))
         return out

@@ -65,3 +65,40 @@ def test_two_rank_flat_bucket_allreduce():
     for r in (0, 1):
         n_sync, rm, rv = out[r][6]
         assert n_sync == 8 and torch.equal(rm, torch.full((4,), 0.5)) and torch.equal(rv, torch.full((4,), 2.0))
+
+
+def test_bucket_bind_after_the_gradients_were_re_pointed():
+    """FlatGradBucket.views are the bucket's own views, in model.parameters() order; bind() makes every p.grad one of them
+    again after somebody else (a zero_grad(), a fresh backward(), another bucket) re-pointed .grad; all_reduce_mean works
+    on the bucket whatever .grad points at."""
+    from r3dfsseg_amd import dist as D
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(7, 3), torch.nn.Linear(3, 2))
+    params = list(net.parameters())
+    bucket = D.FlatGradBucket(net.parameters())
+    off = 0
+    assert len(bucket.views) == len(params)
+    for p, v in zip(params, bucket.views):
+        assert v.shape == p.shape and v.data_ptr() == bucket.flat.data_ptr() + 4 * off
+        assert p.grad.data_ptr() == v.data_ptr()  # the constructor binds
+        off += p.numel()
+    assert off == bucket.flat.numel()
+    x = [torch.full((2, 7), float(e + 1)) for e in range(2)]
+    for p in params:
+        p.grad = None
+    net(x[0]).sum().backward()  # fresh tensors: nothing of this reaches the bucket
+    want = [p.grad.clone() for p in params]
+    assert all(p.grad.data_ptr() != v.data_ptr() for p, v in zip(params, bucket.views))
+    assert not bucket.flat.any()
+    D.FlatGradBucket(net.parameters())  # (a second bucket re-points .grad as well)
+    bucket.bind()
+    for p, v in zip(params, bucket.views):
+        assert p.grad.data_ptr() == v.data_ptr()
+    bucket.zero_()
+    for xe in x:
+        net(xe).sum().backward()  # accumulates into the bound views
+    assert bucket.all_reduce_mean(2) == 0
+    net.zero_grad()
+    net(x[1]).sum().backward()
+    for p, v, w in zip(params, bucket.views, want):
+        assert torch.allclose(v, (w + p.grad) / 2, rtol=1e-6, atol=1e-7)

@@ -75,3 +75,48 @@ def test_test_batch_equals_test_per_episode():
             pred, loss, acc = L.test(ep, None, eval=ev)
             assert torch.equal(got[e][0], pred)
             assert abs(float(got[e][1]) - float(loss)) < 2e-5 and abs(got[e][2] - acc) < 1e-6
+
+
+def test_train_and_train_batch_interleave():
+    """train_batch / train / test / train_batch on one learner: every train_batch step runs on its own gradient bucket,
+    whatever re-pointed the parameters' .grad since its last step (train()'s zero_grad() and backward(); a new trainer
+    when E changes).  The step after the interleaving equals, bit for bit, the same step of a fresh learner loaded from
+    the same weights and running statistics (dropout is off, so nothing else feeds the gradient)."""
+    import copy
+    cfg = S.make_cfg(n_way=2, k_shot=2, pc_npts=512, pretrain_checkpoint_path="synthetic", model_checkpoint_path=None,
+                     lr=1e-3, step_size=5000, gamma=0.5)
+    eps = []
+    for e in range(5):
+        data, _ = S.make_episode(cfg, seed=80 + e, noise_ratio=0.5, train=True)
+        eps.append([t.cuda() for t in data])
+    tdata, sc = S.make_episode(cfg, seed=90, noise_ratio=0.5)
+    tdata = [t.cuda() for t in tdata]
+    b1, e, b2, b3 = eps[0:2], eps[2], eps[3:5], eps[0:3]
+
+    def fresh_step(state, batch):
+        C = _learner(cfg)
+        C.model.load_state_dict(state)
+        out = C.train_batch(batch, None)
+        return [tuple(float(v) for v in o) for o in out], C._batch_trainer.bucket.flat.clone()
+
+    def check(A, state, batch):
+        got = [tuple(float(v) for v in o) for o in A.train_batch(batch, None)]
+        bucket = A._batch_trainer.bucket
+        want, want_flat = fresh_step(state, batch)
+        assert torch.equal(bucket.flat, want_flat)
+        assert got == want and len(got) == len(batch) and all(len(o) == 8 for o in got)
+        for p, v in zip(bucket.params, bucket.views):
+            assert p.grad.data_ptr() == v.data_ptr()
+        assert bucket.flat.abs().max().item() > 0
+
+    A = _learner(cfg)
+    A.train_batch(b1, None)
+    assert len(A.train(e, None)) == 8
+    A.test(tdata, sc)
+    check(A, copy.deepcopy(A.model.state_dict()), b2)
+    assert A.lr_scheduler.last_epoch == 3
+    # E changes and changes back: each change builds a new trainer with a bucket of its own
+    A.train_batch(b3, None)
+    assert A._batch_trainer.batch_size == 3
+    check(A, copy.deepcopy(A.model.state_dict()), b2)
+    assert A._batch_trainer.batch_size == 2 and A.lr_scheduler.last_epoch == 5
