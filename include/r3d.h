@@ -464,6 +464,30 @@ int r3d_protonet_head_bwd(int n_ep, const float* qfeat, long ldq, long feat_ep_r
 int r3d_miou_accumulate(const int32_t* pred, const int64_t* gt, long n, const int32_t* lut, int n_lut, int n_classes,
                         uint64_t* hist, void* stream);
 
+/* ---- Training augmentation of prepared clouds (dataloaders/loader.py:205-213,354-373: --pc_augm) ----
+ * A prepared cloud holds the min-shifted xyz in channels xyz_ch..xyz_ch+2 -- the array the reference hands to
+ * augment_pointcloud -- so for each of B clouds of N points and C channels (3, 6 or 9):
+ *   xyz' = xyz . M^T + jitter,  M = Mirror_y . Mirror_x . Rot_z(angle) . (s I)  (row-major 3 x 3; loader.py:356-368):
+ *     s uniform in [1/scale, scale] when scale > 1, angle uniform in [0, 2 pi) when rot == 1, each mirror with
+ *     probability mirror_prob / 2 when mirror_prob > 0;
+ *   jitter = clip(0.01 normal, -0.05, 0.05) on the three xyz channels when jitter != 0        (loader.py:370-372);
+ *   XYZ' = (xyz' - min_n xyz') / max_n (xyz' - min_n xyz') per axis, IEEE division, into channels XYZ_ch..XYZ_ch+2
+ *     (XYZ_ch = -1: the cloud has none; an axis of zero extent gives NaN as the reference's division does) (loader.py:209-213);
+ *   every other channel is copied.
+ * x and out are addressed as p[b * sb + c * sc + n * sn] (strides in floats): contiguous channel-major (B, C, N) is
+ * (C N, N, 1), point-major rows viewed as (B, C, N) are (N C, 1, C).  out == x (same strides) is allowed and gives the
+ * bits of the out-of-place call; any other overlap is the caller's error.
+ * Randomness is stateless: all a cloud draws is a function of (seed + *seed_dev, first_key + b), the jitter of
+ * (point, axis) besides; seed_dev (may be NULL) is a device word added to seed, so that a frozen launch sequence
+ * advances without re-capture (as r3d_attention_fwd_train).  The normal draws are this library's, not numpy's.
+ * Optional (NULL: absent): mats (B, 9) matrices to use instead of drawing them; noise (B, N, 3) jitter to add instead of
+ * generating it (used whatever `jitter` says); mats_out (B, 9) receives the matrix each cloud used.
+ * One 256-thread workgroup per cloud; min / max reductions only, so results are bit-reproducible. */
+int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* out, long o_sb, long o_sc, long o_sn, int B,
+                       int C, int N, int xyz_ch, int XYZ_ch, float scale, int rot, float mirror_prob, int jitter,
+                       unsigned seed, const unsigned* seed_dev, unsigned first_key, const float* mats, const float* noise,
+                       float* mats_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

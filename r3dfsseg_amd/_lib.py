@@ -131,6 +131,9 @@ _SIGS = {
     "r3d_contrast_bwd_batched": (c_i, [c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_l, c_f, c_f, c_f, c_l, c_f]),
     "r3d_train_metrics_batched": (c_i, [c_i, c_f, c_f, c_f, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_i, c_i, c_i, c_f, c_f]),
     "r3d_clean_shot_detect_batched": (c_i, [c_i, c_f, c_l, c_l, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_l, c_f]),
+    # ---- additive in ABI version 5: training augmentation of prepared clouds
+    "r3d_augment_clouds": (c_i, [c_f, c_l, c_l, c_l, c_f, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_fl, c_i, c_u, c_f,
+                                 c_u, c_f, c_f, c_f, c_f]),
 }
 
 _lib = None

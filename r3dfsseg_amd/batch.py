@@ -50,6 +50,14 @@ class EpisodeBatch:
     def __len__(self):
         return self.E
 
+    def augmented(self, cfg, seed, counter):
+        """A new batch whose clouds went through the reference's --pc_augm transform on the device (augment.py): ONE launch
+        over all E (S + Q) clouds of x_all.  cfg: the reference's dict {'scale', 'rot', 'mirror_prob', 'jitter'}; episode e
+        draws with counter + e, so the result equals E augment.augment_episode calls bit for bit.  Labels, masks and flags
+        are shared with this batch."""
+        from .augment import augment_batch
+        return augment_batch(self, cfg, seed, counter)
+
     def episode(self, e):
         """Episode e in the reference's train layout (views)."""
         return [self.support_x[e], self.support_y[e], self.query_x[e], self.query_y[e], None, None, self.gt_support_y[e],

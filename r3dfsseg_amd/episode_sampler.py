@@ -18,9 +18,11 @@ the reference is everything that gives an episode its MEANING:
   * block -> cloud: the target class keeps its share of the points, xyz shifted to the minimum corner, rgb / 255,
     XYZ = xyz / max                                                                              loader.py:219-231,258-276
   * four extra background clouds from classes outside the episode (train layout only)           loader.py:858-886
+  * --pc_augm: scale, z-rotation, mirrors and clipped jitter of the min-shifted xyz, before XYZ   loader.py:205-213,354-373
 
 Host numpy only (as the reference): this is the caller side of the hot path, SURVEY.md 8(f) N3.
 """
+import math
 import random
 
 import numpy as np
@@ -66,12 +68,49 @@ class SyntheticBlocks:
         return np.concatenate([xyz, rgb, label[:, None], inst[:, None]], 1)
 
 
+def augment_matrix(cfg, pyrng):
+    """The 3 x 3 matrix of loader.py:356-367, M = Mirror_y . Mirror_x . Rot_z(angle) . (s I), drawn from Python's `random`
+    stream in the reference's order (scale, angle, mirror x, mirror y).  The two transforms3d functions it calls are
+    closed forms here: zfdir2mat(s) = s I, zfdir2mat(-1, e_x) = diag(-1, 1, 1), zfdir2mat(-1, e_y) = diag(1, -1, 1),
+    axangle2mat(e_z, a) = [[cos a, -sin a, 0], [sin a, cos a, 0], [0, 0, 1]]."""
+    M = np.eye(3)
+    if cfg["scale"] > 1:
+        s = pyrng.uniform(1 / cfg["scale"], cfg["scale"])
+        M = np.dot(s * np.eye(3), M)
+    if cfg["rot"] == 1:
+        angle = pyrng.uniform(0, 2 * math.pi)
+        c, sn = math.cos(angle), math.sin(angle)
+        M = np.dot(np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]), M)
+    if cfg["mirror_prob"] > 0:  # x and y, not z
+        if pyrng.random() < cfg["mirror_prob"] / 2:
+            M = np.dot(np.diag([-1.0, 1.0, 1.0]), M)
+        if pyrng.random() < cfg["mirror_prob"] / 2:
+            M = np.dot(np.diag([1.0, -1.0, 1.0]), M)
+    return M
+
+
+def augment_pointcloud(P, cfg, pyrng, rng, return_draws=False):
+    """loader.py:354-373 on P (N, 3), the min-shifted xyz: P . M^T, then + clip(0.01 randn, -0.05, 0.05) cast to float32 as
+    the reference casts it.  cfg: {'scale', 'rot', 'mirror_prob', 'jitter'}.  pyrng: Python's `random` stream (the matrix
+    draws), rng: the numpy stream (the jitter, rng.randn(*P.shape), drawn after the matrix).  Returns a new array;
+    return_draws: also M and the jitter that was added (zeros when jitter is off)."""
+    M = augment_matrix(cfg, pyrng)
+    P = np.dot(np.asarray(P, np.float64)[:, :3], M.T)
+    noise = np.zeros(P.shape, np.float32)
+    if cfg["jitter"]:
+        sigma, clip = 0.01, 0.05
+        noise = np.clip(sigma * rng.randn(*P.shape), -1 * clip, clip).astype(np.float32)
+        P = P + noise
+    return (P, M, noise) if return_draws else P
+
+
 def sample_pointcloud(block, num_point, sampled_classes, sampled_class, support, rng, partial_noise=False,
-                      pc_attribs="xyzrgbXYZ", pyrng=None):
+                      pc_attribs="xyzrgbXYZ", pyrng=None, pc_augm=False, pc_augm_config=None):
     """loader.py:202-352 (sample_pointcloud_universal, clean labels): -> (cloud (num_point, 9) f64, label, gt_label).
     support: binary mask of `sampled_class`; query: 1-based position in `sampled_classes`, 0 elsewhere.
     rng: the numpy stream (the reference draws from the global np.random); pyrng: Python's `random` stream, which the
-    reference uses for ONE draw, the foreground flip of partial noise (loader.py:325)."""
+    reference uses for the foreground flip of partial noise (loader.py:325) and for the matrix of the augmentation.
+    pc_augm / pc_augm_config: the reference's --pc_augm, applied between the min-shift and XYZ (loader.py:205-213)."""
     sampled_classes = list(sampled_classes)
     N = block.shape[0]
     if partial_noise:  # loader.py:222-223: plain random sample
@@ -83,6 +122,10 @@ def sample_pointcloud(block, num_point, sampled_classes, sampled_class, support,
                                rng.choice(np.arange(N), num_point - n_valid, replace=(N < num_point))])
     data = block[inds]
     xyz = data[:, 0:3] - np.amin(data[:, 0:3], axis=0)
+    if pc_augm:
+        if pyrng is None or pc_augm_config is None:
+            raise ValueError("pc_augm needs pc_augm_config and pyrng (the matrix is drawn from Python's random stream)")
+        xyz = augment_pointcloud(xyz, pc_augm_config, pyrng, rng)
     parts = []
     if "xyz" in pc_attribs:
         parts.append(xyz)
@@ -121,9 +164,10 @@ def sample_pointcloud(block, num_point, sampled_classes, sampled_class, support,
     return cloud, target, to_target(labels)
 
 
-def _sample_k(source, num_point, scans, sampled_class, sampled_classes, support, rng, partial_noise=False, pyrng=None):
+def _sample_k(source, num_point, scans, sampled_class, sampled_classes, support, rng, partial_noise=False, pyrng=None,
+              augm=None):
     out = [sample_pointcloud(source.load(s), num_point, sampled_classes, sampled_class, support, rng, partial_noise,
-                             pyrng=pyrng)
+                             pyrng=pyrng, pc_augm=augm is not None, pc_augm_config=augm)
            for s in scans]
     return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]), np.stack([o[2] for o in out]))
 
@@ -136,7 +180,7 @@ class NoiseEpisodeSampler:
     split (loader.py:585-588, 669-671, 686-687)."""
 
     def __init__(self, source, classes, n_way=2, k_shot=5, n_queries=1, num_point=2048, mode="test", noise_ratio=0.4,
-                 noise_type="sym", noise_pair_dict=None, seed=0):
+                 noise_type="sym", noise_pair_dict=None, seed=0, pc_augm=False, pc_augm_config=None):
         if mode not in ("train", "test"):
             raise NotImplementedError("Unkown mode %s! [Options: train/test]" % mode)
         if mode == "train":
@@ -146,6 +190,9 @@ class NoiseEpisodeSampler:
         self.n_way, self.k_shot, self.n_queries, self.num_point = n_way, k_shot, n_queries, num_point
         self.mode, self.noise_ratio, self.noise_type = mode, noise_ratio, noise_type
         self.noise_pair_dict = noise_pair_dict
+        if pc_augm and pc_augm_config is None:
+            raise ValueError("pc_augm=True needs pc_augm_config ({'scale', 'rot', 'mirror_prob', 'jitter'})")
+        self.augm = dict(pc_augm_config) if pc_augm else None  # every cloud of an episode, as loader.py:701-875 passes it on
         self.rng = np.random.RandomState(seed)    # np.random.seed(seed) in the reference's process
         self.pyrng = random.Random(seed)          # random.seed(seed): loader.py:325 draws from Python's generator
 
@@ -179,8 +226,10 @@ class NoiseEpisodeSampler:
             clean = rng.choice(unused(cls), k_shot - n_noise + self.n_queries, replace=False)
             black.extend(clean)
             q_scans, s_scans = clean[:self.n_queries], clean[self.n_queries:]
-            s_pc, s_mask, s_gt = _sample_k(self.source, self.num_point, s_scans, cls, sampled_classes, True, rng)
-            q_pc, q_lab, q_gt = _sample_k(self.source, self.num_point, q_scans, cls, sampled_classes, False, rng)
+            s_pc, s_mask, s_gt = _sample_k(self.source, self.num_point, s_scans, cls, sampled_classes, True, rng,
+                                           pyrng=self.pyrng, augm=self.augm)
+            q_pc, q_lab, q_gt = _sample_k(self.source, self.num_point, q_scans, cls, sampled_classes, False, rng,
+                                          pyrng=self.pyrng, augm=self.augm)
             flag = np.zeros(k_shot)
             flag[:len(s_scans)] = cls
             if self.noise_type == "pair":
@@ -209,7 +258,7 @@ class NoiseEpisodeSampler:
                         scan = rng.choice(candidates, 1, replace=False)
                 black.extend(scan)
                 n_pc, n_mask, n_gt = _sample_k(self.source, self.num_point, scan, noisy, sampled_classes, True, rng,
-                                               partial_noise=self.noise_type == "partial", pyrng=self.pyrng)
+                                               partial_noise=self.noise_type == "partial", pyrng=self.pyrng, augm=self.augm)
                 s_pc, s_mask, s_gt = (np.concatenate([a, b], 0) for a, b in ((s_pc, n_pc), (s_mask, n_mask), (s_gt, n_gt)))
                 count[noisy] += 1
                 if count[noisy] == k_shot - n_noise - 1:
@@ -229,7 +278,8 @@ class NoiseEpisodeSampler:
             bg_classes.remove(c)
             scan = rng.choice(unused(c), 1, replace=False)
             black.extend(scan)
-            pc, m, _ = _sample_k(self.source, self.num_point, scan, c, sampled_classes, True, rng)
+            pc, m, _ = _sample_k(self.source, self.num_point, scan, c, sampled_classes, True, rng, pyrng=self.pyrng,
+                                 augm=self.augm)
             bg_x.append(pc); bg_y.append(m)
         sup, mask, gt = np.stack(sup), np.stack(mask), np.stack(gt)
         self.last_black_list = black

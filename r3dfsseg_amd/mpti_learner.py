@@ -29,6 +29,8 @@ class MPTILearner_V3(object):
             raise RuntimeError("MPTILearner_V3 needs an MI355X: the forward pass has no CPU path")
         self.model.cuda()
         self.episode_graphs = bool(getattr(args, 'episode_graphs', False))
+        from .augment import LearnerAugment
+        self._augm = LearnerAugment(args)  # args.device_augm (+ args.pc_augm): --pc_augm on the device, train*() only
         self._trainer = None          # DPTrainer with one captured slot (train)
         self._batch_trainer = None    # DPTrainer(batch_size=E) behind train_batch
         self._batch_runner = None     # EpisodeBatchRunner behind test_batch
@@ -87,6 +89,7 @@ class MPTILearner_V3(object):
         return (loss, lp, con, point_accuracy(logits.argmax(dim=1), data[3])) + tuple(metrics.unbind(0))
 
     def train(self, data, logger):
+        data = self._augm.episode(data)  # once, here: the graph's input copy and a conservative redo see the same clouds
         if self.episode_graphs:
             out = self._train_graph(data, logger)
             if out is not None:
@@ -141,7 +144,11 @@ class MPTILearner_V3(object):
         if self._batch_trainer is None or self._batch_trainer.batch_size != E:
             self._batch_trainer = DPTrainer(self, batch_size=E, batch_graph=True)
         tr = self._batch_trainer
-        tr.step(datas, logger=logger)
+        if self._augm.on:  # once, before the step (its graph input copy, its redo): one launch over the batch's clouds
+            from .batch import EpisodeBatch
+            tr.step([self._augm.batch(EpisodeBatch.from_episodes(datas))], logger=logger)
+        else:
+            tr.step(datas, logger=logger)
         outs = tr.last_outputs
         qy = torch.stack([d[3] for d in datas], 0)
         logits = torch.stack([o[3] for o in outs], 0)

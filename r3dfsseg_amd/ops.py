@@ -549,3 +549,25 @@ def miou_accumulate(pred, gt, lut, hist):
     _lib.check(_lib.load().r3d_miou_accumulate(_p(pred), _p(gt), pred.numel(), _p(lut), lut.numel(), hist.shape[1],
                                                _p(hist), _st()))
     return hist
+
+
+def augment_clouds(x, out, scale, rot, mirror_prob, jitter, seed, first_key=0, xyz_ch=0, XYZ_ch=-1, seed_dev=None, mats=None,
+                   noise=None, mats_out=None):
+    """r3d_augment_clouds on x (B, C, N) fp32 -> out (B, C, N) fp32 (out may BE x): the reference's --pc_augm transform of
+    prepared clouds (dataloaders/loader.py:205-213,354-373).  Either tensor is read as it lies -- contiguous channel-major
+    or a transposed view of point-major rows (is_point_major_view): its three strides travel with it.  seed_dev: a device
+    uint32/int32 word added to seed; mats (B, 9) / noise (B, N, 3): given matrices / jitter instead of drawn ones;
+    mats_out (B, 9): receives the matrices used.  augment.augment_clouds is the surface with defaults and allocation."""
+    assert x.dim() == 3 and x.shape == out.shape and x.dtype == torch.float32 and out.dtype == torch.float32 and x.is_cuda \
+        and out.is_cuda, "expected two (B, C, N) fp32 CUDA tensors of one shape"
+    B, C, N = x.shape
+    for t, shape in ((mats, (B, 9)), (noise, (B, N, 3)), (mats_out, (B, 9))):
+        assert t is None or (tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda), \
+            "mats / mats_out (B, 9), noise (B, N, 3): contiguous fp32 CUDA tensors"
+    assert seed_dev is None or (seed_dev.numel() == 1 and seed_dev.element_size() == 4 and seed_dev.is_cuda)
+    xs, os_ = x.stride(), out.stride()
+    _lib.check(_lib.load().r3d_augment_clouds(_p(x), xs[0], xs[1], xs[2], _p(out), os_[0], os_[1], os_[2], B, C, N, xyz_ch,
+                                              XYZ_ch, float(scale), int(rot), float(mirror_prob), int(bool(jitter)),
+                                              int(seed) & 0xffffffff, _p(seed_dev), int(first_key) & 0xffffffff, _p(mats),
+                                              _p(noise), _p(mats_out), _st()))
+    return out

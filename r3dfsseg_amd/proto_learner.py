@@ -14,6 +14,8 @@ class ProtoLearner(object):
     def __init__(self, args, mode='train'):
         self.model = ProtoNet(args)
         self._batch_trainer = None  # protonet_train.ProtoBatchTrainer behind train_batch
+        from .augment import LearnerAugment
+        self._augm = LearnerAugment(args)  # args.device_augm (+ args.pc_augm): --pc_augm on the device, train*() only
         if not torch.cuda.is_available():
             raise RuntimeError("ProtoLearner needs an MI355X: the forward pass has no CPU path")
         self.model.cuda()
@@ -48,7 +50,7 @@ class ProtoLearner(object):
         the reference's training collate); only the first four entries are used:
         support_x (n_way, k_shot, in_channels, num_points), support_y (n_way, k_shot, num_points),
         query_x (n_queries, in_channels, num_points), query_y (n_queries, num_points)."""
-        support_x, support_y, query_x, query_y = (t.cuda() for t in data[:4])
+        support_x, support_y, query_x, query_y = (t.cuda() for t in self._augm.episode(data)[:4])
         self.model.train()
         query_logits, loss = self.model(support_x, support_y, query_x, query_y)
         self.optimizer.zero_grad()
@@ -81,7 +83,7 @@ class ProtoLearner(object):
         train() computes for it from the same weights and the same dropout seed.  May be interleaved with train() and
         test*() in any order (protonet_train.ProtoBatchTrainer says how the gradients stay apart)."""
         from .protonet_train import ProtoBatchTrainer
-        b = self._batch(datas)
+        b = self._augm.batch(self._batch(datas))
         if not self.model.use_attention:
             raise NotImplementedError("training with use_attention=False (the linear mapper) is not built: the training "
                                       "encoder (train_ops.encoder_forward) needs the attention learner")
