@@ -19,15 +19,19 @@
  *     floats); the reference's channel-major (B, C, N) tensors are converted at the
  *     forward() boundary by r3d_cm_to_pm / r3d_pm_to_cm;
  *   - indices are int32;
- *   - BATCHES OF EPISODES (ABI version 3).  Episodes are independent units (the reference runs one per step,
- *     mpti_train_noise.py:57-98); here E of them go through ONE launch sequence.  Encoder side: the clouds of the batch
- *     are rows of one matrix, episode after episode, [S support clouds | Q query clouds] each; BatchNorm keeps the
- *     statistics of every getFeatures call apart (models/mpti.py:434,436), so the `_seg` entry points take the two
- *     alternating segment sizes (rows_a = S N, rows_b = Q N, or in clouds) -- segment 2 e + p is call p of episode e,
- *     rows_b == 0 means equal segments -- and address the BatchNorm vectors of segment s at (pointer + s * bn_stride).
- *     Head side: the `_batched` entry points take n_ep and the stride of every per-episode array (capacity sized).
+ *   - an operation works on a BATCH OF EPISODES.  Episodes are independent units (the reference runs one per step,
+ *     mpti_train_noise.py:57-98); E of them go through ONE launch sequence, and one episode is a batch of one.
+ *     Encoder side, SEGMENTS: the clouds of the batch are rows of one matrix, episode after episode, [S support clouds |
+ *     Q query clouds] each; BatchNorm keeps the statistics of every getFeatures call apart (models/mpti.py:434,436), so
+ *     the `_seg` entry points take the two alternating segment sizes (rows_a = S N, rows_b = Q N, or in clouds) --
+ *     segment 2 e + p is call p of episode e, rows_b == 0 means equal segments (rows_a = all rows: one segment) -- and
+ *     address the BatchNorm vectors of segment s at (pointer + s * bn_stride).
+ *     Head side: the `_batched` entry points take n_ep and the stride of every per-episode array (capacity sized);
+ *     every pointer addresses episode 0.  The attention calls take seed_group, the clouds per episode.
  *     A segment's / an episode's results do not depend on the batch it runs in: reductions are partitioned by the
  *     segment's own size and summed relative to its first element.
+ *   - a few operations keep a single-episode call beside the batched one (r3d_knn_topk, r3d_label_propagate,
+ *     r3d_protonet_head, r3d_pointwise_conv_stats, the D = 64 attention calls): the same kernels on a batch of one.
  */
 #ifndef R3D_H
 #define R3D_H
@@ -59,7 +63,6 @@ int r3d_debug_set_gemm_bx3(int mask);
 /* ---- layout conversion at the forward() boundary (models/mpti.py:433-437) -------- */
 int r3d_cm_to_pm(const float* in /*(B,C,N)*/, int B, int C, int N, float* out /*(B*N,ld)*/, long ld, void* stream);
 int r3d_pm_to_cm(const float* in /*(B*N,ld)*/, long ld, int B, int C, int N, float* out /*(B,C,N)*/, void* stream);
-int r3d_pm_to_cm_pitched(const float* in, long ld, int B, int C, int N, float* out /*(B,C,pitch)*/, long pitch, void* stream);
 long r3d_cm_pitch(int N); /* row pitch (floats) of internal channel-major copies: avoids power-of-two channel strides */
 int r3d_copy_cols(const float* src, long ld_src, float* dst, long ld_dst, long M, int C, void* stream);
 
@@ -76,7 +79,6 @@ int r3d_copy_cols(const float* src, long ld_src, float* dst, long ld_dst, long M
  * status: optional device int32.  For k > 32 a non-NULL status selects the two-pass
  * append-and-rank kernel; bit 0 set afterwards means its survivor buffer overflowed and the
  * call must be repeated with status == NULL (insertion kernel, always exact). */
-int r3d_sqnorm(const float* x, long ldx, long rows, int C, float* out, void* stream);
 long r3d_knn_norm_ws_words(int B, int N);  /* floats of norm_ws: B*N norms + per-tile overflow flags */
 int r3d_knn_topk(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
                  const int32_t* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out, float* score_out,
@@ -122,14 +124,36 @@ int r3d_pointwise_conv(const float* X, long ldx, const float* W /*(Co,K)*/, long
 int r3d_edgeconv_fwd(const float* PQ, const int32_t* idx, const float* W2, const float* s2, const float* t2,
                      float* out, long ldo, int B, int N, int K, int32_t* argmax_out, void* stream);
 
-/* ---- point self-attention, d = 64 (models/attention.py:43-46) ------------------------
- * qkv (B*N, ld): q*(1/8) | k | v at columns 0 | 64 | 128.  out (B*N, ldo) 64 columns.
- * lse_out optional (B*N). */
-/* ws (optional, r3d_attention_ws_words(B, N) floats): enables the streamed-axis split -- small grids (B*N/128
- * workgroups) are cut along the key axis so that ~512 workgroups exist, partials merged in a fixed order */
+/* ---- point self-attention (models/attention.py:43-46), forward and flash-style backward ----
+ * Head width D in {32, 64, 96, 128} (the reference's --output_dim); any other D is refused (R3D_ERR_ARG) before a launch
+ * and r3d_attention_ws_words_ep_d returns -1 for it.  qkv (B*N, ld >= 3D): q / sqrt(D) | k | v at columns 0 | D | 2D;
+ * out / O / dO (B*N, D columns); lse_out (B*N), saved for the backward; dqkv (B*N, ldd >= 3D).
+ * Dropout on the attention weights (attention.py:45): p_drop, effective seed = seed + *seed_dev (seed_dev may be NULL; a
+ * captured hipGraph bumps *seed_dev per replay).  p_drop = 0 is the inference forward.
+ * Batches of episodes: clouds [e seed_group, (e + 1) seed_group) are episode e (seed_group == 0: all B clouds are one),
+ * whose dropout mask is the one a call on those clouds alone draws with seed + 2 e (the one-episode schedule advances its
+ * seed by 2 per episode); outputs are bit for bit those of that call.
+ * ws: r3d_attention_ws_words_ep_d(B, N, seed_group, D) floats.  It holds the packed bf16 x 3 operands (without it the
+ * forward runs on the fp32 core) and the partials of the key-axis split, which is chosen for ONE episode (seed_group
+ * clouds) whatever the batch.  The forward may run without ws, the backward needs it.
+ * ws_holds_packed_qkv != 0: ws is the workspace the forward ran with on this qkv, untouched since (the bf16 x 3 kernels
+ * reuse the packed q | k | v pieces it holds instead of cutting them again). */
+long r3d_attention_ws_words_ep_d(int B, int N, int seed_group, int D);
+int r3d_attention_fwd_train_ep_d(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
+                                 unsigned seed, const unsigned* seed_dev, int seed_group, int D, float* ws, void* stream);
+int r3d_attention_bwd_ep_d(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
+                           const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, int D,
+                           float q_scale, float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
+/* the D = 64 case on one episode (seed_group = 0); r3d_attention_bwd is r3d_attention_bwd_ws with ws_holds_packed_qkv = 0 */
 long r3d_attention_ws_words(int B, int N);
-int r3d_attention_fwd(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float* ws,
-                      void* stream);
+int r3d_attention_fwd_train(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
+                            unsigned seed, const unsigned* seed_dev, float* ws /*opt*/, void* stream);
+int r3d_attention_bwd(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
+                      const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, float q_scale, float* dqkv,
+                      long ldd, float* ws, void* stream);
+int r3d_attention_bwd_ws(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
+                         const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, float q_scale,
+                         float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
 
 /* ---- multi-prototype extraction (models/mpti.py:597-715) -----------------------------
  * FPS (start index 0, ties lowest index) -> sorted unique seeds -> nearest-seed assignment ->
@@ -138,9 +162,8 @@ int r3d_attention_fwd(const float* qkv, long ld, int B, int N, float* out, long 
  * desc: device int32[r3d_head_desc_words()] = {seg_count[8], seg_m[8], seg_poff[8], n_proto, n_nodes,..}.
  * Seeds per segment of n > k points: what torch_cluster.fps(feat, None, ratio = k / n) draws at the call site
  * models/mpti.py:612-613, ceil(float32(n) * float32(k / n)) = k or k + 1 (101 for 5.8 % of the n <= 20480 at k = 100),
- * so a segment can hold k + 1 prototypes: nodes / node_labels need (n_way + 1) * (k + 1) + n_query_pts rows, k < r3d_head_max_k(). */
+ * so a segment can hold k + 1 prototypes: nodes / node_labels need (n_way + 1) * (k + 1) + n_query_pts rows, k < 128. */
 int r3d_head_desc_words(void);
-int r3d_head_max_k(void);
 /* out[n], n in [0, n_max): the seeds a segment of n points gets at k (n <= k: n), as the device evaluates the count above
  * (device int32 out; for tests that hold it to the host arithmetic over every n). */
 int r3d_fps_sample_count_table(int k, int n_max, int32_t* out, void* stream);
@@ -150,14 +173,9 @@ int r3d_head_proto_ws_offsets(int n_way, int k_shot, int N, long* out6 /* comp,m
  * grid co-resident: episodes in flight x support points / 256 <= ~384 workgroups; desc word 26 (HD_FPS_TIMEOUT) reports
  * a wait time-out); 0 = one launch per round. */
 #define R3D_HEAD_FPS_ONE_LAUNCH 1
-int r3d_head_prototypes(const int32_t* support_y /*(n_way*k_shot,N)*/, const int32_t* shot_keep /*opt (n_way*k_shot)*/,
-                        const float* feat /*(S*N,ldf)*/, long ldf, const float* featT /*(S,D,N)*/,
-                        const float* qfeat /*(n_q*N,ldq)*/, long ldq, int n_way, int k_shot, int N, int D,
-                        int n_query_pts, int k, float* nodes, long ldn, float* node_labels /*(n_cap,4)*/,
-                        int32_t* desc, int32_t* assign_out /*opt (2*S*N)*/, int32_t* cluster_count /*opt (n_cap)*/,
-                        int32_t* ws, long ws_words, int flags, void* stream);
-
-/* n_ep episodes in one launch sequence (every pointer addresses episode 0).  Strides between consecutive episodes:
+/* n_ep episodes in one launch sequence (every pointer addresses episode 0).  Per episode: support_y (n_way*k_shot, N),
+ * shot_keep optional (n_way*k_shot), feat (S*N, ldf), qfeat (n_q*N, ldq), node_labels (n_cap, 4), assign_out (2*S*N;
+ * optional for one episode), cluster_count optional (n_cap).  Strides between consecutive episodes:
  * support_y / shot_keep / desc / assign / cluster_count / ws in int32 words (ws_stride even, >= the scratch size), feat /
  * qfeat / nodes in ROWS.  fps_group: episodes whose farthest-point samplings share one persistent launch (their workgroups
  * must be co-resident: ~500 workgroup slots at D <= 192, 250 above; an episode needs ceil(S N / 256) + n_way + 1). */
@@ -175,7 +193,7 @@ int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_t* support_
  * grouped around an even subsample of the first *n_proto_dev rows, the prototypes), A-DEF2 preconditioner.
  * nodes rows are read as float4 (ldn % 4 == 0, 16-byte aligned); Y, Z (n_cap, 4) fp32, 16-byte aligned; n_cap <= 32768.
  * ws: r3d_lp_ws_words(n_cap, kp1) int32 words, 16-byte aligned; it keeps the graph, the coarse space and the
- * directed weights for r3d_label_propagate_bwd.  stats_out optional device int32[2] = {converged, iterations}.
+ * directed weights for r3d_label_propagate_bwd_batched.  stats_out optional device int32[2] = {converged, iterations}.
  * r3d_lp_ws_offsets: int32-word offsets inside ws of {row_ptr, col (uint16 entries), val, dinv, aggregate ids,
  * solver state} for tests and tools that read the system back. */
 long r3d_lp_ws_words(int n_cap, int kp1);
@@ -211,25 +229,23 @@ int r3d_label_propagate_solve_batched(int n_ep, const float* Y, const int32_t* n
                                       long ws_stride, int32_t* stats_out, long stats_stride, void* stream);
 
 /* Captured episodes: enable the CG kernel nodes (three per iteration) of iterations < budget in an instantiated hipGraph holding
- * r3d_label_propagate / r3d_label_propagate_bwd launches, disable the rest (no dispatch for them).  graph: the
+ * r3d_label_propagate(_batched) / r3d_label_propagate_bwd_batched launches, disable the rest (no dispatch for them).  graph: the
  * hipGraph_t the hipGraphExec_t graph_exec was instantiated from.  n_cg (optional, host): CG nodes found.
  * No reference counterpart (the reference inverts the dense matrix, models/mpti.py:758-776). */
 int r3d_graph_set_lp_budget(void* graph, void* graph_exec, int budget, int* n_cg);
 
-/* ---- query logits + cross entropy (models/mpti.py:558-559, 778-781) ------------------ */
-int r3d_query_logits_ce(const float* Z, const int32_t* n_proto_dev, int n_q, int N, int n_classes,
-                        const int64_t* labels /*opt (n_q,N)*/, float* logits /*(n_q,n_classes,N)*/,
-                        float* loss_out /*opt*/, int32_t* pred_out /*opt (n_q*N)*/, void* stream);
-
-/* per system of a batch: Z rows [e z_ep_rows, ...) -> logits / loss / pred number e of the batch arrays */
+/* ---- query logits + cross entropy (models/mpti.py:558-559, 778-781) ------------------
+ * per system of a batch: Z rows [e z_ep_rows, ...) -> logits / loss / pred number e of the batch arrays; per system
+ * labels optional (n_q, N), logits (n_q, n_classes, N), loss_out optional (1), pred_out optional (n_q*N) */
 int r3d_query_logits_ce_batched(int n_ep, const float* Z, long z_ep_rows, const int32_t* n_proto_dev, long desc_stride, int n_q,
                                 int N, int n_classes, const int64_t* labels, float* logits, float* loss_out, int32_t* pred_out,
                                 void* stream);
 
 /* ==== training mode (BatchNorm with batch statistics, backward) =======================
- * A conv+BN+act layer: z = r3d_pointwise_conv (no affine) -> r3d_colstats mode 0 -> r3d_bn_fold ->
- * r3d_affine_act.  Backward: r3d_colstats mode 1 (sum du, sum du*zhat = dbeta, dgamma) ->
- * r3d_bn_bwd_apply (dz) -> r3d_pointwise_conv(_acc)(dz, W^T) for dX, r3d_gemm_tn(dz, X) for dW.
+ * A conv+BN+act layer: z = r3d_pointwise_conv_stats_seg (GEMM + statistics; or r3d_pointwise_conv, no affine ->
+ * r3d_colstats_seg mode 0) -> r3d_bn_fold_seg -> r3d_affine_act_seg.  Backward: r3d_colstats_seg mode 1 (sum du,
+ * sum du*zhat = dbeta, dgamma) -> r3d_bn_bwd_apply_seg (dz) -> r3d_pointwise_conv(_acc)(dz, W^T) for dX,
+ * r3d_gemm_tn(dz, X) for dW.
  * Reference: nn.BatchNorm{1,2}d in train mode inside models/dgcnn.py:45-80, models/mpti.py:31-39. */
 int r3d_pointwise_conv_acc(const float* X, long ldx, const float* W, long M, int K, int Co, const float* scale,
                            const float* shift, int act, float* Out, long ldo, void* stream);
@@ -238,30 +254,18 @@ int r3d_pointwise_conv_acc(const float* X, long ldx, const float* W, long M, int
 long r3d_pointwise_conv_stats_ws_words(long M, int Co);
 int r3d_pointwise_conv_stats(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out, long ldo,
                              float* sums_out /*[2][Co]*/, float* ws, void* stream);
-/* the same with separate statistics for rows [0, M_first) and [M_first, M) (support and query clouds of an episode in
- * one launch; mpti.py:434,436 normalise them separately).  M_first: a positive multiple of 64. */
-int r3d_pointwise_conv_stats2(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out, long ldo,
-                              long M_first, float* sums_a /*[2][Co]*/, float* sums_b /*[2][Co]*/, float* ws, void* stream);
-/* ... and over the alternating row segments of a batch of episodes (rows_a, rows_b multiples of 64): ONE GEMM launch,
- * sums_out [seg][2][Co] */
+/* the same with separate statistics for the alternating row segments of a batch of episodes (support and query clouds
+ * are normalised separately, mpti.py:434,436; rows_a, rows_b multiples of 64): ONE GEMM launch, sums_out [seg][2][Co] */
 int r3d_pointwise_conv_stats_seg(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out, long ldo,
                                  long rows_a, long rows_b, float* sums_out, float* ws, void* stream);
-int r3d_colreduce(const float* part /*[chunks][2][C]*/, int chunks, int C, float* sums_out /*[2][C]*/, void* stream);
-int r3d_colreduce_seg(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out /*[seg][2][C]*/, void* stream);
-long r3d_colstats_ws_words(long M, int C);
-int r3d_colstats(const float* X, long ldx, const float* DY, long lddy, long M, int C, int mode, const float* scale,
-                 const float* shift, const float* mean, const float* invstd, int act, float* sums_out /*[2][C]*/,
-                 float* ws, void* stream);
-/* rec (optional): instead of updating the running statistics, record (batch mean, unbiased batch variance) as 2 C floats at
- * rec + *rec_index_dev * rec_stride; r3d_bn_running_update then applies n_records such records in order, bit for bit
+/* Column statistics, folding and the element-wise passes over segments: sums / outputs [seg][...], BatchNorm vectors of
+ * segment s at pointer + s * bn_stride, running statistics or records updated in segment order = the reference's order of
+ * getFeatures calls.  r3d_colstats_seg: mode 0 (sum x, sum x^2), mode 1 (sum du, sum du*zhat; needs DY and the vectors);
+ * ws: r3d_colstats_seg_ws_words floats.
+ * rec (optional): instead of updating the running statistics, record (batch mean, unbiased batch variance) as 2 C floats at
+ * rec + (*rec_index_dev + s) * rec_stride; r3d_bn_running_update then applies n_records such records in order, bit for bit
  * what the updates would have given one after the other (captured episodes of several streams record, the owner
  * applies them in episode order after the step). */
-int r3d_bn_fold(const float* sums, double count, int C, const float* gamma, const float* beta, float eps,
-                float momentum, float* running_mean /*opt*/, float* running_var /*opt*/, float* mean, float* invstd,
-                float* scale, float* shift, float* rec /*opt*/, const int32_t* rec_index_dev /*opt*/, long rec_stride,
-                void* stream);
-/* the segmented forms (sums / outputs [seg][...], BatchNorm vectors of segment s at pointer + s * bn_stride, running
- * statistics or records updated in segment order = the reference's order of getFeatures calls) */
 long r3d_colstats_seg_ws_words(long M, int C, long rows_a, long rows_b);
 int r3d_colstats_seg(const float* X, long ldx, const float* DY, long lddy, long M, int C, long rows_a, long rows_b, int mode,
                      const float* scale, const float* shift, const float* mean, const float* invstd, long bn_stride, int act,
@@ -278,11 +282,6 @@ int r3d_bn_bwd_apply_seg(const float* Z, long ldz, const float* DY, long lddy, l
 int r3d_bn_running_update(const float* rec, int n_records, long rec_stride, int C, float momentum,
                           const float* bias /*opt: conv bias in front of the BatchNorm*/, float* running_mean,
                           float* running_var, void* stream);
-int r3d_affine_act(const float* Z, long ldz, long M, int C, const float* scale, const float* shift, int act, float* Y,
-                   long ldy, void* stream);
-int r3d_bn_bwd_apply(const float* Z, long ldz, const float* DY, long lddy, long M, int C, const float* scale,
-                     const float* shift, const float* mean, const float* invstd, int act, const float* sums,
-                     double count, float* DZ, long lddz, void* stream);
 long r3d_gemm_tn_ws_words(long M, int Ca, int Cb);
 int r3d_gemm_tn(const float* A, long lda, const float* B, long ldb, long M, int Ca, int Cb, float alpha, float* out,
                 int accumulate, float* ws, void* stream);
@@ -321,54 +320,12 @@ int r3d_edgeconv_bwd(const float* PQ, const int32_t* idx, const float* s1, const
                      const int32_t* rev_ws /* r3d_edge_reverse of the same idx */, float* dW2, float* bn1_sums, float* dPQ,
                      float* ws, void* stream);
 
-/* attention with dropout on the weights (attention.py:45) and flash-style backward */
-/* effective dropout seed = seed + *seed_dev (seed_dev may be NULL); a captured hipGraph bumps *seed_dev per replay */
-int r3d_attention_fwd_train(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
-                            unsigned seed, const unsigned* seed_dev, float* ws /*opt, as above*/, void* stream);
-int r3d_attention_bwd(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
-                      const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, float q_scale, float* dqkv,
-                      long ldd, float* ws /* r3d_attention_ws_words(B, N) floats */, void* stream);
-/* the same; ws_holds_packed_qkv != 0: ws is the workspace r3d_attention_fwd_train ran with on this qkv, untouched since
- * (the bf16 x 3 kernels reuse the packed q | k | v pieces it holds instead of cutting them again) */
-int r3d_attention_bwd_ws(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
-                         const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, float q_scale,
-                         float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
-
-/* batches of episodes: clouds [e seed_group, (e + 1) seed_group) are episode e, whose dropout mask is the one a call on
- * those clouds alone draws with seed + 2 e (the one-episode schedule advances its seed by 2 per episode); outputs are
- * bit for bit those of that call (p_drop = 0: the inference forward of a batch) */
-long r3d_attention_ws_words_ep(int B, int N, int seed_group); /* workspace of the _ep calls: the key-axis split is the one
-                                                                * of ONE episode (seed_group clouds), whatever the batch */
-int r3d_attention_fwd_train_ep(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
-                               unsigned seed, const unsigned* seed_dev, int seed_group, float* ws, void* stream);
-int r3d_attention_bwd_ep(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
-                         const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, float q_scale,
-                         float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
-
-/* the _ep calls at head width D in {32, 64, 96, 128} (the reference's --output_dim; D = 64 is the calls above): qkv holds
- * q / sqrt(D) | k | v at columns 0 | D | 2D (ld >= 3D), out / O / dO D columns, dqkv (ldd >= 3D).  Any other D is refused
- * (R3D_ERR_ARG) before a launch; r3d_attention_ws_words_ep_d returns -1 for it. */
-long r3d_attention_ws_words_ep_d(int B, int N, int seed_group, int D);
-int r3d_attention_fwd_train_ep_d(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
-                                 unsigned seed, const unsigned* seed_dev, int seed_group, int D, float* ws, void* stream);
-int r3d_attention_bwd_ep_d(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO, long lddo,
-                           const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, int D,
-                           float q_scale, float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream);
-
-/* head backward (reference: autograd through models/mpti.py:488-512,571).  r3d_ce_grad -> G = dL/dZ (scaled by the
- * device scalar *gscale); r3d_label_propagate_bwd: adjoint CG solve on the graph r3d_label_propagate left in ws,
- * then gradients w.r.t. the node features; r3d_head_prototypes_bwd: cluster-mean / query-row backward. */
-int r3d_ce_grad(const float* Z, const int32_t* n_proto_dev, int n_cap, int n_query_pts, int n_classes,
-                const int64_t* labels, const float* gscale_dev, float* G, void* stream);
-int r3d_label_propagate_bwd(const float* nodes, long ldn, int D, int kp1, const float* Z, const float* G,
-                            const int32_t* n_dev, int n_cap, float sigma, float alpha, int max_iter, float tol, float* lam,
-                            float* dnodes, long ldd, int32_t* ws, long ws_words, int32_t* stats_out, void* stream);
-int r3d_head_prototypes_bwd(const float* dnodes, long ldd, int n_way, int k_shot, int N, int D, int n_query_pts,
-                            const int32_t* desc, const int32_t* assign, const int32_t* cluster_count, const int32_t* ws,
-                            float* dsfeat, long lds_, float* dqfeat, long ldq, void* stream);
-
-/* the same for n_ep episodes (layouts as the forward `_batched` calls; G, lam, dnodes: n_cap rows per system; *gscale_dev
- * scales every episode alike: the step's loss is the SUM of the episodes' losses) */
+/* head backward (reference: autograd through models/mpti.py:488-512,571) for n_ep episodes.  r3d_ce_grad_batched -> G =
+ * dL/dZ (scaled by the device scalar *gscale_dev); r3d_label_propagate_bwd_batched: adjoint CG solve on the graph
+ * r3d_label_propagate(_batched) left in ws, then gradients w.r.t. the node features; r3d_head_prototypes_bwd_batched:
+ * cluster-mean / query-row backward (dsfeat must be zero-initialised by the caller).  Layouts as the forward `_batched`
+ * calls; G, lam, dnodes: n_cap rows per system; *gscale_dev scales every episode alike: the step's loss is the SUM of the
+ * episodes' losses. */
 int r3d_ce_grad_batched(int n_ep, const float* Z, const int32_t* n_proto_dev, long desc_stride, int n_cap, int n_query_pts,
                         int n_classes, const int64_t* labels, const float* gscale_dev, float* G, void* stream);
 int r3d_label_propagate_bwd_batched(int n_ep, const float* nodes, long ldn, int D, int kp1, const float* Z, const float* G,
@@ -397,24 +354,19 @@ int r3d_contrast_fwd_batched(int n_ep, const float* feat, long ldf, long feat_ep
                              float temp, float* loss_out, float* ws, long ws_words, long ws_stride, void* stream);
 int r3d_contrast_bwd_batched(int n_ep, int D, int n_way, int k_shot, int N, const float* gscale_dev, float* dfeat, long ldd,
                              long dfeat_ep_rows, float* dW, float* db, float* ws, long ws_stride, void* stream);
+/* training-only debug metrics (mpti.py:515-568): out4 = query_acc_LP, query_acc_original, clean_ratio_LP_avg,
+ * clean_ratio_original_avg per episode; proto_ws: the scratch r3d_head_prototypes_batched ran with */
 int r3d_train_metrics_batched(int n_ep, const int32_t* pred, const int64_t* query_y, const int64_t* gt_query_y, int n_query_pts,
                               const float* Z, long z_ep_rows, const int32_t* desc, long desc_stride, const int32_t* proto_ws,
                               long pws_stride, const int32_t* assign, long assign_stride, const int32_t* gt_support_y, int n_way,
                               int k_shot, int N, float* out4 /*(n_ep,4)*/, void* stream);
-/* training-only debug metrics (mpti.py:515-568): out4 = query_acc_LP, query_acc_original, clean_ratio_LP_avg,
- * clean_ratio_original_avg */
-int r3d_train_metrics(const int32_t* pred, const int64_t* query_y, const int64_t* gt_query_y, int n_query_pts, const float* Z,
-                      const int32_t* desc, const int32_t* proto_ws, const int32_t* assign, const int32_t* gt_support_y,
-                      int n_way, int k_shot, int N, float* out4, void* stream);
 
 /* ---- clean-shot detection, eval only (models/mpti.py:87-223, 316-371) -----------------
  * Per shot: box means of foreground features at scales (1,1,1) and (2,2,1) -> cosine map ->
- * majority vote -> shot_keep (n_way*k_shot) int32 (0 = drop the shot's foreground). */
+ * majority vote -> shot_keep (n_way*k_shot) int32 (0 = drop the shot's foreground).
+ * Per episode: feat (S*N, ldf), episode e feat_ep_rows rows further on; support_x (S, Cin, N); support_y (S, N);
+ * dbg_cos_sum optional (n_way, 2, 4*k_shot); ws: r3d_clean_ws_words int32 words, episode e at ws + e * ws_stride. */
 long r3d_clean_ws_words(int n_way, int k_shot);
-int r3d_clean_shot_detect(const float* feat /*(S*N,ldf)*/, long ldf, int D, const float* support_x /*(S,Cin,N)*/,
-                          int Cin, const int32_t* support_y, int n_way, int k_shot, int N, int32_t* shot_keep,
-                          float* dbg_cos_sum /*opt (n_way,2,4*k_shot)*/, int32_t* ws, void* stream);
-
 int r3d_clean_shot_detect_batched(int n_ep, const float* feat, long ldf, long feat_ep_rows, int D, const float* support_x,
                                   int Cin, const int32_t* support_y, int n_way, int k_shot, int N, int32_t* shot_keep,
                                   float* dbg_cos_sum, int32_t* ws, long ws_stride, void* stream);

@@ -19,131 +19,56 @@ c_fl = ctypes.c_float
 c_d = ctypes.c_double
 c_u = ctypes.c_uint
 
-_SIGS = {
-    "r3d_last_error_string": (ctypes.c_char_p, []),
-    "r3d_abi_version": (c_i, []),
-    "r3d_cm_to_pm": (c_i, [c_f, c_i, c_i, c_i, c_f, c_l, c_f]),
-    "r3d_pm_to_cm": (c_i, [c_f, c_l, c_i, c_i, c_i, c_f, c_f]),
-    "r3d_pm_to_cm_pitched": (c_i, [c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f]),
-    "r3d_cm_pitch": (c_l, [c_i]),
-    "r3d_copy_cols": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_f]),
-    "r3d_sqnorm": (c_i, [c_f, c_l, c_l, c_i, c_f, c_f]),
-    "r3d_knn_topk": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-    "r3d_pointwise_conv": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_f, c_i, c_f, c_l, c_f]),
-    "r3d_edgeconv_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_f]),
-    "r3d_attention_ws_words": (c_l, [c_i, c_i]),
-    "r3d_knn_norm_ws_words": (c_l, [c_i, c_i]),
-    "r3d_attention_fwd": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_f, c_f]),
-    "r3d_head_desc_words": (c_i, []),
-    "r3d_debug_poison_lds": (c_i, [c_u, c_f, c_f]),
-    "r3d_debug_set_cg_spmv_lds_min_blocks": (c_i, [c_i]),
-    "r3d_debug_set_gemm_bx3": (c_i, [c_i]),
-    "r3d_set_matrix_arith": (c_i, [c_i]),
-    "r3d_get_matrix_arith": (c_i, []),
-    "r3d_head_max_k": (c_i, []),
-    "r3d_fps_sample_count_table": (c_i, [c_i, c_i, c_f, c_f]),
-    "r3d_head_proto_ws_words": (c_l, [c_i, c_i, c_i]),
-    "r3d_head_proto_ws_offsets": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_l)]),
-    "r3d_head_prototypes": (c_i, [c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_l,
-                                  c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_f]),
-    "r3d_lp_ws_words": (c_l, [c_i, c_i]),
-    "r3d_lp_ws_offsets": (c_i, [c_i, c_i, ctypes.POINTER(c_l)]),
-    "r3d_label_propagate": (c_i, [c_f, c_l, c_i, c_f, c_i, c_f, c_f, c_f, c_i, c_fl, c_fl, c_i, c_fl, c_f, c_f,
-                                  c_l, c_f, c_f]),
-    "r3d_graph_set_lp_budget": (c_i, [c_f, c_f, c_i, ctypes.POINTER(c_i)]),
-    "r3d_pointwise_conv_acc": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_f, c_i, c_f, c_l, c_f]),
-    "r3d_edgeconv_train_fwd_minmax": (c_i, [c_f, c_f, c_f, c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-    "r3d_edge_select": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_l, c_f, c_l, c_f]),
-    "r3d_pointwise_conv_stats_ws_words": (c_l, [c_l, c_i]),
-    "r3d_pointwise_conv_stats": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_f, c_f]),
-    "r3d_pointwise_conv_stats2": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_l, c_l, c_f, c_f, c_f, c_f]),
-    "r3d_colreduce": (c_i, [c_f, c_i, c_i, c_f, c_f]),
-    "r3d_colstats_ws_words": (c_l, [c_l, c_i]),
-    "r3d_colstats": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f]),
-    "r3d_bn_fold": (c_i, [c_f, c_d, c_i, c_f, c_f, c_fl, c_fl, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_f]),
-    "r3d_bn_running_update": (c_i, [c_f, c_i, c_l, c_i, c_fl, c_f, c_f, c_f, c_f]),
-    "r3d_affine_act": (c_i, [c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_f, c_l, c_f]),
-    "r3d_bn_bwd_apply": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_d, c_f, c_l, c_f]),
-    "r3d_gemm_tn_ws_words": (c_l, [c_l, c_i, c_i]),
-    "r3d_gemm_tn": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_i, c_fl, c_f, c_i, c_f, c_f]),
-    "r3d_add_cols": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_f]),
-    "r3d_edgeconv_train_ws_words": (c_l, [c_i, c_i]),
-    "r3d_edge_stats1": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
-    "r3d_edge_reverse_ws_words": (c_l, [c_i, c_i, c_i]),
-    "r3d_edge_reverse": (c_i, [c_f, c_i, c_i, c_i, c_f, c_l, c_f]),
-    "r3d_edgeconv_bwd": (c_i, [c_f] * 11 + [c_l, c_f, c_f, c_l, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
-    "r3d_attention_fwd_train": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_fl, c_u, c_f, c_f, c_f]),
-    "r3d_attention_bwd": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_fl, c_f, c_l, c_f, c_f]),
-    "r3d_attention_bwd_ws": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_fl, c_f, c_l, c_f, c_i, c_f]),
-    "r3d_ce_grad": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
-    "r3d_label_propagate_bwd": (c_i, [c_f, c_l, c_i, c_i, c_f, c_f, c_f, c_i, c_fl, c_fl, c_i, c_fl, c_f, c_f, c_l, c_f, c_l, c_f, c_f]),
-    "r3d_head_prototypes_bwd": (c_i, [c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_l, c_f, c_l, c_f]),
-    "r3d_contrast_ws_words": (c_l, [c_i, c_i, c_i]),
-    "r3d_contrast_fwd": (c_i, [c_f, c_l, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_fl, c_f, c_f, c_l, c_f]),
-    "r3d_contrast_bwd": (c_i, [c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_f, c_f, c_f, c_f]),
-    "r3d_train_metrics": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f]),
-    "r3d_clean_ws_words": (c_l, [c_i, c_i]),
-    "r3d_clean_shot_detect": (c_i, [c_f, c_l, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
-    "r3d_protonet_head": (c_i, [c_f, c_l, c_f, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_f]),
-    "r3d_protonet_head_ws_words": (c_l, [c_i, c_i, c_i]),
-    "r3d_protonet_head_batched": (c_i, [c_i, c_f, c_l, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f]),
-    "r3d_count_correct_batched": (c_i, [c_i, c_f, c_f, c_l, c_f, c_f]),
-    "r3d_protonet_head_train_ws_words": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
-    "r3d_protonet_head_train_fwd": (c_i, [c_i, c_f, c_l, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f]),
-    "r3d_protonet_head_bwd": (c_i, [c_i, c_f, c_l, c_l, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_l, c_f, c_l, c_l, c_f,
-                                    c_l, c_f]),
-    "r3d_miou_accumulate": (c_i, [c_f, c_f, c_l, c_f, c_i, c_i, c_f, c_f]),
-    "r3d_query_logits_ce": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
-    # ---- ABI version 3: segments (training encoder) and batches of episodes (head)
-    "r3d_knn_topk_batched": (c_i, [c_f, c_l, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_l, c_f, c_f, c_f, c_f]),
-    "r3d_knn_ws_words": (c_l, [c_i, c_i, c_i, c_i, c_i]),
-    "r3d_debug_set_knn_bf16_threshold": (c_i, [c_i]),
-    "r3d_debug_set_knn_bf16_filter": (c_i, [c_i]),
-    "r3d_set_wpack_in_capture": (c_i, [c_i]),
-    "r3d_pointwise_conv_stats_seg": (c_i, [c_f, c_l, c_f, c_l, c_i, c_i, c_f, c_l, c_l, c_l, c_f, c_f, c_f]),
-    "r3d_colreduce_seg": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
-    "r3d_colstats_seg_ws_words": (c_l, [c_l, c_i, c_l, c_l]),
-    "r3d_colstats_seg": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_l, c_l, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_f, c_f]),
-    "r3d_bn_fold_seg": (c_i, [c_f, c_i, c_d, c_d, c_i, c_f, c_f, c_fl, c_fl, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_l, c_f]),
-    "r3d_affine_act_seg": (c_i, [c_f, c_l, c_l, c_i, c_l, c_l, c_f, c_f, c_l, c_i, c_f, c_l, c_f]),
-    "r3d_bn_bwd_apply_seg": (c_i, [c_f, c_l, c_f, c_l, c_l, c_i, c_l, c_l, c_f, c_f, c_f, c_f, c_l, c_i, c_f, c_d, c_d, c_f, c_l, c_f]),
-    "r3d_attention_ws_words_ep": (c_l, [c_i, c_i, c_i]),
-    "r3d_attention_fwd_train_ep": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_f, c_f]),
-    "r3d_attention_bwd_ep": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_fl, c_f, c_l, c_f, c_i, c_f]),
-    "r3d_attention_ws_words_ep_d": (c_l, [c_i, c_i, c_i, c_i]),
-    "r3d_attention_fwd_train_ep_d": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_i, c_f, c_f]),
-    "r3d_attention_bwd_ep_d": (c_i, [c_f, c_l, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_fl, c_u, c_f, c_i, c_i, c_fl, c_f, c_l, c_f, c_i,
-                                     c_f]),
-    "r3d_head_prototypes_batched": (c_i, [c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_l, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_i,
-                                          c_f, c_l, c_l, c_f, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l, c_l, c_i, c_f]),
-    "r3d_head_prototypes_bwd_batched": (c_i, [c_i, c_f, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l,
-                                              c_f, c_l, c_l, c_f, c_l, c_l, c_f]),
-    "r3d_graph_weights_verify_words": (c_l, [c_i, c_i]),
-    "r3d_graph_weights_verify": (c_i, [c_i, c_f, c_l, c_i, c_f, c_l, c_i, c_i, c_fl, c_f, c_l, c_l, c_f, c_f, c_f]),
-    "r3d_label_propagate_solve_batched": (c_i, [c_i, c_f, c_f, c_l, c_i, c_i, c_fl, c_i, c_fl, c_f, c_f, c_l, c_l, c_f, c_l, c_f]),
-    "r3d_label_propagate_batched": (c_i, [c_i, c_f, c_l, c_i, c_f, c_i, c_f, c_f, c_f, c_l, c_i, c_fl, c_fl, c_i, c_fl, c_f, c_f,
-                                          c_l, c_l, c_f, c_l, c_f]),
-    "r3d_label_propagate_bwd_batched": (c_i, [c_i, c_f, c_l, c_i, c_i, c_f, c_f, c_f, c_l, c_i, c_fl, c_fl, c_i, c_fl, c_f, c_f,
-                                              c_l, c_f, c_l, c_l, c_f, c_l, c_f]),
-    "r3d_ce_grad_batched": (c_i, [c_i, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
-    "r3d_query_logits_ce_batched": (c_i, [c_i, c_f, c_l, c_f, c_l, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
-    "r3d_contrast_fwd_batched": (c_i, [c_i, c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_fl, c_f, c_f, c_l, c_l, c_f]),
-    "r3d_contrast_bwd_batched": (c_i, [c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_l, c_l, c_f, c_f, c_f, c_l, c_f]),
-    "r3d_train_metrics_batched": (c_i, [c_i, c_f, c_f, c_f, c_i, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_l, c_f, c_i, c_i, c_i, c_f, c_f]),
-    "r3d_clean_shot_detect_batched": (c_i, [c_i, c_f, c_l, c_l, c_i, c_f, c_i, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_l, c_f]),
-    # ---- additive in ABI version 5: training augmentation of prepared clouds
-    "r3d_augment_clouds": (c_i, [c_f, c_l, c_l, c_l, c_f, c_l, c_l, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_fl, c_i, c_u, c_f,
-                                 c_u, c_f, c_f, c_f, c_f]),
-}
+_SCALARS = {"unsigned": c_u, "double": c_d, "float": c_fl, "long": c_l, "int": c_i, "int32_t": c_i}
 
-_lib = None
+
+def _ctype(decl, what):
+    """ctypes class of `decl`, a C declaration of a type followed by a name: any pointer travels as void*, a scalar by value
+    as its C type.  Anything else raises instead of guessing (int64_t by value among them: none exists, and as c_int it
+    would lose its upper half)."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return c_f
+    if len(words) == 2 and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    raise RuntimeError("r3dfsseg_amd: cannot bind %s: unrecognised declaration %r" % (what, " ".join(decl.split())))
+
+
+def parse_header(txt):
+    """(names, signatures) of the `r3d_*` functions a C header declares: the sorted names, and name -> (restype, [argtypes])
+    for ctypes.  One pass over the text without its comments serves both.  Every name needs a prototype
+    `type r3d_name(parameters);` whose types _ctype knows; else this raises and names the function."""
+    txt = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", txt, flags=re.S))
+    names = sorted(set(re.findall(r"\b(r3d_[a-z0-9_]+)\s*\(", txt)))
+    sigs = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(r3d_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;", txt):
+        if name in sigs:
+            raise RuntimeError("r3dfsseg_amd: %s is declared twice" % name)
+        params = [p.strip() for p in params.split(",")]
+        if params in (["void"], [""]):
+            params = []
+        if ret.replace("*", " * ").split() == ["const", "char", "*"]:
+            res = ctypes.c_char_p
+        elif "*" in ret:
+            raise RuntimeError("r3dfsseg_amd: cannot bind %s: unrecognised return type %r" % (name, ret.strip()))
+        else:
+            res = _ctype(ret + " " + name, "the return type of " + name)
+        sigs[name] = (res, [_ctype(p_, "parameter %d of %s" % (i, name)) for i, p_ in enumerate(params)])
+    if sorted(sigs) != names:
+        raise RuntimeError("r3dfsseg_amd: no prototype parsed for %s" % ", ".join(sorted(set(names) - set(sigs))))
+    return names, sigs
+
+
+# the binding IS the header: read once, at import
+_SYMBOLS, _SIGS = parse_header(open(HEADER_PATH).read())
 
 
 def header_symbols():
     """Function names declared in include/r3d.h."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(r3d_[a-z0-9_]+)\s*\(", txt)))
+    return list(_SYMBOLS)
+
+
+_lib = None
 
 
 ABI_VERSION = 5  # include/r3d.h; 5: r3d_knn_topk_batched takes one workspace of r3d_knn_ws_words floats

@@ -21,7 +21,8 @@ SOURCES = ["error.hip", "knn.hip", "gemm.hip", "gemm_bx3.hip", "edgeconv.hip", "
 # the label-propagation graph weights came out wrong in ~20 % of the solves that ran beside the bf16 x 3 attention
 # kernels, and never once in a build without these instructions.  (The host pass prints "'-packed-fp32-ops' is not a
 # recognized feature" for the second flag: it only applies to the device pass.)
-FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")  # r3d.h: csrc/common.h includes it, so definitions meet their prototypes
+FLAGS = ["-I", INCLUDE, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
          "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value"]
 
@@ -35,7 +36,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdr = [os.path.join(CSRC, h) for h in ("common.h", "edge_tile.h", "edgeconv_bwd_bx3.h")]
+    hdr = [os.path.join(CSRC, h) for h in ("common.h", "edge_tile.h", "edgeconv_bwd_bx3.h")] + [os.path.join(INCLUDE, "r3d.h")]
     objs = []
     procs = []
     for s in [x for x in SOURCES if os.path.exists(os.path.join(CSRC, x))]:

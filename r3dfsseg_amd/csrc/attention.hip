@@ -644,8 +644,7 @@ extern "C" long r3d_attention_ws_words_ep_d(int B, int N, int group, int D) {
   // ... followed by the packed bf16 x 3 operands (q | k | v | dO: 96 words per point and 64-channel block each)
   return attention_part_words(B, N, group > 0 ? group : B, D) + 4L * B * N * (AB_ROW / 2) * ((D + 63) / 64) + 64;
 }
-extern "C" long r3d_attention_ws_words_ep(int B, int N, int group) { return r3d_attention_ws_words_ep_d(B, N, group, 64); }
-extern "C" long r3d_attention_ws_words(int B, int N) { return r3d_attention_ws_words_ep(B, N, 0); }
+extern "C" long r3d_attention_ws_words(int B, int N) { return r3d_attention_ws_words_ep_d(B, N, 0, 64); }
 
 template <int D>
 static void attention_launch_d(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
@@ -697,12 +696,6 @@ static int attention_launch(const float* qkv, long ld, int B, int N, float* out,
   return R3D_OK;
 }
 
-extern "C" int r3d_attention_fwd(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out,
-                                 float* ws /* opt: r3d_attention_ws_words(B, N) floats enable the key split */,
-                                 void* stream) {
-  return attention_launch(qkv, ld, B, N, out, ldo, lse_out, 0.f, 0u, nullptr, 0, 64, ws, stream);
-}
-
 // training forward: dropout p_drop on the attention weights with the stateless mask of attn_keep.
 // Effective seed = seed + *seed_dev (seed_dev may be NULL): a captured hipGraph bumps the device word per replay.
 extern "C" int r3d_attention_fwd_train(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out,
@@ -711,14 +704,8 @@ extern "C" int r3d_attention_fwd_train(const float* qkv, long ld, int B, int N, 
   return attention_launch(qkv, ld, B, N, out, ldo, lse_out, p_drop, seed, seed_dev, 0, 64, ws, stream);
 }
 // the same over a batch of episodes: clouds [e * seed_group, (e + 1) * seed_group) are episode e, whose dropout mask is
-// the one a call on those clouds alone would draw with seed + 2 e (the eager schedule advances its seed by 2 per episode)
-extern "C" int r3d_attention_fwd_train_ep(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out,
-                                          float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, float* ws,
-                                          void* stream) {
-  R3D_REQUIRE(lse_out, "r3d_attention_fwd_train: lse_out is required (saved for the backward pass)");
-  return attention_launch(qkv, ld, B, N, out, ldo, lse_out, p_drop, seed, seed_dev, seed_group, 64, ws, stream);
-}
-// the same at head width D (32, 64, 96 or 128): qkv holds q | k | v at columns 0 | D | 2D, out D columns; ws:
+// the one a call on those clouds alone would draw with seed + 2 e (the eager schedule advances its seed by 2 per episode),
+// at head width D (32, 64, 96 or 128): qkv holds q | k | v at columns 0 | D | 2D, out D columns; ws:
 // r3d_attention_ws_words_ep_d(B, N, seed_group, D) floats.  p_drop = 0 is the inference forward.
 extern "C" int r3d_attention_fwd_train_ep_d(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out,
                                             float p_drop, unsigned seed, const unsigned* seed_dev, int seed_group, int D,
@@ -1370,18 +1357,11 @@ extern "C" int r3d_attention_bwd_ep_d(const float* qkv, long ld, int B, int N, c
   R3D_LAUNCH_CHECK("r3d_attention_bwd");
   return R3D_OK;
 }
-extern "C" int r3d_attention_bwd_ep(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO,
-                                    long lddo, const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev,
-                                    int seed_group, float q_scale, float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv,
-                                    void* stream) {
-  return r3d_attention_bwd_ep_d(qkv, ld, B, N, O, ldo, dO, lddo, lse, p_drop, seed, seed_dev, seed_group, 64, q_scale, dqkv,
-                                ldd, ws, ws_holds_packed_qkv, stream);
-}
 extern "C" int r3d_attention_bwd_ws(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO,
                                     long lddo, const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev,
                                     float q_scale, float* dqkv, long ldd, float* ws, int ws_holds_packed_qkv, void* stream) {
-  return r3d_attention_bwd_ep(qkv, ld, B, N, O, ldo, dO, lddo, lse, p_drop, seed, seed_dev, 0, q_scale, dqkv, ldd, ws,
-                              ws_holds_packed_qkv, stream);
+  return r3d_attention_bwd_ep_d(qkv, ld, B, N, O, ldo, dO, lddo, lse, p_drop, seed, seed_dev, 0, 64, q_scale, dqkv, ldd, ws,
+                                ws_holds_packed_qkv, stream);
 }
 extern "C" int r3d_attention_bwd(const float* qkv, long ld, int B, int N, const float* O, long ldo, const float* dO,
                                  long lddo, const float* lse, float p_drop, unsigned seed, const unsigned* seed_dev,

@@ -393,14 +393,8 @@ extern "C" int r3d_clean_shot_detect_batched(int n_ep, const float* feat, long l
   R3D_LAUNCH_CHECK("r3d_clean_shot_detect");
   return R3D_OK;
 }
-extern "C" int r3d_clean_shot_detect(const float* feat, long ldf, int D, const float* support_x, int Cin,
-                                     const int32_t* support_y, int n_way, int k_shot, int N, int32_t* shot_keep,
-                                     float* dbg_cos_sum, int32_t* ws, void* stream) {
-  return r3d_clean_shot_detect_batched(1, feat, ldf, 0, D, support_x, Cin, support_y, n_way, k_shot, N, shot_keep, dbg_cos_sum, ws,
-                                       0, stream);
-}
 
-// Z (n_q*N, 4) fp32 similarity rows (feed r3d_query_logits_ce with n_proto = 0); more than 3 ways: two planes
+// Z (n_q*N, 4) fp32 similarity rows (feed r3d_query_logits_ce_batched with n_proto = 0); more than 3 ways: two planes
 // (2, n_q*N, 4), classes 4..7 in plane 1 (r3d_query_logits_ce_batched with z_ep_rows = n_q*N).  ws: S*2*256 floats.
 extern "C" int r3d_protonet_head(const float* sfeat, long ldf, const float* qfeat, long ldq, int D,
                                  const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts, int method,

@@ -4,12 +4,21 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "r3d.h"  // the C ABI: every definition is compiled against its prototype
+
 #define R3D_OK 0
 #define R3D_ERR_ARG 1
 #define R3D_ERR_LAUNCH 2
 #define R3D_ERR_UNSUPPORTED 3
 
 void r3d_set_error(const char* fmt, ...);
+
+// launchers shared between translation units (not part of the C ABI: hidden from the dynamic symbol table)
+#define R3D_INTERNAL __attribute__((visibility("hidden")))
+// gemm.hip: (B*N, ld) point-major -> (B, C, pitch) channel-major, pitch >= N
+R3D_INTERNAL int r3d_pm_to_cm_pitched_launch(const float* in, long ld, int B, int C, int N, float* out, long pitch, void* stream);
+// train_ops.hip: [chunks][2][C] partial column sums -> sums_out [seg][2][C]
+R3D_INTERNAL int r3d_colreduce_launch(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out, void* stream);
 
 #define R3D_REQUIRE(cond, ...)          \
   do {                                  \

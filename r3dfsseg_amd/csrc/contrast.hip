@@ -605,10 +605,3 @@ extern "C" int r3d_train_metrics_batched(int n_ep, const int32_t* pred, const in
   R3D_LAUNCH_CHECK("r3d_train_metrics");
   return R3D_OK;
 }
-extern "C" int r3d_train_metrics(const int32_t* pred, const int64_t* query_y, const int64_t* gt_query_y, int n_query_pts,
-                                 const float* Z, const int32_t* desc, const int32_t* proto_ws /* comp at offset 0 */,
-                                 const int32_t* assign, const int32_t* gt_support_y, int n_way, int k_shot, int N,
-                                 float* out4, void* stream) {
-  return r3d_train_metrics_batched(1, pred, query_y, gt_query_y, n_query_pts, Z, 0, desc, 0, proto_ws, 0, assign, 0, gt_support_y,
-                                   n_way, k_shot, N, out4, stream);
-}

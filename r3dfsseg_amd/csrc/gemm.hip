@@ -157,38 +157,20 @@ extern "C" int r3d_pointwise_conv(const float* X, long ldx, const float* W, long
 // sums_out[0..Co) = sum_m Out[m][c], sums_out[Co..2Co) = sum_m Out[m][c]^2, produced in the GEMM epilogue (one
 // partial per 64-row tile, added in ascending tile order in fp64) instead of a second pass over Out.
 // ws: r3d_pointwise_conv_stats_ws_words(M, Co) floats.
-extern "C" int r3d_colreduce(const float* part, int chunks, int C, float* sums_out, void* stream);
 extern "C" long r3d_pointwise_conv_stats_ws_words(long M, int Co) { return (long)r3d_cdiv(M, G_BM) * 2 * Co; }
 extern "C" int r3d_pointwise_conv_stats(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out,
                                         long ldo, float* sums_out, float* ws, void* stream) {
   R3D_REQUIRE(sums_out && ws, "r3d_pointwise_conv_stats: null pointer");
   int rc = pointwise_launch(X, ldx, W, M, K, Co, nullptr, nullptr, R3D_ACT_NONE, Out, ldo, 0, ws, stream);
   if (rc) return rc;
-  return r3d_colreduce(ws, r3d_cdiv(M, G_BM), Co, sums_out, stream);
+  return r3d_colreduce_launch(ws, r3d_cdiv(M, G_BM), 0, 1, Co, sums_out, stream);
 }
 
-// The same over TWO row segments with separate batch statistics (the support clouds and the query clouds of an episode
-// go through one GEMM launch, mpti.py:434,436 keep their BatchNorm statistics apart): rows [0, M_first) -> sums_a,
-// rows [M_first, M) -> sums_b.  M_first must be a multiple of the 64-row tile.
-extern "C" int r3d_pointwise_conv_stats2(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out,
-                                         long ldo, long M_first, float* sums_a, float* sums_b, float* ws, void* stream) {
-  R3D_REQUIRE(sums_a && sums_b && ws, "r3d_pointwise_conv_stats2: null pointer");
-  R3D_REQUIRE(M_first > 0 && M_first < M && M_first % G_BM == 0,
-              "r3d_pointwise_conv_stats2: first segment of %ld rows (of %ld) must be a positive multiple of %d", M_first, M,
-              G_BM);
-  int rc = pointwise_launch(X, ldx, W, M, K, Co, nullptr, nullptr, R3D_ACT_NONE, Out, ldo, 0, ws, stream);
-  if (rc) return rc;
-  const int tiles_a = (int)(M_first / G_BM);
-  rc = r3d_colreduce(ws, tiles_a, Co, sums_a, stream);
-  if (rc) return rc;
-  return r3d_colreduce(ws + (long)tiles_a * 2 * Co, r3d_cdiv(M, G_BM) - tiles_a, Co, sums_b, stream);
-}
-
-// ... and over the alternating segments of a batch of episodes (common.h: r3d_segmap; rows_a, rows_b multiples of the
-// 64-row tile, rows_b == 0: equal segments): ONE GEMM launch over all rows, sums_out [seg][2][Co] reduced per segment
-// from the tile partials.  A tile belongs to one segment and a segment's tiles are added relative to its first one, so
-// its statistics are bit for bit those of the episode running alone.
-extern "C" int r3d_colreduce_seg(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out, void* stream);
+// The same over the alternating segments of a batch of episodes (common.h: r3d_segmap; rows_a, rows_b multiples of the
+// 64-row tile, rows_b == 0: equal segments; mpti.py:434,436 keep the BatchNorm statistics of the support and the query
+// clouds apart): ONE GEMM launch over all rows, sums_out [seg][2][Co] reduced per segment from the tile partials.  A tile
+// belongs to one segment and a segment's tiles are added relative to its first one, so its statistics are bit for bit
+// those of the episode running alone.
 extern "C" int r3d_pointwise_conv_stats_seg(const float* X, long ldx, const float* W, long M, int K, int Co, float* Out,
                                             long ldo, long rows_a, long rows_b, float* sums_out, float* ws, void* stream) {
   R3D_REQUIRE(sums_out && ws, "r3d_pointwise_conv_stats_seg: null pointer");
@@ -198,7 +180,7 @@ extern "C" int r3d_pointwise_conv_stats_seg(const float* X, long ldx, const floa
               G_BM);
   int rc = pointwise_launch(X, ldx, W, M, K, Co, nullptr, nullptr, R3D_ACT_NONE, Out, ldo, 0, ws, stream);
   if (rc) return rc;
-  return r3d_colreduce_seg(ws, r3d_cdiv(rows_a, G_BM), r3d_cdiv(rows_b, G_BM), sm.n_seg(M), Co, sums_out, stream);
+  return r3d_colreduce_launch(ws, r3d_cdiv(rows_a, G_BM), r3d_cdiv(rows_b, G_BM), sm.n_seg(M), Co, sums_out, stream);
 }
 
 // Out += act(scale * X W^T + shift): gradient accumulation into a (slice of a) wider buffer
@@ -286,9 +268,8 @@ extern "C" int r3d_pm_to_cm(const float* in, long ld, int B, int C, int N, float
   return R3D_OK;
 }
 
-// same with a row pitch >= N between channels (out is (B, C, pitch))
-extern "C" int r3d_pm_to_cm_pitched(const float* in, long ld, int B, int C, int N, float* out, long pitch,
-                                    void* stream) {
+// same with a row pitch >= N between channels (out is (B, C, pitch)): the kNN launcher's channel-major copy
+int r3d_pm_to_cm_pitched_launch(const float* in, long ld, int B, int C, int N, float* out, long pitch, void* stream) {
   R3D_REQUIRE(in && out && B > 0 && C > 0 && N > 0 && ld >= C && pitch >= N, "r3d_pm_to_cm_pitched: bad arguments");
   dim3 grid(r3d_cdiv(N, 32), r3d_cdiv(C, 32), B);
   hipLaunchKernelGGL(r3d_pm_to_cm_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, ld, C, N, out, pitch);

@@ -1709,11 +1709,16 @@ __global__ void r3d_ce_grad_kernel(const float4* __restrict__ Z, const int* __re
 }
 
 // Backward through label propagation + affinity.  Requires ws exactly as r3d_label_propagate left it.
-// G (n_cap,4) = dL/dZ (from r3d_ce_grad); lam scratch (n_cap,4); dnodes (n_cap, ldd) out.
-static int label_propagate_bwd_impl(int n_ep, const HgEp& ep, const float* nodes, long ldn, int D, int kp1, const float* Z,
-                                    const float* G, const int32_t* n_dev, int n_cap, float sigma, float alpha, int max_iter,
-                                    float tol, float* lam, float* dnodes, long ldd, int32_t* ws, long ws_words,
-                                    int32_t* stats_out, void* stream) {
+// G (n_cap,4) = dL/dZ (from r3d_ce_grad_batched); lam scratch (n_cap,4); dnodes (n_cap, ldd) out.
+// n_ep systems at once (layout as r3d_label_propagate_batched; G, lam, dnodes: n_cap rows per system)
+extern "C" int r3d_label_propagate_bwd_batched(int n_ep, const float* nodes, long ldn, int D, int kp1, const float* Z,
+                                               const float* G, const int32_t* n_dev, long desc_stride, int n_cap, float sigma,
+                                               float alpha, int max_iter, float tol, float* lam, float* dnodes, long ldd,
+                                               int32_t* ws, long ws_words, long ws_stride, int32_t* stats_out,
+                                               long stats_stride, void* stream) {
+  HgEp ep{};
+  ep.nodes = ep.z = ep.g = ep.lam = ep.dn = n_cap;
+  ep.desc = desc_stride; ep.ws = ws_stride; ep.stats = stats_stride;
   R3D_REQUIRE(nodes && Z && G && n_dev && lam && dnodes && ws, "r3d_label_propagate_bwd: null pointer");
   R3D_REQUIRE(n_cap > 0 && kp1 >= 2 && ws_words >= r3d_lp_ws_words(n_cap, kp1),
               "r3d_label_propagate_bwd: workspace of %ld words is shorter than r3d_lp_ws_words(%d, %d)", ws_words, n_cap, kp1);
@@ -1737,28 +1742,8 @@ static int label_propagate_bwd_impl(int n_ep, const HgEp& ep, const float* nodes
   R3D_LAUNCH_CHECK("r3d_label_propagate_bwd");
   return R3D_OK;
 }
-extern "C" int r3d_label_propagate_bwd(const float* nodes, long ldn, int D, int kp1, const float* Z, const float* G,
-                                       const int32_t* n_dev, int n_cap, float sigma, float alpha, int max_iter, float tol,
-                                       float* lam, float* dnodes, long ldd, int32_t* ws, long ws_words, int32_t* stats_out,
-                                       void* stream) {
-  const HgEp one{};
-  return label_propagate_bwd_impl(1, one, nodes, ldn, D, kp1, Z, G, n_dev, n_cap, sigma, alpha, max_iter, tol, lam, dnodes, ldd,
-                                  ws, ws_words, stats_out, stream);
-}
-// n_ep systems at once (layout as r3d_label_propagate_batched; G, lam, dnodes: n_cap rows per system)
-extern "C" int r3d_label_propagate_bwd_batched(int n_ep, const float* nodes, long ldn, int D, int kp1, const float* Z,
-                                               const float* G, const int32_t* n_dev, long desc_stride, int n_cap, float sigma,
-                                               float alpha, int max_iter, float tol, float* lam, float* dnodes, long ldd,
-                                               int32_t* ws, long ws_words, long ws_stride, int32_t* stats_out,
-                                               long stats_stride, void* stream) {
-  HgEp ep{};
-  ep.nodes = ep.z = ep.g = ep.lam = ep.dn = n_cap;
-  ep.desc = desc_stride; ep.ws = ws_stride; ep.stats = stats_stride;
-  return label_propagate_bwd_impl(n_ep, ep, nodes, ldn, D, kp1, Z, G, n_dev, n_cap, sigma, alpha, max_iter, tol, lam, dnodes, ldd,
-                                  ws, ws_words, stats_out, stream);
-}
 
-// G = dL/dZ of n_ep systems (n_ep == 1: the ABI-version-2 call).  labels: n_query_pts int64 per system; *gscale_dev scales
+// G = dL/dZ of n_ep systems.  labels: n_query_pts int64 per system; *gscale_dev scales
 // every system alike (the step's loss is the SUM of the episodes' losses).
 extern "C" int r3d_ce_grad_batched(int n_ep, const float* Z, const int32_t* n_proto_dev, long desc_stride, int n_cap,
                                    int n_query_pts, int n_classes, const int64_t* labels, const float* gscale_dev, float* G,
@@ -1775,10 +1760,6 @@ extern "C" int r3d_ce_grad_batched(int n_ep, const float* Z, const int32_t* n_pr
                      n_proto_dev, n_cap, n_query_pts, n_classes, (const long long*)labels, gscale_dev, (float4*)G, Z2, G2, ep);
   R3D_LAUNCH_CHECK("r3d_ce_grad");
   return R3D_OK;
-}
-extern "C" int r3d_ce_grad(const float* Z, const int32_t* n_proto_dev, int n_cap, int n_query_pts, int n_classes,
-                           const int64_t* labels, const float* gscale_dev, float* G, void* stream) {
-  return r3d_ce_grad_batched(1, Z, n_proto_dev, 0, n_cap, n_query_pts, n_classes, labels, gscale_dev, G, stream);
 }
 
 // logits (n_q, n_classes, N) fp32, loss (1) fp32, pred (n_q*N) int32 (argmax), labels int64 -- per system; system e reads
@@ -1798,11 +1779,6 @@ extern "C" int r3d_query_logits_ce_batched(int n_ep, const float* Z, long z_ep_r
                      n_proto_dev, n_q, N, n_classes, (const long long*)labels, logits, loss_out, pred_out, ep);
   R3D_LAUNCH_CHECK("r3d_query_logits_ce");
   return R3D_OK;
-}
-extern "C" int r3d_query_logits_ce(const float* Z, const int32_t* n_proto_dev, int n_q, int N, int n_classes,
-                                   const int64_t* labels, float* logits, float* loss_out, int32_t* pred_out,
-                                   void* stream) {
-  return r3d_query_logits_ce_batched(1, Z, 0, n_proto_dev, 0, n_q, N, n_classes, labels, logits, loss_out, pred_out, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -34,7 +34,7 @@ enum {
 
 // Batches of episodes (round 3): every kernel below takes the episode from a grid dimension and shifts its per-episode
 // pointers by the strides of HpEp (elements of each array between consecutive episodes; all capacity sized, so episode e
-// of a batch lives at base + e * stride).  One episode = strides unused = the ABI-version-2 entry points.
+// of a batch lives at base + e * stride).  One episode is a batch of one: its strides are never used.
 struct HpEp {
   long sy, keep, feat, qfeat;                   // support_y, shot_keep, support feature ROWS, query feature ROWS
   long nodes, labels, desc, assign, ccount, ws;  // node rows, label rows, descriptor words, assign words, counts, scratch words
@@ -794,7 +794,6 @@ static int check_query_rows(const char* fn, int n_query_pts, int D) {  // (the q
 }
 
 extern "C" int r3d_head_desc_words(void) { return HD_WORDS; }
-extern "C" int r3d_head_max_k(void) { return HP_MAXK; }
 
 // out[n] = the seeds a segment of n points gets at k (n in [0, n_max)): the device's evaluation of hp_fps_count, so that
 // a test can hold it to numpy's float32 arithmetic for EVERY point count (tests/test_gpu_head.py)
@@ -809,7 +808,7 @@ extern "C" int r3d_fps_sample_count_table(int k, int n_max, int32_t* out, void* 
   return R3D_OK;
 }
 
-// Scratch layout (4-byte words) of r3d_head_prototypes.
+// Scratch layout (4-byte words) of r3d_head_prototypes_batched.
 struct HpWs {
   long comp, mind, assign, cand, sel, seeds, part, part_cnt, featC, xch, best, featP, total;
   long pitch;
@@ -875,11 +874,19 @@ static int fps_slots_clamp(int D, int tb_dense, int fps_group) {
   return fps_group < 1 ? 1 : (fit < 1 ? 1 : (fps_group < fit ? fps_group : fit));
 }
 
-static int head_prototypes_impl(int n_ep, const HpEp& ep, int fps_group, const int32_t* support_y, const int32_t* shot_keep,
-                                const float* feat, long ldf, const float* qfeat, long ldq, int n_way, int k_shot, int N, int D,
-                                int n_query_pts, int k, float* nodes, long ldn, float* node_labels, int32_t* desc,
-                                int32_t* assign_out, int32_t* cluster_count, int32_t* ws, long ws_words, int flags,
-                                void* stream) {
+// Per-episode strides: support_y / shot_keep in int32 words, feat / qfeat in ROWS (episode e's support rows start
+// feat_ep_rows rows after episode e - 1's), nodes / node_labels in rows, desc / assign / cluster_count / ws in int32 words
+// (ws stride even and >= r3d_head_proto_ws_words).
+extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_t* support_y, long sy_stride,
+                                           const int32_t* shot_keep, long keep_stride, const float* feat, long ldf,
+                                           long feat_ep_rows, const float* qfeat, long ldq, long qfeat_ep_rows, int n_way,
+                                           int k_shot, int N, int D, int n_query_pts, int k, float* nodes, long ldn,
+                                           long nodes_ep_rows, float* node_labels, int32_t* desc, long desc_stride,
+                                           int32_t* assign_out, long assign_stride, int32_t* cluster_count,
+                                           long ccount_stride, int32_t* ws, long ws_words, long ws_stride, int flags,
+                                           void* stream) {
+  const HpEp ep{sy_stride, keep_stride, feat_ep_rows, qfeat_ep_rows, nodes_ep_rows, nodes_ep_rows, desc_stride, assign_stride,
+                ccount_stride, ws_stride};
   R3D_REQUIRE(support_y && feat && qfeat && nodes && node_labels && desc && ws, "r3d_head_prototypes: null pointer");
   int rc = check_geom("r3d_head_prototypes", n_way, k_shot, N, D);
   if (rc) return rc;
@@ -923,7 +930,7 @@ static int head_prototypes_impl(int n_ep, const HpEp& ep, int fps_group, const i
   hipLaunchKernelGGL(r3d_head_compact_kernel, dim3(g.nseg(), n_ep), dim3(1024), 0, st, support_y, shot_keep, g, comp, desc, e2);
   hipLaunchKernelGGL(r3d_head_gather_kernel, dim3(tb, n_ep), dim3(HP_BLOCK), 0, st, feat, ldf, D, g, comp, desc, featC, pitch,
                      featP, e2);
-  if (flags & 1 /* R3D_HEAD_FPS_ONE_LAUNCH */) {
+  if (flags & R3D_HEAD_FPS_ONE_LAUNCH) {
     const int tb_dense = (int)((g.cap(0) + HP_BLOCK - 1) / HP_BLOCK) + g.nseg();  // the segments' counts add up to cap(0)
     r3d_fill_words_ep(xch, 0u, 2L * kr * tb_dense + 2L * HP_MAXSEG * HP_MAXK, n_ep, e2.ws, st);
     // the launch's workgroups wait for each other: never more of them than the chip holds at once, whatever the caller asks
@@ -972,35 +979,6 @@ static int head_prototypes_impl(int n_ep, const HpEp& ep, int fps_group, const i
   return R3D_OK;
 }
 
-extern "C" int r3d_head_prototypes(const int32_t* support_y, const int32_t* shot_keep, const float* feat,
-                                   long ldf, const float* featT, const float* qfeat, long ldq, int n_way,
-                                   int k_shot, int N, int D, int n_query_pts, int k, float* nodes, long ldn,
-                                   float* node_labels, int32_t* desc, int32_t* assign_out,
-                                   int32_t* cluster_count, int32_t* ws, long ws_words, int flags, void* stream) {
-  (void)featT;  // (ABI version 2 took a channel-major copy; the compacted copy is built here)
-  const HpEp one{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  return head_prototypes_impl(1, one, 1, support_y, shot_keep, feat, ldf, qfeat, ldq, n_way, k_shot, N, D, n_query_pts, k, nodes,
-                              ldn, node_labels, desc, assign_out, cluster_count, ws, ws_words, flags, stream);
-}
-
-// n_ep episodes in one launch sequence.  Per-episode strides: support_y / shot_keep in int32 words, feat / qfeat in ROWS
-// (episode e's support rows start feat_ep_rows rows after episode e - 1's), nodes / node_labels in rows, desc / assign /
-// cluster_count / ws in int32 words (ws stride even and >= r3d_head_proto_ws_words).
-extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_t* support_y, long sy_stride,
-                                           const int32_t* shot_keep, long keep_stride, const float* feat, long ldf,
-                                           long feat_ep_rows, const float* qfeat, long ldq, long qfeat_ep_rows, int n_way,
-                                           int k_shot, int N, int D, int n_query_pts, int k, float* nodes, long ldn,
-                                           long nodes_ep_rows, float* node_labels, int32_t* desc, long desc_stride,
-                                           int32_t* assign_out, long assign_stride, int32_t* cluster_count,
-                                           long ccount_stride, int32_t* ws, long ws_words, long ws_stride, int flags,
-                                           void* stream) {
-  const HpEp ep{sy_stride, keep_stride, feat_ep_rows, qfeat_ep_rows, nodes_ep_rows, nodes_ep_rows, desc_stride, assign_stride,
-                ccount_stride, ws_stride};
-  return head_prototypes_impl(n_ep, ep, fps_group, support_y, shot_keep, feat, ldf, qfeat, ldq, n_way, k_shot, N, D,
-                              n_query_pts, k, nodes, ldn, node_labels, desc, assign_out, cluster_count, ws, ws_words, flags,
-                              stream);
-}
-
 // ---------------------------------------------------------------------------
 // backward of the cluster means (training): every listed support point receives
 // dproto[cluster] / |cluster| ; query rows copy through.  One wave per list position.
@@ -1041,9 +1019,14 @@ __global__ void r3d_query_bwd_kernel(const float* __restrict__ dnodes, long ldd,
 }
 
 // dsfeat (S*N, lds) must be zero-initialised by the caller (points in no list keep a zero gradient)
-static int head_prototypes_bwd_impl(int n_ep, const HpEp& ep, const float* dnodes, long ldd, int n_way, int k_shot, int N, int D,
-                                    int n_query_pts, const int32_t* desc, const int32_t* assign, const int32_t* cluster_count,
-                                    const int32_t* ws, float* dsfeat, long lds_, float* dqfeat, long ldq, void* stream) {
+// strides as r3d_head_prototypes_batched (dsfeat / dqfeat: rows of the gradient buffers between episodes)
+extern "C" int r3d_head_prototypes_bwd_batched(int n_ep, const float* dnodes, long ldd, long nodes_ep_rows, int n_way, int k_shot,
+                                               int N, int D, int n_query_pts, const int32_t* desc, long desc_stride,
+                                               const int32_t* assign, long assign_stride, const int32_t* cluster_count,
+                                               long ccount_stride, const int32_t* ws, long ws_stride, float* dsfeat, long lds_,
+                                               long dsfeat_ep_rows, float* dqfeat, long ldq, long dqfeat_ep_rows, void* stream) {
+  const HpEp ep{0, 0, dsfeat_ep_rows, dqfeat_ep_rows, nodes_ep_rows, nodes_ep_rows, desc_stride, assign_stride, ccount_stride,
+                ws_stride};
   R3D_REQUIRE(dnodes && desc && assign && cluster_count && ws && dsfeat && dqfeat, "r3d_head_prototypes_bwd: null pointer");
   int rc = check_geom("r3d_head_prototypes_bwd", n_way, k_shot, N, D);
   if (rc) return rc;
@@ -1058,24 +1041,6 @@ static int head_prototypes_bwd_impl(int n_ep, const HpEp& ep, const float* dnode
                      n_query_pts, desc, dqfeat, ldq, ep);
   R3D_LAUNCH_CHECK("r3d_head_prototypes_bwd");
   return R3D_OK;
-}
-extern "C" int r3d_head_prototypes_bwd(const float* dnodes, long ldd, int n_way, int k_shot, int N, int D, int n_query_pts,
-                                       const int32_t* desc, const int32_t* assign, const int32_t* cluster_count, const int32_t* ws,
-                                       float* dsfeat, long lds_, float* dqfeat, long ldq, void* stream) {
-  const HpEp one{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  return head_prototypes_bwd_impl(1, one, dnodes, ldd, n_way, k_shot, N, D, n_query_pts, desc, assign, cluster_count, ws, dsfeat,
-                                  lds_, dqfeat, ldq, stream);
-}
-// strides as r3d_head_prototypes_batched (dsfeat / dqfeat: rows of the gradient buffers between episodes)
-extern "C" int r3d_head_prototypes_bwd_batched(int n_ep, const float* dnodes, long ldd, long nodes_ep_rows, int n_way, int k_shot,
-                                               int N, int D, int n_query_pts, const int32_t* desc, long desc_stride,
-                                               const int32_t* assign, long assign_stride, const int32_t* cluster_count,
-                                               long ccount_stride, const int32_t* ws, long ws_stride, float* dsfeat, long lds_,
-                                               long dsfeat_ep_rows, float* dqfeat, long ldq, long dqfeat_ep_rows, void* stream) {
-  const HpEp ep{0, 0, dsfeat_ep_rows, dqfeat_ep_rows, nodes_ep_rows, nodes_ep_rows, desc_stride, assign_stride, ccount_stride,
-                ws_stride};
-  return head_prototypes_bwd_impl(n_ep, ep, dnodes, ldd, n_way, k_shot, N, D, n_query_pts, desc, assign, cluster_count, ws,
-                                  dsfeat, lds_, dqfeat, ldq, stream);
 }
 
 // Word offsets of the scratch sub-arrays inside ws (for tests that inspect the

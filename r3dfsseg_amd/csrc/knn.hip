@@ -1516,7 +1516,7 @@ static size_t knn_lds_bytes(int C) {
                           (size_t)KNN_Q * (KNN_CH + 1) + KNN_Q);
 }
 
-extern "C" int r3d_sqnorm(const float* x, long ldx, long rows, int C, float* out, void* stream) {
+static int knn_sqnorm_launch(const float* x, long ldx, long rows, int C, float* out, void* stream) {
   R3D_REQUIRE(x && out && rows > 0 && C > 0 && ldx >= C, "r3d_sqnorm: bad arguments");
   hipLaunchKernelGGL(r3d_sqnorm_kernel, dim3(r3d_cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      ldx, (int)rows, C, out);
@@ -1524,8 +1524,6 @@ extern "C" int r3d_sqnorm(const float* x, long ldx, long rows, int C, float* out
   return R3D_OK;
 }
 
-// Forward declarations of the layout kernel living in gemm.hip.
-extern "C" int r3d_pm_to_cm_pitched(const float* in, long ld, int B, int C, int N, float* out, long pitch, void* stream);
 // row pitch of the internal channel-major copies: N + 32 floats, so that consecutive channels of
 // one point do not sit a power-of-two stride apart (same L2 channel for every load of a chain)
 extern "C" long r3d_cm_pitch(int N) { return (long)((N + 31) / 32) * 32 + 32; }
@@ -1637,7 +1635,7 @@ static int knn_cm_operand(KnnCall& c, const float* x_cm) {
   if (!x_cm) {
     R3D_REQUIRE(c.cm && c.x, "r3d_knn_topk: need x_cm or (x and cm_ws)");
     c.ldT = r3d_cm_pitch(c.N);
-    int rc = r3d_pm_to_cm_pitched(c.x, c.ldx, c.B, c.C, c.N, c.cm, c.ldT, c.st);
+    int rc = r3d_pm_to_cm_pitched_launch(c.x, c.ldx, c.B, c.C, c.N, c.cm, c.ldT, c.st);
     if (rc) return rc;
     c.xT = c.cm;
   }
@@ -1687,7 +1685,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
     R3D_REQUIRE(c.x, "r3d_knn_topk: the insertion kernel needs the point-major matrix");
     const size_t lds = knn_lds_bytes(c.C);
     R3D_REQUIRE(lds <= 160 * 1024, "r3d_knn_topk: C=%d needs %zu B of LDS (> 160 KiB)", c.C, lds);
-    int rc = r3d_sqnorm(c.x, c.ldx, (long)c.B * c.N, c.C, c.norms, c.st);
+    int rc = knn_sqnorm_launch(c.x, c.ldx, (long)c.B * c.N, c.C, c.norms, c.st);
     if (rc) return rc;
     if (c.k <= 64) knn_insertion_launch<1>(c, lds);
     else if (c.k <= 128) knn_insertion_launch<2>(c, lds);

@@ -6,9 +6,9 @@
 // estimate, momentum 0.1, eps 1e-5 -- followed by LeakyReLU(0.2) / ReLU / nothing.
 //
 // A conv+BN+act layer in training is:  z = X W^T (r3d_pointwise_conv, no affine) ->
-// r3d_colstats(z) -> r3d_bn_fold (batch mean / invstd -> scale, shift; running stats update) ->
-// r3d_affine_act (y = act(scale z + shift)).  Backward:  r3d_bn_bwd_stats (sum du, sum du zhat) ->
-// r3d_bn_bwd_apply (dz) -> r3d_pointwise_conv(dz, W^T) for dX and r3d_gemm_tn(dz, X) for dW.
+// r3d_colstats_seg(z) -> r3d_bn_fold_seg (batch mean / invstd -> scale, shift; running stats update) ->
+// r3d_affine_act_seg (y = act(scale z + shift)).  Backward:  r3d_colstats_seg mode 1 (sum du, sum du zhat) ->
+// r3d_bn_bwd_apply_seg (dz) -> r3d_pointwise_conv(dz, W^T) for dX and r3d_gemm_tn(dz, X) for dW.
 // All reductions run in a fixed order (partials per row chunk, chunks added ascending, in fp64).
 //
 // SEGMENTS.  A batch of E training episodes goes through ONE launch sequence, but BatchNorm keeps the statistics of
@@ -17,7 +17,7 @@
 // numbers (common.h: r3d_segmap): rows_a = S N, rows_b = Q N; segment 2 e + p is call p of episode e -- the order in
 // which the reference updates the running statistics.  Every reduction below is per segment with a partition that
 // depends on the segment's size alone, so a segment's statistics are bit for bit the same whether its episode runs
-// alone or inside a batch.  The single-segment entry points of ABI version 2 are the case rows_b = 0, rows_a = M.
+// alone or inside a batch.  One segment is the case rows_b = 0, rows_a = M.
 #include "common.h"
 
 #define TS_ROWS 512      // rows per partial
@@ -620,7 +620,6 @@ extern "C" long r3d_colstats_seg_ws_words(long M, int C, long rows_a, long rows_
   const int ca = ts_chunks(rows_a, C), cb = ts_chunks(rows_b, C);
   return (long)sm.n_seg(M) * (ca > cb ? ca : cb) * 2L * C + 16;
 }
-extern "C" long r3d_colstats_ws_words(long M, int C) { return r3d_colstats_seg_ws_words(M, C, M, 0); }
 
 // sums_out [seg][2][C]: mode 0 (sum x, sum x^2); mode 1 (sum du, sum du*zhat) -- see kernel comment.  The BatchNorm
 // vectors of segment s are read at scale + s * bn_stride, ...
@@ -649,24 +648,16 @@ extern "C" int r3d_colstats_seg(const float* X, long ldx, const float* DY, long 
   R3D_LAUNCH_CHECK("r3d_colstats");
   return R3D_OK;
 }
-extern "C" int r3d_colstats(const float* X, long ldx, const float* DY, long lddy, long M, int C, int mode,
-                            const float* scale, const float* shift, const float* mean, const float* invstd, int act,
-                            float* sums_out, float* ws, void* stream) {
-  return r3d_colstats_seg(X, ldx, DY, lddy, M, C, M, 0, mode, scale, shift, mean, invstd, 0, act, sums_out, ws, stream);
-}
 
 // [chunks][2][C] partial column sums -> sums_out [seg][2][C] (shared with the GEMM-epilogue statistics of gemm.hip): the
 // chunks of the segments follow each other, count_a / count_b of them alternating (count_b == 0: count_a each)
-extern "C" int r3d_colreduce_seg(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out, void* stream) {
+int r3d_colreduce_launch(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out, void* stream) {
   R3D_REQUIRE(part && sums_out && count_a > 0 && count_b >= 0 && n_seg > 0 && n_seg <= 65535 && C > 0,
               "r3d_colreduce: bad arguments");
   hipLaunchKernelGGL(r3d_colreduce_kernel, dim3(r3d_cdiv(C, 64), n_seg), dim3(256), 0, (hipStream_t)stream, part, count_a, count_b,
                      0, C, sums_out);
   R3D_LAUNCH_CHECK("r3d_colreduce");
   return R3D_OK;
-}
-extern "C" int r3d_colreduce(const float* part, int chunks, int C, float* sums_out, void* stream) {
-  return r3d_colreduce_seg(part, chunks, 0, 1, C, sums_out, stream);
 }
 
 // sums [seg][2][C] -> mean / invstd / scale / shift of segment s at (pointer + s * bn_stride).  Running statistics (or
@@ -684,13 +675,6 @@ extern "C" int r3d_bn_fold_seg(const float* sums, int n_seg, double count_a, dou
                      rec_index_dev, rec_stride);
   R3D_LAUNCH_CHECK("r3d_bn_fold");
   return R3D_OK;
-}
-extern "C" int r3d_bn_fold(const float* sums, double count, int C, const float* gamma, const float* beta, float eps,
-                           float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
-                           float* scale, float* shift, float* rec, const int32_t* rec_index_dev, long rec_stride,
-                           void* stream) {
-  return r3d_bn_fold_seg(sums, 1, count, 0.0, C, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale,
-                         shift, 0, rec, rec_index_dev, rec_stride, stream);
 }
 
 extern "C" int r3d_bn_running_update(const float* rec, int n_records, long rec_stride, int C, float momentum, const float* bias,
@@ -712,10 +696,6 @@ extern "C" int r3d_affine_act_seg(const float* Z, long ldz, long M, int C, long 
                      scale, shift, bn_stride, act, Y, ldy);
   R3D_LAUNCH_CHECK("r3d_affine_act");
   return R3D_OK;
-}
-extern "C" int r3d_affine_act(const float* Z, long ldz, long M, int C, const float* scale, const float* shift, int act,
-                              float* Y, long ldy, void* stream) {
-  return r3d_affine_act_seg(Z, ldz, M, C, M, 0, scale, shift, 0, act, Y, ldy, stream);
 }
 
 extern "C" int r3d_bn_bwd_apply_seg(const float* Z, long ldz, const float* DY, long lddy, long M, int C, long rows_a,
@@ -743,12 +723,6 @@ extern "C" int r3d_bn_bwd_apply_seg(const float* Z, long ldz, const float* DY, l
                      lddy, (int)M, C, sm, scale, shift, mean, invstd, bn_stride, act, sums, count_a, count_b, DZ, lddz);
   R3D_LAUNCH_CHECK("r3d_bn_bwd_apply");
   return R3D_OK;
-}
-extern "C" int r3d_bn_bwd_apply(const float* Z, long ldz, const float* DY, long lddy, long M, int C, const float* scale,
-                                const float* shift, const float* mean, const float* invstd, int act, const float* sums,
-                                double count, float* DZ, long lddz, void* stream) {
-  return r3d_bn_bwd_apply_seg(Z, ldz, DY, lddy, M, C, M, 0, scale, shift, mean, invstd, 0, act, sums, count, 0.0, DZ, lddz,
-                              stream);
 }
 
 extern "C" long r3d_gemm_tn_ws_words(long M, int Ca, int Cb) {

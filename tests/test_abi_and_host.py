@@ -79,6 +79,105 @@ def test_binding_signatures_match_the_header():
     assert seen == set(_lib._SIGS), seen ^ set(_lib._SIGS)
 
 
+def test_header_parser_on_small_prototypes():
+    """The parser the binding is derived with (_lib.parse_header), on prototypes written here: what include/r3d.h uses today
+    and what must be refused rather than guessed."""
+    names, sigs = _lib.parse_header("""
+        /* a comment naming r3d_not_a_function( and holding a ; */
+        const char* r3d_text(void);
+        int r3d_none();   // r3d_neither(
+        int r3d_many(const float* in /* (B,C,N), channel-major */, long ld,
+                     int B, float* out /*(B*N,ld)*/,
+                     double count, float eps,
+                     unsigned seed, const unsigned* seed_dev,
+                     const int64_t* labels, uint64_t* hist, void* stream);
+        long r3d_offsets(int n_cap, int kp1, long* out6 /* comp,mind,assign */);
+        int r3d_budget(void* graph, int32_t budget, int* n_cg);
+    """)
+    assert names == ["r3d_budget", "r3d_many", "r3d_none", "r3d_offsets", "r3d_text"]
+    c_f, c_i, c_l, c_fl, c_d, c_u = _lib.c_f, _lib.c_i, _lib.c_l, _lib.c_fl, _lib.c_d, _lib.c_u
+    assert sigs == {
+        "r3d_text": (ctypes.c_char_p, []),
+        "r3d_none": (c_i, []),
+        "r3d_many": (c_i, [c_f, c_l, c_i, c_f, c_d, c_fl, c_u, c_f, c_f, c_f, c_f]),
+        "r3d_offsets": (c_l, [c_i, c_i, c_f]),
+        "r3d_budget": (c_i, [c_f, c_i, c_f]),
+    }
+    for bad, named in (("int r3d_a(size_t n);", "r3d_a"),                  # an unknown type
+                       ("int r3d_a(int n, struct cfg c);", "parameter 1 of r3d_a"),
+                       ("int r3d_a(unsigned long n);", "r3d_a"),           # two type words: not guessed
+                       ("int r3d_a(int64_t n);", "r3d_a"),                 # by value it would be cut to 32 bits
+                       ("int r3d_a(int);", "r3d_a"),                       # no parameter name
+                       ("float* r3d_a(void);", "r3d_a"),                   # a pointer return other than const char*
+                       ("int r3d_ok(void);\nint r3d_cb(void (*fn)(int), int n);", "r3d_cb"),  # seen, but not consumed
+                       ("int r3d_ok(void);\nint r3d_open(int n)\n", "r3d_open"),              # no terminating ;
+                       ("int r3d_a(void);\nlong r3d_a(int n);", "r3d_a")):                     # declared twice
+        with pytest.raises(RuntimeError, match=named):
+            _lib.parse_header(bad)
+
+
+def test_binding_spot_pins_on_the_real_header():
+    """A handful of signatures as the binding derives them from include/r3d.h (not a second table)."""
+    sigs = _lib._SIGS
+    res, args = sigs["r3d_bn_fold_seg"]
+    assert res is _lib.c_i and args.count(_lib.c_d) == 2 and args[2] is _lib.c_d and args[3] is _lib.c_d
+    res, args = sigs["r3d_augment_clouds"]
+    assert len(args) == 24 and args[17] is _lib.c_u and args[19] is _lib.c_u and args[18] is _lib.c_f
+    assert args.count(_lib.c_u) == 2
+    assert sigs["r3d_last_error_string"] == (ctypes.c_char_p, [])
+    assert sigs["r3d_lp_ws_offsets"] == (_lib.c_i, [_lib.c_i, _lib.c_i, _lib.c_f])
+    assert sigs["r3d_graph_set_lp_budget"][1][-1] is _lib.c_f  # (host out-pointers travel as void* too)
+    assert sigs["r3d_cm_pitch"] == (_lib.c_l, [_lib.c_i])
+    # as void* the host out-pointers still take what callers pass: ctypes arrays and byref objects
+    fn = ctypes.CFUNCTYPE(*([sigs["r3d_lp_ws_offsets"][0]] + sigs["r3d_lp_ws_offsets"][1]))(lambda a, b, p: 0)
+    assert fn(1, 2, (ctypes.c_long * 6)()) == 0 and fn(1, 2, ctypes.byref(ctypes.c_int(0))) == 0
+
+
+REMOVED_WITHIN_ABI_5 = (
+    "r3d_sqnorm", "r3d_pm_to_cm_pitched", "r3d_attention_fwd", "r3d_head_max_k", "r3d_head_prototypes",
+    "r3d_head_prototypes_bwd", "r3d_pointwise_conv_stats2", "r3d_colreduce", "r3d_colreduce_seg", "r3d_colstats",
+    "r3d_colstats_ws_words", "r3d_bn_fold", "r3d_affine_act", "r3d_bn_bwd_apply", "r3d_ce_grad", "r3d_label_propagate_bwd",
+    "r3d_train_metrics", "r3d_clean_shot_detect", "r3d_query_logits_ce", "r3d_attention_ws_words_ep",
+    "r3d_attention_fwd_train_ep", "r3d_attention_bwd_ep")
+
+
+def _exported_r3d_symbols():
+    """Unmangled r3d_* names in the dynamic symbol table of the built library (None: no tool to read it with)."""
+    import subprocess
+    from r3dfsseg_amd import build
+    path = build.build()
+    llvm = "/opt/rocm/lib/llvm/bin/"
+    if os.path.exists(llvm + "llvm-nm"):
+        out = subprocess.run([llvm + "llvm-nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    elif os.path.exists(llvm + "llvm-objdump"):  # the same table: defined entries are the ones with a section
+        out = subprocess.run([llvm + "llvm-objdump", "-T", path], check=True, capture_output=True, text=True).stdout
+        out = "\n".join(l for l in out.splitlines() if "*UND*" not in l)
+    else:
+        return None
+    return sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("r3d_")})
+
+
+def test_exported_symbols_are_exactly_the_declared_ones():
+    """No wrapper lingers in the library that include/r3d.h does not declare, and none it declares is missing."""
+    exported = _exported_r3d_symbols()
+    if exported is None:
+        pytest.skip("neither llvm-nm nor llvm-objdump is here")
+    assert len(exported) >= 80
+    assert exported == _lib.header_symbols(), set(exported) ^ set(_lib.header_symbols())
+
+
+def test_entry_points_removed_within_abi_5_are_gone():
+    """The wrappers without callers: not declared, not bound, not exported."""
+    import re
+    assert len(set(REMOVED_WITHIN_ABI_5)) == 22
+    words = set(re.findall(r"[A-Za-z0-9_]+", open(_lib.HEADER_PATH).read()))  # comments included
+    exported = _exported_r3d_symbols()
+    for name in REMOVED_WITHIN_ABI_5:
+        assert name not in words, name
+        assert name not in _lib._SIGS and name not in _lib.header_symbols(), name
+        assert exported is None or name not in exported, name
+
+
 def test_abi_argument_validation_without_gpu():
     """Bad arguments are rejected on the host before any launch (error convention of include/r3d.h)."""
     lib = _lib.load()

@@ -8,7 +8,7 @@ objs = []
 for f in ("error", "knn", "gemm", "train_ops", "head_graph"):
     o = "/tmp/st_%s.o" % f
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
-                           "-DCG_STAMPS", "-c", os.path.join(src, f + ".hip"), "-o", o])
+                           "-DCG_STAMPS", "-I", os.path.join(ROOT, "include"), "-c", os.path.join(src, f + ".hip"), "-o", o])
     objs.append(o)
 import torch
 lib = ctypes.CDLL("/dev/null") if False else None

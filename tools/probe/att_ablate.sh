@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 MASKS=${MASKS:-"0 1 2 4"}
 if [ "$1" = "build" ]; then
   for m in $MASKS; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -DATT_ABL=$m -c r3dfsseg_amd/csrc/attention.hip -o /tmp/att_abl_$m.o &
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -DATT_ABL=$m -I include -c r3dfsseg_amd/csrc/attention.hip -o /tmp/att_abl_$m.o &
   done
   wait
   for m in $MASKS; do

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 src = os.path.join(ROOT, "r3dfsseg_amd", "csrc")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
-                       "-DATT_STAMPS", "-c", os.path.join(src, "attention.hip"), "-o", "/tmp/att_st.o"])
+                       "-DATT_STAMPS", "-I", os.path.join(ROOT, "include"), "-c", os.path.join(src, "attention.hip"), "-o", "/tmp/att_st.o"])
 objs = [os.path.join(src, f) for f in os.listdir(src) if f.endswith(".o") and f != "attention.o"]
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", "/tmp/libatt_st.so",
                        "/tmp/att_st.o"] + objs)
