@@ -388,6 +388,20 @@ long r3d_protonet_head_ws_words(int n_ep, int n_way, int k_shot);
 int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows, int D,
                               const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts, int method,
                               float scaler, float* Z, float* ws, long ws_words, void* stream);
+/* The batched head with clean-shot flags (reference ProtoNet_Contrast: getPrototype(clean_flag=...), protonet.py:892-915).
+ * shot_keep (n_ep, n_way*k_shot) int32 in device memory, as r3d_clean_shot_detect_batched writes it: the foreground
+ * prototype of a way is the sum of its KEPT shots' pooled means over the NUMBER kept; the background prototype is still the
+ * sum over all n_way*k_shot shots over n_way*k_shot -- a dropped shot keeps contributing background.  The shots are walked in
+ * the order of r3d_protonet_head_batched, which is this call with shot_keep = NULL: NULL or all ones give its result bit for
+ * bit.  Same launches, same scratch (r3d_protonet_head_ws_words), same limits.  A way with no kept shot is the caller's
+ * error (the detection resets such a way to all kept, protonet.py:529-532).  shot_keep lives on the device and is read
+ * only there, by the workgroups that form the prototypes: the DEVICE DOES NOT CHECK IT and the call returns 0; that way's
+ * prototype is 0 / 0 and its similarity column NaN.  A caller that holds the flags on the host checks them there
+ * (ops.protonet_head_batched does, for a host tensor). */
+int r3d_protonet_head_keep_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows,
+                                   int D, const int32_t* support_y, const int32_t* shot_keep, int n_way, int k_shot, int N,
+                                   int n_query_pts, int method, float scaler, float* Z, float* ws, long ws_words,
+                                   void* stream);
 /* correct (n_ep) int32 = per episode #{pred == label}: pred (n_ep, n_pts) int32 as r3d_query_logits_ce_batched writes it,
  * labels (n_ep, n_pts) int64.  One host read then serves the accuracy of a whole batch. */
 int r3d_count_correct_batched(int n_ep, const int32_t* pred, const int64_t* labels, long n_pts, int32_t* correct,

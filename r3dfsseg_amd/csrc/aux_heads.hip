@@ -218,10 +218,13 @@ __global__ __launch_bounds__(256) void r3d_proto_pool_kernel(const float* __rest
 
 // prototypes (getPrototype) + per-point similarity (calculateSimilarity) -> Z rows (n_q*N, 4).  Workgroup `blk` of `nblk`
 // takes every nblk-th group of 4 query points, one wave per point: a point's arithmetic does not depend on the grid.
-static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ pooled, int n_way, int k_shot,
-                                                    const float* __restrict__ qfeat, long ldq, int D, int n_pts, int method,
-                                                    float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2, int blk,
-                                                    int nblk) {
+// keep (n_way*k_shot) or null: a way's foreground prototype is the mean of its kept shots (getPrototype(clean_flag=...),
+// protonet.py:904-911), walked in shot order as without it -- all kept: the same additions, the same divisor --; the
+// background prototype takes every shot either way.  keep[...] is the same word for every lane: the branch is wave-uniform.
+static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ pooled, const int* __restrict__ keep, int n_way,
+                                                    int k_shot, const float* __restrict__ qfeat, long ldq, int D, int n_pts,
+                                                    int method, float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2,
+                                                    int blk, int nblk) {
   __shared__ float proto[8][AH_DMAX];
   __shared__ float pnorm[8];
   const int tid = threadIdx.x;
@@ -232,8 +235,13 @@ static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ po
     proto[0][tid] = bgp / (float)(n_way * k_shot);
     for (int wy = 0; wy < n_way; ++wy) {
       float f = 0.f;
-      for (int k = 0; k < k_shot; ++k) f += pooled[((long)(wy * k_shot + k) * 2 + 0) * AH_DMAX + tid];
-      proto[wy + 1][tid] = f / (float)k_shot;
+      int n_kept = 0;
+      for (int k = 0; k < k_shot; ++k) {
+        if (keep && keep[wy * k_shot + k] == 0) continue;
+        f += pooled[((long)(wy * k_shot + k) * 2 + 0) * AH_DMAX + tid];
+        ++n_kept;
+      }
+      proto[wy + 1][tid] = f / (float)n_kept;  // (no kept shot: 0 / 0, the caller's error -- r3d.h)
     }
   }
   __syncthreads();
@@ -278,7 +286,7 @@ __global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restr
                                                             const float* __restrict__ qfeat, long ldq, int D, int n_pts,
                                                             int method /*0 cosine, 1 euclidean*/, float scaler,
                                                             float4* __restrict__ Zq, float4* __restrict__ Zq2 /* classes 4..7 */) {
-  ah_proto_sim(pooled, n_way, k_shot, qfeat, ldq, D, n_pts, method, scaler, Zq, Zq2, blockIdx.x, gridDim.x);
+  ah_proto_sim(pooled, nullptr, n_way, k_shot, qfeat, ldq, D, n_pts, method, scaler, Zq, Zq2, blockIdx.x, gridDim.x);
 }
 
 // ---- the same head for a batch of episodes: grid axis y is the episode in both kernels ------------------------------------
@@ -323,14 +331,16 @@ __global__ __launch_bounds__(256) void r3d_proto_pool_ep_kernel(const float* __r
   out[AH_DMAX + tid] = bg / ((float)(N - nfg) + 1e-5f);
 }
 
-// grid (query tiles, n_ep)
-__global__ __launch_bounds__(256) void r3d_proto_sim_ep_kernel(const float* __restrict__ pooled, int n_way, int k_shot,
+// grid (query tiles, n_ep); shot_keep (n_ep, n_way*k_shot) or null
+__global__ __launch_bounds__(256) void r3d_proto_sim_ep_kernel(const float* __restrict__ pooled,
+                                                               const int* __restrict__ shot_keep, int n_way, int k_shot,
                                                                const float* __restrict__ qfeat, long ldq, long feat_ep_rows,
                                                                int D, int n_pts, int method, float scaler,
                                                                float4* __restrict__ Zq, float4* __restrict__ Zq2) {
   const long ep = blockIdx.y;
-  ah_proto_sim(pooled + ep * n_way * k_shot * 2 * AH_DMAX, n_way, k_shot, qfeat + ep * feat_ep_rows * ldq, ldq, D, n_pts, method,
-               scaler, Zq + ep * n_pts, Zq2 ? Zq2 + ep * n_pts : nullptr, blockIdx.x, gridDim.x);
+  ah_proto_sim(pooled + ep * n_way * k_shot * 2 * AH_DMAX, shot_keep ? shot_keep + ep * n_way * k_shot : nullptr, n_way, k_shot,
+               qfeat + ep * feat_ep_rows * ldq, ldq, D, n_pts, method, scaler, Zq + ep * n_pts,
+               Zq2 ? Zq2 + ep * n_pts : nullptr, blockIdx.x, gridDim.x);
 }
 
 // correct[e] = #{pred == label} over the n_pts query points of episode e (integers: any order gives the same count).  grid (n_ep)
@@ -422,13 +432,18 @@ extern "C" long r3d_protonet_head_ws_words(int n_ep, int n_way, int k_shot) {
   if (n_ep < 1 || n_ep > 65535 || n_way < 1 || n_way > 7 || k_shot < 1 || (long)n_way * k_shot > 65535) return -1;
   return (long)n_ep * n_way * k_shot * 2 * AH_DMAX;
 }
-extern "C" int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows,
-                                         int D, const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts,
-                                         int method, float scaler, float* Z, float* ws, long ws_words, void* stream) {
-  R3D_REQUIRE(sfeat && qfeat && support_y && Z && ws, "r3d_protonet_head_batched: null pointer");
+// shot_keep (n_ep, n_way*k_shot) int32 on the device, 0 = the shot's foreground is left out of its way's prototype
+// (r3d_clean_shot_detect_batched writes it); null: every shot is kept, which is r3d_protonet_head_batched bit for bit, as is
+// a vector of ones.  The workgroups that form the prototypes read it: no launch is added and the host never reads it, so a
+// way without a kept shot (which the detection never leaves) is not reported -- its prototype and similarities are NaN.
+static int ah_protonet_head_ep(const char* who, int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq,
+                               long feat_ep_rows, int D, const int32_t* support_y, const int32_t* shot_keep, int n_way,
+                               int k_shot, int N, int n_query_pts, int method, float scaler, float* Z, float* ws,
+                               long ws_words, void* stream) {
+  R3D_REQUIRE(sfeat && qfeat && support_y && Z && ws, "%s: null pointer", who);
   R3D_REQUIRE(n_way >= 1 && n_way <= 7 && D >= 1 && D <= AH_DMAX && k_shot >= 1 && (long)n_way * k_shot <= 65535 && N >= 1 &&
                   n_query_pts >= 1 && ldf >= D && ldq >= D,
-              "r3d_protonet_head_batched: unsupported shape n_way=%d k_shot=%d N=%d D=%d", n_way, k_shot, N, D);
+              "%s: unsupported shape n_way=%d k_shot=%d N=%d D=%d", who, n_way, k_shot, N, D);
   if (method != 0 && method != 1) {
     // the reference raises NotImplementedError for anything but cosine / euclidean (protonet.py:347)
     r3d_set_error("Error! Distance computation method (%d) is unknown!", method);
@@ -436,20 +451,35 @@ extern "C" int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf,
   }
   const int S = n_way * k_shot;
   R3D_REQUIRE(n_ep >= 1 && n_ep <= 65535 && (n_ep == 1 || feat_ep_rows >= (long)S * N),
-              "r3d_protonet_head_batched: %d episodes, %ld rows between them", n_ep, feat_ep_rows);
+              "%s: %d episodes, %ld rows between them", who, n_ep, feat_ep_rows);
   const long need = r3d_protonet_head_ws_words(n_ep, n_way, k_shot);
-  R3D_REQUIRE(ws_words >= need, "r3d_protonet_head_batched: workspace of %ld words is shorter than r3d_protonet_head_ws_words = %ld",
-              ws_words, need);
-  R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)Z & 15) == 0, "r3d_protonet_head_batched: ws and Z must be 16-byte aligned");
+  R3D_REQUIRE(ws_words >= need, "%s: workspace of %ld words is shorter than r3d_protonet_head_ws_words = %ld",
+              who, ws_words, need);
+  R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)Z & 15) == 0, "%s: ws and Z must be 16-byte aligned", who);
+  R3D_REQUIRE(((uintptr_t)shot_keep & 3) == 0, "%s: shot_keep must be 4-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(r3d_proto_pool_ep_kernel, dim3(S, n_ep), dim3(256), 0, st, sfeat, ldf, feat_ep_rows, D, support_y, N, ws);
   // ~2048 workgroups over the batch (8 per CU), 256 for one episode as r3d_protonet_head: every workgroup builds the
   // prototypes of its episode again, so few episodes get many tiles and many episodes few
   const int gx = min(r3d_cdiv(n_query_pts, 4), max(32, min(256, 2048 / n_ep)));
-  hipLaunchKernelGGL(r3d_proto_sim_ep_kernel, dim3(gx, n_ep), dim3(256), 0, st, ws, n_way, k_shot, qfeat, ldq, feat_ep_rows, D,
-                     n_query_pts, method, scaler, (float4*)Z, n_way > 3 ? (float4*)Z + (long)n_ep * n_query_pts : nullptr);
-  R3D_LAUNCH_CHECK("r3d_protonet_head_batched");
+  hipLaunchKernelGGL(r3d_proto_sim_ep_kernel, dim3(gx, n_ep), dim3(256), 0, st, ws, shot_keep, n_way, k_shot, qfeat, ldq,
+                     feat_ep_rows, D, n_query_pts, method, scaler, (float4*)Z,
+                     n_way > 3 ? (float4*)Z + (long)n_ep * n_query_pts : nullptr);
+  R3D_LAUNCH_CHECK(who);
   return R3D_OK;
+}
+extern "C" int r3d_protonet_head_keep_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq,
+                                              long feat_ep_rows, int D, const int32_t* support_y, const int32_t* shot_keep,
+                                              int n_way, int k_shot, int N, int n_query_pts, int method, float scaler, float* Z,
+                                              float* ws, long ws_words, void* stream) {
+  return ah_protonet_head_ep("r3d_protonet_head_keep_batched", n_ep, sfeat, ldf, qfeat, ldq, feat_ep_rows, D, support_y,
+                             shot_keep, n_way, k_shot, N, n_query_pts, method, scaler, Z, ws, ws_words, stream);
+}
+extern "C" int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf, const float* qfeat, long ldq, long feat_ep_rows,
+                                         int D, const int32_t* support_y, int n_way, int k_shot, int N, int n_query_pts,
+                                         int method, float scaler, float* Z, float* ws, long ws_words, void* stream) {
+  return ah_protonet_head_ep("r3d_protonet_head_batched", n_ep, sfeat, ldf, qfeat, ldq, feat_ep_rows, D, support_y, nullptr,
+                             n_way, k_shot, N, n_query_pts, method, scaler, Z, ws, ws_words, stream);
 }
 
 // correct (n_ep) int32: per episode the number of query points whose arg-max (pred (n_ep, n_pts) int32, as

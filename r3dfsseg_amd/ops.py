@@ -470,10 +470,14 @@ def protonet_head(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scale
     return Z
 
 
-def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, n_ep, feat_ep_rows, n_query_pts, scaler=10.0):
+def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, n_ep, feat_ep_rows, n_query_pts, scaler=10.0,
+                          shot_keep=None):
     """protonet_head for n_ep episodes in one launch pair: Z (n_ep * n_query_pts, 4) per plane, episode after episode, per
     episode bit for bit protonet_head's rows.  sfeat_pm / qfeat_pm: the support / query rows of episode 0 (views into ONE
-    feature matrix in which episode e's rows start feat_ep_rows rows further on)."""
+    feature matrix in which episode e's rows start feat_ep_rows rows further on).  shot_keep (n_ep, n_way*k_shot), 0 = the
+    shot's foreground stays out of its way's prototype (clean_shot_detect's result; ProtoNet_Contrast): None or all ones is
+    the plain head bit for bit.  A device tensor is read on the device only; a host tensor is checked here for a way without
+    a kept shot."""
     _, ldf = _rows(sfeat_pm)
     _, ldq = _rows(qfeat_pm)
     code = _proto_method(method)
@@ -483,10 +487,20 @@ def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, metho
     words = lib.r3d_protonet_head_ws_words(n_ep, n_way, k_shot)
     if words < 0:
         raise NotImplementedError("ProtoNet head: 1 <= n_way <= 7, 1 <= episodes <= 65535 (n_way=%d, episodes=%d)" % (n_way, n_ep))
+    keep = None
+    if shot_keep is not None:
+        keep = torch.as_tensor(shot_keep)
+        if keep.numel() != n_ep * n_way * k_shot:
+            raise ValueError("shot_keep has %d entries for %d episodes of %d-way %d-shot" % (keep.numel(), n_ep, n_way, k_shot))
+        if not keep.is_cuda and not bool((keep.reshape(n_ep, n_way, k_shot) != 0).any(-1).all()):
+            raise ValueError("shot_keep drops every shot of a way: its prototype would be 0 / 0 (the detection resets such a "
+                             "way to all kept, models/protonet.py:529-532)")
+        keep = keep.to(device=dev, dtype=torch.int32).reshape(n_ep, n_way * k_shot).contiguous()
     ws = torch.empty(words, device=dev, dtype=torch.float32)
     Z = torch.empty((1 if n_way <= 3 else 2) * n_ep * n_query_pts, 4, device=dev, dtype=torch.float32)  # (planes of 4 classes)
-    _lib.check(lib.r3d_protonet_head_batched(n_ep, _p(sfeat_pm), ldf, _p(qfeat_pm), ldq, feat_ep_rows, sfeat_pm.shape[1], _p(sy),
-                                             n_way, k_shot, N, n_query_pts, code, float(scaler), _p(Z), _p(ws), words, _st()))
+    _lib.check(lib.r3d_protonet_head_keep_batched(n_ep, _p(sfeat_pm), ldf, _p(qfeat_pm), ldq, feat_ep_rows, sfeat_pm.shape[1],
+                                                  _p(sy), _p(keep), n_way, k_shot, N, n_query_pts, code, float(scaler), _p(Z),
+                                                  _p(ws), words, _st()))
     return Z
 
 

@@ -10,7 +10,41 @@ from .metrics import point_accuracy
 from .protonet import ProtoNet
 
 
-class ProtoLearner(object):
+class ProtoEvalBatch(object):
+    """The evaluation half ProtoLearner and ProtoContrastLearner share: E episodes of one shape through
+    self.model.forward_episodes.  Needs self.model only."""
+
+    @staticmethod
+    def _batch(datas):
+        """A list of episodes (the first four tensors of each are used) -> batch.EpisodeBatch on the device."""
+        from .batch import EpisodeBatch
+        if isinstance(datas, EpisodeBatch):
+            return datas
+        if len(datas) == 0:
+            raise ValueError("an empty list of episodes: a batch is at least one episode")
+        eps = [[t.cuda() for t in d[:4]] for d in datas]
+        for e, ep in enumerate(eps[1:], 1):
+            for i, (a, b) in enumerate(zip(eps[0], ep)):
+                if a.shape != b.shape:
+                    raise ValueError("a batch is E episodes of ONE shape: tensor %d of episode %d is %s, of episode 0 %s"
+                                     % (i, e, tuple(b.shape), tuple(a.shape)))
+        return EpisodeBatch.from_episodes(eps)
+
+    def test_batch(self, datas, sampled_classes=None):
+        """test() for E episodes of one shape in ONE launch sequence (ProtoNet.forward_episodes): a list of
+        (pred (n_q, N), loss, accuracy), per episode what test() returns for it."""
+        from . import dist as D
+        b = self._batch(datas)
+        self.model.eval()
+        D.warn_rank_local_stats(self.model, 'evaluation')
+        with torch.no_grad():
+            _, loss, pred, correct = self.model.forward_episodes(b)
+            pred = pred.to(torch.int64)
+        n = b.query_y.shape[1] * b.query_y.shape[2]
+        return [(pred[e], loss[e], c / n) for e, c in enumerate(correct.tolist())]  # (the batch's one host read)
+
+
+class ProtoLearner(ProtoEvalBatch):
     def __init__(self, args, mode='train'):
         self.model = ProtoNet(args)
         self._batch_trainer = None  # protonet_train.ProtoBatchTrainer behind train_batch
@@ -59,22 +93,6 @@ class ProtoLearner(object):
         self.lr_scheduler.step()
         return loss, point_accuracy(query_logits.argmax(dim=1), query_y)
 
-    @staticmethod
-    def _batch(datas):
-        """A list of episodes (the first four tensors of each are used) -> batch.EpisodeBatch on the device."""
-        from .batch import EpisodeBatch
-        if isinstance(datas, EpisodeBatch):
-            return datas
-        if len(datas) == 0:
-            raise ValueError("an empty list of episodes: a batch is at least one episode")
-        eps = [[t.cuda() for t in d[:4]] for d in datas]
-        for e, ep in enumerate(eps[1:], 1):
-            for i, (a, b) in enumerate(zip(eps[0], ep)):
-                if a.shape != b.shape:
-                    raise ValueError("a batch is E episodes of ONE shape: tensor %d of episode %d is %s, of episode 0 %s"
-                                     % (i, e, tuple(b.shape), tuple(a.shape)))
-        return EpisodeBatch.from_episodes(eps)
-
     def train_batch(self, datas, logger):
         """E episodes per optimiser step: ``datas`` is a list of what train() takes, all of one shape.  The E episodes go
         through ONE launch sequence (protonet_train.explicit_train_batch), their gradients are averaged -- over all ranks'
@@ -92,19 +110,6 @@ class ProtoLearner(object):
         loss, _, _, correct = self._batch_trainer.step(b)
         n = b.query_y.shape[1] * b.query_y.shape[2]
         return [(loss[e], c / n) for e, c in enumerate(correct.tolist())]  # (the step's one host read)
-
-    def test_batch(self, datas, sampled_classes=None):
-        """test() for E episodes of one shape in ONE launch sequence (ProtoNet.forward_episodes): a list of
-        (pred (n_q, N), loss, accuracy), per episode what test() returns for it."""
-        from . import dist as D
-        b = self._batch(datas)
-        self.model.eval()
-        D.warn_rank_local_stats(self.model, 'evaluation')
-        with torch.no_grad():
-            _, loss, pred, correct = self.model.forward_episodes(b)
-            pred = pred.to(torch.int64)
-        n = b.query_y.shape[1] * b.query_y.shape[2]
-        return [(pred[e], loss[e], c / n) for e, c in enumerate(correct.tolist())]  # (the batch's one host read)
 
     def test(self, data, sampled_classes, step=None, path=None):
         [support_x, support_y, query_x, query_y, _, _, gt_support_y] = data

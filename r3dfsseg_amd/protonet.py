@@ -1,14 +1,20 @@
 """Host-side mirror of the reference's models/protonet.py::ProtoNet (lines 39-58, 245-354):
 same constructor and forward() signature; encoder / attention / base learner run on the HIP
 kernels (dgcnn.FewShotFeatures), the head is r3d_protonet_head_batched (evaluation: _forward_eval, a single episode is a
-batch of one) or r3d_protonet_head_train_fwd / r3d_protonet_head_bwd (a module in .train() mode: protonet_train.py)."""
+batch of one) or r3d_protonet_head_train_fwd / r3d_protonet_head_bwd (a module in .train() mode: protonet_train.py).
+
+ProtoNet_Contrast (models/protonet.py:357-946, "protonet+CCNS+MDNS") is the same evaluation with the clean-shot detection
+in front of the head: r3d_clean_shot_detect_batched, then r3d_protonet_head_keep_batched.  Evaluation only."""
 import torch
+from torch import nn
 
 from . import ops
 from .dgcnn import FewShotFeatures
 
 
 class ProtoNet(FewShotFeatures):
+    detect_clean_shots = False  # ProtoNet_Contrast: the clean-shot detection decides which shots form a way's prototype
+
     def __init__(self, args):
         super().__init__(args)
         self.dist_method = args.dist_method
@@ -48,7 +54,41 @@ class ProtoNet(FewShotFeatures):
         # eval-mode BatchNorm uses running statistics, so all clouds of all episodes share one encoder pass; rows per
         # episode: its S support clouds, then its n_q query clouds
         feat = self.getFeatures_pm(ops.cat_clouds(sx, query_x, 1).reshape(E * (S + n_q), self.in_channels, N), group=S + n_q)
+        shot_keep = None
+        if self.detect_clean_shots:  # Mean_pl_support_y_multi_scale (protonet.py:491-565): the decision rule of mpti.py:178-223
+            shot_keep = ops.clean_shot_detect(feat, sx, support_y, self.n_way, self.k_shot, N, E=E, feat_ep_rows=(S + n_q) * N)
+        if self._trace is not None:
+            self._trace.update(feat=feat, shot_keep=shot_keep)
         Z = ops.protonet_head_batched(feat, feat[S * N:], support_y, self.n_way, self.k_shot, N, self.dist_method, E,
-                                      (S + n_q) * N, n_q * N)
+                                      (S + n_q) * N, n_q * N, shot_keep=shot_keep)
         labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
         return ops.logits_ce_from_rows(Z, E, n_q, N, self.n_way + 1, labels)
+
+
+class ProtoNet_Contrast(ProtoNet):
+    """The reference's noise-robust baseline at test time: ProtoNet whose foreground prototypes average the shots the
+    clean-shot detection kept (getPrototype(clean_flag=...), protonet.py:892-915); the background prototype takes every
+    shot.  State-dict names are the reference's, `proj` (the contrastive projection, used in training only) included, so a
+    checkpoint saved from the reference class loads strictly.  Training (`train=True`: per_way_contrast_loss) is not built:
+    the reference has no learner that runs it."""
+    detect_clean_shots = True
+
+    def __init__(self, args):
+        super().__init__(args)
+        # the reference hard-codes feat_dim = 192 (protonet.py:382) for proj and for the clean_flag mask of getPrototype
+        if self.feat_dim != 192:
+            raise NotImplementedError("ProtoNet_Contrast: the reference fixes feat_dim = 192 (proj is Linear(192, 128), "
+                                      "models/protonet.py:382-383); these widths give %d, which no checkpoint of it matches"
+                                      % self.feat_dim)
+        self.proj = nn.Linear(self.feat_dim, 128)
+
+    def forward(self, support_x, support_y, query_x, query_y, gt_support_y=None, gt_query_y=None, train=False, logger=None,
+                step=None, path=None, sampled_classes=None, bg_pcd_x=None, bg_pcd_y=None, support_c=None, support_flag=None,
+                pcd_1024=None, label_1024=None, pcd_cutout=None, label_cutout=None):
+        if train or self.training:
+            raise NotImplementedError("ProtoNet_Contrast is built for evaluation (train=False on a module in .eval() mode): "
+                                      "its train=True branch (per_way_contrast_loss) needs a learner the reference does not "
+                                      "have; train the checkpoint as ProtoNet")
+        logits, loss, _ = self._forward_eval(support_x[None], support_y[None], query_x[None],
+                                             query_y[None] if query_y is not None else None)
+        return logits[0], loss[0]
