@@ -135,7 +135,9 @@ int r3d_edgeconv_fwd(const float* PQ, const int32_t* idx, const float* W2, const
  * seed by 2 per episode); outputs are bit for bit those of that call.
  * ws: r3d_attention_ws_words_ep_d(B, N, seed_group, D) floats.  It holds the packed bf16 x 3 operands (without it the
  * forward runs on the fp32 core) and the partials of the key-axis split, which is chosen for ONE episode (seed_group
- * clouds) whatever the batch.  The forward may run without ws, the backward needs it.
+ * clouds) whatever the batch.  The forward may run without ws, the backward needs it.  B is a multiple of seed_group,
+ * except in the forward with p_drop == 0, where seed_group only selects that split: a part of an episode's clouds (a
+ * fitted support set, the query groups attached to it later) is split as the whole episode would be.
  * ws_holds_packed_qkv != 0: ws is the workspace the forward ran with on this qkv, untouched since (the bf16 x 3 kernels
  * reuse the packed q | k | v pieces it holds instead of cutting them again). */
 long r3d_attention_ws_words_ep_d(int B, int N, int seed_group, int D);
@@ -185,6 +187,22 @@ int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_t* support_
                                 long ldn, long nodes_ep_rows, float* node_labels, int32_t* desc, long desc_stride,
                                 int32_t* assign_out, long assign_stride, int32_t* cluster_count, long ccount_stride,
                                 int32_t* ws, long ws_words, long ws_stride, int flags, void* stream);
+/* A support set fitted once, queried many times: the prototypes of models/mpti.py:488-489 depend on the support set alone,
+ * the node matrix of :508 is cat(prototypes, query_feat).  ONE fitted system -- the first rows of the nodes / node_labels a
+ * r3d_head_prototypes_batched call left (n_way > 3: its second label plane fit_label_rows rows behind the first), its desc
+ * and, optionally, its cluster_count -- is attached to n_sys systems of query rows (system g's n_query_pts rows start
+ * qfeat_sys_rows rows after system g - 1's): destination system g (node / label rows [g n_cap, (g + 1) n_cap), plane 1 of
+ * the labels n_sys * n_cap rows behind plane 0) receives the n_proto prototype rows and their label rows, then its query
+ * rows with zero label rows; its desc is the fitted one with n_nodes = n_proto + n_query_pts.  n_proto is read from
+ * fit_desc ON THE DEVICE (no host read) and clamped to proto_cap, the prototype rows the fitted system can hold,
+ * (n_way + 1) * (k + 1); proto_cap + n_query_pts > n_cap is refused with an error code.  One pass of 16-byte loads and
+ * stores: D, fit_ldn, ldq, ldn multiples of 4, all row pointers 16-byte aligned.  Afterwards r3d_knn_topk_batched,
+ * r3d_label_propagate_batched and r3d_query_logits_ce_batched run on the destination as after r3d_head_prototypes_batched. */
+int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes, long fit_ldn, const float* fit_labels,
+                                    long fit_label_rows, const int32_t* fit_desc, const int32_t* fit_cluster_count,
+                                    int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way, int D,
+                                    int n_query_pts, float* nodes, long ldn, int n_cap, float* node_labels, int32_t* desc,
+                                    long desc_stride, int32_t* cluster_count, long ccount_stride, void* stream);
 
 /* ---- affinity + label propagation (models/mpti.py:717-776) ---------------------------
  * nbr (n_cap, kp1) from r3d_knn_topk mode 1 (column 0 is dropped as in mpti.py:736).
@@ -402,6 +420,24 @@ int r3d_protonet_head_keep_batched(int n_ep, const float* sfeat, long ldf, const
                                    int D, const int32_t* support_y, const int32_t* shot_keep, int n_way, int k_shot, int N,
                                    int n_query_pts, int method, float scaler, float* Z, float* ws, long ws_words,
                                    void* stream);
+/* The two halves of the evaluation head, for a support set that is fitted once and queried many times (the prototypes
+ * depend on the support set alone: getPrototype, models/protonet.py:892-915 with clean_flag, :326-336 without).
+ * r3d_protonet_prototypes_batched: masked pooling (getMaskedFeatures, protonet.py:837-842) + prototypes -> protos
+ * (n_ep, n_way + 1, D) fp32, background first; sfeat / feat_ep_rows / support_y / shot_keep as in
+ * r3d_protonet_head_keep_batched (foreground: kept shots, background: every shot), ws: r3d_protonet_head_ws_words floats.
+ * It reads the S*N support rows of each episode and nothing else.
+ * r3d_protonet_similarity_batched: calculateSimilarity (protonet.py:338-349) of n_sys systems' query rows -- system g's
+ * n_query_pts rows start q_sys_rows rows after system g - 1's -- against a prototype table, system g's at protos +
+ * g * proto_stride floats; proto_stride = 0 broadcasts ONE table to every system.  Z as r3d_protonet_head_batched writes
+ * it (n_sys * n_query_pts rows per plane).  It never touches support memory.
+ * The pair computes what r3d_protonet_head_keep_batched computes, bit for bit: the same device functions form the
+ * prototypes and the similarities in both (the fused call keeps the table in LDS instead of writing it out). */
+int r3d_protonet_prototypes_batched(int n_ep, const float* sfeat, long ldf, long feat_ep_rows, int D, const int32_t* support_y,
+                                    const int32_t* shot_keep, int n_way, int k_shot, int N, float* protos, float* ws,
+                                    long ws_words, void* stream);
+int r3d_protonet_similarity_batched(int n_sys, const float* qfeat, long ldq, long q_sys_rows, int D, const float* protos,
+                                    long proto_stride, int n_way, int n_query_pts, int method, float scaler, float* Z,
+                                    void* stream);
 /* correct (n_ep) int32 = per episode #{pred == label}: pred (n_ep, n_pts) int32 as r3d_query_logits_ce_batched writes it,
  * labels (n_ep, n_pts) int64.  One host read then serves the accuracy of a whole batch. */
 int r3d_count_correct_batched(int n_ep, const int32_t* pred, const int64_t* labels, long n_pts, int32_t* correct,

@@ -678,8 +678,10 @@ static void attention_launch_d(const float* qkv, long ld, int B, int N, float* o
 static int attention_launch(const float* qkv, long ld, int B, int N, float* out, long ldo, float* lse_out, float p_drop,
                             unsigned seed, const unsigned* seed_dev, int seed_group, int D, float* ws, void* stream) {
   R3D_REQUIRE(at_width_ok(D), "r3d_attention_fwd: head width %d is not one of 32, 64, 96, 128", D);
-  R3D_REQUIRE(seed_group >= 0 && (seed_group == 0 || B % seed_group == 0), "r3d_attention_fwd: %d clouds in groups of %d", B,
-              seed_group);
+  // (without dropout the group only selects the key-axis split: a part of an episode's clouds -- a fitted support set, the
+  // query groups attached to it later -- is then split as the whole episode of seed_group clouds would be)
+  R3D_REQUIRE(seed_group >= 0 && (seed_group == 0 || B % seed_group == 0 || p_drop == 0.f),
+              "r3d_attention_fwd: %d clouds in groups of %d", B, seed_group);
   R3D_REQUIRE(qkv && out, "r3d_attention_fwd: null pointer");
   R3D_REQUIRE(B > 0 && N > 0 && ld >= 3 * D && ld % 4 == 0 && ldo >= D,
               "r3d_attention_fwd: bad shape B=%d N=%d ld=%ld ldo=%ld D=%d", B, N, ld, ldo, D);

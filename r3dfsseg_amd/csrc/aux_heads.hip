@@ -221,14 +221,12 @@ __global__ __launch_bounds__(256) void r3d_proto_pool_kernel(const float* __rest
 // keep (n_way*k_shot) or null: a way's foreground prototype is the mean of its kept shots (getPrototype(clean_flag=...),
 // protonet.py:904-911), walked in shot order as without it -- all kept: the same additions, the same divisor --; the
 // background prototype takes every shot either way.  keep[...] is the same word for every lane: the branch is wave-uniform.
-static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ pooled, const int* __restrict__ keep, int n_way,
-                                                    int k_shot, const float* __restrict__ qfeat, long ldq, int D, int n_pts,
-                                                    int method, float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2,
-                                                    int blk, int nblk) {
-  __shared__ float proto[8][AH_DMAX];
-  __shared__ float pnorm[8];
+// The two halves are device functions of their own: the fused kernels (one launch pair per head) and the fitted-support
+// kernels (prototype table written out once, similarity against it later) run the SAME arithmetic.
+// ah_build_protos: thread tid < D leaves channel tid of the n_way + 1 prototypes in proto[0 .. n_way][tid].
+static __device__ __forceinline__ void ah_build_protos(const float* __restrict__ pooled, const int* __restrict__ keep, int n_way,
+                                                       int k_shot, int D, float (*proto)[AH_DMAX]) {
   const int tid = threadIdx.x;
-  const int n_classes = n_way + 1;
   if (tid < D) {
     float bgp = 0.f;
     for (int s = 0; s < n_way * k_shot; ++s) bgp += pooled[((long)s * 2 + 1) * AH_DMAX + tid];
@@ -244,6 +242,14 @@ static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ po
       proto[wy + 1][tid] = f / (float)n_kept;  // (no kept shot: 0 / 0, the caller's error -- r3d.h)
     }
   }
+}
+// ah_sim_points: proto[0 .. n_way][0 .. D) filled by the workgroup's threads (not yet synchronised) -> the Z rows of its points
+static __device__ __forceinline__ void ah_sim_points(float (*proto)[AH_DMAX], float* pnorm, int n_way,
+                                                     const float* __restrict__ qfeat, long ldq, int D, int n_pts, int method,
+                                                     float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2, int blk,
+                                                     int nblk) {
+  const int tid = threadIdx.x;
+  const int n_classes = n_way + 1;
   __syncthreads();
   if (tid < D)
     for (int k = n_classes; k < 8; ++k) proto[k][tid] = 0.f;
@@ -280,6 +286,15 @@ static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ po
     if (lane == 0) Zq[p] = make_float4(out[0], out[1], out[2], out[3]);
     if (lane == 0 && Zq2) Zq2[p] = make_float4(out[4], out[5], out[6], out[7]);
   }
+}
+static __device__ __forceinline__ void ah_proto_sim(const float* __restrict__ pooled, const int* __restrict__ keep, int n_way,
+                                                    int k_shot, const float* __restrict__ qfeat, long ldq, int D, int n_pts,
+                                                    int method, float scaler, float4* __restrict__ Zq, float4* __restrict__ Zq2,
+                                                    int blk, int nblk) {
+  __shared__ float proto[8][AH_DMAX];
+  __shared__ float pnorm[8];
+  ah_build_protos(pooled, keep, n_way, k_shot, D, proto);
+  ah_sim_points(proto, pnorm, n_way, qfeat, ldq, D, n_pts, method, scaler, Zq, Zq2, blk, nblk);
 }
 
 __global__ __launch_bounds__(256) void r3d_proto_sim_kernel(const float* __restrict__ pooled, int n_way, int k_shot,
@@ -341,6 +356,36 @@ __global__ __launch_bounds__(256) void r3d_proto_sim_ep_kernel(const float* __re
   ah_proto_sim(pooled + ep * n_way * k_shot * 2 * AH_DMAX, shot_keep ? shot_keep + ep * n_way * k_shot : nullptr, n_way, k_shot,
                qfeat + ep * feat_ep_rows * ldq, ldq, D, n_pts, method, scaler, Zq + ep * n_pts,
                Zq2 ? Zq2 + ep * n_pts : nullptr, blockIdx.x, gridDim.x);
+}
+
+// ---- the head in two calls (a fitted support set): prototype table out, similarity against a table -------------------------
+// grid (n_ep): ah_build_protos of episode e -> protos (n_ep, n_way + 1, D)
+__global__ __launch_bounds__(256) void r3d_proto_table_kernel(const float* __restrict__ pooled,
+                                                              const int* __restrict__ shot_keep, int n_way, int k_shot, int D,
+                                                              float* __restrict__ protos) {
+  __shared__ float proto[8][AH_DMAX];
+  const long ep = blockIdx.x;
+  const int tid = threadIdx.x;
+  ah_build_protos(pooled + ep * n_way * k_shot * 2 * AH_DMAX, shot_keep ? shot_keep + ep * n_way * k_shot : nullptr, n_way,
+                  k_shot, D, proto);
+  if (tid < D)  // (a thread reads back the channel it wrote)
+    for (int c = 0; c <= n_way; ++c) protos[(ep * (n_way + 1) + c) * D + tid] = proto[c][tid];
+}
+// grid (query tiles, n_sys): system g's table at protos + g * proto_stride (0: one table for all), its rows q_sys_rows
+// rows after system g - 1's
+__global__ __launch_bounds__(256) void r3d_proto_sim_table_kernel(const float* __restrict__ protos, long proto_stride, int n_way,
+                                                                  const float* __restrict__ qfeat, long ldq, long q_sys_rows,
+                                                                  int D, int n_pts, int method, float scaler,
+                                                                  float4* __restrict__ Zq, float4* __restrict__ Zq2) {
+  __shared__ float proto[8][AH_DMAX];
+  __shared__ float pnorm[8];
+  const long g = blockIdx.y;
+  const int tid = threadIdx.x;
+  const float* t = protos + g * proto_stride;
+  if (tid < D)
+    for (int c = 0; c <= n_way; ++c) proto[c][tid] = t[(long)c * D + tid];
+  ah_sim_points(proto, pnorm, n_way, qfeat + g * q_sys_rows * ldq, ldq, D, n_pts, method, scaler, Zq + g * n_pts,
+                Zq2 ? Zq2 + g * n_pts : nullptr, blockIdx.x, gridDim.x);
 }
 
 // correct[e] = #{pred == label} over the n_pts query points of episode e (integers: any order gives the same count).  grid (n_ep)
@@ -480,6 +525,58 @@ extern "C" int r3d_protonet_head_batched(int n_ep, const float* sfeat, long ldf,
                                          int method, float scaler, float* Z, float* ws, long ws_words, void* stream) {
   return ah_protonet_head_ep("r3d_protonet_head_batched", n_ep, sfeat, ldf, qfeat, ldq, feat_ep_rows, D, support_y, nullptr,
                              n_way, k_shot, N, n_query_pts, method, scaler, Z, ws, ws_words, stream);
+}
+
+// The head's halves as calls of their own (include/r3d.h): the prototype table of n_ep support sets, and the similarity
+// rows of n_sys query groups against a table.  The table kernel reads pooled means only; the similarity kernel reads the
+// table and the query rows it is given.
+extern "C" int r3d_protonet_prototypes_batched(int n_ep, const float* sfeat, long ldf, long feat_ep_rows, int D,
+                                               const int32_t* support_y, const int32_t* shot_keep, int n_way, int k_shot, int N,
+                                               float* protos, float* ws, long ws_words, void* stream) {
+  const char* who = "r3d_protonet_prototypes_batched";
+  R3D_REQUIRE(sfeat && support_y && protos && ws, "%s: null pointer", who);
+  R3D_REQUIRE(n_way >= 1 && n_way <= 7 && D >= 1 && D <= AH_DMAX && k_shot >= 1 && (long)n_way * k_shot <= 65535 && N >= 1 &&
+                  ldf >= D,
+              "%s: unsupported shape n_way=%d k_shot=%d N=%d D=%d", who, n_way, k_shot, N, D);
+  const int S = n_way * k_shot;
+  R3D_REQUIRE(n_ep >= 1 && n_ep <= 65535 && (n_ep == 1 || feat_ep_rows >= (long)S * N),
+              "%s: %d episodes, %ld rows between them", who, n_ep, feat_ep_rows);
+  const long need = r3d_protonet_head_ws_words(n_ep, n_way, k_shot);
+  R3D_REQUIRE(ws_words >= need, "%s: workspace of %ld words is shorter than r3d_protonet_head_ws_words = %ld", who, ws_words,
+              need);
+  R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)shot_keep & 3) == 0, "%s: ws must be 16-byte, shot_keep 4-byte aligned",
+              who);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(r3d_proto_pool_ep_kernel, dim3(S, n_ep), dim3(256), 0, st, sfeat, ldf, feat_ep_rows, D, support_y, N, ws);
+  hipLaunchKernelGGL(r3d_proto_table_kernel, dim3(n_ep), dim3(256), 0, st, ws, shot_keep, n_way, k_shot, D, protos);
+  R3D_LAUNCH_CHECK(who);
+  return R3D_OK;
+}
+extern "C" int r3d_protonet_similarity_batched(int n_sys, const float* qfeat, long ldq, long q_sys_rows, int D,
+                                               const float* protos, long proto_stride, int n_way, int n_query_pts, int method,
+                                               float scaler, float* Z, void* stream) {
+  const char* who = "r3d_protonet_similarity_batched";
+  R3D_REQUIRE(qfeat && protos && Z, "%s: null pointer", who);
+  R3D_REQUIRE(n_way >= 1 && n_way <= 7 && D >= 1 && D <= AH_DMAX && n_query_pts >= 1 && ldq >= D,
+              "%s: unsupported shape n_way=%d n_query_pts=%d D=%d", who, n_way, n_query_pts, D);
+  if (method != 0 && method != 1) {
+    // the reference raises NotImplementedError for anything but cosine / euclidean (protonet.py:347)
+    r3d_set_error("Error! Distance computation method (%d) is unknown!", method);
+    return R3D_ERR_UNSUPPORTED;
+  }
+  R3D_REQUIRE(n_sys >= 1 && n_sys <= 65535 && (n_sys == 1 || q_sys_rows >= n_query_pts),
+              "%s: %d systems, %ld rows between them", who, n_sys, q_sys_rows);
+  R3D_REQUIRE(proto_stride == 0 || proto_stride >= (long)(n_way + 1) * D,
+              "%s: prototype stride %ld (0 = one table for every system, else >= (n_way + 1) * D = %ld)", who, proto_stride,
+              (long)(n_way + 1) * D);
+  R3D_REQUIRE(((uintptr_t)Z & 15) == 0, "%s: Z must be 16-byte aligned", who);
+  // the tiling of ah_protonet_head_ep (a point's arithmetic does not depend on the grid)
+  const int gx = min(r3d_cdiv(n_query_pts, 4), max(32, min(256, 2048 / n_sys)));
+  hipLaunchKernelGGL(r3d_proto_sim_table_kernel, dim3(gx, n_sys), dim3(256), 0, (hipStream_t)stream, protos, proto_stride, n_way,
+                     qfeat, ldq, q_sys_rows, D, n_query_pts, method, scaler, (float4*)Z,
+                     n_way > 3 ? (float4*)Z + (long)n_sys * n_query_pts : nullptr);
+  R3D_LAUNCH_CHECK(who);
+  return R3D_OK;
 }
 
 // correct (n_ep) int32: per episode the number of query points whose arg-max (pred (n_ep, n_pts) int32, as

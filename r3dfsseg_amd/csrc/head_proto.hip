@@ -980,6 +980,114 @@ extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_
 }
 
 // ---------------------------------------------------------------------------
+// A fitted support set: ONE system's prototype rows in front of n_sys systems' query rows (include/r3d.h).
+// A copy, so a bandwidth kernel: one pass, a thread moves AT_UNROLL float4 (16 bytes along D) of consecutive 256-float4
+// stripes -- the loads of all of them issued before the first store --, a wave's 64 lanes cover 1 KB of contiguous row data
+// (rows are D / 4 float4 long, D % 4 == 0: a float4 never straddles two rows).  Source "row" r of a system is prototype row r
+// for r < proto_cap (skipped beyond the n_proto the fitted desc holds) and query row r - proto_cap after that, which lands
+// at node row n_proto + (r - proto_cap).  The thread of a row's first float4 writes its label row(s); the first workgroup of
+// a system writes its desc.  n_proto comes from fit_desc on the device, clamped to proto_cap (the host checked proto_cap +
+// n_query_pts <= n_cap): no index leaves [0, n_cap).  grid (stripes, n_sys).
+// ---------------------------------------------------------------------------
+#define AT_UNROLL 4
+__global__ __launch_bounds__(256) void r3d_head_attach_queries_kernel(
+    const float4* __restrict__ fit_nodes, long fit_ld4, const float4* __restrict__ fit_labels,
+    const float4* __restrict__ fit_labels2 /* or null */, const int* __restrict__ fit_desc,
+    const int* __restrict__ fit_ccount /* or null */, int proto_cap, const float4* __restrict__ qfeat, long ldq4,
+    long qfeat_sys_rows, int d4, int nq_pts, float4* __restrict__ nodes, long ldn4, int n_cap, float4* __restrict__ labels,
+    float4* __restrict__ labels2 /* or null */, int* __restrict__ desc, long desc_stride, int* __restrict__ ccount /* or null */,
+    long ccount_stride) {
+  const long sys = blockIdx.y;
+  const int tid = threadIdx.x;
+  int n_proto = fit_desc[HD_N_PROTO];
+  n_proto = n_proto < 0 ? 0 : (n_proto > proto_cap ? proto_cap : n_proto);
+  if (blockIdx.x == 0 && tid < HD_WORDS)
+    desc[sys * desc_stride + tid] = tid == HD_N_PROTO ? n_proto : tid == HD_N_NODES ? n_proto + nq_pts : fit_desc[tid];
+  qfeat += sys * qfeat_sys_rows * ldq4;
+  nodes += sys * n_cap * ldn4;
+  labels += sys * n_cap;
+  if (labels2) labels2 += sys * n_cap;
+  const unsigned total = (unsigned)(proto_cap + nq_pts) * (unsigned)d4;  // (< 2^31: checked by the entry point)
+  const unsigned i0 = blockIdx.x * (256u * AT_UNROLL) + tid;
+  float4 v[AT_UNROLL], l0[AT_UNROLL], l1[AT_UNROLL];
+  int dst[AT_UNROLL], col[AT_UNROLL], cnt[AT_UNROLL];
+#pragma unroll
+  for (int u = 0; u < AT_UNROLL; ++u) {
+    const unsigned i = i0 + 256u * u;
+    dst[u] = -1;
+    if (i >= total) continue;
+    const int r = (int)(i / (unsigned)d4), c = (int)(i - (unsigned)r * (unsigned)d4);
+    col[u] = c;
+    l0[u] = l1[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    cnt[u] = -1;
+    if (r < proto_cap) {
+      if (r >= n_proto) continue;  // (a prototype slot the fit left empty)
+      dst[u] = r;
+      v[u] = fit_nodes[(long)r * fit_ld4 + c];
+      if (c == 0) {
+        l0[u] = fit_labels[r];
+        if (fit_labels2) l1[u] = fit_labels2[r];
+        if (fit_ccount) cnt[u] = fit_ccount[r];
+      }
+    } else {
+      const int q = r - proto_cap;
+      dst[u] = n_proto + q;
+      v[u] = qfeat[(long)q * ldq4 + c];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < AT_UNROLL; ++u) {
+    if (dst[u] < 0) continue;
+    nodes[(long)dst[u] * ldn4 + col[u]] = v[u];
+    if (col[u] == 0) {
+      labels[dst[u]] = l0[u];
+      if (labels2) labels2[dst[u]] = l1[u];
+      if (ccount && cnt[u] >= 0) ccount[sys * ccount_stride + dst[u]] = cnt[u];
+    }
+  }
+}
+
+extern "C" int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes, long fit_ldn, const float* fit_labels,
+                                               long fit_label_rows, const int32_t* fit_desc, const int32_t* fit_cluster_count,
+                                               int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way,
+                                               int D, int n_query_pts, float* nodes, long ldn, int n_cap, float* node_labels,
+                                               int32_t* desc, long desc_stride, int32_t* cluster_count, long ccount_stride,
+                                               void* stream) {
+  const char* fn = "r3d_head_attach_queries_batched";
+  R3D_REQUIRE(fit_nodes && fit_labels && fit_desc && qfeat && nodes && node_labels && desc, "%s: null pointer", fn);
+  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= HP_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
+              "%s: unsupported geometry n_way=%d D=%d (n_way <= 7, D <= 256 and a multiple of 4)", fn, n_way, D);
+  R3D_REQUIRE(n_sys >= 1 && n_sys <= 65535 && n_query_pts >= 1 && proto_cap >= 1 && (n_sys == 1 || qfeat_sys_rows >= n_query_pts),
+              "%s: %d systems of %d query rows (%ld rows between them), %d prototype slots", fn, n_sys, n_query_pts,
+              qfeat_sys_rows, proto_cap);
+  R3D_REQUIRE((long)proto_cap + n_query_pts <= n_cap,
+              "%s: node buffer of n_cap = %d rows is shorter than %d prototype slots + %d query rows", fn, n_cap, proto_cap,
+              n_query_pts);
+  R3D_REQUIRE(fit_label_rows >= proto_cap, "%s: %ld label rows per plane hold fewer than %d prototype slots", fn,
+              fit_label_rows, proto_cap);
+  R3D_REQUIRE(((long)proto_cap + n_query_pts) * (D / 4) < 0x7fffffffL, "%s: %d rows x %d channels do not fit 31 bits", fn,
+              proto_cap + n_query_pts, D);
+  R3D_REQUIRE(fit_ldn >= D && ldq >= D && ldn >= D && fit_ldn % 4 == 0 && ldq % 4 == 0 && ldn % 4 == 0,
+              "%s: row pitches %ld / %ld / %ld must be multiples of 4 floats >= D = %d", fn, fit_ldn, ldq, ldn, D);
+  R3D_REQUIRE((((uintptr_t)fit_nodes | (uintptr_t)fit_labels | (uintptr_t)qfeat | (uintptr_t)nodes | (uintptr_t)node_labels) & 15) == 0,
+              "%s: node, label and query rows must be 16-byte aligned", fn);
+  R3D_REQUIRE(desc_stride >= HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)HD_WORDS);
+  R3D_REQUIRE(!cluster_count || n_sys == 1 || ccount_stride >= n_cap, "%s: cluster_count stride %ld < n_cap = %d", fn,
+              ccount_stride, n_cap);
+  const int d4 = D / 4;
+  const long total = ((long)proto_cap + n_query_pts) * d4;
+  const float4* fl = (const float4*)fit_labels;
+  float4* nl = (float4*)node_labels;
+  hipLaunchKernelGGL(r3d_head_attach_queries_kernel, dim3(r3d_cdiv(total, 256L * AT_UNROLL), n_sys), dim3(256), 0,
+                     (hipStream_t)stream, (const float4*)fit_nodes, fit_ldn / 4, fl, n_way > 3 ? fl + fit_label_rows : nullptr,
+                     fit_desc, fit_cluster_count, proto_cap, (const float4*)qfeat, ldq / 4, qfeat_sys_rows, d4, n_query_pts,
+                     (float4*)nodes, ldn / 4, n_cap, nl, n_way > 3 ? nl + (long)n_sys * n_cap : nullptr, desc, desc_stride,
+                     cluster_count, ccount_stride);
+  R3D_LAUNCH_CHECK(fn);
+  return R3D_OK;
+}
+
+// ---------------------------------------------------------------------------
 // backward of the cluster means (training): every listed support point receives
 // dproto[cluster] / |cluster| ; query rows copy through.  One wave per list position.
 // ---------------------------------------------------------------------------

@@ -1,0 +1,177 @@
+"""A support set fitted once, query clouds segmented against it as they arrive.
+
+In .eval() mode BatchNorm uses running statistics and dropout is off, so what the support set contributes to an episode is
+a fixed table: the prototypes of models/protonet.py:837-842,892-915 (ProtoNet, ProtoNet_Contrast) or the multi-prototype
+node rows of models/mpti.py:488-489 (MPTI_SelfAtten).  model.fit_support(...) computes it and returns a FittedSupport that
+owns the device tables -- no features, no support clouds --; model.predict(fitted, query_x) runs the query clouds through
+the encoder and the query half of the head only.  The rule: predict on a query group gives THE SAME BITS as forward() on the
+episode made of that support set and that group (tests/test_gpu_fitted.py).
+
+A FittedSupport is bound to the weights it was fitted with.  Its key is, per parameter and buffer, the `_version` counter
+(what DGCNN._fold keys its folded weights on) and the storage address, plus a 64-bit sum over the words of all of them: the
+counters see optimizer steps, load_state_dict and every in-place operation on the tensors themselves, but a write through
+`.data` has a version counter of its own and only the contents show it.  predict() recomputes the key -- for device
+modules one concatenation, one sum and one host read -- and raises ValueError on a stale fit before it launches anything
+of its own.
+
+This module holds the host logic (argument checks, the key, the object); the launches are in protonet.py and mpti.py.
+"""
+import torch
+
+
+def _tensors(module):
+    return list(module.parameters()) + list(module.buffers())
+
+
+def version_key(module):
+    """(versions, addresses) of the module's parameters and buffers: host only, no device work."""
+    ts = _tensors(module)
+    return tuple(t._version for t in ts), tuple(t.data_ptr() for t in ts)
+
+
+def content_sum(module):
+    """64-bit sum of the 32-bit words of every parameter and buffer (one host read on a device module)."""
+    with torch.no_grad():
+        words = [t.detach().reshape(-1).view(torch.int32) for t in _tensors(module) if t.numel()]
+        if not words:
+            return 0
+        return int(torch.cat(words).sum(dtype=torch.int64).item())
+
+
+def model_key(module):
+    return version_key(module) + (content_sum(module),)
+
+
+class FittedHead:
+    """The one-system head state of an MPTI fit: what r3d_head_attach_queries_batched reads.  nodes (proto_cap, D): the
+    prototype rows (the first desc[HD_N_PROTO] are filled); Y: their label rows, label_rows per plane; desc (32,) int32;
+    cluster_count (label_rows,) int32."""
+
+    def __init__(self, nodes, Y, label_rows, desc, cluster_count, proto_cap):
+        self.nodes, self.Y, self.label_rows, self.desc, self.cluster_count, self.proto_cap = \
+            nodes, Y, label_rows, desc, cluster_count, proto_cap
+
+
+class FittedSupport:
+    """What fit_support returns.  protos: (1, n_way + 1, D) prototype table, background first (ProtoNet family) or None;
+    head: FittedHead (MPTI) or None; shot_keep: (n_way * k_shot,) int32 if the clean-shot detection ran, else None;
+    shape: (n_way, k_shot, in_channels, n_points); eval: the eval flag of the fit; schedule: 'default' or 'conservative'
+    (fitted with lp_iters: one FPS launch per round); key: model_key of the model at fit time."""
+
+    def __init__(self, model, protos=None, head=None, shot_keep=None, eval=False, schedule="default", n_queries=None):
+        self.model_class = type(model).__name__
+        self.model_id = id(model)
+        self.shape = (model.n_way, model.k_shot, model.in_channels, model.n_points)
+        self.protos, self.head, self.shot_keep = protos, head, shot_keep
+        self.eval = bool(eval)
+        self.schedule = schedule
+        self.n_queries = n_queries
+        self.key = model_key(model)
+
+    def is_stale(self, model):
+        """Why this fit no longer belongs to `model` (a string), or None."""
+        if id(model) != self.model_id or type(model).__name__ != self.model_class:
+            return "it was fitted by another model object"
+        vk = version_key(model)
+        if vk != self.key[:2]:
+            return "parameters or running statistics were updated or replaced since fit_support (version counters)"
+        if content_sum(model) != self.key[2]:
+            return "parameter or running-statistic values changed in place since fit_support (content sum)"
+        return None
+
+
+def check_fit_args(model, support_x, support_y):
+    """Raises before anything needs a device.  -> S = n_way * k_shot."""
+    if model.training:
+        raise NotImplementedError("fit_support is the inference path (running-statistics BatchNorm, no dropout: the support "
+                                  "set's contribution is then a fixed table); call model.eval() first")
+    want_x = (model.n_way, model.k_shot, model.in_channels, model.n_points)
+    if not isinstance(support_x, torch.Tensor) or tuple(support_x.shape) != want_x:
+        raise ValueError("fit_support: support_x must be (n_way, k_shot, in_channels, n_points) = %s, got %s"
+                         % (want_x, tuple(support_x.shape) if isinstance(support_x, torch.Tensor) else type(support_x)))
+    want_y = (model.n_way, model.k_shot, model.n_points)
+    if not isinstance(support_y, torch.Tensor) or tuple(support_y.shape) != want_y:
+        raise ValueError("fit_support: support_y must be (n_way, k_shot, n_points) = %s, got %s"
+                         % (want_y, tuple(support_y.shape) if isinstance(support_y, torch.Tensor) else type(support_y)))
+    return model.n_way * model.k_shot
+
+
+def check_predict_args(model, fitted, query_x, query_y):
+    """Raises before any launch.  -> (G, n_q, grouped): query_x is (n_q, C, N) -- one group, grouped False -- or
+    (G, n_q, C, N)."""
+    if model.training:
+        raise NotImplementedError("predict is the inference path; call model.eval() first")
+    if not isinstance(fitted, FittedSupport):
+        raise ValueError("predict: `fitted` must be what fit_support returned, got %s" % type(fitted).__name__)
+    if not isinstance(query_x, torch.Tensor) or query_x.dim() not in (3, 4):
+        raise ValueError("predict: query_x must be (n_q, in_channels, n_points) or (G, n_q, in_channels, n_points)")
+    grouped = query_x.dim() == 4
+    C, N = fitted.shape[2], fitted.shape[3]
+    if tuple(query_x.shape[-2:]) != (C, N) or query_x.shape[-3] < 1 or (grouped and query_x.shape[0] < 1):
+        raise ValueError("predict: query clouds of shape %s do not match the fit: (in_channels, n_points) = (%d, %d)"
+                         % (tuple(query_x.shape), C, N))
+    if fitted.shape != (model.n_way, model.k_shot, model.in_channels, model.n_points):
+        raise ValueError("predict: the fit's episode shape %s is not this model's" % (fitted.shape,))
+    if query_y is not None and tuple(query_y.shape) != tuple(query_x.shape[:-2]) + (N,):
+        raise ValueError("predict: query_y of shape %s does not label query_x of shape %s"
+                         % (tuple(query_y.shape), tuple(query_x.shape)))
+    why = fitted.is_stale(model)
+    if why is not None:
+        raise ValueError("predict: stale fit -- %s; call fit_support again" % why)
+    return (query_x.shape[0] if grouped else 1), query_x.shape[-3], grouped
+
+
+def support_pair(data_or_support):
+    """An episode list (entries 0 and 1) or a (support_x, support_y) pair -> (support_x, support_y)."""
+    if len(data_or_support) < 2:
+        raise ValueError("fit: an episode list or a (support_x, support_y) pair is needed")
+    return data_or_support[0], data_or_support[1]
+
+
+class FittedLearner(object):
+    """fit() / predict() of the learners (needs self.model): annotate a handful of support clouds once, then label query
+    clouds as they arrive.  test(), test_batch() and train*() are untouched by it."""
+
+    fitted = None  # the FittedSupport of the latest fit()
+
+    def fit(self, data_or_support, eval=False):
+        """data_or_support: an episode list (entries 0 and 1 are used) or a (support_x, support_y) pair.  Stores and
+        returns the FittedSupport."""
+        support_x, support_y = support_pair(data_or_support)
+        self.model.eval()
+        with torch.no_grad():
+            self.fitted = self.model.fit_support(support_x.cuda(), support_y.cuda(), eval=eval)
+        return self.fitted
+
+    def _predict_once(self, fitted, query_x, query_y, lp_iters=None):
+        """-> (pred (G, n_q, N) int64, loss (G,) or None, correct (G,) int32 on the device or None)."""
+        from . import ops
+        grouped = check_predict_args(self.model, fitted, query_x, query_y)[2]
+        qx = query_x if grouped else query_x[None]
+        qy = query_y if (grouped or query_y is None) else query_y[None]
+        logits, loss, pred = self.model._predict_groups(fitted, qx, qy, lp_iters)
+        correct = ops.count_correct(pred, qy.to(torch.int64).contiguous()) if qy is not None else None
+        return pred.to(torch.int64), (loss if qy is not None else None), correct
+
+    def _predict_result(self, query_x, pred, loss, correct):
+        n = query_x.shape[-3] * query_x.shape[-1]
+        acc = [c / n for c in correct.tolist()] if correct is not None else [None] * pred.shape[0]  # (the call's host read)
+        res = [(pred[g], loss[g] if loss is not None else None, acc[g]) for g in range(pred.shape[0])]
+        return res if query_x.dim() == 4 else res[0]
+
+    def predict(self, query_x, query_y=None, fitted=None):
+        """query_x (n_q, C, N) -> (pred (n_q, N), loss, accuracy) with test()'s meaning, or (G, n_q, C, N) -> a list of G such
+        tuples from ONE launch sequence; loss and accuracy are None without query_y.  fitted: default the latest fit()."""
+        fitted = self._fitted_or_raise(fitted)
+        self.model.eval()
+        query_x = query_x.cuda()
+        query_y = query_y.cuda() if query_y is not None else None
+        with torch.no_grad():
+            pred, loss, correct = self._predict_once(fitted, query_x, query_y)
+        return self._predict_result(query_x, pred, loss, correct)
+
+    def _fitted_or_raise(self, fitted):
+        fitted = self.fitted if fitted is None else fitted
+        if fitted is None:
+            raise ValueError("predict: no fitted support set -- call fit() first or pass fitted=")
+        return fitted

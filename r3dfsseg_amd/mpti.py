@@ -128,6 +128,68 @@ class MPTI_SelfAtten(FewShotFeatures):
         self._lp_force = bool(lp_iters)
         return self._forward_eval(batch.support_x, batch.support_y, batch.query_x, batch.query_y, eval, lp_iters)
 
+    # ------------------------------------------------------------------ a support set fitted once (fitted.py)
+    def fit_support(self, support_x, support_y, eval=False, lp_iters=None, n_queries=None):
+        """The support half of _forward_eval, once: encoder over the S support clouds, clean-shot detection (eval=True), FPS,
+        assignment and cluster means -> fitted.FittedSupport owning the prototype rows, their labels, desc and cluster
+        counts of ONE system.  lp_iters: fit on the conservative schedule (one FPS launch per round).  One host read, as
+        test(): a persistent-FPS time-out refits with one launch per round, so the table is never one lp_converged() would
+        have rejected.  n_queries: see ProtoNet.fit_support."""
+        from . import fitted as F
+        S, N = F.check_fit_args(self, support_x, support_y), self.n_points
+        sx = support_x.reshape(S, self.in_channels, N)
+        feat = self.getFeatures_pm(sx, group=S + (n_queries or self.n_way))
+        shot_keep = ops.clean_shot_detect(feat, sx, support_y, self.n_way, self.k_shot, N) if eval else None
+        # a head of one system whose only "query" row is a support row it was given: the prototype half is all that is kept
+        hb = ops.HeadBuffers(self.n_way, self.k_shot, N, 1, self.n_subprototypes, self.k_connect, self.feat_dim, feat.device)
+        hb.fps_one_launch = self._slot.fps_one_launch and not lp_iters
+        sy = support_y.reshape(1, S, N).to(torch.int32).contiguous()
+        ops.head_prototypes(hb, sy, shot_keep, feat, feat)
+        if int(hb.desc[ops.HD_FPS_TIMEOUT].item()) != 0:  # (the fit's host read)
+            hb.fps_one_launch = False
+            ops.head_prototypes(hb, sy, shot_keep, feat, feat)
+        cap = hb.n_cap - 1
+        head = F.FittedHead(hb.nodes[:cap], hb.Y, hb.n_cap, hb.desc, hb.cluster_count, cap)
+        return F.FittedSupport(self, head=head, shot_keep=shot_keep, eval=eval,
+                               schedule="conservative" if lp_iters else "default", n_queries=n_queries)
+
+    def _predict_groups(self, fitted, query_x, query_y, lp_iters=None):
+        """query_x (G, n_q, C, N), query_y (G, n_q, N) or None -> logits (G, n_q, n_way + 1, N), loss (G,), pred (G, n_q, N)
+        int32: G systems [fitted prototypes | group g's query rows] in one launch sequence; the graph, the label
+        propagation and the logits are _forward_eval's."""
+        self._lp_force = bool(lp_iters)
+        G, n_q, N = query_x.shape[0], query_x.shape[1], self.n_points
+        S = self.n_way * self.k_shot
+        feat = self.getFeatures_pm(query_x.reshape(G * n_q, self.in_channels, N), group=S + n_q)
+        hb = self._head_buffers(n_q, feat.device, G)
+        ops.head_attach_queries(hb, fitted.head, feat)
+        nbr = ops.knn_nodes(hb, exact=bool(lp_iters))
+        if self.nbr_patch is not None:
+            nbr = self.nbr_patch(nbr)
+        ops.label_propagate(hb, nbr, self.sigma, 0.99, lp_iters or self._lp_next_budget(), self.lp_tol)
+        self._lp_post(hb)
+        labels = query_y.reshape(G, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
+        logits, loss, pred = ops.query_logits_ce(hb, n_q, self.n_classes, labels)
+        self.num_prototypes_dev = hb.desc.view(G, 32)[:, ops.HD_N_PROTO]
+        return logits.reshape(G, n_q, self.n_classes, N), loss.reshape(G), pred.reshape(G, n_q, N)
+
+    def predict(self, fitted, query_x, query_y=None, lp_iters=None):
+        """Segment query clouds against a fitted support set: query_x (n_q, C, N) -> (logits (n_q, n_way + 1, N), loss), or
+        (G, n_q, C, N) -> (logits (G, n_q, n_way + 1, N), loss (G,)); any n_q >= 1; loss is None without query_y.  Per group
+        the bits of forward(..., eval=fitted.eval, lp_iters=lp_iters) on the episode [that support set | that group];
+        lp_converged() then speaks for the G systems, as after forward_episodes.  ValueError, before any launch, for a shape
+        that does not match the fit or a fit whose weights have changed since (fitted.py)."""
+        from . import fitted as F
+        _, _, grouped = F.check_predict_args(self, fitted, query_x, query_y)
+        if fitted.head is None:
+            raise ValueError("predict: the fit holds no MPTI head state (it was fitted by %s)" % fitted.model_class)
+        qx = query_x if grouped else query_x[None]
+        qy = query_y if (grouped or query_y is None) else query_y[None]
+        logits, loss, _ = self._predict_groups(fitted, qx, qy, lp_iters)
+        if not grouped:
+            logits, loss = logits[0], loss[0]
+        return logits, (loss if query_y is not None else None)
+
     def _forward_eval(self, support_x, support_y, query_x, query_y, eval, lp_iters):
         """support_x (E, n_way, k_shot, C, N), support_y (E, n_way, k_shot, N), query_x (E, n_q, C, N), query_y (E, n_q, N)."""
         E = support_x.shape[0]

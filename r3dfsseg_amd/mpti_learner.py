@@ -18,11 +18,12 @@ import torch
 from torch import optim
 
 from .checkpoint_util import load_model_checkpoint, load_pretrain_checkpoint
+from .fitted import FittedLearner
 from .metrics import point_accuracy
 from .mpti import MPTI_SelfAtten
 
 
-class MPTILearner_V3(object):
+class MPTILearner_V3(FittedLearner):
     def __init__(self, args, mode='train'):
         self.model = MPTI_SelfAtten(args)
         if not torch.cuda.is_available():
@@ -180,6 +181,23 @@ class MPTILearner_V3(object):
             return [self.test(b.episode(e)[:4] + [None, None, b.gt_support_y[e]], sampled_classes, step, path, eval)
                     for e in range(b.E)]
         return [(pred[e], loss[e], acc[e]) for e in range(b.E)]
+
+    def predict(self, query_x, query_y=None, fitted=None):
+        """fitted.FittedLearner.predict, following test() on a miss: a call whose budgeted schedule did not converge (or
+        overflowed the 201-NN survivor buffer) is redone with lp_iters=model.lp_max_iter; it raises if that fails too."""
+        fitted = self._fitted_or_raise(fitted)
+        self.model.eval()
+        from . import dist as D
+        D.warn_rank_local_stats(self.model, 'evaluation')
+        query_x = query_x.cuda()
+        query_y = query_y.cuda() if query_y is not None else None
+        with torch.no_grad():
+            pred, loss, correct = self._predict_once(fitted, query_x, query_y)
+            if not self.model.lp_converged():
+                pred, loss, correct = self._predict_once(fitted, query_x, query_y, lp_iters=self.model.lp_max_iter)
+                if not self.model.lp_converged():
+                    raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
+        return self._predict_result(query_x, pred, loss, correct)
 
     def _test_graph(self, data, eval):
         from .episode_graph import EpisodeGraphs

@@ -504,6 +504,66 @@ def protonet_head_batched(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, metho
     return Z
 
 
+def protonet_prototypes(sfeat_pm, support_y, n_way, k_shot, N, n_ep=1, feat_ep_rows=0, shot_keep=None):
+    """The support half of protonet_head_batched: the prototype table (n_ep, n_way + 1, D), background first, of n_ep
+    support sets (sfeat_pm: the support rows of episode 0, episode e feat_ep_rows rows further on; shot_keep as there, a
+    device tensor or None).  Reads support rows only."""
+    _, ldf = _rows(sfeat_pm)
+    D = sfeat_pm.shape[1]
+    sy = support_y.reshape(n_ep * n_way * k_shot, N).to(torch.int32).contiguous()
+    dev = sfeat_pm.device
+    lib = _lib.load()
+    words = lib.r3d_protonet_head_ws_words(n_ep, n_way, k_shot)
+    if words < 0:
+        raise NotImplementedError("ProtoNet head: 1 <= n_way <= 7, 1 <= episodes <= 65535 (n_way=%d, episodes=%d)" % (n_way, n_ep))
+    keep = None
+    if shot_keep is not None:
+        if shot_keep.numel() != n_ep * n_way * k_shot:
+            raise ValueError("shot_keep has %d entries for %d episodes of %d-way %d-shot" % (shot_keep.numel(), n_ep, n_way, k_shot))
+        keep = shot_keep.to(device=dev, dtype=torch.int32).reshape(n_ep, n_way * k_shot).contiguous()
+    ws = torch.empty(words, device=dev, dtype=torch.float32)
+    protos = torch.empty(n_ep, n_way + 1, D, device=dev, dtype=torch.float32)
+    with _timed("protonet_prototypes"):
+        _lib.check(lib.r3d_protonet_prototypes_batched(n_ep, _p(sfeat_pm), ldf, feat_ep_rows, D, _p(sy), _p(keep), n_way, k_shot,
+                                                       N, _p(protos), _p(ws), words, _st()))
+    return protos
+
+
+def protonet_similarity(qfeat_pm, protos, n_way, method, n_sys, n_query_pts, q_sys_rows=None, scaler=10.0):
+    """The query half of protonet_head_batched: similarity rows Z (n_sys * n_query_pts, 4) per plane of n_sys systems' query
+    rows (system g's start q_sys_rows rows after system g - 1's; default: back to back) against a prototype table: protos
+    (n_way + 1, D) or (1, n_way + 1, D) serves every system, (n_sys, n_way + 1, D) gives each its own."""
+    _, ldq = _rows(qfeat_pm)
+    D = qfeat_pm.shape[1]
+    code = _proto_method(method)
+    assert protos.dtype == torch.float32 and protos.is_contiguous() and protos.shape[-2:] == (n_way + 1, D)
+    tables = protos.numel() // ((n_way + 1) * D)
+    assert tables in (1, n_sys), "one prototype table, or one per system"
+    assert qfeat_pm.shape[0] >= (n_sys - 1) * (q_sys_rows or n_query_pts) + n_query_pts
+    Z = torch.empty((1 if n_way <= 3 else 2) * n_sys * n_query_pts, 4, device=qfeat_pm.device, dtype=torch.float32)
+    with _timed("protonet_similarity"):
+        _lib.check(_lib.load().r3d_protonet_similarity_batched(
+            n_sys, _p(qfeat_pm), ldq, n_query_pts if q_sys_rows is None else q_sys_rows, D, _p(protos),
+            0 if tables == 1 else (n_way + 1) * D, n_way, n_query_pts, code, float(scaler), _p(Z), _st()))
+    return Z
+
+
+def head_attach_queries(hb, fit, qfeat_pm, q_sys_rows=None):
+    """The node matrices of hb.E systems from ONE fitted system and hb.E groups of query rows (system g's hb.n_q_pts rows
+    start q_sys_rows rows after system g - 1's; default: back to back).  fit: fitted.FittedHead (prototype rows, label rows,
+    desc and cluster counts of a head_prototypes call on the support set alone).  Afterwards knn_nodes, label_propagate and
+    query_logits_ce run on hb as after head_prototypes."""
+    _, ldq = _rows(qfeat_pm)
+    assert qfeat_pm.shape[1] == hb.D and fit.nodes.shape[1] == hb.D
+    step = hb.n_q_pts if q_sys_rows is None else q_sys_rows
+    assert qfeat_pm.shape[0] >= (hb.E - 1) * step + hb.n_q_pts
+    with _timed("head_attach_queries"):
+        _lib.check(_lib.load().r3d_head_attach_queries_batched(
+            hb.E, _p(fit.nodes), fit.nodes.stride(0), _p(fit.Y), fit.label_rows, _p(fit.desc), _p(fit.cluster_count),
+            fit.proto_cap, _p(qfeat_pm), ldq, step, hb.n_way, hb.D, hb.n_q_pts, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap,
+            _p(hb.Y), _p(hb.desc), 32, _p(hb.cluster_count), hb.n_cap, _st()))
+
+
 def protonet_head_train(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0, n_ep=1, feat_ep_rows=0,
                         n_query_pts=None):
     """Training forward of the ProtoNet head -> (Z, ws): the similarity rows of protonet_head (n_ep > 1: (n_ep * n_query_pts, 4)

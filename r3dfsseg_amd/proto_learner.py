@@ -6,13 +6,15 @@ import torch
 from torch import optim
 
 from .checkpoint_util import load_model_checkpoint, load_pretrain_checkpoint
+from .fitted import FittedLearner
 from .metrics import point_accuracy
 from .protonet import ProtoNet
 
 
-class ProtoEvalBatch(object):
+class ProtoEvalBatch(FittedLearner):
     """The evaluation half ProtoLearner and ProtoContrastLearner share: E episodes of one shape through
-    self.model.forward_episodes.  Needs self.model only."""
+    self.model.forward_episodes, and fit() / predict() (fitted.FittedLearner: a support set fitted once).  Needs self.model
+    only."""
 
     @staticmethod
     def _batch(datas):

@@ -64,6 +64,49 @@ class ProtoNet(FewShotFeatures):
         labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
         return ops.logits_ce_from_rows(Z, E, n_q, N, self.n_way + 1, labels)
 
+    # ------------------------------------------------------------------ a support set fitted once (fitted.py)
+    def fit_support(self, support_x, support_y, eval=False, lp_iters=None, n_queries=None):
+        """The support half of _forward_eval, once: encoder over the S support clouds, clean-shot detection
+        (ProtoNet_Contrast: always; ProtoNet: never -- `eval` and `lp_iters` are MPTI's and ignored here), masked pooling and
+        prototypes -> fitted.FittedSupport owning the (1, n_way + 1, D) table.  n_queries: the query clouds per group predict
+        will be called with, if known (default n_way, the reference's episodes): the attention then splits its key axis as
+        forward() does on the full episode (attention.hip: moot under the default of no split)."""
+        from . import fitted as F
+        S, N = F.check_fit_args(self, support_x, support_y), self.n_points
+        sx = support_x.reshape(S, self.in_channels, N)
+        feat = self.getFeatures_pm(sx, group=S + (n_queries or self.n_way))
+        shot_keep = None
+        if self.detect_clean_shots:
+            shot_keep = ops.clean_shot_detect(feat, sx, support_y, self.n_way, self.k_shot, N)
+        protos = ops.protonet_prototypes(feat, support_y, self.n_way, self.k_shot, N, shot_keep=shot_keep)
+        return F.FittedSupport(self, protos=protos, shot_keep=shot_keep, eval=eval, n_queries=n_queries)
+
+    def _predict_groups(self, fitted, query_x, query_y, lp_iters=None):
+        """query_x (G, n_q, C, N), query_y (G, n_q, N) or None -> logits (G, n_q, n_way + 1, N), loss (G,), pred (G, n_q, N)
+        int32: G groups against ONE fitted table in one launch sequence (encoder over the G n_q query clouds, similarity)."""
+        G, n_q, N = query_x.shape[0], query_x.shape[1], self.n_points
+        S = self.n_way * self.k_shot
+        feat = self.getFeatures_pm(query_x.reshape(G * n_q, self.in_channels, N), group=S + n_q)
+        Z = ops.protonet_similarity(feat, fitted.protos, self.n_way, self.dist_method, G, n_q * N)
+        labels = query_y.reshape(G, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
+        return ops.logits_ce_from_rows(Z, G, n_q, N, self.n_way + 1, labels)
+
+    def predict(self, fitted, query_x, query_y=None, lp_iters=None):
+        """Segment query clouds against a fitted support set: query_x (n_q, C, N) -> (logits (n_q, n_way + 1, N), loss), or
+        (G, n_q, C, N) -> (logits (G, n_q, n_way + 1, N), loss (G,)); any n_q >= 1; loss is None without query_y.  Per group
+        the bits of forward() on the episode [that support set | that group].  ValueError, before any launch, for a shape
+        that does not match the fit or a fit whose weights have changed since (fitted.py)."""
+        from . import fitted as F
+        _, _, grouped = F.check_predict_args(self, fitted, query_x, query_y)
+        if fitted.protos is None:
+            raise ValueError("predict: the fit holds no prototype table (it was fitted by %s)" % fitted.model_class)
+        qx = query_x if grouped else query_x[None]
+        qy = query_y if (grouped or query_y is None) else query_y[None]
+        logits, loss, _ = self._predict_groups(fitted, qx, qy, lp_iters)
+        if not grouped:
+            logits, loss = logits[0], loss[0]
+        return logits, (loss if query_y is not None else None)
+
 
 class ProtoNet_Contrast(ProtoNet):
     """The reference's noise-robust baseline at test time: ProtoNet whose foreground prototypes average the shots the

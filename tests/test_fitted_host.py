@@ -1,0 +1,111 @@
+"""Host side of a fitted support set (r3dfsseg_amd/fitted.py): the header declares the new entry points and the binding
+parses them; the stale-fit key sees a changed parameter and a changed running statistic on CPU modules; fit_support /
+predict refuse bad arguments before anything needs a device."""
+import re
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+from r3dfsseg_amd import _lib, fitted as F, synthetic as S
+from r3dfsseg_amd.mpti import MPTI_SelfAtten
+from r3dfsseg_amd.protonet import ProtoNet, ProtoNet_Contrast
+
+NEW = {"r3d_protonet_prototypes_batched": 14, "r3d_protonet_similarity_batched": 13, "r3d_head_attach_queries_batched": 23}
+
+
+def test_header_declares_the_new_entry_points_and_the_binding_parses_them():
+    txt = open(_lib.HEADER_PATH).read()
+    for name, n_args in NEW.items():
+        assert re.search(r"\bint\s+%s\s*\(" % name, txt), name
+        assert name in _lib.header_symbols()
+        res, args = _lib._SIGS[name]
+        assert res is _lib.c_i and len(args) == n_args, (name, len(args))
+        assert args[-1] is _lib.c_f  # the stream
+    sim = _lib._SIGS["r3d_protonet_similarity_batched"][1]
+    assert sim[3] is _lib.c_l and sim[6] is _lib.c_l and sim[10] is _lib.c_fl  # q_sys_rows, proto_stride, scaler
+    att = _lib._SIGS["r3d_head_attach_queries_batched"][1]
+    assert att[2] is _lib.c_l and att[4] is _lib.c_l and att[7] is _lib.c_i and att[16] is _lib.c_i  # pitches long, caps int
+    assert _lib.ABI_VERSION == 5 and re.search(r"int r3d_abi_version\(void\); /\* 5:", txt)
+
+
+def _cpu_model(cls=ProtoNet, **over):
+    cfg = S.make_cfg(n_way=2, k_shot=1, pc_npts=64, **over)
+    m = cls(SimpleNamespace(**cfg))
+    sd = S.make_state_dict(cfg, 123)
+    m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
+    return m.eval(), cfg
+
+
+def _fit_of(m):
+    return F.FittedSupport(m, protos=torch.zeros(1, m.n_way + 1, m.feat_dim))
+
+
+def test_stale_key_sees_parameters_and_running_statistics():
+    m, _ = _cpu_model()
+    f = _fit_of(m)
+    assert f.is_stale(m) is None and f.is_stale(m) is None
+    p = next(m.parameters())
+    with torch.no_grad():
+        p.add_(1e-3)                      # what an optimizer step does: the version counter moves
+    assert "version" in f.is_stale(m)
+    f = _fit_of(m)
+    p.data.add_(1e-3)                     # through .data: the counter of p does not move, the contents do
+    assert p._version == f.key[0][0] and "content" in f.is_stale(m)
+    f = _fit_of(m)
+    bn = [b for n, b in m.named_buffers() if n.endswith("running_mean")][0]
+    bn.mul_(1.5)                          # a running statistic
+    assert f.is_stale(m) is not None
+    f = _fit_of(m)
+    bn.data.add_(0.25)
+    assert "content" in f.is_stale(m)
+    f = _fit_of(m)
+    m.load_state_dict(m.state_dict())     # same values written again: the counters move, a refit is asked for
+    assert f.is_stale(m) is not None
+    other, _ = _cpu_model()
+    assert "another model" in _fit_of(other).is_stale(m)
+
+
+@pytest.mark.parametrize("cls", [ProtoNet, ProtoNet_Contrast, MPTI_SelfAtten])
+def test_argument_errors_come_before_any_device_work(cls):
+    m, cfg = _cpu_model(cls)
+    (sx, sy, qx, qy), _ = S.make_episode(cfg, seed=1)[0][:4], None
+    with pytest.raises(ValueError, match="support_x"):
+        m.fit_support(sx[..., :-1], sy)
+    with pytest.raises(ValueError, match="support_x"):
+        m.fit_support(sx[0], sy)
+    with pytest.raises(ValueError, match="support_y"):
+        m.fit_support(sx, sy[..., :-1])
+    f = _fit_of(m)
+    with pytest.raises(ValueError, match="fit_support returned"):
+        m.predict(None, qx)
+    with pytest.raises(ValueError, match="do not match the fit"):
+        m.predict(f, qx[..., :-1])        # wrong N
+    with pytest.raises(ValueError, match="do not match the fit"):
+        m.predict(f, qx[:, :-1])          # wrong C
+    with pytest.raises(ValueError, match="query_x must be"):
+        m.predict(f, qx[0])
+    with pytest.raises(ValueError, match="query_y"):
+        m.predict(f, qx, qy[:1])
+    next(m.parameters()).data.add_(1e-3)
+    with pytest.raises(ValueError, match="stale fit"):
+        m.predict(f, qx, qy)
+    m.train()
+    with pytest.raises(NotImplementedError):
+        m.fit_support(sx, sy)
+    with pytest.raises(NotImplementedError):
+        m.predict(_fit_of(m), qx)
+
+
+def test_learner_fit_takes_an_episode_list_or_a_pair():
+    a, b = torch.zeros(1), torch.ones(1)
+    assert F.support_pair([a, b, 3, 4]) == (a, b) and F.support_pair((a, b)) == (a, b)
+    with pytest.raises(ValueError):
+        F.support_pair([a])
+    from r3dfsseg_amd.mpti_learner import MPTILearner_V3
+    from r3dfsseg_amd.proto_contrast_learner import ProtoContrastLearner
+    from r3dfsseg_amd.proto_learner import ProtoLearner
+    for L in (MPTILearner_V3, ProtoLearner, ProtoContrastLearner):
+        assert callable(L.fit) and callable(L.predict) and L.fitted is None
+    with pytest.raises(ValueError, match="call fit"):
+        F.FittedLearner().predict(torch.zeros(1, 9, 8))
