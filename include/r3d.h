@@ -490,6 +490,54 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
                        unsigned seed, const unsigned* seed_dev, unsigned first_key, const float* mats, const float* noise,
                        float* mats_out, void* stream);
 
+/* ---- Labelling a whole scan against a fitted support set (no reference counterpart: the reference scores clouds its
+ * loader cut on the host, dataloaders/loader.py:100-119; definition in INTEGRATION.md, "Labelling a scan") ----
+ * scan: M rows of ld floats, x y z first (r g b behind them when ld >= 6); M <= 2^27.  A point is VALID when x, y and z
+ * are finite.  Nothing here draws a random number or sums floats in an order that depends on scheduling.
+ *
+ *   entry point          what it does                                                         host reads afterwards
+ *   r3d_scene_bounds     rec[0..3] = min x, min y, max x, max y over the valid points (fp32),  rec (read 1 of 2)
+ *                        rec[4] = their count (int32 bits); ws: r3d_scene_bounds_ws_words(M)
+ *   r3d_scene_plan       cell keys cy * ncx + cx with cx = (int)floorf((x - x0) / s) (IEEE         the plan record
+ *                        subtraction and division); stable 8-bit LSD radix sort of the valid points (read 2 of 2)
+ *                        by key (per-tile digit counts, one scan, in-tile ranking in index order);
+ *                        cell offsets; points per block; chunks per block (ceil(n / N), 0 below
+ *                        min_points) and their exclusive scan; the chunk table; the plan record
+ *                        {n_chunks, kept blocks, valid points with a vote, blocks}
+ *   r3d_scene_prepare    chunks first_chunk .. first_chunk + G - 1 as prepared clouds of N slots  -
+ *                        (slot t = member t mod len of the chunk): xyz - min over the slots,
+ *                        rgb / 255.0f at rgb_ch (3 or -1), xyz' / max xyz' at XYZ_ch (behind them, or
+ *                        -1; an axis of zero extent gives 0), written at out[g * o_sb + c * o_sc +
+ *                        t * o_sn] (the strides of r3d_augment_clouds); slot_map (G, N) int32,
+ *                        optional: the scan index of every slot.  Chunks past the plan's n_chunks
+ *                        are left unwritten.
+ *   r3d_scene_vote       per scan point the fp32 sum of logits[chunk][class][slot] over its          -
+ *                        appearances, block id ascending then slot ascending, one at a time;
+ *                        labels = arg-max (lowest class on ties, -1 without a vote), votes = the
+ *                        appearance count.  logits: (n_chunks, n_classes, N), chunk order.  The
+ *                        appearances are computed from the point's cell, its rank in the cell list
+ *                        and the block's cell offsets: no inverted index in memory, no atomics.
+ *
+ * Blocks: r x r cells (1 <= r <= 4), block (bx, by) covers cells bx .. min(bx + r, ncx) - 1 by by .. min(by + r, ncy) - 1,
+ * nbx = max(ncx - r + 1, 1); its point list is its cells' lists by (cy, cx), never materialised.  ncx * ncy <= 65536.
+ * ws: ONE int32 scratch of r3d_scene_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range) shared by plan,
+ * prepare and vote, which must be called with the same (M, ncx, ncy, r, N, chunk_cap); chunk_cap bounds the chunk table
+ * (r * r * n_valid / N + blocks is always enough).  r3d_scene_ws_offsets fills 8 HOST words (the one host pointer of this
+ * header) with the word offsets of {sorted scan indices, sorted keys, sorted position of a scan point, cell offsets
+ * (ncx * ncy + 2), points per block, first chunk of a block (blocks + 1), block of a chunk, plan record (8)}. */
+long r3d_scene_bounds_ws_words(long M);
+int r3d_scene_bounds(const float* scan, int ld, long M, float* rec /* 8 words */, float* ws, long ws_words, void* stream);
+long r3d_scene_ws_words(long M, int ncx, int ncy, long chunk_cap);
+int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out);
+int r3d_scene_plan(const float* scan, int ld, long M, float x0, float y0, float s, int ncx, int ncy, int r, int N,
+                   int min_points, long chunk_cap, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
+                      long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc,
+                      long o_sn, int32_t* slot_map, void* stream);
+int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                   const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

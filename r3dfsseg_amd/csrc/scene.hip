@@ -1,0 +1,661 @@
+// Labelling a whole scan against a fitted support set: the device side of scene.py (definition: INTEGRATION.md,
+// "Labelling a scan").  The reference only scores clouds that were cut out of a room, sampled, min-shifted and given
+// their channels on the host (dataloaders/loader.py:100-119); these kernels do that cutting on the device, without a
+// random number, and sum the per-chunk logits back onto the scan points:
+//   bounds   valid points, their xy extent                               -> an 8-word record the host reads (read 1)
+//   plan     cell keys, stable radix sort by key, cell offsets, block sizes, chunk offsets, chunk table
+//                                                                        -> a record the host reads (read 2)
+//   prepare  the G chunks of one predict launch as prepared clouds, gathered straight from the scan
+//   vote     per scan point the sum of its chunk logits (closed-form inverted index: no atomics, a fixed order)
+// All of it is bandwidth-bound integer and min / max work; the only floating-point sums are the vote's, one running
+// sum per (point, class) in a fixed order.
+#include "common.h"
+
+#define SC_THREADS 256
+#define SC_TILE 2048                 // points per sort tile, elements per scan block (8 per thread)
+#define SC_PER_THREAD (SC_TILE / SC_THREADS)
+#define SC_BOUNDS_BLOCKS 1024
+#define SC_MAX_CELLS 65536
+#define SC_MAX_POINTS (1L << 27)
+#define SC_PLAN_THREADS 1024
+
+// record of r3d_scene_bounds (floats, n_valid as int bits)
+#define SC_B_X0 0
+#define SC_B_Y0 1
+#define SC_B_XMAX 2
+#define SC_B_YMAX 3
+#define SC_B_NVALID 4
+// record of r3d_scene_plan (ints)
+#define SC_P_NCHUNKS 0
+#define SC_P_NBLOCKS 1
+#define SC_P_NVOTED 2
+
+// ------------------------------------------------------------------------------------------------ workspace layout
+struct sc_layout {
+  long key[2], idx[2];  // ping-pong (key, scan index) pairs of the sort, M words each
+  long pos;             // M: sorted position of every scan point
+  long hist;            // 256 * n_tiles digit counts, [digit][tile], scanned in place
+  long part;            // one partial per SC_TILE words of hist
+  long cell;            // n_cells + 2 cell offsets into the sorted order (cell n_cells: the invalid points)
+  long blk_n;           // n_cells: points of a block (n_blocks <= n_cells)
+  long chunk0;          // n_cells + 1: first chunk of a block (exclusive scan of the chunk counts)
+  long chunk_blk;       // chunk_cap: block of a chunk
+  long rec;             // 8
+  long total;
+  int n_tiles, n_part, passes, sorted;  // sorted: which of the two pairs holds the result
+};
+
+static long sc_align(long w) { return (w + 3) & ~3L; }  // 16-byte aligned arrays
+
+static sc_layout sc_make_layout(long M, long n_cells, long chunk_cap) {
+  sc_layout L;
+  long o = 0;
+  const long Ma = sc_align(M);
+  L.n_tiles = (int)((M + SC_TILE - 1) / SC_TILE);
+  const long n_hist = 256L * L.n_tiles;
+  L.n_part = (int)((n_hist + SC_TILE - 1) / SC_TILE);
+  L.passes = n_cells < 256 ? 1 : (n_cells < 65536 ? 2 : 3);  // keys run 0 .. n_cells (n_cells: invalid point)
+  L.sorted = L.passes & 1;
+  L.key[0] = o; o += Ma;
+  L.key[1] = o; o += Ma;
+  L.idx[0] = o; o += Ma;
+  L.idx[1] = o; o += Ma;
+  L.pos = o; o += Ma;
+  L.hist = o; o += sc_align(n_hist);
+  L.part = o; o += sc_align(L.n_part);
+  L.cell = o; o += sc_align(n_cells + 2);
+  L.blk_n = o; o += sc_align(n_cells);
+  L.chunk0 = o; o += sc_align(n_cells + 1);
+  L.chunk_blk = o; o += sc_align(chunk_cap);
+  L.rec = o; o += 8;
+  L.total = o;
+  return L;
+}
+
+static bool sc_shape_ok(long M, int ncx, int ncy, int r, long chunk_cap) {
+  return M > 0 && M <= SC_MAX_POINTS && ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS && r >= 1 && r <= 4 &&
+         chunk_cap >= 0 && chunk_cap < (1L << 30);
+}
+
+// ------------------------------------------------------------------------------------------------ bounds
+static __device__ __forceinline__ bool sc_finite3(float x, float y, float z) {
+  return isfinite(x) && isfinite(y) && isfinite(z);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_bounds_part_kernel(const float* __restrict__ scan, int ld, int M,
+                                                                           float* __restrict__ part) {
+  __shared__ float red[5][SC_THREADS / R3D_WAVE];
+  float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+  int n = 0;
+  for (int i = blockIdx.x * SC_THREADS + threadIdx.x; i < M; i += gridDim.x * SC_THREADS) {
+    const float* p = scan + (long)i * ld;
+    const float x = p[0], y = p[1], z = p[2];
+    if (sc_finite3(x, y, z)) {
+      x0 = fminf(x0, x); y0 = fminf(y0, y);
+      x1 = fmaxf(x1, x); y1 = fmaxf(y1, y);
+      ++n;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    x0 = fminf(x0, __shfl_xor(x0, o)); y0 = fminf(y0, __shfl_xor(y0, o));
+    x1 = fmaxf(x1, __shfl_xor(x1, o)); y1 = fmaxf(y1, __shfl_xor(y1, o));
+    n += __shfl_xor(n, o);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[0][w] = x0; red[1][w] = y0; red[2][w] = x1; red[3][w] = y1; red[4][w] = __int_as_float(n);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < SC_THREADS / R3D_WAVE; ++k) {
+      x0 = fminf(x0, red[0][k]); y0 = fminf(y0, red[1][k]);
+      x1 = fmaxf(x1, red[2][k]); y1 = fmaxf(y1, red[3][k]);
+      n += __float_as_int(red[4][k]);
+    }
+    float* o = part + 5L * blockIdx.x;
+    o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1; o[4] = __int_as_float(n);
+  }
+}
+
+__global__ __launch_bounds__(R3D_WAVE) void r3d_scene_bounds_final_kernel(const float* __restrict__ part, int n_part,
+                                                                          float* __restrict__ rec) {
+  float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+  int n = 0;
+  for (int i = threadIdx.x; i < n_part; i += R3D_WAVE) {
+    const float* p = part + 5L * i;
+    x0 = fminf(x0, p[0]); y0 = fminf(y0, p[1]);
+    x1 = fmaxf(x1, p[2]); y1 = fmaxf(y1, p[3]);
+    n += __float_as_int(p[4]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    x0 = fminf(x0, __shfl_xor(x0, o)); y0 = fminf(y0, __shfl_xor(y0, o));
+    x1 = fmaxf(x1, __shfl_xor(x1, o)); y1 = fmaxf(y1, __shfl_xor(y1, o));
+    n += __shfl_xor(n, o);
+  }
+  if (threadIdx.x == 0) {
+    rec[SC_B_X0] = x0; rec[SC_B_Y0] = y0; rec[SC_B_XMAX] = x1; rec[SC_B_YMAX] = y1;
+    rec[SC_B_NVALID] = __int_as_float(n);
+    rec[5] = 0.0f; rec[6] = 0.0f; rec[7] = 0.0f;
+  }
+}
+
+static int sc_bounds_blocks(long M) {
+  const long b = (M + SC_THREADS - 1) / SC_THREADS;
+  return (int)(b < SC_BOUNDS_BLOCKS ? b : SC_BOUNDS_BLOCKS);
+}
+
+extern "C" long r3d_scene_bounds_ws_words(long M) { return M > 0 ? 5L * sc_bounds_blocks(M) : 0; }
+
+extern "C" int r3d_scene_bounds(const float* scan, int ld, long M, float* rec, float* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(scan && rec && ws, "r3d_scene_bounds: null pointer (scan %p, rec %p, ws %p)", (const void*)scan, (void*)rec,
+              (void*)ws);
+  R3D_REQUIRE(M > 0 && M <= SC_MAX_POINTS, "r3d_scene_bounds: M %ld (1 .. 2^27 points)", M);
+  R3D_REQUIRE(ld >= 3 && ld <= 64, "r3d_scene_bounds: ld %d (a scan row holds x y z first: 3 .. 64 floats)", ld);
+  R3D_REQUIRE(ws_words >= r3d_scene_bounds_ws_words(M), "r3d_scene_bounds: workspace of %ld words, %ld needed", ws_words,
+              r3d_scene_bounds_ws_words(M));
+  const int nb = sc_bounds_blocks(M);
+  hipLaunchKernelGGL(r3d_scene_bounds_part_kernel, dim3(nb), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M, ws);
+  hipLaunchKernelGGL(r3d_scene_bounds_final_kernel, dim3(1), dim3(R3D_WAVE), 0, (hipStream_t)stream, ws, nb, rec);
+  R3D_LAUNCH_CHECK("r3d_scene_bounds");
+  return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ cell keys
+// (int)floorf((v - v0) / s): an IEEE subtraction and an IEEE division (the build neither contracts nor uses a
+// reciprocal).  The clamp never acts on a valid point when the host derived n from the same arithmetic (the
+// expression is monotone in v); it keeps a key inside the cell table whatever the caller passed.
+static __device__ __forceinline__ int sc_cell(float v, float v0, float s, int n) {
+  const int c = (int)floorf((v - v0) / s);
+  return c < 0 ? 0 : (c >= n ? n - 1 : c);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_keys_kernel(const float* __restrict__ scan, int ld, int M, float x0,
+                                                                    float y0, float s, int ncx, int ncy,
+                                                                    int* __restrict__ key, int* __restrict__ idx) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const float* p = scan + (long)i * ld;
+  const float x = p[0], y = p[1], z = p[2];
+  int k = ncx * ncy;  // invalid points sort behind every cell
+  if (sc_finite3(x, y, z)) k = sc_cell(y, y0, s, ncy) * ncx + sc_cell(x, x0, s, ncx);
+  key[i] = k;
+  idx[i] = i;
+}
+
+// ------------------------------------------------------------------------------------------------ radix sort
+// LSD passes of 8 bits over (key, scan index) pairs.  Pass: per-tile digit counts [digit][tile]; one exclusive scan
+// over that table gives every (digit, tile) its first output position; the scatter ranks the elements of a tile
+// with the same digit in index order, which keeps the sort stable.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_hist_kernel(const int* __restrict__ key, int M, int shift, int n_tiles,
+                                                                    int* __restrict__ hist) {
+  __shared__ int cnt[256];
+  const int t = blockIdx.x;
+  cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int base = t * SC_TILE;
+#pragma unroll
+  for (int k = 0; k < SC_PER_THREAD; ++k) {
+    const int i = base + k * SC_THREADS + threadIdx.x;
+    if (i < M) atomicAdd(&cnt[(key[i] >> shift) & 255], 1);  // integer counts in LDS: order-independent
+  }
+  __syncthreads();
+  hist[(long)threadIdx.x * n_tiles + t] = cnt[threadIdx.x];
+}
+
+// exclusive scan of the calling workgroup's value per thread; every thread also gets the workgroup's total
+template <int THREADS>
+static __device__ __forceinline__ int sc_block_excl_scan(int v, int* wsum /* THREADS / 64 + 1 LDS ints */, int& total) {
+  const int incl = r3d_wave_incl_scan(v);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[w] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < THREADS / R3D_WAVE; ++k) {
+    const int s = wsum[k];
+    if (k < w) off += s;
+    tot += s;
+  }
+  __syncthreads();  // wsum may be written again by the caller's next round
+  total = tot;
+  return off + incl - v;
+}
+
+// in-place exclusive scan of a[0 .. n) in three launches: sums of SC_TILE-word blocks, scan of the sums, local scans
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_scan_sum_kernel(const int* __restrict__ a, long n,
+                                                                        int* __restrict__ part) {
+  __shared__ int wsum[SC_THREADS / R3D_WAVE];
+  const long base = (long)blockIdx.x * SC_TILE + (long)threadIdx.x * SC_PER_THREAD;
+  int v = 0;
+#pragma unroll
+  for (int k = 0; k < SC_PER_THREAD; ++k)
+    if (base + k < n) v += a[base + k];
+  int total;
+  sc_block_excl_scan<SC_THREADS>(v, wsum, total);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_scan_part_kernel(int* __restrict__ part, int n) {
+  __shared__ int wsum[SC_PLAN_THREADS / R3D_WAVE];
+  int carry = 0;
+  for (int b = 0; b < n; b += SC_PLAN_THREADS) {
+    const int i = b + threadIdx.x;
+    const int v = i < n ? part[i] : 0;
+    int total;
+    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(v, wsum, total);
+    if (i < n) part[i] = carry + ex;
+    carry += total;
+  }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_scan_local_kernel(int* __restrict__ a, long n,
+                                                                          const int* __restrict__ part) {
+  __shared__ int wsum[SC_THREADS / R3D_WAVE];
+  const long base = (long)blockIdx.x * SC_TILE + (long)threadIdx.x * SC_PER_THREAD;
+  int e[SC_PER_THREAD];
+  int v = 0;
+#pragma unroll
+  for (int k = 0; k < SC_PER_THREAD; ++k) {
+    e[k] = base + k < n ? a[base + k] : 0;
+    v += e[k];
+  }
+  int total;
+  int run = part[blockIdx.x] + sc_block_excl_scan<SC_THREADS>(v, wsum, total);
+#pragma unroll
+  for (int k = 0; k < SC_PER_THREAD; ++k) {
+    if (base + k < n) a[base + k] = run;
+    run += e[k];
+  }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_scatter_kernel(const int* __restrict__ key_in,
+                                                                       const int* __restrict__ idx_in, int M, int shift,
+                                                                       int n_tiles, const int* __restrict__ offs,
+                                                                       int* __restrict__ key_out, int* __restrict__ idx_out) {
+  __shared__ int base[256];                           // next output position of a digit in this tile
+  __shared__ int wcnt[SC_THREADS / R3D_WAVE][256];    // elements of a digit per wave in the current round
+  const int t = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  base[tid] = offs[(long)tid * n_tiles + t];
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  for (int k = 0; k < SC_PER_THREAD; ++k) {
+    for (int j = tid; j < (SC_THREADS / R3D_WAVE) * 256; j += SC_THREADS) (&wcnt[0][0])[j] = 0;
+    __syncthreads();
+    const int i = t * SC_TILE + k * SC_THREADS + tid;
+    const bool live = i < M;
+    const int ky = live ? key_in[i] : 0, id = live ? idx_in[i] : 0;
+    const int d = (ky >> shift) & 255;
+    // lanes of this wave with the same digit
+    unsigned long long peers = __ballot(live);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1;
+      const unsigned long long m = __ballot(bit);
+      peers &= bit ? m : ~m;
+    }
+    const int rank = __popcll(peers & below);
+    if (live && rank == 0) wcnt[w][d] = __popcll(peers);  // one writer per (wave, digit)
+    __syncthreads();
+    if (live) {
+      int o = base[d] + rank;
+      for (int q = 0; q < w; ++q) o += wcnt[q][d];
+      // offsets come from counts of these very keys, so o < M; the guard only matters for a corrupted table
+      if (o >= 0 && o < M) {
+        key_out[o] = ky;
+        idx_out[o] = id;
+      }
+    }
+    __syncthreads();
+    int add = 0;
+#pragma unroll
+    for (int q = 0; q < SC_THREADS / R3D_WAVE; ++q) add += wcnt[q][tid];
+    base[tid] += add;
+    __syncthreads();
+  }
+}
+
+// cell offsets from the sorted keys (every cell written by exactly one thread, empty cells included) and the sorted
+// position of every scan point
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_cells_kernel(const int* __restrict__ skey, const int* __restrict__ order,
+                                                                     int M, int n_cells, int* __restrict__ cell,
+                                                                     int* __restrict__ pos) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= M) return;
+  int k = skey[i];
+  k = k < 0 ? 0 : (k > n_cells ? n_cells : k);
+  const int kp = i > 0 ? skey[i - 1] : -1;
+  for (int c = (kp < -1 ? -1 : kp) + 1; c <= k; ++c) cell[c] = i;
+  if (i == M - 1)
+    for (int c = k + 1; c <= n_cells + 1; ++c) cell[c] = M;
+  const int p = order[i];
+  if (p >= 0 && p < M) pos[p] = i;
+}
+
+// ------------------------------------------------------------------------------------------------ blocks and chunks
+struct sc_grid {
+  int ncx, ncy, r, nbx, nby, M;
+};
+
+// points of block (bx, by) in front of row `row` of its cells (row = rows of the block: all of them), and the
+// sorted position at which that row's run of cells starts
+static __device__ __forceinline__ int sc_row_start(const int* __restrict__ cell, const sc_grid& g, int bx, int cy) {
+  return cell[cy * g.ncx + bx];
+}
+static __device__ __forceinline__ int sc_row_end(const int* __restrict__ cell, const sc_grid& g, int bx, int cy) {
+  const int ex = bx + g.r < g.ncx ? bx + g.r : g.ncx;
+  return cell[cy * g.ncx + ex];
+}
+static __device__ __forceinline__ int sc_block_rows(const sc_grid& g, int by) {
+  return (by + g.r < g.ncy ? by + g.r : g.ncy) - by;
+}
+
+// one workgroup: block sizes, chunk counts and their exclusive scan; kept blocks; valid points with a vote
+__global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_blocks_kernel(const int* __restrict__ cell, sc_grid g, int N,
+                                                                           int min_points, int* __restrict__ blk_n,
+                                                                           int* __restrict__ chunk0, int* __restrict__ rec) {
+  __shared__ int wsum[SC_PLAN_THREADS / R3D_WAVE];
+  __shared__ int kept, voted;
+  if (threadIdx.x == 0) kept = voted = 0;
+  __syncthreads();
+  const int nb = g.nbx * g.nby;
+  int carry = 0;
+  for (int b0 = 0; b0 < nb; b0 += SC_PLAN_THREADS) {
+    const int b = b0 + threadIdx.x;
+    int n = 0, nc = 0;
+    if (b < nb) {
+      const int bx = b % g.nbx, by = b / g.nbx, rows = sc_block_rows(g, by);
+      for (int k = 0; k < rows; ++k) n += sc_row_end(cell, g, bx, by + k) - sc_row_start(cell, g, bx, by + k);
+      if (n >= min_points) nc = (n + N - 1) / N;
+      blk_n[b] = n;
+      if (nc > 0) atomicAdd(&kept, 1);
+    }
+    int total;
+    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(nc, wsum, total);
+    if (b < nb) chunk0[b] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) chunk0[nb] = carry;
+  __syncthreads();  // chunk0 of every block is visible to the workgroup
+  const int n_cells = g.ncx * g.ncy;
+  for (int c = threadIdx.x; c < n_cells; c += SC_PLAN_THREADS) {
+    const int cx = c % g.ncx, cy = c / g.ncx;
+    bool any = false;
+    for (int by = cy - g.r + 1 > 0 ? cy - g.r + 1 : 0; by <= cy && by < g.nby; ++by)
+      for (int bx = cx - g.r + 1 > 0 ? cx - g.r + 1 : 0; bx <= cx && bx < g.nbx; ++bx) {
+        const int b = by * g.nbx + bx;
+        any = any || chunk0[b + 1] > chunk0[b];
+      }
+    if (any) atomicAdd(&voted, cell[c + 1] - cell[c]);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    rec[SC_P_NCHUNKS] = carry;
+    rec[SC_P_NBLOCKS] = kept;
+    rec[SC_P_NVOTED] = voted;
+    rec[3] = nb;
+    rec[4] = rec[5] = rec[6] = rec[7] = 0;
+  }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_chunk_table_kernel(const int* __restrict__ chunk0, int nb, int chunk_cap,
+                                                                           int* __restrict__ chunk_blk) {
+  const int b = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (b >= nb) return;
+  const int c0 = chunk0[b], c1 = chunk0[b + 1];
+  for (int c = c0; c < c1 && c < chunk_cap; ++c) chunk_blk[c] = b;
+}
+
+extern "C" long r3d_scene_ws_words(long M, int ncx, int ncy, long chunk_cap) {
+  if (!sc_shape_ok(M, ncx, ncy, 1, chunk_cap)) return -1;
+  return sc_make_layout(M, (long)ncx * ncy, chunk_cap).total;
+}
+
+extern "C" int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out /* 8 HOST words */) {
+  R3D_REQUIRE(out, "r3d_scene_ws_offsets: null pointer");
+  R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap), "r3d_scene_ws_offsets: M %ld, cells %d x %d, chunk_cap %ld out of range", M,
+              ncx, ncy, chunk_cap);
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  out[0] = L.idx[L.sorted]; out[1] = L.key[L.sorted]; out[2] = L.pos; out[3] = L.cell;
+  out[4] = L.blk_n; out[5] = L.chunk0; out[6] = L.chunk_blk; out[7] = L.rec;
+  return R3D_OK;
+}
+
+#define SC_REQUIRE_PLAN_ARGS(name)                                                                                        \
+  R3D_REQUIRE(M > 0 && M <= SC_MAX_POINTS, name ": M %ld (1 .. 2^27 points)", M);                                         \
+  R3D_REQUIRE(ld >= 3 && ld <= 64, name ": ld %d (a scan row holds x y z first: 3 .. 64 floats)", ld);                    \
+  R3D_REQUIRE(ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS, name ": %d x %d cells (1 .. 65536)", ncx, ncy);      \
+  R3D_REQUIRE(r >= 1 && r <= 4, name ": r %d (block_size / stride is 1 .. 4)", r);                                        \
+  R3D_REQUIRE(N > 0 && N <= (1 << 20), name ": N %d points per cloud", N);                                                \
+  R3D_REQUIRE(chunk_cap > 0 && chunk_cap < (1L << 30), name ": chunk_cap %ld", chunk_cap);                                \
+  R3D_REQUIRE(ws_words >= r3d_scene_ws_words(M, ncx, ncy, chunk_cap), name ": workspace of %ld words, %ld needed",        \
+              ws_words, r3d_scene_ws_words(M, ncx, ncy, chunk_cap))
+
+static sc_grid sc_make_grid(int ncx, int ncy, int r, long M) {
+  sc_grid g;
+  g.ncx = ncx; g.ncy = ncy; g.r = r; g.M = (int)M;
+  g.nbx = ncx - r + 1 > 1 ? ncx - r + 1 : 1;
+  g.nby = ncy - r + 1 > 1 ? ncy - r + 1 : 1;
+  return g;
+}
+
+extern "C" int r3d_scene_plan(const float* scan, int ld, long M, float x0, float y0, float s, int ncx, int ncy, int r, int N,
+                              int min_points, long chunk_cap, int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(scan && ws, "r3d_scene_plan: null pointer (scan %p, ws %p)", (const void*)scan, (void*)ws);
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_plan");
+  R3D_REQUIRE(min_points >= 1, "r3d_scene_plan: min_points %d (at least 1)", min_points);
+  R3D_REQUIRE(x0 == x0 && y0 == y0 && s > 0.0f && s < INFINITY, "r3d_scene_plan: origin (%g, %g), cell size %g", (double)x0,
+              (double)y0, (double)s);
+  const hipStream_t st = (hipStream_t)stream;
+  const int n_cells = ncx * ncy;
+  const sc_layout L = sc_make_layout(M, n_cells, chunk_cap);
+  const int gm = (int)((M + SC_THREADS - 1) / SC_THREADS);
+  hipLaunchKernelGGL(r3d_scene_keys_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, x0, y0, s, ncx, ncy,
+                     ws + L.key[0], ws + L.idx[0]);
+  const long n_hist = 256L * L.n_tiles;
+  for (int p = 0; p < L.passes; ++p) {
+    const int a = p & 1, b = a ^ 1;
+    hipLaunchKernelGGL(r3d_scene_hist_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], (int)M, 8 * p, L.n_tiles,
+                       ws + L.hist);
+    hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
+    hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.part, L.n_part);
+    hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
+    hipLaunchKernelGGL(r3d_scene_scatter_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], ws + L.idx[a], (int)M,
+                       8 * p, L.n_tiles, ws + L.hist, ws + L.key[b], ws + L.idx[b]);
+  }
+  hipLaunchKernelGGL(r3d_scene_cells_kernel, dim3(gm), dim3(SC_THREADS), 0, st, ws + L.key[L.sorted], ws + L.idx[L.sorted], (int)M,
+                     n_cells, ws + L.cell, ws + L.pos);
+  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
+  const int nb = g.nbx * g.nby;
+  hipLaunchKernelGGL(r3d_scene_blocks_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.cell, g, N, min_points, ws + L.blk_n,
+                     ws + L.chunk0, ws + L.rec);
+  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st,
+                     ws + L.chunk0, nb, (int)chunk_cap, ws + L.chunk_blk);
+  R3D_LAUNCH_CHECK("r3d_scene_plan");
+  return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ prepared clouds
+// what a chunk is: block b with n points, chunk j of nc; its members are list positions j, j + nc, ...
+struct sc_chunk {
+  int bx, by, n, nc, j, len;
+};
+
+// list position q of block (bx, by) -> sorted position (the block's list is its rows of cells, one run each)
+static __device__ __forceinline__ int sc_list_to_sorted(const int* __restrict__ cell, const sc_grid& g, int bx, int by, int q) {
+  const int rows = sc_block_rows(g, by);
+  int s = 0;
+  for (int k = 0; k < rows; ++k) {
+    const int a = sc_row_start(cell, g, bx, by + k), e = sc_row_end(cell, g, bx, by + k);
+    if (q < e - a || k == rows - 1) {
+      s = a + q;
+      break;
+    }
+    q -= e - a;
+  }
+  return s < 0 ? 0 : (s >= g.M ? g.M - 1 : s);  // inside the sorted order whatever the tables hold
+}
+
+// one workgroup per chunk.  Pass 1: minima and maxima of xyz over the N slots; pass 2: gather again, write.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
+    const float* __restrict__ scan, int ld, int M, const int* __restrict__ order, const int* __restrict__ cell,
+    const int* __restrict__ blk_n, const int* __restrict__ chunk0, const int* __restrict__ chunk_blk,
+    const int* __restrict__ rec, sc_grid g, int first_chunk, int N, int C, int rgb_ch, int XYZ_ch, float* __restrict__ out,
+    long o_sb, long o_sc, long o_sn, int* __restrict__ slot_map) {
+  __shared__ float red[6][SC_THREADS / R3D_WAVE];
+  const int c = first_chunk + blockIdx.x, tid = threadIdx.x;
+  if (c >= rec[SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
+  const int b = chunk_blk[c];
+  if (b < 0 || b >= g.nbx * g.nby) return;
+  const int bx = b % g.nbx, by = b / g.nbx;
+  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = c - chunk0[b];
+  if (nc <= 0 || j < 0 || j >= nc || n <= j) return;
+  const int len = (n - j + nc - 1) / nc;
+  out += (long)blockIdx.x * o_sb;
+
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  const int members = len < N ? len : N;  // slots 0 .. members - 1 hold every member once
+  for (int t = tid; t < members; t += SC_THREADS) {
+    int p = order[sc_list_to_sorted(cell, g, bx, by, j + t * nc)];
+    p = p < 0 ? 0 : (p >= M ? M - 1 : p);
+    const float* q = scan + (long)p * ld;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      mn[a] = fminf(mn[a], q[a]);
+      mx[a] = fmaxf(mx[a], q[a]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
+      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
+    }
+    if ((tid & 63) == 0) {
+      red[a][tid >> 6] = mn[a];
+      red[3 + a][tid >> 6] = mx[a];
+    }
+  }
+  __syncthreads();
+  float lo[3], ext[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float u = red[a][0], v = red[3 + a][0];
+#pragma unroll
+    for (int w = 1; w < SC_THREADS / R3D_WAVE; ++w) {
+      u = fminf(u, red[a][w]);
+      v = fmaxf(v, red[3 + a][w]);
+    }
+    lo[a] = u;
+    ext[a] = v - u;  // == max over the slots of (xyz - min): the subtraction is monotone
+  }
+
+  for (int t = tid; t < N; t += SC_THREADS) {
+    int p = order[sc_list_to_sorted(cell, g, bx, by, j + (t % len) * nc)];
+    p = p < 0 ? 0 : (p >= M ? M - 1 : p);
+    const float* q = scan + (long)p * ld;
+    float* o = out + (long)t * o_sn;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float v = q[a] - lo[a];
+      o[a * o_sc] = v;
+      if (XYZ_ch >= 0) o[(XYZ_ch + a) * o_sc] = ext[a] > 0.0f ? v / ext[a] : 0.0f;  // flat axis: 0, not the reference's 0 / 0
+      if (rgb_ch >= 0) o[(rgb_ch + a) * o_sc] = q[3 + a] / 255.0f;
+    }
+    if (slot_map) slot_map[(long)blockIdx.x * N + t] = p;
+  }
+}
+
+extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
+                                 const int32_t* ws, long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch,
+                                 float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
+  R3D_REQUIRE(scan && ws && out, "r3d_scene_prepare: null pointer (scan %p, ws %p, out %p)", (const void*)scan, (const void*)ws,
+              (void*)out);
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_prepare");
+  R3D_REQUIRE(G > 0 && first_chunk >= 0 && (long)first_chunk + G <= chunk_cap,
+              "r3d_scene_prepare: chunks %d .. %d + %d outside the chunk table of %ld", first_chunk, first_chunk, G, chunk_cap);
+  R3D_REQUIRE(C == 3 || C == 6 || C == 9, "r3d_scene_prepare: C %d (3, 6 or 9 channels)", C);
+  R3D_REQUIRE(rgb_ch == -1 || rgb_ch == 3, "r3d_scene_prepare: rgb_ch %d (3, or -1: none)", rgb_ch);
+  R3D_REQUIRE(rgb_ch == -1 || ld >= 6, "r3d_scene_prepare: a scan row of %d floats has no colour", ld);
+  R3D_REQUIRE(XYZ_ch == -1 || XYZ_ch == (rgb_ch == 3 ? 6 : 3), "r3d_scene_prepare: XYZ_ch %d (behind xyz and rgb, or -1: none)",
+              XYZ_ch);
+  R3D_REQUIRE(C == 3 + (rgb_ch >= 0 ? 3 : 0) + (XYZ_ch >= 0 ? 3 : 0), "r3d_scene_prepare: C %d does not hold xyz%s%s", C,
+              rgb_ch >= 0 ? " rgb" : "", XYZ_ch >= 0 ? " XYZ" : "");
+  R3D_REQUIRE(o_sb >= 0 && o_sc > 0 && o_sn > 0, "r3d_scene_prepare: strides must be positive (out %ld %ld %ld)", o_sb, o_sc, o_sn);
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  hipLaunchKernelGGL(r3d_scene_prepare_kernel, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M,
+                     ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, ws + L.chunk_blk, ws + L.rec,
+                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map);
+  R3D_LAUNCH_CHECK("r3d_scene_prepare");
+  return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ votes
+// One thread per scan point.  Its appearances follow from its cell, its rank in the cell list and the block's row
+// offsets: list position q in block (bx, by) -> chunk q % nc, member q / nc, slots member, member + len, ... < N.
+// Blocks by ascending id (by, then bx), slots ascending, one running fp32 sum per class: a fixed order, no atomics.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
+    int M, const int* __restrict__ skey, const int* __restrict__ pos, const int* __restrict__ cell,
+    const int* __restrict__ blk_n, const int* __restrict__ chunk0, sc_grid g, int N, int K, const float* __restrict__ logits,
+    int n_chunks, float* __restrict__ scores, long long* __restrict__ labels, int* __restrict__ votes) {
+  const int p = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (p >= M) return;
+  const int n_cells = g.ncx * g.ncy;
+  const int sp = pos[p];
+  const int key = (sp >= 0 && sp < M) ? skey[sp] : n_cells;
+  int n_votes = 0, best = -1;
+  float best_v = 0.0f;
+  const bool valid = key >= 0 && key < n_cells;
+  const int cx = valid ? key % g.ncx : 0, cy = valid ? key / g.ncx : 0;
+  const int by0 = cy - g.r + 1 > 0 ? cy - g.r + 1 : 0, bx0 = cx - g.r + 1 > 0 ? cx - g.r + 1 : 0;
+  for (int k = 0; k < K; ++k) {
+    float acc = 0.0f;
+    int cnt = 0;
+    if (valid) {
+      for (int by = by0; by <= cy && by < g.nby; ++by)
+        for (int bx = bx0; bx <= cx && bx < g.nbx; ++bx) {
+          const int b = by * g.nbx + bx;
+          const int c0 = chunk0[b], nc = chunk0[b + 1] - c0;
+          if (nc <= 0) continue;  // dropped block
+          int q = sp - sc_row_start(cell, g, bx, cy);  // position inside its row of the block
+          for (int row = by; row < cy; ++row) q += sc_row_end(cell, g, bx, row) - sc_row_start(cell, g, bx, row);
+          const int n = blk_n[b], j = q % nc, m = q / nc;
+          const int len = (n - j + nc - 1) / nc;
+          const int ch = c0 + j;
+          if (q < 0 || q >= n || len <= 0 || ch >= n_chunks) continue;
+          const float* z = logits + ((long)ch * K + k) * N;
+          for (int t = m; t < N; t += len) {
+            acc += z[t];
+            ++cnt;
+          }
+        }
+    }
+    scores[(long)p * K + k] = acc;
+    if (k == 0) n_votes = cnt;
+    if (cnt > 0 && (best < 0 || acc > best_v)) {
+      best = k;
+      best_v = acc;
+    }
+  }
+  votes[p] = n_votes;
+  labels[p] = best;
+}
+
+extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                              const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
+                              void* stream) {
+  R3D_REQUIRE(ws && logits && scores && labels && votes,
+              "r3d_scene_vote: null pointer (ws %p, logits %p, scores %p, labels %p, votes %p)", (const void*)ws,
+              (const void*)logits, (void*)scores, (void*)labels, (void*)votes);
+  const int ld = 3;
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_vote");
+  R3D_REQUIRE(n_chunks > 0 && n_chunks <= chunk_cap, "r3d_scene_vote: n_chunks %d (1 .. chunk_cap %ld)", n_chunks, chunk_cap);
+  R3D_REQUIRE(n_classes >= 1 && n_classes <= 64, "r3d_scene_vote: n_classes %d (1 .. 64)", n_classes);
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  hipLaunchKernelGGL(r3d_scene_vote_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (int)M, ws + L.key[L.sorted], ws + L.pos, ws + L.cell, ws + L.blk_n, ws + L.chunk0,
+                     sc_make_grid(ncx, ncy, r, M), N, n_classes, logits, n_chunks, scores, (long long*)labels, votes);
+  R3D_LAUNCH_CHECK("r3d_scene_vote");
+  return R3D_OK;
+}

@@ -296,6 +296,8 @@ class FewShotFeatures(nn.Module):
         self.k_shot = args.k_shot
         self.in_channels = args.pc_in_dim
         self.n_points = args.pc_npts
+        # the reference's --pc_attribs (its default, main.py: xyzrgbXYZ); only predict_scene, which builds the channels, reads it
+        self.pc_attribs = getattr(args, "pc_attribs", {3: "xyz", 6: "xyzrgb", 9: "xyzrgbXYZ"}.get(args.pc_in_dim))
         self.use_attention = args.use_attention
         if self.n_way > 7:
             raise NotImplementedError("the head kernels carry at most 8 classes (n_way <= 7): two planes of 4 label columns")
@@ -334,6 +336,12 @@ class FewShotFeatures(nn.Module):
             ops.pointwise_conv(level2, W, None, None, ops.ACT_NONE, out=feat[:, d1:d1 + od])
         self.base_learner.forward_pm(level2, feat[:, d1 + od:])
         return feat
+
+    def predict_scene(self, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None):
+        """Label a whole scan (M, 6) `x y z r g b` -- (M, 3) without rgb in pc_attribs -- against a fitted support set:
+        blocks, chunks of n_points, predict on every chunk, votes summed per scan point -> scene.SceneResult (scene.py)."""
+        from . import scene
+        return scene.predict_scene(self, fitted, scan, block_size, stride, min_points, groups_per_launch, launch)
 
     def getFeatures(self, x):
         """Reference signature: (B, C_in, L) -> (B, C_out, L)."""

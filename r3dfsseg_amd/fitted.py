@@ -170,6 +170,20 @@ class FittedLearner(object):
             pred, loss, correct = self._predict_once(fitted, query_x, query_y)
         return self._predict_result(query_x, pred, loss, correct)
 
+    def _scene_launch(self, fitted, query_x):
+        """One launch of predict_scene: query_x (G, 1, C, N) -> (logits (G, 1, n_way + 1, N), redone)."""
+        return self.model._predict_groups(fitted, query_x, None)[0], False
+
+    def predict_scene(self, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, fitted=None):
+        """Label a whole scan -- (M, 6) rows `x y z r g b`, host or device; (M, 3) for a model without rgb -- against the
+        fitted support set: scene.SceneResult with a label, the summed logits and the vote count per scan point
+        (scene.py; INTEGRATION.md, "Labelling a scan").  fitted: default the latest fit()."""
+        fitted = self._fitted_or_raise(fitted)
+        self.model.eval()
+        with torch.no_grad():
+            return self.model.predict_scene(fitted, scan, block_size, stride, min_points, groups_per_launch,
+                                            launch=self._scene_launch)
+
     def _fitted_or_raise(self, fitted):
         fitted = self.fitted if fitted is None else fitted
         if fitted is None:

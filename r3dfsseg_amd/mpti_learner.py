@@ -199,6 +199,16 @@ class MPTILearner_V3(FittedLearner):
                     raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
         return self._predict_result(query_x, pred, loss, correct)
 
+    def _scene_launch(self, fitted, query_x):
+        """One launch of predict_scene under predict()'s rule: a launch that did not converge is redone as a whole."""
+        logits = self.model._predict_groups(fitted, query_x, None)[0]
+        if self.model.lp_converged():
+            return logits, False
+        logits = self.model._predict_groups(fitted, query_x, None, lp_iters=self.model.lp_max_iter)[0]
+        if not self.model.lp_converged():
+            raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
+        return logits, True
+
     def _test_graph(self, data, eval):
         from .episode_graph import EpisodeGraphs
         episode = list(data[:4])

@@ -645,3 +645,64 @@ def augment_clouds(x, out, scale, rot, mirror_prob, jitter, seed, first_key=0, x
                                               int(seed) & 0xffffffff, _p(seed_dev), int(first_key) & 0xffffffff, _p(mats),
                                               _p(noise), _p(mats_out), _st()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- labelling a scan (scene.py)
+SCENE_WS_NAMES = ("order", "sorted_key", "pos", "cell_start", "block_points", "block_chunk0", "chunk_block", "rec")
+
+
+def scene_bounds(scan):
+    """scan (M, ld) fp32 on the device -> the (8,) fp32 device record of r3d_scene_bounds: min x, min y, max x, max y over
+    the valid points, then their count as int32 bits."""
+    assert scan.dim() == 2 and scan.dtype == torch.float32 and scan.is_cuda and scan.is_contiguous()
+    lib = _lib.load()
+    M, ld = scan.shape
+    words = lib.r3d_scene_bounds_ws_words(M)
+    ws = torch.empty(max(words, 1), device=scan.device, dtype=torch.float32)
+    rec = torch.empty(8, device=scan.device, dtype=torch.float32)
+    _lib.check(lib.r3d_scene_bounds(_p(scan), ld, M, _p(rec), _p(ws), ws.numel(), _st()))
+    return rec
+
+
+def scene_workspace(M, ncx, ncy, chunk_cap, device):
+    """-> (ws int32 of r3d_scene_ws_words words, {name: word offset}) for SCENE_WS_NAMES."""
+    lib = _lib.load()
+    words = lib.r3d_scene_ws_words(M, ncx, ncy, chunk_cap)
+    if words < 0:
+        raise ValueError("scene: M %d, %d x %d cells, chunk_cap %d out of range" % (M, ncx, ncy, chunk_cap))
+    offs = (ctypes.c_long * 8)()
+    _lib.check(lib.r3d_scene_ws_offsets(M, ncx, ncy, chunk_cap, offs))
+    return torch.empty(words, device=device, dtype=torch.int32), dict(zip(SCENE_WS_NAMES, list(offs)))
+
+
+def scene_plan(scan, x0, y0, s, ncx, ncy, r, N, min_points, chunk_cap, ws):
+    M, ld = scan.shape
+    _lib.check(_lib.load().r3d_scene_plan(_p(scan), ld, M, float(x0), float(y0), float(s), ncx, ncy, r, N, min_points,
+                                          chunk_cap, _p(ws), ws.numel(), _st()))
+
+
+def scene_prepare(scan, ncx, ncy, r, N, chunk_cap, ws, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None):
+    """Chunks first_chunk .. first_chunk + G - 1 -> out (G, C, N) fp32, read as it lies (contiguous channel-major or a
+    transposed view of point-major rows: its strides travel with it).  slot_map (G, N) int32: the scan index per slot."""
+    assert out.dim() == 3 and out.dtype == torch.float32 and out.is_cuda
+    G, C, N_ = out.shape
+    assert N_ == N and (slot_map is None or (tuple(slot_map.shape) == (G, N) and slot_map.dtype == torch.int32
+                                             and slot_map.is_contiguous() and slot_map.is_cuda))
+    M, ld = scan.shape
+    os_ = out.stride()
+    _lib.check(_lib.load().r3d_scene_prepare(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), first_chunk, G, C,
+                                             rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map), _st()))
+    return out
+
+
+def scene_vote(M, ncx, ncy, r, N, chunk_cap, ws, logits):
+    """logits (n_chunks, n_classes, N) fp32 contiguous -> (scores (M, n_classes) fp32, labels (M,) int64, votes (M,) int32)."""
+    assert logits.dim() == 3 and logits.shape[2] == N and logits.dtype == torch.float32 and logits.is_contiguous() and logits.is_cuda
+    n_chunks, K = logits.shape[0], logits.shape[1]
+    dev = logits.device
+    scores = torch.empty(M, K, device=dev, dtype=torch.float32)
+    labels = torch.empty(M, device=dev, dtype=torch.int64)
+    votes = torch.empty(M, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_vote(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(logits), n_chunks, K, _p(scores),
+                                          _p(labels), _p(votes), _st()))
+    return scores, labels, votes

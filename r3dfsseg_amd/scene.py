@@ -1,0 +1,169 @@
+"""Label a whole scan against a fitted support set.
+
+fit() / predict() take what the reference's episode files hold: clouds of exactly pc_npts points that its loader cut out of
+a room, sampled, min-shifted and gave their channels on the host (dataloaders/loader.py:100-119).  predict_scene takes
+the scan itself -- (M, 6) rows `x y z r g b`, or (M, 3) for a model without colour -- and returns a label per point.  The
+reference has no such function, so the behaviour is defined here ("Labelling a scan"; tests/scene_ref.py
+restates it in numpy) and it draws no random number: the same scan gives the same bits.
+
+  1. valid points (finite x, y, z) and their xy extent                       r3d_scene_bounds      host read 1 of 2
+  2. cells of `stride` metres, the valid points sorted by cell (stable)      r3d_scene_plan
+  3. blocks of r x r cells, r = block_size / stride in 1..4; blocks below
+     min_points are dropped; a kept block of n points makes ceil(n / N)
+     chunks, chunk j holding list positions j, j + nc, ...                   r3d_scene_plan        host read 2 of 2
+  4. per launch, G chunks as prepared clouds of N slots (short chunks wrap)  r3d_scene_prepare
+  5. model._predict_groups on them, every chunk its own group (n_q = 1)      what model.predict launches
+  6. per scan point the sum of its chunks' logits, in a fixed order          r3d_scene_vote
+
+This module holds the host logic; the kernels are csrc/scene.hip.  All chunk logits are kept ((n_chunks, n_way + 1, N)
+floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory and one more
+pass over the scores per launch."""
+import numpy as np
+import torch
+
+from . import ops
+
+MAX_CELLS = 65536
+MAX_POINTS = 2 ** 27
+ATTRIBS = {"xyz": (-1, -1), "xyzrgb": (3, -1), "xyzXYZ": (-1, 3), "xyzrgbXYZ": (3, 6)}  # -> (rgb_ch, XYZ_ch)
+
+
+class SceneResult:
+    """labels (M,) int64 in 0..n_way, -1 without a vote; scores (M, n_way + 1) fp32 summed logits; votes (M,) int32 chunk
+    slots that held the point -- all on the device; n_blocks (kept), n_chunks, n_unlabelled, redone: host ints."""
+
+    def __init__(self, labels, scores, votes, n_blocks, n_chunks, n_unlabelled, redone):
+        self.labels, self.scores, self.votes = labels, scores, votes
+        self.n_blocks, self.n_chunks, self.n_unlabelled, self.redone = n_blocks, n_chunks, n_unlabelled, redone
+
+
+def overlap_ratio(block_size, stride):
+    """-> (r, s): r = block_size / stride as an integer in 1..4, s = the cell size as fp32."""
+    stride = block_size if stride is None else stride
+    if not (np.isfinite(block_size) and np.isfinite(stride) and block_size > 0 and stride > 0):
+        raise ValueError("predict_scene: block_size %r and stride %r must be positive" % (block_size, stride))
+    ratio = float(block_size) / float(stride)
+    r = int(round(ratio))
+    if r < 1 or r > 4 or abs(ratio - r) > 1e-6 * r:
+        raise ValueError("predict_scene: block_size / stride = %r must be an integer in 1..4" % ratio)
+    return r, np.float32(stride)
+
+
+def n_cells_along(lo, hi, s):
+    """(int)floorf((hi - lo) / s) + 1 in fp32: the arithmetic the keys kernel applies to every point."""
+    return int(np.floor((np.float32(hi) - np.float32(lo)) / np.float32(s))) + 1
+
+
+def check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch):
+    """Raises before anything needs a device.  -> (scan as a tensor, r, s, rgb_ch, XYZ_ch)."""
+    if model.training:
+        raise NotImplementedError("predict_scene is the inference path; call model.eval() first")
+    attribs = getattr(model, "pc_attribs", None)
+    if attribs not in ATTRIBS or 3 * (1 + sum(c >= 0 for c in ATTRIBS[attribs])) != model.in_channels:
+        raise ValueError("predict_scene: a scan cannot supply pc_attribs %r for %d input channels (xyz, then rgb and XYZ if "
+                         "present: %s)" % (attribs, model.in_channels, ", ".join(ATTRIBS)))
+    rgb_ch, XYZ_ch = ATTRIBS[attribs]
+    if isinstance(scan, np.ndarray):
+        scan = torch.from_numpy(scan)
+    want = 6 if rgb_ch >= 0 else 3
+    if not isinstance(scan, torch.Tensor) or scan.dim() != 2 or scan.shape[1] != want or scan.shape[0] < 1:
+        raise ValueError("predict_scene: scan must be (M, %d) rows `%s` for pc_attribs %r, got %s"
+                         % (want, "x y z r g b" if want == 6 else "x y z", attribs,
+                            tuple(scan.shape) if isinstance(scan, torch.Tensor) else type(scan).__name__))
+    if scan.dtype != torch.float32:
+        raise ValueError("predict_scene: scan must be float32, got %s" % scan.dtype)
+    if scan.shape[0] > MAX_POINTS:
+        raise ValueError("predict_scene: %d points (at most 2^27)" % scan.shape[0])
+    r, s = overlap_ratio(block_size, stride)
+    if int(min_points) != min_points or min_points < 1:
+        raise ValueError("predict_scene: min_points %r must be an integer >= 1" % (min_points,))
+    if int(groups_per_launch) != groups_per_launch or groups_per_launch < 1:
+        raise ValueError("predict_scene: groups_per_launch %r must be an integer >= 1" % (groups_per_launch,))
+    return scan, r, s, rgb_ch, XYZ_ch
+
+
+class ScenePlan:
+    """Steps 1-5 of the definition for one scan on the device: what r3d_scene_plan left in its workspace, as views.
+    order (n_valid,): scan indices sorted by cell, stable; cell_start (n_cells + 1,): offsets of the cells into it;
+    block_points (nb,); block_chunk0 (nb + 1,): first chunk of a block; chunk_block (n_chunks,).  Host: x0, y0, xmax,
+    ymax (fp32), n_valid, ncx, ncy, nbx, nby, n_chunks, n_blocks (kept), n_voted (valid points of a kept block)."""
+
+    def __init__(self, scan, N, block_size=1.0, stride=None, min_points=100):
+        if not (scan.is_cuda and scan.dim() == 2 and scan.dtype == torch.float32):
+            raise ValueError("ScenePlan: scan must be a (M, ld) float32 tensor on the device")
+        self.scan = scan.contiguous()
+        self.M, self.N, self.min_points = scan.shape[0], int(N), int(min_points)
+        self.r, self.s = overlap_ratio(block_size, stride)
+        if self.M > MAX_POINTS:
+            raise ValueError("predict_scene: %d points (at most 2^27)" % self.M)
+        rec = ops.scene_bounds(self.scan).cpu()  # host read 1 of 2
+        self.x0, self.y0, self.xmax, self.ymax = (np.float32(v) for v in rec[:4].tolist())
+        self.n_valid = int(rec.view(torch.int32)[4])
+        if self.n_valid == 0:
+            raise ValueError("predict_scene: the scan has no point with finite x, y and z")
+        self.ncx, self.ncy = n_cells_along(self.x0, self.xmax, self.s), n_cells_along(self.y0, self.ymax, self.s)
+        if self.ncx * self.ncy > MAX_CELLS:
+            raise ValueError("predict_scene: %d x %d cells of %g (at most 65536): use a larger stride or split the scan"
+                             % (self.ncx, self.ncy, float(self.s)))
+        self.n_cells = self.ncx * self.ncy
+        self.nbx, self.nby = max(self.ncx - self.r + 1, 1), max(self.ncy - self.r + 1, 1)
+        nb = self.nbx * self.nby
+        self.chunk_cap = self.r * self.r * self.n_valid // self.N + nb  # sum of ceil(n_b / N) over blocks never exceeds it
+        self.ws, o = ops.scene_workspace(self.M, self.ncx, self.ncy, self.chunk_cap, scan.device)
+        ops.scene_plan(self.scan, self.x0, self.y0, self.s, self.ncx, self.ncy, self.r, self.N, self.min_points, self.chunk_cap,
+                       self.ws)
+        self.n_chunks, self.n_blocks, self.n_voted = self.ws[o["rec"]:o["rec"] + 3].tolist()  # host read 2 of 2
+        view = lambda name, n: self.ws[o[name]:o[name] + n]
+        self.order, self.sorted_key, self.pos = view("order", self.n_valid), view("sorted_key", self.M), view("pos", self.M)
+        self.cell_start = view("cell_start", self.n_cells + 1)
+        self.block_points, self.block_chunk0 = view("block_points", nb), view("block_chunk0", nb + 1)
+        self.chunk_block = view("chunk_block", self.n_chunks)
+
+    def _geometry(self):
+        return self.ncx, self.ncy, self.r, self.N, self.chunk_cap, self.ws
+
+    def prepare(self, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None):
+        """Chunks first_chunk .. first_chunk + out.shape[0] - 1 as prepared clouds -> out (G, C, N), in out's own layout."""
+        return ops.scene_prepare(self.scan, *self._geometry(), first_chunk, out, rgb_ch, XYZ_ch, slot_map)
+
+    def vote(self, logits):
+        """logits (n_chunks, n_classes, N) -> (scores (M, n_classes), labels (M,) int64, votes (M,) int32)."""
+        if logits.shape[0] != self.n_chunks:
+            raise ValueError("vote: logits of %d chunks, the plan has %d" % (logits.shape[0], self.n_chunks))
+        if self.n_chunks == 0:  # every block was dropped: nobody votes
+            dev, K = self.scan.device, logits.shape[1]
+            return (torch.zeros(self.M, K, device=dev), torch.full((self.M,), -1, device=dev, dtype=torch.int64),
+                    torch.zeros(self.M, device=dev, dtype=torch.int32))
+        return ops.scene_vote(self.M, *self._geometry(), logits.contiguous())
+
+
+def staging(G, C, N, device):
+    """The reused buffer of G prepared clouds: point-major rows, handed on as the (G, C, N) view the encoder takes as it
+    lies (ops.input_layouts: no transpose launch)."""
+    return torch.empty(G, N, C, device=device, dtype=torch.float32).transpose(1, 2)
+
+
+def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None):
+    """model.predict_scene: see the module text.  launch(fitted, query_x (G, 1, C, N)) -> (logits (G, 1, n_way + 1, N),
+    redone: bool) runs one launch; the default is the model's own predict launch sequence, the learners pass theirs (MPTI:
+    with the redo rule of MPTILearner_V3.predict)."""
+    from . import fitted as F
+    scan, r, s, rgb_ch, XYZ_ch = check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch)
+    if launch is None:
+        launch = lambda f, qx: (model._predict_groups(f, qx, None)[0], False)
+    scan = scan.cuda()
+    C, N, K = model.in_channels, model.n_points, model.n_way + 1
+    G_max = int(groups_per_launch)
+    buf = staging(G_max, C, N, scan.device)
+    F.check_predict_args(model, fitted, buf[:, None], None)  # once: stale fit, shapes, mode -- before the first scene launch
+    plan = ScenePlan(scan, N, block_size, stride, min_points)
+    logits = torch.empty(plan.n_chunks, K, N, device=scan.device, dtype=torch.float32)
+    redone = 0
+    for c0 in range(0, plan.n_chunks, G_max):
+        G = min(G_max, plan.n_chunks - c0)
+        qx = plan.prepare(c0, buf[:G], rgb_ch, XYZ_ch)
+        z, again = launch(fitted, qx[:, None])
+        redone += bool(again)
+        logits[c0:c0 + G].copy_(z.reshape(G, K, N))
+    scores, labels, votes = plan.vote(logits)
+    return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_chunks, plan.M - plan.n_voted, redone)

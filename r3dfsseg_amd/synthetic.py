@@ -194,3 +194,22 @@ def make_episode(cfg, seed=0, noise_ratio=0.0, dup_frac=0.0, train=False, noise_
     if train:
         data += [t(qy.copy()), t(np.zeros((1, 9, N), np.float32)), t(np.zeros((1, N), np.int32)), t(flag)]
     return data, sampled_classes
+
+
+def make_scene(cfg, seed=0, extent=(8.0, 6.0, 3.0), n_points=100000, origin=(-12.3, 40.7, 0.5)):
+    """A seeded room as a deployed scan: (scan (M, 6) fp32 rows `x y z r g b` with colours in 0..255, labels (M,) int64 in
+    0..n_way).  The box-and-colour recipe of make_episode's clouds -- uniform points, one tinted box per way -- in absolute
+    coordinates: `extent` metres from an offset `origin`, nothing min-shifted or normalised (predict_scene does that)."""
+    rs = np.random.RandomState(seed)
+    M, n_way = int(n_points), cfg["n_way"]
+    ext = np.asarray(extent, np.float32)
+    pts = np.concatenate([rs.uniform(0, 1, (M, 3)).astype(np.float32) * ext, rs.uniform(0, 1, (M, 3)).astype(np.float32)], 1)
+    labels = np.zeros(M, np.int64)
+    for w in range(n_way):
+        m = _box_mask(rs, pts, 0.08, 0.30) & (labels == 0)
+        tint = np.zeros(3, np.float32); tint[w % 3] = 0.5
+        pts[m, 3:6] = np.clip(pts[m, 3:6] * 0.5 + tint, 0, 1)
+        labels[m] = w + 1
+    pts[:, :3] += np.asarray(origin, np.float32)
+    pts[:, 3:6] = np.round(pts[:, 3:6] * 255.0)
+    return torch.from_numpy(pts.astype(np.float32)), torch.from_numpy(labels)
