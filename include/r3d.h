@@ -210,6 +210,8 @@ int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes, long fit_
  * diagonal, solved by two-level conjugate gradients: coarse space = D^1/2 x indicators of 64 aggregates (nodes
  * grouped around an even subsample of the first *n_proto_dev rows, the prototypes), A-DEF2 preconditioner.
  * nodes rows are read as float4 (ldn % 4 == 0, 16-byte aligned); Y, Z (n_cap, 4) fp32, 16-byte aligned; n_cap <= 32768.
+ * D: a multiple of 4, at most 256 -- anything else is refused before a launch, by r3d_label_propagate(_batched) and by
+ * r3d_label_propagate_bwd_batched alike (the seed rows of the coarse space are staged as whole float4).
  * ws: r3d_lp_ws_words(n_cap, kp1) int32 words, 16-byte aligned; it keeps the graph, the coarse space and the
  * directed weights for r3d_label_propagate_bwd_batched.  stats_out optional device int32[2] = {converged, iterations}.
  * r3d_lp_ws_offsets: int32-word offsets inside ws of {row_ptr, col (uint16 entries), val, dinv, aggregate ids,

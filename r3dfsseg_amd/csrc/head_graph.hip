@@ -1725,8 +1725,9 @@ extern "C" int r3d_label_propagate_bwd_batched(int n_ep, const float* nodes, lon
   R3D_REQUIRE((ldn & 3) == 0 && ((uintptr_t)nodes & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)Z & 15) == 0 &&
                   ((uintptr_t)G & 15) == 0 && ((uintptr_t)lam & 15) == 0,
               "r3d_label_propagate_bwd: ldn must be a multiple of 4; nodes, ws, Z, G, lam 16-byte aligned");
-  R3D_REQUIRE(n_cap > 0 && n_cap <= 32768 && D > 0 && D <= 256 && max_iter > 0 && max_iter <= HG_MAX_ITER,
-              "r3d_label_propagate_bwd: bad arguments");
+  // D % 4 != 0 is refused as in the forward (its coarse space stages whole float4 only), whose ws this call needs
+  R3D_REQUIRE(n_cap > 0 && n_cap <= 32768 && D > 0 && D <= 256 && (D & 3) == 0 && max_iter > 0 && max_iter <= HG_MAX_ITER,
+              "r3d_label_propagate_bwd: unsupported n_cap=%d D=%d (a multiple of 4, <= 256) max_iter=%d", n_cap, D, max_iter);
   R3D_REQUIRE(n_ep >= 1 && n_ep <= 4096 && (n_ep == 1 || ((ep.ws & 3) == 0 && ep.ws >= ws_words)),
               "r3d_label_propagate_bwd: %d systems need a scratch stride that is a multiple of 4 words and >= the scratch size", n_ep);
   hipStream_t st = (hipStream_t)stream;
