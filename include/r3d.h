@@ -540,6 +540,51 @@ int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const
                    const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
                    void* stream);
 
+/* ---- predict_scene on a subsample: a cap on the chunks of a block, and labels for the points it leaves without a vote
+ * ("Labelling a scan", steps 7a, 8' and 9).  Additive: the entry points above and what they compute are
+ * as they were.
+ *
+ *   entry point            what it does
+ *   r3d_scene_run_tables   after r3d_scene_plan and before the host reads the plan record: with cap c = max_chunks >= 1,
+ *                          chunk j of a block with nc chunks RUNS when j < c.  Writes the exclusive scan of min(nc, c) over
+ *                          the blocks (first run chunk of a block), the block of every run chunk, and into the plan record
+ *                          rec[4] = run chunks, rec[5] = skipped chunks, rec[6] = valid points with a vote under the cap
+ *                          (the plan leaves zeros there).
+ *   r3d_scene_prepare_run  r3d_scene_prepare with first_chunk .. first_chunk + G - 1 numbering the run chunks; a run chunk
+ *   r3d_scene_vote_run     is still chunk (b, j) of nc: same members, same len.  r3d_scene_vote with logits (n_run,
+ *                          n_classes, N) in run-chunk order; an appearance counts when its chunk ran.  With a cap that
+ *                          skips nothing both give the bits of the entry points they are named after.
+ *   r3d_scene_transfer     after a vote (capped or not): every valid point p with votes[p] == 0 takes scores and label of
+ *                          the voted point q with the smallest d = (dx * dx + dy * dy) + dz * dz (fp32, dx = x_q - x_p,
+ *                          every operation rounded on its own; +inf is a value like any other), the lowest scan index on
+ *                          equal d, among the voted points of the 3 x 3 cells around p's cell (clipped at the grid).
+ *                          source (M,) int64 = q for such a point (votes[p] stays 0), p itself for a voted point, -1 for
+ *                          an invalid point or one that found no candidate, which is left as the vote left it.  Voted
+ *                          points go, in sorted order, into packed rows {x, y, z, index}; the others into a list per
+ *                          cell, cut into tiles of 256 queries; one workgroup per tile stages the candidate runs of the
+ *                          three cell rows through LDS, 1024 rows at a time, one thread per query keeping the
+ *                          lexicographic minimum of (d, index): no float is summed across threads, the one atomic is an
+ *                          integer count.  The sparse record's word 0 = receivers that found a source.
+ *
+ * sws: a SECOND int32 scratch of r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range), for the
+ * same (M, ncx, ncy, chunk_cap) as ws; a shorter one is refused.  r3d_scene_sparse_ws_offsets fills 8 HOST words with the
+ * word offsets of {first run chunk of a block (blocks + 1), block of a run chunk, voted points in front of a sorted
+ * position (M + 1), scan indices of the points without a vote, first query tile of a cell (ncx * ncy + 1), candidate rows
+ * (4 * M), sparse record (8), scan partials}. */
+long r3d_scene_sparse_ws_words(long M, int ncx, int ncy, long chunk_cap);
+int r3d_scene_sparse_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out);
+int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long chunk_cap, int32_t* ws, long ws_words, int max_chunks,
+                         int32_t* sws, long sws_words, void* stream);
+int r3d_scene_prepare_run(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
+                          long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G, int C, int rgb_ch,
+                          int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream);
+int r3d_scene_vote_run(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                       const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes, float* scores,
+                       int64_t* labels, int32_t* votes, void* stream);
+int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws, long ws_words,
+                       int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels, const int32_t* votes,
+                       int64_t* source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@
 //                                                                        -> a record the host reads (read 2)
 //   prepare  the G chunks of one predict launch as prepared clouds, gathered straight from the scan
 //   vote     per scan point the sum of its chunk logits (closed-form inverted index: no atomics, a fixed order)
+//   run tables, prepare / vote under a cap on the chunks of a block (only chunks j < cap of a block run)
+//   transfer scores and labels of the nearest voted point, among the 3 x 3 cells, to every point without a vote
 // All of it is bandwidth-bound integer and min / max work; the only floating-point sums are the vote's, one running
 // sum per (point, class) in a fixed order.
 #include "common.h"
@@ -29,6 +31,16 @@
 #define SC_P_NCHUNKS 0
 #define SC_P_NBLOCKS 1
 #define SC_P_NVOTED 2
+// written by r3d_scene_run_tables (r3d_scene_plan leaves zeros)
+#define SC_P_NRUN 4
+#define SC_P_NSKIPPED 5
+#define SC_P_NVOTED_RUN 6
+// transfer: queries per workgroup (one thread each), candidate rows staged through LDS at a time (16 KiB)
+#define SC_Q_TILE 256
+#define SC_C_TILE 1024
+// record of r3d_scene_transfer (ints, in the sparse workspace)
+#define SC_T_NTRANSFERRED 0
+#define SC_T_NTILES 1
 
 // ------------------------------------------------------------------------------------------------ workspace layout
 struct sc_layout {
@@ -75,6 +87,37 @@ static sc_layout sc_make_layout(long M, long n_cells, long chunk_cap) {
 static bool sc_shape_ok(long M, int ncx, int ncy, int r, long chunk_cap) {
   return M > 0 && M <= SC_MAX_POINTS && ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS && r >= 1 && r <= 4 &&
          chunk_cap >= 0 && chunk_cap < (1L << 30);
+}
+
+// the second workspace: what a cap on the chunks of a block and the transfer add.  r3d_scene_ws_words and the layout above
+// stay as they are, so a caller that uses neither allocates and sees what it always did.
+struct sp_layout {
+  long run0;     // n_cells + 1: first run chunk of a block (exclusive scan of min(nc, cap))
+  long run_blk;  // chunk_cap: block of a run chunk
+  long voff;     // M + 1: voted points in front of a sorted position
+  long part;     // one partial per SC_TILE words of voff
+  long uq;       // M: scan indices of the points without a vote, in sorted order
+  long tile0;    // n_cells + 1: first query tile of a cell
+  long rec;      // 8
+  long cand;     // 4 * M: rows {x, y, z, scan index} of the voted points, in sorted order (16-byte aligned)
+  long total;
+  int n_part;
+};
+
+static sp_layout sp_make_layout(long M, long n_cells, long chunk_cap) {
+  sp_layout S;
+  long o = 0;
+  S.n_part = (int)((M + 1 + SC_TILE - 1) / SC_TILE);
+  S.run0 = o; o += sc_align(n_cells + 1);
+  S.run_blk = o; o += sc_align(chunk_cap);
+  S.voff = o; o += sc_align(M + 1);
+  S.part = o; o += sc_align(S.n_part);
+  S.uq = o; o += sc_align(M);
+  S.tile0 = o; o += sc_align(n_cells + 1);
+  S.rec = o; o += 8;
+  S.cand = o; o += 4 * M;
+  S.total = o;
+  return S;
 }
 
 // ------------------------------------------------------------------------------------------------ bounds
@@ -411,6 +454,21 @@ extern "C" long r3d_scene_ws_words(long M, int ncx, int ncy, long chunk_cap) {
   return sc_make_layout(M, (long)ncx * ncy, chunk_cap).total;
 }
 
+extern "C" long r3d_scene_sparse_ws_words(long M, int ncx, int ncy, long chunk_cap) {
+  if (!sc_shape_ok(M, ncx, ncy, 1, chunk_cap)) return -1;
+  return sp_make_layout(M, (long)ncx * ncy, chunk_cap).total;
+}
+
+extern "C" int r3d_scene_sparse_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out /* 8 HOST words */) {
+  R3D_REQUIRE(out, "r3d_scene_sparse_ws_offsets: null pointer");
+  R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap), "r3d_scene_sparse_ws_offsets: M %ld, cells %d x %d, chunk_cap %ld out of range",
+              M, ncx, ncy, chunk_cap);
+  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
+  out[0] = S.run0; out[1] = S.run_blk; out[2] = S.voff; out[3] = S.uq;
+  out[4] = S.tile0; out[5] = S.cand; out[6] = S.rec; out[7] = S.part;
+  return R3D_OK;
+}
+
 extern "C" int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out /* 8 HOST words */) {
   R3D_REQUIRE(out, "r3d_scene_ws_offsets: null pointer");
   R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap), "r3d_scene_ws_offsets: M %ld, cells %d x %d, chunk_cap %ld out of range", M,
@@ -430,6 +488,10 @@ extern "C" int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, lo
   R3D_REQUIRE(chunk_cap > 0 && chunk_cap < (1L << 30), name ": chunk_cap %ld", chunk_cap);                                \
   R3D_REQUIRE(ws_words >= r3d_scene_ws_words(M, ncx, ncy, chunk_cap), name ": workspace of %ld words, %ld needed",        \
               ws_words, r3d_scene_ws_words(M, ncx, ncy, chunk_cap))
+
+#define SC_REQUIRE_SPARSE_WS(name)                                                                                        \
+  R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap) && sws_words >= r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap),    \
+              name ": sparse workspace of %ld words, %ld needed", sws_words, r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap))
 
 static sc_grid sc_make_grid(int ncx, int ncy, int r, long M) {
   sc_grid g;
@@ -501,14 +563,16 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
     const float* __restrict__ scan, int ld, int M, const int* __restrict__ order, const int* __restrict__ cell,
     const int* __restrict__ blk_n, const int* __restrict__ chunk0, const int* __restrict__ chunk_blk,
     const int* __restrict__ rec, sc_grid g, int first_chunk, int N, int C, int rgb_ch, int XYZ_ch, float* __restrict__ out,
-    long o_sb, long o_sc, long o_sn, int* __restrict__ slot_map) {
+    long o_sb, long o_sc, long o_sn, int* __restrict__ slot_map, const int* __restrict__ run0,
+    const int* __restrict__ run_blk) {
   __shared__ float red[6][SC_THREADS / R3D_WAVE];
   const int c = first_chunk + blockIdx.x, tid = threadIdx.x;
-  if (c >= rec[SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
-  const int b = chunk_blk[c];
+  // run0 / run_blk (both or neither): c numbers the chunks that run under the cap; the chunk itself is (b, j) of nc as ever
+  if (c >= rec[run0 ? SC_P_NRUN : SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
+  const int b = run0 ? run_blk[c] : chunk_blk[c];
   if (b < 0 || b >= g.nbx * g.nby) return;
   const int bx = b % g.nbx, by = b / g.nbx;
-  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = c - chunk0[b];
+  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = c - (run0 ? run0[b] : chunk0[b]);
   if (nc <= 0 || j < 0 || j >= nc || n <= j) return;
   const int len = (n - j + nc - 1) / nc;
   out += (long)blockIdx.x * o_sb;
@@ -567,9 +631,10 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
   }
 }
 
-extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
-                                 const int32_t* ws, long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch,
-                                 float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
+// r3d_scene_prepare (sws NULL) and r3d_scene_prepare_run: one argument list, one launch
+static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
+                      long ws_words, const int32_t* sws, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch, float* out,
+                      long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
   R3D_REQUIRE(scan && ws && out, "r3d_scene_prepare: null pointer (scan %p, ws %p, out %p)", (const void*)scan, (const void*)ws,
               (void*)out);
   SC_REQUIRE_PLAN_ARGS("r3d_scene_prepare");
@@ -584,11 +649,30 @@ extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int
               rgb_ch >= 0 ? " rgb" : "", XYZ_ch >= 0 ? " XYZ" : "");
   R3D_REQUIRE(o_sb >= 0 && o_sc > 0 && o_sn > 0, "r3d_scene_prepare: strides must be positive (out %ld %ld %ld)", o_sb, o_sc, o_sn);
   const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
   hipLaunchKernelGGL(r3d_scene_prepare_kernel, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M,
                      ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, ws + L.chunk_blk, ws + L.rec,
-                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map);
+                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map,
+                     sws ? sws + S.run0 : nullptr, sws ? sws + S.run_blk : nullptr);
   R3D_LAUNCH_CHECK("r3d_scene_prepare");
   return R3D_OK;
+}
+
+extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
+                                 const int32_t* ws, long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch,
+                                 float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
+  return sc_prepare(scan, ld, M, ncx, ncy, r, N, chunk_cap, ws, ws_words, nullptr, first_chunk, G, C, rgb_ch, XYZ_ch, out, o_sb,
+                    o_sc, o_sn, slot_map, stream);
+}
+
+extern "C" int r3d_scene_prepare_run(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
+                                     const int32_t* ws, long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G,
+                                     int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn,
+                                     int32_t* slot_map, void* stream) {
+  R3D_REQUIRE(sws, "r3d_scene_prepare_run: null pointer (sws)");
+  SC_REQUIRE_SPARSE_WS("r3d_scene_prepare_run");
+  return sc_prepare(scan, ld, M, ncx, ncy, r, N, chunk_cap, ws, ws_words, sws, first_chunk, G, C, rgb_ch, XYZ_ch, out, o_sb,
+                    o_sc, o_sn, slot_map, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ votes
@@ -598,7 +682,8 @@ extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
     int M, const int* __restrict__ skey, const int* __restrict__ pos, const int* __restrict__ cell,
     const int* __restrict__ blk_n, const int* __restrict__ chunk0, sc_grid g, int N, int K, const float* __restrict__ logits,
-    int n_chunks, float* __restrict__ scores, long long* __restrict__ labels, int* __restrict__ votes) {
+    int n_chunks, float* __restrict__ scores, long long* __restrict__ labels, int* __restrict__ votes,
+    const int* __restrict__ run0) {
   const int p = blockIdx.x * SC_THREADS + threadIdx.x;
   if (p >= M) return;
   const int n_cells = g.ncx * g.ncy;
@@ -622,7 +707,11 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
           for (int row = by; row < cy; ++row) q += sc_row_end(cell, g, bx, row) - sc_row_start(cell, g, bx, row);
           const int n = blk_n[b], j = q % nc, m = q / nc;
           const int len = (n - j + nc - 1) / nc;
-          const int ch = c0 + j;
+          int ch = c0 + j;
+          if (run0) {  // under a cap: the appearance counts when its chunk ran; logits are numbered by run chunk
+            if (j >= run0[b + 1] - run0[b]) continue;
+            ch = run0[b] + j;
+          }
           if (q < 0 || q >= n || len <= 0 || ch >= n_chunks) continue;
           const float* z = logits + ((long)ch * K + k) * N;
           for (int t = m; t < N; t += len) {
@@ -642,9 +731,9 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
   labels[p] = best;
 }
 
-extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
-                              const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
-                              void* stream) {
+static int sc_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words, const int32_t* sws,
+                   const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
+                   void* stream) {
   R3D_REQUIRE(ws && logits && scores && labels && votes,
               "r3d_scene_vote: null pointer (ws %p, logits %p, scores %p, labels %p, votes %p)", (const void*)ws,
               (const void*)logits, (void*)scores, (void*)labels, (void*)votes);
@@ -653,9 +742,271 @@ extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk
   R3D_REQUIRE(n_chunks > 0 && n_chunks <= chunk_cap, "r3d_scene_vote: n_chunks %d (1 .. chunk_cap %ld)", n_chunks, chunk_cap);
   R3D_REQUIRE(n_classes >= 1 && n_classes <= 64, "r3d_scene_vote: n_classes %d (1 .. 64)", n_classes);
   const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
   hipLaunchKernelGGL(r3d_scene_vote_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
                      (hipStream_t)stream, (int)M, ws + L.key[L.sorted], ws + L.pos, ws + L.cell, ws + L.blk_n, ws + L.chunk0,
-                     sc_make_grid(ncx, ncy, r, M), N, n_classes, logits, n_chunks, scores, (long long*)labels, votes);
+                     sc_make_grid(ncx, ncy, r, M), N, n_classes, logits, n_chunks, scores, (long long*)labels, votes,
+                     sws ? sws + S.run0 : nullptr);
   R3D_LAUNCH_CHECK("r3d_scene_vote");
+  return R3D_OK;
+}
+
+extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                              const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
+                              void* stream) {
+  return sc_vote(M, ncx, ncy, r, N, chunk_cap, ws, ws_words, nullptr, logits, n_chunks, n_classes, scores, labels, votes, stream);
+}
+
+extern "C" int r3d_scene_vote_run(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                                  const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes,
+                                  float* scores, int64_t* labels, int32_t* votes, void* stream) {
+  R3D_REQUIRE(sws, "r3d_scene_vote_run: null pointer (sws)");
+  SC_REQUIRE_SPARSE_WS("r3d_scene_vote_run");
+  return sc_vote(M, ncx, ncy, r, N, chunk_cap, ws, ws_words, sws, logits, n_chunks, n_classes, scores, labels, votes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ a cap on the chunks of a block
+// With cap c, chunk j of a block with nc chunks runs when j < c; run chunks are numbered by block id, then j.  One
+// workgroup: the exclusive scan of min(nc, c) over the blocks, and the counts for the plan record.
+__global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_run_scan_kernel(const int* __restrict__ chunk0, int nb, int cap,
+                                                                             int* __restrict__ run0, int* __restrict__ rec) {
+  __shared__ int wsum[SC_PLAN_THREADS / R3D_WAVE];
+  int carry = 0;
+  for (int b0 = 0; b0 < nb; b0 += SC_PLAN_THREADS) {
+    const int b = b0 + threadIdx.x;
+    int rc = 0;
+    if (b < nb) {
+      const int nc = chunk0[b + 1] - chunk0[b];
+      rc = nc < cap ? nc : cap;
+      rc = rc < 0 ? 0 : rc;
+    }
+    int total;
+    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(rc, wsum, total);
+    if (b < nb) run0[b] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    run0[nb] = carry;
+    rec[SC_P_NRUN] = carry;
+    rec[SC_P_NSKIPPED] = chunk0[nb] - carry;
+    rec[SC_P_NVOTED_RUN] = 0;  // counted by the next launch
+  }
+}
+
+// valid points with a vote under the cap: the walk of the vote kernel without the logits.  Integer counts, one atomic
+// per wave: the sum does not depend on the order.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_run_count_kernel(int M, const int* __restrict__ skey,
+                                                                         const int* __restrict__ pos, const int* __restrict__ cell,
+                                                                         const int* __restrict__ blk_n,
+                                                                         const int* __restrict__ chunk0,
+                                                                         const int* __restrict__ run0, sc_grid g,
+                                                                         int* __restrict__ rec) {
+  const int p = blockIdx.x * SC_THREADS + threadIdx.x;
+  bool voted = false;
+  if (p < M) {
+    const int n_cells = g.ncx * g.ncy;
+    const int sp = pos[p];
+    const int key = (sp >= 0 && sp < M) ? skey[sp] : n_cells;
+    if (key >= 0 && key < n_cells) {
+      const int cx = key % g.ncx, cy = key / g.ncx;
+      const int by0 = cy - g.r + 1 > 0 ? cy - g.r + 1 : 0, bx0 = cx - g.r + 1 > 0 ? cx - g.r + 1 : 0;
+      for (int by = by0; by <= cy && by < g.nby; ++by)
+        for (int bx = bx0; bx <= cx && bx < g.nbx; ++bx) {
+          const int b = by * g.nbx + bx;
+          const int nc = chunk0[b + 1] - chunk0[b];
+          if (nc <= 0) continue;
+          int q = sp - sc_row_start(cell, g, bx, cy);
+          for (int row = by; row < cy; ++row) q += sc_row_end(cell, g, bx, row) - sc_row_start(cell, g, bx, row);
+          if (q < 0 || q >= blk_n[b]) continue;
+          voted = voted || q % nc < run0[b + 1] - run0[b];
+        }
+    }
+  }
+  const int n = __popcll(__ballot(voted));
+  if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(&rec[SC_P_NVOTED_RUN], n);
+}
+
+extern "C" int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long chunk_cap, int32_t* ws, long ws_words,
+                                    int max_chunks, int32_t* sws, long sws_words, void* stream) {
+  R3D_REQUIRE(ws && sws, "r3d_scene_run_tables: null pointer (ws %p, sws %p)", (void*)ws, (void*)sws);
+  const int ld = 3;
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_run_tables");
+  SC_REQUIRE_SPARSE_WS("r3d_scene_run_tables");
+  R3D_REQUIRE(max_chunks >= 1, "r3d_scene_run_tables: max_chunks %d (at least 1)", max_chunks);
+  const hipStream_t st = (hipStream_t)stream;
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
+  const int nb = g.nbx * g.nby;
+  hipLaunchKernelGGL(r3d_scene_run_scan_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.chunk0, nb, max_chunks,
+                     sws + S.run0, ws + L.rec);
+  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st,
+                     sws + S.run0, nb, (int)chunk_cap, sws + S.run_blk);
+  hipLaunchKernelGGL(r3d_scene_run_count_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st, (int)M,
+                     ws + L.key[L.sorted], ws + L.pos, ws + L.cell, ws + L.blk_n, ws + L.chunk0, sws + S.run0, g, ws + L.rec);
+  R3D_LAUNCH_CHECK("r3d_scene_run_tables");
+  return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ transfer
+// Every valid point without a vote takes scores and label of the nearest voted point among the 3 x 3 cells around its
+// own: d = (dx * dx + dy * dy) + dz * dz, every operation rounded on its own; on equal d the lowest scan index.  The
+// minimum over (d, index) pairs does not depend on the order the candidates are met in.
+//   flags    voff[i] = 1 when the point at sorted position i is voted; source = the point itself, or -1
+//   scan     voff in place, exclusive (the three scan kernels of the sort)
+//   compact  voted points -> cand rows {x, y, z, index} at voff; the others -> uq at i - voff[i]
+//   tiles    per cell ceil(points without a vote / SC_Q_TILE) query tiles, their exclusive scan
+//   transfer one workgroup per query tile; the candidate runs of the three cell rows go through LDS
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_transfer_flags_kernel(int M, const int* __restrict__ order,
+                                                                              const int* __restrict__ votes,
+                                                                              int* __restrict__ voff,
+                                                                              long long* __restrict__ source) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i > M) return;
+  int f = 0;
+  if (i < M) {
+    source[i] = votes[i] > 0 ? i : -1;
+    const int p = order[i];
+    f = p >= 0 && p < M && votes[p] > 0;
+  }
+  voff[i] = f;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_transfer_compact_kernel(const float* __restrict__ scan, int ld, int M,
+                                                                                const int* __restrict__ order,
+                                                                                const int* __restrict__ votes,
+                                                                                const int* __restrict__ voff,
+                                                                                float4* __restrict__ cand,
+                                                                                int* __restrict__ uq) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const int p = order[i], v = voff[i];
+  if (p < 0 || p >= M || v < 0 || v > i) return;  // holds for the tables of a plan; keeps both writes inside M rows
+  if (votes[p] > 0) {
+    const float* q = scan + (long)p * ld;
+    cand[v] = make_float4(q[0], q[1], q[2], __int_as_float(p));
+  } else {
+    uq[i - v] = p;
+  }
+}
+
+static __device__ __forceinline__ int sc_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_transfer_tiles_kernel(const int* __restrict__ cell,
+                                                                                   const int* __restrict__ voff, int n_cells,
+                                                                                   int M, int* __restrict__ tile0,
+                                                                                   int* __restrict__ rec) {
+  __shared__ int wsum[SC_PLAN_THREADS / R3D_WAVE];
+  int carry = 0;
+  for (int c0 = 0; c0 < n_cells; c0 += SC_PLAN_THREADS) {
+    const int c = c0 + threadIdx.x;
+    int t = 0;
+    if (c < n_cells) {
+      const int s = sc_clamp(cell[c], 0, M), e = sc_clamp(cell[c + 1], s, M);
+      const int u = (e - s) - (voff[e] - voff[s]);
+      t = u > 0 ? (u + SC_Q_TILE - 1) / SC_Q_TILE : 0;
+    }
+    int total;
+    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(t, wsum, total);
+    if (c < n_cells) tile0[c] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    tile0[n_cells] = carry;
+    rec[SC_T_NTRANSFERRED] = 0;
+    rec[SC_T_NTILES] = carry;
+    for (int k = 2; k < 8; ++k) rec[k] = 0;
+  }
+}
+
+__global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
+    const float* __restrict__ scan, int ld, int M, const int* __restrict__ cell, const int* __restrict__ voff,
+    const int* __restrict__ uq, const int* __restrict__ tile0, const float4* __restrict__ cand, int ncx, int ncy, int K,
+    float* __restrict__ scores, long long* __restrict__ labels, long long* __restrict__ source, int* __restrict__ rec) {
+  __shared__ float4 rows[SC_C_TILE];
+  const int n_cells = ncx * ncy, t = blockIdx.x, tid = threadIdx.x;
+  if (t >= tile0[n_cells]) return;  // (uniform) the grid is an upper bound of the tiles
+  int lo = 0, hi = n_cells;         // tile0[lo] <= t < tile0[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tile0[mid] <= t) lo = mid; else hi = mid;
+  }
+  const int c = lo, cx = c % ncx, cy = c / ncx;
+  const int s = sc_clamp(cell[c], 0, M), e = sc_clamp(cell[c + 1], s, M);
+  const int u = (s - voff[s]) + (t - tile0[c]) * SC_Q_TILE + tid;
+  const bool live = u >= 0 && u < e - voff[e] && u < M;
+  int p = live ? uq[u] : 0;
+  p = sc_clamp(p, 0, M - 1);
+  const float* pp = scan + (long)p * ld;
+  const float px = pp[0], py = pp[1], pz = pp[2];
+  float best_d = INFINITY;
+  int best_i = 0x7fffffff;
+  const int cx0 = cx > 0 ? cx - 1 : 0, cx1 = cx + 1 < ncx ? cx + 1 : ncx - 1;
+  for (int row = cy > 0 ? cy - 1 : 0; row <= cy + 1 && row < ncy; ++row) {
+    // cells (cx0 .. cx1, row) are neighbours in the sorted order: one run of candidate rows
+    const int a = sc_clamp(voff[sc_clamp(cell[row * ncx + cx0], 0, M)], 0, M);
+    const int b = sc_clamp(voff[sc_clamp(cell[row * ncx + cx1 + 1], 0, M)], a, M);
+    for (int base = a; base < b; base += SC_C_TILE) {
+      const int n = b - base < SC_C_TILE ? b - base : SC_C_TILE;
+      __syncthreads();  // the previous tile has been read
+      for (int k = tid; k < n; k += SC_Q_TILE) rows[k] = cand[base + k];
+      __syncthreads();
+      if (live) {
+#pragma unroll 4
+        for (int k = 0; k < n; ++k) {
+          const float4 q = rows[k];  // every lane reads the same row: a broadcast
+          const float dx = __fsub_rn(q.x, px), dy = __fsub_rn(q.y, py), dz = __fsub_rn(q.z, pz);
+          const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+          const int qi = __float_as_int(q.w);
+          if (d < best_d || (d == best_d && qi < best_i)) {
+            best_d = d;
+            best_i = qi;
+          }
+        }
+      }
+    }
+  }
+  const bool found = live && best_i >= 0 && best_i < M;
+  if (found) {
+    source[p] = best_i;
+    labels[p] = labels[best_i];
+    for (int k = 0; k < K; ++k) scores[(long)p * K + k] = scores[(long)best_i * K + k];  // a voted row: nobody writes it
+  }
+  const int n = __popcll(__ballot(found));
+  if ((tid & 63) == 0 && n > 0) atomicAdd(&rec[SC_T_NTRANSFERRED], n);  // an integer count: order-independent
+}
+
+extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
+                                  long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
+                                  const int32_t* votes, int64_t* source, void* stream) {
+  R3D_REQUIRE(scan && ws && sws && scores && labels && votes && source,
+              "r3d_scene_transfer: null pointer (scan %p, ws %p, sws %p, scores %p, labels %p, votes %p, source %p)",
+              (const void*)scan, (const void*)ws, (void*)sws, (void*)scores, (void*)labels, (const void*)votes, (void*)source);
+  const int r = 1, N = 1;
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_transfer");
+  SC_REQUIRE_SPARSE_WS("r3d_scene_transfer");
+  R3D_REQUIRE(n_classes >= 1 && n_classes <= 64, "r3d_scene_transfer: n_classes %d (1 .. 64)", n_classes);
+  const hipStream_t st = (hipStream_t)stream;
+  const int n_cells = ncx * ncy;
+  const sc_layout L = sc_make_layout(M, n_cells, chunk_cap);
+  const sp_layout S = sp_make_layout(M, n_cells, chunk_cap);
+  const int* order = ws + L.idx[L.sorted];
+  float4* cand = (float4*)(sws + S.cand);
+  const int gm = (int)((M + SC_THREADS - 1) / SC_THREADS), gm1 = (int)((M + 1 + SC_THREADS - 1) / SC_THREADS);
+  hipLaunchKernelGGL(r3d_scene_transfer_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, order, votes, sws + S.voff,
+                     (long long*)source);
+  hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
+  hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, sws + S.part, S.n_part);
+  hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
+  hipLaunchKernelGGL(r3d_scene_transfer_compact_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, order, votes,
+                     sws + S.voff, cand, sws + S.uq);
+  hipLaunchKernelGGL(r3d_scene_transfer_tiles_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.cell, sws + S.voff, n_cells,
+                     (int)M, sws + S.tile0, sws + S.rec);
+  // sum over the cells of ceil(u / SC_Q_TILE) <= U / SC_Q_TILE + cells that hold such a point
+  const long tiles = M / SC_Q_TILE + (n_cells < M ? n_cells : M) + 1;
+  hipLaunchKernelGGL(r3d_scene_transfer_kernel, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
+                     sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
+                     (long long*)source, sws + S.rec);
+  R3D_LAUNCH_CHECK("r3d_scene_transfer");
   return R3D_OK;
 }

@@ -337,11 +337,13 @@ class FewShotFeatures(nn.Module):
         self.base_learner.forward_pm(level2, feat[:, d1 + od:])
         return feat
 
-    def predict_scene(self, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None):
+    def predict_scene(self, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None,
+                      max_chunks_per_block=None, transfer=None):
         """Label a whole scan (M, 6) `x y z r g b` -- (M, 3) without rgb in pc_attribs -- against a fitted support set:
         blocks, chunks of n_points, predict on every chunk, votes summed per scan point -> scene.SceneResult (scene.py)."""
         from . import scene
-        return scene.predict_scene(self, fitted, scan, block_size, stride, min_points, groups_per_launch, launch)
+        return scene.predict_scene(self, fitted, scan, block_size, stride, min_points, groups_per_launch, launch,
+                                   max_chunks_per_block, transfer)
 
     def getFeatures(self, x):
         """Reference signature: (B, C_in, L) -> (B, C_out, L)."""

@@ -174,15 +174,18 @@ class FittedLearner(object):
         """One launch of predict_scene: query_x (G, 1, C, N) -> (logits (G, 1, n_way + 1, N), redone)."""
         return self.model._predict_groups(fitted, query_x, None)[0], False
 
-    def predict_scene(self, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, fitted=None):
+    def predict_scene(self, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, fitted=None,
+                      max_chunks_per_block=None, transfer=None):
         """Label a whole scan -- (M, 6) rows `x y z r g b`, host or device; (M, 3) for a model without rgb -- against the
         fitted support set: scene.SceneResult with a label, the summed logits and the vote count per scan point
-        (scene.py; INTEGRATION.md, "Labelling a scan").  fitted: default the latest fit()."""
+        (scene.py; INTEGRATION.md, "Labelling a scan").  fitted: default the latest fit().  max_chunks_per_block=c runs
+        only c chunks of a block; transfer="nearest" labels the points without a vote from their nearest voted neighbour."""
         fitted = self._fitted_or_raise(fitted)
         self.model.eval()
         with torch.no_grad():
             return self.model.predict_scene(fitted, scan, block_size, stride, min_points, groups_per_launch,
-                                            launch=self._scene_launch)
+                                            launch=self._scene_launch, max_chunks_per_block=max_chunks_per_block,
+                                            transfer=transfer)
 
     def _fitted_or_raise(self, fitted):
         fitted = self.fitted if fitted is None else fitted

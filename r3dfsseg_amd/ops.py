@@ -681,28 +681,72 @@ def scene_plan(scan, x0, y0, s, ncx, ncy, r, N, min_points, chunk_cap, ws):
                                           chunk_cap, _p(ws), ws.numel(), _st()))
 
 
-def scene_prepare(scan, ncx, ncy, r, N, chunk_cap, ws, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None):
+def scene_prepare(scan, ncx, ncy, r, N, chunk_cap, ws, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None, sws=None):
     """Chunks first_chunk .. first_chunk + G - 1 -> out (G, C, N) fp32, read as it lies (contiguous channel-major or a
-    transposed view of point-major rows: its strides travel with it).  slot_map (G, N) int32: the scan index per slot."""
+    transposed view of point-major rows: its strides travel with it).  slot_map (G, N) int32: the scan index per slot.
+    sws (the sparse workspace after scene_run_tables): first_chunk numbers the chunks that run under the cap."""
     assert out.dim() == 3 and out.dtype == torch.float32 and out.is_cuda
     G, C, N_ = out.shape
     assert N_ == N and (slot_map is None or (tuple(slot_map.shape) == (G, N) and slot_map.dtype == torch.int32
                                              and slot_map.is_contiguous() and slot_map.is_cuda))
     M, ld = scan.shape
     os_ = out.stride()
-    _lib.check(_lib.load().r3d_scene_prepare(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), first_chunk, G, C,
-                                             rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map), _st()))
+    tail = (first_chunk, G, C, rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map), _st())
+    if sws is None:
+        _lib.check(_lib.load().r3d_scene_prepare(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), *tail))
+    else:
+        _lib.check(_lib.load().r3d_scene_prepare_run(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws),
+                                                     sws.numel(), *tail))
     return out
 
 
-def scene_vote(M, ncx, ncy, r, N, chunk_cap, ws, logits):
-    """logits (n_chunks, n_classes, N) fp32 contiguous -> (scores (M, n_classes) fp32, labels (M,) int64, votes (M,) int32)."""
+def scene_vote(M, ncx, ncy, r, N, chunk_cap, ws, logits, sws=None):
+    """logits (n_chunks, n_classes, N) fp32 contiguous -> (scores (M, n_classes) fp32, labels (M,) int64, votes (M,) int32).
+    sws (the sparse workspace after scene_run_tables): logits of the chunks that run; an appearance counts when its chunk ran."""
     assert logits.dim() == 3 and logits.shape[2] == N and logits.dtype == torch.float32 and logits.is_contiguous() and logits.is_cuda
     n_chunks, K = logits.shape[0], logits.shape[1]
     dev = logits.device
     scores = torch.empty(M, K, device=dev, dtype=torch.float32)
     labels = torch.empty(M, device=dev, dtype=torch.int64)
     votes = torch.empty(M, device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().r3d_scene_vote(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(logits), n_chunks, K, _p(scores),
-                                          _p(labels), _p(votes), _st()))
+    tail = (_p(logits), n_chunks, K, _p(scores), _p(labels), _p(votes), _st())
+    if sws is None:
+        _lib.check(_lib.load().r3d_scene_vote(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), *tail))
+    else:
+        _lib.check(_lib.load().r3d_scene_vote_run(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(), *tail))
     return scores, labels, votes
+
+
+# ---- predict_scene on a subsample: a cap on the chunks of a block, the transfer to the points without a vote
+SCENE_SPARSE_WS_NAMES = ("run_chunk0", "run_block", "voted_before", "unvoted", "tile0", "cand", "rec", "part")
+SCENE_TRANSFER_QUERY_TILE = 256   # SC_Q_TILE of csrc/scene.hip: queries of one cell per workgroup
+SCENE_TRANSFER_CAND_TILE = 1024   # SC_C_TILE: candidate rows staged through LDS at a time
+
+
+def scene_sparse_workspace(M, ncx, ncy, chunk_cap, device):
+    """-> (sws int32 of r3d_scene_sparse_ws_words words, {name: word offset}) for SCENE_SPARSE_WS_NAMES."""
+    lib = _lib.load()
+    words = lib.r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap)
+    if words < 0:
+        raise ValueError("scene: M %d, %d x %d cells, chunk_cap %d out of range" % (M, ncx, ncy, chunk_cap))
+    offs = (ctypes.c_long * 8)()
+    _lib.check(lib.r3d_scene_sparse_ws_offsets(M, ncx, ncy, chunk_cap, offs))
+    return torch.empty(words, device=device, dtype=torch.int32), dict(zip(SCENE_SPARSE_WS_NAMES, list(offs)))
+
+
+def scene_run_tables(M, ncx, ncy, r, N, chunk_cap, ws, max_chunks, sws):
+    """After scene_plan, before the plan record is read: the run tables of cap max_chunks into sws, the counts into the record."""
+    _lib.check(_lib.load().r3d_scene_run_tables(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), int(max_chunks), _p(sws),
+                                                sws.numel(), _st()))
+
+
+def scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
+    """In place: scores (M, K) fp32 and labels (M,) int64 of the points with votes == 0 from their nearest voted neighbour
+    in the 3 x 3 cells -> source (M,) int64; the count of receivers is word 0 of the sparse record, on the device."""
+    M, ld = scan.shape
+    assert scan.is_contiguous() and scores.is_contiguous() and tuple(scores.shape[:1]) == (M,) and scores.dtype == torch.float32
+    assert tuple(labels.shape) == (M,) and labels.dtype == torch.int64 and tuple(votes.shape) == (M,) and votes.dtype == torch.int32
+    source = torch.empty(M, device=scan.device, dtype=torch.int64)
+    _lib.check(_lib.load().r3d_scene_transfer(_p(scan), ld, M, ncx, ncy, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(),
+                                              scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source), _st()))
+    return source

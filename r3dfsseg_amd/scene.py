@@ -15,9 +15,14 @@ restates it in numpy) and it draws no random number: the same scan gives the sam
   5. model._predict_groups on them, every chunk its own group (n_q = 1)      what model.predict launches
   6. per scan point the sum of its chunks' logits, in a fixed order          r3d_scene_vote
 
-This module holds the host logic; the kernels are csrc/scene.hip.  All chunk logits are kept ((n_chunks, n_way + 1, N)
-floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory and one more
-pass over the scores per launch."""
+Two options, both off by default, label a dense scan on an even subsample (steps 7a, 8' and 9 of the definition):
+max_chunks_per_block=c runs only chunks j < c of a block (r3d_scene_run_tables, _prepare_run, _vote_run; still two
+host reads), and transfer="nearest" gives every valid point without a vote the scores and label of the nearest voted
+point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receivers is one more host read, at the end).
+
+This module holds the host logic; the kernels are csrc/scene.hip.  The logits of the chunks that run are kept ((n_chunks,
+n_way + 1, N) floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory
+and one more pass over the scores per launch."""
 import numpy as np
 import torch
 
@@ -30,11 +35,16 @@ ATTRIBS = {"xyz": (-1, -1), "xyzrgb": (3, -1), "xyzXYZ": (-1, 3), "xyzrgbXYZ": (
 
 class SceneResult:
     """labels (M,) int64 in 0..n_way, -1 without a vote; scores (M, n_way + 1) fp32 summed logits; votes (M,) int32 chunk
-    slots that held the point -- all on the device; n_blocks (kept), n_chunks, n_unlabelled, redone: host ints."""
+    slots that held the point -- all on the device; n_blocks (kept), n_chunks (that went through the model), n_unlabelled
+    (points whose label is -1), redone: host ints.  With transfer="nearest": source (M,) int64 on the device, the scan index
+    a point's label and scores come from (itself with a vote, another point when transferred -- its votes stay 0 --, -1
+    without a label), and n_transferred; source is None otherwise.  n_chunks_skipped: chunks a cap left out."""
 
-    def __init__(self, labels, scores, votes, n_blocks, n_chunks, n_unlabelled, redone):
+    def __init__(self, labels, scores, votes, n_blocks, n_chunks, n_unlabelled, redone, source=None, n_transferred=0,
+                 n_chunks_skipped=0):
         self.labels, self.scores, self.votes = labels, scores, votes
         self.n_blocks, self.n_chunks, self.n_unlabelled, self.redone = n_blocks, n_chunks, n_unlabelled, redone
+        self.source, self.n_transferred, self.n_chunks_skipped = source, n_transferred, n_chunks_skipped
 
 
 def overlap_ratio(block_size, stride):
@@ -54,7 +64,15 @@ def n_cells_along(lo, hi, s):
     return int(np.floor((np.float32(hi) - np.float32(lo)) / np.float32(s))) + 1
 
 
-def check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch):
+def check_sparse_args(max_chunks_per_block, transfer):
+    c = max_chunks_per_block
+    if c is not None and (isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1):
+        raise ValueError("predict_scene: max_chunks_per_block %r must be None or an integer >= 1" % (c,))
+    if transfer is not None and not (isinstance(transfer, str) and transfer == "nearest"):
+        raise ValueError("predict_scene: transfer %r must be None or \"nearest\"" % (transfer,))
+
+
+def check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch, max_chunks_per_block=None, transfer=None):
     """Raises before anything needs a device.  -> (scan as a tensor, r, s, rgb_ch, XYZ_ch)."""
     if model.training:
         raise NotImplementedError("predict_scene is the inference path; call model.eval() first")
@@ -79,6 +97,7 @@ def check_scene_args(model, scan, block_size, stride, min_points, groups_per_lau
         raise ValueError("predict_scene: min_points %r must be an integer >= 1" % (min_points,))
     if int(groups_per_launch) != groups_per_launch or groups_per_launch < 1:
         raise ValueError("predict_scene: groups_per_launch %r must be an integer >= 1" % (groups_per_launch,))
+    check_sparse_args(max_chunks_per_block, transfer)
     return scan, r, s, rgb_ch, XYZ_ch
 
 
@@ -86,9 +105,13 @@ class ScenePlan:
     """Steps 1-5 of the definition for one scan on the device: what r3d_scene_plan left in its workspace, as views.
     order (n_valid,): scan indices sorted by cell, stable; cell_start (n_cells + 1,): offsets of the cells into it;
     block_points (nb,); block_chunk0 (nb + 1,): first chunk of a block; chunk_block (n_chunks,).  Host: x0, y0, xmax,
-    ymax (fp32), n_valid, ncx, ncy, nbx, nby, n_chunks, n_blocks (kept), n_voted (valid points of a kept block)."""
+    ymax (fp32), n_valid, ncx, ncy, nbx, nby, n_chunks, n_blocks (kept), n_voted (valid points of a kept block).
+    With max_chunks_per_block=c (step 7a): run_chunk0 (nb + 1,): first run chunk of a block; run_block (n_run,); host:
+    n_run, n_skipped, and n_voted counts the valid points of a chunk that runs; prepare and vote then number the run
+    chunks.  Without a cap n_run == n_chunks and n_skipped == 0."""
 
-    def __init__(self, scan, N, block_size=1.0, stride=None, min_points=100):
+    def __init__(self, scan, N, block_size=1.0, stride=None, min_points=100, max_chunks_per_block=None):
+        check_sparse_args(max_chunks_per_block, None)
         if not (scan.is_cuda and scan.dim() == 2 and scan.dtype == torch.float32):
             raise ValueError("ScenePlan: scan must be a (M, ld) float32 tensor on the device")
         self.scan = scan.contiguous()
@@ -112,7 +135,18 @@ class ScenePlan:
         self.ws, o = ops.scene_workspace(self.M, self.ncx, self.ncy, self.chunk_cap, scan.device)
         ops.scene_plan(self.scan, self.x0, self.y0, self.s, self.ncx, self.ncy, self.r, self.N, self.min_points, self.chunk_cap,
                        self.ws)
-        self.n_chunks, self.n_blocks, self.n_voted = self.ws[o["rec"]:o["rec"] + 3].tolist()  # host read 2 of 2
+        self.cap, self.sws = max_chunks_per_block, None
+        if self.cap is not None:
+            self._sparse_workspace()
+            ops.scene_run_tables(self.M, *self._geometry(), min(int(self.cap), 2 ** 30), self.sws)
+        rec = self.ws[o["rec"]:o["rec"] + 8].tolist()  # host read 2 of 2
+        self.n_chunks, self.n_blocks, self.n_voted = rec[:3]
+        self.n_run, self.n_skipped = (self.n_chunks, 0) if self.cap is None else rec[4:6]
+        if self.cap is not None:
+            self.n_voted = rec[6]
+            so = self.so
+            self.run_chunk0 = self.sws[so["run_chunk0"]:so["run_chunk0"] + nb + 1]
+            self.run_block = self.sws[so["run_block"]:so["run_block"] + self.n_run]
         view = lambda name, n: self.ws[o[name]:o[name] + n]
         self.order, self.sorted_key, self.pos = view("order", self.n_valid), view("sorted_key", self.M), view("pos", self.M)
         self.cell_start = view("cell_start", self.n_cells + 1)
@@ -122,19 +156,32 @@ class ScenePlan:
     def _geometry(self):
         return self.ncx, self.ncy, self.r, self.N, self.chunk_cap, self.ws
 
+    def _sparse_workspace(self):
+        if self.sws is None:
+            self.sws, self.so = ops.scene_sparse_workspace(self.M, self.ncx, self.ncy, self.chunk_cap, self.scan.device)
+        return self.sws
+
     def prepare(self, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None):
-        """Chunks first_chunk .. first_chunk + out.shape[0] - 1 as prepared clouds -> out (G, C, N), in out's own layout."""
-        return ops.scene_prepare(self.scan, *self._geometry(), first_chunk, out, rgb_ch, XYZ_ch, slot_map)
+        """Chunks first_chunk .. first_chunk + out.shape[0] - 1 (under a cap: of the chunks that run) as prepared clouds ->
+        out (G, C, N), in out's own layout."""
+        return ops.scene_prepare(self.scan, *self._geometry(), first_chunk, out, rgb_ch, XYZ_ch, slot_map,
+                                 sws=None if self.cap is None else self.sws)
 
     def vote(self, logits):
-        """logits (n_chunks, n_classes, N) -> (scores (M, n_classes), labels (M,) int64, votes (M,) int32)."""
-        if logits.shape[0] != self.n_chunks:
-            raise ValueError("vote: logits of %d chunks, the plan has %d" % (logits.shape[0], self.n_chunks))
-        if self.n_chunks == 0:  # every block was dropped: nobody votes
+        """logits (n_run, n_classes, N) -> (scores (M, n_classes), labels (M,) int64, votes (M,) int32)."""
+        if logits.shape[0] != self.n_run:
+            raise ValueError("vote: logits of %d chunks, the plan has %d" % (logits.shape[0], self.n_run))
+        if self.n_run == 0:  # every block was dropped: nobody votes
             dev, K = self.scan.device, logits.shape[1]
             return (torch.zeros(self.M, K, device=dev), torch.full((self.M,), -1, device=dev, dtype=torch.int64),
                     torch.zeros(self.M, device=dev, dtype=torch.int32))
-        return ops.scene_vote(self.M, *self._geometry(), logits.contiguous())
+        return ops.scene_vote(self.M, *self._geometry(), logits.contiguous(), sws=None if self.cap is None else self.sws)
+
+    def transfer(self, scores, labels, votes):
+        """Step 9, in place on what vote() returned -> (source (M,) int64, n_transferred: a (1,) int32 device view)."""
+        sws = self._sparse_workspace()
+        source = ops.scene_transfer(self.scan, self.ncx, self.ncy, self.chunk_cap, self.ws, sws, scores, labels, votes)
+        return source, sws[self.so["rec"]:self.so["rec"] + 1]
 
 
 def staging(G, C, N, device):
@@ -143,12 +190,14 @@ def staging(G, C, N, device):
     return torch.empty(G, N, C, device=device, dtype=torch.float32).transpose(1, 2)
 
 
-def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None):
+def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=100, groups_per_launch=32, launch=None,
+                  max_chunks_per_block=None, transfer=None):
     """model.predict_scene: see the module text.  launch(fitted, query_x (G, 1, C, N)) -> (logits (G, 1, n_way + 1, N),
     redone: bool) runs one launch; the default is the model's own predict launch sequence, the learners pass theirs (MPTI:
     with the redo rule of MPTILearner_V3.predict)."""
     from . import fitted as F
-    scan, r, s, rgb_ch, XYZ_ch = check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch)
+    scan, r, s, rgb_ch, XYZ_ch = check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch,
+                                                  max_chunks_per_block, transfer)
     if launch is None:
         launch = lambda f, qx: (model._predict_groups(f, qx, None)[0], False)
     scan = scan.cuda()
@@ -156,14 +205,19 @@ def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=1
     G_max = int(groups_per_launch)
     buf = staging(G_max, C, N, scan.device)
     F.check_predict_args(model, fitted, buf[:, None], None)  # once: stale fit, shapes, mode -- before the first scene launch
-    plan = ScenePlan(scan, N, block_size, stride, min_points)
-    logits = torch.empty(plan.n_chunks, K, N, device=scan.device, dtype=torch.float32)
+    plan = ScenePlan(scan, N, block_size, stride, min_points, max_chunks_per_block)
+    logits = torch.empty(plan.n_run, K, N, device=scan.device, dtype=torch.float32)
     redone = 0
-    for c0 in range(0, plan.n_chunks, G_max):
-        G = min(G_max, plan.n_chunks - c0)
+    for c0 in range(0, plan.n_run, G_max):
+        G = min(G_max, plan.n_run - c0)
         qx = plan.prepare(c0, buf[:G], rgb_ch, XYZ_ch)
         z, again = launch(fitted, qx[:, None])
         redone += bool(again)
         logits[c0:c0 + G].copy_(z.reshape(G, K, N))
     scores, labels, votes = plan.vote(logits)
-    return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_chunks, plan.M - plan.n_voted, redone)
+    source, n_transferred = None, 0
+    if transfer is not None:
+        source, count = plan.transfer(scores, labels, votes)
+        n_transferred = int(count.item())  # the one host read the transfer adds, after everything is queued
+    return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_run, plan.M - plan.n_voted - n_transferred, redone,
+                       source, n_transferred, plan.n_skipped)
