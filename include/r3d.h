@@ -565,6 +565,17 @@ int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const
  *                          three cell rows through LDS, 1024 rows at a time, one thread per query keeping the
  *                          lexicographic minimum of (d, index): no float is summed across threads, the one atomic is an
  *                          integer count.  The sparse record's word 0 = receivers that found a source.
+ *   r3d_scene_transfer_idw r3d_scene_transfer -- same receivers, candidates, d, checks and launch sequence -- with another
+ *                          reduction per receiver (step 9'): q0, q1, q2 = the three smallest candidates in (d, scan index)
+ *                          order (fewer when there are fewer), w_i = 1.0f / (d_i + 1e-8f) (+inf gives 0), m_i[k] =
+ *                          scores[q_i][k] / (float)votes[q_i], and per class acc = w_0 m_0; acc += w_1 m_1; acc += w_2 m_2;
+ *                          scores[p][k] = acc / ((w_0 + w_1) + w_2), or m_0[k] when that sum is 0; every operation an IEEE
+ *                          one rounded on its own.  labels[p] = the arg-max (lowest class on ties), source[p] = q0, votes[p]
+ *                          stays 0.  neighbours (M, 3) int64: q0 q1 q2 (-1: missing) for a receiver, {p, -1, -1} for a voted
+ *                          point, else -1; weights (M, 3) fp32: the w_i (0: missing), {1, 0, 0} for a voted point, else 0.
+ *                          A receiver's scores are on the scale of mean logits, a voted point's stay sums over its votes.
+ *                          Each thread keeps its three pairs sorted in registers; a candidate costs one comparison against
+ *                          the third, the insertion sits behind that branch.
  *
  * sws: a SECOND int32 scratch of r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range), for the
  * same (M, ncx, ncy, chunk_cap) as ws; a shorter one is refused.  r3d_scene_sparse_ws_offsets fills 8 HOST words with the
@@ -584,6 +595,9 @@ int r3d_scene_vote_run(long M, int ncx, int ncy, int r, int N, long chunk_cap, c
 int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws, long ws_words,
                        int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels, const int32_t* votes,
                        int64_t* source, void* stream);
+int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
+                           long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
+                           const int32_t* votes, int64_t* source, int64_t* neighbours, float* weights, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,8 @@
 //   prepare  the G chunks of one predict launch as prepared clouds, gathered straight from the scan
 //   vote     per scan point the sum of its chunk logits (closed-form inverted index: no atomics, a fixed order)
 //   run tables, prepare / vote under a cap on the chunks of a block (only chunks j < cap of a block run)
-//   transfer scores and labels of the nearest voted point, among the 3 x 3 cells, to every point without a vote
+//   transfer scores and labels of the nearest voted point, among the 3 x 3 cells, to every point without a vote; or
+//            (idw) mean logits of the three nearest, weighted by 1 / d
 // All of it is bandwidth-bound integer and min / max work; the only floating-point sums are the vote's, one running
 // sum per (point, class) in a fixed order.
 #include "common.h"
@@ -860,12 +861,21 @@ extern "C" int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_transfer_flags_kernel(int M, const int* __restrict__ order,
                                                                               const int* __restrict__ votes,
                                                                               int* __restrict__ voff,
-                                                                              long long* __restrict__ source) {
+                                                                              long long* __restrict__ source,
+                                                                              long long* __restrict__ neighbours,
+                                                                              float* __restrict__ weights) {
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
   if (i > M) return;
   int f = 0;
   if (i < M) {
-    source[i] = votes[i] > 0 ? i : -1;
+    const bool voted = votes[i] > 0;
+    source[i] = voted ? i : -1;
+    if (neighbours) {  // (uniform) idw: a voted point is its own one neighbour, of weight 1; the receivers' rows come later
+      neighbours[3L * i] = voted ? i : -1;
+      neighbours[3L * i + 1] = neighbours[3L * i + 2] = -1;
+      weights[3L * i] = voted ? 1.0f : 0.0f;
+      weights[3L * i + 1] = weights[3L * i + 2] = 0.0f;
+    }
     const int p = order[i];
     f = p >= 0 && p < M && votes[p] > 0;
   }
@@ -919,10 +929,19 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_transfer_tiles_kern
   }
 }
 
+// (d, i) before (bd, bi) in lexicographic order
+static __device__ __forceinline__ bool sc_closer(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
+
+// NN = 1: the nearest voted point.  NN = 3 (idw): the three smallest (d, index) pairs, kept sorted in registers; a candidate
+// meets one comparison, against the third, and the insertion (at most two shifts) sits behind that branch.  Then per class
+// the means scores[q] / votes[q] of the three, weighted by w = 1 / (d + 1e-8), every operation rounded on its own.  Voted
+// rows are only read and a receiver's row is written by its own thread.
+template <int NN>
 __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
     const float* __restrict__ scan, int ld, int M, const int* __restrict__ cell, const int* __restrict__ voff,
     const int* __restrict__ uq, const int* __restrict__ tile0, const float4* __restrict__ cand, int ncx, int ncy, int K,
-    float* __restrict__ scores, long long* __restrict__ labels, long long* __restrict__ source, int* __restrict__ rec) {
+    float* __restrict__ scores, long long* __restrict__ labels, long long* __restrict__ source, int* __restrict__ rec,
+    const int* __restrict__ votes, long long* __restrict__ neighbours, float* __restrict__ weights) {
   __shared__ float4 rows[SC_C_TILE];
   const int n_cells = ncx * ncy, t = blockIdx.x, tid = threadIdx.x;
   if (t >= tile0[n_cells]) return;  // (uniform) the grid is an upper bound of the tiles
@@ -939,8 +958,13 @@ __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
   p = sc_clamp(p, 0, M - 1);
   const float* pp = scan + (long)p * ld;
   const float px = pp[0], py = pp[1], pz = pp[2];
-  float best_d = INFINITY;
-  int best_i = 0x7fffffff;
+  float bd[NN];
+  int bi[NN];
+#pragma unroll
+  for (int j = 0; j < NN; ++j) {
+    bd[j] = INFINITY;
+    bi[j] = 0x7fffffff;  // no candidate: every scan index comes before it
+  }
   const int cx0 = cx > 0 ? cx - 1 : 0, cx1 = cx + 1 < ncx ? cx + 1 : ncx - 1;
   for (int row = cy > 0 ? cy - 1 : 0; row <= cy + 1 && row < ncy; ++row) {
     // cells (cx0 .. cx1, row) are neighbours in the sorted order: one run of candidate rows
@@ -958,27 +982,76 @@ __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
           const float dx = __fsub_rn(q.x, px), dy = __fsub_rn(q.y, py), dz = __fsub_rn(q.z, pz);
           const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
           const int qi = __float_as_int(q.w);
-          if (d < best_d || (d == best_d && qi < best_i)) {
-            best_d = d;
-            best_i = qi;
+          if (d < bd[NN - 1] || (d == bd[NN - 1] && qi < bi[NN - 1])) {
+            if constexpr (NN == 3) {
+              if (sc_closer(d, qi, bd[1], bi[1])) {
+                bd[2] = bd[1]; bi[2] = bi[1];
+                if (sc_closer(d, qi, bd[0], bi[0])) {
+                  bd[1] = bd[0]; bi[1] = bi[0];
+                  bd[0] = d; bi[0] = qi;
+                } else {
+                  bd[1] = d; bi[1] = qi;
+                }
+              } else {
+                bd[2] = d; bi[2] = qi;
+              }
+            } else {
+              bd[0] = d;
+              bi[0] = qi;
+            }
           }
         }
       }
     }
   }
+  const int best_i = bi[0];
   const bool found = live && best_i >= 0 && best_i < M;
   if (found) {
     source[p] = best_i;
-    labels[p] = labels[best_i];
-    for (int k = 0; k < K; ++k) scores[(long)p * K + k] = scores[(long)best_i * K + k];  // a voted row: nobody writes it
+    if constexpr (NN == 3) {
+      // the pairs are sorted, so the missing ones (fewer than three candidates) are the last
+      const int nn = !(bi[1] >= 0 && bi[1] < M) ? 1 : (!(bi[2] >= 0 && bi[2] < M) ? 2 : 3);
+      float w[3], cnt[3];
+      int q[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        q[j] = j < nn ? bi[j] : best_i;
+        w[j] = j < nn ? __fdiv_rn(1.0f, __fadd_rn(bd[j], 1e-8f)) : 0.0f;  // d = +inf: w = 0
+        cnt[j] = (float)votes[q[j]];
+        neighbours[3L * p + j] = j < nn ? q[j] : -1;
+        weights[3L * p + j] = w[j];
+      }
+      float wsum = w[0];
+      if (nn > 1) wsum = __fadd_rn(wsum, w[1]);
+      if (nn > 2) wsum = __fadd_rn(wsum, w[2]);
+      int best = 0;
+      float best_v = 0.0f;
+      for (int k = 0; k < K; ++k) {
+        const float m0 = __fdiv_rn(scores[(long)q[0] * K + k], cnt[0]);  // voted rows: nobody writes them
+        float acc = __fmul_rn(w[0], m0);
+        if (nn > 1) acc = __fadd_rn(acc, __fmul_rn(w[1], __fdiv_rn(scores[(long)q[1] * K + k], cnt[1])));
+        if (nn > 2) acc = __fadd_rn(acc, __fmul_rn(w[2], __fdiv_rn(scores[(long)q[2] * K + k], cnt[2])));
+        const float v = wsum == 0.0f ? m0 : __fdiv_rn(acc, wsum);  // every d infinite: the nearest one's means
+        scores[(long)p * K + k] = v;
+        if (k == 0 || v > best_v) {
+          best = k;
+          best_v = v;
+        }
+      }
+      labels[p] = best;
+    } else {
+      labels[p] = labels[best_i];
+      for (int k = 0; k < K; ++k) scores[(long)p * K + k] = scores[(long)best_i * K + k];  // a voted row: nobody writes it
+    }
   }
   const int n = __popcll(__ballot(found));
   if ((tid & 63) == 0 && n > 0) atomicAdd(&rec[SC_T_NTRANSFERRED], n);  // an integer count: order-independent
 }
 
-extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
-                                  long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
-                                  const int32_t* votes, int64_t* source, void* stream) {
+// r3d_scene_transfer (neighbours NULL) and r3d_scene_transfer_idw: one argument list, one launch sequence
+static int sc_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws, long ws_words,
+                       int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels, const int32_t* votes,
+                       int64_t* source, int64_t* neighbours, float* weights, void* stream) {
   R3D_REQUIRE(scan && ws && sws && scores && labels && votes && source,
               "r3d_scene_transfer: null pointer (scan %p, ws %p, sws %p, scores %p, labels %p, votes %p, source %p)",
               (const void*)scan, (const void*)ws, (void*)sws, (void*)scores, (void*)labels, (const void*)votes, (void*)source);
@@ -994,7 +1067,7 @@ extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, in
   float4* cand = (float4*)(sws + S.cand);
   const int gm = (int)((M + SC_THREADS - 1) / SC_THREADS), gm1 = (int)((M + 1 + SC_THREADS - 1) / SC_THREADS);
   hipLaunchKernelGGL(r3d_scene_transfer_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, order, votes, sws + S.voff,
-                     (long long*)source);
+                     (long long*)source, (long long*)neighbours, weights);
   hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
   hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, sws + S.part, S.n_part);
   hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
@@ -1004,9 +1077,31 @@ extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, in
                      (int)M, sws + S.tile0, sws + S.rec);
   // sum over the cells of ceil(u / SC_Q_TILE) <= U / SC_Q_TILE + cells that hold such a point
   const long tiles = M / SC_Q_TILE + (n_cells < M ? n_cells : M) + 1;
-  hipLaunchKernelGGL(r3d_scene_transfer_kernel, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
-                     sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
-                     (long long*)source, sws + S.rec);
+  if (neighbours)
+    hipLaunchKernelGGL(r3d_scene_transfer_kernel<3>, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
+                       sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
+                       (long long*)source, sws + S.rec, votes, (long long*)neighbours, weights);
+  else
+    hipLaunchKernelGGL(r3d_scene_transfer_kernel<1>, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
+                       sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
+                       (long long*)source, sws + S.rec, votes, (long long*)nullptr, (float*)nullptr);
   R3D_LAUNCH_CHECK("r3d_scene_transfer");
   return R3D_OK;
+}
+
+extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
+                                  long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
+                                  const int32_t* votes, int64_t* source, void* stream) {
+  return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
+                     nullptr, nullptr, stream);
+}
+
+extern "C" int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
+                                      long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores,
+                                      int64_t* labels, const int32_t* votes, int64_t* source, int64_t* neighbours,
+                                      float* weights, void* stream) {
+  R3D_REQUIRE(neighbours && weights, "r3d_scene_transfer_idw: null pointer (neighbours %p, weights %p)", (void*)neighbours,
+              (void*)weights);
+  return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
+                     neighbours, weights, stream);
 }

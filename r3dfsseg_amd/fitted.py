@@ -179,7 +179,8 @@ class FittedLearner(object):
         """Label a whole scan -- (M, 6) rows `x y z r g b`, host or device; (M, 3) for a model without rgb -- against the
         fitted support set: scene.SceneResult with a label, the summed logits and the vote count per scan point
         (scene.py; INTEGRATION.md, "Labelling a scan").  fitted: default the latest fit().  max_chunks_per_block=c runs
-        only c chunks of a block; transfer="nearest" labels the points without a vote from their nearest voted neighbour."""
+        only c chunks of a block; transfer="nearest" labels the points without a vote from their nearest voted neighbour,
+        transfer="idw" from the mean logits of the three nearest, weighted by inverse squared distance."""
         fitted = self._fitted_or_raise(fitted)
         self.model.eval()
         with torch.no_grad():

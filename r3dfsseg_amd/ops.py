@@ -750,3 +750,19 @@ def scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
     _lib.check(_lib.load().r3d_scene_transfer(_p(scan), ld, M, ncx, ncy, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(),
                                               scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source), _st()))
     return source
+
+
+def scene_transfer_idw(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
+    """In place: scores (M, K) fp32 and labels (M,) int64 of the points with votes == 0 from the three nearest voted points
+    of the 3 x 3 cells, their mean logits weighted by 1 / (d + 1e-8) -> (source (M,) int64, neighbours (M, 3) int64,
+    weights (M, 3) fp32); the count of receivers is word 0 of the sparse record, on the device."""
+    M, ld = scan.shape
+    assert scan.is_contiguous() and scores.is_contiguous() and tuple(scores.shape[:1]) == (M,) and scores.dtype == torch.float32
+    assert tuple(labels.shape) == (M,) and labels.dtype == torch.int64 and tuple(votes.shape) == (M,) and votes.dtype == torch.int32
+    source = torch.empty(M, device=scan.device, dtype=torch.int64)
+    neighbours = torch.empty(M, 3, device=scan.device, dtype=torch.int64)
+    weights = torch.empty(M, 3, device=scan.device, dtype=torch.float32)
+    _lib.check(_lib.load().r3d_scene_transfer_idw(_p(scan), ld, M, ncx, ncy, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(),
+                                                  scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source),
+                                                  _p(neighbours), _p(weights), _st()))
+    return source, neighbours, weights

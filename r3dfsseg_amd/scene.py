@@ -18,7 +18,9 @@ restates it in numpy) and it draws no random number: the same scan gives the sam
 Two options, both off by default, label a dense scan on an even subsample (steps 7a, 8' and 9 of the definition):
 max_chunks_per_block=c runs only chunks j < c of a block (r3d_scene_run_tables, _prepare_run, _vote_run; still two
 host reads), and transfer="nearest" gives every valid point without a vote the scores and label of the nearest voted
-point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receivers is one more host read, at the end).
+point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receivers is one more host read, at the end);
+transfer="idw" (step 9') gives it the mean logits of the three nearest such points, weighted by 1 / (d + 1e-8) with d the
+squared distance, and the arg-max of those (r3d_scene_transfer_idw: same receivers, same candidates, same host read).
 
 This module holds the host logic; the kernels are csrc/scene.hip.  The logits of the chunks that run are kept ((n_chunks,
 n_way + 1, N) floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory
@@ -30,6 +32,7 @@ from . import ops
 
 MAX_CELLS = 65536
 MAX_POINTS = 2 ** 27
+TRANSFERS = ("nearest", "idw")
 ATTRIBS = {"xyz": (-1, -1), "xyzrgb": (3, -1), "xyzXYZ": (-1, 3), "xyzrgbXYZ": (3, 6)}  # -> (rgb_ch, XYZ_ch)
 
 
@@ -38,13 +41,19 @@ class SceneResult:
     slots that held the point -- all on the device; n_blocks (kept), n_chunks (that went through the model), n_unlabelled
     (points whose label is -1), redone: host ints.  With transfer="nearest": source (M,) int64 on the device, the scan index
     a point's label and scores come from (itself with a vote, another point when transferred -- its votes stay 0 --, -1
-    without a label), and n_transferred; source is None otherwise.  n_chunks_skipped: chunks a cap left out."""
+    without a label), and n_transferred; source is None otherwise.  n_chunks_skipped: chunks a cap left out.
+    With transfer="idw": source is the nearest of the neighbours, as with "nearest"; neighbours (M, 3) int64, the scan
+    indices q0 q1 q2 a receiver's scores were interpolated from (-1: fewer candidates), (p, -1, -1) for a voted point p, -1
+    without a label; weights (M, 3) fp32, their w_i (0 where missing), (1, 0, 0) for a voted point.  A receiver's scores
+    are then MEAN logits (every source's sum divided by its votes) while a voted point's stay SUMS over its votes: compare
+    scores across the two kinds only after dividing the voted ones by votes.  Both are None otherwise."""
 
     def __init__(self, labels, scores, votes, n_blocks, n_chunks, n_unlabelled, redone, source=None, n_transferred=0,
-                 n_chunks_skipped=0):
+                 n_chunks_skipped=0, neighbours=None, weights=None):
         self.labels, self.scores, self.votes = labels, scores, votes
         self.n_blocks, self.n_chunks, self.n_unlabelled, self.redone = n_blocks, n_chunks, n_unlabelled, redone
         self.source, self.n_transferred, self.n_chunks_skipped = source, n_transferred, n_chunks_skipped
+        self.neighbours, self.weights = neighbours, weights
 
 
 def overlap_ratio(block_size, stride):
@@ -68,8 +77,8 @@ def check_sparse_args(max_chunks_per_block, transfer):
     c = max_chunks_per_block
     if c is not None and (isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1):
         raise ValueError("predict_scene: max_chunks_per_block %r must be None or an integer >= 1" % (c,))
-    if transfer is not None and not (isinstance(transfer, str) and transfer == "nearest"):
-        raise ValueError("predict_scene: transfer %r must be None or \"nearest\"" % (transfer,))
+    if transfer is not None and not (isinstance(transfer, str) and transfer in TRANSFERS):
+        raise ValueError("predict_scene: transfer %r must be None, \"nearest\" or \"idw\"" % (transfer,))
 
 
 def check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch, max_chunks_per_block=None, transfer=None):
@@ -177,11 +186,18 @@ class ScenePlan:
                     torch.zeros(self.M, device=dev, dtype=torch.int32))
         return ops.scene_vote(self.M, *self._geometry(), logits.contiguous(), sws=None if self.cap is None else self.sws)
 
-    def transfer(self, scores, labels, votes):
-        """Step 9, in place on what vote() returned -> (source (M,) int64, n_transferred: a (1,) int32 device view)."""
+    def transfer(self, scores, labels, votes, mode="nearest"):
+        """Step 9 (mode "nearest") or 9' ("idw"), in place on what vote() returned -> (source (M,) int64, n_transferred: a
+        (1,) int32 device view), and for "idw" two more: neighbours (M, 3) int64 and weights (M, 3) fp32."""
+        if not (isinstance(mode, str) and mode in TRANSFERS):
+            raise ValueError("ScenePlan.transfer: mode %r must be \"nearest\" or \"idw\"" % (mode,))
         sws = self._sparse_workspace()
-        source = ops.scene_transfer(self.scan, self.ncx, self.ncy, self.chunk_cap, self.ws, sws, scores, labels, votes)
-        return source, sws[self.so["rec"]:self.so["rec"] + 1]
+        count = sws[self.so["rec"]:self.so["rec"] + 1]
+        args = (self.scan, self.ncx, self.ncy, self.chunk_cap, self.ws, sws, scores, labels, votes)
+        if mode == "idw":
+            source, neighbours, weights = ops.scene_transfer_idw(*args)
+            return source, count, neighbours, weights
+        return ops.scene_transfer(*args), count
 
 
 def staging(G, C, N, device):
@@ -215,9 +231,9 @@ def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=1
         redone += bool(again)
         logits[c0:c0 + G].copy_(z.reshape(G, K, N))
     scores, labels, votes = plan.vote(logits)
-    source, n_transferred = None, 0
+    source, n_transferred, extra = None, 0, ()
     if transfer is not None:
-        source, count = plan.transfer(scores, labels, votes)
+        source, count, *extra = plan.transfer(scores, labels, votes, transfer)  # "idw": neighbours and weights as well
         n_transferred = int(count.item())  # the one host read the transfer adds, after everything is queued
     return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_run, plan.M - plan.n_voted - n_transferred, redone,
-                       source, n_transferred, plan.n_skipped)
+                       source, n_transferred, plan.n_skipped, *extra)

@@ -2,7 +2,7 @@
 models (pc_npts 2048), MPTILearner_V3 (fitted with eval=True) and ProtoLearner.
 
     python tools/scene_label_cost.py [--points 1000000] [--extent 8 6 3] [--block-size 1.0] [--stride S] [--groups 32]
-                                     [--calls 3] [--max-chunks-per-block C] [--transfer nearest] [--sweep]
+                                     [--calls 3] [--max-chunks-per-block C] [--transfer nearest|idw] [--sweep]
 
 The whole call is timed with one HIP event pair per call (it contains the plan's two host reads and, for MPTI, one
 convergence read per launch).  The spans -- plan, chunk preparation, predict launches, vote -- are bracketed by event pairs
@@ -10,11 +10,11 @@ THIS TOOL puts around scene.ScenePlan's constructor / prepare / vote and around 
 the product path records nothing.  Per span the tool also reports the bytes the algorithm has to move (what each kernel
 must read and write once, gathers counted per element) and that over the span's time.  For the predict span only the
 clouds in and the logits out are counted, not the network's own traffic, so its figure is no bandwidth.  With
-transfer="nearest" a fifth span brackets ScenePlan.transfer (its kernels; the read of its count comes after).
+transfer="nearest" or "idw" a fifth span brackets ScenePlan.transfer (its kernels; the read of its count comes after).
 
---sweep measures, in one run, max_chunks_per_block = None, 4, 2 and 1, each without and with the transfer, and reports for
-every capped run the share of scan points whose label equals the uncapped run's label with the same transfer setting
-(`agree`), and the share that has a label at all (`labelled`).  Prints one JSON line."""
+--sweep measures, in one run, max_chunks_per_block = None, 4, 2 and 1, each without the transfer, with "nearest" and with
+"idw", and reports for every capped run the share of scan points whose label equals the uncapped run's label with the
+same transfer setting (`agree`), and the share that has a label at all (`labelled`).  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -71,9 +71,12 @@ class Spans:
         return {k: sum(a.elapsed_time(b) for a, b in v) for k, v in self.events.items()}
 
 
-def needed_bytes(plan, ld, C, K):
+def needed_bytes(plan, ld, C, K, transfer=None):
     """Bytes each span has to move once (4-byte words)."""
     M, N, n = plan.M, plan.N, plan.n_run
+    # "idw": three int64 neighbours and three weights per point from the flags pass; per receiver three vote counts and three
+    # score rows in instead of one row, and its neighbours and weights out again
+    idw = 4 * M * 9 + 4 * (M - plan.n_voted) * (3 + 2 * K + 9) if transfer == "idw" else 0
     passes = 1 if plan.n_cells < 256 else (2 if plan.n_cells < 65536 else 3)
     return {
         # bounds and keys read the scan rows; keys write (key, index); a pass reads keys for the counts, then reads and
@@ -87,7 +90,7 @@ def needed_bytes(plan, ld, C, K):
         # flags, scan and compaction: order and votes in, offsets in and out, a 4-word row or an index out, an int64 source;
         # then per receiver its row in and K scores, a label and a source out.  The candidate rows a workgroup stages are
         # re-read by every tile of a cell and are not counted: the span is arithmetic, not traffic
-        "transfer": 4 * M * (2 + 3 + 4 + 2) + 4 * (M - plan.n_voted) * (1 + 3 + 2 * K + 4),
+        "transfer": 4 * M * (2 + 3 + 4 + 2) + 4 * (M - plan.n_voted) * (1 + 3 + 2 * K + 4) + idw,
     }
 
 
@@ -106,7 +109,7 @@ def measure(learner, scan, kw, calls, cfg):
     with Spans(learner) as sp:
         res = learner.predict_scene(scan, **kw)
         span_ms = sp.ms()
-    need = needed_bytes(sp.plan, scan.shape[1], cfg["pc_in_dim"], cfg["n_way"] + 1)
+    need = needed_bytes(sp.plan, scan.shape[1], cfg["pc_in_dim"], cfg["n_way"] + 1, kw["transfer"])
     total = sum(span_ms.values())
     return {
         "max_chunks_per_block": kw["max_chunks_per_block"], "transfer": kw["transfer"],
@@ -130,8 +133,8 @@ def main():
     ap.add_argument("--groups", type=int, default=32)
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--max-chunks-per-block", type=int, default=None)
-    ap.add_argument("--transfer", choices=["nearest"], default=None)
-    ap.add_argument("--sweep", action="store_true", help="max_chunks_per_block None, 4, 2, 1, each without and with the transfer")
+    ap.add_argument("--transfer", choices=["nearest", "idw"], default=None)
+    ap.add_argument("--sweep", action="store_true", help="max_chunks_per_block None, 4, 2, 1, each without the transfer, with nearest and with idw")
     args = ap.parse_args()
     cfg = S.workload_cfg("S")
     scan = S.make_scene(cfg, seed=0, extent=tuple(args.extent), n_points=args.points)[0].cuda()
@@ -141,7 +144,7 @@ def main():
            "pc_npts": cfg["pc_npts"], "groups_per_launch": args.groups, "calls": args.calls}
     configs = [(args.max_chunks_per_block, args.transfer)]
     if args.sweep:
-        configs = [(c, t) for c in (None, 4, 2, 1) for t in (None, "nearest")]
+        configs = [(c, t) for c in (None, 4, 2, 1) for t in (None, "nearest", "idw")]
     for name in ("mpti", "protonet"):
         if name == "mpti":
             from r3dfsseg_amd.mpti_learner import MPTILearner_V3 as L
