@@ -599,6 +599,37 @@ int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, 
                            long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
                            const int32_t* votes, int64_t* source, int64_t* neighbours, float* weights, void* stream);
 
+/* ---- fit_scene: the support set from an annotated scan ("Fitting from an annotated scan", S1-S5).
+ * Additive: the entry points above and what they compute are as they were.  All three run after r3d_scene_plan (no cap) on
+ * its ws, with the same (M, ncx, ncy, r, N, chunk_cap).  The CLOUD of a kept block of n points and nc = ceil(n / N) chunks is
+ * its chunk 0: list positions 0, nc, 2 nc, ..., len = ceil(n / nc) members, slot t = member t mod len.
+ * labels: M class ids, int32 (label_bytes 4) or int64 (8), read as they are; the labels of invalid points are never read.
+ *
+ *   entry point               what it does
+ *   r3d_scene_support_counts  fg (blocks, n_way) int32: fg[b][w] = the members of block b's cloud whose label equals
+ *                             classes[w] (a device array of n_way <= 7 int32 ids), every member once; 0 for a dropped
+ *                             block.  One workgroup per block, a ballot and a population count per wave and way, the
+ *                             waves' integer counts summed in LDS.
+ *   r3d_scene_support_pick    thr[b] = max((int)floorf((float)len * min_ratio), min_fg), one IEEE fp32 multiplication;
+ *                             a kept block is ELIGIBLE for way w when fg[b][w] > thr[b].  shot_block / shot_fg (n_way,
+ *                             k_shot) int32: way w's eligible blocks by fg descending, then block id ascending, the first
+ *                             k_shot (a missing one: block -1, fg 0); rec (8 words): rec[w] = eligible blocks of way w.
+ *                             One workgroup per way, per shot one maximum of (fg << 32) | (0xFFFFFFFF - b) below the last.
+ *   r3d_scene_prepare_blocks  r3d_scene_prepare for a device list of G block ids: cloud g is chunk 0 of blocks[g], with
+ *                             that entry point's bits, strides and slot_map; a block id outside the grid or a dropped
+ *                             block leaves its cloud unwritten.  With labels, cloud_class (G int32 ids) and mask (G, N)
+ *                             int32 -- all three or none --: mask[g][t] = (labels[slot_map[g][t]] == cloud_class[g]). */
+int r3d_scene_support_counts(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                             const void* labels, int label_bytes, const int32_t* classes, int n_way, int32_t* fg,
+                             void* stream);
+int r3d_scene_support_pick(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                           const int32_t* fg, int n_way, int k_shot, float min_ratio, int min_fg, int32_t* shot_block,
+                           int32_t* shot_fg, int32_t* rec, void* stream);
+int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
+                             const int32_t* ws, long ws_words, const int32_t* blocks, int G, int C, int rgb_ch, int XYZ_ch,
+                             float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, const void* labels,
+                             int label_bytes, const int32_t* cloud_class, int32_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

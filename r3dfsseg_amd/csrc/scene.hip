@@ -10,6 +10,8 @@
 //   run tables, prepare / vote under a cap on the chunks of a block (only chunks j < cap of a block run)
 //   transfer scores and labels of the nearest voted point, among the 3 x 3 cells, to every point without a vote; or
 //            (idw) mean logits of the three nearest, weighted by 1 / d
+//   support  (fit_scene) per block and way the points of the block's chunk 0 that carry the way's class id; per way the
+//            k_shot blocks with most of them; those chunks as prepared clouds with their masks
 // All of it is bandwidth-bound integer and min / max work; the only floating-point sums are the vote's, one running
 // sum per (point, class) in a fixed order.
 #include "common.h"
@@ -560,20 +562,24 @@ static __device__ __forceinline__ int sc_list_to_sorted(const int* __restrict__ 
 }
 
 // one workgroup per chunk.  Pass 1: minima and maxima of xyz over the N slots; pass 2: gather again, write.
+// blocks (r3d_scene_prepare_blocks): workgroup i prepares chunk 0 of block blocks[i] instead of a numbered chunk; with
+// labels (element type L), cloud_class and mask: mask[i][t] = the label of slot t's point equals cloud_class[i].
+template <typename L>
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
     const float* __restrict__ scan, int ld, int M, const int* __restrict__ order, const int* __restrict__ cell,
     const int* __restrict__ blk_n, const int* __restrict__ chunk0, const int* __restrict__ chunk_blk,
     const int* __restrict__ rec, sc_grid g, int first_chunk, int N, int C, int rgb_ch, int XYZ_ch, float* __restrict__ out,
     long o_sb, long o_sc, long o_sn, int* __restrict__ slot_map, const int* __restrict__ run0,
-    const int* __restrict__ run_blk) {
+    const int* __restrict__ run_blk, const int* __restrict__ blocks, const L* __restrict__ labels,
+    const int* __restrict__ cloud_class, int* __restrict__ mask) {
   __shared__ float red[6][SC_THREADS / R3D_WAVE];
   const int c = first_chunk + blockIdx.x, tid = threadIdx.x;
   // run0 / run_blk (both or neither): c numbers the chunks that run under the cap; the chunk itself is (b, j) of nc as ever
-  if (c >= rec[run0 ? SC_P_NRUN : SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
-  const int b = run0 ? run_blk[c] : chunk_blk[c];
+  if (!blocks && c >= rec[run0 ? SC_P_NRUN : SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
+  const int b = blocks ? blocks[blockIdx.x] : (run0 ? run_blk[c] : chunk_blk[c]);
   if (b < 0 || b >= g.nbx * g.nby) return;
   const int bx = b % g.nbx, by = b / g.nbx;
-  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = c - (run0 ? run0[b] : chunk0[b]);
+  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = blocks ? 0 : c - (run0 ? run0[b] : chunk0[b]);
   if (nc <= 0 || j < 0 || j >= nc || n <= j) return;
   const int len = (n - j + nc - 1) / nc;
   out += (long)blockIdx.x * o_sb;
@@ -629,17 +635,27 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
       if (rgb_ch >= 0) o[(rgb_ch + a) * o_sc] = q[3 + a] / 255.0f;
     }
     if (slot_map) slot_map[(long)blockIdx.x * N + t] = p;
+    if (mask) mask[(long)blockIdx.x * N + t] = (long long)labels[p] == (long long)cloud_class[blockIdx.x] ? 1 : 0;
   }
 }
 
-// r3d_scene_prepare (sws NULL) and r3d_scene_prepare_run: one argument list, one launch
+// what r3d_scene_prepare_blocks adds to the argument list: a device list of G block ids and, optionally, the labels
+struct sc_block_args {
+  const int32_t* blocks;
+  const void* labels;
+  int label_bytes;
+  const int32_t* cloud_class;
+  int32_t* mask;
+};
+
+// r3d_scene_prepare (sws NULL), r3d_scene_prepare_run and r3d_scene_prepare_blocks (ba): one argument list, one launch
 static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
                       long ws_words, const int32_t* sws, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch, float* out,
-                      long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
+                      long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream, const sc_block_args* ba = nullptr) {
   R3D_REQUIRE(scan && ws && out, "r3d_scene_prepare: null pointer (scan %p, ws %p, out %p)", (const void*)scan, (const void*)ws,
               (void*)out);
   SC_REQUIRE_PLAN_ARGS("r3d_scene_prepare");
-  R3D_REQUIRE(G > 0 && first_chunk >= 0 && (long)first_chunk + G <= chunk_cap,
+  R3D_REQUIRE(G > 0 && first_chunk >= 0 && (ba || (long)first_chunk + G <= chunk_cap),  // ba: G block ids, checked by the caller
               "r3d_scene_prepare: chunks %d .. %d + %d outside the chunk table of %ld", first_chunk, first_chunk, G, chunk_cap);
   R3D_REQUIRE(C == 3 || C == 6 || C == 9, "r3d_scene_prepare: C %d (3, 6 or 9 channels)", C);
   R3D_REQUIRE(rgb_ch == -1 || rgb_ch == 3, "r3d_scene_prepare: rgb_ch %d (3, or -1: none)", rgb_ch);
@@ -651,10 +667,17 @@ static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r
   R3D_REQUIRE(o_sb >= 0 && o_sc > 0 && o_sn > 0, "r3d_scene_prepare: strides must be positive (out %ld %ld %ld)", o_sb, o_sc, o_sn);
   const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
   const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
-  hipLaunchKernelGGL(r3d_scene_prepare_kernel, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M,
-                     ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, ws + L.chunk_blk, ws + L.rec,
-                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map,
-                     sws ? sws + S.run0 : nullptr, sws ? sws + S.run_blk : nullptr);
+#define SC_LAUNCH_PREPARE(T)                                                                                                \
+  hipLaunchKernelGGL(r3d_scene_prepare_kernel<T>, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M,          \
+                     ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, ws + L.chunk_blk, ws + L.rec,              \
+                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map,          \
+                     sws ? sws + S.run0 : nullptr, sws ? sws + S.run_blk : nullptr, ba ? ba->blocks : nullptr,                  \
+                     (const T*)(ba ? ba->labels : nullptr), ba ? ba->cloud_class : nullptr, ba ? ba->mask : nullptr)
+  if (ba && ba->label_bytes == 8)
+    SC_LAUNCH_PREPARE(long long);
+  else
+    SC_LAUNCH_PREPARE(int);
+#undef SC_LAUNCH_PREPARE
   R3D_LAUNCH_CHECK("r3d_scene_prepare");
   return R3D_OK;
 }
@@ -1104,4 +1127,182 @@ extern "C" int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx
               (void*)weights);
   return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
                      neighbours, weights, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ a support set from an annotated scan
+// fit_scene ("Fitting from an annotated scan"): the cloud of a block is its chunk 0 -- list positions
+// 0, nc, 2 nc, ..., len = ceil(n / nc) members --; fg[b][w] counts the members labelled classes[w]; way w's shots are
+// its eligible blocks (fg > max((int)floorf(len * min_ratio), min_fg)) by fg descending, block id ascending.
+#define SC_MAX_WAYS 7
+
+// One workgroup per block: threads stride over the len members, per way a ballot and a population count per wave, then
+// the integer sum of the waves in LDS.  Every member counts once (wrap-around slots are not visited); dropped blocks get 0.
+template <typename L>
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_counts_kernel(
+    const L* __restrict__ labels, int M, const int* __restrict__ order, const int* __restrict__ cell,
+    const int* __restrict__ blk_n, const int* __restrict__ chunk0, sc_grid g, const int* __restrict__ classes, int n_way,
+    int* __restrict__ fg) {
+  __shared__ int wcnt[SC_THREADS / R3D_WAVE][SC_MAX_WAYS + 1];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b];
+  if (nc <= 0 || n <= 0) {  // (uniform) a dropped block
+    if (tid < n_way) fg[(long)b * n_way + tid] = 0;
+    return;
+  }
+  const int bx = b % g.nbx, by = b / g.nbx, len = (n + nc - 1) / nc;
+  long long cls[SC_MAX_WAYS];
+  int acc[SC_MAX_WAYS];
+#pragma unroll
+  for (int k = 0; k < SC_MAX_WAYS; ++k) {
+    cls[k] = k < n_way ? (long long)classes[k] : 0;
+    acc[k] = 0;
+  }
+  for (int t0 = 0; t0 < len; t0 += SC_THREADS) {  // a uniform trip count: every lane reaches every ballot
+    const int t = t0 + tid;
+    const bool live = t < len;
+    long long lab = 0;
+    if (live) {
+      int p = order[sc_list_to_sorted(cell, g, bx, by, t * nc)];
+      p = p < 0 ? 0 : (p >= M ? M - 1 : p);
+      lab = (long long)labels[p];
+    }
+#pragma unroll
+    for (int k = 0; k < SC_MAX_WAYS; ++k)
+      if (k < n_way) acc[k] += __popcll(__ballot(live && lab == cls[k]));  // the wave's count, the same in every lane
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < SC_MAX_WAYS; ++k) wcnt[tid >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < n_way) {
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < SC_THREADS / R3D_WAVE; ++w) s += wcnt[w][tid];
+    fg[(long)b * n_way + tid] = s;
+  }
+}
+
+static __device__ __forceinline__ unsigned long long sc_shfl_xor_u64(unsigned long long v, int o) {
+  const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffu), o), hi = __shfl_xor((unsigned)(v >> 32), o);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// One workgroup per way, k_shot rounds.  A round takes the maximum of key = (fg << 32) | (0xFFFFFFFF - b) over the eligible
+// blocks whose key is below the previous round's pick: fg descending, then block id ascending, no "taken" flags.  An
+// eligible block has fg >= 1, so key 0 says "none left": shot_block -1, shot_fg 0.  rec[w] = the way's eligible blocks.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_pick_kernel(
+    const int* __restrict__ blk_n, const int* __restrict__ chunk0, int nb, const int* __restrict__ fg, int n_way, int k_shot,
+    float min_ratio, int min_fg, int* __restrict__ shot_block, int* __restrict__ shot_fg, int* __restrict__ rec) {
+  __shared__ unsigned long long wmax[SC_THREADS / R3D_WAVE];
+  __shared__ int wcnt[SC_THREADS / R3D_WAVE];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  unsigned long long prev = ~0ull;
+  for (int round = 0; round < k_shot; ++round) {
+    unsigned long long best = 0;
+    int cnt = 0;
+    for (int b = tid; b < nb; b += SC_THREADS) {
+      const int nc = chunk0[b + 1] - chunk0[b], n = blk_n[b];
+      if (nc <= 0 || n <= 0) continue;
+      const int len = (n + nc - 1) / nc;
+      const int ratio = (int)floorf((float)len * min_ratio);  // fp32, one IEEE multiplication (the build does not contract)
+      const int thr = ratio > min_fg ? ratio : min_fg;
+      const int f = fg[(long)b * n_way + w];
+      if (f > thr) {
+        ++cnt;
+        const unsigned long long key = ((unsigned long long)(unsigned)f << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)b);
+        if (key < prev && key > best) best = key;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = sc_shfl_xor_u64(best, o);
+      best = other > best ? other : best;
+      cnt += __shfl_xor(cnt, o);
+    }
+    if ((tid & 63) == 0) {
+      wmax[tid >> 6] = best;
+      wcnt[tid >> 6] = cnt;
+    }
+    __syncthreads();
+    best = wmax[0];
+    cnt = wcnt[0];
+#pragma unroll
+    for (int k = 1; k < SC_THREADS / R3D_WAVE; ++k) {
+      best = wmax[k] > best ? wmax[k] : best;
+      cnt += wcnt[k];
+    }
+    __syncthreads();  // wmax / wcnt are written again in the next round
+    if (tid == 0) {
+      shot_block[w * k_shot + round] = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xffffffffu)) : -1;
+      shot_fg[w * k_shot + round] = (int)(best >> 32);
+      if (round == 0) rec[w] = cnt;
+    }
+    prev = best;  // 0 after the last eligible block: nothing is below it
+  }
+  if (w == 0 && tid >= n_way && tid < 8) rec[tid] = 0;
+}
+
+#define SC_REQUIRE_SUPPORT_ARGS(name)                                                                                     \
+  R3D_REQUIRE(n_way >= 1 && n_way <= SC_MAX_WAYS, name ": n_way %d (1 .. 7)", n_way)
+
+extern "C" int r3d_scene_support_counts(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
+                                        long ws_words, const void* labels, int label_bytes, const int32_t* classes, int n_way,
+                                        int32_t* fg, void* stream) {
+  R3D_REQUIRE(ws && labels && classes && fg, "r3d_scene_support_counts: null pointer (ws %p, labels %p, classes %p, fg %p)",
+              (const void*)ws, labels, (const void*)classes, (void*)fg);
+  const int ld = 3;
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_support_counts");
+  SC_REQUIRE_SUPPORT_ARGS("r3d_scene_support_counts");
+  R3D_REQUIRE(label_bytes == 4 || label_bytes == 8, "r3d_scene_support_counts: labels of %d bytes (int32 or int64)", label_bytes);
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
+  const int nb = g.nbx * g.nby;
+  if (label_bytes == 8)
+    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<long long>, dim3(nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                       (const long long*)labels, (int)M, ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, g, classes,
+                       n_way, fg);
+  else
+    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<int>, dim3(nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                       (const int*)labels, (int)M, ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, g, classes, n_way,
+                       fg);
+  R3D_LAUNCH_CHECK("r3d_scene_support_counts");
+  return R3D_OK;
+}
+
+extern "C" int r3d_scene_support_pick(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                                      const int32_t* fg, int n_way, int k_shot, float min_ratio, int min_fg,
+                                      int32_t* shot_block, int32_t* shot_fg, int32_t* rec, void* stream) {
+  R3D_REQUIRE(ws && fg && shot_block && shot_fg && rec,
+              "r3d_scene_support_pick: null pointer (ws %p, fg %p, shot_block %p, shot_fg %p, rec %p)", (const void*)ws,
+              (const void*)fg, (void*)shot_block, (void*)shot_fg, (void*)rec);
+  const int ld = 3;
+  SC_REQUIRE_PLAN_ARGS("r3d_scene_support_pick");
+  SC_REQUIRE_SUPPORT_ARGS("r3d_scene_support_pick");
+  R3D_REQUIRE(k_shot >= 1 && k_shot <= 64, "r3d_scene_support_pick: k_shot %d (1 .. 64)", k_shot);
+  R3D_REQUIRE(min_ratio >= 0.0f && min_ratio < 1.0f, "r3d_scene_support_pick: min_ratio %g (0 <= ratio < 1)", (double)min_ratio);
+  R3D_REQUIRE(min_fg >= 0, "r3d_scene_support_pick: min_fg %d (at least 0)", min_fg);
+  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
+  hipLaunchKernelGGL(r3d_scene_support_pick_kernel, dim3(n_way), dim3(SC_THREADS), 0, (hipStream_t)stream, ws + L.blk_n,
+                     ws + L.chunk0, g.nbx * g.nby, fg, n_way, k_shot, min_ratio, min_fg, shot_block, shot_fg, rec);
+  R3D_LAUNCH_CHECK("r3d_scene_support_pick");
+  return R3D_OK;
+}
+
+extern "C" int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
+                                        const int32_t* ws, long ws_words, const int32_t* blocks, int G, int C, int rgb_ch,
+                                        int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map,
+                                        const void* labels, int label_bytes, const int32_t* cloud_class, int32_t* mask,
+                                        void* stream) {
+  R3D_REQUIRE(blocks, "r3d_scene_prepare_blocks: null pointer (blocks)");
+  R3D_REQUIRE(G > 0 && G <= SC_MAX_CELLS, "r3d_scene_prepare_blocks: G %d (1 .. 65536 block ids)", G);
+  R3D_REQUIRE((labels && cloud_class && mask) || (!labels && !cloud_class && !mask),
+              "r3d_scene_prepare_blocks: labels %p, cloud_class %p and mask %p go together", labels, (const void*)cloud_class,
+              (void*)mask);
+  R3D_REQUIRE(!labels || label_bytes == 4 || label_bytes == 8, "r3d_scene_prepare_blocks: labels of %d bytes (int32 or int64)",
+              label_bytes);
+  const sc_block_args ba = {blocks, labels, label_bytes, cloud_class, mask};
+  return sc_prepare(scan, ld, M, ncx, ncy, r, N, chunk_cap, ws, ws_words, nullptr, 0, G, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn,
+                    slot_map, stream, &ba);
 }

@@ -345,6 +345,14 @@ class FewShotFeatures(nn.Module):
         return scene.predict_scene(self, fitted, scan, block_size, stride, min_points, groups_per_launch, launch,
                                    max_chunks_per_block, transfer)
 
+    def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
+                  eval=False):
+        """Fit the support set from an annotated scan: `scan` as for predict_scene, labels (M,) class ids, way w =
+        classes[w - 1]; per way the k_shot blocks whose cloud holds most points of the class, their prepared clouds and
+        masks, then fit_support -> scene_support.SceneSupport (scene_support.py)."""
+        from . import scene_support
+        return scene_support.fit_scene(self, scan, labels, classes, block_size, stride, min_points, min_ratio, min_fg, eval)
+
     def getFeatures(self, x):
         """Reference signature: (B, C_in, L) -> (B, C_out, L)."""
         B, _, N = x.shape

@@ -188,6 +188,19 @@ class FittedLearner(object):
                                             launch=self._scene_launch, max_chunks_per_block=max_chunks_per_block,
                                             transfer=transfer)
 
+    def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
+                  eval=False):
+        """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64
+        class ids (host or device), classes: n_way distinct ints, way w = classes[w - 1].  Per way the k_shot blocks whose
+        cloud holds most points of the class become the shots (scene_support.py; INTEGRATION.md, "Fitting from an annotated
+        scan").  Stores the FittedSupport and returns the scene_support.SceneSupport that holds it; a way with fewer than
+        k_shot eligible blocks raises ValueError and leaves the latest fit as it was."""
+        self.model.eval()
+        with torch.no_grad():
+            sup = self.model.fit_scene(scan, labels, classes, block_size, stride, min_points, min_ratio, min_fg, eval=eval)
+        self.fitted = sup.fitted
+        return sup
+
     def _fitted_or_raise(self, fitted):
         fitted = self.fitted if fitted is None else fitted
         if fitted is None:

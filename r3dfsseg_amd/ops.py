@@ -766,3 +766,59 @@ def scene_transfer_idw(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes
                                                   scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source),
                                                   _p(neighbours), _p(weights), _st()))
     return source, neighbours, weights
+
+
+# ---- fit_scene: the support set from an annotated scan (scene_support.py)
+SCENE_SUPPORT_MAX_WAYS = 7  # SC_MAX_WAYS of csrc/scene.hip
+
+
+def _label_bytes(labels, M):
+    assert labels.is_cuda and labels.is_contiguous() and tuple(labels.shape) == (M,) and labels.dtype in (torch.int32, torch.int64)
+    return labels.element_size()
+
+
+def scene_support_counts(M, ncx, ncy, r, N, chunk_cap, ws, labels, classes):
+    """labels (M,) int32 or int64 on the device, read as they are; classes (n_way,) int32 on the device -> fg (blocks, n_way)
+    int32: per block of the plan in ws the members of its cloud (chunk 0) labelled classes[w], 0 for a dropped block."""
+    assert classes.is_cuda and classes.dtype == torch.int32 and classes.is_contiguous() and classes.dim() == 1
+    n_way = classes.numel()
+    nb = max(ncx - r + 1, 1) * max(ncy - r + 1, 1)
+    fg = torch.empty(nb, n_way, device=labels.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_support_counts(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(labels),
+                                                    _label_bytes(labels, M), _p(classes), n_way, _p(fg), _st()))
+    return fg
+
+
+def scene_support_pick(M, ncx, ncy, r, N, chunk_cap, ws, fg, k_shot, min_ratio, min_fg):
+    """fg (blocks, n_way) int32 -> (shot_block (n_way, k_shot) int32, shot_fg (n_way, k_shot) int32, rec (8,) int32 whose
+    word w counts way w's eligible blocks): per way the eligible blocks by fg descending, then block id ascending."""
+    assert fg.is_cuda and fg.dtype == torch.int32 and fg.is_contiguous() and fg.dim() == 2
+    n_way = fg.shape[1]
+    assert fg.shape[0] == max(ncx - r + 1, 1) * max(ncy - r + 1, 1)
+    shot_block = torch.empty(n_way, k_shot, device=fg.device, dtype=torch.int32)
+    shot_fg = torch.empty(n_way, k_shot, device=fg.device, dtype=torch.int32)
+    rec = torch.empty(8, device=fg.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_support_pick(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(fg), n_way, k_shot,
+                                                  float(min_ratio), int(min_fg), _p(shot_block), _p(shot_fg), _p(rec), _st()))
+    return shot_block, shot_fg, rec
+
+
+def scene_prepare_blocks(scan, ncx, ncy, r, N, chunk_cap, ws, blocks, out, rgb_ch, XYZ_ch, slot_map=None, labels=None,
+                         cloud_class=None, mask=None):
+    """Chunk 0 of every block in blocks (G,) int32 on the device -> out (G, C, N) fp32, read as it lies, with the bits of
+    scene_prepare on that chunk; slot_map (G, N) int32.  labels (M,), cloud_class (G,) int32 and mask (G, N) int32, all or
+    none: mask[g, t] = (labels[slot_map[g, t]] == cloud_class[g])."""
+    assert out.dim() == 3 and out.dtype == torch.float32 and out.is_cuda
+    G, C, N_ = out.shape
+    i32 = lambda t, shape: t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape
+    assert N_ == N and i32(blocks, (G,)) and (slot_map is None or i32(slot_map, (G, N)))
+    M, ld = scan.shape
+    nbytes = 0
+    if labels is not None or cloud_class is not None or mask is not None:
+        assert i32(cloud_class, (G,)) and i32(mask, (G, N))
+        nbytes = _label_bytes(labels, M)
+    os_ = out.stride()
+    _lib.check(_lib.load().r3d_scene_prepare_blocks(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(blocks), G,
+                                                    C, rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map),
+                                                    _p(labels), nbytes, _p(cloud_class), _p(mask), _st()))
+    return out
