@@ -103,6 +103,20 @@ int r3d_knn_topk_batched(const float* x, long ldx, const float* x_cm, int B, int
 int r3d_debug_set_knn_bf16_threshold(int on);
 /* the same for the second pass: <= 0 keeps it the all-pairs fp32 pass, > 0 the bf16 filter where it applies (same results) */
 int r3d_debug_set_knn_bf16_filter(int on);
+/* test utility: the kernel configuration r3d_knn_topk[_batched] would launch for this call, as the launcher itself decides
+ * it (one host function serves both), under the two switches above as they are set.  Launches nothing, needs no device.
+ * flags: bit 0 status given, bit 1 x_cm given (as r3d_knn_ws_words), bit 2 x is NULL, bit 3 the call is r3d_knn_topk
+ * (fixed scratch: no bf16 pieces, no split lists).  ldx: row pitch of x; x_misalign_bytes: address of x modulo 16.
+ * Returns a bit mask, or -1 for a shape the calls refuse:
+ *   bits 0-1  path: 0 = k <= 32 append-and-rank (overflowed tiles redone exactly), 1 = large-k append-and-rank
+ *             (overflow -> status bit 0), 2 = sorted insertion
+ *   bit 2     few: (path 0) 8 waves per query tile instead of 4
+ *   bit 3     split: (path 1) the candidate axis dealt to two workgroups per tile, lists merged
+ *   bit 4     bfa: the threshold pass runs on the bf16 matrix core
+ *   bit 5     filter: (path 0) pass B is the bf16 filter + exact scores of the survivors
+ *   bits 6-7  channel configuration: 0 = chunks of 64 with a padded tail, 1 = (path 0) C <= 16, 2 = C % 64 == 0
+ *   bits 8-9  (path 2) list registers per lane: 1 -> 1, 2 -> 2, 3 -> 4 (k <= 64, <= 128, <= 256) */
+int r3d_debug_knn_path(int B, int N, int C, int k, int flags, long ldx, int x_misalign_bytes);
 /* 1: launches captured into a hipGraph may use their stream's packed-weight scratch of the bf16 x 3 point-wise GEMM (it
  * must exist already: run the sequence eagerly on that stream first).  The caller promises that the captured graph is the
  * only user of that stream's scratch while it replays.  Default 0: captured launches take the kernel that cuts W itself

@@ -1537,6 +1537,8 @@ enum KnnPath {
 };
 struct KnnPlan {
   KnnPath path;
+  int C, k;
+  long tiles;  // 32-row query tiles per set (the streamed kernels' grid.x)
   bool few;    // (small) fewer row tiles than CUs: 8 waves per tile instead of 4
   bool split;  // (large) the candidate axis dealt to two workgroups per tile, their lists merged
   bool bf;     // bf16 pieces of the points: the threshold pass (and in the small path the filter) on the bf16 matrix core
@@ -1548,6 +1550,9 @@ struct KnnPlan {
 static KnnPlan knn_plan(int B, int N, int C, int k, bool status, bool x_cm, bool extras) {
   KnnPlan p = {};
   const long tiles = ((long)N + 31) / 32;
+  p.C = C;
+  p.k = k;
+  p.tiles = tiles;
   if (k <= 32 && C <= 64) {
     p.path = KNN_STREAMED_SMALL;
     // (the 2 query clouds of a training episode: 128 tiles; each wave's chain of sub-tiles is half as long with 8 waves)
@@ -1583,6 +1588,49 @@ static KnnPlan knn_plan(int B, int N, int C, int k, bool status, bool x_cm, bool
 
 extern "C" long r3d_knn_ws_words(int B, int N, int C, int k, int flags) {
   return knn_plan(B, N, C, k, flags & 1, flags & 2, true).words;
+}
+
+// What one call launches: the ONE place that decides it.  knn_choose is a pure host function of the plan, the two A/B
+// switches and what the caller handed over; knn_topk_impl branches on its result and on nothing else, and
+// r3d_debug_knn_path returns the same result as a bit mask (tests assert the path a case claims to reach).
+enum KnnChan {
+  KNN_CHAN_ANY,   // channel chunks of 64, the last one padded (FULLC = false)
+  KNN_CHAN_LE16,  // (small path) C <= 16: one chunk of 16 channels
+  KNN_CHAN_FULL,  // C % 64 == 0: every chunk is whole (FULLC)
+};
+struct KnnChoice {
+  KnnPath path;
+  bool few, split;  // as planned
+  bool bfa;         // the threshold pass runs on the bf16 pieces
+  bool filter;      // (small) ... and pass B is the bf16 filter + exact scores of the survivors
+  KnnChan chan;
+  int regs;         // (insertion) list registers per lane: 1, 2 or 4
+};
+static KnnChoice knn_choose(const KnnPlan& p, bool bf16_threshold, bool bf16_filter, bool has_x, int ldx_mod4,
+                            bool x_aligned16) {
+  KnnChoice ch = {};
+  ch.path = p.path;
+  if (p.path == KNN_INSERTION) {
+    ch.regs = p.k <= 64 ? 1 : p.k <= 128 ? 2 : 4;
+    return ch;
+  }
+  ch.few = p.few;
+  ch.split = p.split;
+  ch.chan = p.path == KNN_STREAMED_SMALL && p.C <= 16 ? KNN_CHAN_LE16 : p.C % 64 == 0 ? KNN_CHAN_FULL : KNN_CHAN_ANY;
+  ch.bfa = p.bf && bf16_threshold && has_x;  // the pieces are cut from the point-major rows (p.bf: C % 64 == 0)
+  // the filter reads the point-major rows as 16-byte vectors, and its survivor bitmap, 32 words per sub-tile, sits in
+  // the index buffer's 32 KM_CAP words
+  ch.filter = p.path == KNN_STREAMED_SMALL && ch.bfa && bf16_filter && ldx_mod4 == 0 && x_aligned16 && p.tiles <= KM_CAP;
+  return ch;
+}
+// flags: bit 0 status given, bit 1 x_cm given (as r3d_knn_ws_words), bit 2 x is NULL, bit 3 the call is r3d_knn_topk
+// (two fixed scratch buffers: no bf16 pieces, no split lists).  Launches nothing, needs no device.
+extern "C" int r3d_debug_knn_path(int B, int N, int C, int k, int flags, long ldx, int x_misalign_bytes) {
+  if (B <= 0 || N <= 0 || C <= 0 || k <= 0 || k > N || k > 256) return -1;
+  const KnnChoice ch = knn_choose(knn_plan(B, N, C, k, flags & 1, flags & 2, !(flags & 8)), g_knn_bf16_threshold,
+                                  g_knn_bf16_filter, !(flags & 4), (int)(ldx & 3), (x_misalign_bytes & 15) == 0);
+  return (int)ch.path | ch.few << 2 | ch.split << 3 | ch.bfa << 4 | ch.filter << 5 | (int)ch.chan << 6 |
+         (ch.regs == 4 ? 3 : ch.regs) << 8;
 }
 
 // one call's operands and scratch, as the kernels take them (xT: the streamed kernels' channel-major operand)
@@ -1663,6 +1711,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
   R3D_REQUIRE(k > 0 && k <= N && k <= 256, "r3d_knn_topk: unsupported k=%d (need 1..min(N,256))", k);
   R3D_REQUIRE(mode == R3D_SCORE_DGCNN || mode == R3D_SCORE_L2, "r3d_knn_topk: unknown mode %d", mode);
   const KnnPlan p = knn_plan(B, N, C, k, status, x_cm, ws);
+  const KnnChoice ch = knn_choose(p, g_knn_bf16_threshold, g_knn_bf16_filter, x, (int)(ldx & 3), ((uintptr_t)x & 15) == 0);
   KnnCall c = {x, ldx, nullptr, 0, B, N, C, k, mode, n_valid_dev, n_valid_stride, idx_out, score_out, (hipStream_t)stream};
   if (ws) {
     R3D_REQUIRE(((uintptr_t)ws & 15) == 0 && ws_words >= p.words,
@@ -1681,65 +1730,62 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
     c.tile_flags = (int*)(norm_ws + (long)B * N);  // r3d_knn_norm_ws_words reserves B ceil(N/32) words here
     c.cm = cm_ws;
   }
-  if (p.path == KNN_INSERTION) {
+  if (ch.path == KNN_INSERTION) {
     R3D_REQUIRE(c.x, "r3d_knn_topk: the insertion kernel needs the point-major matrix");
     const size_t lds = knn_lds_bytes(c.C);
     R3D_REQUIRE(lds <= 160 * 1024, "r3d_knn_topk: C=%d needs %zu B of LDS (> 160 KiB)", c.C, lds);
     int rc = knn_sqnorm_launch(c.x, c.ldx, (long)c.B * c.N, c.C, c.norms, c.st);
     if (rc) return rc;
-    if (c.k <= 64) knn_insertion_launch<1>(c, lds);
-    else if (c.k <= 128) knn_insertion_launch<2>(c, lds);
+    if (ch.regs == 1) knn_insertion_launch<1>(c, lds);
+    else if (ch.regs == 2) knn_insertion_launch<2>(c, lds);
     else knn_insertion_launch<4>(c, lds);
     R3D_LAUNCH_CHECK("r3d_knn_topk");
     return R3D_OK;
   }
   int rc = knn_cm_operand(c, x_cm);
   if (rc) return rc;
-  const bool bfa = p.bf && g_knn_bf16_threshold && c.x;  // the pieces are cut from the point-major rows
   const dim3 grid(r3d_cdiv(c.N, 32), c.B);
-  if (p.path == KNN_STREAMED_SMALL) {
+  if (ch.path == KNN_STREAMED_SMALL) {
     // append-and-rank (mid configuration); tiles whose survivor buffer overflowed are redone by the exact
     // two-pass kernel in the same stream -- no host round trip, never a wrong result
     r3d_zero_words(c.tile_flags, (long)c.B * grid.x, c.st);
-    if (c.C <= 16) {
-      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
+    if (ch.chan == KNN_CHAN_LE16) {
+      rc = ch.few ? knn_append_launch<8, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
-    } else if (bfa) {
+    } else if (ch.bfa) {
       knn_pack_bf(c);
-      // the filter on the bf16 core as well: exact scores come from the point-major rows, read as 16-byte vectors; its
-      // survivor bitmap, 32 words per sub-tile, sits in the index buffer's 32 KM_CAP words.  (With the filter the threshold
+      // the filter on the bf16 core as well: exact scores come from the point-major rows.  (With the filter the threshold
       // pass visits EVERY sub-tile: a tighter threshold means fewer survivors, and their exact scores cost more than the
       // half pass saved -- 3.30 against 3.63 ms per 384 clouds.)
-      const bool filter = g_knn_bf16_filter && (c.ldx & 3) == 0 && ((uintptr_t)c.x & 15) == 0 && grid.x <= KM_CAP;
-      rc = filter ? knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, 1, true, true, true>(c, grid, nullptr, c.tile_flags)
-                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true, true>(c, grid, nullptr, c.tile_flags);
-    } else if (c.C % 64 == 0) {
-      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags)
+      rc = ch.filter ? knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, 1, true, true, true>(c, grid, nullptr, c.tile_flags)
+                     : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true, true>(c, grid, nullptr, c.tile_flags);
+    } else if (ch.chan == KNN_CHAN_FULL) {
+      rc = ch.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags)
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags);
     } else {
-      rc = p.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
+      rc = ch.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(c.C <= 16 ? r3d_knn_small_kernel<8> : r3d_knn_small_kernel<32>, grid, dim3(256), 0, c.st, c.xT, c.ldT, c.N,
-                       c.C, c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, (const int*)c.tile_flags);
+    hipLaunchKernelGGL(ch.chan == KNN_CHAN_LE16 ? r3d_knn_small_kernel<8> : r3d_knn_small_kernel<32>, grid, dim3(256), 0, c.st,
+                       c.xT, c.ldT, c.N, c.C, c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, (const int*)c.tile_flags);
     R3D_LAUNCH_CHECK("r3d_knn_topk(small)");
     return R3D_OK;
   }
   // large k; *status bit 0 reports survivor-buffer overflow (the caller re-runs with status == NULL, which selects the
   // insertion kernel)
   r3d_zero_words(status, 1, c.st);
-  const dim3 gb(grid.x, c.B, p.split ? 2 : 1);
-  if (bfa) {
+  const dim3 gb(grid.x, c.B, ch.split ? 2 : 1);
+  if (ch.bfa) {
     knn_pack_bf(c);
     rc = knn_append_launch<8, 384, 2, 32, 1, true, true>(c, gb, status, nullptr);
-  } else if (c.C % 64 == 0) {
+  } else if (ch.chan == KNN_CHAN_FULL) {
     rc = knn_append_launch<8, 384, 2, 32, 1, true>(c, gb, status, nullptr);
   } else {
     rc = knn_append_launch<8, 384, 2, 32, 1, false>(c, gb, status, nullptr);
   }
   if (rc) return rc;
-  if (p.split)
+  if (ch.split)
     hipLaunchKernelGGL(r3d_knn_merge_kernel, dim3(r3d_cdiv((long)c.B * c.N, 4)), dim3(256), 0, c.st, c.split_idx, c.split_sc, 2,
                        (long)c.B * c.N, c.k, c.n_dev, c.n_stride, c.N, c.idx, c.sc);
   R3D_LAUNCH_CHECK("r3d_knn_topk(big)");

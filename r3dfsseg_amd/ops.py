@@ -13,6 +13,13 @@ ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 SCORE_DGCNN, SCORE_L2 = 0, 1
 HD_SEG_COUNT, HD_SEG_M, HD_SEG_POFF, HD_N_PROTO, HD_N_NODES, HD_FPS_TIMEOUT = 0, 8, 16, 24, 25, 26
 HEAD_FPS_ONE_LAUNCH = 1
+# r3d_debug_knn_path: fields of the bit mask (include/r3d.h) and the values of the two enumerated ones
+KNN_PATH_MASK, KNN_PATH_FEW, KNN_PATH_SPLIT, KNN_PATH_BFA, KNN_PATH_FILTER = 0x3, 0x4, 0x8, 0x10, 0x20
+KNN_PATH_CHAN_SHIFT, KNN_PATH_CHAN_MASK, KNN_PATH_REGS_SHIFT, KNN_PATH_REGS_MASK = 6, 0xC0, 8, 0x300
+KNN_PATH_SMALL, KNN_PATH_LARGE, KNN_PATH_INSERTION = 0, 1, 2
+KNN_CHAN_ANY, KNN_CHAN_LE16, KNN_CHAN_FULL = 0 << 6, 1 << 6, 2 << 6
+KNN_REGS_1, KNN_REGS_2, KNN_REGS_4 = 1 << 8, 2 << 8, 3 << 8
+KNN_FLAG_STATUS, KNN_FLAG_X_CM, KNN_FLAG_NO_X, KNN_FLAG_FIXED_SCRATCH = 1, 2, 4, 8
 
 
 def _p(t):
@@ -203,6 +210,14 @@ def knn(x_pm, B, N, k, mode=SCORE_DGCNN, n_valid=None, return_scores=False, x_cm
         _lib.check(lib.r3d_knn_topk_batched(_p(x_pm), ld, _p(x_cm), B, N, C, k, mode, _p(n_valid), n_valid_stride, _p(ws), words,
                                             _p(idx), _p(sc), _p(status), _st()))
     return (idx, sc) if return_scores else idx
+
+
+def knn_path(x_pm, B, N, k, x_cm=None, status=None):
+    """The kernel configuration knn() launches for these operands under the debug switches as set: the KNN_PATH_* bit mask
+    of r3d_debug_knn_path.  Launches nothing."""
+    _, ld = _rows(x_pm)
+    flags = (KNN_FLAG_STATUS if status is not None else 0) | (KNN_FLAG_X_CM if x_cm is not None else 0)
+    return _lib.load().r3d_debug_knn_path(B, N, x_pm.shape[1], k, flags, ld, x_pm.data_ptr() % 16)
 
 
 def pointwise_conv(x_pm, W, scale=None, shift=None, act=ACT_NONE, out=None):

@@ -76,15 +76,24 @@ def test_knn_massive_duplicates_overflow_repair(ops):
     assert np.array_equal(got.cpu().numpy().astype(np.int64), want.numpy())
 
 
-@pytest.mark.parametrize("case", ["offset", "tiny", "mixed_scale", "nonfinite"])
-def test_knn_bf16_threshold_pass_keeps_the_bits(ops, case):
+@pytest.mark.parametrize("B,case", [pytest.param(B, case, id=case if B == 2 else "%s-B%d" % (case, B))
+                                    for B in (2, 9) for case in ("offset", "tiny", "mixed_scale", "nonfinite")])
+def test_knn_bf16_threshold_pass_keeps_the_bits(ops, B, case):
     """The streamed kernels estimate their selection threshold on the bf16 matrix core (csrc/knn.hip: BFA) -- a LOWER bound
     of every score, so the fp32 pass that emits neighbours and scores decides exactly what it decided before.  Inputs that
     strain the bound: a large common offset (norms >> distances: the margin 2^-12 (|x|^2 + |y|^2) dwarfs the score gaps,
     far more survivors, possibly the overflow repair), tiny values (pieces near the bf16 subnormal range), channels of
-    very different scale, and non-finite rows (no valid bound: the tile must be flagged and redone exactly)."""
+    very different scale, and non-finite rows (no valid bound: the tile must be flagged and redone exactly).
+
+    The bf16 passes run only above 256 query tiles (knn_plan: `few`).  B = 2 is 64 tiles: BOTH runs below are the 8-wave
+    fp32 kernel, the switch changes nothing, and the comparison only says that the call repeats itself.  B = 9 (288
+    tiles) is where the first run takes the bf16 threshold and filter passes and the second the 4-wave fp32 kernel; each
+    run asserts the configuration it is (r3d_debug_knn_path).  tests/test_gpu_knn_paths.py has the other configurations."""
     rs = np.random.RandomState(17)
-    B, C, N, k = 2, 64, 1024, 20
+    C, N, k = 64, 1024, 20
+    P_FP32 = ops.KNN_PATH_SMALL | ops.KNN_CHAN_FULL
+    path_bf, path_fp32 = ((P_FP32 | ops.KNN_PATH_FEW,) * 2 if B == 2 else
+                          (P_FP32 | ops.KNN_PATH_BFA | ops.KNN_PATH_FILTER, P_FP32))
     x = rs.randn(B, C, N).astype(np.float32)
     if case == "offset":
         x = x * 0.05 + 7.0
@@ -98,9 +107,12 @@ def test_knn_bf16_threshold_pass_keeps_the_bits(ops, case):
     x = torch.from_numpy(x)
     from r3dfsseg_amd import _lib
     lib = _lib.load()
-    got, gsc = ops.knn(ops.cm_to_pm(_dev(x)), B, N, k, return_scores=True)
+    x_pm = ops.cm_to_pm(_dev(x))
+    assert ops.knn_path(x_pm, B, N, k) == path_bf
+    got, gsc = ops.knn(x_pm, B, N, k, return_scores=True)
     old = lib.r3d_debug_set_knn_bf16_threshold(0)
     try:
+        assert ops.knn_path(x_pm, B, N, k) == path_fp32
         ref, rsc = ops.knn(ops.cm_to_pm(_dev(x)), B, N, k, return_scores=True)   # threshold pass on the fp32 core
     finally:
         lib.r3d_debug_set_knn_bf16_threshold(old)
