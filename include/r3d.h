@@ -644,6 +644,35 @@ int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy
                              float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, const void* labels,
                              int label_bytes, const int32_t* cloud_class, int32_t* mask, void* stream);
 
+/* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
+ * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
+ * episodes on the device").  Additive: the entry points above and what they compute are as they were.
+ * Pool: points (T, 6) fp32 rows x y z r g b, labels (T,) int32, offsets (n_blocks + 1,) int64: block k is rows
+ * offsets[k] .. offsets[k + 1] - 1, 1 .. 2^20 of them; T < 2^31.
+ * desc: (E (S + Q), 5) int32, one row {block, share_class, m_A, flags, key} per cloud, per episode the S support clouds then
+ * the Q query clouds (x_all order); flags bit 0: 0 support / 1 query (must agree with the position), bit 1: the ground-truth
+ * mask is zero.  classes: (E, n_way) int32, the sampled classes of every episode (n_way <= 32).
+ * With n the block's points, N <= 8192 the cloud's, c = share_class, mix / stream / draw the hash of r3d_augment_clouds,
+ * hA = stream(seed, 2 key), hB = stream(seed, 2 key + 1):
+ *   A   slots 0 .. m_A - 1: the m_A points of class c with the smallest (draw(hA, i), i), by ascending local index i;
+ *   B   n >= N: slots m_A .. N - 1: the N - m_A points with the smallest (draw(hB, i), i), by ascending i;
+ *   B'  n <  N: slot m_A + j = (uint64(draw(hB, j)) * n) >> 32;
+ *   C   over the N slots the prepared cloud of r3d_scene_prepare (the same device function): xyz - min, rgb / 255.0f at
+ *       rgb_ch, xyz' / max at XYZ_ch (a flat axis gives 0), written at out[b * o_sb + ch * o_sc + t * o_sn];
+ *   D   support cloud (e, i): mask[e S + i][t] = (label of slot t == c), gt_mask = mask, or zeros under flags bit 1;
+ *       query cloud (e, j): query_y[e Q + j][t] = gt_query_y = 1 + the first position of the label in classes[e], 0 if absent;
+ *       slot_map (E (S + Q), N) int32: the pool row of every slot.
+ * rec: 2 int32 words the caller zeroes.  A cloud whose descriptor cannot be cut (block outside the pool, m_A outside
+ * 0 .. min(N, points of class c), unknown flag bits, a kind that disagrees with the position, offsets outside the pool)
+ * writes nothing but rec[0] += 1 and rec[1] = max(rec[1], 1 + its index); every index is bounded before it is used.
+ * One 256-thread workgroup per cloud; the m smallest by a radix select over the draw (four 256-bin histograms in LDS,
+ * draws recomputed), ties by index, survivors compacted in index order by ballot and prefix count.  Integer counts and
+ * min / max only: the same descriptors and seed give the same bits, whatever else is in the launch. */
+int r3d_episode_cut(const float* points, const int32_t* labels, const int64_t* offsets, int n_blocks, long T,
+                    const int32_t* desc, const int32_t* classes, int E, int n_way, int S, int Q, int N, unsigned seed, int C,
+                    int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* mask, int32_t* gt_mask,
+                    int64_t* query_y, int64_t* gt_query_y, int32_t* slot_map, int32_t* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

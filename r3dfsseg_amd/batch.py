@@ -47,6 +47,31 @@ class EpisodeBatch:
         return EpisodeBatch(st(0), st(1), st(2), st(3), st(6) if full else None, st(7) if full else None,
                             st(10) if full else None)
 
+    @staticmethod
+    def from_x_all(x_all, n_way, k_shot, support_y, query_y, gt_support_y=None, gt_query_y=None, support_flag=None):
+        """A batch around clouds that were written as ONE (E, S + Q, C, N) tensor (block_pool.DeviceEpisodeSampler): x_all is
+        kept as it lies, contiguous channel-major or a point-major view; support_x / query_x are dense copies in its
+        layout (two device copies: the training launch sequences read the clouds through x_all alone)."""
+        E, SQ, C, N = x_all.shape
+        S = n_way * k_shot
+        if ops.is_point_major_view(x_all):
+            dense = lambda t: t.transpose(-1, -2).contiguous().transpose(-1, -2)
+        elif x_all.is_contiguous() and x_all.dtype == torch.float32:
+            dense = lambda t: t.contiguous()
+        else:
+            raise ValueError("from_x_all: x_all must be contiguous fp32 (E, S + Q, C, N) or a point-major view of that shape")
+        new = object.__new__(EpisodeBatch)
+        new.E = E
+        new.x_all = x_all
+        new.support_x = dense(x_all[:, :S]).reshape(E, n_way, k_shot, C, N)
+        new.query_x = dense(x_all[:, S:])
+        new.support_y = support_y.to(torch.int32).contiguous()
+        new.query_y = query_y.to(torch.int64).contiguous()
+        new.gt_support_y = (gt_support_y if gt_support_y is not None else support_y).to(torch.int32).contiguous()
+        new.gt_query_y = (gt_query_y if gt_query_y is not None else query_y).to(torch.int64).contiguous()
+        new.support_flag = support_flag.to(torch.int32).contiguous() if support_flag is not None else None
+        return new
+
     def __len__(self):
         return self.E
 

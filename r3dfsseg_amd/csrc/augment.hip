@@ -15,17 +15,9 @@
 #define AUG_THREADS 256
 #define AUG_MAX_C 9
 
-// draw `idx` of cloud stream `h` (h = aug_stream(seed, key)): 32 mixed bits
-static __device__ __forceinline__ unsigned aug_mix(unsigned x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-static __device__ __forceinline__ unsigned aug_stream(unsigned seed, unsigned key) {
-  return aug_mix(key * 0x9E3779B1u + seed) + seed * 0x85EBCA77u;
-}
-static __device__ __forceinline__ unsigned aug_draw(unsigned h, unsigned idx) { return aug_mix(h ^ (idx * 0x9E3779B1u + 0x632BE5ABu)); }
+// draw `idx` of cloud stream `h` (h = r3d_stream(seed, key)): 32 mixed bits, r3d_draw of common.h
 // [0, 1) in steps of 2^-24
-static __device__ __forceinline__ float aug_uniform(unsigned h, unsigned idx) { return (float)(aug_draw(h, idx) >> 8) * 0x1p-24f; }
+static __device__ __forceinline__ float aug_uniform(unsigned h, unsigned idx) { return (float)(r3d_draw(h, idx) >> 8) * 0x1p-24f; }
 
 // draws 0..3 of a stream make the matrix, draws 8 + 2 (3 point + axis) + {0, 1} the jitter of (point, axis)
 #define AUG_DRAW_SCALE 0u
@@ -37,7 +29,7 @@ static __device__ __forceinline__ float aug_uniform(unsigned h, unsigned idx) { 
 // clip(0.01 z, -0.05, 0.05), z standard normal by Box-Muller from two draws (|z| <= sqrt(48 ln 2) = 5.77: the clip acts)
 static __device__ __forceinline__ float aug_jitter(unsigned h, unsigned point, unsigned axis) {
   const unsigned i = AUG_DRAW_JITTER + 2u * (3u * point + axis);
-  const float u1 = (float)((aug_draw(h, i) >> 8) + 1u) * 0x1p-24f;  // (0, 1]
+  const float u1 = (float)((r3d_draw(h, i) >> 8) + 1u) * 0x1p-24f;  // (0, 1]
   const float u2 = aug_uniform(h, i + 1u);
   const float z = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958648f * u2);
   return fminf(fmaxf(0.01f * z, -0.05f), 0.05f);
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(AUG_THREADS) void r3d_augment_kernel(
   __shared__ float red[6][AUG_THREADS / R3D_WAVE];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (seed_dev) seed += *seed_dev;  // per-replay seed of a frozen launch sequence lives in device memory
-  const unsigned h = aug_stream(seed, first_key + (unsigned)b);
+  const unsigned h = r3d_stream(seed, first_key + (unsigned)b);
   x += (long)b * x_sb;
   out += (long)b * o_sb;
   const float* noise_b = noise ? noise + (long)b * N * 3 : nullptr;

@@ -91,6 +91,85 @@ static __device__ __forceinline__ float r3d_wave_max(float v) {
   return v;
 }
 
+// exclusive scan of the calling workgroup's value per thread; every thread also gets the workgroup's total
+template <int THREADS>
+static __device__ __forceinline__ int r3d_block_excl_scan(int v, int* wsum /* THREADS / 64 LDS ints */, int& total) {
+  const int incl = r3d_wave_incl_scan(v);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[w] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < THREADS / R3D_WAVE; ++k) {
+    const int s = wsum[k];
+    if (k < w) off += s;
+    tot += s;
+  }
+  __syncthreads();  // wsum may be written again by the caller's next round
+  total = tot;
+  return off + incl - v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Stateless random draws (augment.hip, episode_cut.hip): all a cloud draws is a function of (seed, cloud key); a stream
+// h = r3d_stream(seed, key) gives 32 mixed bits per draw index.
+static __device__ __forceinline__ unsigned r3d_mix(unsigned x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+static __device__ __forceinline__ unsigned r3d_stream(unsigned seed, unsigned key) {
+  return r3d_mix(key * 0x9E3779B1u + seed) + seed * 0x85EBCA77u;
+}
+static __device__ __forceinline__ unsigned r3d_draw(unsigned h, unsigned idx) { return r3d_mix(h ^ (idx * 0x9E3779B1u + 0x632BE5ABu)); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// A prepared cloud (dataloaders/loader.py:105-119, 258-276 in fp32) from N gathered rows `x y z [r g b]`: the ONE place
+// its arithmetic is written, shared by r3d_scene_prepare* (scene.hip) and r3d_episode_cut (episode_cut.hip).
+// r3d_prep_extent: a thread's running minima / maxima of xyz over its slots -> the workgroup's lo = min and
+// ext = max - min (== max over the slots of (xyz - min): the subtraction is monotone).  min / max only: the same
+// bits whatever the order.  red: 6 x (THREADS / 64) LDS floats.
+template <int THREADS>
+static __device__ __forceinline__ void r3d_prep_extent(float* mn, float* mx, float (*red)[THREADS / R3D_WAVE], float* lo,
+                                                       float* ext) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
+      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
+    }
+    if ((tid & 63) == 0) {
+      red[a][tid >> 6] = mn[a];
+      red[3 + a][tid >> 6] = mx[a];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float u = red[a][0], v = red[3 + a][0];
+#pragma unroll
+    for (int w = 1; w < THREADS / R3D_WAVE; ++w) {
+      u = fminf(u, red[a][w]);
+      v = fmaxf(v, red[3 + a][w]);
+    }
+    lo[a] = u;
+    ext[a] = v - u;
+  }
+}
+// one slot: q = its source row, o = its first output element, channels o_sc floats apart.  xyz - lo at channels 0-2,
+// rgb / 255.0f at rgb_ch (-1: none), xyz' / ext at XYZ_ch (-1: none; a flat axis gives 0, not the reference's 0 / 0).
+static __device__ __forceinline__ void r3d_prep_slot(const float* __restrict__ q, const float* lo, const float* ext, int rgb_ch,
+                                                     int XYZ_ch, float* __restrict__ o, long o_sc) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float v = q[a] - lo[a];
+    o[a * o_sc] = v;
+    if (XYZ_ch >= 0) o[(XYZ_ch + a) * o_sc] = ext[a] > 0.0f ? v / ext[a] : 0.0f;
+    if (rgb_ch >= 0) o[(rgb_ch + a) * o_sc] = q[3 + a] / 255.0f;
+  }
+}
+
 // keep ? v : 0 WITHOUT a select on the loaded value: hipcc (CodeGenPrepare) turns
 // `cond ? load : 0` -- even with the load hoisted by hand -- into a branch around the load and
 // then waits vmcnt(0) after every such load, serialising a whole staging pass.

@@ -250,25 +250,6 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_hist_kernel(const int* _
   hist[(long)threadIdx.x * n_tiles + t] = cnt[threadIdx.x];
 }
 
-// exclusive scan of the calling workgroup's value per thread; every thread also gets the workgroup's total
-template <int THREADS>
-static __device__ __forceinline__ int sc_block_excl_scan(int v, int* wsum /* THREADS / 64 + 1 LDS ints */, int& total) {
-  const int incl = r3d_wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63) wsum[w] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < THREADS / R3D_WAVE; ++k) {
-    const int s = wsum[k];
-    if (k < w) off += s;
-    tot += s;
-  }
-  __syncthreads();  // wsum may be written again by the caller's next round
-  total = tot;
-  return off + incl - v;
-}
-
 // in-place exclusive scan of a[0 .. n) in three launches: sums of SC_TILE-word blocks, scan of the sums, local scans
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_scan_sum_kernel(const int* __restrict__ a, long n,
                                                                         int* __restrict__ part) {
@@ -279,7 +260,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_scan_sum_kernel(const in
   for (int k = 0; k < SC_PER_THREAD; ++k)
     if (base + k < n) v += a[base + k];
   int total;
-  sc_block_excl_scan<SC_THREADS>(v, wsum, total);
+  r3d_block_excl_scan<SC_THREADS>(v, wsum, total);
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
@@ -290,7 +271,7 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_scan_part_kernel(in
     const int i = b + threadIdx.x;
     const int v = i < n ? part[i] : 0;
     int total;
-    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(v, wsum, total);
+    const int ex = r3d_block_excl_scan<SC_PLAN_THREADS>(v, wsum, total);
     if (i < n) part[i] = carry + ex;
     carry += total;
   }
@@ -308,7 +289,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_scan_local_kernel(int* _
     v += e[k];
   }
   int total;
-  int run = part[blockIdx.x] + sc_block_excl_scan<SC_THREADS>(v, wsum, total);
+  int run = part[blockIdx.x] + r3d_block_excl_scan<SC_THREADS>(v, wsum, total);
 #pragma unroll
   for (int k = 0; k < SC_PER_THREAD; ++k) {
     if (base + k < n) a[base + k] = run;
@@ -417,7 +398,7 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_blocks_kernel(const
       if (nc > 0) atomicAdd(&kept, 1);
     }
     int total;
-    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(nc, wsum, total);
+    const int ex = r3d_block_excl_scan<SC_PLAN_THREADS>(nc, wsum, total);
     if (b < nb) chunk0[b] = carry + ex;
     carry += total;
   }
@@ -596,44 +577,14 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
       mx[a] = fmaxf(mx[a], q[a]);
     }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
-      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
-    }
-    if ((tid & 63) == 0) {
-      red[a][tid >> 6] = mn[a];
-      red[3 + a][tid >> 6] = mx[a];
-    }
-  }
-  __syncthreads();
   float lo[3], ext[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float u = red[a][0], v = red[3 + a][0];
-#pragma unroll
-    for (int w = 1; w < SC_THREADS / R3D_WAVE; ++w) {
-      u = fminf(u, red[a][w]);
-      v = fmaxf(v, red[3 + a][w]);
-    }
-    lo[a] = u;
-    ext[a] = v - u;  // == max over the slots of (xyz - min): the subtraction is monotone
-  }
+  r3d_prep_extent<SC_THREADS>(mn, mx, red, lo, ext);
 
   for (int t = tid; t < N; t += SC_THREADS) {
     int p = order[sc_list_to_sorted(cell, g, bx, by, j + (t % len) * nc)];
     p = p < 0 ? 0 : (p >= M ? M - 1 : p);
     const float* q = scan + (long)p * ld;
-    float* o = out + (long)t * o_sn;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = q[a] - lo[a];
-      o[a * o_sc] = v;
-      if (XYZ_ch >= 0) o[(XYZ_ch + a) * o_sc] = ext[a] > 0.0f ? v / ext[a] : 0.0f;  // flat axis: 0, not the reference's 0 / 0
-      if (rgb_ch >= 0) o[(rgb_ch + a) * o_sc] = q[3 + a] / 255.0f;
-    }
+    r3d_prep_slot(q, lo, ext, rgb_ch, XYZ_ch, out + (long)t * o_sn, o_sc);
     if (slot_map) slot_map[(long)blockIdx.x * N + t] = p;
     if (mask) mask[(long)blockIdx.x * N + t] = (long long)labels[p] == (long long)cloud_class[blockIdx.x] ? 1 : 0;
   }
@@ -805,7 +756,7 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_run_scan_kernel(con
       rc = rc < 0 ? 0 : rc;
     }
     int total;
-    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(rc, wsum, total);
+    const int ex = r3d_block_excl_scan<SC_PLAN_THREADS>(rc, wsum, total);
     if (b < nb) run0[b] = carry + ex;
     carry += total;
   }
@@ -940,7 +891,7 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_transfer_tiles_kern
       t = u > 0 ? (u + SC_Q_TILE - 1) / SC_Q_TILE : 0;
     }
     int total;
-    const int ex = sc_block_excl_scan<SC_PLAN_THREADS>(t, wsum, total);
+    const int ex = r3d_block_excl_scan<SC_PLAN_THREADS>(t, wsum, total);
     if (c < n_cells) tile0[c] = carry + ex;
     carry += total;
   }

@@ -172,6 +172,78 @@ def _sample_k(source, num_point, scans, sampled_class, sampled_classes, support,
     return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]), np.stack([o[2] for o in out]))
 
 
+def episode_rules(rng, classes, class2scans, sampled_classes, k_shot, n_queries, mode, noise_ratio, noise_type,
+                  noise_pair_dict, cut, poor=None):
+    """The rules of generate_one_episode (loader.py:662-834) without the clouds: which blocks, which noisy shots, which
+    flags.  Draws from `rng` call for call as the reference does and calls `cut(scans, cls, support, partial) -> one item
+    per scan` where, and in the order in which, the reference cuts clouds (a cutter may draw from rng itself, as the
+    host sampler's does; block_pool.EpisodePlanner's records a descriptor instead).  poor(name): the re-draw test of
+    partial noise.  -> (ways, black, unused): per way (shots, gt_zero, flag, queries) -- the k_shot items in shuffled
+    order, whether a shot's ground-truth mask is zero, the (k_shot,) absolute class ids, the n_queries query items -- the
+    black list, and unused(cls) over it."""
+    if mode == "train":
+        n_noise = int(round(k_shot * rng.choice(noise_ratio)))
+    else:
+        n_noise = int(round(k_shot * noise_ratio))
+    if mode == "train":
+        noise_range = list(classes)
+    elif noise_type == "sym":
+        noise_range = list(sampled_classes)
+    elif noise_type == "ood":
+        noise_range = [c for c in classes if c not in sampled_classes]
+    elif noise_type in ("partial", "pair"):
+        noise_range = None
+    else:
+        raise NotImplementedError("noise type %s" % noise_type)
+    black = []
+
+    def unused(cls):
+        return [s for s in class2scans[cls] if s not in black]
+
+    ways = []
+    for cls in sampled_classes:
+        clean = rng.choice(unused(cls), k_shot - n_noise + n_queries, replace=False)
+        black.extend(clean)
+        q_scans, s_scans = clean[:n_queries], clean[n_queries:]
+        shots = list(cut(s_scans, cls, True, False))
+        queries = list(cut(q_scans, cls, False, False))
+        flag = np.zeros(k_shot)
+        flag[:len(s_scans)] = cls
+        if noise_type == "pair":
+            if noise_pair_dict is None:
+                raise AttributeError("noise_type 'pair' needs noise_pair_dict (commented out in loader.py:592-593)")
+            way_range = [noise_pair_dict[cls]]
+        elif noise_type == "partial":
+            way_range = [cls]
+        else:
+            way_range = list(noise_range)
+        for i in range(n_noise):
+            count = {c: 0 for c in way_range}  # re-created per shot, as loader.py:748 does
+            if noise_type in ("pair", "partial"):
+                noisy = rng.choice(way_range, 1)[0]
+            else:
+                noisy = cls
+                while noisy == cls:
+                    noisy = rng.choice(way_range, 1)[0]
+            candidates = unused(noisy)
+            scan = rng.choice(candidates, 1, replace=False)
+            if noise_type == "partial":
+                while poor(scan[0]):
+                    scan = rng.choice(candidates, 1, replace=False)
+            black.extend(scan)
+            shots += list(cut(scan, noisy, True, noise_type == "partial"))
+            count[noisy] += 1
+            if count[noisy] == k_shot - n_noise - 1:
+                way_range.remove(noisy)
+            flag[len(s_scans) + i] = noisy
+        assert len(shots) == k_shot
+        gt_zero = [j >= k_shot - n_noise for j in range(k_shot)]
+        order = np.arange(k_shot)
+        rng.shuffle(order)
+        ways.append(([shots[j] for j in order], [gt_zero[j] for j in order], flag[order], queries))
+    return ways, black, unused
+
+
 class NoiseEpisodeSampler:
     """generate_one_episode of the reference's NoiseInMetaTest (loader.py:562-890) on a block source.
 
@@ -200,77 +272,28 @@ class NoiseEpisodeSampler:
         return self.rng.choice(self.classes, self.n_way, replace=False)  # loader.py:618
 
     def generate_one_episode(self, sampled_classes):
-        rng, k_shot = self.rng, self.k_shot
-        if self.mode == "train":
-            n_noise = int(round(k_shot * rng.choice(self.noise_ratio)))
-        else:
-            n_noise = int(round(k_shot * self.noise_ratio))
-        if self.mode == "train":
-            noise_range = list(self.classes)
-        elif self.noise_type == "sym":
-            noise_range = list(sampled_classes)
-        elif self.noise_type == "ood":
-            noise_range = [c for c in self.classes if c not in sampled_classes]
-        elif self.noise_type in ("partial", "pair"):
-            noise_range = None
-        else:
-            raise NotImplementedError("noise type %s" % self.noise_type)
-        black = []
-        class2scans = self.source.class2scans
+        rng = self.rng
 
-        def unused(cls):
-            return [s for s in class2scans[cls] if s not in black]
+        def cut(scans, cls, support, partial):
+            return [sample_pointcloud(self.source.load(s), self.num_point, sampled_classes, cls, support, rng, partial,
+                                      pyrng=self.pyrng, pc_augm=self.augm is not None, pc_augm_config=self.augm) for s in scans]
 
+        def poor(name):  # loader.py:763-770: a block with fewer than 3 objects or classes is re-drawn
+            blk = self.source.load(name)
+            return len(np.unique(blk[:, -1])) < 3 or len(np.unique(blk[:, 6])) < 3
+
+        ways, black, unused = episode_rules(rng, self.classes, self.source.class2scans, sampled_classes, self.k_shot,
+                                            self.n_queries, self.mode, self.noise_ratio, self.noise_type, self.noise_pair_dict,
+                                            cut, poor)
         sup, mask, gt, flags, qry, qlab, gqlab = [], [], [], [], [], [], []
-        for cls in sampled_classes:
-            clean = rng.choice(unused(cls), k_shot - n_noise + self.n_queries, replace=False)
-            black.extend(clean)
-            q_scans, s_scans = clean[:self.n_queries], clean[self.n_queries:]
-            s_pc, s_mask, s_gt = _sample_k(self.source, self.num_point, s_scans, cls, sampled_classes, True, rng,
-                                           pyrng=self.pyrng, augm=self.augm)
-            q_pc, q_lab, q_gt = _sample_k(self.source, self.num_point, q_scans, cls, sampled_classes, False, rng,
-                                          pyrng=self.pyrng, augm=self.augm)
-            flag = np.zeros(k_shot)
-            flag[:len(s_scans)] = cls
-            if self.noise_type == "pair":
-                if self.noise_pair_dict is None:
-                    raise AttributeError("noise_type 'pair' needs noise_pair_dict (commented out in loader.py:592-593)")
-                way_range = [self.noise_pair_dict[cls]]
-            elif self.noise_type == "partial":
-                way_range = [cls]
-            else:
-                way_range = list(noise_range)
-            for i in range(n_noise):
-                count = {c: 0 for c in way_range}  # re-created per shot, as loader.py:748 does
-                if self.noise_type in ("pair", "partial"):
-                    noisy = rng.choice(way_range, 1)[0]
-                else:
-                    noisy = cls
-                    while noisy == cls:
-                        noisy = rng.choice(way_range, 1)[0]
-                candidates = unused(noisy)
-                scan = rng.choice(candidates, 1, replace=False)
-                if self.noise_type == "partial":  # loader.py:763-770: a block with fewer than 3 objects or classes is re-drawn
-                    def poor(name):
-                        blk = self.source.load(name)
-                        return len(np.unique(blk[:, -1])) < 3 or len(np.unique(blk[:, 6])) < 3
-                    while poor(scan[0]):
-                        scan = rng.choice(candidates, 1, replace=False)
-                black.extend(scan)
-                n_pc, n_mask, n_gt = _sample_k(self.source, self.num_point, scan, noisy, sampled_classes, True, rng,
-                                               partial_noise=self.noise_type == "partial", pyrng=self.pyrng, augm=self.augm)
-                s_pc, s_mask, s_gt = (np.concatenate([a, b], 0) for a, b in ((s_pc, n_pc), (s_mask, n_mask), (s_gt, n_gt)))
-                count[noisy] += 1
-                if count[noisy] == k_shot - n_noise - 1:
-                    way_range.remove(noisy)
-                flag[len(s_scans) + i] = noisy
-            if n_noise > 0:
-                s_gt[-n_noise:] = 0
-            assert len(s_pc) == k_shot
-            order = np.arange(k_shot)
-            rng.shuffle(order)
-            sup.append(s_pc[order]); mask.append(s_mask[order]); gt.append(s_gt[order]); flags.append(flag[order])
-            qry.append(q_pc); qlab.append(q_lab); gqlab.append(q_gt)
+        for shots, gt_zero, flag, queries in ways:
+            sup.append(np.stack([o[0] for o in shots]))
+            mask.append(np.stack([o[1] for o in shots]))
+            gt.append(np.stack([np.zeros_like(o[2]) if z else o[2] for o, z in zip(shots, gt_zero)]))
+            flags.append(flag)
+            qry.append(np.stack([o[0] for o in queries]))
+            qlab.append(np.stack([o[1] for o in queries]))
+            gqlab.append(np.stack([o[2] for o in queries]))
         bg_x, bg_y = [], []
         bg_classes = [c for c in self.classes if c not in sampled_classes]
         for _ in range(min(4, len(bg_classes))):  # loader.py:858-886

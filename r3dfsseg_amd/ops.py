@@ -837,3 +837,35 @@ def scene_prepare_blocks(scan, ncx, ncy, r, N, chunk_cap, ws, blocks, out, rgb_c
                                                     C, rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map),
                                                     _p(labels), nbytes, _p(cloud_class), _p(mask), _st()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- cutting episodes (block_pool.py)
+def episode_cut(points, labels, offsets, desc, classes, S, Q, N, seed, out, rgb_ch, XYZ_ch, mask, gt_mask, query_y, gt_query_y,
+                slot_map):
+    """r3d_episode_cut: the E (S + Q) clouds described by desc (E (S + Q), 5) int32, cut from the pool (points (T, 6) fp32,
+    labels (T,) int32, offsets (n_blocks + 1,) int64) -> out (E (S + Q), C, N) fp32, read as it lies (contiguous channel-major
+    or a transposed view of point-major rows), mask / gt_mask (E S, N) int32, query_y / gt_query_y (E Q, N) int64, slot_map
+    (E (S + Q), N) int32.  classes (E, n_way) int32.  Reads the kernel's record afterwards and raises ValueError when a
+    descriptor could not be cut; the clouds of the other descriptors are complete then, that cloud's outputs untouched."""
+    E, n_way = classes.shape
+    B = E * (S + Q)
+    for t, shape, dt in ((points, (points.shape[0], 6), torch.float32), (labels, (points.shape[0],), torch.int32),
+                         (offsets, (offsets.shape[0],), torch.int64), (desc, (B, 5), torch.int32),
+                         (classes, (E, n_way), torch.int32), (mask, (E * S, N), torch.int32), (gt_mask, (E * S, N), torch.int32),
+                         (query_y, (E * Q, N), torch.int64), (gt_query_y, (E * Q, N), torch.int64),
+                         (slot_map, (B, N), torch.int32)):
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous() and t.is_cuda, (tuple(t.shape), shape, t.dtype, dt)
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[2] == N and out.dtype == torch.float32 and out.is_cuda
+    rec = torch.zeros(2, device=out.device, dtype=torch.int32)
+    os_ = out.stride()
+    _lib.check(_lib.load().r3d_episode_cut(_p(points), _p(labels), _p(offsets), offsets.shape[0] - 1, points.shape[0], _p(desc),
+                                           _p(classes), E, n_way, S, Q, N, int(seed) & 0xffffffff, out.shape[1], rgb_ch, XYZ_ch,
+                                           _p(out), os_[0], os_[1], os_[2], _p(mask), _p(gt_mask),
+                                           _p(query_y) if Q else None, _p(gt_query_y) if Q else None, _p(slot_map), _p(rec),
+                                           _st()))
+    bad, last = rec.tolist()
+    if bad:
+        raise ValueError("episode_cut: %d of %d descriptors could not be cut (the last of them: cloud %d, %s): block outside "
+                         "the pool, m_A outside 0 .. min(N, points of the class), or flags that disagree with the position"
+                         % (bad, B, last - 1, desc[last - 1].tolist()))
+    return out
