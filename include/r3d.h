@@ -673,6 +673,34 @@ int r3d_episode_cut(const float* points, const int32_t* labels, const int64_t* o
                     int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* mask, int32_t* gt_mask,
                     int64_t* query_y, int64_t* gt_query_y, int32_t* slot_map, int32_t* rec, void* stream);
 
+/* ---- Partial noise in a cut episode (dataloaders/loader.py:239-322: one wrong object is flipped into a support mask and,
+ * with probability 0.3, one right object is taken out; :741-779: the shots it is applied to.  Definition: INTEGRATION.md,
+ * "Cutting episodes on the device", steps P0-P7).  Additive: r3d_episode_cut keeps its arguments and results and still
+ * refuses flags bit 2.
+ * r3d_episode_cut_partial takes r3d_episode_cut's arguments, then instances (T,) int32 -- the object id of every pool row,
+ * may be null -- and info (E (S + Q), 8) int32; rec has 4 words the caller zeroes.  A descriptor without flags bit 2 is cut
+ * with the bits of r3d_episode_cut and gets info = 0.  Bit 2 is legal on a support cloud with m_A == 0 when instances is
+ * given; otherwise the cloud is refused as any bad descriptor (rec[0], rec[1], nothing else written, info included).
+ * With bit 2, over the N slots of steps B / B' (m_A = 0: a uniform sample), lab / inst read through the slot:
+ *   mask0[t] = (lab[t] == c);  objects o_0 < .. < o_{K-1}: the distinct inst, ascending as signed;  first(o): the lowest
+ *   slot holding o;  eligible(o) = lab[first(o)] != c;  fg(o): some slot of o has mask0;  e, f: how many are eligible, fg;
+ *   multi = K > 1 and some lab[t] != lab[0];
+ *   flip, if multi and e > 0: the r-th eligible object, r = (uint64(draw(hA, 0)) * e) >> 32, joins the mask;
+ *   drop, if draw(hA, 1) > 0xB3333333 and f > 0: the r2-th fg object, r2 = (uint64(draw(hA, 2)) * f) >> 32, leaves it
+ *   (after the flip) -- unless that leaves no point, then it is not applied;
+ *   mask = the result, gt_mask = zeros under bit 1, else mask0.  A final mask without a point: rec[2] += 1,
+ *   rec[3] = max(rec[3], 1 + the cloud's index); the cloud is written in full.
+ *   info[cloud] = {K, e, f, did, o_flip, n_flip, o_drop, n_drop}: did bit 0 flipped, bit 1 dropped, bit 2 drop drawn but
+ *   skipped; n_*: slots holding the object; ids and counts 0 where nothing happened.
+ * The objects come from a bitonic sort of 64-bit keys (inst biased to unsigned << 32 | slot) in LDS, run ids and the r-th
+ * object from ballot counts, the flags from integer atomicOr: integers only, nothing depends on scheduling.  LDS: 8 P + 8 N
+ * bytes, P the power of two >= N (128 KiB at N = 8192). */
+int r3d_episode_cut_partial(const float* points, const int32_t* labels, const int64_t* offsets, int n_blocks, long T,
+                            const int32_t* desc, const int32_t* classes, int E, int n_way, int S, int Q, int N, unsigned seed,
+                            int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* mask,
+                            int32_t* gt_mask, int64_t* query_y, int64_t* gt_query_y, int32_t* slot_map, int32_t* rec,
+                            const int32_t* instances, int32_t* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,25 +9,33 @@ E (S + Q) clouds of a batch into an `EpisodeBatch` (`DeviceEpisodeSampler`).
 
 The random stream of the point draws is this library's own (the stateless hash of the device augmentation, keyed by
 (seed, cloud key)), not numpy's; tests/episode_cut_ref.py restates it in numpy and the kernel is held to it bit for bit.
-Not here: partial noise (it needs instance ids and a rejection loop over loaded blocks: use NoiseEpisodeSampler) and the
-four background clouds of the train layout (no model here reads them, EpisodeBatch does not carry them)."""
+Partial noise (noise_type="partial": a noisy shot is a block of the way's own class with one wrong OBJECT flipped into its
+mask and, with probability 0.3, one right object taken out; loader.py:239-322, 741-779) needs a pool built with
+instances=True: the planner answers the reference's "poor block" re-draw from the pool's books, the mask edit is steps
+P0-P7 of the definition in the same launch (r3d_episode_cut_partial; tests/episode_partial_ref.py restates it), and
+EpisodeBatch.partial_info records per cloud what was flipped and dropped.
+Not here: the four background clouds of the train layout (no model here reads them, EpisodeBatch does not carry them)."""
 import numpy as np
 import torch
 
 from .episode_sampler import episode_rules
 
 MAX_BLOCK_POINTS = 1 << 20
-FLAG_QUERY, FLAG_GT_ZERO = 1, 2
+FLAG_QUERY, FLAG_GT_ZERO, FLAG_PARTIAL = 1, 2, 4
 ATTRIB_SETS = {"xyz": (3, -1, -1), "xyzrgb": (6, 3, -1), "xyzXYZ": (6, -1, 3), "xyzrgbXYZ": (9, 3, 6)}  # C, rgb_ch, XYZ_ch
 
 
 class BlockPool:
     """The blocks of a source, concatenated: points (T, 6) fp32 rows x y z r g b, labels (T,) int32, offsets
     (n_blocks + 1,) int64 on `device`; on the host names, index[name], class2scans restricted to the pooled names and
-    count(block, cls), the points of class cls in a block (one bincount per block, taken while the array is in hand)."""
+    count(block, cls), the points of class cls in a block (one bincount per block, taken while the array is in hand).
+    Built with instances=True also: instances (T,) int32 on `device`, the object id of every point (the LAST column of a
+    block, as the reference indexes it: data[:, -1]), and on the host n_objects / n_classes (n_blocks,), the distinct object
+    ids / labels of every block.  Without: instances, n_objects and n_classes are None."""
 
-    def __init__(self, points, labels, offsets, names, class2scans, counts):
+    def __init__(self, points, labels, offsets, names, class2scans, counts, instances=None, n_objects=None, n_classes=None):
         self.points, self.labels, self.offsets = points, labels, offsets
+        self.instances, self.n_objects, self.n_classes = instances, n_objects, n_classes
         self.names = list(names)
         self.index = {n: i for i, n in enumerate(self.names)}
         self.class2scans = class2scans
@@ -35,16 +43,17 @@ class BlockPool:
         self.sizes = np.diff(offsets.cpu().numpy())  # host copy of the block sizes
 
     @staticmethod
-    def from_source(source, names=None, device="cuda"):
+    def from_source(source, names=None, device="cuda", instances=False):
         """source: any object with load(name) -> (n, >= 7) rows x y z r g b label ... and a class2scans dict (the contract of
         SyntheticBlocks and of the reference's block files).  names: the blocks to pool (default: every name listed in
-        class2scans, in order of first appearance)."""
+        class2scans, in order of first appearance).  instances: also pool the object ids, the last of >= 8 columns."""
         if names is None:
             names = list(dict.fromkeys(str(n) for c in source.class2scans for n in source.class2scans[c]))
         names = [str(n) for n in names]
         if not names or len(set(names)) != len(names):
             raise ValueError("BlockPool: %d names, %d distinct (need at least one, each once)" % (len(names), len(set(names))))
         pts, labs, counts, offsets = [], [], [], [0]
+        insts, n_obj, n_cls = [], [], []
         for name in names:
             blk = np.asarray(source.load(name))
             if blk.ndim != 2 or blk.shape[1] < 7:
@@ -58,6 +67,17 @@ class BlockPool:
                 raise ValueError("BlockPool: block %s has a label that is not an int32" % name)
             ids, cnt = np.unique(li, return_counts=True)  # (a bincount that also takes negative ids)
             counts.append({int(i): int(k) for i, k in zip(ids, cnt)})
+            if instances:
+                if blk.shape[1] < 8:
+                    raise ValueError("BlockPool: block %s has shape %s (instances=True: rows x y z r g b label ... instance)"
+                                     % (name, blk.shape))
+                ins = blk[:, -1]
+                ii = ins.astype(np.int64)
+                if not (np.all(np.isfinite(ins)) and np.all(ii == ins) and ii.min() >= -2 ** 31 and ii.max() < 2 ** 31):
+                    raise ValueError("BlockPool: block %s has an instance id that is not an int32" % name)
+                insts.append(ii.astype(np.int32))
+                n_obj.append(len(np.unique(ii)))
+                n_cls.append(len(ids))
             pts.append(blk[:, :6].astype(np.float32))
             labs.append(li.astype(np.int32))
             offsets.append(offsets[-1] + n)
@@ -67,7 +87,9 @@ class BlockPool:
         c2s = {c: [str(n) for n in v if str(n) in pooled] for c, v in source.class2scans.items()}
         dev = torch.device(device)
         return BlockPool(torch.from_numpy(np.concatenate(pts)).to(dev), torch.from_numpy(np.concatenate(labs)).to(dev),
-                         torch.tensor(offsets, dtype=torch.int64).to(dev), names, c2s, counts)
+                         torch.tensor(offsets, dtype=torch.int64).to(dev), names, c2s, counts,
+                         *((torch.from_numpy(np.concatenate(insts)).to(dev), np.array(n_obj), np.array(n_cls))
+                           if instances else ()))
 
     def __len__(self):
         return len(self.names)
@@ -118,10 +140,11 @@ class EpisodePlanner:
             noise_type = "train"
             if not isinstance(noise_ratio, list):
                 raise ValueError("train mode draws its noise ratio from a list")
-        if noise_type == "partial":
-            raise NotImplementedError("partial noise flips whole objects into the mask, which needs instance ids and a rejection "
-                                      "loop over loaded blocks: episode_sampler.NoiseEpisodeSampler does it on the host")
-        if noise_type not in ("train", "sym", "ood", "pair"):
+        if noise_type == "partial" and pool.instances is None:
+            raise NotImplementedError("partial noise flips whole objects into the mask, which needs instance ids: build the "
+                                      "pool with BlockPool.from_source(..., instances=True), or let "
+                                      "episode_sampler.NoiseEpisodeSampler do it on the host")
+        if noise_type not in ("train", "sym", "ood", "pair", "partial"):
             raise NotImplementedError("noise type %s" % noise_type)
         self.pool, self.classes = pool, np.array(classes)
         self.n_way, self.k_shot, self.n_queries, self.num_point = n_way, k_shot, n_queries, num_point
@@ -136,6 +159,8 @@ class EpisodePlanner:
         pool, N = self.pool, self.num_point
 
         def cut(scans, cls, support, partial):
+            if partial:  # the mask is edited, not shared out: a uniform sample (loader.py:222-223), steps P0-P7
+                return [[pool.index[str(s)], int(cls), 0, FLAG_PARTIAL] for s in scans]
             out = []
             for s in scans:
                 b = pool.index[str(s)]
@@ -146,8 +171,17 @@ class EpisodePlanner:
                 out.append([b, int(cls), m_A, 0 if support else FLAG_QUERY])
             return out
 
+        def poor(name):  # loader.py:755-763, from the pool's books: no block is loaded
+            b = pool.index[str(name)]
+            return pool.n_objects[b] < 3 or pool.n_classes[b] < 3
+
+        def stuck(cls, candidates):  # where the reference's re-draw loop would never end
+            if all(poor(s) for s in candidates):
+                raise ValueError("class %d: every one of its %d unused blocks has fewer than 3 objects or fewer than 3 "
+                                 "classes: no block to draw a partial-noise shot from" % (cls, len(candidates)))
+
         ways, black, _ = episode_rules(self.rng, self.classes, pool.class2scans, sc, self.k_shot, self.n_queries, self.mode,
-                                       self.noise_ratio, self.noise_type, self.noise_pair_dict, cut)
+                                       self.noise_ratio, self.noise_type, self.noise_pair_dict, cut, poor, stuck)
         rows = [[d[0], d[1], d[2], d[3] | (FLAG_GT_ZERO if z else 0), 0] for shots, gt_zero, _, _ in ways
                 for d, z in zip(shots, gt_zero)]
         rows += [d + [0] for _, _, _, queries in ways for d in queries]
@@ -159,10 +193,11 @@ class EpisodePlanner:
 class DeviceEpisodeSampler:
     """Episodes as EpisodeBatch objects on the pool's device.  batch(E): E plans on the host, ONE descriptor upload, ONE
     launch; gt_support_y, gt_query_y and support_flag are filled, .sampled_classes is (E, n_way) on the host, .slot_map
-    (E, S + Q, N) int32 the pool row of every point.  The cloud key of cloud i of the episode with counter c is
-    c (S + Q) + i, the convention of augment.py: a batch at counter c equals E single cuts at c, c + 1, ... bit for bit;
-    the counter advances by E per batch, as the augmentation's does.  layout: "cm" contiguous channel-major clouds,
-    "pm" point-major rows handed on as (.., C, N) views, which the encoder reads as they lie."""
+    (E, S + Q, N) int32 the pool row of every point, .partial_info (E, S + Q, 8) int32 under noise_type="partial" (per cloud
+    {K, e, f, did, o_flip, n_flip, o_drop, n_drop}, step P7; None otherwise).  The cloud key of cloud i of the episode with
+    counter c is c (S + Q) + i, the convention of augment.py: a batch at counter c equals E single cuts at c, c + 1, ... bit
+    for bit; the counter advances by E per batch, as the augmentation's does.  layout: "cm" contiguous channel-major
+    clouds, "pm" point-major rows handed on as (.., C, N) views, which the encoder reads as they lie."""
 
     def __init__(self, pool, classes, n_way=2, k_shot=5, n_queries=1, num_point=2048, mode="test", noise_ratio=0.4,
                  noise_type="sym", noise_pair_dict=None, seed=0, pc_attribs="xyzrgbXYZ", layout="cm"):
@@ -185,9 +220,14 @@ class DeviceEpisodeSampler:
     def check(self, desc):
         """The host's view of the kernel's own checks: raises before anything is launched."""
         pool, N = self.pool, self.num_point
+        S, Q = self.n_way * self.k_shot, self.n_way * self.n_queries
         for i, (b, c, m_A, flags, _) in enumerate(desc.tolist()):
             if not 0 <= b < len(pool):
                 raise ValueError("cloud %d: block %d outside the pool of %d" % (i, b, len(pool)))
+            if flags & FLAG_PARTIAL and (self.planner.noise_type != "partial" or pool.instances is None or flags & FLAG_QUERY
+                                         or i % (S + Q) >= S or m_A != 0):  # P0
+                raise ValueError("cloud %d: flags %d ask for partial noise, which is cut only by a partial-noise sampler over a "
+                                 "pool with instance ids, on a support cloud with m_A == 0 (m_A %d)" % (i, flags, m_A))
             if not 0 <= m_A <= min(N, pool.count(b, c)):
                 raise ValueError("cloud %d: m_A %d outside 0 .. min(N %d, the %d points of class %d in block %s)"
                                  % (i, m_A, N, pool.count(b, c), c, pool.names[b]))
@@ -225,8 +265,14 @@ class DeviceEpisodeSampler:
         qy = torch.empty(E * Q, N, device=dev, dtype=torch.int64)
         gt_qy = torch.empty_like(qy)
         slot_map = torch.empty(B, N, device=dev, dtype=torch.int32)
-        ops.episode_cut(pool.points, pool.labels, pool.offsets, desc_d, classes_d, S, Q, N, self.seed, x, rgb_ch, XYZ_ch, mask,
-                        gt_mask, qy, gt_qy, slot_map)
+        info = None
+        if self.planner.noise_type == "partial":
+            info = torch.empty(B, 8, device=dev, dtype=torch.int32)
+            ops.episode_cut_partial(pool.points, pool.labels, pool.offsets, desc_d, classes_d, S, Q, N, self.seed, x, rgb_ch,
+                                    XYZ_ch, mask, gt_mask, qy, gt_qy, slot_map, pool.instances, info)
+        else:
+            ops.episode_cut(pool.points, pool.labels, pool.offsets, desc_d, classes_d, S, Q, N, self.seed, x, rgb_ch, XYZ_ch,
+                            mask, gt_mask, qy, gt_qy, slot_map)
         flag = torch.from_numpy(np.stack([p.support_flag for p in plans])).to(dev)
         b = EpisodeBatch.from_x_all(x.unflatten(0, (E, S + Q)) if self.layout == "cm" else
                                     x.transpose(1, 2).unflatten(0, (E, S + Q)).transpose(2, 3),
@@ -234,5 +280,6 @@ class DeviceEpisodeSampler:
                                     gt_mask.view(E, n_way, k_shot, N), gt_qy.view(E, Q, N), flag)
         b.sampled_classes = classes
         b.slot_map = slot_map.view(E, S + Q, N)
+        b.partial_info = info.view(E, S + Q, 8) if info is not None else None
         b.plans = list(plans)
         return b

@@ -173,14 +173,16 @@ def _sample_k(source, num_point, scans, sampled_class, sampled_classes, support,
 
 
 def episode_rules(rng, classes, class2scans, sampled_classes, k_shot, n_queries, mode, noise_ratio, noise_type,
-                  noise_pair_dict, cut, poor=None):
+                  noise_pair_dict, cut, poor=None, stuck=None):
     """The rules of generate_one_episode (loader.py:662-834) without the clouds: which blocks, which noisy shots, which
     flags.  Draws from `rng` call for call as the reference does and calls `cut(scans, cls, support, partial) -> one item
     per scan` where, and in the order in which, the reference cuts clouds (a cutter may draw from rng itself, as the
     host sampler's does; block_pool.EpisodePlanner's records a descriptor instead).  poor(name): the re-draw test of
-    partial noise.  -> (ways, black, unused): per way (shots, gt_zero, flag, queries) -- the k_shot items in shuffled
-    order, whether a shot's ground-truth mask is zero, the (k_shot,) absolute class ids, the n_queries query items -- the
-    black list, and unused(cls) over it."""
+    partial noise.  stuck(cls, candidates), optional: called before that re-draw loop, without a draw (the planner raises
+    from it where the loop could not end; the host sampler passes none and loops as the reference does).
+    -> (ways, black, unused): per way (shots, gt_zero, flag, queries) -- the k_shot items in shuffled order, whether a
+    shot's ground-truth mask is zero, the (k_shot,) absolute class ids, the n_queries query items -- the black list, and
+    unused(cls) over it."""
     if mode == "train":
         n_noise = int(round(k_shot * rng.choice(noise_ratio)))
     else:
@@ -228,6 +230,8 @@ def episode_rules(rng, classes, class2scans, sampled_classes, k_shot, n_queries,
             candidates = unused(noisy)
             scan = rng.choice(candidates, 1, replace=False)
             if noise_type == "partial":
+                if stuck is not None:
+                    stuck(noisy, candidates)
                 while poor(scan[0]):
                     scan = rng.choice(candidates, 1, replace=False)
             black.extend(scan)

@@ -1,7 +1,11 @@
 """What cutting episodes on the device costs: DeviceEpisodeSampler.batch(E) on workload S (2-way 5-shot, 2048 points, train
 mode) against NoiseEpisodeSampler on the same source with its blocks cached in memory.
 
-    python tools/episode_cut_cost.py [--episodes 32] [--iters 20] [--out profiles/r16_episode_cut.md]
+    python tools/episode_cut_cost.py [--episodes 32] [--iters 20] [--noise train|sym|partial] [--out profiles/NAME.md]
+
+--noise: `train` (the default) is train mode with noise ratios 0 / 0.2 / 0.4; `sym` and `partial` are test mode at noise
+ratio 0.4.  The partial leg pools the instance ids and launches r3d_episode_cut_partial; the other two launch
+r3d_episode_cut (profiles/r17_episode_partial.md sets the three side by side).
 
 How the time is taken.  batch(): a host clock around calls that end in a device synchronise (the call itself reads the
 kernel's record back, so it ends synchronised anyway); after 3 warm-up calls, `iters` calls per round, 5 rounds, mean and
@@ -55,14 +59,20 @@ def main():
     ap.add_argument("--episodes", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--host-episodes", type=int, default=40)
+    ap.add_argument("--noise", default="train", choices=("train", "sym", "partial"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     E, N = args.episodes, 2048
     classes = list(range(1, 7))
-    shape = dict(n_way=2, k_shot=5, n_queries=1, num_point=N, mode="train", noise_ratio=[0.0, 0.2, 0.4], seed=0)
+    shape = dict(n_way=2, k_shot=5, n_queries=1, num_point=N, seed=0)
+    if args.noise == "train":
+        shape.update(mode="train", noise_ratio=[0.0, 0.2, 0.4])
+    else:
+        shape.update(mode="test", noise_type=args.noise, noise_ratio=0.4)
+    partial = args.noise == "partial"
     source = Cached(SyntheticBlocks(classes=classes, scans_per_class=24, points_per_block=3000, seed=0))
-    pool = BlockPool.from_source(source)
-    res = {"workload": "S", "episodes": E, "clouds": E * 12, "points": N, "blocks": len(pool), "pool_rows": int(pool.points.shape[0])}
+    pool = BlockPool.from_source(source, instances=True) if partial else BlockPool.from_source(source)
+    res = {"workload": "S", "noise": args.noise, "episodes": E, "clouds": E * 12, "points": N, "blocks": len(pool), "pool_rows": int(pool.points.shape[0])}
 
     for layout in ("cm", "pm"):
         s = DeviceEpisodeSampler(pool, classes, layout=layout, **shape)
@@ -81,8 +91,12 @@ def main():
     mask, gt = torch.empty(E * 10, N, device=dev, dtype=torch.int32), torch.empty(E * 10, N, device=dev, dtype=torch.int32)
     qy, gqy = torch.empty(E * 2, N, device=dev, dtype=torch.int64), torch.empty(E * 2, N, device=dev, dtype=torch.int64)
     sm = torch.empty(E * 12, N, device=dev, dtype=torch.int32)
-    launch = lambda: ops.episode_cut(pool.points, pool.labels, pool.offsets, desc, cls, 10, 2, N, 0, x, rgb_ch, XYZ_ch, mask, gt, qy,
-                                     gqy, sm)
+    cut_args = (pool.points, pool.labels, pool.offsets, desc, cls, 10, 2, N, 0, x, rgb_ch, XYZ_ch, mask, gt, qy, gqy, sm)
+    if partial:
+        info = torch.empty(E * 12, 8, device=dev, dtype=torch.int32)
+        launch = lambda: ops.episode_cut_partial(*cut_args, pool.instances, info)
+    else:
+        launch = lambda: ops.episode_cut(*cut_args)
     for _ in range(3):
         launch()
     ev = []
@@ -110,8 +124,8 @@ def main():
         with open(args.out, "w") as f:
             f.write("""# Cutting episodes on the device: what it costs
 
-`python tools/episode_cut_cost.py --episodes %d --iters %d` on one MI355X; workload S (2-way 5-shot, 1 query per way,
-2048 points, train mode, noise ratios 0 / 0.2 / 0.4), %d synthetic blocks of 2500 to 3500 points (%d pool rows)
+`python tools/episode_cut_cost.py --episodes %d --iters %d --noise %s` on one MI355X; workload S (2-way 5-shot, 1 query per
+way, 2048 points; %s), %d synthetic blocks of 2500 to 3500 points (%d pool rows)
 resident on the device; %d clouds per batch.
 
 | what | ms (mean of 5 rounds) | best round | episodes/s |
@@ -119,18 +133,21 @@ resident on the device; %d clouds per batch.
 | `DeviceEpisodeSampler.batch(%d)`, channel-major | %.3f | %.3f | %.0f |
 | `DeviceEpisodeSampler.batch(%d)`, point-major views | %.3f | %.3f | %.0f |
 | of which: %d `plan()` calls on the host | %.3f | %.3f | |
-| of which: the `r3d_episode_cut` launch with its record read | %.3f | %.3f | |
+| of which: the `%s` launch with its record read | %.3f | %.3f | |
 | `NoiseEpisodeSampler.episode()`, one core, blocks cached in memory | %.3f per episode | | %.0f |
 
 How the time was taken: `batch()`, `plan()` and the host sampler by a host clock around calls that end in a device
 synchronise (`batch()` reads the kernel's record back, so every call ends synchronised); 3 warm-up calls, %d calls per
-round, 5 rounds.  The launch by HIP events around %d back-to-back `ops.episode_cut` calls on resident descriptors, 5
+round, 5 rounds.  The launch by HIP events around %d back-to-back `ops.%s` calls on resident descriptors, 5
 rounds: the kernel and its record read, without planning, descriptor upload and the two dense copies `EpisodeBatch`
 keeps of `support_x` / `query_x`.  No profiler attached.  The trainer's rate is what `bench.py --gpus 1` reports
 (388 episodes/s in `BENCH_r04.json`).
-""" % (E, args.iters, len(pool), res["pool_rows"], E * 12, E, b["mean_ms"], b["best_ms"], b["episodes_per_s"], E,
+""" % (E, args.iters, args.noise,
+       "train mode, noise ratios 0 / 0.2 / 0.4" if args.noise == "train" else "test mode, %s noise at ratio 0.4" % args.noise,
+       len(pool), res["pool_rows"], E * 12, E, b["mean_ms"], b["best_ms"], b["episodes_per_s"], E,
        res["batch_pm"]["mean_ms"], res["batch_pm"]["best_ms"], res["batch_pm"]["episodes_per_s"], E, res["plan"]["mean_ms"],
-       res["plan"]["best_ms"], res["launch"]["mean_ms"], res["launch"]["best_ms"], ms, 1e3 / ms, args.iters, args.iters))
+       res["plan"]["best_ms"], "r3d_episode_cut_partial" if partial else "r3d_episode_cut", res["launch"]["mean_ms"],
+       res["launch"]["best_ms"], ms, 1e3 / ms, args.iters, args.iters, "episode_cut_partial" if partial else "episode_cut"))
 
 
 if __name__ == "__main__":
