@@ -343,9 +343,10 @@ int r3d_edge_select(float* zmax /*in: max, out: selected z*/, const float* zmin,
 long r3d_edge_reverse_ws_words(int B, int N, int K);
 int r3d_edge_reverse(const int32_t* idx, int B, int N, int K, int32_t* rev_ws, long ws_words, void* stream);
 /* bn2_sums [seg][2][64] in; dW2 (64,64) summed over the WHOLE batch, bn1_sums [seg][2][64], dPQ (B*N,128) out.
- * zwin (B*N,64): z2 of every max-pool winner (zmax after r3d_edge_select); esum: from r3d_edge_stats1.  Both given, N % 8 == 0
- * and r3d_set_matrix_arith(1): the three edge GEMMs of the backward run on the bf16 matrix core in three-piece arithmetic
- * (none decides an index: the winner and its side of the LeakyReLU kink come from argmax / zwin); else on the fp32 core. */
+ * zwin (B*N,64): z2 of every max-pool winner (zmax after r3d_edge_select); esum: from r3d_edge_stats1.  Both given, N % 8 == 0,
+ * dout 16-byte aligned with lddo % 4 == 0 and r3d_set_matrix_arith(1): the three edge GEMMs of the backward run on the bf16
+ * matrix core in three-piece arithmetic (none decides an index: the winner and its side of the LeakyReLU kink come from
+ * argmax / zwin); else on the fp32 core (r3d_debug_edgeconv_bwd_path tells which). */
 int r3d_edgeconv_bwd(const float* PQ, const int32_t* idx, const float* s1, const float* t1, const float* mean1,
                      const float* invstd1, const float* W2, const float* s2, const float* t2, const float* mean2,
                      const float* invstd2, long bn_stride, const float* bn2_sums, const float* dout, long lddo,
@@ -353,6 +354,11 @@ int r3d_edgeconv_bwd(const float* PQ, const int32_t* idx, const float* s1, const
                      int clouds_a, int clouds_b, float* DY1 /*(B*N*K,64) scratch*/, float* BE /*(B*N,128) scratch*/,
                      const int32_t* rev_ws /* r3d_edge_reverse of the same idx */, float* dW2, float* bn1_sums, float* dPQ,
                      float* ws, void* stream);
+/* test utility: the form r3d_edgeconv_bwd takes for these operands, as the launcher itself decides it (one host function
+ * serves both), under r3d_get_matrix_arith() as it is set: 1 = bf16 x 3, 0 = fp32 core.  The bf16 x 3 form needs
+ * r3d_set_matrix_arith(1), zwin and esum (have_zwin_esum != 0), N % 8 == 0, lddo % 4 == 0 and a 16-byte aligned dout
+ * (dout_misalign_bytes: its address modulo 16).  Launches nothing, needs no device. */
+int r3d_debug_edgeconv_bwd_path(int N, long lddo, int dout_misalign_bytes, int have_zwin_esum);
 
 /* head backward (reference: autograd through models/mpti.py:488-512,571) for n_ep episodes.  r3d_ce_grad_batched -> G =
  * dL/dZ (scaled by the device scalar *gscale_dev); r3d_label_propagate_bwd_batched: adjoint CG solve on the graph

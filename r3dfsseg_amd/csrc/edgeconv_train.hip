@@ -861,14 +861,28 @@ extern "C" int r3d_edge_reverse(const int32_t* idx, int B, int N, int K, int32_t
   return R3D_OK;
 }
 
+// The form r3d_edgeconv_bwd's pass B1 takes: the bf16 x 3 kernel (edgeconv_bwd_bx3.h) under r3d_set_matrix_arith(1) when the
+// forward's zwin and esum are given, a cloud is whole units of EB_PTS points (N % 8 == 0) and the kernel's 16-byte loads of
+// dout rows are aligned (dout itself, and lddo % 4 == 0); the fp32-core kernel otherwise.  One function: the launcher and
+// r3d_debug_edgeconv_bwd_path cannot disagree.
+static bool et_bwd_bx3(int N, long lddo, int dout_misalign_bytes, bool have_zwin_esum) {
+  return g_r3d_matrix_arith == 1 && have_zwin_esum && N % EB_PTS == 0 && (lddo & 3) == 0 && (dout_misalign_bytes & 15) == 0;
+}
+// test utility: 1 = bf16 x 3, 0 = fp32 core, as r3d_edgeconv_bwd decides it for these operands under the arithmetic that is
+// set.  Launches nothing, needs no device.
+extern "C" int r3d_debug_edgeconv_bwd_path(int N, long lddo, int dout_misalign_bytes, int have_zwin_esum) {
+  return et_bwd_bx3(N, lddo, dout_misalign_bytes, have_zwin_esum != 0) ? 1 : 0;
+}
+
 // Backward over all B clouds of a batch.  The BatchNorm vectors of both edge layers (s1 .. invstd2) hold one set per
 // segment at + s * bn_stride; bn2_sums [seg][2][64] = (sum dy2, sum dy2*zhat2) of every segment (from the point-level
 // winners, computed by the caller with r3d_colstats_seg mode 1 on zmax).  Outputs: dW2 (64,64) summed over the WHOLE batch,
 // bn1_sums [seg][2][64] (sum dy1, sum dy1*ehat1), dPQ (B*N,128) (every entry written).  Scratch: DY1 B*N*K*64 floats, BE
 // B*N*128 floats, ws r3d_edgeconv_train_ws_words(B, N); rev_ws from r3d_edge_reverse on the same idx.
 // zwin (B*N, 64): z2 of every (point, channel)'s max-pool winner as r3d_edge_select left it in zmax; esum (B*N, 64): sum_t e1
-// from r3d_edge_stats1.  With both given, N % 8 == 0 and r3d_set_matrix_arith(1) (the default) the edge GEMMs run on the
-// bf16 matrix core in three-piece arithmetic (edgeconv_bwd_bx3.h); otherwise (either may be NULL) on the fp32 core.
+// from r3d_edge_stats1.  With both given, N % 8 == 0, an aligned dout and r3d_set_matrix_arith(1) (the default) the edge GEMMs
+// run on the bf16 matrix core in three-piece arithmetic (edgeconv_bwd_bx3.h); otherwise (either may be NULL) on the fp32
+// core: et_bwd_bx3 above.
 extern "C" int r3d_edgeconv_bwd(const float* PQ, const int32_t* idx, const float* s1, const float* t1, const float* mean1,
                                 const float* invstd1, const float* W2, const float* s2, const float* t2, const float* mean2,
                                 const float* invstd2, long bn_stride, const float* bn2_sums, const float* dout, long lddo,
@@ -889,7 +903,7 @@ extern "C" int r3d_edgeconv_bwd(const float* PQ, const int32_t* idx, const float
   float* part_bn = ws + (long)ET_MAXBLK * 4096;
   const EcBn bn{s1, t1, mean1, invstd1, s2, t2, mean2, invstd2, bn_stride};
   int grid = 0;
-  const bool bx3 = g_r3d_matrix_arith == 1 && zwin && esum && N % EB_PTS == 0 && (lddo & 3) == 0 && ((uintptr_t)dout & 15) == 0;
+  const bool bx3 = et_bwd_bx3(N, lddo, (int)((uintptr_t)dout & 15), zwin && esum);
 #define E2_CASE(RT)                                                                                                        \
   case RT:                                                                                                                 \
     rc = bx3 ? bwd1_bx3_launch_rt<RT>(n_chunks, st, PQ, idx, bn, W2, bn2_sums, dout, lddo, argmax, zwin, gm, cs, DY1, BE,  \

@@ -190,6 +190,25 @@ def test_abi_argument_validation_without_gpu():
     assert rc != 0 and b"r3d_graph_set_lp_budget" in lib.r3d_last_error_string()
 
 
+def test_edgeconv_bwd_path_states_the_three_fallbacks_without_gpu():
+    """r3d_debug_edgeconv_bwd_path (the host function r3d_edgeconv_bwd branches on): bf16 x 3 only under arithmetic 1 with
+    zwin and esum, N % 8 == 0, lddo % 4 == 0 and a 16-byte aligned dout; the fp32 core otherwise."""
+    lib = _lib.load()
+    before = lib.r3d_get_matrix_arith()
+    try:
+        _lib.check(lib.r3d_set_matrix_arith(1))
+        assert lib.r3d_debug_edgeconv_bwd_path(40, 64, 0, 1) == 1 and lib.r3d_debug_edgeconv_bwd_path(1064, 192, 0, 1) == 1
+        assert lib.r3d_debug_edgeconv_bwd_path(36, 64, 0, 1) == 0    # N % 8 != 0
+        assert lib.r3d_debug_edgeconv_bwd_path(40, 64, 4, 1) == 0    # dout not 16-byte aligned
+        assert lib.r3d_debug_edgeconv_bwd_path(40, 67, 0, 1) == 0    # lddo % 4 != 0
+        assert lib.r3d_debug_edgeconv_bwd_path(40, 64, 0, 0) == 0    # no zwin / esum
+        _lib.check(lib.r3d_set_matrix_arith(0))
+        assert lib.r3d_debug_edgeconv_bwd_path(40, 64, 0, 1) == 0
+    finally:
+        _lib.check(lib.r3d_set_matrix_arith(before))
+    assert "r3d_debug_edgeconv_bwd_path" in _lib._SIGS and _lib._SIGS["r3d_debug_edgeconv_bwd_path"] == (_lib.c_i, [_lib.c_i, _lib.c_l, _lib.c_i, _lib.c_i])
+
+
 def test_state_dict_names_match_reference_contract():
     """Key names and shapes of SURVEY.md 8b (verified there against the reference DGCNN)."""
     from r3dfsseg_amd.mpti import MPTI_SelfAtten
