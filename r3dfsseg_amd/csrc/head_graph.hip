@@ -652,7 +652,10 @@ static __device__ __forceinline__ void cg_block_partials(const float4* rs, const
                                                          float4* sm, float4* wpart /* [2][4][HG_M] */) {
   const int a = threadIdx.x & 63, w = threadIdx.x >> 6;
   float4 t = f4_zero(), t2 = f4_zero();
-  // rows >= n carry r = 0 and u = 0 in LDS (the callers zero them), so no row guard is needed
+  // rows >= n carry r = 0 and u = 0 in LDS (the callers zero them), so no row guard is needed.
+  // (Unrolled by 16, m[k] is indexed by the loop counter and lives in scratch: 272 B per lane, the 40 MB per launch the
+  // write counter shows for r3d_cg_update_kernel.  Unrolled whole it stays in registers, the kernel takes 256 of them and
+  // no scratch -- and the same 36 us per launch: profiles/r18_cg_spmv.md.)
 #pragma unroll 16
   for (int k = 0; k < 64; ++k) {
     const float4 rv = rs[64 * w + k];
@@ -949,23 +952,42 @@ __global__ __launch_bounds__(256) void r3d_cg_spmv_kernel(
 // S with the residual of the system in LDS (n x float4 <= SL_MAX_LDS).  Once a batch of systems streams its matrices
 // from HBM, what is left in the way is the gather: every matrix entry fetches a 16-byte row of r through a 64-byte L2
 // sector (4 x the traffic, ~14 TB/s of sector reads per iteration for 32 systems of workload S) -- the launch was bound
-// by L2 -> CU bandwidth at 1.6 TB/s of algorithmic bytes.  Here a workgroup of 8 waves takes SL_ROWS consecutive rows of
+// by L2 -> CU bandwidth at 1.6 TB/s of algorithmic bytes.  Here a workgroup of 8 waves takes a share of the rows of
 // ONE system, stages that system's r in LDS once (70 KB at S: coalesced, 12 % of what the gathers read) and gathers
-// from there; a wave walks 16 rows with the next row's column / value loads in flight behind the current row's
-// gather, and the 16 row tails (p, q updates) run lane-parallel with coalesced loads and stores.  The arithmetic is
+// from there, and the row tails (p, q updates) run lane-parallel with coalesced loads and stores.  The arithmetic is
 // that of r3d_cg_spmv_kernel bit for bit, INCLUDING the <p, q> partials (one per 4 rows, added in row order): which of
 // the two kernels a solve runs on -- a matter of how many systems the launch holds -- changes no bit of its result.
+//
+// ONE RESIDENT ROUND: the launch holds as many workgroups per system as the chip keeps resident at once (lp_solve asks
+// the occupancy query), and a workgroup goes on through its share of the system's 4-row groups -- r is staged once per
+// workgroup, not once per 128 rows, and no partly filled last round trails the launch.  A wave sees its rows in passes
+// of SL_PASS_RPW = 64 (their CSR bounds sit one per lane); the <p q> products of a pass meet in LDS.
+//
+// THE MATRIX STREAM RUNS AHEAD OF THE GATHER: a wave's work is a flat list of items, one per (row, 384-entry chunk), and
+// the column / value / (M W) loads of the next SL_DEPTH items are in flight while an item is gathered -- a cursor walks
+// the list SL_DEPTH items ahead of the consumer and does not care where a row ends, so the chunks of a hub row (trained
+// state: 1100 rows of 32 systems hold more than 1024 entries) stream like everything else instead of being one exposed
+// round trip each.  An item is 13 registers in flight; the value's mask is applied when the item is consumed.
+// Measured (32 systems of workload S, us per SpMV + update pair, fresh weights / after 150 optimiser steps; the form
+// before this one -- one workgroup per 128 rows, 1120 of them in 2.2 rounds, hub chunks one exposed trip each -- 107 /
+// 142): depth 1 89.9 / 98.0, depth 2 89.5 / 97.8, depth 3 (gathers in two halves to stay under 128 registers) 89.2 /
+// 95.8, run-to-run spread ~2.  The depth does not show: with 16 waves per CU one item of lookahead covers the memory
+// round trip, provided it never breaks at a row or chunk boundary.  What pays is the resident round (the kernel alone,
+// every system alive: 68.5 -> 47.9 us for 265 MB of algorithmic bytes, 3.9 -> 5.5 TB/s) and, on the trained graphs,
+// the hub chunks riding the list.
 //
 // WHICH rows a wave takes is free (the whole r is in LDS), and it matters: the graph's hubs are the prototype nodes, the
 // first ~200 rows of a system, and they grow with training (after 150 optimiser steps at S: mean row 273 entries,
 // p99.9 2745; the 16 consecutive hub rows of one wave held 10 x the entries of an average wave and the iteration took
 // 181 us instead of 107).  So the 4-row groups of the system are dealt cyclically to its workgroups (group c n_wg + b is
-// the c-th of workgroup b) and the 128 rows of a workgroup cyclically to its 8 waves (local row 8 k + w is the k-th of
+// the c-th of workgroup b) and the rows of a workgroup cyclically to its 8 waves (local row 8 k + w is the k-th of
 // wave w): consecutive hub rows land in different waves of different workgroups.  The four <p q> products of a group
 // then sit in four waves; they meet in LDS and are added in row order as before.
 #define SL_ROWS 128
 #define SL_WAVES 8
-#define SL_RPW (SL_ROWS / SL_WAVES)
+#define SL_PASS_RPW 64                          // rows of a wave per pass
+#define SL_PASS_ROWS (SL_PASS_RPW * SL_WAVES)   // rows of a workgroup per pass
+#define SL_DEPTH 2                              // items in flight ahead of the one being gathered
 #define SL_MAX_LDS (144 * 1024)
 __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
     const int* __restrict__ row_ptr, const hg_col_t* __restrict__ col, const float* __restrict__ val,
@@ -982,23 +1004,11 @@ __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
     HG_WS(row_ptr); HG_WS(col); HG_WS(val); HG_WS(dinv); HG_WS(agg); HG_WS(MW); HG_AT(n_dev, st.desc); HG_WS(r); HG_WS(p);
     HG_WS(q); HG_WS(part_pq);
   }
-  __shared__ float4 pq_s[SL_ROWS];  // the <p q> products of the workgroup's rows, by local row
+  __shared__ float4 pq_s[SL_PASS_ROWS];  // the <p q> products of the pass's rows, by local row
   const int n = min(*n_dev, n_cap);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int n_wg = gridDim.x, bx = blockIdx.x;
   const int n_part = (n_cap + 3) / 4;  // partials of <p, q>: one per 4 rows, as r3d_cg_spmv_kernel with rows_per_block = 4
-  // the k-th row of this wave: local row l = 8 k + w of the workgroup = member l & 3 of its group l >> 2
-  auto row_of = [&](int k) {
-    const int l = SL_WAVES * k + w;
-    return 4 * ((l >> 2) * n_wg + bx) + (l & 3);
-  };
-  // (rows ascend with k, so the rows below n are a prefix of the wave's 16)
-  int nrows = 0;
-#pragma unroll
-  for (int k = 0; k < SL_RPW; ++k) nrows += row_of(k) < n ? 1 : 0;  // uniform over the wave
-  // this wave's row bounds: lane k holds those of its k-th row
-  const int my_row = min(row_of(min(lane, SL_RPW - 1)), max(n - 1, 0));
-  const int my_rb = row_ptr[my_row], my_re = row_ptr[my_row + 1];
   // stage r: 4 float4 per thread in flight
   for (int i0 = tid; i0 < n; i0 += 4 * 64 * SL_WAVES) {
     float4 v[4];
@@ -1009,143 +1019,155 @@ __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
       if (i0 + u * 64 * SL_WAVES < n) rs[i0 + u * 64 * SL_WAVES] = v[u];
   }
   if (tid < HG_M) mu_s[tid] = reinterpret_cast<const float4*>(cg->mu)[tid];
-  const float4 beta = *reinterpret_cast<const float4*>(cg->beta);
   __syncthreads();
   const float4 mul = mu_s[lane];
-  int jv[6], jn[6];
-  float av[6], an[6];
-  float mw = 0.f, mwn = 0.f;
-  auto issue = [&](int k, int (&jj)[6], float (&aa)[6], float& mm) {
-    const int rb = __builtin_amdgcn_readlane(my_rb, k), re = __builtin_amdgcn_readlane(my_re, k);
+  const int n_c = (n_part + n_wg - 1) / n_wg;  // 4-row groups of this workgroup (the last may lie beyond n_part)
+  for (int c0 = 0; c0 < n_c; c0 += SL_PASS_ROWS / 4) {
+    // the k-th row of this wave in this pass: local row l = 8 k + w of the workgroup = member l & 3 of its group l >> 2
+    auto row_of = [&](int k) {
+      const int l = SL_WAVES * k + w;
+      return 4 * ((c0 + (l >> 2)) * n_wg + bx) + (l & 3);
+    };
+    // this wave's row bounds: lane k holds those of its k-th row (rows ascend with k: the rows below n are a prefix)
+    const int nrows = __popcll(__ballot(row_of(lane) < n));  // uniform over the wave
+    const int my_row = min(row_of(lane), max(n - 1, 0));
+    const int my_rb = row_ptr[my_row], my_re = row_ptr[my_row + 1];
+    // the ring of items in flight and the cursor that fills it: row ck of the pass, entries from ce on, row end cre
+    int rj[SL_DEPTH][6];
+    float ra[SL_DEPTH][6], rm[SL_DEPTH];
 #pragma unroll
-    for (int u = 0; u < 6; ++u) {
-      const int e = rb + lane + 64 * u;
-      const int ec = max(min(e, re - 1), 0);
-      jj[u] = col[ec];
-      aa[u] = r3d_keep(val[ec], e < re);
+    for (int d = 0; d < SL_DEPTH; ++d) {
+#pragma unroll
+      for (int u = 0; u < 6; ++u) { rj[d][u] = 0; ra[d][u] = 0.f; }
+      rm[d] = 0.f;
     }
-    mm = MW[(long)row_of(k) * HG_M + lane];
-  };
-  // Rows go in two groups of 8.  A lane keeps its partial sums of the group's rows in registers and the 64 lanes'
-  // partials meet in ONE transposed butterfly per group: the xor-32 step halves the rows a lane is responsible for (it
-  // sends the other half to its partner), xor-16 and xor-8 halve again, and the last three steps run on the one row
-  // left -- lanes 8 g .. 8 g + 7 end up with the total of row g.  Every row still sees the pairs (l, l ^ 32), (l, l ^ 16),
-  // ... (l, l ^ 1) in this order, i.e. the additions of the plain butterfly of r3d_cg_spmv_kernel (x + y = y + x bit for
-  // bit), at 5 cross-lane moves per row and column instead of 24: the moves go through the LDS crossbar, which the
-  // gathers need (the first version of this kernel was bound by exactly that: 153 us per launch, as slow as gathering
-  // from L2).
-  float4 tot[2] = {f4_zero(), f4_zero()};  // lanes 8 g ..: row 8 h + g of this wave (h = group)
-  if (nrows > 0) issue(0, jv, av, mw);
+    int ck = 0, ce = __builtin_amdgcn_readlane(my_rb, 0), cre = __builtin_amdgcn_readlane(my_re, 0);
+    auto issue = [&](int (&jj)[6], float (&aa)[6], float& mm) {
+      if (ck < nrows) {  // uniform
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float4 acc[8];
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const int k = 8 * h + kk;
-      acc[kk] = f4_zero();
-      if (k < nrows) {  // uniform
-        if (k + 1 < nrows) issue(k + 1, jn, an, mwn);
-        const int rb = __builtin_amdgcn_readlane(my_rb, k), re = __builtin_amdgcn_readlane(my_re, k);
-        float4 s = f4_zero();
-        {
-          float4 rj[6];
-#pragma unroll
-          for (int u = 0; u < 6; ++u) rj[u] = rs[jv[u]];
-#pragma unroll
-          for (int u = 0; u < 6; ++u) {
-            s.x = __builtin_fmaf(av[u], rj[u].x, s.x); s.y = __builtin_fmaf(av[u], rj[u].y, s.y);
-            s.z = __builtin_fmaf(av[u], rj[u].z, s.z); s.w = __builtin_fmaf(av[u], rj[u].w, s.w);
-          }
+        for (int u = 0; u < 6; ++u) {
+          const int ec = max(min(ce + lane + 64 * u, cre - 1), 0);
+          jj[u] = col[ec];
+          aa[u] = val[ec];
         }
-        // rows with more than 384 entries (uniform trip count).  (Prefetching the next 384 entries behind the current
-        // gather made the whole kernel slower -- 141 -> 194 us per iteration in the trained state: the registers it takes
-        // cost every row.)
-        for (int e0 = rb + 384; e0 < re; e0 += 384) {
-          int j2[6];
-          float a2[6];
-#pragma unroll
-          for (int u = 0; u < 6; ++u) {
-            const int e = e0 + lane + 64 * u;
-            const int ec = min(e, re - 1);
-            j2[u] = col[ec];
-            a2[u] = r3d_keep(val[ec], e < re);
-          }
-#pragma unroll
-          for (int u = 0; u < 6; ++u) {
-            const float4 rj = rs[j2[u]];
-            s.x = __builtin_fmaf(a2[u], rj.x, s.x); s.y = __builtin_fmaf(a2[u], rj.y, s.y);
-            s.z = __builtin_fmaf(a2[u], rj.z, s.z); s.w = __builtin_fmaf(a2[u], rj.w, s.w);
-          }
+        mm = MW[(long)row_of(ck) * HG_M + lane];
+        ce += 384;
+        if (ce >= cre) {  // on to the next row (a row without entries is one item all the same)
+          ++ck;
+          const int kc = __builtin_amdgcn_readfirstlane(min(ck, SL_PASS_RPW - 1));
+          ce = __builtin_amdgcn_readlane(my_rb, kc);
+          cre = __builtin_amdgcn_readlane(my_re, kc);
         }
-        // (M W) mu rides the same butterfly: per lane -alpha s + MW[i][lane] mu[lane]
-        s.x = __builtin_fmaf(mw, mul.x, -alpha_lp * s.x); s.y = __builtin_fmaf(mw, mul.y, -alpha_lp * s.y);
-        s.z = __builtin_fmaf(mw, mul.z, -alpha_lp * s.z); s.w = __builtin_fmaf(mw, mul.w, -alpha_lp * s.w);
-        acc[kk] = s;
-#pragma unroll
-        for (int u = 0; u < 6; ++u) { jv[u] = jn[u]; av[u] = an[u]; }
-        mw = mwn;
       }
-    }
-    // transposed butterfly: 8 rows -> 4 -> 2 -> 1 row per lane, then the plain steps
-    float4 a4[4], a2[2], a1;
-    {
-      const bool hi = (lane & 32) != 0;
+    };
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float4 keepv = hi ? acc[4 + t] : acc[t], sendv = hi ? acc[t] : acc[4 + t];
-        a4[t].x = keepv.x + __shfl_xor(sendv.x, 32); a4[t].y = keepv.y + __shfl_xor(sendv.y, 32);
-        a4[t].z = keepv.z + __shfl_xor(sendv.z, 32); a4[t].w = keepv.w + __shfl_xor(sendv.w, 32);
+    for (int d = 0; d < SL_DEPTH; ++d) issue(rj[d], ra[d], rm[d]);
+    // Rows go in groups of 4.  A lane keeps its partial sums of the group's rows in registers and the 64 lanes'
+    // partials meet in ONE transposed butterfly per group: the xor-32 step halves the rows a lane is responsible for (it
+    // sends the other half to its partner), xor-16 halves again, and the last four steps run on the one row left --
+    // lanes 16 g .. 16 g + 15 end up with the total of row g.  Every row still sees the pairs (l, l ^ 32), (l, l ^ 16),
+    // ... (l, l ^ 1) in this order, i.e. the additions of the plain butterfly of r3d_cg_spmv_kernel (x + y = y + x bit for
+    // bit), at 7 cross-lane moves per 4 rows and column instead of 24: the moves go through the LDS crossbar, which the
+    // gathers need (the first version of this kernel was bound by exactly that: 153 us per launch, as slow as gathering
+    // from L2).  (Groups of 8 rows take 5 moves per 4 rows and 16 registers more: with two items in flight that is over
+    // the 128 registers at which two workgroups share a CU.)
+    float4 tot = f4_zero();  // lane 16 g + h: row 4 h + g of this wave's pass
+    const int ngrp = (nrows + 3) >> 2;
+    for (int h = 0; h < ngrp; ++h) {
+      float4 acc[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const int k = 4 * h + kk;
+        acc[kk] = f4_zero();
+        if (k < nrows) {  // uniform
+          const int kc = __builtin_amdgcn_readfirstlane(k);
+          const int rb = __builtin_amdgcn_readlane(my_rb, kc), re = __builtin_amdgcn_readlane(my_re, kc);
+          float4 s = f4_zero();
+          float mw = 0.f;
+          int e0 = rb;
+          do {  // the row's items, 384 entries each (uniform trip count): entry e0 + lane + 64 u is this lane's u-th
+            int cj[6];
+            float ca[6];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) { cj[u] = rj[0][u]; ca[u] = ra[0][u]; }
+            mw = rm[0];
+#pragma unroll
+            for (int d = 0; d + 1 < SL_DEPTH; ++d) {
+#pragma unroll
+              for (int u = 0; u < 6; ++u) { rj[d][u] = rj[d + 1][u]; ra[d][u] = ra[d + 1][u]; }
+              rm[d] = rm[d + 1];
+            }
+            issue(rj[SL_DEPTH - 1], ra[SL_DEPTH - 1], rm[SL_DEPTH - 1]);
+            float4 g[6];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) g[u] = rs[cj[u]];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+              const float a = r3d_keep(ca[u], e0 + lane + 64 * u < re);
+              s.x = __builtin_fmaf(a, g[u].x, s.x); s.y = __builtin_fmaf(a, g[u].y, s.y);
+              s.z = __builtin_fmaf(a, g[u].z, s.z); s.w = __builtin_fmaf(a, g[u].w, s.w);
+            }
+            e0 += 384;
+          } while (e0 < re);
+          // (M W) mu rides the same butterfly: per lane -alpha s + MW[i][lane] mu[lane]
+          s.x = __builtin_fmaf(mw, mul.x, -alpha_lp * s.x); s.y = __builtin_fmaf(mw, mul.y, -alpha_lp * s.y);
+          s.z = __builtin_fmaf(mw, mul.z, -alpha_lp * s.z); s.w = __builtin_fmaf(mw, mul.w, -alpha_lp * s.w);
+          acc[kk] = s;
+        }
       }
-    }
-    {
-      const bool hi = (lane & 16) != 0;
+      // transposed butterfly: 4 rows -> 2 -> 1 row per lane, then the plain steps
+      float4 a2[2], a1;
+      {
+        const bool hi = (lane & 32) != 0;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float4 keepv = hi ? a4[2 + t] : a4[t], sendv = hi ? a4[t] : a4[2 + t];
-        a2[t].x = keepv.x + __shfl_xor(sendv.x, 16); a2[t].y = keepv.y + __shfl_xor(sendv.y, 16);
-        a2[t].z = keepv.z + __shfl_xor(sendv.z, 16); a2[t].w = keepv.w + __shfl_xor(sendv.w, 16);
+        for (int t = 0; t < 2; ++t) {
+          const float4 keepv = hi ? acc[2 + t] : acc[t], sendv = hi ? acc[t] : acc[2 + t];
+          a2[t].x = keepv.x + __shfl_xor(sendv.x, 32); a2[t].y = keepv.y + __shfl_xor(sendv.y, 32);
+          a2[t].z = keepv.z + __shfl_xor(sendv.z, 32); a2[t].w = keepv.w + __shfl_xor(sendv.w, 32);
+        }
       }
-    }
-    {
-      const bool hi = (lane & 8) != 0;
-      const float4 keepv = hi ? a2[1] : a2[0], sendv = hi ? a2[0] : a2[1];
-      a1.x = keepv.x + __shfl_xor(sendv.x, 8); a1.y = keepv.y + __shfl_xor(sendv.y, 8);
-      a1.z = keepv.z + __shfl_xor(sendv.z, 8); a1.w = keepv.w + __shfl_xor(sendv.w, 8);
-    }
+      {
+        const bool hi = (lane & 16) != 0;
+        const float4 keepv = hi ? a2[1] : a2[0], sendv = hi ? a2[0] : a2[1];
+        a1.x = keepv.x + __shfl_xor(sendv.x, 16); a1.y = keepv.y + __shfl_xor(sendv.y, 16);
+        a1.z = keepv.z + __shfl_xor(sendv.z, 16); a1.w = keepv.w + __shfl_xor(sendv.w, 16);
+      }
 #pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-      a1.x += __shfl_xor(a1.x, o); a1.y += __shfl_xor(a1.y, o);
-      a1.z += __shfl_xor(a1.z, o); a1.w += __shfl_xor(a1.w, o);
+      for (int o = 8; o > 0; o >>= 1) {
+        a1.x += __shfl_xor(a1.x, o); a1.y += __shfl_xor(a1.y, o);
+        a1.z += __shfl_xor(a1.z, o); a1.w += __shfl_xor(a1.w, o);
+      }
+      if ((lane & 15) == h) tot = a1;
     }
-    tot[h] = a1;
-  }
-  // the wave's row tails: lane 8 g + h takes row 8 h + g (16 lanes busy; rows of a group sit 8 lanes apart)
-  float4 acc_pq = f4_zero();
-  const int trow = 8 * (lane & 7) + (lane >> 3);  // (meaningful for lane & 7 < 2)
-  if ((lane & 7) < 2 && trow < nrows) {
-    const float4 keep = (lane & 1) ? tot[1] : tot[0];
-    const int i = row_of(trow);
-    const float4 ri = rs[i], pi = p[i], qi = q[i];
-    const float u = 1.f / dinv[i];
-    const float4 m = mu_s[agg[i]];
-    const float4 pn = make_float4((ri.x + u * m.x) + beta.x * pi.x, (ri.y + u * m.y) + beta.y * pi.y,
-                                  (ri.z + u * m.z) + beta.z * pi.z, (ri.w + u * m.w) + beta.w * pi.w);
-    const float4 qn = make_float4((ri.x + keep.x) + beta.x * qi.x, (ri.y + keep.y) + beta.y * qi.y,
-                                  (ri.z + keep.z) + beta.z * qi.z, (ri.w + keep.w) + beta.w * qi.w);
-    p[i] = pn;
-    q[i] = qn;
-    acc_pq = make_float4(pn.x * qn.x, pn.y * qn.y, pn.z * qn.z, pn.w * qn.w);
-  }
-  // one partial per 4 rows, ((r0 + r1) + r2) + r3: the order in which r3d_cg_spmv_kernel adds its four waves.  The rows
-  // of a group are the k-th rows of four neighbouring waves: through LDS (rows beyond n contribute the zero they hold).
-  if ((lane & 7) < 2) pq_s[SL_WAVES * trow + w] = acc_pq;
-  __syncthreads();
-  if (tid < SL_ROWS / 4) {
-    const float4 a = pq_s[4 * tid], b2 = pq_s[4 * tid + 1], c2 = pq_s[4 * tid + 2], d2 = pq_s[4 * tid + 3];
-    const float4 t = make_float4(((a.x + b2.x) + c2.x) + d2.x, ((a.y + b2.y) + c2.y) + d2.y, ((a.z + b2.z) + c2.z) + d2.z,
-                                 ((a.w + b2.w) + c2.w) + d2.w);
-    const int gidx = tid * n_wg + bx;
-    if (gidx < n_part) part_pq[gidx] = t;
+    // the wave's row tails: lane 16 g + h takes row 4 h + g (rows of a group of 4 sit 16 lanes apart)
+    float4 acc_pq = f4_zero();
+    const int trow = 4 * (lane & 15) + (lane >> 4);
+    if (trow < nrows) {
+      const int i = row_of(trow);
+      const float4 beta = *reinterpret_cast<const float4*>(cg->beta);
+      const float4 ri = rs[i], pi = p[i], qi = q[i];
+      const float u = 1.f / dinv[i];
+      const float4 m = mu_s[agg[i]];
+      const float4 pn = make_float4((ri.x + u * m.x) + beta.x * pi.x, (ri.y + u * m.y) + beta.y * pi.y,
+                                    (ri.z + u * m.z) + beta.z * pi.z, (ri.w + u * m.w) + beta.w * pi.w);
+      const float4 qn = make_float4((ri.x + tot.x) + beta.x * qi.x, (ri.y + tot.y) + beta.y * qi.y,
+                                    (ri.z + tot.z) + beta.z * qi.z, (ri.w + tot.w) + beta.w * qi.w);
+      p[i] = pn;
+      q[i] = qn;
+      acc_pq = make_float4(pn.x * qn.x, pn.y * qn.y, pn.z * qn.z, pn.w * qn.w);
+    }
+    // one partial per 4 rows, ((r0 + r1) + r2) + r3: the order in which r3d_cg_spmv_kernel adds its four waves.  The rows
+    // of a group are the k-th rows of four neighbouring waves: through LDS (rows beyond n contribute the zero they hold).
+    pq_s[SL_WAVES * trow + w] = acc_pq;
+    __syncthreads();
+    if (tid < SL_PASS_ROWS / 4) {
+      const float4 a = pq_s[4 * tid], b2 = pq_s[4 * tid + 1], c2 = pq_s[4 * tid + 2], d2 = pq_s[4 * tid + 3];
+      const float4 t = make_float4(((a.x + b2.x) + c2.x) + d2.x, ((a.y + b2.y) + c2.y) + d2.y, ((a.z + b2.z) + c2.z) + d2.z,
+                                   ((a.w + b2.w) + c2.w) + d2.w);
+      const int gidx = (c0 + tid) * n_wg + bx;
+      if (gidx < n_part) part_pq[gidx] = t;  // (groups past the workgroup's n_c lie past n_part)
+    }
+    __syncthreads();  // pq_s is free for the next pass
   }
 }
 
@@ -1429,6 +1451,26 @@ extern "C" int r3d_debug_set_cg_spmv_lds_min_blocks(int min_blocks) {
   return old;
 }
 
+// Workgroups of r3d_cg_spmv_lds_kernel the chip holds at once with lds_r bytes of residual each (occupancy x CUs; asked
+// once per size).
+static int cg_lds_slots(size_t lds_r) {
+  static size_t asked = 0;
+  static int slots = 0;
+  if (lds_r != asked || !slots) {
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_cg_spmv_lds_kernel, 64 * SL_WAVES, lds_r) == hipSuccess &&
+        per_cu > 0 && hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+      slots = per_cu * cus;
+    else {
+      (void)hipGetLastError();
+      slots = 256;  // one workgroup per CU: always resident
+    }
+    asked = lds_r;
+  }
+  return slots;
+}
+
 // two-level CG on the already built graphs and coarse spaces: X = (I - alpha S)^-1 RHS for every system of the batch.
 // rhs_stride / x_stride: float4 rows between the systems' right-hand sides / solutions.
 static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int32_t* n_dev, int n_cap, float alpha, int max_iter,
@@ -1445,8 +1487,8 @@ static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int3
   for (int mode = 0; mode < 2; ++mode)
     hipLaunchKernelGGL(r3d_cg_init_kernel, dim3(nblk_v, n_ep), dim3(256), 0, st, (const float4*)RHS, L.dinv, L.agg, L.MW, n_dev,
                        n_cap, mode, x, L.r, L.p, L.q, L.part, L.Einv, tol2, L.cg, ep, rhs_stride, x_stride);
-  // the SpMV with the residual in LDS when it fits and the launch holds enough systems to fill the chip with 128-row
-  // workgroups (a single system is 35 of them at workload S: there the one-row-per-wave kernel, 1099 workgroups, is the
+  // the SpMV with the residual in LDS when it fits and the launch holds enough systems to fill the chip at one workgroup
+  // per 128 rows (a single system is 35 of them at workload S: there the one-row-per-wave kernel, 1099 workgroups, is the
   // faster one); same bits either way
   const size_t lds_r = (size_t)n_cap * sizeof(float4);
   const bool use_lds = lds_r <= SL_MAX_LDS && rpb == HG_ROWS_PER_BLOCK_MIN && (long)n_ep * r3d_cdiv(n_cap, SL_ROWS) >= g_cg_lds_min_blocks;
@@ -1458,7 +1500,9 @@ static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int3
       attr = lds_r;
     }
   }
-  const int nblk_l = r3d_cdiv(n_cap, SL_ROWS);
+  // one resident round: the workgroups the chip holds at once, shared out among the systems (a system never takes more
+  // than one per 128 rows, and a batch of more systems than slots runs one workgroup per system in several rounds)
+  const int nblk_l = use_lds ? std::max(1, std::min(r3d_cdiv(n_cap, SL_ROWS), cg_lds_slots(lds_r) / n_ep)) : 0;
   const int nblk_pq = nblk_s;  // (the LDS kernel writes the same 4-row partials)
   for (int it = 0; it < max_iter; ++it) {
     if (use_lds)
