@@ -327,6 +327,16 @@ __global__ void r3d_graph_normalize_kernel(const int* __restrict__ row_ptr, cons
 //                         rz, beta, convergence test -- the step that was a one-workgroup launch of its own (R) at first:
 //                         every launch on this dependent chain costs ~3 us of dispatch plus a ~2 us memory hop between
 //                         XCDs (measured: R 7.5 us, U 7.5 us, S 6.4 us per iteration as three launches)
+//    LDS form of S (r3d_cg_spmv_lds_kernel, batches of systems): ONE launch per iteration.  Launch j > 0 does U's work of
+//    iteration j - 1 in its head -- every workgroup of a system forms alpha and r - alpha q of all rows on its way into
+//    LDS, x += alpha p on its own rows, the 256-row blocks of U's partition are dealt to the system's workgroups, the
+//    one whose ticket comes last runs the same reduction step and PUBLISHES mu, beta and the convergence decision as
+//    {tag = j, value} words; the others wait for them inside the launch (bounded, with the first matrix items already
+//    on their way) and go on to the SpMV.  A solve is init, init, K_0 .. K_{T-1}, one closing U: T + 3 launches for
+//    2 T + 2, same arithmetic, same bits.  LIVENESS: a workgroup waits only for workgroups of its own system, none of
+//    which waits before its ticket, and lp_solve keeps all workgroups of a launch resident (or gives a system one
+//    workgroup, which then waits for itself); a wait that runs out of polls (CG_SPIN_LIMIT) sets CgState::fail, the
+//    solve stops and reports "not converged", which the callers already redo.
 //    Why not one persistent kernel with a grid barrier: measured on MI355X (tools/probe/grid_barrier.hip) a
 //    device-wide barrier whose workgroups exchange data needs agent-scope release/acquire fences, i.e. an L2
 //    write-back + invalidate per workgroup, and costs 3 us at 32 workgroups, 7 us at 128 and 13 us at 256.
@@ -341,17 +351,27 @@ struct CgState {            // device memory
   int done;                 // set once every column has converged; later S / U launches return at once
   int iters;                // iterations performed when `done` was set (or so far)
   unsigned ticket;          // workgroups of the vector kernels that have delivered their partials (zeroed per solve)
-  int pad_;
+  unsigned ticket_k;        // the same for the fused S launches, which add another count per launch (zeroed per solve)
   float bb[HG_NC];          // ||b||^2
   float rz[HG_NC];          // <r, z> of the current iteration
   float beta[HG_NC];
   float mu[HG_M * HG_NC];   // E^-1 (W^T r - (MW)^T r) of the current iteration; c0 = E^-1 W^T b before the first
+  int fail;                 // a fused S launch gave up waiting for its coefficients: the solve stops and reports "not converged"
+  int pad_;
+  // what the last workgroup of a fused S launch hands to the others INSIDE the launch, as {tag = iteration, value}
+  // words: mu, beta, and whether the system has converged (zeroed per solve: no tag of an earlier solve survives)
+  unsigned long long pub[HG_M * HG_NC + HG_NC + 1];
 };
+#define CG_PUB_BETA (HG_M * HG_NC)
+#define CG_PUB_CONV (HG_M * HG_NC + HG_NC)
+#define CG_SPIN_LIMIT (1 << 18)  // polls of a fused S launch for its coefficients before it gives up (~0.3 s)
+static_assert(offsetof(CgState, pub) % 8 == 0 && sizeof(CgState) % 4 == 0, "CgState: the published words are 8-byte words");
 
 static __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// fixed-order block reduction of a float4, result broadcast to all threads
-static __device__ __forceinline__ float4 block_sum4(float4 v, float4* sm /*[4]*/) {
+// fixed-order block reduction of a float4 over 256 threads, result broadcast to all threads.  In a workgroup of 512
+// (the fused S) the two halves reduce independently, each as a workgroup of 256 would: sm holds 4 entries per half.
+static __device__ __forceinline__ float4 block_sum4(float4 v, float4* sm /*[4] per 256 threads*/) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -361,14 +381,16 @@ static __device__ __forceinline__ float4 block_sum4(float4 v, float4* sm /*[4]*/
   __syncthreads();
   if (lane == 0) sm[w] = v;
   __syncthreads();
-  float4 r = sm[0];
-  for (int q = 1; q < 4; ++q) { r.x += sm[q].x; r.y += sm[q].y; r.z += sm[q].z; r.w += sm[q].w; }
+  const float4* sh = sm + (w & ~3);
+  float4 r = sh[0];
+  for (int q = 1; q < 4; ++q) { r.x += sh[q].x; r.y += sh[q].y; r.z += sh[q].z; r.w += sh[q].w; }
   return r;
 }
 
+// (in a workgroup of 512 both halves compute the same sum: thread t and thread t + 256 take the same partials)
 static __device__ __forceinline__ float4 reduce_partials(const float4* part, int nblk, float4* sm) {
   float4 a = f4_zero();
-  for (int q0 = threadIdx.x; q0 < nblk; q0 += 8 * 256) {  // 8 loads in flight per trip (blockDim.x == 256), fixed add order
+  for (int q0 = threadIdx.x & 255; q0 < nblk; q0 += 8 * 256) {  // 8 loads in flight per trip, fixed add order
     float4 p[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -694,47 +716,97 @@ static __device__ __forceinline__ void cg_block_partials(const float4* rs, const
 // The reduction step between U and S, run by the workgroup that delivered its partials last.
 // phase 0: c0 = E^-1 W^T b, bb (partials of b itself); phase 1: mu, rz, beta, convergence test before iteration `it`.
 // ev: column a = tid & 63 of E^-1 in registers (loaded by the caller at kernel start).
+// K8: called by the 8 waves of the fused S (phase 1 only).  Waves 0 .. 3 are the 256 threads of the other form; waves
+// 4 .. 7 take the t2 and rr partials off them (the sums keep their order; 64 + 96 registers in flight do not fit the
+// 128 of that kernel) and hand the sums over in LDS.  pub (K8): the coefficients also go out as {tag, value} words for
+// the workgroups waiting INSIDE this launch -- relaxed agent-scope 8-byte stores, the data is the flag
+// (cdna_hip_programming.md Guideline 16, form R2).
+static __device__ __forceinline__ void cg_publish(unsigned long long* g, unsigned tag, unsigned value) {
+  __hip_atomic_store(g, ((unsigned long long)tag << 32) | value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool K8>
 static __device__ __forceinline__ void cg_reduce_step(const float* __restrict__ part, int nblk, const float* __restrict__ Einv,
                                                       int phase, int it, float tol2, CgState* __restrict__ cg, double* d_s,
-                                                      float* t_s, float* rr_s) {
-  const int a = threadIdx.x & 63, c = threadIdx.x >> 6;
+                                                      float* t_s, float* rr_s, unsigned tag = 0) {
+  const int a = threadIdx.x & 63, c = (threadIdx.x >> 6) & 3;
+  const bool lo = !K8 || threadIdx.x < 256;  // uniform over a wave
   // column a of E^-1 (symmetric: read as row-strided, coalesced over the lanes), requested together with the partials.
   // (Measured with phase stamps: prefetching it in EVERY workgroup at kernel start put 64 more loads in front of the
   // alpha-dependent work of all 18 workgroups -- the 63-deep vmcnt queue turns that into a third load round.)
   float ev[HG_M];
-#pragma unroll
-  for (int b = 0; b < HG_M; ++b) ev[b] = Einv[b * HG_M + a];
   const float rz_old = cg->rz[c];
   const float bbv = cg->bb[threadIdx.x & 3];
   float t = 0.f, t2 = 0.f, rrp = 0.f;
   const float* pa = part + 4 + a * HG_NC + c;
-  for (int b0 = 0; b0 < nblk; b0 += 32) {  // 32 workgroups' partials in flight per trip (ONE trip at workload S: each
-    // trip is a ~2 us round trip to the memory side); the add order stays fixed
-    float tv[32], t2v[32], rv[32];
+  // 32 workgroups' partials in flight per trip (ONE trip at workload S: each trip is a ~2 us round trip to the memory
+  // side); the add order stays fixed.  sc1 loads: the partials were stored write-through by other workgroups of THIS
+  // launch (cg_delivered_last)
+  if (!K8) {
 #pragma unroll
-    for (int u = 0; u < 32; ++u) {
-      const long b = min(b0 + u, nblk - 1);
-      const bool ok = b0 + u < nblk;
-      // sc1 loads: the partials were stored write-through by other workgroups of THIS launch (cg_delivered_last)
-      tv[u] = r3d_keep(cg_load_sc1(pa + b * HG_PART), ok);
-      t2v[u] = r3d_keep(cg_load_sc1(pa + b * HG_PART + HG_M * HG_NC), ok);
-      rv[u] = r3d_keep(cg_load_sc1(part + b * HG_PART + (threadIdx.x & 3)), ok);
+    for (int b = 0; b < HG_M; ++b) ev[b] = Einv[b * HG_M + a];
+    for (int b0 = 0; b0 < nblk; b0 += 32) {
+      float tv[32], t2v[32], rv[32];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) {
+        const long b = min(b0 + u, nblk - 1);
+        const bool ok = b0 + u < nblk;
+        tv[u] = r3d_keep(cg_load_sc1(pa + b * HG_PART), ok);
+        t2v[u] = r3d_keep(cg_load_sc1(pa + b * HG_PART + HG_M * HG_NC), ok);
+        rv[u] = r3d_keep(cg_load_sc1(part + b * HG_PART + (threadIdx.x & 3)), ok);
+      }
+#pragma unroll
+      for (int u = 0; u < 32; ++u) { t += tv[u]; t2 += t2v[u]; rrp += rv[u]; }
     }
+    if (threadIdx.x < HG_NC) rr_s[threadIdx.x] = rrp;
+  } else {
+    if (lo) {
 #pragma unroll
-    for (int u = 0; u < 32; ++u) { t += tv[u]; t2 += t2v[u]; rrp += rv[u]; }
+      for (int b = 0; b < HG_M; ++b) ev[b] = Einv[b * HG_M + a];
+      for (int b0 = 0; b0 < nblk; b0 += 32) {
+        float tv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) tv[u] = r3d_keep(cg_load_sc1(pa + (long)min(b0 + u, nblk - 1) * HG_PART), b0 + u < nblk);
+#pragma unroll
+        for (int u = 0; u < 32; ++u) t += tv[u];
+      }
+    } else {
+      for (int b0 = 0; b0 < nblk; b0 += 32) {
+        float t2v[32], rv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) {
+          const long b = min(b0 + u, nblk - 1);
+          const bool ok = b0 + u < nblk;
+          t2v[u] = r3d_keep(cg_load_sc1(pa + b * HG_PART + HG_M * HG_NC), ok);
+          rv[u] = r3d_keep(cg_load_sc1(part + b * HG_PART + (threadIdx.x & 3)), ok);
+        }
+#pragma unroll
+        for (int u = 0; u < 32; ++u) { t2 += t2v[u]; rrp += rv[u]; }
+      }
+      t_s[a * HG_NC + c] = t2;  // waves 4 .. 7 -> waves 0 .. 3 (t_s carries t2 for a moment)
+      if ((threadIdx.x & 255) < HG_NC) rr_s[threadIdx.x & 255] = rrp;
+    }
+    __syncthreads();
+    if (lo) t2 = t_s[a * HG_NC + c];
+    __syncthreads();
   }
-  if (threadIdx.x < HG_NC) rr_s[threadIdx.x] = rrp;
-  d_s[a * HG_NC + c] = phase == 0 ? (double)t : (double)t - (double)t2;
-  t_s[a * HG_NC + c] = t;
+  if (lo) {
+    d_s[a * HG_NC + c] = phase == 0 ? (double)t : (double)t - (double)t2;
+    t_s[a * HG_NC + c] = t;
+  }
   __syncthreads();
   if (phase == 1) {
     const bool conv = rr_s[0] <= tol2 * __shfl(bbv, 0) && rr_s[1] <= tol2 * __shfl(bbv, 1) &&
                       rr_s[2] <= tol2 * __shfl(bbv, 2) && rr_s[3] <= tol2 * __shfl(bbv, 3);
     if (conv) {  // uniform over the workgroup
-      if (threadIdx.x == 0) { cg->done = 1; cg->iters = it; }
+      if (threadIdx.x == 0) {
+        cg->done = 1; cg->iters = it;
+        if (K8) cg_publish(cg->pub + CG_PUB_CONV, tag, 1u);
+      }
       return;
     }
   }
+  if (!lo) return;  // (no barrier below)
   double m4[4] = {0.0, 0.0, 0.0, 0.0};  // four independent fp64 chains (a single 64-long chain is 64 dependent DFMAs)
 #pragma unroll
   for (int b = 0; b < HG_M; b += 4) {
@@ -745,18 +817,22 @@ static __device__ __forceinline__ void cg_reduce_step(const float* __restrict__ 
   float tm = t_s[a * HG_NC + c] * mu;
   tm = r3d_wave_sum(tm);  // one wave = one column c
   cg->mu[a * HG_NC + c] = mu;
+  if (K8) cg_publish(cg->pub + a * HG_NC + c, tag, __float_as_uint(mu));
   if (a == 0) {
     if (phase == 0) {
       cg->bb[c] = rr_s[c];
     } else {
       const float rz = rr_s[c] + tm;
-      cg->beta[c] = (it > 0 && rz_old > 0.f) ? rz / rz_old : 0.f;
+      const float bt = (it > 0 && rz_old > 0.f) ? rz / rz_old : 0.f;
+      cg->beta[c] = bt;
       cg->rz[c] = rz;
+      if (K8) cg_publish(cg->pub + CG_PUB_BETA + c, tag, __float_as_uint(bt));
     }
   }
   if (threadIdx.x == 0) {
     if (phase == 0) { cg->done = 0; cg->iters = 0; }
     else cg->iters = it;
+    if (K8) cg_publish(cg->pub + CG_PUB_CONV, tag, 0u);
   }
 }
 
@@ -865,7 +941,7 @@ __global__ __launch_bounds__(256) void r3d_cg_init_kernel(const float4* __restri
   }
   __syncthreads();
   cg_block_partials(rs, us, ag, row0, n, m, mode == 1, part + (long)blockIdx.x * HG_PART, sm, wpart);
-  if (cg_delivered_last(cg, gridDim.x, &last_s)) cg_reduce_step(part, gridDim.x, Einv, mode, 0, tol2, cg, d_s, t_s, rr_s);
+  if (cg_delivered_last(cg, gridDim.x, &last_s)) cg_reduce_step<false>(part, gridDim.x, Einv, mode, 0, tol2, cg, d_s, t_s, rr_s);
 }
 
 // S: p = r + u mu[agg] + beta p ; q = (r - alpha S r) + (M W) mu + beta q ; partial <p, q>.
@@ -983,6 +1059,17 @@ __global__ __launch_bounds__(256) void r3d_cg_spmv_kernel(
 // the c-th of workgroup b) and the rows of a workgroup cyclically to its 8 waves (local row 8 k + w is the k-th of
 // wave w): consecutive hub rows land in different waves of different workgroups.  The four <p q> products of a group
 // then sit in four waves; they meet in LDS and are added in row order as before.
+//
+// THE UPDATE RIDES IN THE HEAD (it > 0; section 5's comment has the sequence).  Hand-offs inside the launch, both in the
+// forms of cdna_hip_programming.md Guideline 16: block partials -> last workgroup by sc1 stores, every storing wave
+// drained, barrier, relaxed ticket add, sc1 loads (cg_delivered_last's form, on a ticket word of this kernel's own);
+// coefficients -> waiting workgroups as 8-byte {tag, value} words, relaxed agent-scope stores and loads, the data is
+// the flag.  The words are zeroed per solve and the tag is the iteration, so nothing of an earlier solve or replay can
+// pass for this one's.  All reads of r, q, <p q> partials and rz that other workgroups of the system make come before
+// their ticket, hence before any store made behind the wait: no buffer is doubled.  The wait is bounded (CG_SPIN_LIMIT
+// polls with a sleep between them); workgroups wait only for their own system, whose workgroups lp_solve keeps resident
+// together.  Resources: 128 registers, no scratch, 9.2 KB of static LDS beside the residual (two workgroups per CU up to
+// 70.8 KB of residual); the head's scratch arrays lie in pq_s.
 #define SL_ROWS 128
 #define SL_WAVES 8
 #define SL_PASS_RPW 64                          // rows of a wave per pass
@@ -993,34 +1080,175 @@ __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
     const int* __restrict__ row_ptr, const hg_col_t* __restrict__ col, const float* __restrict__ val,
     const float* __restrict__ dinv, const int* __restrict__ agg, const float* __restrict__ MW,
     const int* __restrict__ n_dev, int n_cap, float alpha_lp, int it, int rows_per_block,
-    const float4* __restrict__ r, float4* __restrict__ p, float4* __restrict__ q,
-    float4* __restrict__ part_pq /* [ceil(n_cap / 4)] */, const CgState* __restrict__ cg, HgEp st) {
+    float4* __restrict__ r, float4* __restrict__ p, float4* __restrict__ q,
+    float4* __restrict__ part_pq /* [ceil(n_cap / 4)] */, CgState* cg, HgEp st,
+    float4* __restrict__ x, float* __restrict__ part, const float* __restrict__ Einv, float tol2, int nblk_pq, int nblk_v,
+    long x_stride) {
   extern __shared__ __attribute__((aligned(16))) float4 rs[];  // [n] the system's residual
   __shared__ float4 mu_s[HG_M];
+  __shared__ float4 beta_s;
+  __shared__ float4 sm[8];
+  __shared__ int last_s, wait_s;
   {
     const int ep = blockIdx.y;
     HG_WS(cg);
-    if (cg->done) return;  // this system has converged: the launch goes on for the others
+    if (cg->done | cg->fail) return;  // this system has converged (or gave up): the launch goes on for the others
     HG_WS(row_ptr); HG_WS(col); HG_WS(val); HG_WS(dinv); HG_WS(agg); HG_WS(MW); HG_AT(n_dev, st.desc); HG_WS(r); HG_WS(p);
-    HG_WS(q); HG_WS(part_pq);
+    HG_WS(q); HG_WS(part_pq); HG_AT(x, x_stride); HG_WS(part); HG_WS(Einv);
   }
-  __shared__ float4 pq_s[SL_PASS_ROWS];  // the <p q> products of the pass's rows, by local row
+  __shared__ float4 pq_s[SL_PASS_ROWS];  // the <p q> products of the pass's rows, by local row; the head's scratch before
   const int n = min(*n_dev, n_cap);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int n_wg = gridDim.x, bx = blockIdx.x;
   const int n_part = (n_cap + 3) / 4;  // partials of <p, q>: one per 4 rows, as r3d_cg_spmv_kernel with rows_per_block = 4
-  // stage r: 4 float4 per thread in flight
-  for (int i0 = tid; i0 < n; i0 += 4 * 64 * SL_WAVES) {
-    float4 v[4];
+  const bool fused = it > 0;  // uniform over the launch
+  if (!fused) {
+    // stage r: 4 float4 per thread in flight
+    for (int i0 = tid; i0 < n; i0 += 4 * 64 * SL_WAVES) {
+      float4 v[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = r[min(i0 + u * 64 * SL_WAVES, n - 1)];
+      for (int u = 0; u < 4; ++u) v[u] = r[min(i0 + u * 64 * SL_WAVES, n - 1)];
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i0 + u * 64 * SL_WAVES < n) rs[i0 + u * 64 * SL_WAVES] = v[u];
+      for (int u = 0; u < 4; ++u)
+        if (i0 + u * 64 * SL_WAVES < n) rs[i0 + u * 64 * SL_WAVES] = v[u];
+    }
+    if (tid < HG_M) mu_s[tid] = reinterpret_cast<const float4*>(cg->mu)[tid];
+    if (tid == 0) beta_s = *reinterpret_cast<const float4*>(cg->beta);
+  } else {
+    // ---- the head: iteration it - 1's update.  The two halves of the workgroup (waves 0 .. 3, 4 .. 7) work as two
+    // workgroups of r3d_cg_update_kernel would: half h takes the 256-row block bx + h n_wg of U's partition, then
+    // 2 n_wg further on.
+    const int half = w >> 2, wl = w & 3, t8 = tid & 255;
+    // column `lane` of M W over this wave's 64 rows of the block.  Rows 0 .. 47 are requested up front; rows 48 .. 63 go
+    // into the registers of rows 0 .. 15 once those are used up (mb), with 32 rows of arithmetic to cover their trip: 64
+    // values held at once take the kernel over the 128 registers at which two workgroups share a CU
+    float m[48], mb[16];
+    float ul = 0.f;    // u = D^1/2 and the aggregate of row `lane` of those 64: read below by lane broadcast
+    int agl = 0;
+    auto load_block = [&](int blk) {
+      if (blk < nblk_v) {  // uniform over the wave
+        const int row = __builtin_amdgcn_readfirstlane(blk * HG_UROWS + 64 * wl);  // (scalar row addresses + the lane)
+#pragma unroll
+        for (int k = 0; k < 48; ++k) m[k] = MW[(long)min(row + k, n_cap - 1) * HG_M + lane];
+        const int rl = min(row + lane, n_cap - 1);
+        const float dv = dinv[rl];
+        const int av = agg[rl];
+        ul = row + lane < n ? 1.f / dv : 0.f;
+        agl = row + lane < n ? av : 0;
+      }
+    };
+    const float4 rz = *reinterpret_cast<const float4*>(cg->rz);
+    const float4 pq = reduce_partials(part_pq, nblk_pq, sm);
+    load_block(bx + half * n_wg);  // (behind the <p, q> partials: in front of them it costs 8 registers too many; its trip
+    // runs under the staging of r below)
+    float4 al;
+    al.x = pq.x > 0.f ? rz.x / pq.x : 0.f;
+    al.y = pq.y > 0.f ? rz.y / pq.y : 0.f;
+    al.z = pq.z > 0.f ? rz.z / pq.z : 0.f;
+    al.w = pq.w > 0.f ? rz.w / pq.w : 0.f;
+    // r - alpha q of EVERY row into LDS (every workgroup of the system gathers from all of it).  Global r keeps the old
+    // residual until the wait below is over: the other workgroups of the system are still reading it.
+    for (int i0 = tid; i0 < n; i0 += 4 * 64 * SL_WAVES) {
+      float4 v[4], qv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int ic = min(i0 + u * 64 * SL_WAVES, n - 1);
+        v[u] = r[ic];
+        qv[u] = q[ic];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i0 + u * 64 * SL_WAVES < n) {
+          float4 ri = v[u];
+          const float4 qi = qv[u];
+          ri.x -= al.x * qi.x; ri.y -= al.y * qi.y; ri.z -= al.z * qi.z; ri.w -= al.w * qi.w;
+          rs[i0 + u * 64 * SL_WAVES] = ri;
+        }
+    }
+    __syncthreads();
+    // the blocks' partials of the new residual (cg_block_partials, with the rows read from the LDS copy)
+    float4* wp = pq_s + 256 * half;  // [4][HG_M]: the half's four waves' t, then their t2
+    for (int b0 = bx;;) {  // (uniform trip count: a workgroup without a block still takes every barrier)
+      const int blk = b0 + half * n_wg;
+      const bool has = blk < nblk_v;  // uniform over the half
+      const int row0 = blk * HG_UROWS;
+      float4 t = f4_zero(), t2 = f4_zero();
+      if (has) {
+        const int rw = __builtin_amdgcn_readfirstlane(row0 + 64 * wl);
+#pragma unroll
+        for (int k = 0; k < 64; ++k) {
+          // (unrolled whole so that m[k] stays in registers; the fence keeps the scheduler from hoisting all 64 LDS reads
+          // to the top, which takes 256 registers)
+          if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+          if (k == 16) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) mb[j] = MW[(long)min(rw + 48 + j, n_cap - 1) * HG_M + lane];
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          const float mk = k < 48 ? m[k] : mb[k < 48 ? 0 : k - 48];
+          const int row = rw + k;
+          float4 rv = rs[min(row, n_cap - 1)];  // (LDS holds n_cap rows; those from n on are not written: masked)
+          rv.x = r3d_keep(rv.x, row < n); rv.y = r3d_keep(rv.y, row < n); rv.z = r3d_keep(rv.z, row < n); rv.w = r3d_keep(rv.w, row < n);
+          const float uk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ul), k));
+          const float uw = __builtin_amdgcn_readlane(agl, k) == lane ? uk : 0.f;
+          t.x = __builtin_fmaf(uw, rv.x, t.x); t.y = __builtin_fmaf(uw, rv.y, t.y);
+          t.z = __builtin_fmaf(uw, rv.z, t.z); t.w = __builtin_fmaf(uw, rv.w, t.w);
+          t2.x = __builtin_fmaf(mk, rv.x, t2.x); t2.y = __builtin_fmaf(mk, rv.y, t2.y);
+          t2.z = __builtin_fmaf(mk, rv.z, t2.z); t2.w = __builtin_fmaf(mk, rv.w, t2.w);
+        }
+      }
+      float4 sq = f4_zero();
+      if (has && row0 + t8 < n) {
+        const float4 v = rs[row0 + t8];
+        sq = make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w);
+      }
+      wp[wl * HG_M + lane] = t;
+      sq = block_sum4(sq, sm);  // its barriers also publish wp
+      float st = 0.f, st2 = 0.f;  // thread (a = lane, c = wl) adds the four waves' partials of entry [a][c]
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) st += f4_get(wp[q4 * HG_M + lane], wl);
+      __syncthreads();
+      wp[wl * HG_M + lane] = t2;
+      __syncthreads();
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) st2 += f4_get(wp[q4 * HG_M + lane], wl);
+      if (has) {
+        float* pb = part + (long)blk * HG_PART;
+        if (t8 < 4) cg_store_sc1(pb + t8, f4_get(sq, t8));
+        cg_store_sc1(pb + 4 + lane * HG_NC + wl, st);
+        cg_store_sc1(pb + 4 + HG_M * HG_NC + lane * HG_NC + wl, st2);
+      }
+      b0 += 2 * n_wg;
+      if (b0 >= nblk_v) break;
+      __syncthreads();  // wp is free again
+      load_block(b0 + half * n_wg);
+    }
+    // ticket: every storing wave drains, workgroup barrier, one relaxed add (cg_delivered_last, on this kernel's word)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned tk = __hip_atomic_fetch_add(&cg->ticket_k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last_s = (tk + 1u) % (unsigned)n_wg == 0u;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    if (last_s) {  // the coefficients and the convergence test of iteration `it`, published for the waiting workgroups
+      char* scr = reinterpret_cast<char*>(pq_s);
+      cg_reduce_step<true>(part, nblk_v, Einv, 1, it, tol2, cg, reinterpret_cast<double*>(scr),
+                           reinterpret_cast<float*>(scr + 2048), reinterpret_cast<float*>(scr + 3072), (unsigned)it);
+    }
+    // x += alpha p on the rows whose tails this workgroup runs (nobody else touches their x or p)
+    for (int j = tid;; j += 64 * SL_WAVES) {
+      const int i = 4 * ((j >> 2) * n_wg + bx) + (j & 3);
+      if (i >= n) break;  // (i grows with j)
+      const float4 pi = p[i];
+      float4 xi = x[i];
+      xi.x += al.x * pi.x; xi.y += al.y * pi.y; xi.z += al.z * pi.z; xi.w += al.w * pi.w;
+      x[i] = xi;
+    }
   }
-  if (tid < HG_M) mu_s[tid] = reinterpret_cast<const float4*>(cg->mu)[tid];
   __syncthreads();
-  const float4 mul = mu_s[lane];
+  float4 mul = f4_zero();
   const int n_c = (n_part + n_wg - 1) / n_wg;  // 4-row groups of this workgroup (the last may lie beyond n_part)
   for (int c0 = 0; c0 < n_c; c0 += SL_PASS_ROWS / 4) {
     // the k-th row of this wave in this pass: local row l = 8 k + w of the workgroup = member l & 3 of its group l >> 2
@@ -1062,7 +1290,55 @@ __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
     };
 #pragma unroll
     for (int d = 0; d < SL_DEPTH; ++d) issue(rj[d], ra[d], rm[d]);
-    // Rows go in groups of 4.  A lane keeps its partial sums of the group's rows in registers and the 64 lanes'
+    if (c0 == 0) {
+      if (fused) {
+        // ---- the wait, as late as the arithmetic allows: the first items are on their way.  Wave 0 polls the published
+        // words (sc1 loads, a sleep between polls, a bounded number of them) until all carry this iteration's tag.
+        if (w == 0) {
+          const unsigned long long* pub = cg->pub;
+          const unsigned tag = (unsigned)it;
+          int state = -1;  // -1 gave up, 0 go on, 1 the system has converged
+          for (int spins = 0; spins < CG_SPIN_LIMIT; ++spins) {
+            unsigned long long pv[5];
+            const unsigned long long cv = __hip_atomic_load(pub + CG_PUB_CONV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pv[k] = __hip_atomic_load(pub + lane + 64 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pv[4] = __hip_atomic_load(pub + CG_PUB_BETA + (lane & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool have = (unsigned)(cv >> 32) == tag;  // (one address for the wave: uniform)
+            if (have && (unsigned)cv != 0u) { state = 1; break; }
+            bool ok = have;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) ok = ok && (unsigned)(pv[k] >> 32) == tag;
+            if (__all(ok)) {
+              float* mf = reinterpret_cast<float*>(mu_s);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) mf[lane + 64 * k] = __uint_as_float((unsigned)pv[k]);
+              if (lane < HG_NC) reinterpret_cast<float*>(&beta_s)[lane] = __uint_as_float((unsigned)pv[4]);
+              state = 0;
+              break;
+            }
+            __builtin_amdgcn_s_sleep(8);
+          }
+          if (lane == 0) {
+            wait_s = state;
+            if (state < 0) __hip_atomic_store(&cg->fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+        __syncthreads();
+        const int state = wait_s;
+        if (state < 0) return;  // uniform.  The solve stops here and reports "not converged": the caller redoes it
+        if (state > 0) {        // converged: leave the residual r3d_cg_update_kernel would have left (x is done above)
+          for (int j = tid;; j += 64 * SL_WAVES) {
+            const int i = 4 * ((j >> 2) * n_wg + bx) + (j & 3);
+            if (i >= n) break;
+            r[i] = rs[i];
+          }
+          return;
+        }
+      }
+      mul = mu_s[lane];
+    }
+    // Rows go in groups of 4. A lane keeps its partial sums of the group's rows in registers and the 64 lanes'
     // partials meet in ONE transposed butterfly per group: the xor-32 step halves the rows a lane is responsible for (it
     // sends the other half to its partner), xor-16 halves again, and the last four steps run on the one row left --
     // lanes 16 g .. 16 g + 15 end up with the total of row g.  Every row still sees the pairs (l, l ^ 32), (l, l ^ 16),
@@ -1144,8 +1420,9 @@ __global__ __launch_bounds__(64 * SL_WAVES) void r3d_cg_spmv_lds_kernel(
     const int trow = 4 * (lane & 15) + (lane >> 4);
     if (trow < nrows) {
       const int i = row_of(trow);
-      const float4 beta = *reinterpret_cast<const float4*>(cg->beta);
+      const float4 beta = beta_s;
       const float4 ri = rs[i], pi = p[i], qi = q[i];
+      if (fused) r[i] = ri;  // the head's r - alpha q: every workgroup of the system has staged the old one by now
       const float u = 1.f / dinv[i];
       const float4 m = mu_s[agg[i]];
       const float4 pn = make_float4((ri.x + u * m.x) + beta.x * pi.x, (ri.y + u * m.y) + beta.y * pi.y,
@@ -1204,6 +1481,11 @@ __global__ __launch_bounds__(256) void r3d_cg_update_kernel(
     HG_AT(n_dev, st.desc); HG_WS(dinv); HG_WS(agg); HG_WS(MW); HG_WS(p); HG_WS(q); HG_AT(x, x_stride); HG_WS(r); HG_WS(part_pq);
     HG_WS(part); HG_WS(Einv); HG_WS(cg);
   }
+  if (cg->done | cg->fail) return;  // uniform: this system has converged (or a fused S gave up): nothing is loaded
+  // it < 0: the closing update behind a chain of fused S launches.  The iteration it completes is the one the last
+  // fused launch that ran began, which the device knows (cg->iters) and the host does not once a captured graph runs
+  // with fewer iterations enabled than it holds (r3d_graph_set_lp_budget).
+  if (it < 0) it = cg->iters;
   const int row0 = blockIdx.x * HG_UROWS;
   const int i = row0 + threadIdx.x;
   const int ic = min(i, n_cap - 1);
@@ -1214,12 +1496,10 @@ __global__ __launch_bounds__(256) void r3d_cg_update_kernel(
   float4 xi = x[ic], ri = r[ic];
   const float dv = dinv[ic];
   const int av = agg[ic];
-  const int done = cg->done;
   const float4 rz = *reinterpret_cast<const float4*>(cg->rz);
   const int n = min(*n_dev, n_cap);
   const float4 pq = reduce_partials(part_pq, nblk_pq, sm);
   CSTAMP(1);
-  if (done) return;  // uniform
   float4 al;
   al.x = pq.x > 0.f ? rz.x / pq.x : 0.f;
   al.y = pq.y > 0.f ? rz.y / pq.y : 0.f;
@@ -1246,7 +1526,7 @@ __global__ __launch_bounds__(256) void r3d_cg_update_kernel(
   CSTAMP(4);
   if (last) {
     CSTAMP_LAST(0);
-    cg_reduce_step(part, gridDim.x, Einv, 1, it + 1, tol2, cg, d_s, t_s, rr_s);
+    cg_reduce_step<false>(part, gridDim.x, Einv, 1, it + 1, tol2, cg, d_s, t_s, rr_s);
     CSTAMP_LAST(1);
   }
 }
@@ -1420,7 +1700,7 @@ extern "C" int r3d_graph_weights_verify(int n_ep, const float* nodes, long ldn, 
 __global__ void r3d_cg_stats_kernel(const CgState* __restrict__ cg, int* __restrict__ stats_out, HgEp st) {
   const int ep = blockIdx.x;
   HG_WS(cg); HG_AT(stats_out, st.stats);
-  if (threadIdx.x == 0) { stats_out[0] = cg->done; stats_out[1] = cg->iters; }
+  if (threadIdx.x == 0) { stats_out[0] = cg->fail ? 0 : cg->done; stats_out[1] = cg->iters; }  // (fail: a wait gave up)
 }
 
 // coarse space of the graph r3d_label_propagate built: aggregates, M W, E^-1 (shared by forward and adjoint solve)
@@ -1482,7 +1762,9 @@ static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int3
   R3D_REQUIRE(nblk_s <= HG_MAX_PART, "r3d_label_propagate: n_cap too large");
   float4* x = (float4*)X;
   const float tol2 = tol * tol;
-  r3d_fill_words_ep(&L.cg->ticket, 0u, 1, n_ep, ep.ws, st);
+  // zeroed per solve: both tickets, the give-up flag and the tagged words of the fused launches (one fill from `ticket` to
+  // the end of the state; what lies between is written by the init launches before anything reads it)
+  r3d_fill_words_ep(&L.cg->ticket, 0u, (long)((sizeof(CgState) - offsetof(CgState, ticket)) / 4), n_ep, ep.ws, st);
   // partials of b -> (last workgroup) c0 = E^-1 W^T b ; x0 = W c0, r0 = b - (M W) c0 -> (last workgroup) mu, rz of iteration 0
   for (int mode = 0; mode < 2; ++mode)
     hipLaunchKernelGGL(r3d_cg_init_kernel, dim3(nblk_v, n_ep), dim3(256), 0, st, (const float4*)RHS, L.dinv, L.agg, L.MW, n_dev,
@@ -1504,16 +1786,23 @@ static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int3
   // than one per 128 rows, and a batch of more systems than slots runs one workgroup per system in several rounds)
   const int nblk_l = use_lds ? std::max(1, std::min(r3d_cdiv(n_cap, SL_ROWS), cg_lds_slots(lds_r) / n_ep)) : 0;
   const int nblk_pq = nblk_s;  // (the LDS kernel writes the same 4-row partials)
+  // LDS form: one launch per iteration.  Launch `it` > 0 begins with the update of iteration it - 1 and one closing
+  // update ends the chain (it = -1: it takes the iteration from the device, see r3d_cg_update_kernel).
   for (int it = 0; it < max_iter; ++it) {
-    if (use_lds)
+    if (use_lds) {
       hipLaunchKernelGGL(r3d_cg_spmv_lds_kernel, dim3(nblk_l, n_ep), dim3(64 * SL_WAVES), lds_r, st, L.row_ptr, L.col, L.val, L.dinv,
-                         L.agg, L.MW, n_dev, n_cap, alpha, it, SL_ROWS, L.r, L.p, L.q, L.part_pq, L.cg, ep);
-    else
-      hipLaunchKernelGGL(r3d_cg_spmv_kernel, dim3(nblk_s, n_ep), dim3(256), 0, st, L.row_ptr, L.col, L.val, L.dinv, L.agg, L.MW,
-                         n_dev, n_cap, alpha, it, rpb, L.r, L.p, L.q, L.part_pq, L.cg, ep);
+                         L.agg, L.MW, n_dev, n_cap, alpha, it, SL_ROWS, L.r, L.p, L.q, L.part_pq, L.cg, ep, x, L.part, L.Einv, tol2,
+                         nblk_pq, nblk_v, x_stride);
+      continue;
+    }
+    hipLaunchKernelGGL(r3d_cg_spmv_kernel, dim3(nblk_s, n_ep), dim3(256), 0, st, L.row_ptr, L.col, L.val, L.dinv, L.agg, L.MW,
+                       n_dev, n_cap, alpha, it, rpb, L.r, L.p, L.q, L.part_pq, L.cg, ep);
     hipLaunchKernelGGL(r3d_cg_update_kernel, dim3(nblk_v, n_ep), dim3(256), 0, st, n_dev, n_cap, it, nblk_pq, L.dinv, L.agg, L.MW,
                        L.p, L.q, x, L.r, L.part_pq, L.part, L.Einv, tol2, L.cg, ep, x_stride);
   }
+  if (use_lds)
+    hipLaunchKernelGGL(r3d_cg_update_kernel, dim3(nblk_v, n_ep), dim3(256), 0, st, n_dev, n_cap, -1, nblk_pq, L.dinv, L.agg, L.MW,
+                       L.p, L.q, x, L.r, L.part_pq, L.part, L.Einv, tol2, L.cg, ep, x_stride);
   if (stats_out) hipLaunchKernelGGL(r3d_cg_stats_kernel, dim3(n_ep), dim3(64), 0, st, L.cg, stats_out, ep);
   return R3D_OK;
 }
