@@ -217,6 +217,16 @@ int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes, long fit_
                                     int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way, int D,
                                     int n_query_pts, float* nodes, long ldn, int n_cap, float* node_labels, int32_t* desc,
                                     long desc_stride, int32_t* cluster_count, long ccount_stride, void* stream);
+/* r3d_head_attach_queries_sets: n_sets fitted systems against n_groups groups of query rows in one launch.  fits: a
+ * DEVICE table of n_sets rows of 4 addresses {nodes, node_labels, desc, cluster_count or 0} of fitted systems that share
+ * fit_ldn, fit_label_rows and proto_cap (fits of one model do); their pointers meet the alignment rules above, which only
+ * the caller can check.  Destination system g * n_sets + k is what r3d_head_attach_queries_batched builds from fit k and
+ * group g -- the same device function, so the same bits in its node matrix, label rows, desc and cluster counts --;
+ * plane 1 of the labels lies n_groups * n_sets * n_cap rows behind plane 0.  At most 65535 systems. */
+int r3d_head_attach_queries_sets(int n_groups, int n_sets, const uint64_t* fits, long fit_ldn, long fit_label_rows,
+                                 int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way, int D,
+                                 int n_query_pts, float* nodes, long ldn, int n_cap, float* node_labels, int32_t* desc,
+                                 long desc_stride, int32_t* cluster_count, long ccount_stride, void* stream);
 
 /* ---- affinity + label propagation (models/mpti.py:717-776) ---------------------------
  * nbr (n_cap, kp1) from r3d_knn_topk mode 1 (column 0 is dropped as in mpti.py:736).
@@ -460,6 +470,16 @@ int r3d_protonet_prototypes_batched(int n_ep, const float* sfeat, long ldf, long
 int r3d_protonet_similarity_batched(int n_sys, const float* qfeat, long ldq, long q_sys_rows, int D, const float* protos,
                                     long proto_stride, int n_way, int n_query_pts, int method, float scaler, float* Z,
                                     void* stream);
+/* r3d_protonet_similarity_sets: n_sets prototype tables (table k at protos + k * proto_stride floats, n_sets * (n_way + 1)
+ * <= 64 rows in all) against the query rows of n_groups groups (group g's n_query_pts rows start q_sys_rows rows after
+ * group g - 1's), ONE launch in which a query row is read once and scored against every table.  System g * n_sets + k
+ * is rows [(g * n_sets + k) * n_query_pts, ...) of Z (per plane n_groups * n_sets * n_query_pts rows), so
+ * r3d_query_logits_ce_batched with n_ep = n_groups * n_sets leaves logits (n_groups, n_sets * (n_way + 1), N) when a
+ * group is one cloud.  Per (row, prototype) the operations of r3d_protonet_similarity_batched in their order: set k's
+ * rows have the bits of that call on table k alone. */
+int r3d_protonet_similarity_sets(int n_groups, int n_sets, const float* qfeat, long ldq, long q_sys_rows, int D,
+                                 const float* protos, long proto_stride, int n_way, int n_query_pts, int method, float scaler,
+                                 float* Z, void* stream);
 /* correct (n_ep) int32 = per episode #{pred == label}: pred (n_ep, n_pts) int32 as r3d_query_logits_ce_batched writes it,
  * labels (n_ep, n_pts) int64.  One host read then serves the accuracy of a whole batch. */
 int r3d_count_correct_batched(int n_ep, const int32_t* pred, const int64_t* labels, long n_pts, int32_t* correct,
@@ -618,6 +638,23 @@ int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long
 int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
                            long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
                            const int32_t* votes, int64_t* source, int64_t* neighbours, float* weights, void* stream);
+
+/* ---- predict_scene_sets: one scan against several support sets ("Labelling a scan against several support
+ * sets", step 10).  Additive: the entry points above and what they compute are as they were.
+ * r3d_scene_merge_sets: scores (M, n_sets, n_classes) fp32 -- what r3d_scene_vote(_run) and the transfers leave for logits
+ * whose columns are set after set, n_classes = n_way + 1 >= 2 each, n_sets * n_classes <= 64 --, votes (M,), source (M,)
+ * of a transfer or NULL.  One thread per point, no atomics, nothing summed.  A point HAS A LABEL when votes[p] > 0 or
+ * (source given) source[p] >= 0; any other point gets set_labels -1, labels -1, set_of -1, margin 0.  Per set k of a point
+ * with a label: l_k = the arg-max of its n_classes scores with the comparison of r3d_scene_vote (lowest class on ties; one
+ * device function serves both kernels), set_labels[p][k] = l_k; with l_k >= 1 the set CLAIMS p with the margin m_k =
+ * s[l_k] - s[r], r the arg-max over the classes other than l_k by the same comparison -- one IEEE fp32 subtraction; a NaN
+ * margin does not claim.  The claim with the greatest margin wins, the lowest k on equal margins: labels[p] =
+ * classes[k * (n_classes - 1) + l_k - 1] (classes: n_sets * n_way int32 on the device), set_of[p] = k, margin[p] = m_k.
+ * Without a claim labels[p] = background, set_of[p] = -1, margin[p] = 0.  set_labels (M, n_sets) and labels (M,) int64,
+ * set_of (M,) int32, margin (M,) fp32. */
+int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const float* scores, const int32_t* votes, const int64_t* source,
+                         const int32_t* classes, long background, int64_t* set_labels, int64_t* labels, int32_t* set_of,
+                         float* margin, void* stream);
 
 /* ---- fit_scene: the support set from an annotated scan ("Fitting from an annotated scan", S1-S5).
  * Additive: the entry points above and what they compute are as they were.  All three run after r3d_scene_plan (no cap) on

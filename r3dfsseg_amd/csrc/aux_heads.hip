@@ -388,6 +388,75 @@ __global__ __launch_bounds__(256) void r3d_proto_sim_table_kernel(const float* _
                 Zq2 ? Zq2 + g * n_pts : nullptr, blockIdx.x, gridDim.x);
 }
 
+// ---- K prototype tables against the same query rows (predict_scene_sets) -----------------------------------------------------
+// grid (query tiles, n_groups).  All K tables of a workgroup sit in LDS, R = K * (n_way + 1) <= 64 rows with an odd pitch
+// (the norm pass walks a row per thread), and a query row is read ONCE: one wave per point, its D <= 256 channels in four
+// registers per lane, then row after row of the tables against them.  Per (point, prototype) the operations of
+// ah_sim_points in its order -- channels lane, lane + 64, ... into one chain per lane, r3d_wave_sum, the same final
+// expression -- so set k's rows have the bits of r3d_proto_sim_table_kernel on table k alone.  Only the distance the
+// method asks for is formed (ah_sim_points forms both and drops one).  System g * K + k: rows [(g K + k) n_pts, ...) of Z.
+__global__ __launch_bounds__(256) void r3d_proto_sim_sets_kernel(const float* __restrict__ protos, long proto_stride, int K,
+                                                                 int n_way, const float* __restrict__ qfeat, long ldq,
+                                                                 long q_sys_rows, int D, int n_pts, int method, float scaler,
+                                                                 float4* __restrict__ Zq, float4* __restrict__ Zq2) {
+  extern __shared__ float ah_sets[];  // [R][pitch] prototype rows, then [R] their norms
+  const int C = n_way + 1, R = K * C, pitch = D | 1;
+  float* pnorm = ah_sets + R * pitch;
+  const long g = blockIdx.y;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < R * D; i += 256) {
+    const int r = i / D, c = i - r * D;
+    ah_sets[r * pitch + c] = protos[(long)(r / C) * proto_stride + (long)(r % C) * D + c];
+  }
+  __syncthreads();
+  if (tid < R) {
+    float s = 0.f;
+    for (int c = 0; c < D; ++c) s += ah_sets[tid * pitch + c] * ah_sets[tid * pitch + c];
+    pnorm[tid] = sqrtf(s);
+  }
+  __syncthreads();
+  const int lane = tid & 63, w = tid >> 6;
+  const float* qg = qfeat + g * q_sys_rows * ldq;
+  for (int p = blockIdx.x * 4 + w; p < n_pts; p += gridDim.x * 4) {  // one wave per query point
+    const float* q = qg + (long)p * ldq;
+    float v[4], qq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = lane + 64 * i;
+      v[i] = c < D ? q[c] : 0.f;
+      if (c < D) qq += v[i] * v[i];
+    }
+    qq = r3d_wave_sum(qq);
+    for (int k = 0; k < K; ++k) {
+      float out[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        out[j] = 0.f;
+        if (j >= C) continue;
+        const float* pr = ah_sets + (k * C + j) * pitch;
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int c = lane + 64 * i;
+          if (c >= D) continue;
+          if (method == 0) {
+            acc += v[i] * pr[c];
+          } else {
+            const float df = (v[i] - pr[c]) + 1e-6f;  // pairwise_distance eps (torch 1.8 semantics)
+            acc += df * df;
+          }
+        }
+        acc = r3d_wave_sum(acc);
+        if (method == 0) out[j] = acc / fmaxf(sqrtf(qq) * pnorm[k * C + j], 1e-8f) * scaler;
+        else { const float dist = sqrtf(acc); out[j] = -(dist * dist); }
+      }
+      const long row = (g * K + k) * n_pts + p;
+      if (lane == 0) Zq[row] = make_float4(out[0], out[1], out[2], out[3]);
+      if (lane == 0 && Zq2) Zq2[row] = make_float4(out[4], out[5], out[6], out[7]);
+    }
+  }
+}
+
 // correct[e] = #{pred == label} over the n_pts query points of episode e (integers: any order gives the same count).  grid (n_ep)
 __global__ __launch_bounds__(256) void r3d_count_correct_kernel(const int* __restrict__ pred, const long long* __restrict__ labels,
                                                                 long n_pts, int* __restrict__ correct) {
@@ -575,6 +644,43 @@ extern "C" int r3d_protonet_similarity_batched(int n_sys, const float* qfeat, lo
   hipLaunchKernelGGL(r3d_proto_sim_table_kernel, dim3(gx, n_sys), dim3(256), 0, (hipStream_t)stream, protos, proto_stride, n_way,
                      qfeat, ldq, q_sys_rows, D, n_query_pts, method, scaler, (float4*)Z,
                      n_way > 3 ? (float4*)Z + (long)n_sys * n_query_pts : nullptr);
+  R3D_LAUNCH_CHECK(who);
+  return R3D_OK;
+}
+
+extern "C" int r3d_protonet_similarity_sets(int n_groups, int n_sets, const float* qfeat, long ldq, long q_sys_rows, int D,
+                                            const float* protos, long proto_stride, int n_way, int n_query_pts, int method,
+                                            float scaler, float* Z, void* stream) {
+  const char* who = "r3d_protonet_similarity_sets";
+  R3D_REQUIRE(qfeat && protos && Z, "%s: null pointer", who);
+  R3D_REQUIRE(n_way >= 1 && n_way <= 7 && D >= 1 && D <= AH_DMAX && n_query_pts >= 1 && ldq >= D,
+              "%s: unsupported shape n_way=%d n_query_pts=%d D=%d", who, n_way, n_query_pts, D);
+  if (method != 0 && method != 1) {
+    r3d_set_error("Error! Distance computation method (%d) is unknown!", method);
+    return R3D_ERR_UNSUPPORTED;
+  }
+  R3D_REQUIRE(n_sets >= 1 && n_sets * (n_way + 1) <= 64, "%s: %d sets of %d classes (at most 64 prototype rows)", who, n_sets,
+              n_way + 1);
+  R3D_REQUIRE(n_groups >= 1 && n_groups <= 65535 && (n_groups == 1 || q_sys_rows >= n_query_pts) &&
+                  (long)n_groups * n_sets * n_query_pts < 0x7fffffffL,
+              "%s: %d groups x %d sets, %ld rows between the groups", who, n_groups, n_sets, q_sys_rows);
+  R3D_REQUIRE(n_sets == 1 || proto_stride >= (long)(n_way + 1) * D, "%s: prototype stride %ld (>= (n_way + 1) * D = %ld)", who,
+              proto_stride, (long)(n_way + 1) * D);
+  R3D_REQUIRE(((uintptr_t)Z & 15) == 0, "%s: Z must be 16-byte aligned", who);
+  const int R = n_sets * (n_way + 1);
+  const size_t lds = sizeof(float) * ((size_t)R * (D | 1) + R);
+  static size_t reserved = 64 * 1024;  // what a kernel may ask for without the attribute
+  if (lds > reserved) {
+    hipError_t e = hipFuncSetAttribute((const void*)r3d_proto_sim_sets_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    R3D_REQUIRE(e == hipSuccess, "%s: cannot reserve %zu B of LDS", who, lds);
+    reserved = lds;
+  }
+  // the tiling of r3d_protonet_similarity_batched over the groups (a point's arithmetic does not depend on the grid)
+  const int gx = min(r3d_cdiv(n_query_pts, 4), max(32, min(256, 2048 / n_groups)));
+  const long plane = (long)n_groups * n_sets * n_query_pts;
+  hipLaunchKernelGGL(r3d_proto_sim_sets_kernel, dim3(gx, n_groups), dim3(256), lds, (hipStream_t)stream, protos, proto_stride,
+                     n_sets, n_way, qfeat, ldq, q_sys_rows, D, n_query_pts, method, scaler, (float4*)Z,
+                     n_way > 3 ? (float4*)Z + plane : nullptr);
   R3D_LAUNCH_CHECK(who);
   return R3D_OK;
 }

@@ -990,20 +990,22 @@ extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_
 // n_query_pts <= n_cap): no index leaves [0, n_cap).  grid (stripes, n_sys).
 // ---------------------------------------------------------------------------
 #define AT_UNROLL 4
-__global__ __launch_bounds__(256) void r3d_head_attach_queries_kernel(
-    const float4* __restrict__ fit_nodes, long fit_ld4, const float4* __restrict__ fit_labels,
+// at_attach_system: destination system `sys` from one fitted system and query group `grp` (its rows start grp *
+// qfeat_sys_rows rows behind qfeat).  Both attach kernels are this function: r3d_head_attach_queries_kernel with grp = sys
+// and one fit, r3d_head_attach_queries_sets_kernel with the fit read from a table.
+static __device__ __forceinline__ void at_attach_system(
+    long sys, long grp, const float4* __restrict__ fit_nodes, long fit_ld4, const float4* __restrict__ fit_labels,
     const float4* __restrict__ fit_labels2 /* or null */, const int* __restrict__ fit_desc,
     const int* __restrict__ fit_ccount /* or null */, int proto_cap, const float4* __restrict__ qfeat, long ldq4,
     long qfeat_sys_rows, int d4, int nq_pts, float4* __restrict__ nodes, long ldn4, int n_cap, float4* __restrict__ labels,
     float4* __restrict__ labels2 /* or null */, int* __restrict__ desc, long desc_stride, int* __restrict__ ccount /* or null */,
     long ccount_stride) {
-  const long sys = blockIdx.y;
   const int tid = threadIdx.x;
   int n_proto = fit_desc[HD_N_PROTO];
   n_proto = n_proto < 0 ? 0 : (n_proto > proto_cap ? proto_cap : n_proto);
   if (blockIdx.x == 0 && tid < HD_WORDS)
     desc[sys * desc_stride + tid] = tid == HD_N_PROTO ? n_proto : tid == HD_N_NODES ? n_proto + nq_pts : fit_desc[tid];
-  qfeat += sys * qfeat_sys_rows * ldq4;
+  qfeat += grp * qfeat_sys_rows * ldq4;
   nodes += sys * n_cap * ldn4;
   labels += sys * n_cap;
   if (labels2) labels2 += sys * n_cap;
@@ -1047,6 +1049,34 @@ __global__ __launch_bounds__(256) void r3d_head_attach_queries_kernel(
   }
 }
 
+__global__ __launch_bounds__(256) void r3d_head_attach_queries_kernel(
+    const float4* __restrict__ fit_nodes, long fit_ld4, const float4* __restrict__ fit_labels,
+    const float4* __restrict__ fit_labels2 /* or null */, const int* __restrict__ fit_desc,
+    const int* __restrict__ fit_ccount /* or null */, int proto_cap, const float4* __restrict__ qfeat, long ldq4,
+    long qfeat_sys_rows, int d4, int nq_pts, float4* __restrict__ nodes, long ldn4, int n_cap, float4* __restrict__ labels,
+    float4* __restrict__ labels2 /* or null */, int* __restrict__ desc, long desc_stride, int* __restrict__ ccount /* or null */,
+    long ccount_stride) {
+  at_attach_system(blockIdx.y, blockIdx.y, fit_nodes, fit_ld4, fit_labels, fit_labels2, fit_desc, fit_ccount, proto_cap, qfeat,
+                   ldq4, qfeat_sys_rows, d4, nq_pts, nodes, ldn4, n_cap, labels, labels2, desc, desc_stride, ccount,
+                   ccount_stride);
+}
+
+// K fitted systems, G query groups: destination system g * K + k from fit k and group g.  fits: K rows of 4 device
+// addresses {nodes, labels, desc, cluster_count or 0}, every fit with the pitch fit_ld4 and fit_label_rows label rows per
+// plane.  grid (stripes, G * K).
+__global__ __launch_bounds__(256) void r3d_head_attach_queries_sets_kernel(
+    const unsigned long long* __restrict__ fits, int n_sets, long fit_ld4, long fit_label_rows, int two_planes, int proto_cap,
+    const float4* __restrict__ qfeat, long ldq4, long qfeat_sys_rows, int d4, int nq_pts, float4* __restrict__ nodes, long ldn4,
+    int n_cap, float4* __restrict__ labels, float4* __restrict__ labels2 /* or null */, int* __restrict__ desc, long desc_stride,
+    int* __restrict__ ccount /* or null */, long ccount_stride) {
+  const long sys = blockIdx.y;
+  const unsigned long long* f = fits + 4 * (sys % n_sets);
+  const float4* fl = (const float4*)f[1];
+  at_attach_system(sys, sys / n_sets, (const float4*)f[0], fit_ld4, fl, two_planes ? fl + fit_label_rows : nullptr,
+                   (const int*)f[2], (const int*)f[3], proto_cap, qfeat, ldq4, qfeat_sys_rows, d4, nq_pts, nodes, ldn4, n_cap,
+                   labels, labels2, desc, desc_stride, ccount, ccount_stride);
+}
+
 extern "C" int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes, long fit_ldn, const float* fit_labels,
                                                long fit_label_rows, const int32_t* fit_desc, const int32_t* fit_cluster_count,
                                                int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way,
@@ -1083,6 +1113,46 @@ extern "C" int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes
                      fit_desc, fit_cluster_count, proto_cap, (const float4*)qfeat, ldq / 4, qfeat_sys_rows, d4, n_query_pts,
                      (float4*)nodes, ldn / 4, n_cap, nl, n_way > 3 ? nl + (long)n_sys * n_cap : nullptr, desc, desc_stride,
                      cluster_count, ccount_stride);
+  R3D_LAUNCH_CHECK(fn);
+  return R3D_OK;
+}
+
+extern "C" int r3d_head_attach_queries_sets(int n_groups, int n_sets, const uint64_t* fits, long fit_ldn, long fit_label_rows,
+                                            int proto_cap, const float* qfeat, long ldq, long qfeat_sys_rows, int n_way, int D,
+                                            int n_query_pts, float* nodes, long ldn, int n_cap, float* node_labels,
+                                            int32_t* desc, long desc_stride, int32_t* cluster_count, long ccount_stride,
+                                            void* stream) {
+  const char* fn = "r3d_head_attach_queries_sets";
+  R3D_REQUIRE(fits && qfeat && nodes && node_labels && desc, "%s: null pointer", fn);
+  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= HP_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
+              "%s: unsupported geometry n_way=%d D=%d (n_way <= 7, D <= 256 and a multiple of 4)", fn, n_way, D);
+  R3D_REQUIRE(n_groups >= 1 && n_sets >= 1 && (long)n_groups * n_sets <= 65535 && n_query_pts >= 1 && proto_cap >= 1 &&
+                  (n_groups == 1 || qfeat_sys_rows >= n_query_pts),
+              "%s: %d groups of %d query rows (%ld rows between them) x %d sets (at most 65535 systems), %d prototype slots", fn,
+              n_groups, n_query_pts, qfeat_sys_rows, n_sets, proto_cap);
+  R3D_REQUIRE((long)proto_cap + n_query_pts <= n_cap,
+              "%s: node buffer of n_cap = %d rows is shorter than %d prototype slots + %d query rows", fn, n_cap, proto_cap,
+              n_query_pts);
+  R3D_REQUIRE(fit_label_rows >= proto_cap, "%s: %ld label rows per plane hold fewer than %d prototype slots", fn,
+              fit_label_rows, proto_cap);
+  R3D_REQUIRE(((long)proto_cap + n_query_pts) * (D / 4) < 0x7fffffffL, "%s: %d rows x %d channels do not fit 31 bits", fn,
+              proto_cap + n_query_pts, D);
+  R3D_REQUIRE(fit_ldn >= D && ldq >= D && ldn >= D && fit_ldn % 4 == 0 && ldq % 4 == 0 && ldn % 4 == 0,
+              "%s: row pitches %ld / %ld / %ld must be multiples of 4 floats >= D = %d", fn, fit_ldn, ldq, ldn, D);
+  R3D_REQUIRE((((uintptr_t)fits & 7) | (((uintptr_t)qfeat | (uintptr_t)nodes | (uintptr_t)node_labels) & 15)) == 0,
+              "%s: the fit table must be 8-byte, node, label and query rows 16-byte aligned", fn);
+  const long n_sys = (long)n_groups * n_sets;
+  R3D_REQUIRE(desc_stride >= HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)HD_WORDS);
+  R3D_REQUIRE(!cluster_count || n_sys == 1 || ccount_stride >= n_cap, "%s: cluster_count stride %ld < n_cap = %d", fn,
+              ccount_stride, n_cap);
+  const int d4 = D / 4;
+  const long total = ((long)proto_cap + n_query_pts) * d4;
+  float4* nl = (float4*)node_labels;
+  hipLaunchKernelGGL(r3d_head_attach_queries_sets_kernel, dim3(r3d_cdiv(total, 256L * AT_UNROLL), (int)n_sys), dim3(256), 0,
+                     (hipStream_t)stream, (const unsigned long long*)fits, n_sets, fit_ldn / 4, fit_label_rows,
+                     n_way > 3 ? 1 : 0, proto_cap, (const float4*)qfeat, ldq / 4, qfeat_sys_rows, d4, n_query_pts, (float4*)nodes,
+                     ldn / 4, n_cap, nl, n_way > 3 ? nl + n_sys * n_cap : nullptr, desc, desc_stride, cluster_count,
+                     ccount_stride);
   R3D_LAUNCH_CHECK(fn);
   return R3D_OK;
 }

@@ -654,6 +654,16 @@ extern "C" int r3d_scene_prepare_run(const float* scan, int ld, long M, int ncx,
 // One thread per scan point.  Its appearances follow from its cell, its rank in the cell list and the block's row
 // offsets: list position q in block (bx, by) -> chunk q % nc, member q / nc, slots member, member + len, ... < N.
 // Blocks by ascending id (by, then bx), slots ascending, one running fp32 sum per class: a fixed order, no atomics.
+
+// One step of the arg-max of the vote and of the merge (r3d_scene_merge_sets): class k with value v becomes the best when
+// it is the first one or greater than the best so far -- the lowest class wins a tie, a NaN never replaces a value.
+static __device__ __forceinline__ void sc_argmax_step(int k, float v, int& best, float& best_v) {
+  if (best < 0 || v > best_v) {
+    best = k;
+    best_v = v;
+  }
+}
+
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
     int M, const int* __restrict__ skey, const int* __restrict__ pos, const int* __restrict__ cell,
     const int* __restrict__ blk_n, const int* __restrict__ chunk0, sc_grid g, int N, int K, const float* __restrict__ logits,
@@ -697,10 +707,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
     }
     scores[(long)p * K + k] = acc;
     if (k == 0) n_votes = cnt;
-    if (cnt > 0 && (best < 0 || acc > best_v)) {
-      best = k;
-      best_v = acc;
-    }
+    if (cnt > 0) sc_argmax_step(k, acc, best, best_v);
   }
   votes[p] = n_votes;
   labels[p] = best;
@@ -1078,6 +1085,65 @@ extern "C" int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx
               (void*)weights);
   return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
                      neighbours, weights, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ several support sets, one label
+// predict_scene_sets, step 10 ("Labelling a scan against several support sets"): scores (M, K, C) are the
+// voted (and transferred) scores of K support sets of C = n_way + 1 classes each.  One thread per scan point; a point has a
+// label when it has a vote or a transfer source.  Per set the arg-max l of its C scores by sc_argmax_step; a set with
+// l >= 1 claims the point with the margin m = s[l] - s[r], r the arg-max over the other classes by the same step, one fp32
+// subtraction; a NaN margin does not claim.  The greatest margin wins, the lowest set on equal margins.  Nothing is summed
+// and no thread reads what another writes.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_merge_sets_kernel(
+    int M, int K, int C, const float* __restrict__ scores, const int* __restrict__ votes,
+    const long long* __restrict__ source /* or null */, const int* __restrict__ classes, long long background,
+    long long* __restrict__ set_labels, long long* __restrict__ labels, int* __restrict__ set_of, float* __restrict__ margin) {
+  const int p = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (p >= M) return;
+  const bool has = votes[p] > 0 || (source && source[p] >= 0);
+  int win = -1, win_l = 0;
+  float win_m = 0.0f;
+  for (int k = 0; k < K; ++k) {
+    if (!has) {
+      set_labels[(long)p * K + k] = -1;
+      continue;
+    }
+    const float* s = scores + ((long)p * K + k) * C;
+    int l = -1, r = -1;
+    float lv = 0.0f, rv = 0.0f;
+    for (int j = 0; j < C; ++j) sc_argmax_step(j, s[j], l, lv);
+    set_labels[(long)p * K + k] = l;
+    if (l < 1) continue;  // the set says background
+    for (int j = 0; j < C; ++j)
+      if (j != l) sc_argmax_step(j, s[j], r, rv);
+    const float m = __fsub_rn(lv, rv);
+    if (m != m) continue;
+    if (win < 0 || m > win_m) {
+      win = k;
+      win_l = l;
+      win_m = m;
+    }
+  }
+  labels[p] = !has ? -1 : (win < 0 ? background : (long long)classes[win * (C - 1) + win_l - 1]);
+  set_of[p] = win;
+  margin[p] = win < 0 ? 0.0f : win_m;
+}
+
+extern "C" int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const float* scores, const int32_t* votes,
+                                    const int64_t* source, const int32_t* classes, long background, int64_t* set_labels,
+                                    int64_t* labels, int32_t* set_of, float* margin, void* stream) {
+  R3D_REQUIRE(scores && votes && classes && set_labels && labels && set_of && margin,
+              "r3d_scene_merge_sets: null pointer (scores %p, votes %p, classes %p, set_labels %p, labels %p, set_of %p, margin %p)",
+              (const void*)scores, (const void*)votes, (const void*)classes, (void*)set_labels, (void*)labels, (void*)set_of,
+              (void*)margin);
+  R3D_REQUIRE(M >= 1 && M <= (1L << 27), "r3d_scene_merge_sets: M %ld (1 .. 2^27)", M);
+  R3D_REQUIRE(n_sets >= 1 && n_classes >= 2 && (long)n_sets * n_classes <= 64,
+              "r3d_scene_merge_sets: %d sets of %d classes (at least 2 classes, at most 64 score columns)", n_sets, n_classes);
+  hipLaunchKernelGGL(r3d_scene_merge_sets_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (int)M, n_sets, n_classes, scores, votes, (const long long*)source, classes,
+                     (long long)background, (long long*)set_labels, (long long*)labels, set_of, margin);
+  R3D_LAUNCH_CHECK("r3d_scene_merge_sets");
+  return R3D_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ a support set from an annotated scan

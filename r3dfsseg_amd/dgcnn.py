@@ -345,6 +345,21 @@ class FewShotFeatures(nn.Module):
         return scene.predict_scene(self, fitted, scan, block_size, stride, min_points, groups_per_launch, launch,
                                    max_chunks_per_block, transfer)
 
+    def _query_features(self, query_x):
+        """The encoder pass of _predict_groups and _predict_groups_sets: query_x (G, n_q, C, N) -> point-major feature rows
+        (G * n_q * N, feat_dim), with the attention group of the episode [support set | one query group]."""
+        G, n_q = query_x.shape[0], query_x.shape[1]
+        return self.getFeatures_pm(query_x.reshape(G * n_q, self.in_channels, self.n_points),
+                                   group=self.n_way * self.k_shot + n_q)
+
+    def predict_scene_sets(self, fits, scan, classes=None, block_size=1.0, stride=None, min_points=100, groups_per_launch=32,
+                           launch=None, max_chunks_per_block=None, transfer=None, background=-1):
+        """predict_scene against K fitted support sets with one plan and one encoder pass per launch; per set the bits of
+        predict_scene, and one merged class id per point -> scene.SceneSetsResult (scene.py)."""
+        from . import scene
+        return scene.predict_scene_sets(self, fits, scan, classes, block_size, stride, min_points, groups_per_launch, launch,
+                                        max_chunks_per_block, transfer, background)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """Fit the support set from an annotated scan: `scan` as for predict_scene, labels (M,) class ids, way w =

@@ -68,14 +68,15 @@ class FittedSupport:
         self.n_queries = n_queries
         self.key = model_key(model)
 
-    def is_stale(self, model):
-        """Why this fit no longer belongs to `model` (a string), or None."""
+    def is_stale(self, model, key=None):
+        """Why this fit no longer belongs to `model` (a string), or None.  key: model_key(model) taken by the caller, who
+        checks several fits against one reading of the model (predict_scene_sets); default: read it here."""
         if id(model) != self.model_id or type(model).__name__ != self.model_class:
             return "it was fitted by another model object"
-        vk = version_key(model)
+        vk = version_key(model) if key is None else key[:2]
         if vk != self.key[:2]:
             return "parameters or running statistics were updated or replaced since fit_support (version counters)"
-        if content_sum(model) != self.key[2]:
+        if (content_sum(model) if key is None else key[2]) != self.key[2]:
             return "parameter or running-statistic values changed in place since fit_support (content sum)"
         return None
 
@@ -96,9 +97,9 @@ def check_fit_args(model, support_x, support_y):
     return model.n_way * model.k_shot
 
 
-def check_predict_args(model, fitted, query_x, query_y):
+def check_predict_args(model, fitted, query_x, query_y, key=None):
     """Raises before any launch.  -> (G, n_q, grouped): query_x is (n_q, C, N) -- one group, grouped False -- or
-    (G, n_q, C, N)."""
+    (G, n_q, C, N).  key: see FittedSupport.is_stale."""
     if model.training:
         raise NotImplementedError("predict is the inference path; call model.eval() first")
     if not isinstance(fitted, FittedSupport):
@@ -115,10 +116,47 @@ def check_predict_args(model, fitted, query_x, query_y):
     if query_y is not None and tuple(query_y.shape) != tuple(query_x.shape[:-2]) + (N,):
         raise ValueError("predict: query_y of shape %s does not label query_x of shape %s"
                          % (tuple(query_y.shape), tuple(query_x.shape)))
-    why = fitted.is_stale(model)
+    why = fitted.is_stale(model, key)
     if why is not None:
         raise ValueError("predict: stale fit -- %s; call fit_support again" % why)
     return (query_x.shape[0] if grouped else 1), query_x.shape[-3], grouped
+
+
+class FittedSets(tuple):
+    """K FittedSupports of one model, checked together (check_sets_args), as predict_scene_sets hands them to a launch.
+    table: what the model's head reads them through, built on the first launch and kept for the call -- the (K, n_way + 1,
+    D) prototype tables in one tensor (ProtoNet family) or the device table of addresses of ops.head_fit_table (MPTI)."""
+    table = None
+
+
+def check_sets_args(model, fits):
+    """predict_scene_sets' `fits`, before anything needs a device: a non-empty list or tuple of FittedSupports of this
+    model that hold its kind of table, K * (n_way + 1) <= 64, one schedule; every fit passes check_predict_args against ONE
+    reading of the model's key (one host read for a device model, not K).  -> FittedSets."""
+    if model.training:
+        raise NotImplementedError("predict_scene_sets is the inference path; call model.eval() first")
+    if not isinstance(fits, (list, tuple)) or len(fits) == 0:
+        raise ValueError("predict_scene_sets: `fits` must be a non-empty list or tuple of what fit() returned, got %s"
+                         % (type(fits).__name__ if not isinstance(fits, (list, tuple)) else "an empty one"))
+    K, C = len(fits), model.n_way + 1
+    if K * C > 64:
+        raise ValueError("predict_scene_sets: %d support sets of %d classes make %d score columns (at most 64)" % (K, C, K * C))
+    key = None
+    query = torch.empty(1, 1, model.in_channels, model.n_points, device="meta")  # a shape, no memory
+    for k, f in enumerate(fits):
+        if isinstance(f, FittedSupport) and key is None:
+            key = model_key(model)
+        try:
+            check_predict_args(model, f, query, None, key=key)
+        except ValueError as e:
+            raise ValueError("predict_scene_sets: fits[%d] -- %s" % (k, e)) from None
+        if getattr(f, model.fit_table) is None:
+            raise ValueError("predict_scene_sets: fits[%d] holds no %s (it was fitted by %s)"
+                             % (k, "MPTI head state" if model.fit_table == "head" else "prototype table", f.model_class))
+        if f.schedule != fits[0].schedule:
+            raise ValueError("predict_scene_sets: fits[%d] was fitted on the %s schedule, fits[0] on the %s one"
+                             % (k, f.schedule, fits[0].schedule))
+    return FittedSets(fits)
 
 
 def support_pair(data_or_support):
@@ -187,6 +225,25 @@ class FittedLearner(object):
             return self.model.predict_scene(fitted, scan, block_size, stride, min_points, groups_per_launch,
                                             launch=self._scene_launch, max_chunks_per_block=max_chunks_per_block,
                                             transfer=transfer)
+
+    def _scene_launch_sets(self, fits, query_x):
+        """One launch of predict_scene_sets: query_x (G, 1, C, N) -> (logits (G, K * (n_way + 1), N), redone)."""
+        return self.model._predict_groups_sets(fits, query_x).reshape(query_x.shape[0], -1, query_x.shape[-1]), False
+
+    def predict_scene_sets(self, scan, fits, classes=None, block_size=1.0, stride=None, min_points=100, groups_per_launch=32,
+                           max_chunks_per_block=None, transfer=None, background=-1):
+        """Label a whole scan against K fitted support sets at once -- fits: a list of what fit() returned, K * (n_way + 1)
+        <= 64 -- with ONE plan and ONE encoder pass per launch: scene.SceneSetsResult with, per set, the scores and labels
+        predict_scene(scan, fitted=fits[k], ...) gives bit for bit, and one merged class id per point (scene.py;
+        INTEGRATION.md, "Labelling a scan against several support sets").  classes: K sequences of n_way class ids, way w of
+        set k is classes[k][w - 1]; default k * n_way + (w - 1).  background: the id of a labelled point no set claims; the
+        default -1 is also the id of a point without a label -- `votes` and `set_labels` tell them apart.  The other
+        arguments are predict_scene's; head memory of MPTI grows with K * groups_per_launch (scene.py)."""
+        self.model.eval()
+        with torch.no_grad():
+            return self.model.predict_scene_sets(fits, scan, classes, block_size, stride, min_points, groups_per_launch,
+                                                 launch=self._scene_launch_sets, max_chunks_per_block=max_chunks_per_block,
+                                                 transfer=transfer, background=background)
 
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):

@@ -13,6 +13,8 @@ from .dgcnn import EpisodeSlot, FewShotFeatures  # noqa: F401  (EpisodeSlot: bat
 
 
 class MPTI_SelfAtten(FewShotFeatures):
+    fit_table = "head"  # the field of a fitted.FittedSupport this model's predict reads
+
     def __init__(self, args):
         super().__init__(args)
         self.n_subprototypes = args.n_subprototypes
@@ -159,19 +161,41 @@ class MPTI_SelfAtten(FewShotFeatures):
         propagation and the logits are _forward_eval's."""
         self._lp_force = bool(lp_iters)
         G, n_q, N = query_x.shape[0], query_x.shape[1], self.n_points
-        S = self.n_way * self.k_shot
-        feat = self.getFeatures_pm(query_x.reshape(G * n_q, self.in_channels, N), group=S + n_q)
+        feat = self._query_features(query_x)
         hb = self._head_buffers(n_q, feat.device, G)
         ops.head_attach_queries(hb, fitted.head, feat)
+        labels = query_y.reshape(G, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
+        logits, loss, pred = self._attached_head(hb, n_q, labels, lp_iters)
+        return logits.reshape(G, n_q, self.n_classes, N), loss.reshape(G), pred.reshape(G, n_q, N)
+
+    def _attached_head(self, hb, n_q, labels, lp_iters):
+        """What follows the attach in _predict_groups and _predict_groups_sets: the 201-NN graph, the label propagation and
+        the logits of hb's E systems, one launch sequence -> query_logits_ce's (logits, loss, pred)."""
         nbr = ops.knn_nodes(hb, exact=bool(lp_iters))
         if self.nbr_patch is not None:
             nbr = self.nbr_patch(nbr)
         ops.label_propagate(hb, nbr, self.sigma, 0.99, lp_iters or self._lp_next_budget(), self.lp_tol)
         self._lp_post(hb)
-        labels = query_y.reshape(G, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
-        logits, loss, pred = ops.query_logits_ce(hb, n_q, self.n_classes, labels)
-        self.num_prototypes_dev = hb.desc.view(G, 32)[:, ops.HD_N_PROTO]
-        return logits.reshape(G, n_q, self.n_classes, N), loss.reshape(G), pred.reshape(G, n_q, N)
+        out = ops.query_logits_ce(hb, n_q, self.n_classes, labels)
+        self.num_prototypes_dev = hb.desc.view(hb.E, 32)[:, ops.HD_N_PROTO]
+        return out
+
+    def _predict_groups_sets(self, fits, query_x, lp_iters=None):
+        """_predict_groups against K fitted systems with ONE encoder pass and ONE head sequence: fits: fitted.FittedSets (or
+        a list of FittedSupports), query_x (G, n_q, C, N) -> logits (G, K, n_q, n_way + 1, N); [:, k] has the bits of
+        _predict_groups(fits[k], query_x, None, lp_iters).  The K * G systems [prototypes of fit k | query rows of group g]
+        are ordered group-major (system g * K + k) in a HeadBuffers of E = K * G; lp_converged() then speaks for all."""
+        from . import fitted as F
+        fits = fits if isinstance(fits, F.FittedSets) else F.FittedSets(fits)
+        self._lp_force = bool(lp_iters)
+        G, n_q, N, K = query_x.shape[0], query_x.shape[1], self.n_points, len(fits)
+        feat = self._query_features(query_x)
+        if fits.table is None:
+            fits.table = ops.head_fit_table([f.head for f in fits], feat.device)
+        hb = self._head_buffers(n_q, feat.device, G * K)
+        ops.head_attach_queries_sets(hb, [f.head for f in fits], fits.table, feat)
+        logits = self._attached_head(hb, n_q, None, lp_iters)[0]
+        return logits.reshape(G, K, n_q, self.n_classes, N)
 
     def predict(self, fitted, query_x, query_y=None, lp_iters=None):
         """Segment query clouds against a fitted support set: query_x (n_q, C, N) -> (logits (n_q, n_way + 1, N), loss), or

@@ -209,6 +209,18 @@ class MPTILearner_V3(FittedLearner):
             raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
         return logits, True
 
+    def _scene_launch_sets(self, fits, query_x):
+        """_scene_launch for K support sets: lp_converged() speaks for the K * G systems of the launch, and a miss redoes
+        all of them."""
+        flat = lambda z: z.reshape(query_x.shape[0], -1, query_x.shape[-1])
+        logits = self.model._predict_groups_sets(fits, query_x)
+        if self.model.lp_converged():
+            return flat(logits), False
+        logits = self.model._predict_groups_sets(fits, query_x, lp_iters=self.model.lp_max_iter)
+        if not self.model.lp_converged():
+            raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
+        return flat(logits), True
+
     def _test_graph(self, data, eval):
         from .episode_graph import EpisodeGraphs
         episode = list(data[:4])

@@ -579,6 +579,58 @@ def head_attach_queries(hb, fit, qfeat_pm, q_sys_rows=None):
             _p(hb.Y), _p(hb.desc), 32, _p(hb.cluster_count), hb.n_cap, _st()))
 
 
+def protonet_similarity_sets(qfeat_pm, tables, n_way, method, n_groups, n_query_pts, q_sys_rows=None, scaler=10.0):
+    """protonet_similarity of n_groups query groups against K prototype tables in ONE launch that reads a query row once:
+    tables (K, n_way + 1, D) contiguous, K * (n_way + 1) <= 64.  -> Z (n_groups * K * n_query_pts, 4) per plane, system
+    g * K + k (group g, table k) after system g * K + k - 1; per table the bits of protonet_similarity on it alone."""
+    _, ldq = _rows(qfeat_pm)
+    D = qfeat_pm.shape[1]
+    code = _proto_method(method)
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.dim() == 3 and tables.shape[1:] == (n_way + 1, D)
+    K = tables.shape[0]
+    assert K * (n_way + 1) <= 64, "at most 64 prototype rows"
+    assert qfeat_pm.shape[0] >= (n_groups - 1) * (q_sys_rows or n_query_pts) + n_query_pts
+    Z = torch.empty((1 if n_way <= 3 else 2) * n_groups * K * n_query_pts, 4, device=qfeat_pm.device, dtype=torch.float32)
+    with _timed("protonet_similarity"):
+        _lib.check(_lib.load().r3d_protonet_similarity_sets(
+            n_groups, K, _p(qfeat_pm), ldq, n_query_pts if q_sys_rows is None else q_sys_rows, D, _p(tables), (n_way + 1) * D,
+            n_way, n_query_pts, code, float(scaler), _p(Z), _st()))
+    return Z
+
+
+def head_fit_table(fits, device):
+    """The device table r3d_head_attach_queries_sets reads: per fitted.FittedHead the addresses of its nodes, label rows,
+    desc and cluster counts, (K, 4) int64.  The fits must share pitch, label rows and prototype capacity (fits of one
+    model do) and stay alive while the table is used."""
+    f0 = fits[0]
+    rows = []
+    for f in fits:
+        assert (f.nodes.stride(0), f.nodes.shape[1], f.label_rows, f.proto_cap) == \
+            (f0.nodes.stride(0), f0.nodes.shape[1], f0.label_rows, f0.proto_cap), "fits of different geometry"
+        assert f.nodes.dtype == torch.float32 and f.Y.dtype == torch.float32 and f.desc.dtype == torch.int32
+        assert f.nodes.data_ptr() % 16 == 0 and f.Y.data_ptr() % 16 == 0 and f.nodes.stride(0) % 4 == 0
+        assert f.Y.numel() >= 4 * f.label_rows and f.desc.numel() >= 32 and f.cluster_count.numel() >= f.proto_cap
+        rows.append([f.nodes.data_ptr(), f.Y.data_ptr(), f.desc.data_ptr(), f.cluster_count.data_ptr()])
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def head_attach_queries_sets(hb, fits, table, qfeat_pm, q_sys_rows=None):
+    """head_attach_queries for K fits at once: hb.E = G * K systems, system g * K + k from fits[k] and query group g, one
+    launch.  table: head_fit_table(fits).  Per system the bits head_attach_queries gives it."""
+    _, ldq = _rows(qfeat_pm)
+    K, f0 = len(fits), fits[0]
+    assert tuple(table.shape) == (K, 4) and table.dtype == torch.int64 and table.is_cuda and table.is_contiguous()
+    assert hb.E % K == 0 and qfeat_pm.shape[1] == hb.D and f0.nodes.shape[1] == hb.D
+    G = hb.E // K
+    step = hb.n_q_pts if q_sys_rows is None else q_sys_rows
+    assert qfeat_pm.shape[0] >= (G - 1) * step + hb.n_q_pts
+    with _timed("head_attach_queries"):
+        _lib.check(_lib.load().r3d_head_attach_queries_sets(
+            G, K, _p(table), f0.nodes.stride(0), f0.label_rows, f0.proto_cap, _p(qfeat_pm), ldq, step, hb.n_way, hb.D,
+            hb.n_q_pts, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap, _p(hb.Y), _p(hb.desc), 32, _p(hb.cluster_count), hb.n_cap,
+            _st()))
+
+
 def protonet_head_train(sfeat_pm, qfeat_pm, support_y, n_way, k_shot, N, method, scaler=10.0, n_ep=1, feat_ep_rows=0,
                         n_query_pts=None):
     """Training forward of the ProtoNet head -> (Z, ws): the similarity rows of protonet_head (n_ep > 1: (n_ep * n_query_pts, 4)
@@ -781,6 +833,26 @@ def scene_transfer_idw(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes
                                                   scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source),
                                                   _p(neighbours), _p(weights), _st()))
     return source, neighbours, weights
+
+
+# ---- predict_scene_sets: the scores of K support sets merged into one label per point
+def scene_merge_sets(scores, votes, source, classes, background):
+    """scores (M, K, C) fp32 contiguous (C = n_way + 1, K * C <= 64), votes (M,) int32, source (M,) int64 or None, classes
+    (K, C - 1) int32 on the device, background: an int -> (set_labels (M, K) int64, labels (M,) int64, set_of (M,) int32,
+    margin (M,) fp32): step 10 of predict_scene_sets (r3d_scene_merge_sets in include/r3d.h)."""
+    assert scores.dim() == 3 and scores.dtype == torch.float32 and scores.is_contiguous() and scores.is_cuda
+    M, K, C = scores.shape
+    assert tuple(votes.shape) == (M,) and votes.dtype == torch.int32 and votes.is_contiguous()
+    assert source is None or (tuple(source.shape) == (M,) and source.dtype == torch.int64 and source.is_contiguous())
+    assert tuple(classes.shape) == (K, C - 1) and classes.dtype == torch.int32 and classes.is_contiguous() and classes.is_cuda
+    dev = scores.device
+    set_labels = torch.empty(M, K, device=dev, dtype=torch.int64)
+    labels = torch.empty(M, device=dev, dtype=torch.int64)
+    set_of = torch.empty(M, device=dev, dtype=torch.int32)
+    margin = torch.empty(M, device=dev, dtype=torch.float32)
+    _lib.check(_lib.load().r3d_scene_merge_sets(M, K, C, _p(scores), _p(votes), _p(source), _p(classes), int(background),
+                                                _p(set_labels), _p(labels), _p(set_of), _p(margin), _st()))
+    return set_labels, labels, set_of, margin
 
 
 # ---- fit_scene: the support set from an annotated scan (scene_support.py)

@@ -14,6 +14,7 @@ from .dgcnn import FewShotFeatures
 
 class ProtoNet(FewShotFeatures):
     detect_clean_shots = False  # ProtoNet_Contrast: the clean-shot detection decides which shots form a way's prototype
+    fit_table = "protos"        # the field of a fitted.FittedSupport this model's predict reads
 
     def __init__(self, args):
         super().__init__(args)
@@ -85,11 +86,23 @@ class ProtoNet(FewShotFeatures):
         """query_x (G, n_q, C, N), query_y (G, n_q, N) or None -> logits (G, n_q, n_way + 1, N), loss (G,), pred (G, n_q, N)
         int32: G groups against ONE fitted table in one launch sequence (encoder over the G n_q query clouds, similarity)."""
         G, n_q, N = query_x.shape[0], query_x.shape[1], self.n_points
-        S = self.n_way * self.k_shot
-        feat = self.getFeatures_pm(query_x.reshape(G * n_q, self.in_channels, N), group=S + n_q)
+        feat = self._query_features(query_x)
         Z = ops.protonet_similarity(feat, fitted.protos, self.n_way, self.dist_method, G, n_q * N)
         labels = query_y.reshape(G, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
         return ops.logits_ce_from_rows(Z, G, n_q, N, self.n_way + 1, labels)
+
+    def _predict_groups_sets(self, fits, query_x, lp_iters=None):
+        """_predict_groups against K fitted tables with ONE encoder pass: fits: fitted.FittedSets (or a list of
+        FittedSupports), query_x (G, n_q, C, N) -> logits (G, K, n_q, n_way + 1, N); [:, k] has the bits of
+        _predict_groups(fits[k], query_x).  One similarity launch scores every query row against all K tables."""
+        from . import fitted as F
+        fits = fits if isinstance(fits, F.FittedSets) else F.FittedSets(fits)
+        if fits.table is None:
+            fits.table = torch.cat([f.protos.reshape(1, self.n_way + 1, -1) for f in fits]).contiguous()
+        G, n_q, N, K = query_x.shape[0], query_x.shape[1], self.n_points, len(fits)
+        feat = self._query_features(query_x)
+        Z = ops.protonet_similarity_sets(feat, fits.table, self.n_way, self.dist_method, G, n_q * N)
+        return ops.logits_ce_from_rows(Z, G * K, n_q, N, self.n_way + 1, None)[0].reshape(G, K, n_q, self.n_way + 1, N)
 
     def predict(self, fitted, query_x, query_y=None, lp_iters=None):
         """Segment query clouds against a fitted support set: query_x (n_q, C, N) -> (logits (n_q, n_way + 1, N), loss), or

@@ -22,6 +22,11 @@ point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receiver
 transfer="idw" (step 9') gives it the mean logits of the three nearest such points, weighted by 1 / (d + 1e-8) with d the
 squared distance, and the arg-max of those (r3d_scene_transfer_idw: same receivers, same candidates, same host read).
 
+predict_scene_sets labels the scan against K fitted support sets at once ("Labelling a scan against several
+support sets"): steps 1-6 once, per launch one encoder pass and the K heads on its feature rows (step 7s), the vote and the
+transfer on logits of K * (n_way + 1) columns, and one merged class id per point (step 10, r3d_scene_merge_sets); per set
+the bits of predict_scene.
+
 This module holds the host logic; the kernels are csrc/scene.hip.  The logits of the chunks that run are kept ((n_chunks,
 n_way + 1, N) floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory
 and one more pass over the scores per launch."""
@@ -216,11 +221,26 @@ def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=1
                                                   max_chunks_per_block, transfer)
     if launch is None:
         launch = lambda f, qx: (model._predict_groups(f, qx, None)[0], False)
-    scan = scan.cuda()
-    C, N, K = model.in_channels, model.n_points, model.n_way + 1
+    # once: stale fit, shapes, mode -- before the first scene launch
+    check = lambda buf: F.check_predict_args(model, fitted, buf[:, None], None)
+    plan, scores, labels, votes, redone, source, n_transferred, extra = _voted_scan(
+        model, fitted, launch, model.n_way + 1, scan.cuda(), rgb_ch, XYZ_ch, block_size, stride, min_points, groups_per_launch,
+        max_chunks_per_block, transfer, check)
+    return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_run, plan.M - plan.n_voted - n_transferred, redone,
+                       source, n_transferred, plan.n_skipped, *extra)
+
+
+def _voted_scan(model, fitted, launch, n_cols, scan, rgb_ch, XYZ_ch, block_size, stride, min_points, groups_per_launch,
+                max_chunks_per_block, transfer, check=None):
+    """Steps 1-9' for a scan on the device, shared by predict_scene and predict_scene_sets: the plan, per launch the
+    prepared chunks and launch(fitted, query_x (G, 1, C, N)) -> (logits that reshape to (G, n_cols, N), redone), the vote
+    over the (n_run, n_cols, N) logits and the transfer.  -> (plan, scores (M, n_cols), labels, votes, redone, source,
+    n_transferred, extra: () or (neighbours, weights))."""
+    C, N, K = model.in_channels, model.n_points, n_cols
     G_max = int(groups_per_launch)
     buf = staging(G_max, C, N, scan.device)
-    F.check_predict_args(model, fitted, buf[:, None], None)  # once: stale fit, shapes, mode -- before the first scene launch
+    if check is not None:
+        check(buf)
     plan = ScenePlan(scan, N, block_size, stride, min_points, max_chunks_per_block)
     logits = torch.empty(plan.n_run, K, N, device=scan.device, dtype=torch.float32)
     redone = 0
@@ -235,5 +255,79 @@ def predict_scene(model, fitted, scan, block_size=1.0, stride=None, min_points=1
     if transfer is not None:
         source, count, *extra = plan.transfer(scores, labels, votes, transfer)  # "idw": neighbours and weights as well
         n_transferred = int(count.item())  # the one host read the transfer adds, after everything is queued
-    return SceneResult(labels, scores, votes, plan.n_blocks, plan.n_run, plan.M - plan.n_voted - n_transferred, redone,
-                       source, n_transferred, plan.n_skipped, *extra)
+    return plan, scores, labels, votes, redone, source, n_transferred, tuple(extra)
+
+
+class SceneSetsResult:
+    """What predict_scene_sets returns for K support sets of n_way classes.  On the device: scores (M, K, n_way + 1) fp32 and
+    set_labels (M, K) int64 -- [:, k] are the scores and labels predict_scene gives against set k alone, bit for bit --;
+    votes (M,) int32, one plan so one count for all sets; labels (M,) int64, the merged class id: classes[k][l - 1] of the
+    set k that claims the point with the greatest margin, `background` for a labelled point no set claims, -1 for a point
+    without a label (the default background is -1 too: votes and set_labels tell the two apart); set_of (M,) int32, that
+    set, or -1; margin (M,) fp32, its margin, 0 where set_of == -1; source, neighbours, weights: as in SceneResult.  Host
+    ints with SceneResult's meaning: n_blocks, n_chunks, n_unlabelled (points without a label), redone, n_transferred,
+    n_chunks_skipped."""
+
+    def __init__(self, scores, set_labels, votes, labels, set_of, margin, n_blocks, n_chunks, n_unlabelled, redone, source=None,
+                 n_transferred=0, n_chunks_skipped=0, neighbours=None, weights=None):
+        self.scores, self.set_labels, self.votes = scores, set_labels, votes
+        self.labels, self.set_of, self.margin = labels, set_of, margin
+        self.n_blocks, self.n_chunks, self.n_unlabelled, self.redone = n_blocks, n_chunks, n_unlabelled, redone
+        self.source, self.n_transferred, self.n_chunks_skipped = source, n_transferred, n_chunks_skipped
+        self.neighbours, self.weights = neighbours, weights
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_sets_classes(K, n_way, classes, background):
+    """-> the (K, n_way) int32 class table of predict_scene_sets (classes None: k * n_way + w - 1); raises ValueError."""
+    if not _is_int(background) or not -2 ** 63 <= int(background) < 2 ** 63:
+        raise ValueError("predict_scene_sets: background %r must be an integer that fits int64" % (background,))
+    if classes is None:
+        return np.arange(K * n_way, dtype=np.int32).reshape(K, n_way)
+    ok = isinstance(classes, (list, tuple, np.ndarray)) and len(classes) == K and all(
+        isinstance(row, (list, tuple, np.ndarray)) and len(row) == n_way and
+        all(_is_int(v) and -2 ** 31 <= int(v) < 2 ** 31 for v in row) for row in classes)
+    if not ok:
+        raise ValueError("predict_scene_sets: classes must be None or %d sequences (one per support set) of n_way = %d "
+                         "integers that fit int32, got %r" % (K, n_way, classes))
+    return np.array([[int(v) for v in row] for row in classes], dtype=np.int32).reshape(K, n_way)
+
+
+def predict_scene_sets(model, fits, scan, classes=None, block_size=1.0, stride=None, min_points=100, groups_per_launch=32,
+                       launch=None, max_chunks_per_block=None, transfer=None, background=-1):
+    """model.predict_scene_sets: one scan against K fitted support sets ("Labelling a scan against several
+    support sets").  Steps 1-6, 7a, 8, 8', 9, 9' are predict_scene's, run ONCE: one plan, one staging buffer, every chunk
+    prepared once.  Step 7s: per launch of G chunks one encoder pass, then the heads of the K sets on those feature rows;
+    the launch's logits lie as (G, K * (n_way + 1), N), set k in columns k * (n_way + 1) .. k * (n_way + 1) + n_way, and the
+    vote and the transfer take the (n_run, K * (n_way + 1), N) buffer as it is -- no column of theirs depends on another,
+    so set k's scores have the bits predict_scene gives against fits[k].  Step 10: r3d_scene_merge_sets, one label per point.
+
+    launch(fits: fitted.FittedSets, query_x (G, 1, C, N)) -> (logits (G, K * (n_way + 1), N), redone: bool); the default is
+    the model's own _predict_groups_sets, the learners pass theirs (MPTI: a launch in which any of the K * G systems missed
+    is redone as a whole, as in predict_scene).
+
+    Memory: the logits buffer is K times predict_scene's.  MPTI's head works on E = K * groups_per_launch systems at once
+    (ops.HeadBuffers): with n_cap = (n_way + 1) * (n_subprototypes + 1) + n_points and kp1 = k_connect + 1, about
+    E * (n_cap * (4 * feat_dim + 32 * planes + 4 * kp1) + 4 * r3d_lp_ws_words(n_cap, kp1)) bytes (node rows, label and
+    result rows, the 201-NN lists, the solver's workspace; planes = 1 up to 3 ways, else 2).  Lower groups_per_launch when
+    that is too much for the device: it is never lowered silently."""
+    from . import fitted as F
+    scan, r, s, rgb_ch, XYZ_ch = check_scene_args(model, scan, block_size, stride, min_points, groups_per_launch,
+                                                  max_chunks_per_block, transfer)
+    fits = F.check_sets_args(model, fits)
+    K, C = len(fits), model.n_way + 1
+    table = check_sets_classes(K, model.n_way, classes, background)
+    if launch is None:
+        launch = lambda f, qx: (model._predict_groups_sets(f, qx).reshape(qx.shape[0], K * C, qx.shape[-1]), False)
+    scan = scan.cuda()
+    plan, scores, _, votes, redone, source, n_transferred, extra = _voted_scan(
+        model, fits, launch, K * C, scan, rgb_ch, XYZ_ch, block_size, stride, min_points, groups_per_launch,
+        max_chunks_per_block, transfer)
+    scores = scores.view(plan.M, K, C)
+    set_labels, labels, set_of, margin = ops.scene_merge_sets(scores, votes, source, torch.from_numpy(table).to(scan.device),
+                                                              int(background))
+    return SceneSetsResult(scores, set_labels, votes, labels, set_of, margin, plan.n_blocks, plan.n_run,
+                           plan.M - plan.n_voted - n_transferred, redone, source, n_transferred, plan.n_skipped, *extra)
