@@ -415,7 +415,17 @@ int r3d_train_metrics_batched(int n_ep, const int32_t* pred, const int64_t* quer
  * Per shot: box means of foreground features at scales (1,1,1) and (2,2,1) -> cosine map ->
  * majority vote -> shot_keep (n_way*k_shot) int32 (0 = drop the shot's foreground).
  * Per episode: feat (S*N, ldf), episode e feat_ep_rows rows further on; support_x (S, Cin, N); support_y (S, N);
- * dbg_cos_sum optional (n_way, 2, 4*k_shot); ws: r3d_clean_ws_words int32 words, episode e at ws + e * ws_stride. */
+ * dbg_cos_sum optional (n_way, 2, 4*k_shot); ws: r3d_clean_ws_words int32 words, episode e at ws + e * ws_stride.
+ * The vote: a seed is a non-empty box (bounds in fp32, inclusive on both sides: a point on a split plane lies in two
+ * boxes); per way and scale a seed votes "clean" when its row sum is ABOVE the mean of the way's row sums, a shot's flag at
+ * that scale is 1 when MORE than half of its seeds do, and the shot is dropped when the mean of its two flags is below 0.5.
+ * A shot WITHOUT a seed at a scale -- no foreground point, which the reference cannot run on -- takes flag 0 at that
+ * scale (so it is dropped while its way keeps another shot); a way that would lose every shot, a way without any
+ * foreground included, keeps all of them.  dbg_cos_sum receives the row sums of the seeds that exist, entry
+ * [way][scale][i] for seed i in shot order then box order, and is left untouched beyond them.
+ * Layout of ws after the call (the tests read it; S = n_way*k_shot): box_sum (S, 5, 256) fp32 -- per shot and box the sum
+ * of the foreground rows inside the box, channels >= D zero; box 0 is scale (1,1,1), boxes 1..4 scale (2,2,1), x outer,
+ * y inner -- then, S*5*256 words in, box_cnt (S, 5) int32, the number of those rows.  The words beyond are not written. */
 long r3d_clean_ws_words(int n_way, int k_shot);
 int r3d_clean_shot_detect_batched(int n_ep, const float* feat, long ldf, long feat_ep_rows, int D, const float* support_x,
                                   int Cin, const int32_t* support_y, int n_way, int k_shot, int N, int32_t* shot_keep,
@@ -504,7 +514,10 @@ int r3d_protonet_head_bwd(int n_ep, const float* qfeat, long ldq, long feat_ep_r
                           int k_shot, int N, int n_query_pts, int method, float scaler, const float* dZ, float* dsfeat,
                           long ldds, float* dqfeat, long lddq, long dfeat_ep_rows, float* ws, long ws_words, void* stream);
 
-/* ---- mIoU accumulator (eval_noise.py:23-72): hist (3, n_classes) uint64 = GT | predicted | TP */
+/* ---- mIoU accumulator (eval_noise.py:23-72): hist (3, n_classes) uint64 = GT | predicted | TP, ADDED to what hist holds.
+ * lut (n_lut) int32: test-class index of an episode label (0 = background).  A label or prediction outside [0, n_lut) is
+ * CLAMPED into the table -- negative to entry 0, too large to entry n_lut - 1 -- before the look-up; a true positive is
+ * gt == pred before clamping, counted under the ground truth's entry.  Every lut entry must lie in [0, n_classes). */
 int r3d_miou_accumulate(const int32_t* pred, const int64_t* gt, long n, const int32_t* lut, int n_lut, int n_classes,
                         uint64_t* hist, void* stream);
 

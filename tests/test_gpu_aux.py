@@ -34,16 +34,18 @@ def test_clean_shot_detection_vs_oracle(noise, seed):
     sfeat = ops.pm_to_cm(feat, Sn, 512).cpu().view(2, 5, 192, 512)
     pl, clean_flag = O.mean_pl_support_y_multi_scale(sfeat, sy, sx)
     assert torch.equal(keep.cpu().view(2, 5).float(), clean_flag), (keep.cpu().view(2, 5), clean_flag)
-    # real-valued intermediate: row sums of the cosine map at scale (1,1,1)
+    # real-valued intermediate: row sums of the cosine map at scale (1,1,1) (cubed) and at scale (2,2,1)
     for way in range(2):
-        seeds = []
-        for k in range(5):
-            fg = sy[way, k] == 1
-            s, _, _ = O.grid_sampling(sx[way, k][:, fg].t(), sfeat[way, k][:, fg].t(), 1, 1, 1)
-            seeds.append(s)
-        sd_ = torch.nn.functional.normalize(torch.cat(seeds, 0), p=2, dim=1)
-        cos = (sd_ @ sd_.t() * (1 - torch.eye(len(sd_)))).pow(3).sum(1)
-        np.testing.assert_allclose(dbg[way, 0, :len(cos)].cpu().numpy(), cos.numpy(), atol=1e-4, rtol=1e-4)
+        for scale, n in enumerate((1, 2)):
+            seeds = []
+            for k in range(5):
+                fg = sy[way, k] == 1
+                s, _, _ = O.grid_sampling(sx[way, k][:, fg].t(), sfeat[way, k][:, fg].t(), n, n, 1)
+                seeds.append(s)
+            sd_ = torch.nn.functional.normalize(torch.cat(seeds, 0), p=2, dim=1)
+            cos = sd_ @ sd_.t() * (1 - torch.eye(len(sd_)))
+            cos = (cos.pow(3) if n == 1 else cos).sum(1)
+            np.testing.assert_allclose(dbg[way, scale, :len(cos)].cpu().numpy(), cos.numpy(), atol=1e-4, rtol=1e-4)
 
 
 def test_mpti_forward_eval_true_vs_oracle():
