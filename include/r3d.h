@@ -700,6 +700,53 @@ int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy
                              float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, const void* labels,
                              int label_bytes, const int32_t* cloud_class, int32_t* mask, void* stream);
 
+/* ---- pool_segments: one label per user-given segment of the scan ("Pooling scores over segments", P1-P5).
+ * Additive: the entry points above and what they compute are as they were.  Replaces what a caller would write in torch as
+ * a sort plus index_add_ -- floating-point atomics, a summation order that changes from run to run -- with sums in a
+ * defined order: the reference has no such step, the definition is this project's.
+ * segments: M ids, int32 (seg_bytes 4) or int64 (8), read as they are; g < 0: the point is in no segment; legal ids are
+ * 0 .. 2^31 - 2.  ws: ONE int32 scratch of r3d_scene_seg_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the four
+ * calls of one pooling; its first 16 words are the record the host reads:
+ *   [0] largest legal id + 1 (0: none)   [1] negative ids   [2] ids >= 2^31 - 1   [4..5] the largest of those (uint64)
+ *   [6] segments S   [7] contributors   [8] tiles   [9] pooled points   [10] pooled points whose label was -1
+ *   [11] labels that are -1 in the result
+ *
+ *   entry point           what it does                                                                   host reads
+ *   r3d_scene_seg_ids     zeroes the record, then words 0 .. 5 of it (integer maxima and counts)          words 0 .. 5
+ *   r3d_scene_seg_group   max_id, n_negative: words 0 (less one) and 1 as read.  Stable LSD radix sort of
+ *                         (id, scan index), the kernels of r3d_scene_plan, 8 bits a pass up to the highest
+ *                         set bit of the largest key (1 .. 4 passes); a negative id sorts under the key
+ *                         max_id + 1.  CONTRIBUTOR: a point in a segment with votes > 0.  Segment rows are in
+ *                         ascending id order; segment_index (M,) int32: the row of a point's segment, -1
+ *                         without one.  Contributors of a segment by ascending scan index, cut into TILES
+ *                         of 256 ranks; tiles never span two segments.                                   words 6 .. 8
+ *   r3d_scene_seg_pool    n_segments, n_tiles: words 6 and 8 as read; part: n_tiles * n_cols floats of
+ *                         scratch.  Row of contributor p: c[j] = scores[p][j] / (float)votes[p].  Tile:
+ *                         part = c of its first rank, then += the next, one fp32 addition at a time; segment:
+ *                         tot = its first tile's part, then += the next; seg_scores = tot / (float)members,
+ *                         zeros without a member.  seg_labels (may be NULL): the arg-max with the comparison
+ *                         of r3d_scene_vote, -1 without a member.  seg_ids (S,) int64, seg_points (every
+ *                         point with the id) and seg_members (contributors) (S,) int32.  One wave per tile,
+ *                         rows staged in LDS, lane j adds column j; one wave per segment.  No float atomics.  -
+ *   r3d_scene_seg_spread  point p with segment_index s >= 0 and seg_members[s] >= min_members is POOLED: it
+ *                         takes seg_scores[s], seg_labels[s] and, with n_sets > 0 (then the set fields are
+ *                         needed, else NULL), seg_set_labels / seg_set_of / seg_margin; any other point the
+ *                         in_* fields of its own row.  pooled (M,) bytes 0 / 1.  One thread per point decides,
+ *                         the workgroup copies the rows; one integer atomic per count and workgroup.    words 9 .. 11 */
+long r3d_scene_seg_ws_words(long M);
+int r3d_scene_seg_ids(const void* segments, int seg_bytes, long M, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_seg_group(const void* segments, int seg_bytes, long M, const int32_t* votes, long max_id, long n_negative,
+                        int32_t* segment_index, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_seg_pool(long M, int n_cols, const float* scores, const int32_t* votes, long n_segments, long n_tiles,
+                       const int32_t* ws, long ws_words, float* part, int64_t* seg_ids, int32_t* seg_points,
+                       int32_t* seg_members, float* seg_scores, int64_t* seg_labels, void* stream);
+int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int min_members, const int32_t* segment_index,
+                         const int32_t* seg_members, const float* seg_scores, const int64_t* seg_labels,
+                         const int64_t* seg_set_labels, const int32_t* seg_set_of, const float* seg_margin,
+                         const float* in_scores, const int64_t* in_labels, const int64_t* in_set_labels,
+                         const int32_t* in_set_of, const float* in_margin, float* scores, int64_t* labels, uint8_t* pooled,
+                         int64_t* set_labels, int32_t* set_of, float* margin, int32_t* ws, long ws_words, void* stream);
+
 /* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.

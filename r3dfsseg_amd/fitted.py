@@ -245,6 +245,17 @@ class FittedLearner(object):
                                                  launch=self._scene_launch_sets, max_chunks_per_block=max_chunks_per_block,
                                                  transfer=transfer, background=background)
 
+    def pool_segments(self, res, segments, min_members=1, classes=None, background=-1):
+        """One label per segment of a labelled scan: res is what predict_scene or predict_scene_sets returned, segments (M,)
+        int32 or int64 ids of a partition of its points (instances, supervoxels; negative: in no segment; host or device).
+        Per segment the mean logits of its voted points, summed in a fixed order, and their arg-max; every point of a
+        segment with at least min_members voted points takes them, any other point keeps what res holds: a
+        scene_segments.SegmentResult (scene_segments.py; INTEGRATION.md, "Pooling scores over segments").  classes and
+        background: those of the predict_scene_sets call, for its result only.  Needs no fit and changes neither res nor the
+        learner."""
+        from . import scene_segments
+        return scene_segments.pool_segments(res, segments, min_members, classes, background)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

@@ -911,6 +911,94 @@ def scene_prepare_blocks(scan, ncx, ncy, r, N, chunk_cap, ws, blocks, out, rgb_c
     return out
 
 
+# ---- pool_segments: scores pooled over user-given segments (scene_segments.py)
+SCENE_SEG_TILE = 256   # SG_TILE of csrc/scene.hip: contributor ranks per tile
+SCENE_SEG_REC = 16     # words of the record in front of the workspace
+# the record's words (include/r3d.h, "pool_segments")
+SEG_R_MAX1, SEG_R_NNEG, SEG_R_NBAD, SEG_R_BADMAX, SEG_R_S, SEG_R_NCONTRIB, SEG_R_NTILES = 0, 1, 2, 4, 6, 7, 8
+SEG_R_NPOOLED, SEG_R_NFILLED, SEG_R_NUNLAB = 9, 10, 11
+
+
+def scene_seg_workspace(M, device):
+    """-> ws, int32 of r3d_scene_seg_ws_words(M) words: the one scratch of a pool_segments call, its record in front."""
+    words = _lib.load().r3d_scene_seg_ws_words(M)
+    if words < 0:
+        raise ValueError("pool_segments: %d points (1 .. 2^27)" % M)
+    return torch.empty(words, device=device, dtype=torch.int32)
+
+
+def _seg_ws_ok(ws):
+    return ws.is_cuda and ws.dtype == torch.int32 and ws.is_contiguous() and ws.dim() == 1
+
+
+def scene_seg_ids(segments, ws):
+    """segments (M,) int32 or int64 on the device, read as they are -> words 0 .. 5 of the record in ws, on the device."""
+    M = segments.numel()
+    assert _seg_ws_ok(ws)
+    _lib.check(_lib.load().r3d_scene_seg_ids(_p(segments), _label_bytes(segments, M), M, _p(ws), ws.numel(), _st()))
+
+
+def scene_seg_group(segments, votes, max_id, n_negative, ws):
+    """After scene_seg_ids and the read of its record: the sort by (id, scan index), the segment and tile tables into ws,
+    words 6 .. 8 of the record -> segment_index (M,) int32."""
+    M = segments.numel()
+    assert _seg_ws_ok(ws)
+    assert tuple(votes.shape) == (M,) and votes.dtype == torch.int32 and votes.is_contiguous() and votes.is_cuda
+    segment_index = torch.empty(M, device=segments.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_seg_group(_p(segments), _label_bytes(segments, M), M, _p(votes), int(max_id), int(n_negative),
+                                               _p(segment_index), _p(ws), ws.numel(), _st()))
+    return segment_index
+
+
+def scene_seg_pool(scores, votes, n_segments, n_tiles, ws, want_labels=True):
+    """scores (M, cols) fp32 contiguous, cols <= 64; n_segments, n_tiles as read from the record -> (segment_ids (S,) int64,
+    segment_points (S,) int32, segment_members (S,) int32, segment_scores (S, cols) fp32, segment_labels (S,) int64 or None)."""
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.is_contiguous() and scores.is_cuda
+    M, C = scores.shape
+    assert tuple(votes.shape) == (M,) and votes.dtype == torch.int32 and votes.is_contiguous() and _seg_ws_ok(ws)
+    dev, S = scores.device, int(n_segments)
+    part = torch.empty(int(n_tiles), C, device=dev, dtype=torch.float32)
+    ids = torch.empty(S, device=dev, dtype=torch.int64)
+    points = torch.empty(S, device=dev, dtype=torch.int32)
+    members = torch.empty(S, device=dev, dtype=torch.int32)
+    seg_scores = torch.empty(S, C, device=dev, dtype=torch.float32)
+    seg_labels = torch.empty(S, device=dev, dtype=torch.int64) if want_labels else None
+    nz = lambda t: _p(t) if t is not None and t.numel() else None
+    _lib.check(_lib.load().r3d_scene_seg_pool(M, C, _p(scores), _p(votes), S, int(n_tiles), _p(ws), ws.numel(), nz(part), nz(ids),
+                                              nz(points), nz(members), nz(seg_scores), nz(seg_labels), _st()))
+    return ids, points, members, seg_scores, seg_labels
+
+
+def scene_seg_spread(min_members, segment_index, seg_members, seg_fields, in_fields, ws):
+    """seg_fields / in_fields: (scores (rows, cols), labels (rows,) int64, set_labels (rows, K) int64 or None, set_of (rows,)
+    int32 or None, margin (rows,) fp32 or None) of the segments and of res -> the same five for the scan, freshly
+    allocated, and pooled (M,) bool; words 9 .. 11 of the record."""
+    sc_in, lab_in, sl_in, so_in, mg_in = in_fields
+    sc_seg, lab_seg, sl_seg, so_seg, mg_seg = seg_fields
+    assert sc_in.dim() == 2 and sc_in.dtype == torch.float32 and sc_in.is_contiguous() and sc_in.is_cuda
+    M, C = sc_in.shape
+    S = sc_seg.shape[0]
+    K = 0 if sl_in is None else sl_in.shape[1]
+    ok = lambda t, shape, dt: tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous() and t.is_cuda
+    assert ok(segment_index, (M,), torch.int32) and ok(seg_members, (S,), torch.int32) and _seg_ws_ok(ws)
+    assert ok(lab_in, (M,), torch.int64) and ok(sc_seg, (S, C), torch.float32) and ok(lab_seg, (S,), torch.int64)
+    if K:
+        assert ok(sl_in, (M, K), torch.int64) and ok(so_in, (M,), torch.int32) and ok(mg_in, (M,), torch.float32)
+        assert ok(sl_seg, (S, K), torch.int64) and ok(so_seg, (S,), torch.int32) and ok(mg_seg, (S,), torch.float32)
+    else:
+        assert all(t is None for t in (sl_in, so_in, mg_in, sl_seg, so_seg, mg_seg))
+    dev = sc_in.device
+    scores, labels = torch.empty_like(sc_in), torch.empty_like(lab_in)
+    pooled = torch.empty(M, device=dev, dtype=torch.bool)
+    set_labels, set_of, margin = (torch.empty_like(sl_in), torch.empty_like(so_in), torch.empty_like(mg_in)) if K else (None,) * 3
+    nz = lambda t: _p(t) if t is not None and t.numel() else None
+    _lib.check(_lib.load().r3d_scene_seg_spread(M, C, K, S, int(min_members), _p(segment_index), nz(seg_members), nz(sc_seg),
+                                                nz(lab_seg), nz(sl_seg), nz(so_seg), nz(mg_seg), _p(sc_in), _p(lab_in), _p(sl_in),
+                                                _p(so_in), _p(mg_in), _p(scores), _p(labels), _p(pooled), _p(set_labels),
+                                                _p(set_of), _p(margin), _p(ws), ws.numel(), _st()))
+    return scores, labels, set_labels, set_of, margin, pooled
+
+
 # ---------------------------------------------------------------------------------------------- cutting episodes (block_pool.py)
 def _episode_cut_args(points, labels, offsets, desc, classes, S, Q, N, out, mask, gt_mask, query_y, gt_query_y, slot_map):
     E, n_way = classes.shape
