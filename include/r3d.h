@@ -42,7 +42,7 @@ extern "C" {
 #endif
 
 const char* r3d_last_error_string(void);
-int r3d_abi_version(void); /* 5: r3d_knn_topk_batched takes one workspace (r3d_knn_ws_words) */
+int r3d_abi_version(void); /* 6: r3d_scene_prepare / _vote take the optional sws, r3d_scene_transfer the optional idw outputs */
 /* Arithmetic of the GEMM-shaped kernels that decide no index (self-attention forward / backward, r3d_pointwise_conv*,
  * r3d_gemm_tn): 0 = fp32 matrix core (v_mfma_f32_32x32x2_f32), 1 = every fp32 operand cut into three bf16 pieces, six
  * v_mfma_f32_32x32x16_bf16 per product block accumulated in fp32 (fp32-level accuracy at 2.67x the matrix rate;
@@ -546,7 +546,7 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
                        float* mats_out, void* stream);
 
 /* ---- Labelling a whole scan against a fitted support set (no reference counterpart: the reference scores clouds its
- * loader cut on the host, dataloaders/loader.py:100-119; definition in INTEGRATION.md, "Labelling a scan") ----
+ * loader cut on the host, dataloaders/loader.py:100-119; definition in INTEGRATION.md, "Labelling a scan", steps 1-9') ----
  * scan: M rows of ld floats, x y z first (r g b behind them when ld >= 6); M <= 2^27.  A point is VALID when x, y and z
  * are finite.  Nothing here draws a random number or sums floats in an order that depends on scheduling.
  *
@@ -558,103 +558,92 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
  *                        by key (per-tile digit counts, one scan, in-tile ranking in index order);
  *                        cell offsets; points per block; chunks per block (ceil(n / N), 0 below
  *                        min_points) and their exclusive scan; the chunk table; the plan record
- *                        {n_chunks, kept blocks, valid points with a vote, blocks}
- *   r3d_scene_prepare    chunks first_chunk .. first_chunk + G - 1 as prepared clouds of N slots  -
+ *                        {n_chunks, kept blocks, valid points with a vote, blocks, run chunks =
+ *                        n_chunks, skipped chunks = 0, valid points with a vote again, 0}
+ *   r3d_scene_run_tables optional, after r3d_scene_plan and before the host reads the plan record:  -
+ *                        with cap c = max_chunks >= 1, chunk j of a block with nc chunks RUNS when
+ *                        j < c.  Writes into sws the exclusive scan of min(nc, c) over the blocks (first
+ *                        run chunk of a block) and the block of every run chunk, and into the plan
+ *                        record rec[4] = run chunks, rec[5] = skipped chunks, rec[6] = valid points
+ *                        with a vote under the cap.
+ *   r3d_scene_prepare    run chunks first_chunk .. first_chunk + G - 1 as prepared clouds of N slots -
  *                        (slot t = member t mod len of the chunk): xyz - min over the slots,
  *                        rgb / 255.0f at rgb_ch (3 or -1), xyz' / max xyz' at XYZ_ch (behind them, or
  *                        -1; an axis of zero extent gives 0), written at out[g * o_sb + c * o_sc +
  *                        t * o_sn] (the strides of r3d_augment_clouds); slot_map (G, N) int32,
- *                        optional: the scan index of every slot.  Chunks past the plan's n_chunks
- *                        are left unwritten.
- *   r3d_scene_vote       per scan point the fp32 sum of logits[chunk][class][slot] over its          -
- *                        appearances, block id ascending then slot ascending, one at a time;
- *                        labels = arg-max (lowest class on ties, -1 without a vote), votes = the
- *                        appearance count.  logits: (n_chunks, n_classes, N), chunk order.  The
- *                        appearances are computed from the point's cell, its rank in the cell list
- *                        and the block's cell offsets: no inverted index in memory, no atomics.
+ *                        optional: the scan index of every slot.  Chunks past the record's run
+ *                        chunks are left unwritten.
+ *   r3d_scene_vote       per scan point the fp32 sum of logits[run chunk][class][slot] over its      -
+ *                        appearances in chunks that ran, block id ascending then slot ascending, one
+ *                        at a time; labels = arg-max (lowest class on ties, -1 without a vote),
+ *                        votes = the appearance count.  logits: (n_chunks, n_classes, N), run-chunk
+ *                        order.  The appearances are computed from the point's cell, its rank in the
+ *                        cell list and the block's cell offsets: no inverted index in memory, no
+ *                        atomics.
+ *   r3d_scene_transfer   after a vote: every valid point p with votes[p] == 0 takes scores and     word 0 of the
+ *                        label of the voted point q with the smallest d = (dx * dx + dy * dy) +     sparse record:
+ *                        dz * dz (fp32, dx = x_q - x_p, every operation rounded on its own; +inf is  receivers that
+ *                        a value like any other), the lowest scan index on equal d, among the voted  found a source
+ *                        points of the 3 x 3 cells around p's cell (clipped at the grid).  source
+ *                        (M,) int64 = q for such a point (votes[p] stays 0), p itself for a voted
+ *                        point, -1 for an invalid point or one that found no candidate, which is
+ *                        left as the vote left it.  Voted points go, in sorted order, into packed
+ *                        rows {x, y, z, index}; the others into a list per cell, cut into tiles of
+ *                        256 queries; one workgroup per tile stages the candidate runs of the three
+ *                        cell rows through LDS, 1024 rows at a time, one thread per query keeping the
+ *                        lexicographic minimum of (d, index): no float is summed across threads, the
+ *                        one atomic is an integer count.
+ *
+ * sws of r3d_scene_prepare and r3d_scene_vote: NULL with sws_words 0 means NO CAP -- every chunk runs, run chunk c is
+ * chunk c, and the plan's own chunk tables serve as the run tables --; else the sparse workspace that
+ * r3d_scene_run_tables filled.  A run chunk is still chunk (b, j) of nc: same members, same len; with a cap that skips
+ * nothing both give the bits of the call without sws.  NULL with sws_words != 0 is refused.
+ * neighbours and weights of r3d_scene_transfer: both NULL is the transfer above ("nearest"); both given is step 9' ("idw"),
+ * the same receivers, candidates, d, checks and launch sequence with another reduction per receiver: q0, q1, q2 = the
+ * three smallest candidates in (d, scan index) order (fewer when there are fewer), w_i = 1.0f / (d_i + 1e-8f) (+inf gives
+ * 0), m_i[k] = scores[q_i][k] / (float)votes[q_i], and per class acc = w_0 m_0; acc += w_1 m_1; acc += w_2 m_2;
+ * scores[p][k] = acc / ((w_0 + w_1) + w_2), or m_0[k] when that sum is 0; every operation an IEEE one rounded on its own.
+ * labels[p] = the arg-max (lowest class on ties), source[p] = q0, votes[p] stays 0.  neighbours (M, 3) int64: q0 q1 q2
+ * (-1: missing) for a receiver, {p, -1, -1} for a voted point, else -1; weights (M, 3) fp32: the w_i (0: missing),
+ * {1, 0, 0} for a voted point, else 0.  A receiver's scores are on the scale of mean logits, a voted point's stay sums
+ * over its votes.  Each thread keeps its three pairs sorted in registers; a candidate costs one comparison against the
+ * third, the insertion sits behind that branch.  One of the two without the other is refused.
  *
  * Blocks: r x r cells (1 <= r <= 4), block (bx, by) covers cells bx .. min(bx + r, ncx) - 1 by by .. min(by + r, ncy) - 1,
  * nbx = max(ncx - r + 1, 1); its point list is its cells' lists by (cy, cx), never materialised.  ncx * ncy <= 65536.
- * ws: ONE int32 scratch of r3d_scene_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range) shared by plan,
- * prepare and vote, which must be called with the same (M, ncx, ncy, r, N, chunk_cap); chunk_cap bounds the chunk table
+ * ws: ONE int32 scratch of r3d_scene_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range) shared by all of
+ * them, which must be called with the same (M, ncx, ncy, r, N, chunk_cap); chunk_cap bounds the chunk table
  * (r * r * n_valid / N + blocks is always enough).  r3d_scene_ws_offsets fills 8 HOST words (the one host pointer of this
  * header) with the word offsets of {sorted scan indices, sorted keys, sorted position of a scan point, cell offsets
- * (ncx * ncy + 2), points per block, first chunk of a block (blocks + 1), block of a chunk, plan record (8)}. */
+ * (ncx * ncy + 2), points per block, first chunk of a block (blocks + 1), block of a chunk, plan record (8)}.
+ * sws: a SECOND int32 scratch of r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range), for
+ * the same (M, ncx, ncy, chunk_cap) as ws, needed by the cap and by the transfer only; a shorter one is refused.
+ * r3d_scene_sparse_ws_offsets fills 8 HOST words with the word offsets of {first run chunk of a block (blocks + 1), block
+ * of a run chunk, voted points in front of a sorted position (M + 1), scan indices of the points without a vote, first
+ * query tile of a cell (ncx * ncy + 1), candidate rows (4 * M), sparse record (8), scan partials}. */
 long r3d_scene_bounds_ws_words(long M);
 int r3d_scene_bounds(const float* scan, int ld, long M, float* rec /* 8 words */, float* ws, long ws_words, void* stream);
 long r3d_scene_ws_words(long M, int ncx, int ncy, long chunk_cap);
 int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out);
-int r3d_scene_plan(const float* scan, int ld, long M, float x0, float y0, float s, int ncx, int ncy, int r, int N,
-                   int min_points, long chunk_cap, int32_t* ws, long ws_words, void* stream);
-int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
-                      long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc,
-                      long o_sn, int32_t* slot_map, void* stream);
-int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
-                   const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
-                   void* stream);
-
-/* ---- predict_scene on a subsample: a cap on the chunks of a block, and labels for the points it leaves without a vote
- * ("Labelling a scan", steps 7a, 8' and 9).  Additive: the entry points above and what they compute are
- * as they were.
- *
- *   entry point            what it does
- *   r3d_scene_run_tables   after r3d_scene_plan and before the host reads the plan record: with cap c = max_chunks >= 1,
- *                          chunk j of a block with nc chunks RUNS when j < c.  Writes the exclusive scan of min(nc, c) over
- *                          the blocks (first run chunk of a block), the block of every run chunk, and into the plan record
- *                          rec[4] = run chunks, rec[5] = skipped chunks, rec[6] = valid points with a vote under the cap
- *                          (the plan leaves zeros there).
- *   r3d_scene_prepare_run  r3d_scene_prepare with first_chunk .. first_chunk + G - 1 numbering the run chunks; a run chunk
- *   r3d_scene_vote_run     is still chunk (b, j) of nc: same members, same len.  r3d_scene_vote with logits (n_run,
- *                          n_classes, N) in run-chunk order; an appearance counts when its chunk ran.  With a cap that
- *                          skips nothing both give the bits of the entry points they are named after.
- *   r3d_scene_transfer     after a vote (capped or not): every valid point p with votes[p] == 0 takes scores and label of
- *                          the voted point q with the smallest d = (dx * dx + dy * dy) + dz * dz (fp32, dx = x_q - x_p,
- *                          every operation rounded on its own; +inf is a value like any other), the lowest scan index on
- *                          equal d, among the voted points of the 3 x 3 cells around p's cell (clipped at the grid).
- *                          source (M,) int64 = q for such a point (votes[p] stays 0), p itself for a voted point, -1 for
- *                          an invalid point or one that found no candidate, which is left as the vote left it.  Voted
- *                          points go, in sorted order, into packed rows {x, y, z, index}; the others into a list per
- *                          cell, cut into tiles of 256 queries; one workgroup per tile stages the candidate runs of the
- *                          three cell rows through LDS, 1024 rows at a time, one thread per query keeping the
- *                          lexicographic minimum of (d, index): no float is summed across threads, the one atomic is an
- *                          integer count.  The sparse record's word 0 = receivers that found a source.
- *   r3d_scene_transfer_idw r3d_scene_transfer -- same receivers, candidates, d, checks and launch sequence -- with another
- *                          reduction per receiver (step 9'): q0, q1, q2 = the three smallest candidates in (d, scan index)
- *                          order (fewer when there are fewer), w_i = 1.0f / (d_i + 1e-8f) (+inf gives 0), m_i[k] =
- *                          scores[q_i][k] / (float)votes[q_i], and per class acc = w_0 m_0; acc += w_1 m_1; acc += w_2 m_2;
- *                          scores[p][k] = acc / ((w_0 + w_1) + w_2), or m_0[k] when that sum is 0; every operation an IEEE
- *                          one rounded on its own.  labels[p] = the arg-max (lowest class on ties), source[p] = q0, votes[p]
- *                          stays 0.  neighbours (M, 3) int64: q0 q1 q2 (-1: missing) for a receiver, {p, -1, -1} for a voted
- *                          point, else -1; weights (M, 3) fp32: the w_i (0: missing), {1, 0, 0} for a voted point, else 0.
- *                          A receiver's scores are on the scale of mean logits, a voted point's stay sums over its votes.
- *                          Each thread keeps its three pairs sorted in registers; a candidate costs one comparison against
- *                          the third, the insertion sits behind that branch.
- *
- * sws: a SECOND int32 scratch of r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range), for the
- * same (M, ncx, ncy, chunk_cap) as ws; a shorter one is refused.  r3d_scene_sparse_ws_offsets fills 8 HOST words with the
- * word offsets of {first run chunk of a block (blocks + 1), block of a run chunk, voted points in front of a sorted
- * position (M + 1), scan indices of the points without a vote, first query tile of a cell (ncx * ncy + 1), candidate rows
- * (4 * M), sparse record (8), scan partials}. */
 long r3d_scene_sparse_ws_words(long M, int ncx, int ncy, long chunk_cap);
 int r3d_scene_sparse_ws_offsets(long M, int ncx, int ncy, long chunk_cap, long* out);
+int r3d_scene_plan(const float* scan, int ld, long M, float x0, float y0, float s, int ncx, int ncy, int r, int N,
+                   int min_points, long chunk_cap, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long chunk_cap, int32_t* ws, long ws_words, int max_chunks,
                          int32_t* sws, long sws_words, void* stream);
-int r3d_scene_prepare_run(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
-                          long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G, int C, int rgb_ch,
-                          int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream);
-int r3d_scene_vote_run(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
-                       const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes, float* scores,
-                       int64_t* labels, int32_t* votes, void* stream);
+int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
+                      long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G, int C, int rgb_ch,
+                      int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream);
+int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                   const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes, float* scores,
+                   int64_t* labels, int32_t* votes, void* stream);
 int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws, long ws_words,
                        int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels, const int32_t* votes,
-                       int64_t* source, void* stream);
-int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
-                           long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
-                           const int32_t* votes, int64_t* source, int64_t* neighbours, float* weights, void* stream);
+                       int64_t* source, int64_t* neighbours, float* weights, void* stream);
 
 /* ---- predict_scene_sets: one scan against several support sets ("Labelling a scan against several support
- * sets", step 10).  Additive: the entry points above and what they compute are as they were.
- * r3d_scene_merge_sets: scores (M, n_sets, n_classes) fp32 -- what r3d_scene_vote(_run) and the transfers leave for logits
+ * sets", step 10).
+ * r3d_scene_merge_sets: scores (M, n_sets, n_classes) fp32 -- what r3d_scene_vote and r3d_scene_transfer leave for logits
  * whose columns are set after set, n_classes = n_way + 1 >= 2 each, n_sets * n_classes <= 64 --, votes (M,), source (M,)
  * of a transfer or NULL.  One thread per point, no atomics, nothing summed.  A point HAS A LABEL when votes[p] > 0 or
  * (source given) source[p] >= 0; any other point gets set_labels -1, labels -1, set_of -1, margin 0.  Per set k of a point
@@ -670,9 +659,9 @@ int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const float* scores,
                          float* margin, void* stream);
 
 /* ---- fit_scene: the support set from an annotated scan ("Fitting from an annotated scan", S1-S5).
- * Additive: the entry points above and what they compute are as they were.  All three run after r3d_scene_plan (no cap) on
- * its ws, with the same (M, ncx, ncy, r, N, chunk_cap).  The CLOUD of a kept block of n points and nc = ceil(n / N) chunks is
- * its chunk 0: list positions 0, nc, 2 nc, ..., len = ceil(n / nc) members, slot t = member t mod len.
+ * All three run after r3d_scene_plan (no cap) on its ws, with the same (M, ncx, ncy, r, N, chunk_cap).  The CLOUD of a kept
+ * block of n points and nc = ceil(n / N) chunks is its chunk 0: list positions 0, nc, 2 nc, ..., len = ceil(n / nc) members,
+ * slot t = member t mod len.
  * labels: M class ids, int32 (label_bytes 4) or int64 (8), read as they are; the labels of invalid points are never read.
  *
  *   entry point               what it does
@@ -701,9 +690,8 @@ int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy
                              int label_bytes, const int32_t* cloud_class, int32_t* mask, void* stream);
 
 /* ---- pool_segments: one label per user-given segment of the scan ("Pooling scores over segments", P1-P5).
- * Additive: the entry points above and what they compute are as they were.  Replaces what a caller would write in torch as
- * a sort plus index_add_ -- floating-point atomics, a summation order that changes from run to run -- with sums in a
- * defined order: the reference has no such step, the definition is this project's.
+ * Replaces what a caller would write in torch as a sort plus index_add_ -- floating-point atomics, a summation order that
+ * changes from run to run -- with sums in a defined order: the reference has no such step, the definition is this project's.
  * segments: M ids, int32 (seg_bytes 4) or int64 (8), read as they are; g < 0: the point is in no segment; legal ids are
  * 0 .. 2^31 - 2.  ws: ONE int32 scratch of r3d_scene_seg_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the four
  * calls of one pooling; its first 16 words are the record the host reads:

@@ -71,7 +71,7 @@ def header_symbols():
 _lib = None
 
 
-ABI_VERSION = 5  # include/r3d.h; 5: r3d_knn_topk_batched takes one workspace of r3d_knn_ws_words floats
+ABI_VERSION = 6  # include/r3d.h; 6: one scene entry point per step (prepare / vote take the optional sws, transfer the idw outputs)
 
 
 def load():

@@ -7,9 +7,11 @@
 //                                                                        -> a record the host reads (read 2)
 //   prepare  the G chunks of one predict launch as prepared clouds, gathered straight from the scan
 //   vote     per scan point the sum of its chunk logits (closed-form inverted index: no atomics, a fixed order)
-//   run tables, prepare / vote under a cap on the chunks of a block (only chunks j < cap of a block run)
+//   run tables (a cap on the chunks of a block: only chunks j < cap run); prepare and vote number the chunks that run
+//            through them, and without a cap the plan's own chunk tables stand in for them: the cap nobody reaches
+//            (the vote then skips the test against them, which no appearance would fail)
 //   transfer scores and labels of the nearest voted point, among the 3 x 3 cells, to every point without a vote; or
-//            (idw) mean logits of the three nearest, weighted by 1 / d
+//            (idw, when given neighbours and weights) mean logits of the three nearest, weighted by 1 / d
 //   support  (fit_scene) per block and way the points of the block's chunk 0 that carry the way's class id; per way the
 //            k_shot blocks with most of them; those chunks as prepared clouds with their masks
 //   segments (pool_segments) the scores pooled over user-given point segments: the sort below on (id, scan index), per
@@ -36,7 +38,7 @@
 #define SC_P_NCHUNKS 0
 #define SC_P_NBLOCKS 1
 #define SC_P_NVOTED 2
-// written by r3d_scene_run_tables (r3d_scene_plan leaves zeros)
+// the chunks that run: r3d_scene_plan writes {n_chunks, 0, voted}, r3d_scene_run_tables the counts under its cap
 #define SC_P_NRUN 4
 #define SC_P_NSKIPPED 5
 #define SC_P_NVOTED_RUN 6
@@ -344,6 +346,29 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_scatter_kernel(const int
   }
 }
 
+// a[0 .. n) -> its exclusive scan, in place; part: one word per SC_TILE words of a
+static void sc_excl_scan(int* a, long n, int* part, hipStream_t st) {
+  const int nb = (int)((n + SC_TILE - 1) / SC_TILE);
+  hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(nb), dim3(SC_THREADS), 0, st, a, n, part);
+  hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, part, nb);
+  hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(nb), dim3(SC_THREADS), 0, st, a, n, part);
+}
+
+// The M (key, scan index) pairs at key[0] / idx[0] sorted by the low 8 * passes bits of the key; key, idx, hist and part
+// are word offsets into ws (hist: 256 * n_tiles words, part: one per SC_TILE of them).  -> which pair holds the result.
+static int sc_sort_pairs(int32_t* ws, const long key[2], const long idx[2], long hist, long part, long M, int n_tiles,
+                         int passes, hipStream_t st) {
+  for (int p = 0; p < passes; ++p) {
+    const int a = p & 1, b = a ^ 1;
+    hipLaunchKernelGGL(r3d_scene_hist_kernel, dim3(n_tiles), dim3(SC_THREADS), 0, st, ws + key[a], (int)M, 8 * p, n_tiles,
+                       ws + hist);
+    sc_excl_scan(ws + hist, 256L * n_tiles, ws + part, st);
+    hipLaunchKernelGGL(r3d_scene_scatter_kernel, dim3(n_tiles), dim3(SC_THREADS), 0, st, ws + key[a], ws + idx[a], (int)M, 8 * p,
+                       n_tiles, ws + hist, ws + key[b], ws + idx[b]);
+  }
+  return passes & 1;
+}
+
 // cell offsets from the sorted keys (every cell written by exactly one thread, empty cells included) and the sorted
 // position of every scan point
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_cells_kernel(const int* __restrict__ skey, const int* __restrict__ order,
@@ -423,7 +448,10 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_blocks_kernel(const
     rec[SC_P_NBLOCKS] = kept;
     rec[SC_P_NVOTED] = voted;
     rec[3] = nb;
-    rec[4] = rec[5] = rec[6] = rec[7] = 0;
+    rec[SC_P_NRUN] = carry;  // without a cap every chunk runs
+    rec[SC_P_NSKIPPED] = 0;
+    rec[SC_P_NVOTED_RUN] = voted;
+    rec[7] = 0;
   }
 }
 
@@ -465,60 +493,101 @@ extern "C" int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, lo
   return R3D_OK;
 }
 
-#define SC_REQUIRE_PLAN_ARGS(name)                                                                                        \
-  R3D_REQUIRE(M > 0 && M <= SC_MAX_POINTS, name ": M %ld (1 .. 2^27 points)", M);                                         \
-  R3D_REQUIRE(ld >= 3 && ld <= 64, name ": ld %d (a scan row holds x y z first: 3 .. 64 floats)", ld);                    \
-  R3D_REQUIRE(ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS, name ": %d x %d cells (1 .. 65536)", ncx, ncy);      \
-  R3D_REQUIRE(r >= 1 && r <= 4, name ": r %d (block_size / stride is 1 .. 4)", r);                                        \
-  R3D_REQUIRE(N > 0 && N <= (1 << 20), name ": N %d points per cloud", N);                                                \
-  R3D_REQUIRE(chunk_cap > 0 && chunk_cap < (1L << 30), name ": chunk_cap %ld", chunk_cap);                                \
-  R3D_REQUIRE(ws_words >= r3d_scene_ws_words(M, ncx, ncy, chunk_cap), name ": workspace of %ld words, %ld needed",        \
-              ws_words, r3d_scene_ws_words(M, ncx, ncy, chunk_cap))
+// ------------------------------------------------------------------------------------------------ argument checks, the plan on the host
+#define SC_TRY(call)        \
+  do {                      \
+    const int e_ = (call);  \
+    if (e_) return e_;      \
+  } while (0)
 
-#define SC_REQUIRE_SPARSE_WS(name)                                                                                        \
-  R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap) && sws_words >= r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap),    \
-              name ": sparse workspace of %ld words, %ld needed", sws_words, r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap))
+// what every entry point that works on a plan has: the scan's size, the cells and the workspace
+static int sc_check_plan(const char* name, long M, int ncx, int ncy, long chunk_cap, long ws_words) {
+  R3D_REQUIRE(M > 0 && M <= SC_MAX_POINTS, "%s: M %ld (1 .. 2^27 points)", name, M);
+  R3D_REQUIRE(ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS, "%s: %d x %d cells (1 .. 65536)", name, ncx, ncy);
+  R3D_REQUIRE(chunk_cap > 0 && chunk_cap < (1L << 30), "%s: chunk_cap %ld", name, chunk_cap);
+  R3D_REQUIRE(ws_words >= r3d_scene_ws_words(M, ncx, ncy, chunk_cap), "%s: workspace of %ld words, %ld needed", name, ws_words,
+              r3d_scene_ws_words(M, ncx, ncy, chunk_cap));
+  return R3D_OK;
+}
 
-static sc_grid sc_make_grid(int ncx, int ncy, int r, long M) {
+static int sc_check_ld(const char* name, int ld) {
+  R3D_REQUIRE(ld >= 3 && ld <= 64, "%s: ld %d (a scan row holds x y z first: 3 .. 64 floats)", name, ld);
+  return R3D_OK;
+}
+
+static int sc_check_blocks(const char* name, int r, int N) {
+  R3D_REQUIRE(r >= 1 && r <= 4, "%s: r %d (block_size / stride is 1 .. 4)", name, r);
+  R3D_REQUIRE(N > 0 && N <= (1 << 20), "%s: N %d points per cloud", name, N);
+  return R3D_OK;
+}
+
+static int sc_check_sparse_ws(const char* name, long M, int ncx, int ncy, long chunk_cap, long sws_words) {
+  R3D_REQUIRE(sc_shape_ok(M, ncx, ncy, 1, chunk_cap) && sws_words >= r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap),
+              "%s: sparse workspace of %ld words, %ld needed", name, sws_words, r3d_scene_sparse_ws_words(M, ncx, ncy, chunk_cap));
+  return R3D_OK;
+}
+
+// the optional sws of prepare and vote: NULL with 0 words (no cap), or a whole sparse workspace
+static int sc_check_optional_sparse_ws(const char* name, long M, int ncx, int ncy, long chunk_cap, const int32_t* sws,
+                                       long sws_words) {
+  R3D_REQUIRE(sws || sws_words == 0, "%s: null pointer (sws) with sws_words %ld", name, sws_words);
+  return sws ? sc_check_sparse_ws(name, M, ncx, ncy, chunk_cap, sws_words) : R3D_OK;
+}
+
+// What the entry points after r3d_scene_plan read, as pointers into ws (and sws); L and S for the arrays they write.
+struct sc_view {
+  const int *order, *skey, *pos, *cell, *blk_n, *chunk0, *run0, *run_blk, *rec;
   sc_grid g;
-  g.ncx = ncx; g.ncy = ncy; g.r = r; g.M = (int)M;
-  g.nbx = ncx - r + 1 > 1 ? ncx - r + 1 : 1;
-  g.nby = ncy - r + 1 > 1 ? ncy - r + 1 : 1;
-  return g;
+  int n_cells, nb;
+  sc_layout L;
+  sp_layout S;
+};
+
+static sc_view sc_make_view(long M, int ncx, int ncy, int r, long chunk_cap, const int32_t* ws, const int32_t* sws) {
+  sc_view v;
+  v.n_cells = ncx * ncy;
+  v.L = sc_make_layout(M, v.n_cells, chunk_cap);
+  v.S = sp_make_layout(M, v.n_cells, chunk_cap);
+  v.g.ncx = ncx; v.g.ncy = ncy; v.g.r = r; v.g.M = (int)M;
+  v.g.nbx = ncx - r + 1 > 1 ? ncx - r + 1 : 1;
+  v.g.nby = ncy - r + 1 > 1 ? ncy - r + 1 : 1;
+  v.nb = v.g.nbx * v.g.nby;
+  v.order = ws + v.L.idx[v.L.sorted];
+  v.skey = ws + v.L.key[v.L.sorted];
+  v.pos = ws + v.L.pos;
+  v.cell = ws + v.L.cell;
+  v.blk_n = ws + v.L.blk_n;
+  v.chunk0 = ws + v.L.chunk0;
+  v.rec = ws + v.L.rec;
+  // Without sws no cap: the chunk tables under a second name (the plan record counts every chunk as a run chunk).  The
+  // prepare kernel takes both names as const __restrict__ pointers and only reads through them, which is well defined.
+  v.run0 = sws ? sws + v.S.run0 : v.chunk0;
+  v.run_blk = sws ? sws + v.S.run_blk : ws + v.L.chunk_blk;
+  return v;
 }
 
 extern "C" int r3d_scene_plan(const float* scan, int ld, long M, float x0, float y0, float s, int ncx, int ncy, int r, int N,
                               int min_points, long chunk_cap, int32_t* ws, long ws_words, void* stream) {
   R3D_REQUIRE(scan && ws, "r3d_scene_plan: null pointer (scan %p, ws %p)", (const void*)scan, (void*)ws);
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_plan");
+  SC_TRY(sc_check_ld("r3d_scene_plan", ld));
+  SC_TRY(sc_check_plan("r3d_scene_plan", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_plan", r, N));
   R3D_REQUIRE(min_points >= 1, "r3d_scene_plan: min_points %d (at least 1)", min_points);
   R3D_REQUIRE(x0 == x0 && y0 == y0 && s > 0.0f && s < INFINITY, "r3d_scene_plan: origin (%g, %g), cell size %g", (double)x0,
               (double)y0, (double)s);
   const hipStream_t st = (hipStream_t)stream;
-  const int n_cells = ncx * ncy;
-  const sc_layout L = sc_make_layout(M, n_cells, chunk_cap);
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, nullptr);
+  const sc_layout& L = v.L;
   const int gm = (int)((M + SC_THREADS - 1) / SC_THREADS);
   hipLaunchKernelGGL(r3d_scene_keys_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, x0, y0, s, ncx, ncy,
                      ws + L.key[0], ws + L.idx[0]);
-  const long n_hist = 256L * L.n_tiles;
-  for (int p = 0; p < L.passes; ++p) {
-    const int a = p & 1, b = a ^ 1;
-    hipLaunchKernelGGL(r3d_scene_hist_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], (int)M, 8 * p, L.n_tiles,
-                       ws + L.hist);
-    hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
-    hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.part, L.n_part);
-    hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
-    hipLaunchKernelGGL(r3d_scene_scatter_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], ws + L.idx[a], (int)M,
-                       8 * p, L.n_tiles, ws + L.hist, ws + L.key[b], ws + L.idx[b]);
-  }
-  hipLaunchKernelGGL(r3d_scene_cells_kernel, dim3(gm), dim3(SC_THREADS), 0, st, ws + L.key[L.sorted], ws + L.idx[L.sorted], (int)M,
-                     n_cells, ws + L.cell, ws + L.pos);
-  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
-  const int nb = g.nbx * g.nby;
-  hipLaunchKernelGGL(r3d_scene_blocks_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.cell, g, N, min_points, ws + L.blk_n,
+  sc_sort_pairs(ws, L.key, L.idx, L.hist, L.part, M, L.n_tiles, L.passes, st);  // into pair L.sorted: v.skey, v.order
+  hipLaunchKernelGGL(r3d_scene_cells_kernel, dim3(gm), dim3(SC_THREADS), 0, st, v.skey, v.order, (int)M, v.n_cells, ws + L.cell,
+                     ws + L.pos);
+  hipLaunchKernelGGL(r3d_scene_blocks_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, v.cell, v.g, N, min_points, ws + L.blk_n,
                      ws + L.chunk0, ws + L.rec);
-  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st,
-                     ws + L.chunk0, nb, (int)chunk_cap, ws + L.chunk_blk);
+  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((v.nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st, v.chunk0,
+                     v.nb, (int)chunk_cap, ws + L.chunk_blk);
   R3D_LAUNCH_CHECK("r3d_scene_plan");
   return R3D_OK;
 }
@@ -550,19 +619,19 @@ static __device__ __forceinline__ int sc_list_to_sorted(const int* __restrict__ 
 template <typename L>
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_prepare_kernel(
     const float* __restrict__ scan, int ld, int M, const int* __restrict__ order, const int* __restrict__ cell,
-    const int* __restrict__ blk_n, const int* __restrict__ chunk0, const int* __restrict__ chunk_blk,
-    const int* __restrict__ rec, sc_grid g, int first_chunk, int N, int C, int rgb_ch, int XYZ_ch, float* __restrict__ out,
-    long o_sb, long o_sc, long o_sn, int* __restrict__ slot_map, const int* __restrict__ run0,
-    const int* __restrict__ run_blk, const int* __restrict__ blocks, const L* __restrict__ labels,
-    const int* __restrict__ cloud_class, int* __restrict__ mask) {
+    const int* __restrict__ blk_n, const int* __restrict__ chunk0, const int* __restrict__ rec, sc_grid g, int first_chunk,
+    int N, int C, int rgb_ch, int XYZ_ch, float* __restrict__ out, long o_sb, long o_sc, long o_sn,
+    int* __restrict__ slot_map, const int* __restrict__ run0, const int* __restrict__ run_blk,
+    const int* __restrict__ blocks, const L* __restrict__ labels, const int* __restrict__ cloud_class,
+    int* __restrict__ mask) {
   __shared__ float red[6][SC_THREADS / R3D_WAVE];
   const int c = first_chunk + blockIdx.x, tid = threadIdx.x;
-  // run0 / run_blk (both or neither): c numbers the chunks that run under the cap; the chunk itself is (b, j) of nc as ever
-  if (!blocks && c >= rec[run0 ? SC_P_NRUN : SC_P_NCHUNKS]) return;  // (uniform) a launch past the plan's chunks writes nothing
-  const int b = blocks ? blocks[blockIdx.x] : (run0 ? run_blk[c] : chunk_blk[c]);
+  // c numbers the chunks that run (run0 / run_blk; without a cap: all of them); the chunk itself is (b, j) of nc as ever
+  if (!blocks && c >= rec[SC_P_NRUN]) return;  // (uniform) a launch past the plan's chunks writes nothing
+  const int b = blocks ? blocks[blockIdx.x] : run_blk[c];
   if (b < 0 || b >= g.nbx * g.nby) return;
   const int bx = b % g.nbx, by = b / g.nbx;
-  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = blocks ? 0 : c - (run0 ? run0[b] : chunk0[b]);
+  const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b], j = blocks ? 0 : c - run0[b];
   if (nc <= 0 || j < 0 || j >= nc || n <= j) return;
   const int len = (n - j + nc - 1) / nc;
   out += (long)blockIdx.x * o_sb;
@@ -601,13 +670,15 @@ struct sc_block_args {
   int32_t* mask;
 };
 
-// r3d_scene_prepare (sws NULL), r3d_scene_prepare_run and r3d_scene_prepare_blocks (ba): one argument list, one launch
+// r3d_scene_prepare and r3d_scene_prepare_blocks (ba): one argument list, one launch
 static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
                       long ws_words, const int32_t* sws, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch, float* out,
                       long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream, const sc_block_args* ba = nullptr) {
   R3D_REQUIRE(scan && ws && out, "r3d_scene_prepare: null pointer (scan %p, ws %p, out %p)", (const void*)scan, (const void*)ws,
               (void*)out);
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_prepare");
+  SC_TRY(sc_check_ld("r3d_scene_prepare", ld));
+  SC_TRY(sc_check_plan("r3d_scene_prepare", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_prepare", r, N));
   R3D_REQUIRE(G > 0 && first_chunk >= 0 && (ba || (long)first_chunk + G <= chunk_cap),  // ba: G block ids, checked by the caller
               "r3d_scene_prepare: chunks %d .. %d + %d outside the chunk table of %ld", first_chunk, first_chunk, G, chunk_cap);
   R3D_REQUIRE(C == 3 || C == 6 || C == 9, "r3d_scene_prepare: C %d (3, 6 or 9 channels)", C);
@@ -618,14 +689,12 @@ static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r
   R3D_REQUIRE(C == 3 + (rgb_ch >= 0 ? 3 : 0) + (XYZ_ch >= 0 ? 3 : 0), "r3d_scene_prepare: C %d does not hold xyz%s%s", C,
               rgb_ch >= 0 ? " rgb" : "", XYZ_ch >= 0 ? " XYZ" : "");
   R3D_REQUIRE(o_sb >= 0 && o_sc > 0 && o_sn > 0, "r3d_scene_prepare: strides must be positive (out %ld %ld %ld)", o_sb, o_sc, o_sn);
-  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
-#define SC_LAUNCH_PREPARE(T)                                                                                                \
-  hipLaunchKernelGGL(r3d_scene_prepare_kernel<T>, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M,          \
-                     ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, ws + L.chunk_blk, ws + L.rec,              \
-                     sc_make_grid(ncx, ncy, r, M), first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map,          \
-                     sws ? sws + S.run0 : nullptr, sws ? sws + S.run_blk : nullptr, ba ? ba->blocks : nullptr,                  \
-                     (const T*)(ba ? ba->labels : nullptr), ba ? ba->cloud_class : nullptr, ba ? ba->mask : nullptr)
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, sws);
+#define SC_LAUNCH_PREPARE(T)                                                                                                  \
+  hipLaunchKernelGGL(r3d_scene_prepare_kernel<T>, dim3(G), dim3(SC_THREADS), 0, (hipStream_t)stream, scan, ld, (int)M, v.order,   \
+                     v.cell, v.blk_n, v.chunk0, v.rec, v.g, first_chunk, N, C, rgb_ch, XYZ_ch, out, o_sb, o_sc, o_sn, slot_map,   \
+                     v.run0, v.run_blk, ba ? ba->blocks : nullptr, (const T*)(ba ? ba->labels : nullptr),                         \
+                     ba ? ba->cloud_class : nullptr, ba ? ba->mask : nullptr)
   if (ba && ba->label_bytes == 8)
     SC_LAUNCH_PREPARE(long long);
   else
@@ -636,18 +705,10 @@ static int sc_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r
 }
 
 extern "C" int r3d_scene_prepare(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
-                                 const int32_t* ws, long ws_words, int first_chunk, int G, int C, int rgb_ch, int XYZ_ch,
-                                 float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map, void* stream) {
-  return sc_prepare(scan, ld, M, ncx, ncy, r, N, chunk_cap, ws, ws_words, nullptr, first_chunk, G, C, rgb_ch, XYZ_ch, out, o_sb,
-                    o_sc, o_sn, slot_map, stream);
-}
-
-extern "C" int r3d_scene_prepare_run(const float* scan, int ld, long M, int ncx, int ncy, int r, int N, long chunk_cap,
-                                     const int32_t* ws, long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G,
-                                     int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn,
-                                     int32_t* slot_map, void* stream) {
-  R3D_REQUIRE(sws, "r3d_scene_prepare_run: null pointer (sws)");
-  SC_REQUIRE_SPARSE_WS("r3d_scene_prepare_run");
+                                 const int32_t* ws, long ws_words, const int32_t* sws, long sws_words, int first_chunk, int G,
+                                 int C, int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* slot_map,
+                                 void* stream) {
+  SC_TRY(sc_check_optional_sparse_ws("r3d_scene_prepare", M, ncx, ncy, chunk_cap, sws, sws_words));
   return sc_prepare(scan, ld, M, ncx, ncy, r, N, chunk_cap, ws, ws_words, sws, first_chunk, G, C, rgb_ch, XYZ_ch, out, o_sb,
                     o_sc, o_sn, slot_map, stream);
 }
@@ -695,7 +756,10 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
           const int n = blk_n[b], j = q % nc, m = q / nc;
           const int len = (n - j + nc - 1) / nc;
           int ch = c0 + j;
-          if (run0) {  // under a cap: the appearance counts when its chunk ran; logits are numbered by run chunk
+          // under a cap: the appearance counts when its chunk ran; logits are numbered by run chunk.  Reading chunk0 as
+          // run0 without a cap gives the same bits, but the kernel without this (uniform) branch took 3 % longer at 10^6
+          // points (profiles/r21_scene_one_entry_point.md): the vote alone is given run0 == NULL for "no cap".
+          if (run0) {
             if (j >= run0[b + 1] - run0[b]) continue;
             ch = run0[b] + j;
           }
@@ -715,38 +779,23 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_vote_kernel(
   labels[p] = best;
 }
 
-static int sc_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words, const int32_t* sws,
-                   const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
-                   void* stream) {
+extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
+                              const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes,
+                              float* scores, int64_t* labels, int32_t* votes, void* stream) {
+  SC_TRY(sc_check_optional_sparse_ws("r3d_scene_vote", M, ncx, ncy, chunk_cap, sws, sws_words));
   R3D_REQUIRE(ws && logits && scores && labels && votes,
               "r3d_scene_vote: null pointer (ws %p, logits %p, scores %p, labels %p, votes %p)", (const void*)ws,
               (const void*)logits, (void*)scores, (void*)labels, (void*)votes);
-  const int ld = 3;
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_vote");
+  SC_TRY(sc_check_plan("r3d_scene_vote", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_vote", r, N));
   R3D_REQUIRE(n_chunks > 0 && n_chunks <= chunk_cap, "r3d_scene_vote: n_chunks %d (1 .. chunk_cap %ld)", n_chunks, chunk_cap);
   R3D_REQUIRE(n_classes >= 1 && n_classes <= 64, "r3d_scene_vote: n_classes %d (1 .. 64)", n_classes);
-  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, sws);
   hipLaunchKernelGGL(r3d_scene_vote_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
-                     (hipStream_t)stream, (int)M, ws + L.key[L.sorted], ws + L.pos, ws + L.cell, ws + L.blk_n, ws + L.chunk0,
-                     sc_make_grid(ncx, ncy, r, M), N, n_classes, logits, n_chunks, scores, (long long*)labels, votes,
-                     sws ? sws + S.run0 : nullptr);
+                     (hipStream_t)stream, (int)M, v.skey, v.pos, v.cell, v.blk_n, v.chunk0, v.g, N, n_classes, logits, n_chunks,
+                     scores, (long long*)labels, votes, sws ? v.run0 : nullptr);
   R3D_LAUNCH_CHECK("r3d_scene_vote");
   return R3D_OK;
-}
-
-extern "C" int r3d_scene_vote(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
-                              const float* logits, int n_chunks, int n_classes, float* scores, int64_t* labels, int32_t* votes,
-                              void* stream) {
-  return sc_vote(M, ncx, ncy, r, N, chunk_cap, ws, ws_words, nullptr, logits, n_chunks, n_classes, scores, labels, votes, stream);
-}
-
-extern "C" int r3d_scene_vote_run(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
-                                  const int32_t* sws, long sws_words, const float* logits, int n_chunks, int n_classes,
-                                  float* scores, int64_t* labels, int32_t* votes, void* stream) {
-  R3D_REQUIRE(sws, "r3d_scene_vote_run: null pointer (sws)");
-  SC_REQUIRE_SPARSE_WS("r3d_scene_vote_run");
-  return sc_vote(M, ncx, ncy, r, N, chunk_cap, ws, ws_words, sws, logits, n_chunks, n_classes, scores, labels, votes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ a cap on the chunks of a block
@@ -813,21 +862,18 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_run_count_kernel(int M, 
 extern "C" int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long chunk_cap, int32_t* ws, long ws_words,
                                     int max_chunks, int32_t* sws, long sws_words, void* stream) {
   R3D_REQUIRE(ws && sws, "r3d_scene_run_tables: null pointer (ws %p, sws %p)", (void*)ws, (void*)sws);
-  const int ld = 3;
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_run_tables");
-  SC_REQUIRE_SPARSE_WS("r3d_scene_run_tables");
+  SC_TRY(sc_check_plan("r3d_scene_run_tables", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_run_tables", r, N));
+  SC_TRY(sc_check_sparse_ws("r3d_scene_run_tables", M, ncx, ncy, chunk_cap, sws_words));
   R3D_REQUIRE(max_chunks >= 1, "r3d_scene_run_tables: max_chunks %d (at least 1)", max_chunks);
   const hipStream_t st = (hipStream_t)stream;
-  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sp_layout S = sp_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
-  const int nb = g.nbx * g.nby;
-  hipLaunchKernelGGL(r3d_scene_run_scan_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.chunk0, nb, max_chunks,
-                     sws + S.run0, ws + L.rec);
-  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st,
-                     sws + S.run0, nb, (int)chunk_cap, sws + S.run_blk);
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, sws);
+  hipLaunchKernelGGL(r3d_scene_run_scan_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, v.chunk0, v.nb, max_chunks,
+                     sws + v.S.run0, ws + v.L.rec);
+  hipLaunchKernelGGL(r3d_scene_chunk_table_kernel, dim3((v.nb + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st, v.run0,
+                     v.nb, (int)chunk_cap, sws + v.S.run_blk);
   hipLaunchKernelGGL(r3d_scene_run_count_kernel, dim3((int)((M + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st, (int)M,
-                     ws + L.key[L.sorted], ws + L.pos, ws + L.cell, ws + L.blk_n, ws + L.chunk0, sws + S.run0, g, ws + L.rec);
+                     v.skey, v.pos, v.cell, v.blk_n, v.chunk0, v.run0, v.g, ws + v.L.rec);
   R3D_LAUNCH_CHECK("r3d_scene_run_tables");
   return R3D_OK;
 }
@@ -1031,62 +1077,39 @@ __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
   if ((tid & 63) == 0 && n > 0) atomicAdd(&rec[SC_T_NTRANSFERRED], n);  // an integer count: order-independent
 }
 
-// r3d_scene_transfer (neighbours NULL) and r3d_scene_transfer_idw: one argument list, one launch sequence
-static int sc_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws, long ws_words,
-                       int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels, const int32_t* votes,
-                       int64_t* source, int64_t* neighbours, float* weights, void* stream) {
+// neighbours and weights both NULL: "nearest" (NN = 1); both given: "idw" (NN = 3).  One launch sequence.
+extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
+                                  long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
+                                  const int32_t* votes, int64_t* source, int64_t* neighbours, float* weights, void* stream) {
   R3D_REQUIRE(scan && ws && sws && scores && labels && votes && source,
               "r3d_scene_transfer: null pointer (scan %p, ws %p, sws %p, scores %p, labels %p, votes %p, source %p)",
               (const void*)scan, (const void*)ws, (void*)sws, (void*)scores, (void*)labels, (const void*)votes, (void*)source);
-  const int r = 1, N = 1;
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_transfer");
-  SC_REQUIRE_SPARSE_WS("r3d_scene_transfer");
+  R3D_REQUIRE(!neighbours == !weights, "r3d_scene_transfer: null pointer (neighbours %p, weights %p go together)",
+              (void*)neighbours, (void*)weights);
+  SC_TRY(sc_check_ld("r3d_scene_transfer", ld));
+  SC_TRY(sc_check_plan("r3d_scene_transfer", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_sparse_ws("r3d_scene_transfer", M, ncx, ncy, chunk_cap, sws_words));
   R3D_REQUIRE(n_classes >= 1 && n_classes <= 64, "r3d_scene_transfer: n_classes %d (1 .. 64)", n_classes);
   const hipStream_t st = (hipStream_t)stream;
-  const int n_cells = ncx * ncy;
-  const sc_layout L = sc_make_layout(M, n_cells, chunk_cap);
-  const sp_layout S = sp_make_layout(M, n_cells, chunk_cap);
-  const int* order = ws + L.idx[L.sorted];
+  const sc_view v = sc_make_view(M, ncx, ncy, 1, chunk_cap, ws, sws);  // cells only: the transfer knows no blocks
+  const sp_layout& S = v.S;
   float4* cand = (float4*)(sws + S.cand);
   const int gm = (int)((M + SC_THREADS - 1) / SC_THREADS), gm1 = (int)((M + 1 + SC_THREADS - 1) / SC_THREADS);
-  hipLaunchKernelGGL(r3d_scene_transfer_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, order, votes, sws + S.voff,
+  hipLaunchKernelGGL(r3d_scene_transfer_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, v.order, votes, sws + S.voff,
                      (long long*)source, (long long*)neighbours, weights);
-  hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
-  hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, sws + S.part, S.n_part);
-  hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(S.n_part), dim3(SC_THREADS), 0, st, sws + S.voff, M + 1, sws + S.part);
-  hipLaunchKernelGGL(r3d_scene_transfer_compact_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, order, votes,
+  sc_excl_scan(sws + S.voff, M + 1, sws + S.part, st);
+  hipLaunchKernelGGL(r3d_scene_transfer_compact_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, v.order, votes,
                      sws + S.voff, cand, sws + S.uq);
-  hipLaunchKernelGGL(r3d_scene_transfer_tiles_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.cell, sws + S.voff, n_cells,
+  hipLaunchKernelGGL(r3d_scene_transfer_tiles_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, v.cell, sws + S.voff, v.n_cells,
                      (int)M, sws + S.tile0, sws + S.rec);
   // sum over the cells of ceil(u / SC_Q_TILE) <= U / SC_Q_TILE + cells that hold such a point
-  const long tiles = M / SC_Q_TILE + (n_cells < M ? n_cells : M) + 1;
-  if (neighbours)
-    hipLaunchKernelGGL(r3d_scene_transfer_kernel<3>, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
-                       sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
-                       (long long*)source, sws + S.rec, votes, (long long*)neighbours, weights);
-  else
-    hipLaunchKernelGGL(r3d_scene_transfer_kernel<1>, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, ws + L.cell,
-                       sws + S.voff, sws + S.uq, sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels,
-                       (long long*)source, sws + S.rec, votes, (long long*)nullptr, (float*)nullptr);
+  const long tiles = M / SC_Q_TILE + (v.n_cells < M ? v.n_cells : M) + 1;
+  const auto kernel = neighbours ? r3d_scene_transfer_kernel<3> : r3d_scene_transfer_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, v.cell, sws + S.voff, sws + S.uq,
+                     sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels, (long long*)source, sws + S.rec, votes,
+                     (long long*)neighbours, weights);
   R3D_LAUNCH_CHECK("r3d_scene_transfer");
   return R3D_OK;
-}
-
-extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
-                                  long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores, int64_t* labels,
-                                  const int32_t* votes, int64_t* source, void* stream) {
-  return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
-                     nullptr, nullptr, stream);
-}
-
-extern "C" int r3d_scene_transfer_idw(const float* scan, int ld, long M, int ncx, int ncy, long chunk_cap, const int32_t* ws,
-                                      long ws_words, int32_t* sws, long sws_words, int n_classes, float* scores,
-                                      int64_t* labels, const int32_t* votes, int64_t* source, int64_t* neighbours,
-                                      float* weights, void* stream) {
-  R3D_REQUIRE(neighbours && weights, "r3d_scene_transfer_idw: null pointer (neighbours %p, weights %p)", (void*)neighbours,
-              (void*)weights);
-  return sc_transfer(scan, ld, M, ncx, ncy, chunk_cap, ws, ws_words, sws, sws_words, n_classes, scores, labels, votes, source,
-                     neighbours, weights, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ several support sets, one label
@@ -1270,21 +1293,17 @@ extern "C" int r3d_scene_support_counts(long M, int ncx, int ncy, int r, int N, 
                                         int32_t* fg, void* stream) {
   R3D_REQUIRE(ws && labels && classes && fg, "r3d_scene_support_counts: null pointer (ws %p, labels %p, classes %p, fg %p)",
               (const void*)ws, labels, (const void*)classes, (void*)fg);
-  const int ld = 3;
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_support_counts");
+  SC_TRY(sc_check_plan("r3d_scene_support_counts", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_support_counts", r, N));
   SC_REQUIRE_SUPPORT_ARGS("r3d_scene_support_counts");
   R3D_REQUIRE(label_bytes == 4 || label_bytes == 8, "r3d_scene_support_counts: labels of %d bytes (int32 or int64)", label_bytes);
-  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
-  const int nb = g.nbx * g.nby;
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, nullptr);
   if (label_bytes == 8)
-    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<long long>, dim3(nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
-                       (const long long*)labels, (int)M, ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, g, classes,
-                       n_way, fg);
+    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<long long>, dim3(v.nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                       (const long long*)labels, (int)M, v.order, v.cell, v.blk_n, v.chunk0, v.g, classes, n_way, fg);
   else
-    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<int>, dim3(nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
-                       (const int*)labels, (int)M, ws + L.idx[L.sorted], ws + L.cell, ws + L.blk_n, ws + L.chunk0, g, classes, n_way,
-                       fg);
+    hipLaunchKernelGGL(r3d_scene_support_counts_kernel<int>, dim3(v.nb), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                       (const int*)labels, (int)M, v.order, v.cell, v.blk_n, v.chunk0, v.g, classes, n_way, fg);
   R3D_LAUNCH_CHECK("r3d_scene_support_counts");
   return R3D_OK;
 }
@@ -1295,16 +1314,15 @@ extern "C" int r3d_scene_support_pick(long M, int ncx, int ncy, int r, int N, lo
   R3D_REQUIRE(ws && fg && shot_block && shot_fg && rec,
               "r3d_scene_support_pick: null pointer (ws %p, fg %p, shot_block %p, shot_fg %p, rec %p)", (const void*)ws,
               (const void*)fg, (void*)shot_block, (void*)shot_fg, (void*)rec);
-  const int ld = 3;
-  SC_REQUIRE_PLAN_ARGS("r3d_scene_support_pick");
+  SC_TRY(sc_check_plan("r3d_scene_support_pick", M, ncx, ncy, chunk_cap, ws_words));
+  SC_TRY(sc_check_blocks("r3d_scene_support_pick", r, N));
   SC_REQUIRE_SUPPORT_ARGS("r3d_scene_support_pick");
   R3D_REQUIRE(k_shot >= 1 && k_shot <= 64, "r3d_scene_support_pick: k_shot %d (1 .. 64)", k_shot);
   R3D_REQUIRE(min_ratio >= 0.0f && min_ratio < 1.0f, "r3d_scene_support_pick: min_ratio %g (0 <= ratio < 1)", (double)min_ratio);
   R3D_REQUIRE(min_fg >= 0, "r3d_scene_support_pick: min_fg %d (at least 0)", min_fg);
-  const sc_layout L = sc_make_layout(M, (long)ncx * ncy, chunk_cap);
-  const sc_grid g = sc_make_grid(ncx, ncy, r, M);
-  hipLaunchKernelGGL(r3d_scene_support_pick_kernel, dim3(n_way), dim3(SC_THREADS), 0, (hipStream_t)stream, ws + L.blk_n,
-                     ws + L.chunk0, g.nbx * g.nby, fg, n_way, k_shot, min_ratio, min_fg, shot_block, shot_fg, rec);
+  const sc_view v = sc_make_view(M, ncx, ncy, r, chunk_cap, ws, nullptr);
+  hipLaunchKernelGGL(r3d_scene_support_pick_kernel, dim3(n_way), dim3(SC_THREADS), 0, (hipStream_t)stream, v.blk_n, v.chunk0,
+                     v.nb, fg, n_way, k_shot, min_ratio, min_fg, shot_block, shot_fg, rec);
   R3D_LAUNCH_CHECK("r3d_scene_support_pick");
   return R3D_OK;
 }
@@ -1512,13 +1530,6 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_flags_kernel(const i
   contrib[i] = c;
 }
 
-static void sg_excl_scan(int* a, long n, int* part, hipStream_t st) {
-  const int nb = (int)((n + SC_TILE - 1) / SC_TILE);
-  hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(nb), dim3(SC_THREADS), 0, st, a, n, part);
-  hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, part, nb);
-  hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(nb), dim3(SC_THREADS), 0, st, a, n, part);
-}
-
 // after the scans: heads[i] = segments opened in front of i, contrib[i] = contributors in front of i.  Every segment's
 // row of the tables is written by the thread of its first sorted position, row S by the thread of position M.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_tables_kernel(
@@ -1595,18 +1606,7 @@ extern "C" int r3d_scene_seg_group(const void* segments, int seg_bytes, long M, 
   else
     hipLaunchKernelGGL(r3d_scene_seg_keys_kernel<int>, dim3(gm), dim3(SC_THREADS), 0, st, (const int*)segments, (int)M, none,
                        ws + L.key[0], ws + L.idx[0]);
-  const long n_hist = 256L * L.n_tiles;
-  for (int p = 0; p < passes; ++p) {
-    const int a = p & 1, b = a ^ 1;
-    hipLaunchKernelGGL(r3d_scene_hist_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], (int)M, 8 * p, L.n_tiles,
-                       ws + L.hist);
-    hipLaunchKernelGGL(r3d_scene_scan_sum_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
-    hipLaunchKernelGGL(r3d_scene_scan_part_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, ws + L.part, L.n_part);
-    hipLaunchKernelGGL(r3d_scene_scan_local_kernel, dim3(L.n_part), dim3(SC_THREADS), 0, st, ws + L.hist, n_hist, ws + L.part);
-    hipLaunchKernelGGL(r3d_scene_scatter_kernel, dim3(L.n_tiles), dim3(SC_THREADS), 0, st, ws + L.key[a], ws + L.idx[a], (int)M,
-                       8 * p, L.n_tiles, ws + L.hist, ws + L.key[b], ws + L.idx[b]);
-  }
-  const int sorted = passes & 1, spare = sorted ^ 1;
+  const int sorted = sc_sort_pairs(ws, L.key, L.idx, L.hist, L.part, M, L.n_tiles, passes, st), spare = sorted ^ 1;
   int* skey = ws + L.key[sorted];
   int* order = ws + L.idx[sorted];
   int* heads = ws + L.key[spare];
@@ -1614,13 +1614,13 @@ extern "C" int r3d_scene_seg_group(const void* segments, int seg_bytes, long M, 
   const int n_in_seg = (int)(M - n_negative);
   hipLaunchKernelGGL(r3d_scene_seg_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, skey, order, (int)M, none, votes, heads,
                      contrib);
-  sg_excl_scan(heads, M + 1, ws + L.part, st);
-  sg_excl_scan(contrib, M + 1, ws + L.part, st);
+  sc_excl_scan(heads, M + 1, ws + L.part, st);
+  sc_excl_scan(contrib, M + 1, ws + L.part, st);
   hipLaunchKernelGGL(r3d_scene_seg_tables_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, skey, order, (int)M, n_in_seg, heads, contrib,
                      ws + L.seg_start, ws + L.cstart, ws + L.seg_id, ws + L.clist, segment_index);
   hipLaunchKernelGGL(r3d_scene_seg_tile_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, n_in_seg, heads, contrib,
                      ws + L.cstart, ws + L.tiles);
-  sg_excl_scan(ws + L.tiles, M + 1, ws + L.part, st);
+  sc_excl_scan(ws + L.tiles, M + 1, ws + L.part, st);
   hipLaunchKernelGGL(r3d_scene_seg_tile_table_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, (int)M, n_in_seg, heads, contrib,
                      ws + L.tiles, ws + L.tile_seg, ws + L.rec);
   R3D_LAUNCH_CHECK("r3d_scene_seg_group");

@@ -751,19 +751,16 @@ def scene_plan(scan, x0, y0, s, ncx, ncy, r, N, min_points, chunk_cap, ws):
 def scene_prepare(scan, ncx, ncy, r, N, chunk_cap, ws, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None, sws=None):
     """Chunks first_chunk .. first_chunk + G - 1 -> out (G, C, N) fp32, read as it lies (contiguous channel-major or a
     transposed view of point-major rows: its strides travel with it).  slot_map (G, N) int32: the scan index per slot.
-    sws (the sparse workspace after scene_run_tables): first_chunk numbers the chunks that run under the cap."""
+    sws (the sparse workspace after scene_run_tables): first_chunk numbers the chunks that run under the cap; None: no cap."""
     assert out.dim() == 3 and out.dtype == torch.float32 and out.is_cuda
     G, C, N_ = out.shape
     assert N_ == N and (slot_map is None or (tuple(slot_map.shape) == (G, N) and slot_map.dtype == torch.int32
                                              and slot_map.is_contiguous() and slot_map.is_cuda))
     M, ld = scan.shape
     os_ = out.stride()
-    tail = (first_chunk, G, C, rgb_ch, XYZ_ch, _p(out), os_[0], os_[1], os_[2], _p(slot_map), _st())
-    if sws is None:
-        _lib.check(_lib.load().r3d_scene_prepare(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), *tail))
-    else:
-        _lib.check(_lib.load().r3d_scene_prepare_run(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws),
-                                                     sws.numel(), *tail))
+    _lib.check(_lib.load().r3d_scene_prepare(_p(scan), ld, M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws),
+                                             0 if sws is None else sws.numel(), first_chunk, G, C, rgb_ch, XYZ_ch, _p(out),
+                                             os_[0], os_[1], os_[2], _p(slot_map), _st()))
     return out
 
 
@@ -776,11 +773,9 @@ def scene_vote(M, ncx, ncy, r, N, chunk_cap, ws, logits, sws=None):
     scores = torch.empty(M, K, device=dev, dtype=torch.float32)
     labels = torch.empty(M, device=dev, dtype=torch.int64)
     votes = torch.empty(M, device=dev, dtype=torch.int32)
-    tail = (_p(logits), n_chunks, K, _p(scores), _p(labels), _p(votes), _st())
-    if sws is None:
-        _lib.check(_lib.load().r3d_scene_vote(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), *tail))
-    else:
-        _lib.check(_lib.load().r3d_scene_vote_run(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(), *tail))
+    _lib.check(_lib.load().r3d_scene_vote(M, ncx, ncy, r, N, chunk_cap, _p(ws), ws.numel(), _p(sws),
+                                          0 if sws is None else sws.numel(), _p(logits), n_chunks, K, _p(scores), _p(labels),
+                                          _p(votes), _st()))
     return scores, labels, votes
 
 
@@ -807,32 +802,30 @@ def scene_run_tables(M, ncx, ncy, r, N, chunk_cap, ws, max_chunks, sws):
                                                 sws.numel(), _st()))
 
 
-def scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
-    """In place: scores (M, K) fp32 and labels (M,) int64 of the points with votes == 0 from their nearest voted neighbour
-    in the 3 x 3 cells -> source (M,) int64; the count of receivers is word 0 of the sparse record, on the device."""
+def _scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes, idw):
     M, ld = scan.shape
     assert scan.is_contiguous() and scores.is_contiguous() and tuple(scores.shape[:1]) == (M,) and scores.dtype == torch.float32
     assert tuple(labels.shape) == (M,) and labels.dtype == torch.int64 and tuple(votes.shape) == (M,) and votes.dtype == torch.int32
     source = torch.empty(M, device=scan.device, dtype=torch.int64)
+    neighbours = torch.empty(M, 3, device=scan.device, dtype=torch.int64) if idw else None
+    weights = torch.empty(M, 3, device=scan.device, dtype=torch.float32) if idw else None
     _lib.check(_lib.load().r3d_scene_transfer(_p(scan), ld, M, ncx, ncy, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(),
-                                              scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source), _st()))
-    return source
+                                              scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source), _p(neighbours),
+                                              _p(weights), _st()))
+    return source, neighbours, weights
+
+
+def scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
+    """In place: scores (M, K) fp32 and labels (M,) int64 of the points with votes == 0 from their nearest voted neighbour
+    in the 3 x 3 cells -> source (M,) int64; the count of receivers is word 0 of the sparse record, on the device."""
+    return _scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes, False)[0]
 
 
 def scene_transfer_idw(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes):
     """In place: scores (M, K) fp32 and labels (M,) int64 of the points with votes == 0 from the three nearest voted points
     of the 3 x 3 cells, their mean logits weighted by 1 / (d + 1e-8) -> (source (M,) int64, neighbours (M, 3) int64,
     weights (M, 3) fp32); the count of receivers is word 0 of the sparse record, on the device."""
-    M, ld = scan.shape
-    assert scan.is_contiguous() and scores.is_contiguous() and tuple(scores.shape[:1]) == (M,) and scores.dtype == torch.float32
-    assert tuple(labels.shape) == (M,) and labels.dtype == torch.int64 and tuple(votes.shape) == (M,) and votes.dtype == torch.int32
-    source = torch.empty(M, device=scan.device, dtype=torch.int64)
-    neighbours = torch.empty(M, 3, device=scan.device, dtype=torch.int64)
-    weights = torch.empty(M, 3, device=scan.device, dtype=torch.float32)
-    _lib.check(_lib.load().r3d_scene_transfer_idw(_p(scan), ld, M, ncx, ncy, chunk_cap, _p(ws), ws.numel(), _p(sws), sws.numel(),
-                                                  scores.shape[1], _p(scores), _p(labels), _p(votes), _p(source),
-                                                  _p(neighbours), _p(weights), _st()))
-    return source, neighbours, weights
+    return _scene_transfer(scan, ncx, ncy, chunk_cap, ws, sws, scores, labels, votes, True)
 
 
 # ---- predict_scene_sets: the scores of K support sets merged into one label per point

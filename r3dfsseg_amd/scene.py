@@ -16,11 +16,12 @@ restates it in numpy) and it draws no random number: the same scan gives the sam
   6. per scan point the sum of its chunks' logits, in a fixed order          r3d_scene_vote
 
 Two options, both off by default, label a dense scan on an even subsample (steps 7a, 8' and 9 of the definition):
-max_chunks_per_block=c runs only chunks j < c of a block (r3d_scene_run_tables, _prepare_run, _vote_run; still two
-host reads), and transfer="nearest" gives every valid point without a vote the scores and label of the nearest voted
-point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receivers is one more host read, at the end);
-transfer="idw" (step 9') gives it the mean logits of the three nearest such points, weighted by 1 / (d + 1e-8) with d the
-squared distance, and the arg-max of those (r3d_scene_transfer_idw: same receivers, same candidates, same host read).
+max_chunks_per_block=c runs only chunks j < c of a block (r3d_scene_run_tables; r3d_scene_prepare and r3d_scene_vote then
+number the chunks that run; still two host reads), and transfer="nearest" gives every valid point without a vote the
+scores and label of the nearest voted point among the 3 x 3 cells around it (r3d_scene_transfer; its count of receivers
+is one more host read, at the end); transfer="idw" (step 9') gives it the mean logits of the three nearest such points,
+weighted by 1 / (d + 1e-8) with d the squared distance, and the arg-max of those (r3d_scene_transfer given neighbours and
+weights: same receivers, same candidates, same host read).  No cap is the cap nobody reaches: every chunk runs.
 
 predict_scene_sets labels the scan against K fitted support sets at once ("Labelling a scan against several
 support sets"): steps 1-6 once, per launch one encoder pass and the K heads on its feature rows (step 7s), the vote and the
@@ -119,10 +120,11 @@ class ScenePlan:
     """Steps 1-5 of the definition for one scan on the device: what r3d_scene_plan left in its workspace, as views.
     order (n_valid,): scan indices sorted by cell, stable; cell_start (n_cells + 1,): offsets of the cells into it;
     block_points (nb,); block_chunk0 (nb + 1,): first chunk of a block; chunk_block (n_chunks,).  Host: x0, y0, xmax,
-    ymax (fp32), n_valid, ncx, ncy, nbx, nby, n_chunks, n_blocks (kept), n_voted (valid points of a kept block).
-    With max_chunks_per_block=c (step 7a): run_chunk0 (nb + 1,): first run chunk of a block; run_block (n_run,); host:
-    n_run, n_skipped, and n_voted counts the valid points of a chunk that runs; prepare and vote then number the run
-    chunks.  Without a cap n_run == n_chunks and n_skipped == 0."""
+    ymax (fp32), n_valid, ncx, ncy, nbx, nby, n_chunks, n_blocks (kept).
+    The chunks that run (all of them, or with max_chunks_per_block=c those of step 7a): run_chunk0 (nb + 1,): first run
+    chunk of a block; run_block (n_run,); host: n_run, n_skipped, n_voted (the valid points of a chunk that runs); prepare
+    and vote number the run chunks.  Without a cap the run tables are block_chunk0 and chunk_block themselves, n_run ==
+    n_chunks and n_skipped == 0."""
 
     def __init__(self, scan, N, block_size=1.0, stride=None, min_points=100, max_chunks_per_block=None):
         check_sparse_args(max_chunks_per_block, None)
@@ -150,17 +152,16 @@ class ScenePlan:
         ops.scene_plan(self.scan, self.x0, self.y0, self.s, self.ncx, self.ncy, self.r, self.N, self.min_points, self.chunk_cap,
                        self.ws)
         self.cap, self.sws = max_chunks_per_block, None
+        self.run_sws = None  # what prepare and vote are given: the run tables, or None for the plan's own chunk tables
+        run, run_chunk0, run_block = self.ws, o["block_chunk0"], o["chunk_block"]
         if self.cap is not None:
-            self._sparse_workspace()
+            run = self.run_sws = self._sparse_workspace()
+            run_chunk0, run_block = self.so["run_chunk0"], self.so["run_block"]
             ops.scene_run_tables(self.M, *self._geometry(), min(int(self.cap), 2 ** 30), self.sws)
         rec = self.ws[o["rec"]:o["rec"] + 8].tolist()  # host read 2 of 2
-        self.n_chunks, self.n_blocks, self.n_voted = rec[:3]
-        self.n_run, self.n_skipped = (self.n_chunks, 0) if self.cap is None else rec[4:6]
-        if self.cap is not None:
-            self.n_voted = rec[6]
-            so = self.so
-            self.run_chunk0 = self.sws[so["run_chunk0"]:so["run_chunk0"] + nb + 1]
-            self.run_block = self.sws[so["run_block"]:so["run_block"] + self.n_run]
+        self.n_chunks, self.n_blocks = rec[:2]
+        self.n_run, self.n_skipped, self.n_voted = rec[4:7]
+        self.run_chunk0, self.run_block = run[run_chunk0:run_chunk0 + nb + 1], run[run_block:run_block + self.n_run]
         view = lambda name, n: self.ws[o[name]:o[name] + n]
         self.order, self.sorted_key, self.pos = view("order", self.n_valid), view("sorted_key", self.M), view("pos", self.M)
         self.cell_start = view("cell_start", self.n_cells + 1)
@@ -178,8 +179,7 @@ class ScenePlan:
     def prepare(self, first_chunk, out, rgb_ch, XYZ_ch, slot_map=None):
         """Chunks first_chunk .. first_chunk + out.shape[0] - 1 (under a cap: of the chunks that run) as prepared clouds ->
         out (G, C, N), in out's own layout."""
-        return ops.scene_prepare(self.scan, *self._geometry(), first_chunk, out, rgb_ch, XYZ_ch, slot_map,
-                                 sws=None if self.cap is None else self.sws)
+        return ops.scene_prepare(self.scan, *self._geometry(), first_chunk, out, rgb_ch, XYZ_ch, slot_map, sws=self.run_sws)
 
     def vote(self, logits):
         """logits (n_run, n_classes, N) -> (scores (M, n_classes), labels (M,) int64, votes (M,) int32)."""
@@ -189,7 +189,7 @@ class ScenePlan:
             dev, K = self.scan.device, logits.shape[1]
             return (torch.zeros(self.M, K, device=dev), torch.full((self.M,), -1, device=dev, dtype=torch.int64),
                     torch.zeros(self.M, device=dev, dtype=torch.int32))
-        return ops.scene_vote(self.M, *self._geometry(), logits.contiguous(), sws=None if self.cap is None else self.sws)
+        return ops.scene_vote(self.M, *self._geometry(), logits.contiguous(), sws=self.run_sws)
 
     def transfer(self, scores, labels, votes, mode="nearest"):
         """Step 9 (mode "nearest") or 9' ("idw"), in place on what vote() returned -> (source (M,) int64, n_transferred: a

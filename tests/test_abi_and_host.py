@@ -22,7 +22,7 @@ def test_library_of_abi_5_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert set(_lib._SIGS) == set(declared), set(_lib._SIGS) ^ set(declared)
     lib.r3d_abi_version.restype = ctypes.c_int
-    assert lib.r3d_abi_version() == 5
+    assert lib.r3d_abi_version() == 6
     lib.r3d_head_desc_words.restype = ctypes.c_int
     assert lib.r3d_head_desc_words() == 32
     lib.r3d_lp_ws_words.restype = ctypes.c_long
@@ -31,16 +31,16 @@ def test_library_of_abi_5_exports_every_declared_symbol():
 
 def test_loading_a_library_of_another_abi_version_than_5_is_refused(monkeypatch):
     """A stale libr3d_hip.so would be called with this package's argument lists (ABI 5 replaced the four scratch buffers of
-    r3d_knn_topk_batched with one workspace): load() compares r3d_abi_version() with the version the bindings were written
+    r3d_knn_topk_batched with one workspace, ABI 6 gave r3d_scene_prepare, _vote and _transfer more arguments): load() compares r3d_abi_version() with the version the bindings were written
     for and says how to rebuild."""
     from r3dfsseg_amd import build
     build.build()
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="C ABI version 5.*rebuild"):
+    with pytest.raises(RuntimeError, match="C ABI version 6.*rebuild"):
         _lib.load()
-    monkeypatch.setattr(_lib, "ABI_VERSION", 5)
-    assert _lib.load().r3d_abi_version() == 5
+    monkeypatch.setattr(_lib, "ABI_VERSION", 6)
+    assert _lib.load().r3d_abi_version() == 6
 
 
 def test_binding_signatures_match_the_header():

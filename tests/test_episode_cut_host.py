@@ -28,7 +28,7 @@ def pool(source):
 
 
 def test_abi_declares_the_cut_and_stays_version_5():
-    assert _lib.ABI_VERSION == 5 and "r3d_episode_cut" in _lib.header_symbols()
+    assert _lib.ABI_VERSION == 6 and "r3d_episode_cut" in _lib.header_symbols()
     res, args = _lib._SIGS["r3d_episode_cut"]
     assert res is _lib.c_i and len(args) == 27 and args[12] is _lib.c_u and args[4] is _lib.c_l
 

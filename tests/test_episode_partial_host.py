@@ -47,7 +47,7 @@ def _rows(labels, inst, seed=0):
 
 
 def test_abi_declares_the_partial_cut_and_stays_version_5():
-    assert _lib.ABI_VERSION == 5 and "r3d_episode_cut_partial" in _lib.header_symbols()
+    assert _lib.ABI_VERSION == 6 and "r3d_episode_cut_partial" in _lib.header_symbols()
     res, args = _lib._SIGS["r3d_episode_cut_partial"]
     old = _lib._SIGS["r3d_episode_cut"][1]
     assert res is _lib.c_i and len(old) == 27 and len(args) == 29

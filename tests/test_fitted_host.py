@@ -26,7 +26,7 @@ def test_header_declares_the_new_entry_points_and_the_binding_parses_them():
     assert sim[3] is _lib.c_l and sim[6] is _lib.c_l and sim[10] is _lib.c_fl  # q_sys_rows, proto_stride, scaler
     att = _lib._SIGS["r3d_head_attach_queries_batched"][1]
     assert att[2] is _lib.c_l and att[4] is _lib.c_l and att[7] is _lib.c_i and att[16] is _lib.c_i  # pitches long, caps int
-    assert _lib.ABI_VERSION == 5 and re.search(r"int r3d_abi_version\(void\); /\* 5:", txt)
+    assert _lib.ABI_VERSION == 6 and re.search(r"int r3d_abi_version\(void\); /\* 6:", txt)
 
 
 def _cpu_model(cls=ProtoNet, **over):

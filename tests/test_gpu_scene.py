@@ -60,6 +60,24 @@ def test_plan_small(r):
     _same_plan(_device_plan(scan, SC.SMALL["N"], r, SC.SMALL["stride"], SC.SMALL["min_points"]), p)
 
 
+@pytest.mark.parametrize("r", [1, 2])
+def test_without_a_cap_every_chunk_is_a_run_chunk(r):
+    """r3d_scene_plan alone leaves the record of a cap nobody reaches -- run chunks = chunks, none skipped, the same voted
+    points -- and ScenePlan's run tables are then the plan's own chunk tables."""
+    from r3dfsseg_amd import ops
+    scan, _ = SC.small_scan()
+    p = SC.small_plan(r)
+    d = _device_plan(scan, SC.SMALL["N"], r, SC.SMALL["stride"], SC.SMALL["min_points"])
+    assert d.cap is None and d.sws is None  # no run tables were written
+    at = ops.scene_workspace(d.M, d.ncx, d.ncy, d.chunk_cap, "cuda")[1]["rec"]
+    rec = d.ws[at:at + 8].tolist()
+    assert rec[0] == p.n_chunks > 0 and rec[2] > 0
+    assert rec[4] == rec[0] and rec[5] == 0 and rec[6] == rec[2]
+    assert (d.n_run, d.n_skipped, d.n_voted) == (rec[0], 0, rec[2])
+    assert torch.equal(d.run_chunk0, d.block_chunk0) and torch.equal(d.run_block, d.chunk_block)
+    assert d.run_chunk0.data_ptr() == d.block_chunk0.data_ptr() and d.run_block.data_ptr() == d.chunk_block.data_ptr()
+
+
 # ---- 2. more than one tile and more than one radix pass ----------------------------------------------------------------------
 @pytest.mark.parametrize("r", [1, 4])
 def test_plan_many_tiles_two_radix_passes(r):

@@ -25,7 +25,7 @@ def test_header_and_binding_declare_the_batched_protonet_head():
         assert len(protos[name]) == len(_lib._SIGS[name][1]) == n_args, (name, protos[name], _lib._SIGS[name][1])
     assert _lib._SIGS["r3d_protonet_head_ws_words"][0] is _lib.c_l
     assert _lib._SIGS["r3d_protonet_head_batched"][0] is _lib.c_i
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
 
 
 def test_library_exports_the_batched_protonet_head_under_abi_5():
@@ -36,7 +36,7 @@ def test_library_exports_the_batched_protonet_head_under_abi_5():
     for name in NEW:
         assert hasattr(lib, name), name
     lib.r3d_abi_version.restype = ctypes.c_int
-    assert lib.r3d_abi_version() == 5
+    assert lib.r3d_abi_version() == 6
     # the scratch size is host arithmetic: S * 2 * 256 floats per episode, negative for a shape the kernels do not carry
     f = lib.r3d_protonet_head_ws_words
     f.restype, f.argtypes = ctypes.c_long, [ctypes.c_int] * 3

@@ -77,4 +77,4 @@ def test_training_entry_points_are_declared_and_bound():
     names = {"r3d_protonet_head_train_ws_words", "r3d_protonet_head_train_fwd", "r3d_protonet_head_bwd"}
     assert names <= set(_lib._SIGS)
     assert names <= set(_lib.header_symbols())
-    assert _lib.ABI_VERSION == 5  # additive change
+    assert _lib.ABI_VERSION == 6  # additive change

@@ -124,7 +124,7 @@ def test_entry_points_refuse_null_pointers_and_short_workspaces():
     lib = _lib.load()
     err = lambda: lib.r3d_last_error_string().decode()
     p = ctypes.c_void_p(64)  # never dereferenced: every call below fails its argument checks before any launch
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
     assert lib.r3d_scene_bounds_ws_words(1000) == 5 * 4 and lib.r3d_scene_bounds_ws_words(10 ** 7) == 5 * 1024
     assert lib.r3d_scene_bounds(None, 6, 1000, p, p, 20, None) != 0 and "null" in err()
     assert lib.r3d_scene_bounds(p, 6, 1000, p, p, 19, None) != 0 and "workspace" in err()
@@ -145,15 +145,15 @@ def test_entry_points_refuse_null_pointers_and_short_workspaces():
     assert plan(p, p, words, mp=0) != 0 and "min_points" in err()
     assert plan(p, p, words, s=0.0) != 0 and "cell size" in err()
     assert plan(p, p, 1 << 30, ncx=70000) != 0 and "cells" in err()
-    prep = lambda scan, ws, out, n, **k: lib.r3d_scene_prepare(scan, k.get("ld", 6), 1000, 6, 4, 2, 256, 50, ws, n, k.get("c0", 0),
-                                                               k.get("G", 8), k.get("C", 9), k.get("rgb", 3), k.get("XYZ", 6), out,
+    prep = lambda scan, ws, out, n, **k: lib.r3d_scene_prepare(scan, k.get("ld", 6), 1000, 6, 4, 2, 256, 50, ws, n, None, 0,
+                                                               k.get("c0", 0), k.get("G", 8), k.get("C", 9), k.get("rgb", 3), k.get("XYZ", 6), out,
                                                                9 * 256, 1, 9, None, None)
     assert prep(p, p, None, words) != 0 and "null" in err()
     assert prep(p, p, p, words - 1) != 0 and "workspace" in err()
     assert prep(p, p, p, words, c0=45) != 0 and "chunk table" in err()
     assert prep(p, p, p, words, C=6) != 0 and "does not hold" in err()
     assert prep(p, p, p, words, ld=3) != 0 and "colour" in err()
-    vote = lambda ws, lg, n, **k: lib.r3d_scene_vote(1000, 6, 4, 2, 256, 50, ws, n, lg, k.get("nch", 10), 3, p, p, p, None)
+    vote = lambda ws, lg, n, **k: lib.r3d_scene_vote(1000, 6, 4, 2, 256, 50, ws, n, None, 0, lg, k.get("nch", 10), 3, p, p, p, None)
     assert vote(p, None, words) != 0 and "null" in err()
     assert vote(p, p, words - 1) != 0 and "workspace" in err()
     assert vote(p, p, words, nch=51) != 0 and "n_chunks" in err()

@@ -50,7 +50,7 @@ def test_the_result_keeps_its_constructor():
     assert (res.source, res.n_transferred, res.n_chunks_skipped) == (8, 9, 10) and res.neighbours is None and res.weights is None
     res = scene.SceneResult(1, 2, 3, 4, 5, 6, 7, neighbours="n", weights="w")
     assert (res.neighbours, res.weights) == ("n", "w")
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
 
 
 def _candidates(p, votes, rcv):
@@ -150,11 +150,13 @@ def test_the_new_entry_point_refuses_null_pointers_and_short_workspaces():
     lib = _lib.load()
     err = lambda: lib.r3d_last_error_string().decode()
     p = ctypes.c_void_p(64)  # never dereferenced: every call below fails its argument checks before any launch
-    assert _lib.ABI_VERSION == 5 and "r3d_scene_transfer_idw" in _lib.header_symbols()
+    assert _lib.ABI_VERSION == 6 and "r3d_scene_transfer" in _lib.header_symbols()
+    # ABI 6 merged the twins into the entry points they were named after
+    assert not {"r3d_scene_" + twin for twin in ("prepare_run", "vote_run", "transfer_idw")} & set(_lib.header_symbols())
     words, sw = lib.r3d_scene_ws_words(1000, 6, 4, 50), lib.r3d_scene_sparse_ws_words(1000, 6, 4, 50)
 
     def idw(n=words, sn=sw, K=3, scan=p, ws=p, sws=p, scores=p, labels=p, votes=p, src=p, nbr=p, wgt=p):
-        return lib.r3d_scene_transfer_idw(scan, 6, 1000, 6, 4, 50, ws, n, sws, sn, K, scores, labels, votes, src, nbr, wgt, None)
+        return lib.r3d_scene_transfer(scan, 6, 1000, 6, 4, 50, ws, n, sws, sn, K, scores, labels, votes, src, nbr, wgt, None)
     for name in ("scan", "ws", "sws", "scores", "labels", "votes", "src", "nbr", "wgt"):
         assert idw(**{name: None}) != 0 and "null" in err(), name
     assert idw(n=words - 1) != 0 and "workspace" in err()
@@ -162,7 +164,7 @@ def test_the_new_entry_point_refuses_null_pointers_and_short_workspaces():
     assert idw(K=65) != 0 and "n_classes" in err()
     assert idw(K=0) != 0 and "n_classes" in err()
     # the messages are those of r3d_scene_transfer
-    tr = lambda n, sn, K=3: lib.r3d_scene_transfer(p, 6, 1000, 6, 4, 50, p, n, p, sn, K, p, p, p, p, None)
+    tr = lambda n, sn, K=3: lib.r3d_scene_transfer(p, 6, 1000, 6, 4, 50, p, n, p, sn, K, p, p, p, p, None, None, None)
     for kw, args in ((dict(n=words - 1), (words - 1, sw)), (dict(sn=sw - 1), (words, sw - 1)), (dict(K=65), (words, sw, 65))):
         assert idw(**kw) != 0
         mine = err()

@@ -99,7 +99,7 @@ def test_signatures_and_abi():
         sig = inspect.signature(L.pool_segments)
         assert list(sig.parameters) == ["self", "res", "segments"] + list(want)
         assert {k: sig.parameters[k].default for k in want} == want
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
     for name in ("r3d_scene_seg_ws_words", "r3d_scene_seg_ids", "r3d_scene_seg_group", "r3d_scene_seg_pool",
                  "r3d_scene_seg_spread"):
         assert name in _lib.header_symbols()

@@ -136,7 +136,7 @@ def test_signatures():
     sig = inspect.signature(FewShotFeatures.predict_scene_sets)
     assert list(sig.parameters)[:3] == ["self", "fits", "scan"] and sig.parameters["launch"].default is None
     assert list(inspect.signature(scene.predict_scene_sets).parameters) == ["model"] + list(sig.parameters)[1:]
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
     for name in ("r3d_scene_merge_sets", "r3d_protonet_similarity_sets", "r3d_head_attach_queries_sets"):
         assert name in _lib.header_symbols()
 

@@ -135,7 +135,7 @@ def test_new_entry_points_refuse_null_pointers_and_short_workspaces():
     lib = _lib.load()
     err = lambda: lib.r3d_last_error_string().decode()
     p = ctypes.c_void_p(64)  # never dereferenced: every call below fails its argument checks before any launch
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
     words, sw = lib.r3d_scene_ws_words(1000, 6, 4, 50), lib.r3d_scene_sparse_ws_words(1000, 6, 4, 50)
     assert sw > 5 * 1000 and lib.r3d_scene_sparse_ws_words(1000, 300, 300, 50) == -1
     offs = (ctypes.c_long * 8)()
@@ -149,15 +149,38 @@ def test_new_entry_points_refuse_null_pointers_and_short_workspaces():
     assert run(p, p, words - 1, sw) != 0 and "workspace" in err()
     assert run(p, p, words, sw - 1) != 0 and "sparse workspace" in err()
     assert run(p, p, words, sw, cap=0) != 0 and "max_chunks" in err()
-    prep = lambda sws, sn: lib.r3d_scene_prepare_run(p, 6, 1000, 6, 4, 2, 256, 50, p, words, sws, sn, 0, 8, 9, 3, 6, p, 9 * 256, 1, 9,
-                                                     None, None)
+    prep = lambda sws, sn: lib.r3d_scene_prepare(p, 6, 1000, 6, 4, 2, 256, 50, p, words, sws, sn, 0, 8, 9, 3, 6, p, 9 * 256, 1, 9,
+                                                 None, None)
     assert prep(None, sw) != 0 and "null" in err()
     assert prep(p, sw - 1) != 0 and "sparse workspace" in err()
-    vote = lambda sws, sn: lib.r3d_scene_vote_run(1000, 6, 4, 2, 256, 50, p, words, sws, sn, p, 10, 3, p, p, p, None)
+    vote = lambda sws, sn: lib.r3d_scene_vote(1000, 6, 4, 2, 256, 50, p, words, sws, sn, p, 10, 3, p, p, p, None)
     assert vote(None, sw) != 0 and "null" in err()
     assert vote(p, sw - 1) != 0 and "sparse workspace" in err()
-    tr = lambda src, n, sn, K=3: lib.r3d_scene_transfer(p, 6, 1000, 6, 4, 50, p, n, p, sn, K, p, p, p, src, None)
+    tr = lambda src, n, sn, K=3: lib.r3d_scene_transfer(p, 6, 1000, 6, 4, 50, p, n, p, sn, K, p, p, p, src, None, None, None)
     assert tr(None, words, sw) != 0 and "null" in err()
     assert tr(p, words - 1, sw) != 0 and "workspace" in err()
     assert tr(p, words, sw - 1) != 0 and "sparse workspace" in err()
     assert tr(p, words, sw, K=65) != 0 and "n_classes" in err()
+
+
+def test_optional_arguments_are_both_there_or_both_absent():
+    """ABI 6: sws of r3d_scene_prepare / r3d_scene_vote is NULL with 0 words (no cap) or a whole sparse workspace; neighbours
+    and weights of r3d_scene_transfer come together ("idw") or not at all ("nearest").  The NULL / 0 form gets past those
+    checks: the call then fails on a later one, a short ws."""
+    lib = _lib.load()
+    err = lambda: lib.r3d_last_error_string().decode()
+    p = ctypes.c_void_p(64)  # never dereferenced: every call below fails its argument checks before any launch
+    words, sw = lib.r3d_scene_ws_words(1000, 6, 4, 50), lib.r3d_scene_sparse_ws_words(1000, 6, 4, 50)
+    prep = lambda sws, sn, n=words: lib.r3d_scene_prepare(p, 6, 1000, 6, 4, 2, 256, 50, p, n, sws, sn, 0, 8, 9, 3, 6, p, 9 * 256, 1,
+                                                          9, None, None)
+    vote = lambda sws, sn, n=words: lib.r3d_scene_vote(1000, 6, 4, 2, 256, 50, p, n, sws, sn, p, 10, 3, p, p, p, None)
+    for call in (prep, vote):
+        assert call(None, sw) != 0 and "null" in err()
+        assert call(None, 1) != 0 and "null" in err()
+        assert call(None, 0, words - 1) != 0 and "null" not in err() and "sparse" not in err() and "workspace" in err()
+        assert call(p, sw, words - 1) != 0 and "null" not in err() and "sparse" not in err() and "workspace" in err()
+    tr = lambda nbr, wgt, n=words: lib.r3d_scene_transfer(p, 6, 1000, 6, 4, 50, p, n, p, sw, 3, p, p, p, p, nbr, wgt, None)
+    assert tr(p, None) != 0 and "null" in err()
+    assert tr(None, p) != 0 and "null" in err()
+    for both in (None, p):
+        assert tr(both, both, words - 1) != 0 and "null" not in err() and "workspace" in err()
