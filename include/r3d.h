@@ -735,6 +735,59 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
                          const int32_t* in_set_of, const float* in_margin, float* scores, int64_t* labels, uint8_t* pooled,
                          int64_t* set_labels, int32_t* set_of, float* margin, int32_t* ws, long ws_words, void* stream);
 
+/* ---- build_segments: the segments of r3d_scene_seg_* grown from the scan itself ("Building segments",
+ * G1-G7).  Additive: no entry point above changes.  The reference reads segment ids that an offline script wrote
+ * (dataloaders/loader.py:339-349); the definition is this project's.  A VALID point has finite x y z.  Voxel of a valid
+ * point: i_a = (int)floorf((v_a - v0_a) / voxel) per axis, v0 the minima read from the record, key = (iz * ny + iy) * nx +
+ * ix, nx, ny, nz <= 1024 the host's counts from the same arithmetic at the maxima.  ws: ONE int32 scratch of
+ * r3d_scene_grow_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the six calls of one build, which pass the same M
+ * and nx, ny, nz; its first 16 words are the record the host reads:
+ *   [0..2] min x y z, [3..5] max x y z (float bits)   [6] valid points   [7] occupied voxels V   [8] components
+ *   [9] kept components S   [10] points of dropped components   [11] != 0: a bounded loop of the union-find ran out
+ *
+ *   entry point                what it does                                                              host reads
+ *   r3d_scene_grow_bounds      words 0 .. 6 of the record, zeros in the others (r3d_scene_bounds keeps no z
+ *                              and stays as it is)                                                       words 0 .. 6
+ *   r3d_scene_grow_sort        keys (an invalid point: nx ny nz), the stable LSD radix sort of
+ *                              r3d_scene_plan on (key, scan index), 8 bits a pass up to the highest set bit
+ *                              of nx ny nz; the first sorted position of every voxel as a flag, their scan   word 7
+ *   r3d_scene_grow_voxels      n_valid, n_voxels: words 6 and 7 as read.  The voxel table: rows in ascending
+ *                              key order, a row's points by ascending scan index; voxel_index (M,) int32: the
+ *                              row of a point's voxel, -1 for an invalid point.  voxel_mean (V, 3) fp32 or
+ *                              NULL (no colour; else ld >= 6): the mean of columns 3 .. 5 per voxel, summed as
+ *                              r3d_scene_seg_pool sums a segment whose points all have one vote: ranks in
+ *                              tiles of 256, part = the first row, += the next, tot = the first tile's part,
+ *                              += the next, tot / (float)count.                                              -
+ *   r3d_scene_grow_union       parent[v] = v, then one thread per voxel a and the offsets (dx, dy, dz) with a
+ *                              larger key (3 for connectivity 6, 13 for 26): the neighbour's coordinates are
+ *                              checked against 0 .. n - 1 per axis, its key found by binary search among the
+ *                              rows behind a; with voxel_mean (else NULL) the pair is joined only when
+ *                              |mean_c(a) - mean_c(b)| <= colour_tol for c = r, g, b (fp32; a NaN joins
+ *                              nothing).  A joined pair is united by lock-free hooking: both roots found
+ *                              (path halving by atomicMin), the larger root compare-and-swapped onto the
+ *                              smaller, a failed swap goes on from the value it returned.  parent[v] <= v throughout; only agent-scope atomics
+ *                              touch parent[]; no thread waits; a find is bounded by V links and a unite by
+ *                              V + 1 attempts, an overrun sets word 11 and returns.                          -
+ *   r3d_scene_grow_components  root[v] = the root of v (the smallest row of its component), a launch of its
+ *                              own; points per root by integer atomics (the lanes of a wave that share a root
+ *                              add first); a root is KEPT when its component has at least min_points points;
+ *                              the kept roots' scan.                                                     words 8, 9, 11
+ *   r3d_scene_grow_ids         n_segments: word 9 as read.  Kept components are numbered 0 .. S - 1 by
+ *                              ascending root; segments (M,) int32: that number, -1 for an invalid point
+ *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          word 10
+ * No float atomics: the component of a voxel depends on the joined pairs alone, so the same scan gives the same bits. */
+long r3d_scene_grow_ws_words(long M);
+int r3d_scene_grow_bounds(const float* scan, int ld, long M, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny, int nz,
+                        int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, int ny, int nz, long n_valid, long n_voxels,
+                          int32_t* voxel_index, float* voxel_mean, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_union(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                         float colour_tol, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
+                       int32_t* segment_points, int32_t* ws, long ws_words, void* stream);
+
 /* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.

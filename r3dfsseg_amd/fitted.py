@@ -256,6 +256,16 @@ class FittedLearner(object):
         from . import scene_segments
         return scene_segments.pool_segments(res, segments, min_members, classes, background)
 
+    def build_segments(self, scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
+        """The segments pool_segments takes, grown from the scan itself: scan (M, 3) or (M, >= 6) float32 rows x y z [r g b],
+        host or device.  Points fall into voxels of edge `voxel`; occupied voxels that touch (connectivity 6: by a face, 26:
+        also by an edge or a corner) and, with colour_tol, whose mean colours differ by at most colour_tol in every channel
+        are joined; a connected component with at least min_points points is a segment: a scene_grow.GrownSegments whose
+        .segments goes to pool_segments as it is (scene_grow.py; INTEGRATION.md, "Building segments").  Needs no fit and no
+        model."""
+        from . import scene_grow
+        return scene_grow.build_segments(scan, voxel, colour_tol, connectivity, min_points)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

@@ -992,6 +992,79 @@ def scene_seg_spread(min_members, segment_index, seg_members, seg_fields, in_fie
     return scores, labels, set_labels, set_of, margin, pooled
 
 
+# ---- build_segments: segments grown from the scan (scene_grow.py)
+SCENE_GROW_REC = 16    # words of the record in front of the workspace
+SCENE_GROW_AXIS = 1024  # GR_AXIS_MAX of csrc/scene.hip: voxels per axis
+# the record's words (include/r3d.h, "build_segments")
+GROW_R_MIN, GROW_R_MAX, GROW_R_NVALID, GROW_R_V, GROW_R_NCOMP, GROW_R_S, GROW_R_NDROPPED, GROW_R_ERROR = 0, 3, 6, 7, 8, 9, 10, 11
+
+
+def scene_grow_workspace(M, device):
+    """-> ws, int32 of r3d_scene_grow_ws_words(M) words: the one scratch of a build_segments call, its record in front."""
+    words = _lib.load().r3d_scene_grow_ws_words(M)
+    if words < 0:
+        raise ValueError("build_segments: %d points (1 .. 2^27)" % M)
+    return torch.empty(words, device=device, dtype=torch.int32)
+
+
+def _grow_scan_ok(scan):
+    return scan.dim() == 2 and scan.dtype == torch.float32 and scan.is_cuda and scan.is_contiguous()
+
+
+def scene_grow_bounds(scan, ws):
+    """scan (M, ld) fp32 on the device -> words 0 .. 6 of the record in ws (zeros in the others), on the device."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    _lib.check(_lib.load().r3d_scene_grow_bounds(_p(scan), ld, M, _p(ws), ws.numel(), _st()))
+
+
+def scene_grow_sort(scan, origin, voxel, grid, ws):
+    """origin (x0, y0, z0) as read from the record, grid (nx, ny, nz): keys, the sort, the voxel heads -> word 7 (V)."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    x0, y0, z0 = (float(v) for v in origin)
+    _lib.check(_lib.load().r3d_scene_grow_sort(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid), _p(ws),
+                                               ws.numel(), _st()))
+
+
+def scene_grow_voxels(scan, grid, n_valid, n_voxels, colour, ws):
+    """After the read of V: the voxel table into ws -> (voxel_index (M,) int32, voxel_mean (V, 3) fp32 or None without
+    colour)."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    voxel_index = torch.empty(M, device=scan.device, dtype=torch.int32)
+    voxel_mean = torch.empty(int(n_voxels), 3, device=scan.device, dtype=torch.float32) if colour else None
+    _lib.check(_lib.load().r3d_scene_grow_voxels(_p(scan), ld, M, *(int(n) for n in grid), int(n_valid), int(n_voxels),
+                                                 _p(voxel_index), _p(voxel_mean), _p(ws), ws.numel(), _st()))
+    return voxel_index, voxel_mean
+
+
+def scene_grow_union(M, grid, n_voxels, connectivity, voxel_mean, colour_tol, ws):
+    """The union-find over the voxel graph, in ws; voxel_mean None: adjacency alone."""
+    assert _seg_ws_ok(ws)
+    assert voxel_mean is None or (tuple(voxel_mean.shape) == (int(n_voxels), 3) and voxel_mean.dtype == torch.float32
+                                  and voxel_mean.is_contiguous() and voxel_mean.is_cuda and colour_tol is not None)
+    _lib.check(_lib.load().r3d_scene_grow_union(M, *(int(n) for n in grid), int(n_voxels), int(connectivity), _p(voxel_mean),
+                                                0.0 if voxel_mean is None else float(colour_tol), _p(ws), ws.numel(), _st()))
+
+
+def scene_grow_components(M, n_voxels, min_points, ws):
+    """Roots, points per root, kept roots and their scan, in ws -> words 8 (components), 9 (S) and 11 (error)."""
+    assert _seg_ws_ok(ws)
+    _lib.check(_lib.load().r3d_scene_grow_components(M, int(n_voxels), int(min(min_points, 2 ** 31 - 1)), _p(ws), ws.numel(), _st()))
+
+
+def scene_grow_ids(voxel_index, n_voxels, n_segments, ws):
+    """After the read of S -> (segments (M,) int32, segment_points (S,) int32); word 10 (points of dropped components)."""
+    assert _seg_ws_ok(ws) and voxel_index.dtype == torch.int32 and voxel_index.is_contiguous() and voxel_index.is_cuda
+    M, S = voxel_index.numel(), int(n_segments)
+    segments = torch.empty(M, device=voxel_index.device, dtype=torch.int32)
+    segment_points = torch.empty(S, device=voxel_index.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_grow_ids(M, int(n_voxels), S, _p(voxel_index), _p(segments),
+                                              _p(segment_points) if S else None, _p(ws), ws.numel(), _st()))
+    return segments, segment_points
+
+
 # ---------------------------------------------------------------------------------------------- cutting episodes (block_pool.py)
 def _episode_cut_args(points, labels, offsets, desc, classes, S, Q, N, out, mask, gt_mask, query_y, gt_query_y, slot_map):
     E, n_way = classes.shape

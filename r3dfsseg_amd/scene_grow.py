@@ -1,0 +1,135 @@
+"""Segments grown from the scan itself: the partition that scene_segments.pool_segments takes, built on the device.
+
+pool_segments needs a partition of the scan's points, and the reference only ever reads one that an offline script wrote
+(dataloaders/loader.py:339-349).  build_segments makes one from a raw `x y z [r g b]` scan by the simplest useful criterion,
+adjacency and colour: points fall into voxels, occupied voxels that touch -- and, with colour_tol, whose mean colours agree
+-- are joined, the connected components are the segments.  The behaviour is defined here ("Building
+segments", G1-G7; tests/scene_grow_ref.py restates it in numpy).  Like the rest of the scene path it draws no random number
+and adds no float by an atomic; the union-find runs on integer atomics, and the component a voxel ends in depends on the
+graph alone, so the same scan gives the same bits.
+
+  1. valid points, their xyz extent                                               r3d_scene_grow_bounds      host read 1 of 4
+  2. voxel keys, stable sort of (key, scan index), voxel heads and their scan     r3d_scene_grow_sort        host read 2 of 4
+  3. the voxel table in ascending key order, the voxel of every point, mean
+     colours in the summation order of pool_segments                              r3d_scene_grow_voxels
+  4. every voxel united with the occupied neighbours in front of it               r3d_scene_grow_union
+  5. roots, points per root, the roots with at least min_points points            r3d_scene_grow_components  host read 3 of 4
+  6. kept components numbered by ascending root, spread to the points             r3d_scene_grow_ids         host read 4 of 4
+
+This module holds the host logic; the kernels are in csrc/scene.hip, beside the sort they use."""
+import numpy as np
+import torch
+
+from . import ops, scene
+
+MAX_AXIS = ops.SCENE_GROW_AXIS
+AXES = "xyz"
+
+
+class GrownSegments:
+    """What build_segments returns.  On the device: segments (M,) int32, 0 .. S - 1, or -1 for an invalid point or a point
+    of a dropped component; segment_points (S,) int32; voxel_index (M,) int32, the row of the point's voxel in the voxel
+    table (ascending key order), -1 for an invalid point; voxel_means (V, 3) fp32, the mean colour of every voxel, None
+    without colour_tol.  Host ints: n_segments (S), n_voxels, n_components (before min_points), n_dropped_points, n_invalid;
+    grid (nx, ny, nz), (0, 0, 0) without a valid point."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
+    """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
+    if isinstance(scan, np.ndarray):
+        scan = torch.from_numpy(scan)
+    if not isinstance(scan, torch.Tensor) or scan.dim() != 2 or scan.shape[0] < 1 or not (scan.shape[1] == 3 or scan.shape[1] >= 6):
+        raise ValueError("build_segments: scan must be (M, 3) rows `x y z` or (M, >= 6) rows `x y z r g b ...`, got %s" % (
+            tuple(scan.shape) if isinstance(scan, torch.Tensor) else type(scan).__name__,))
+    if scan.dtype != torch.float32:
+        raise ValueError("build_segments: scan must be float32, got %s" % scan.dtype)
+    if scan.shape[0] > scene.MAX_POINTS:
+        raise ValueError("build_segments: %d points (at most 2^27)" % scan.shape[0])
+    with np.errstate(over="ignore", under="ignore"):
+        v32 = np.float32(voxel) if _is_real(voxel) else np.float32(np.nan)
+        t32 = np.float32(colour_tol) if _is_real(colour_tol) else np.float32(np.nan)
+    if not (_is_real(voxel) and np.isfinite(voxel) and voxel > 0 and np.isfinite(v32) and v32 > 0):
+        raise ValueError("build_segments: voxel %r must be a finite float > 0 (in float32 too)" % (voxel,))
+    if not scene._is_int(connectivity) or int(connectivity) not in (6, 26):
+        raise ValueError("build_segments: connectivity %r must be 6 or 26" % (connectivity,))
+    if not scene._is_int(min_points) or min_points < 1:
+        raise ValueError("build_segments: min_points %r must be an integer >= 1" % (min_points,))
+    if colour_tol is not None:
+        if not (_is_real(colour_tol) and np.isfinite(colour_tol) and colour_tol >= 0 and np.isfinite(t32)):
+            raise ValueError("build_segments: colour_tol %r must be None or a finite float >= 0" % (colour_tol,))
+        if scan.shape[1] < 6:
+            raise ValueError("build_segments: colour_tol %r given, but a scan of %d columns has no colour (x y z r g b)"
+                             % (colour_tol, scan.shape[1]))
+    return scan, v32
+
+
+def grid_of(lo, hi, voxel):
+    """lo, hi (3,) float32 minima and maxima of the valid points -> (nx, ny, nz) by G2: the keys kernel's arithmetic at the
+    maximum, plus one.  Raises ValueError, naming the axis, when one of them exceeds 1024."""
+    grid = tuple(scene.n_cells_along(lo[a], hi[a], voxel) for a in range(3))
+    for a, n in enumerate(grid):
+        if n > MAX_AXIS:
+            extent = float(np.float32(hi[a]) - np.float32(lo[a]))
+            raise ValueError("build_segments: %d voxels of %g along %s (at most %d per axis); the extent %g fits with any voxel "
+                             "above %.9g" % (n, float(voxel), AXES[a], MAX_AXIS, extent, extent / MAX_AXIS))
+    return grid
+
+
+def read_record(ws):
+    """The record in front of the workspace as host ints: a host read (the call has at most four)."""
+    return ws[:ops.SCENE_GROW_REC].tolist()
+
+
+def _raise_on_error(rec):
+    if rec[ops.GROW_R_ERROR]:
+        raise RuntimeError("build_segments: the union-find ran out of its bounded loops (error word %d: bit 0 a find, bit 1 a "
+                           "unite): its table is corrupted, no result" % rec[ops.GROW_R_ERROR])
+
+
+def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
+    """scan (M, 3) or (M, >= 6) float32 rows x y z [r g b ...], host or device, M <= 2^27 -> GrownSegments.  voxel: the edge
+    of a voxel, at most 1024 of them along an axis; connectivity 6 (faces) or 26 (faces, edges, corners); colour_tol: None,
+    or the largest difference of two neighbouring voxels' mean colours, per channel, that still joins them; min_points: a
+    component with fewer points is dropped, its points get -1.  See the module text and INTEGRATION.md, "Building segments"."""
+    scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points)
+    if not torch.cuda.is_available():
+        raise RuntimeError("build_segments: no device (there is no CPU path)")
+    dev = scan.device if scan.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if scan.shape[1] > 64:  # the kernels take rows of up to 64 floats; only the first six are ever read
+        scan = scan[:, :6]
+    scan = scan.to(dev).contiguous()
+    M = scan.shape[0]
+    ws = ops.scene_grow_workspace(M, dev)
+    ops.scene_grow_bounds(scan, ws)
+    rec = read_record(ws)  # host read 1 of 4
+    n_valid = rec[ops.GROW_R_NVALID]
+    if n_valid == 0:  # G1: nothing else is launched
+        none = torch.full((M,), -1, device=dev, dtype=torch.int32)
+        means = None if colour_tol is None else torch.empty(0, 3, device=dev, dtype=torch.float32)
+        return GrownSegments(segments=none, segment_points=torch.empty(0, device=dev, dtype=torch.int32), voxel_index=none.clone(),
+                             voxel_means=means, n_segments=0, n_voxels=0, n_components=0, n_dropped_points=0, n_invalid=M,
+                             grid=(0, 0, 0))
+    ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
+    lo, hi = ext[:3], ext[3:]
+    grid = grid_of(lo, hi, voxel)
+    ops.scene_grow_sort(scan, lo, voxel, grid, ws)
+    V = read_record(ws)[ops.GROW_R_V]  # host read 2 of 4
+    voxel_index, voxel_means = ops.scene_grow_voxels(scan, grid, n_valid, V, colour_tol is not None, ws)
+    ops.scene_grow_union(M, grid, V, connectivity, voxel_means, colour_tol, ws)
+    ops.scene_grow_components(M, V, min_points, ws)
+    rec = read_record(ws)  # host read 3 of 4: the tables' sizes
+    _raise_on_error(rec)
+    n_components, S = rec[ops.GROW_R_NCOMP], rec[ops.GROW_R_S]
+    segments, segment_points = ops.scene_grow_ids(voxel_index, V, S, ws)
+    rec = read_record(ws)  # host read 4 of 4, after everything is queued
+    _raise_on_error(rec)
+    return GrownSegments(segments=segments, segment_points=segment_points, voxel_index=voxel_index, voxel_means=voxel_means,
+                         n_segments=S, n_voxels=V, n_components=n_components, n_dropped_points=rec[ops.GROW_R_NDROPPED],
+                         n_invalid=M - n_valid, grid=grid)
