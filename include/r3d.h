@@ -775,7 +775,36 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  *   r3d_scene_grow_ids         n_segments: word 9 as read.  Kept components are numbered 0 .. S - 1 by
  *                              ascending root; segments (M,) int32: that number, -1 for an invalid point
  *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          word 10
- * No float atomics: the component of a voxel depends on the joined pairs alone, so the same scan gives the same bits. */
+ * No float atomics: the component of a voxel depends on the joined pairs alone, so the same scan gives the same bits.
+ *
+ * With normal_tol (G3c, G3n and the normal test of G4) two launches go between voxels and the union, and the union is
+ * r3d_scene_grow_union_normals; without it none of the three is called.  Every operation below is fp32 and rounded on its
+ * own (__fadd_rn, __fsub_rn, __fmul_rn, __fdiv_rn; nothing is contracted).  The three tables are the caller's, the
+ * workspace and its size are as above.
+ *   r3d_scene_grow_centroids   x0 y0 z0, voxel, the grid: those of the sort.  voxel_centroid (V, 3) fp32: per voxel the
+ *                              mean of u_a = (v_a - v0_a) - (float)i_a * voxel over its points, i decoded from the
+ *                              voxel's key (the offset inside the voxel: second moments do not cancel against the
+ *                              room's extent), summed as voxel_mean: ascending scan index in tiles of 256, part = the
+ *                              first, += the next, the parts in tile order, one division by (float)count.
+ *   r3d_scene_grow_normals     one thread per voxel v and the offsets o = 0 .. 26 = (dz, dy, dx) in lexicographic
+ *                              order over -1, 0, 1 (13: v itself), whatever the connectivity.  A neighbour is
+ *                              occupied when its coordinates lie in the grid and its key is in the table: per (dz,
+ *                              dy) one binary search for the first x-neighbour inside the grid, the next rows of the
+ *                              table checked by key.  voxel_support (V,) int32: k, the occupied offsets, 1 .. 27.
+ *                              q_o[a] = (float)d_a * voxel + centroid[b_o][a]; m = (q_first + q_next + ...) /
+ *                              (float)k by ascending o; e_o = q_o - m; C = sum_o e_o e_o^T, entries 00 01 02 11 12
+ *                              22, each the rounded products added by ascending o, the first starts the sum.
+ *                              voxel_normal (V, 3) fp32: three NaNs when k < 4, an entry of C is not finite or s =
+ *                              max(C00, C11, C22) is not > 0.  Else B = C / s, t = (B00 + B11) + B22, A = t I - B
+ *                              (off-diagonal -Bij), then eight times N = A A with every entry (x y + x' y') + x'' y''
+ *                              in the index order of the product, A = N / max(N00, N11, N22); the row of A with the
+ *                              largest diagonal entry (the lowest on a tie): not of unit length, that entry is 1.
+ *   r3d_scene_grow_union_normals  r3d_scene_grow_union (same kernel, same arguments, voxel_mean may be NULL) where a
+ *                              pair a, b is joined only when also dot * dot >= (cos2 * la) * lb, dot = (na0 nb0 +
+ *                              na1 nb1) + na2 nb2, la and lb the same of a row with itself; 0 <= cos2 <= 1.  No
+ *                              square root, no normalisation, the sign of a row does not matter; a NaN makes the
+ *                              comparison false, so a voxel without a normal joins nothing; a row of zeros reads
+ *                              0 >= 0 and joins (r3d_scene_grow_normals writes none). */
 long r3d_scene_grow_ws_words(long M);
 int r3d_scene_grow_bounds(const float* scan, int ld, long M, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny, int nz,
@@ -784,6 +813,13 @@ int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, int ny, int
                           int32_t* voxel_index, float* voxel_mean, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_grow_union(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
                          float colour_tol, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_centroids(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny,
+                             int nz, long n_voxels, float* voxel_centroid, const int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_normals(long M, int nx, int ny, int nz, long n_voxels, float voxel, const float* voxel_centroid,
+                           float* voxel_normal, int32_t* voxel_support, const int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_union_normals(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                                 float colour_tol, const float* voxel_normal, float cos2, int32_t* ws, long ws_words,
+                                 void* stream);
 int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
                        int32_t* segment_points, int32_t* ws, long ws_words, void* stream);

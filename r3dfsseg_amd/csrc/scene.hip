@@ -1866,15 +1866,19 @@ extern "C" int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segme
 
 // ------------------------------------------------------------------------------------------------ segments grown on the device
 // build_segments ("Building segments", G1-G7): the partition that pool_segments takes, grown from the scan
-// itself.  Points fall into voxels, occupied voxels that touch (and, with a tolerance, whose mean colours agree) are joined,
-// the connected components are the segments.
+// itself.  Points fall into voxels, occupied voxels that touch (and, with a tolerance, whose mean colours agree; with
+// normal_tol, whose normals agree) are joined, the connected components are the segments.
 //   bounds      valid points, their xyz extent                                    -> words 0 .. 6 of the record (read 1)
 //   sort        voxel keys, the stable radix sort above on (key, scan index), voxel heads as flags, their scan
 //                                                                                 -> V (read 2)
 //   voxels      the voxel table in ascending key order, the voxel of every point, the mean colour of a voxel (the sums of
 //               the segment pool: tiles of 256 ranks, one addition at a time, tiles in order, one division)
+//   centroids   with normal_tol: the mean offset of a voxel's points inside the voxel, by the loop of the mean colours
+//   normals     with normal_tol: per voxel the second moments of the centroids of the occupied voxels among the 27 around
+//               it, (t I - B)^256 by eight squarings, the row of the largest diagonal entry; the support
 //   union       one thread per voxel and the forward half of its neighbourhood; a neighbour is found by its coordinates
-//               and a binary search of its key; joined pairs are united in parent[] by lock-free hooking
+//               and a binary search of its key; joined pairs are united in parent[] by lock-free hooking; with normal_tol
+//               (r3d_scene_grow_union_normals) the same kernel with the test on the squared cosine of two normals
 //   components  root[v] = find(v) in a launch of its own, points per root, kept roots as flags, their scan
 //                                                                                 -> components, S (read 3)
 //   ids         the kept components numbered in ascending root order, spread to the points   -> the counts (read 4)
@@ -2131,20 +2135,19 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_table_kernel(const 
   }
 }
 
-// One thread per voxel: its points in sorted order (ascending scan index: the sort is stable), columns 3 .. 5 summed as
-// the segment pool sums a segment whose rows all have one vote.
-__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_mean_kernel(const float* __restrict__ scan, int ld, int M, int V,
-                                                                         const int* __restrict__ order, const int* __restrict__ vstart,
-                                                                         float* __restrict__ mean) {
-  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
-  if (v >= V) return;
+// One thread per voxel: its points in sorted order (ascending scan index: the sort is stable), three values per point
+// (row(p, c): those of scan row p) summed as the segment pool sums a segment whose rows all have one vote.
+template <class Row>
+static __device__ __forceinline__ void gr_voxel_mean(int v, int M, const int* __restrict__ order, const int* __restrict__ vstart,
+                                                     float* __restrict__ mean, Row row) {
   const int a = sc_clamp(vstart[v], 0, M), b = sc_clamp(vstart[v + 1], a, M);
   float tot[3] = {0.0f, 0.0f, 0.0f};
   for (int t0 = a; t0 < b; t0 += SG_TILE) {
     const int t1 = t0 + SG_TILE < b ? t0 + SG_TILE : b;
     float part[3] = {0.0f, 0.0f, 0.0f};
     for (int i = t0; i < t1; ++i) {
-      const float* c = scan + (long)sc_clamp(order[i], 0, M - 1) * ld + 3;
+      float c[3];
+      row(sc_clamp(order[i], 0, M - 1), c);
 #pragma unroll
       for (int j = 0; j < 3; ++j) part[j] = i == t0 ? c[j] : __fadd_rn(part[j], c[j]);
     }
@@ -2153,6 +2156,19 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_mean_kernel(const f
   }
 #pragma unroll
   for (int j = 0; j < 3; ++j) mean[3L * v + j] = b > a ? __fdiv_rn(tot[j], (float)(b - a)) : 0.0f;
+}
+
+// the mean colour of a voxel (G3): columns 3 .. 5
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_mean_kernel(const float* __restrict__ scan, int ld, int M, int V,
+                                                                         const int* __restrict__ order, const int* __restrict__ vstart,
+                                                                         float* __restrict__ mean) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  gr_voxel_mean(v, M, order, vstart, mean, [&](int p, float* c) {
+    const float* r = scan + (long)p * ld + 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = r[j];
+  });
 }
 
 struct gr_view {
@@ -2189,6 +2205,179 @@ extern "C" int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, 
     hipLaunchKernelGGL(r3d_scene_grow_mean_kernel, dim3((int)((n_voxels + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st,
                        scan, ld, (int)M, (int)n_voxels, v.order, ws + v.L.vstart, voxel_mean);
   R3D_LAUNCH_CHECK("r3d_scene_grow_voxels");
+  return R3D_OK;
+}
+
+// ---- centroids (G3c) and normals (G3n): only with normal_tol
+// The centroid of a voxel: the mean of its points' offsets INSIDE the voxel, (v - v0) - (float)i * voxel with i decoded from
+// the voxel's key, summed as the mean colours are.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_centroid_kernel(const float* __restrict__ scan, int ld, int M, int V,
+                                                                             gr_grid g, const int* __restrict__ order,
+                                                                             const int* __restrict__ vstart,
+                                                                             const int* __restrict__ vkey, float* __restrict__ centroid) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int key = vkey[v];
+  const float v0[3] = {g.x0, g.y0, g.z0};
+  const float off[3] = {__fmul_rn((float)(key % g.nx), g.s), __fmul_rn((float)((key / g.nx) % g.ny), g.s),
+                        __fmul_rn((float)(key / (g.nx * g.ny)), g.s)};
+  gr_voxel_mean(v, M, order, vstart, centroid, [&](int p, float* c) {
+    const float* r = scan + (long)p * ld;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = __fsub_rn(__fsub_rn(r[j], v0[j]), off[j]);
+  });
+}
+
+extern "C" int r3d_scene_grow_centroids(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx,
+                                        int ny, int nz, long n_voxels, float* voxel_centroid, const int32_t* ws, long ws_words,
+                                        void* stream) {
+  R3D_REQUIRE(scan && voxel_centroid, "r3d_scene_grow_centroids: null pointer (scan %p, voxel_centroid %p)", (const void*)scan,
+              (void*)voxel_centroid);
+  SC_TRY(sc_check_ld("r3d_scene_grow_centroids", ld));
+  SC_TRY(gr_check("r3d_scene_grow_centroids", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
+              "r3d_scene_grow_centroids: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_centroids: %ld voxels of %ld points", n_voxels, M);
+  const gr_view v = gr_make_view(M, nx, ny, nz, ws);
+  const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
+  hipLaunchKernelGGL(r3d_scene_grow_centroid_kernel, dim3((int)((n_voxels + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, scan, ld, (int)M, (int)n_voxels, g, v.order, ws + v.L.vstart, ws + v.L.vkey,
+                     voxel_centroid);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_centroids");
+  return R3D_OK;
+}
+
+#define GR_MIN_SUPPORT 4  // occupied voxels of the 27 below which a voxel has no normal
+#define GR_SQUARINGS 8    // (t I - B)^(2^8)
+
+// q of the neighbour at offset o (dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1), whose centroid is c
+static __device__ __forceinline__ void gr_q(int o, float s, const float* __restrict__ c, float* q) {
+  q[0] = __fadd_rn(__fmul_rn((float)(o % 3 - 1), s), c[0]);
+  q[1] = __fadd_rn(__fmul_rn((float)((o / 3) % 3 - 1), s), c[1]);
+  q[2] = __fadd_rn(__fmul_rn((float)(o / 9 - 1), s), c[2]);
+}
+
+// One thread per voxel.  The three x-neighbours of one (dz, dy) row have consecutive keys: one binary search finds the
+// first candidate row of the table, the next two are checked by key, and an x outside the grid is never looked up, so a
+// key that belongs to the neighbouring row of the grid is no neighbour.  The 27 rows stay in registers (every loop over
+// them is unrolled, no index is a run-time value); the centroids are gathered once for the mean and once more for the
+// second moments.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_normals_kernel(int V, int nx, int ny, int nz, float s,
+                                                                            const int* __restrict__ vkey,
+                                                                            const float* __restrict__ centroid,
+                                                                            float* __restrict__ normal, int* __restrict__ support) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int key = vkey[v];
+  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
+  int nb[27];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int jy = iy + r % 3 - 1, jz = iz + r / 3 - 1;
+    nb[3 * r] = nb[3 * r + 1] = nb[3 * r + 2] = -1;
+    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    const int base = (jz * ny + jy) * nx;
+    const int first = base + (ix > 0 ? ix - 1 : 0);
+    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
+    if (r == 4) {
+      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
+    } else {
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int jx = ix + d - 1;
+      if (jx < 0 || jx >= nx) continue;
+      if (lo < V && vkey[lo] == base + jx) {
+        nb[3 * r + d] = lo;
+        ++lo;
+        ++k;
+      }
+    }
+  }
+  float m[3] = {0.0f, 0.0f, 0.0f};
+  bool first = true;
+#pragma unroll
+  for (int o = 0; o < 27; ++o) {
+    float q[3];
+    gr_q(o, s, centroid + 3L * (nb[o] < 0 ? v : nb[o]), q);
+    if (nb[o] >= 0) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) m[a] = first ? q[a] : __fadd_rn(m[a], q[a]);
+      first = false;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) m[a] = __fdiv_rn(m[a], (float)k);
+  float C[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // 00 01 02 11 12 22
+  first = true;
+#pragma unroll
+  for (int o = 0; o < 27; ++o) {
+    float q[3];
+    gr_q(o, s, centroid + 3L * (nb[o] < 0 ? v : nb[o]), q);
+    if (nb[o] >= 0) {
+      const float e0 = __fsub_rn(q[0], m[0]), e1 = __fsub_rn(q[1], m[1]), e2 = __fsub_rn(q[2], m[2]);
+      const float p[6] = {__fmul_rn(e0, e0), __fmul_rn(e0, e1), __fmul_rn(e0, e2), __fmul_rn(e1, e1), __fmul_rn(e1, e2),
+                          __fmul_rn(e2, e2)};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) C[j] = first ? p[j] : __fadd_rn(C[j], p[j]);
+      first = false;
+    }
+  }
+  support[v] = k;
+  bool finite = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) finite = finite && fabsf(C[j]) < INFINITY;
+  const float top = fmaxf(fmaxf(C[0], C[3]), C[5]);
+  float* out = normal + 3L * v;
+  if (k < GR_MIN_SUPPORT || !finite || !(top > 0.0f)) {
+    out[0] = out[1] = out[2] = __int_as_float(0x7fc00000);
+    return;
+  }
+  float A[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) A[j] = __fdiv_rn(C[j], top);  // B
+  const float t = __fadd_rn(__fadd_rn(A[0], A[3]), A[5]);
+  A[0] = __fsub_rn(t, A[0]);
+  A[1] = -A[1];
+  A[2] = -A[2];
+  A[3] = __fsub_rn(t, A[3]);
+  A[4] = -A[4];
+  A[5] = __fsub_rn(t, A[5]);
+#define GR_DOT3(x0, y0, x1, y1, x2, y2) __fadd_rn(__fadd_rn(__fmul_rn(x0, y0), __fmul_rn(x1, y1)), __fmul_rn(x2, y2))
+  for (int it = 0; it < GR_SQUARINGS; ++it) {
+    const float N[6] = {GR_DOT3(A[0], A[0], A[1], A[1], A[2], A[2]), GR_DOT3(A[0], A[1], A[1], A[3], A[2], A[4]),
+                        GR_DOT3(A[0], A[2], A[1], A[4], A[2], A[5]), GR_DOT3(A[1], A[1], A[3], A[3], A[4], A[4]),
+                        GR_DOT3(A[1], A[2], A[3], A[4], A[4], A[5]), GR_DOT3(A[2], A[2], A[4], A[4], A[5], A[5])};
+    const float mx = fmaxf(fmaxf(N[0], N[3]), N[5]);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) A[j] = __fdiv_rn(N[j], mx);
+  }
+  // the row of the largest diagonal entry, the lowest on a tie
+  const int j = A[3] > A[0] ? (A[5] > A[3] ? 2 : 1) : (A[5] > A[0] ? 2 : 0);
+  out[0] = j == 0 ? A[0] : (j == 1 ? A[1] : A[2]);
+  out[1] = j == 0 ? A[1] : (j == 1 ? A[3] : A[4]);
+  out[2] = j == 0 ? A[2] : (j == 1 ? A[4] : A[5]);
+}
+
+extern "C" int r3d_scene_grow_normals(long M, int nx, int ny, int nz, long n_voxels, float voxel, const float* voxel_centroid,
+                                      float* voxel_normal, int32_t* voxel_support, const int32_t* ws, long ws_words,
+                                      void* stream) {
+  R3D_REQUIRE(voxel_centroid && voxel_normal && voxel_support,
+              "r3d_scene_grow_normals: null pointer (voxel_centroid %p, voxel_normal %p, voxel_support %p)",
+              (const void*)voxel_centroid, (void*)voxel_normal, (void*)voxel_support);
+  SC_TRY(gr_check("r3d_scene_grow_normals", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(voxel > 0.0f && voxel < INFINITY, "r3d_scene_grow_normals: voxel size %g", (double)voxel);
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_normals: %ld voxels of %ld points", n_voxels, M);
+  const gr_layout L = gr_make_layout(M);
+  hipLaunchKernelGGL(r3d_scene_grow_normals_kernel, dim3((int)((n_voxels + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (int)n_voxels, nx, ny, nz, voxel, ws + L.vkey, voxel_centroid, voxel_normal,
+                     voxel_support);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_normals");
   return R3D_OK;
 }
 
@@ -2242,12 +2431,26 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_init_kernel(int V, 
 
 // One thread per voxel a, the forward half of the neighbourhood (the offsets whose key is larger): 3 of 6, 13 of 26.  The
 // neighbour's coordinates are checked against the grid, its key is looked up by binary search among the rows behind a.
+// NORMALS (r3d_scene_grow_union_normals): a pair is joined only when dot^2 >= (cos2 la) lb as well, la and lb the squared
+// lengths of the two normal rows; a NaN in either row makes the comparison false.
+static __device__ __forceinline__ float gr_dot3(const float* x, const float* y) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
+}
+
+template <bool NORMALS>
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_union_kernel(int V, int nx, int ny, int nz, int conn,
                                                                           const int* __restrict__ vkey, int use_colour, float tol,
-                                                                          const float* __restrict__ mean, int* __restrict__ parent,
-                                                                          int* __restrict__ err) {
+                                                                          const float* __restrict__ mean,
+                                                                          const float* __restrict__ normal, float cos2,
+                                                                          int* __restrict__ parent, int* __restrict__ err) {
   const int a = blockIdx.x * SC_THREADS + threadIdx.x;
   if (a >= V) return;
+  float na[3] = {0.0f, 0.0f, 0.0f}, la = 0.0f;
+  if (NORMALS) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) na[j] = normal[3L * a + j];
+    la = __fmul_rn(cos2, gr_dot3(na, na));
+  }
   const int key = vkey[a];
   const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
   float ma[3] = {0.0f, 0.0f, 0.0f};
@@ -2273,26 +2476,52 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_union_kernel(int V,
       for (int j = 0; j < 3; ++j) alike = alike && fabsf(__fsub_rn(ma[j], mean[3L * lo + j])) <= tol;  // a NaN joins nothing
       if (!alike) continue;
     }
+    if (NORMALS) {
+      const float nb[3] = {normal[3L * lo], normal[3L * lo + 1], normal[3L * lo + 2]};
+      const float dot = gr_dot3(na, nb);
+      if (!(__fmul_rn(dot, dot) >= __fmul_rn(la, gr_dot3(nb, nb)))) continue;
+    }
     gr_unite(parent, a, lo, V, err);
   }
 }
 
-extern "C" int r3d_scene_grow_union(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
-                                    float colour_tol, int32_t* ws, long ws_words, void* stream) {
+static int gr_union(const char* name, long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                    float colour_tol, const float* voxel_normal, float cos2, int32_t* ws, long ws_words, void* stream) {
   const bool colour = voxel_mean != nullptr;
-  SC_TRY(gr_check("r3d_scene_grow_union", M, nx, ny, nz, ws, ws_words));
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_union: %ld voxels of %ld points", n_voxels, M);
-  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "r3d_scene_grow_union: connectivity %d (6 or 26)", connectivity);
-  R3D_REQUIRE(!colour || (colour_tol >= 0.0f && colour_tol < INFINITY), "r3d_scene_grow_union: colour_tol %g (finite, >= 0)",
+  SC_TRY(gr_check(name, M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "%s: %ld voxels of %ld points", name, n_voxels, M);
+  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "%s: connectivity %d (6 or 26)", name, connectivity);
+  R3D_REQUIRE(!colour || (colour_tol >= 0.0f && colour_tol < INFINITY), "%s: colour_tol %g (finite, >= 0)", name,
               (double)colour_tol);
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int V = (int)n_voxels, gv = (V + SC_THREADS - 1) / SC_THREADS;
   hipLaunchKernelGGL(r3d_scene_grow_init_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.parent);
-  hipLaunchKernelGGL(r3d_scene_grow_union_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity, ws + L.vkey,
-                     colour ? 1 : 0, colour_tol, voxel_mean, ws + L.parent, ws + L.rec + GR_R_ERROR);
-  R3D_LAUNCH_CHECK("r3d_scene_grow_union");
+  if (voxel_normal)
+    hipLaunchKernelGGL(r3d_scene_grow_union_kernel<true>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
+                       ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
+                       ws + L.rec + GR_R_ERROR);
+  else
+    hipLaunchKernelGGL(r3d_scene_grow_union_kernel<false>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
+                       ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
+                       ws + L.rec + GR_R_ERROR);
+  R3D_LAUNCH_CHECK(name);
   return R3D_OK;
+}
+
+extern "C" int r3d_scene_grow_union(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                                    float colour_tol, int32_t* ws, long ws_words, void* stream) {
+  return gr_union("r3d_scene_grow_union", M, nx, ny, nz, n_voxels, connectivity, voxel_mean, colour_tol, nullptr, 0.0f, ws,
+                  ws_words, stream);
+}
+
+extern "C" int r3d_scene_grow_union_normals(long M, int nx, int ny, int nz, long n_voxels, int connectivity,
+                                            const float* voxel_mean, float colour_tol, const float* voxel_normal, float cos2,
+                                            int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(voxel_normal, "r3d_scene_grow_union_normals: null pointer (voxel_normal)");
+  R3D_REQUIRE(cos2 >= 0.0f && cos2 <= 1.0f, "r3d_scene_grow_union_normals: cos2 %g (0 .. 1)", (double)cos2);
+  return gr_union("r3d_scene_grow_union_normals", M, nx, ny, nz, n_voxels, connectivity, voxel_mean, colour_tol, voxel_normal,
+                  cos2, ws, ws_words, stream);
 }
 
 // ---- components (G5, G6): root[v] = find(v) in a launch of its own, into another array.  No hook happens here, so the

@@ -266,6 +266,15 @@ class FittedLearner(object):
         from . import scene_grow
         return scene_grow.build_segments(scan, voxel, colour_tol, connectivity, min_points)
 
+    def grow_segments(self, scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None):
+        """build_segments with one more criterion, normal_tol: None, or the largest angle in degrees (0 .. 90) between the
+        surface normals of two neighbouring voxels that still joins them -- so a floor and a wall, which touch, fall apart.
+        A voxel's normal comes from the occupied voxels among the 27 around it; a voxel with fewer than 4 of them has none
+        and stays alone.  Combines with colour_tol (both must hold) and needs no colour columns (scene_grow.py;
+        INTEGRATION.md, "Building segments", G3c, G3n, G4)."""
+        from . import scene_grow
+        return scene_grow.grow_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

@@ -1048,6 +1048,43 @@ def scene_grow_union(M, grid, n_voxels, connectivity, voxel_mean, colour_tol, ws
                                                 0.0 if voxel_mean is None else float(colour_tol), _p(ws), ws.numel(), _st()))
 
 
+def _grow_table_ok(t, n_voxels):
+    return (tuple(t.shape) == (int(n_voxels), 3) and t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda)
+
+
+def scene_grow_centroids(scan, origin, voxel, grid, n_voxels, ws):
+    """With normal_tol, after scene_grow_voxels: origin, voxel, grid as given to scene_grow_sort -> voxel_centroid (V, 3) fp32,
+    the mean offset of a voxel's points inside the voxel (G3c)."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    x0, y0, z0 = (float(v) for v in origin)
+    centroid = torch.empty(int(n_voxels), 3, device=scan.device, dtype=torch.float32)
+    _lib.check(_lib.load().r3d_scene_grow_centroids(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid),
+                                                    int(n_voxels), _p(centroid), _p(ws), ws.numel(), _st()))
+    return centroid
+
+
+def scene_grow_normals(M, grid, n_voxels, voxel, voxel_centroid, ws):
+    """-> (voxel_normal (V, 3) fp32, a NaN row where a voxel has no normal, voxel_support (V,) int32: the occupied voxels among
+    the 27 around it) by G3n."""
+    assert _seg_ws_ok(ws) and _grow_table_ok(voxel_centroid, n_voxels)
+    normal = torch.empty_like(voxel_centroid)
+    support = torch.empty(int(n_voxels), device=voxel_centroid.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_grow_normals(M, *(int(n) for n in grid), int(n_voxels), float(voxel), _p(voxel_centroid),
+                                                  _p(normal), _p(support), _p(ws), ws.numel(), _st()))
+    return normal, support
+
+
+def scene_grow_union_normals(M, grid, n_voxels, connectivity, voxel_mean, colour_tol, voxel_normal, cos2, ws):
+    """scene_grow_union with the normal test of G4 as well: voxel_normal (V, 3) fp32, cos2 the float32 squared cosine of the
+    tolerance; voxel_mean None: no colour test."""
+    assert _seg_ws_ok(ws) and _grow_table_ok(voxel_normal, n_voxels)
+    assert voxel_mean is None or (_grow_table_ok(voxel_mean, n_voxels) and colour_tol is not None)
+    _lib.check(_lib.load().r3d_scene_grow_union_normals(M, *(int(n) for n in grid), int(n_voxels), int(connectivity),
+                                                        _p(voxel_mean), 0.0 if voxel_mean is None else float(colour_tol),
+                                                        _p(voxel_normal), float(cos2), _p(ws), ws.numel(), _st()))
+
+
 def scene_grow_components(M, n_voxels, min_points, ws):
     """Roots, points per root, kept roots and their scan, in ws -> words 8 (components), 9 (S) and 11 (error)."""
     assert _seg_ws_ok(ws)

@@ -2,21 +2,30 @@
 
 pool_segments needs a partition of the scan's points, and the reference only ever reads one that an offline script wrote
 (dataloaders/loader.py:339-349).  build_segments makes one from a raw `x y z [r g b]` scan by the simplest useful criterion,
-adjacency and colour: points fall into voxels, occupied voxels that touch -- and, with colour_tol, whose mean colours agree
--- are joined, the connected components are the segments.  The behaviour is defined here ("Building
-segments", G1-G7; tests/scene_grow_ref.py restates it in numpy).  Like the rest of the scene path it draws no random number
-and adds no float by an atomic; the union-find runs on integer atomics, and the component a voxel ends in depends on the
-graph alone, so the same scan gives the same bits.
+adjacency, colour and surface normal: points fall into voxels, occupied voxels that touch -- and, with colour_tol, whose
+mean colours agree, and, with normal_tol, whose normals agree -- are joined, the connected components are the segments.
+Adjacency alone joins a floor to every wall and to what stands on it; normal_tol is plane-wise region growing: a voxel's
+normal comes from the centroids of the occupied voxels among the 27 around it, by a fixed sequence of fp32 operations (no
+eigen-solver), and two neighbours are joined only when the angle between their normals is at most normal_tol degrees.  The
+behaviour is defined here ("Building segments", G1-G7 with G3c and G3n; tests/scene_grow_ref.py and
+tests/scene_grow_normals_ref.py restate it in numpy).  Like the rest of the scene path it draws no random number and adds
+no float by an atomic; the union-find runs on integer atomics, and the component a voxel ends in depends on the graph
+alone, so the same scan gives the same bits.
 
   1. valid points, their xyz extent                                               r3d_scene_grow_bounds      host read 1 of 4
   2. voxel keys, stable sort of (key, scan index), voxel heads and their scan     r3d_scene_grow_sort        host read 2 of 4
   3. the voxel table in ascending key order, the voxel of every point, mean
      colours in the summation order of pool_segments                              r3d_scene_grow_voxels
-  4. every voxel united with the occupied neighbours in front of it               r3d_scene_grow_union
+  3c. with normal_tol: the centroid of every voxel, inside the voxel             r3d_scene_grow_centroids
+  3n. with normal_tol: the normal and the support of every voxel                  r3d_scene_grow_normals
+  4. every voxel united with the occupied neighbours in front of it               r3d_scene_grow_union, or with normal_tol
+                                                                                  r3d_scene_grow_union_normals
   5. roots, points per root, the roots with at least min_points points            r3d_scene_grow_components  host read 3 of 4
   6. kept components numbered by ascending root, spread to the points             r3d_scene_grow_ids         host read 4 of 4
 
 This module holds the host logic; the kernels are in csrc/scene.hip, beside the sort they use."""
+import math
+
 import numpy as np
 import torch
 
@@ -30,7 +39,9 @@ class GrownSegments:
     """What build_segments returns.  On the device: segments (M,) int32, 0 .. S - 1, or -1 for an invalid point or a point
     of a dropped component; segment_points (S,) int32; voxel_index (M,) int32, the row of the point's voxel in the voxel
     table (ascending key order), -1 for an invalid point; voxel_means (V, 3) fp32, the mean colour of every voxel, None
-    without colour_tol.  Host ints: n_segments (S), n_voxels, n_components (before min_points), n_dropped_points, n_invalid;
+    without colour_tol.  With normal_tol, else None: voxel_centroids (V, 3) fp32, the mean position of a voxel's points
+    measured from the voxel's lower corner; voxel_normals (V, 3) fp32, not of unit length, its largest component 1, a row of
+    NaNs where a voxel has no normal; voxel_support (V,) int32, the occupied voxels among the 27 around it.  Host ints: n_segments (S), n_voxels, n_components (before min_points), n_dropped_points, n_invalid;
     grid (nx, ny, nz), (0, 0, 0) without a valid point."""
 
     def __init__(self, **fields):
@@ -41,7 +52,12 @@ def _is_real(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
 
 
-def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
+def cos2_of(normal_tol):
+    """The threshold of the normal test (G4): float32(cos(radians(normal_tol)) ** 2), computed in float64, rounded once."""
+    return np.float32(math.cos(math.radians(float(normal_tol))) ** 2)
+
+
+def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None):
     """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
     if isinstance(scan, np.ndarray):
         scan = torch.from_numpy(scan)
@@ -67,6 +83,8 @@ def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
         if scan.shape[1] < 6:
             raise ValueError("build_segments: colour_tol %r given, but a scan of %d columns has no colour (x y z r g b)"
                              % (colour_tol, scan.shape[1]))
+    if normal_tol is not None and not (_is_real(normal_tol) and np.isfinite(normal_tol) and 0 <= normal_tol <= 90):
+        raise ValueError("grow_segments: normal_tol %r must be None or a finite real number of degrees in [0, 90]" % (normal_tol,))
     return scan, v32
 
 
@@ -94,11 +112,19 @@ def _raise_on_error(rec):
 
 
 def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
+    """grow_segments without normal_tol: adjacency and, with colour_tol, colour.  Its signature is kept as it was; the
+    normal criterion is a keyword of grow_segments."""
+    return grow_segments(scan, voxel, colour_tol, connectivity, min_points)
+
+
+def grow_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None):
     """scan (M, 3) or (M, >= 6) float32 rows x y z [r g b ...], host or device, M <= 2^27 -> GrownSegments.  voxel: the edge
     of a voxel, at most 1024 of them along an axis; connectivity 6 (faces) or 26 (faces, edges, corners); colour_tol: None,
     or the largest difference of two neighbouring voxels' mean colours, per channel, that still joins them; min_points: a
-    component with fewer points is dropped, its points get -1.  See the module text and INTEGRATION.md, "Building segments"."""
-    scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points)
+    component with fewer points is dropped, its points get -1; normal_tol: None, or the largest angle in degrees, 0 .. 90,
+    between the normals of two neighbouring voxels that still joins them (both must have a normal; with colour_tol both
+    tests must hold; needs no colour).  See the module text and INTEGRATION.md, "Building segments"."""
+    scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points, normal_tol)
     if not torch.cuda.is_available():
         raise RuntimeError("build_segments: no device (there is no CPU path)")
     dev = scan.device if scan.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -112,17 +138,25 @@ def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points
     n_valid = rec[ops.GROW_R_NVALID]
     if n_valid == 0:  # G1: nothing else is launched
         none = torch.full((M,), -1, device=dev, dtype=torch.int32)
-        means = None if colour_tol is None else torch.empty(0, 3, device=dev, dtype=torch.float32)
+        table = lambda on, *shape: torch.empty(0, *shape, device=dev, dtype=torch.float32) if on else None
         return GrownSegments(segments=none, segment_points=torch.empty(0, device=dev, dtype=torch.int32), voxel_index=none.clone(),
-                             voxel_means=means, n_segments=0, n_voxels=0, n_components=0, n_dropped_points=0, n_invalid=M,
-                             grid=(0, 0, 0))
+                             voxel_means=table(colour_tol is not None, 3), n_segments=0, n_voxels=0, n_components=0,
+                             n_dropped_points=0, n_invalid=M, grid=(0, 0, 0), voxel_centroids=table(normal_tol is not None, 3),
+                             voxel_normals=table(normal_tol is not None, 3),
+                             voxel_support=None if normal_tol is None else torch.empty(0, device=dev, dtype=torch.int32))
     ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
     lo, hi = ext[:3], ext[3:]
     grid = grid_of(lo, hi, voxel)
     ops.scene_grow_sort(scan, lo, voxel, grid, ws)
     V = read_record(ws)[ops.GROW_R_V]  # host read 2 of 4
     voxel_index, voxel_means = ops.scene_grow_voxels(scan, grid, n_valid, V, colour_tol is not None, ws)
-    ops.scene_grow_union(M, grid, V, connectivity, voxel_means, colour_tol, ws)
+    centroids = normals = support = None
+    if normal_tol is None:
+        ops.scene_grow_union(M, grid, V, connectivity, voxel_means, colour_tol, ws)
+    else:
+        centroids = ops.scene_grow_centroids(scan, lo, voxel, grid, V, ws)
+        normals, support = ops.scene_grow_normals(M, grid, V, voxel, centroids, ws)
+        ops.scene_grow_union_normals(M, grid, V, connectivity, voxel_means, colour_tol, normals, cos2_of(normal_tol), ws)
     ops.scene_grow_components(M, V, min_points, ws)
     rec = read_record(ws)  # host read 3 of 4: the tables' sizes
     _raise_on_error(rec)
@@ -132,4 +166,4 @@ def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points
     _raise_on_error(rec)
     return GrownSegments(segments=segments, segment_points=segment_points, voxel_index=voxel_index, voxel_means=voxel_means,
                          n_segments=S, n_voxels=V, n_components=n_components, n_dropped_points=rec[ops.GROW_R_NDROPPED],
-                         n_invalid=M - n_valid, grid=grid)
+                         n_invalid=M - n_valid, grid=grid, voxel_centroids=centroids, voxel_normals=normals, voxel_support=support)

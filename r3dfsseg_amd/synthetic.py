@@ -213,3 +213,37 @@ def make_scene(cfg, seed=0, extent=(8.0, 6.0, 3.0), n_points=100000, origin=(-12
     pts[:, :3] += np.asarray(origin, np.float32)
     pts[:, 3:6] = np.round(pts[:, 3:6] * 255.0)
     return torch.from_numpy(pts.astype(np.float32)), torch.from_numpy(labels)
+
+
+def make_room(seed=0, n_points=120000, extent=(4.0, 3.0, 2.5), n_boxes=3, noise=0.003, colour_noise=8.0,
+              origin=(-12.3, 40.7, 0.5)):
+    """A seeded room of SURFACES as a deployed scan: (scan (M, 6) fp32 rows `x y z r g b` with colours in 0..255, surface (M,)
+    int64, the surface a point was drawn on).  Surface 0 is the floor, 1 .. 4 the walls at x = 0, y = 0, x = extent[0] and
+    y = extent[1], then five per box (its top and its four sides; the boxes stand on the floor, apart from each other and
+    from the walls).  Every surface gets points in proportion to its area, uniform on it, displaced by Gaussian `noise`
+    (metres) on all three axes, and one base colour with Gaussian `colour_noise` per channel.  make_scene fills a volume
+    with uniform points and has no surface in it; this is the scan a segment grower is meant for."""
+    rs = np.random.RandomState(seed)
+    ex, ey, ez = (float(v) for v in extent)
+    # a rectangle: corner o, edges u and v
+    rects = [((0, 0, 0), (ex, 0, 0), (0, ey, 0)), ((0, 0, 0), (0, ey, 0), (0, 0, ez)), ((0, 0, 0), (ex, 0, 0), (0, 0, ez)),
+             ((ex, 0, 0), (0, ey, 0), (0, 0, ez)), ((0, ey, 0), (ex, 0, 0), (0, 0, ez))]
+    for b in range(int(n_boxes)):  # one box per strip of the floor along x, so that no two touch
+        w = ex / max(int(n_boxes), 1)
+        sx, sy, sz = rs.uniform(0.35, 0.6) * w, rs.uniform(0.2, 0.4) * ey, rs.uniform(0.2, 0.5) * ez
+        x0 = b * w + rs.uniform(0.15, 0.85) * (w - sx) * 0.9 + 0.05 * w
+        y0 = rs.uniform(0.15, 0.85) * (ey - sy)
+        rects += [((x0, y0, sz), (sx, 0, 0), (0, sy, 0)), ((x0, y0, 0), (sx, 0, 0), (0, 0, sz)),
+                  ((x0, y0 + sy, 0), (sx, 0, 0), (0, 0, sz)), ((x0, y0, 0), (0, sy, 0), (0, 0, sz)),
+                  ((x0 + sx, y0, 0), (0, sy, 0), (0, 0, sz))]
+    rects = np.asarray(rects, np.float64)
+    area = np.linalg.norm(np.cross(rects[:, 1], rects[:, 2]), axis=1)
+    surface = np.sort(rs.choice(len(rects), int(n_points), p=area / area.sum()))
+    ab = rs.uniform(0, 1, (len(surface), 2))
+    xyz = rects[surface, 0] + ab[:, :1] * rects[surface, 1] + ab[:, 1:] * rects[surface, 2]
+    xyz += rs.normal(0, noise, xyz.shape) if noise > 0 else 0.0
+    base = rs.uniform(40, 215, (len(rects), 3))
+    rgb = np.clip(np.round(base[surface] + rs.normal(0, colour_noise, xyz.shape)), 0, 255)
+    perm = rs.permutation(len(surface))
+    scan = np.concatenate([xyz + np.asarray(origin, np.float64), rgb], 1).astype(np.float32)[perm]
+    return torch.from_numpy(scan), torch.from_numpy(surface[perm].astype(np.int64))

@@ -3,16 +3,20 @@ calls it sits between and beside the numpy restatement on the CPU (the only base
 library).
 
     python tools/scene_grow_cost.py [--points 1000000] [--calls 7] [--voxel 0.05] [--colour-tol 64] [--baseline one]
+                                    [--scan scene|room] [--normal-tol DEGREES]
 
-scan: the seeded room of synthetic.make_scene, 8 m x 6 m x 3 m of uniform points with colours in 0 .. 255 -- about one point
-per occupied voxel at 0.05 m, so the voxel graph is as large as the scan allows.  Configurations: connectivity 6 and 26,
-without colour and with colour_tol; and both with colour_tol = 0, which joins next to nothing on this scan: the union span is then
-the neighbour searches alone, and what the other configurations take beyond it is the hooking.
+--scan scene (the default): the seeded room of synthetic.make_scene, 8 m x 6 m x 3 m of uniform points with colours in
+0 .. 255 -- about one point per occupied voxel at 0.05 m, so the voxel graph is as large as the scan allows.  --scan room:
+synthetic.make_room, the same extent as SURFACES (a floor, four walls, three boxes) with 3 mm of noise: fewer voxels with
+more points, the scan normal_tol is meant for.  Configurations: connectivity 6 and 26, without colour and with colour_tol;
+and both with colour_tol = 0, which joins next to nothing on the uniform scan: the union span is then the neighbour searches
+alone, and what the other configurations take beyond it is the hooking.  With --normal-tol the first four are run once
+more with that normal_tol, and their spans include the two launches it adds, centroids and normals.
 
 Per configuration, after a warm-up call: `calls` calls each timed with one HIP event pair (the call's four host reads lie
 inside it) and with the host clock, reported as median, minimum and maximum; then `calls` more with event pairs THIS TOOL
-puts around the ops wrappers -- bounds, sort (keys, radix sort, heads, scan), voxels (table and mean colours), union,
-flatten (roots, counts, kept flags, scan), ids -- and the host clock around the record reads (a read waits for what is
+puts around the ops wrappers -- bounds, sort (keys, radix sort, heads, scan), voxels (table and mean colours), centroids
+and normals (with normal_tol), union, flatten (roots, counts, kept flags, scan), ids -- and the host clock around the record reads (a read waits for what is
 queued in front of it, so it is at least that device time); the medians per span.  predict_scene (ProtoLearner, workload S)
 and pool_segments (on the grown segments) are timed the same way on the same scan.  --baseline one | all | none: the numpy
 restatement tests/scene_grow_ref.py on the host clock for the first configuration, or for all four, and the check that the
@@ -33,8 +37,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from r3dfsseg_amd import ops, scene_grow as G, scene_segments as SS, synthetic as S  # noqa: E402
 
-SPANS = {"scene_grow_bounds": "bounds", "scene_grow_sort": "sort", "scene_grow_voxels": "voxels", "scene_grow_union": "union",
-         "scene_grow_components": "flatten", "scene_grow_ids": "ids"}
+SPANS = {"scene_grow_bounds": "bounds", "scene_grow_sort": "sort", "scene_grow_voxels": "voxels",
+         "scene_grow_centroids": "centroids", "scene_grow_normals": "normals", "scene_grow_union": "union",
+         "scene_grow_union_normals": "union", "scene_grow_components": "flatten", "scene_grow_ids": "ids"}
 
 
 def stats(ms):
@@ -59,7 +64,7 @@ def timed_calls(fn, calls):
 
 def spans(fn, calls):
     """`calls` calls with event pairs around the ops wrappers and the host clock around the record reads -> medians."""
-    orig = {n: getattr(ops, n) for n in SPANS}
+    orig = {n: getattr(ops, n) for n in SPANS if hasattr(ops, n)}
     read = G.read_record
     runs, reads = [], []
 
@@ -82,8 +87,8 @@ def spans(fn, calls):
             this_reads.append((time.perf_counter() - t0) * 1e3)
             return out
         try:
-            for n, span in SPANS.items():
-                setattr(ops, n, wrap(span, orig[n], events))
+            for n, f in orig.items():
+                setattr(ops, n, wrap(SPANS[n], f, events))
             G.read_record = timed_read
             fn()
             torch.cuda.synchronize()
@@ -93,7 +98,7 @@ def spans(fn, calls):
             G.read_record = read
         runs.append({span: e0.elapsed_time(e1) for span, e0, e1 in events})
         reads.append(this_reads)
-    out = {span: stats([r[span] for r in runs]) for span in SPANS.values()}
+    out = {span: stats([r[span] for r in runs]) for span in dict.fromkeys(SPANS.values()) if span in runs[0]}
     out["host_reads_median"] = [round(float(np.median([r[i] for r in reads])), 4) for i in range(len(reads[0]))]
     return out
 
@@ -105,35 +110,53 @@ def main():
     ap.add_argument("--voxel", type=float, default=0.05)
     ap.add_argument("--colour-tol", type=float, default=64.0)
     ap.add_argument("--baseline", choices=["none", "one", "all"], default="one")
+    ap.add_argument("--scan", choices=["scene", "room"], default="scene")
+    ap.add_argument("--normal-tol", type=float, default=None)
     args = ap.parse_args()
     from r3dfsseg_amd.proto_learner import ProtoLearner
     cfg = S.workload_cfg("S")
-    scan_host = S.make_scene(cfg, seed=0, extent=(8.0, 6.0, 3.0), n_points=args.points)[0]
+    if args.scan == "room":
+        scan_host = S.make_room(seed=0, n_points=args.points, extent=(8.0, 6.0, 3.0))[0]
+    else:
+        scan_host = S.make_scene(cfg, seed=0, extent=(8.0, 6.0, 3.0), n_points=args.points)[0]
     scan = scan_host.cuda()
     learner = ProtoLearner(SimpleNamespace(**dict(cfg, model_checkpoint_path="synthetic")), mode="test")
     learner.fit(S.make_episode(cfg, seed=0, noise_ratio=0.2)[0][:2])
     predict = lambda: learner.predict_scene(scan, block_size=1.0)
-    out = {"points": args.points, "calls": args.calls, "voxel": args.voxel,
+    out = {"points": args.points, "calls": args.calls, "voxel": args.voxel, "scan": args.scan,
            "predict_scene": timed_calls(predict, min(args.calls, 3)), "runs": []}
     res = predict()
-    for n, (conn, tol) in enumerate([(6, None), (26, None), (6, args.colour_tol), (26, args.colour_tol), (6, 0.0), (26, 0.0)]):
-        grow = lambda: G.build_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn)
-        rec = {"connectivity": conn, "colour_tol": tol, "build_segments": timed_calls(grow, args.calls)}
+    configs = [(6, None, None), (26, None, None), (6, args.colour_tol, None), (26, args.colour_tol, None), (6, 0.0, None),
+               (26, 0.0, None)]
+    if args.normal_tol is not None:
+        configs += [(conn, tol, args.normal_tol) for conn, tol, _ in configs[:4]]
+    for n, (conn, tol, ntol) in enumerate(configs):
+        if ntol is None:  # (the call of a tree that has no normal_tol, too)
+            grow = lambda: G.build_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn)
+        else:
+            grow = lambda: G.grow_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn, normal_tol=ntol)
+        rec = {"connectivity": conn, "colour_tol": tol, "normal_tol": ntol, "build_segments": timed_calls(grow, args.calls)}
         rec["span_ms"] = spans(grow, args.calls)
         sg = grow()
         rec.update(n_voxels=sg.n_voxels, n_components=sg.n_components, n_segments=sg.n_segments, grid=list(sg.grid),
-                   largest_segment_points=int(sg.segment_points.max()))
+                   largest_segment_points=sorted(sg.segment_points.tolist(), reverse=True)[:6])
+        if ntol is not None:
+            rec["voxels_without_normal"] = int(torch.isnan(sg.voxel_normals[:, 0]).sum())
         rec["pool_segments"] = timed_calls(lambda: SS.pool_segments(res, sg.segments), args.calls)
-        if (args.baseline == "all" and n < 4) or (args.baseline == "one" and n == 0):
-            import scene_grow_ref
+        if (args.baseline == "all" and (n < 4 or ntol is not None)) or (args.baseline == "one" and n == 0):
             t0 = time.perf_counter()
-            want = scene_grow_ref.grow(scan_host.numpy(), args.voxel, tol, conn)
+            if ntol is None:
+                import scene_grow_ref
+                want = scene_grow_ref.grow(scan_host.numpy(), args.voxel, tol, conn)
+            else:
+                import scene_grow_normals_ref
+                want = scene_grow_normals_ref.grow(scan_host.numpy(), args.voxel, tol, conn, normal_tol=ntol)
             rec["numpy_restatement_host_s"] = round(time.perf_counter() - t0, 2)
             rec["equals_restatement"] = bool(np.array_equal(sg.segments.cpu().numpy(), want["segments"])
                                              and np.array_equal(sg.voxel_index.cpu().numpy(), want["voxel_index"])
                                              and sg.n_components == want["n_components"])
         out["runs"].append(rec)
-        print("connectivity %d, colour_tol %s: done" % (conn, tol), file=sys.stderr, flush=True)
+        print("connectivity %d, colour_tol %s, normal_tol %s: done" % (conn, tol, ntol), file=sys.stderr, flush=True)
     print(json.dumps(out))
 
 
