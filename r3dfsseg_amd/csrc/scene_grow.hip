@@ -1,0 +1,671 @@
+// Segments grown on the device: the device side of scene_grow.py.
+// build_segments ("Building segments", G1-G7): the partition that pool_segments takes, grown from the scan
+// itself.  Points fall into voxels, occupied voxels that touch (and, with a tolerance, whose mean colours agree; with
+// normal_tol, whose normals agree) are joined, the connected components are the segments.
+//   bounds      (scene_sort.hip) valid points, their xyz extent                -> words 0 .. 6 of the record (read 1)
+//   sort        voxel keys, the stable radix sort of scene_sort.hip on (key, scan index), voxel heads as flags, their scan
+//                                                                                 -> V (read 2)
+//   voxels      the voxel table in ascending key order, the voxel of every point, the mean colour of a voxel (the sums of
+//               the segment pool: tiles of 256 ranks, one addition at a time, tiles in order, one division)
+//   centroids   with normal_tol: the mean offset of a voxel's points inside the voxel, by the loop of the mean colours
+//   normals     with normal_tol: per voxel the second moments of the centroids of the occupied voxels among the 27 around
+//               it, (t I - B)^256 by eight squarings, the row of the largest diagonal entry; the support
+//   union       one thread per voxel and the forward half of its neighbourhood; a neighbour is found by its coordinates
+//               and a binary search of its key; joined pairs are united in parent[] by lock-free hooking; with normal_tol
+//               (r3d_scene_grow_union_normals) the same kernel with the test on the squared cosine of two normals
+//   components  root[v] = find(v) in a launch of its own, points per root, kept roots as flags, their scan
+//                                                                                 -> components, S (read 3)
+//   ids         the kept components numbered in ascending root order, spread to the points   -> the counts (read 4)
+// The union-find holds integers only and the component of a voxel depends on the graph alone: whichever thread hooks
+// first, the root of a component ends as its smallest row.  Floats are added by __fadd_rn in the stated order.
+#include "scene_common.h"
+
+#define GR_AXIS_MAX 1024  // voxels per axis: keys stay below 2^30
+// the record, words of ws[0 .. 16)
+#define GR_R_MIN 0        // x0 y0 z0 (float bits)
+#define GR_R_MAX 3        // the maxima (float bits)
+#define GR_R_NVALID 6
+#define GR_R_V 7          // occupied voxels
+#define GR_R_NCOMP 8      // components
+#define GR_R_S 9          // kept components
+#define GR_R_NDROPPED 10  // points of dropped components
+#define GR_R_ERROR 11     // != 0: a bounded loop of the union-find ran out (bit 0 a find, bit 1 a unite)
+
+struct gr_layout {
+  long rec;              // 16
+  long bpart;            // 7 * SC_BOUNDS_BLOCKS: partial bounds
+  sc_sort_ws sort;       // pairs of M + 1 words; key of the pair the sort leaves free: the voxel heads, scanned
+  long vkey;             // V: key of a voxel row
+  long vstart;           // V + 1: first sorted position of a voxel
+  long parent, root;     // V each
+  long cnt;              // V: points of the component, at its root
+  long kept;             // V + 1: kept roots in front of a voxel row
+  long total;
+};
+
+static gr_layout gr_make_layout(long M) {
+  gr_layout L;
+  const long Ma = sc_align(M + 1);
+  long o = 0;
+  L.rec = o; o += 16;
+  L.bpart = o; o += sc_align(7L * SC_BOUNDS_BLOCKS);
+  o = sc_sort_ws_append(L.sort, o, M, Ma, sc_sort_part_words(M, M + 1));
+  L.vkey = o; o += Ma;
+  L.vstart = o; o += Ma;
+  L.parent = o; o += Ma;
+  L.root = o; o += Ma;
+  L.cnt = o; o += Ma;
+  L.kept = o; o += Ma;
+  L.total = o;
+  return L;
+}
+
+extern "C" long r3d_scene_grow_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? gr_make_layout(M).total : -1; }
+
+// what every entry point after the bounds has: the scan's size, the grid and the workspace
+static int gr_check(const char* name, long M, int nx, int ny, int nz, const int32_t* ws, long ws_words) {
+  R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
+  SC_TRY(sc_check_points(name, M));
+  R3D_REQUIRE(nx >= 1 && nx <= GR_AXIS_MAX && ny >= 1 && ny <= GR_AXIS_MAX && nz >= 1 && nz <= GR_AXIS_MAX,
+              "%s: %d x %d x %d voxels (1 .. 1024 per axis)", name, nx, ny, nz);
+  return sc_check_ws(name, ws_words, r3d_scene_grow_ws_words(M));
+}
+
+// ---- bounds: the launcher of r3d_scene_bounds with z, into words 0 .. 6 of the record; the other words start at 0
+extern "C" int r3d_scene_grow_bounds(const float* scan, int ld, long M, int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(scan, "r3d_scene_grow_bounds: null pointer (scan)");
+  SC_TRY(sc_check_ld("r3d_scene_grow_bounds", ld));
+  SC_TRY(gr_check("r3d_scene_grow_bounds", M, 1, 1, 1, ws, ws_words));
+  const gr_layout L = gr_make_layout(M);
+  sc_bounds(scan, ld, M, 3, (float*)(ws + L.bpart), (float*)(ws + L.rec), (hipStream_t)stream);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_bounds");
+  return R3D_OK;
+}
+
+// ---- sort: keys (G2), the sort, the voxel heads and their scan
+struct gr_grid {
+  float x0, y0, z0, s;
+  int nx, ny, nz;
+};
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_keys_kernel(const float* __restrict__ scan, int ld, int M, gr_grid g,
+                                                                         int* __restrict__ key, int* __restrict__ idx) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= M) return;
+  const float* p = scan + (long)i * ld;
+  const float x = p[0], y = p[1], z = p[2];
+  int k = g.nx * g.ny * g.nz;  // invalid points sort behind every voxel
+  if (sc_finite3(x, y, z)) k = (sc_cell(z, g.z0, g.s, g.nz) * g.ny + sc_cell(y, g.y0, g.s, g.ny)) * g.nx + sc_cell(x, g.x0, g.s, g.nx);
+  key[i] = k;
+  idx[i] = i;
+}
+
+// sorted position i: heads[i] = it opens a voxel; word M is 0, so that the exclusive scan leaves V there
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_heads_kernel(const int* __restrict__ skey, int M, int n_cells,
+                                                                          int* __restrict__ heads) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i > M) return;
+  int h = 0;
+  if (i < M) {
+    const int k = skey[i];
+    h = k >= 0 && k < n_cells && (i == 0 || skey[i - 1] != k);
+  }
+  heads[i] = h;
+}
+
+__global__ void r3d_scene_grow_word_kernel(const int* __restrict__ src, int* __restrict__ dst) { *dst = *src; }
+
+extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny,
+                                   int nz, int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(scan, "r3d_scene_grow_sort: null pointer (scan)");
+  SC_TRY(sc_check_ld("r3d_scene_grow_sort", ld));
+  SC_TRY(gr_check("r3d_scene_grow_sort", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
+              "r3d_scene_grow_sort: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_layout L = gr_make_layout(M);
+  const int n_cells = nx * ny * nz;
+  const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
+  const int gm = sc_grid_of(M), gm1 = sc_grid_of(M + 1);
+  hipLaunchKernelGGL(r3d_scene_grow_keys_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, g, ws + L.sort.key[0],
+                     ws + L.sort.idx[0]);
+  const int sorted = sc_sort_pairs(ws, L.sort, M, sc_passes(n_cells), st);  // keys run 0 .. n_cells (n_cells: invalid point)
+  int* heads = ws + L.sort.key[sorted ^ 1];
+  hipLaunchKernelGGL(r3d_scene_grow_heads_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, ws + L.sort.key[sorted], (int)M, n_cells, heads);
+  sc_excl_scan(heads, M + 1, ws + L.sort.part, st);
+  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, heads + M, ws + L.rec + GR_R_V);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_sort");
+  return R3D_OK;
+}
+
+// ---- voxels: the table (G3)
+// after the scan: heads[i] = voxels opened in front of i.  A voxel's row is written by the thread of its first sorted
+// position, row V of vstart by the thread of position M.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_table_kernel(const int* __restrict__ skey, const int* __restrict__ order,
+                                                                          int M, int n_cells, int V, int n_valid,
+                                                                          const int* __restrict__ heads, int* __restrict__ vkey,
+                                                                          int* __restrict__ vstart, int* __restrict__ voxel_index) {
+  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i > M) return;
+  if (i == M) {
+    vstart[V] = n_valid;
+    return;
+  }
+  const int k = skey[i], v = heads[i + 1] - 1;
+  const bool in = k >= 0 && k < n_cells && v >= 0 && v < V;
+  const int p = sc_clamp(order[i], 0, M - 1);
+  voxel_index[p] = in ? v : -1;
+  if (in && heads[i + 1] != heads[i]) {
+    vkey[v] = k;
+    vstart[v] = i;
+  }
+}
+
+// One thread per voxel: its points in sorted order (ascending scan index: the sort is stable), three values per point
+// (row(p, c): those of scan row p) summed as the segment pool sums a segment whose rows all have one vote.
+template <class Row>
+static __device__ __forceinline__ void gr_voxel_mean(int v, int M, const int* __restrict__ order, const int* __restrict__ vstart,
+                                                     float* __restrict__ mean, Row row) {
+  const int a = sc_clamp(vstart[v], 0, M), b = sc_clamp(vstart[v + 1], a, M);
+  float tot[3] = {0.0f, 0.0f, 0.0f};
+  for (int t0 = a; t0 < b; t0 += SG_TILE) {
+    const int t1 = t0 + SG_TILE < b ? t0 + SG_TILE : b;
+    float part[3] = {0.0f, 0.0f, 0.0f};
+    for (int i = t0; i < t1; ++i) {
+      float c[3];
+      row(sc_clamp(order[i], 0, M - 1), c);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) part[j] = i == t0 ? c[j] : __fadd_rn(part[j], c[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) tot[j] = t0 == a ? part[j] : __fadd_rn(tot[j], part[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) mean[3L * v + j] = b > a ? __fdiv_rn(tot[j], (float)(b - a)) : 0.0f;
+}
+
+// the mean colour of a voxel (G3): columns 3 .. 5
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_mean_kernel(const float* __restrict__ scan, int ld, int M, int V,
+                                                                         const int* __restrict__ order, const int* __restrict__ vstart,
+                                                                         float* __restrict__ mean) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  gr_voxel_mean(v, M, order, vstart, mean, [&](int p, float* c) {
+    const float* r = scan + (long)p * ld + 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = r[j];
+  });
+}
+
+struct gr_view {
+  const int *skey, *order, *heads;
+  gr_layout L;
+};
+
+static gr_view gr_make_view(long M, int nx, int ny, int nz, const int32_t* ws) {
+  gr_view v;
+  v.L = gr_make_layout(M);
+  const int sorted = sc_passes((long)nx * ny * nz) & 1;
+  v.skey = ws + v.L.sort.key[sorted];
+  v.order = ws + v.L.sort.idx[sorted];
+  v.heads = ws + v.L.sort.key[sorted ^ 1];
+  return v;
+}
+
+extern "C" int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, int ny, int nz, long n_valid, long n_voxels,
+                                     int32_t* voxel_index, float* voxel_mean, int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(scan && voxel_index, "r3d_scene_grow_voxels: null pointer (scan %p, voxel_index %p)", (const void*)scan,
+              (void*)voxel_index);
+  const bool colour = voxel_mean != nullptr;
+  SC_TRY(sc_check_ld("r3d_scene_grow_voxels", ld));
+  SC_TRY(gr_check("r3d_scene_grow_voxels", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(n_valid >= 0 && n_valid <= M && n_voxels >= 0 && n_voxels <= n_valid,
+              "r3d_scene_grow_voxels: %ld voxels of %ld valid points among %ld", n_voxels, n_valid, M);
+  R3D_REQUIRE(!colour || ld >= 6, "r3d_scene_grow_voxels: a scan row of %d floats has no colour", ld);
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_view v = gr_make_view(M, nx, ny, nz, ws);
+  const int gm1 = sc_grid_of(M + 1);
+  hipLaunchKernelGGL(r3d_scene_grow_table_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, v.skey, v.order, (int)M, nx * ny * nz,
+                     (int)n_voxels, (int)n_valid, v.heads, ws + v.L.vkey, ws + v.L.vstart, voxel_index);
+  if (colour && n_voxels > 0)
+    hipLaunchKernelGGL(r3d_scene_grow_mean_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0, st,
+                       scan, ld, (int)M, (int)n_voxels, v.order, ws + v.L.vstart, voxel_mean);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_voxels");
+  return R3D_OK;
+}
+
+// ---- centroids (G3c) and normals (G3n): only with normal_tol
+// The centroid of a voxel: the mean of its points' offsets INSIDE the voxel, (v - v0) - (float)i * voxel with i decoded from
+// the voxel's key, summed as the mean colours are.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_centroid_kernel(const float* __restrict__ scan, int ld, int M, int V,
+                                                                             gr_grid g, const int* __restrict__ order,
+                                                                             const int* __restrict__ vstart,
+                                                                             const int* __restrict__ vkey, float* __restrict__ centroid) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int key = vkey[v];
+  const float v0[3] = {g.x0, g.y0, g.z0};
+  const float off[3] = {__fmul_rn((float)(key % g.nx), g.s), __fmul_rn((float)((key / g.nx) % g.ny), g.s),
+                        __fmul_rn((float)(key / (g.nx * g.ny)), g.s)};
+  gr_voxel_mean(v, M, order, vstart, centroid, [&](int p, float* c) {
+    const float* r = scan + (long)p * ld;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = __fsub_rn(__fsub_rn(r[j], v0[j]), off[j]);
+  });
+}
+
+extern "C" int r3d_scene_grow_centroids(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx,
+                                        int ny, int nz, long n_voxels, float* voxel_centroid, const int32_t* ws, long ws_words,
+                                        void* stream) {
+  R3D_REQUIRE(scan && voxel_centroid, "r3d_scene_grow_centroids: null pointer (scan %p, voxel_centroid %p)", (const void*)scan,
+              (void*)voxel_centroid);
+  SC_TRY(sc_check_ld("r3d_scene_grow_centroids", ld));
+  SC_TRY(gr_check("r3d_scene_grow_centroids", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
+              "r3d_scene_grow_centroids: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_centroids: %ld voxels of %ld points", n_voxels, M);
+  const gr_view v = gr_make_view(M, nx, ny, nz, ws);
+  const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
+  hipLaunchKernelGGL(r3d_scene_grow_centroid_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, scan, ld, (int)M, (int)n_voxels, g, v.order, ws + v.L.vstart, ws + v.L.vkey,
+                     voxel_centroid);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_centroids");
+  return R3D_OK;
+}
+
+#define GR_MIN_SUPPORT 4  // occupied voxels of the 27 below which a voxel has no normal
+#define GR_SQUARINGS 8    // (t I - B)^(2^8)
+
+// q of the neighbour at offset o (dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1), whose centroid is c
+static __device__ __forceinline__ void gr_q(int o, float s, const float* __restrict__ c, float* q) {
+  q[0] = __fadd_rn(__fmul_rn((float)(o % 3 - 1), s), c[0]);
+  q[1] = __fadd_rn(__fmul_rn((float)((o / 3) % 3 - 1), s), c[1]);
+  q[2] = __fadd_rn(__fmul_rn((float)(o / 9 - 1), s), c[2]);
+}
+
+// One thread per voxel.  The three x-neighbours of one (dz, dy) row have consecutive keys: one binary search finds the
+// first candidate row of the table, the next two are checked by key, and an x outside the grid is never looked up, so a
+// key that belongs to the neighbouring row of the grid is no neighbour.  The 27 rows stay in registers (every loop over
+// them is unrolled, no index is a run-time value); the centroids are gathered once for the mean and once more for the
+// second moments.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_normals_kernel(int V, int nx, int ny, int nz, float s,
+                                                                            const int* __restrict__ vkey,
+                                                                            const float* __restrict__ centroid,
+                                                                            float* __restrict__ normal, int* __restrict__ support) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int key = vkey[v];
+  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
+  int nb[27];
+  int k = 0;
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int jy = iy + r % 3 - 1, jz = iz + r / 3 - 1;
+    nb[3 * r] = nb[3 * r + 1] = nb[3 * r + 2] = -1;
+    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    const int base = (jz * ny + jy) * nx;
+    const int first = base + (ix > 0 ? ix - 1 : 0);
+    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
+    if (r == 4) {
+      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
+    } else {
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int jx = ix + d - 1;
+      if (jx < 0 || jx >= nx) continue;
+      if (lo < V && vkey[lo] == base + jx) {
+        nb[3 * r + d] = lo;
+        ++lo;
+        ++k;
+      }
+    }
+  }
+  float m[3] = {0.0f, 0.0f, 0.0f};
+  bool first = true;
+#pragma unroll
+  for (int o = 0; o < 27; ++o) {
+    float q[3];
+    gr_q(o, s, centroid + 3L * (nb[o] < 0 ? v : nb[o]), q);
+    if (nb[o] >= 0) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) m[a] = first ? q[a] : __fadd_rn(m[a], q[a]);
+      first = false;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) m[a] = __fdiv_rn(m[a], (float)k);
+  float C[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // 00 01 02 11 12 22
+  first = true;
+#pragma unroll
+  for (int o = 0; o < 27; ++o) {
+    float q[3];
+    gr_q(o, s, centroid + 3L * (nb[o] < 0 ? v : nb[o]), q);
+    if (nb[o] >= 0) {
+      const float e0 = __fsub_rn(q[0], m[0]), e1 = __fsub_rn(q[1], m[1]), e2 = __fsub_rn(q[2], m[2]);
+      const float p[6] = {__fmul_rn(e0, e0), __fmul_rn(e0, e1), __fmul_rn(e0, e2), __fmul_rn(e1, e1), __fmul_rn(e1, e2),
+                          __fmul_rn(e2, e2)};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) C[j] = first ? p[j] : __fadd_rn(C[j], p[j]);
+      first = false;
+    }
+  }
+  support[v] = k;
+  bool finite = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) finite = finite && fabsf(C[j]) < INFINITY;
+  const float top = fmaxf(fmaxf(C[0], C[3]), C[5]);
+  float* out = normal + 3L * v;
+  if (k < GR_MIN_SUPPORT || !finite || !(top > 0.0f)) {
+    out[0] = out[1] = out[2] = __int_as_float(0x7fc00000);
+    return;
+  }
+  float A[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) A[j] = __fdiv_rn(C[j], top);  // B
+  const float t = __fadd_rn(__fadd_rn(A[0], A[3]), A[5]);
+  A[0] = __fsub_rn(t, A[0]);
+  A[1] = -A[1];
+  A[2] = -A[2];
+  A[3] = __fsub_rn(t, A[3]);
+  A[4] = -A[4];
+  A[5] = __fsub_rn(t, A[5]);
+#define GR_DOT3(x0, y0, x1, y1, x2, y2) __fadd_rn(__fadd_rn(__fmul_rn(x0, y0), __fmul_rn(x1, y1)), __fmul_rn(x2, y2))
+  for (int it = 0; it < GR_SQUARINGS; ++it) {
+    const float N[6] = {GR_DOT3(A[0], A[0], A[1], A[1], A[2], A[2]), GR_DOT3(A[0], A[1], A[1], A[3], A[2], A[4]),
+                        GR_DOT3(A[0], A[2], A[1], A[4], A[2], A[5]), GR_DOT3(A[1], A[1], A[3], A[3], A[4], A[4]),
+                        GR_DOT3(A[1], A[2], A[3], A[4], A[4], A[5]), GR_DOT3(A[2], A[2], A[4], A[4], A[5], A[5])};
+    const float mx = fmaxf(fmaxf(N[0], N[3]), N[5]);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) A[j] = __fdiv_rn(N[j], mx);
+  }
+  // the row of the largest diagonal entry, the lowest on a tie
+  const int j = A[3] > A[0] ? (A[5] > A[3] ? 2 : 1) : (A[5] > A[0] ? 2 : 0);
+  out[0] = j == 0 ? A[0] : (j == 1 ? A[1] : A[2]);
+  out[1] = j == 0 ? A[1] : (j == 1 ? A[3] : A[4]);
+  out[2] = j == 0 ? A[2] : (j == 1 ? A[4] : A[5]);
+}
+
+extern "C" int r3d_scene_grow_normals(long M, int nx, int ny, int nz, long n_voxels, float voxel, const float* voxel_centroid,
+                                      float* voxel_normal, int32_t* voxel_support, const int32_t* ws, long ws_words,
+                                      void* stream) {
+  R3D_REQUIRE(voxel_centroid && voxel_normal && voxel_support,
+              "r3d_scene_grow_normals: null pointer (voxel_centroid %p, voxel_normal %p, voxel_support %p)",
+              (const void*)voxel_centroid, (void*)voxel_normal, (void*)voxel_support);
+  SC_TRY(gr_check("r3d_scene_grow_normals", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(voxel > 0.0f && voxel < INFINITY, "r3d_scene_grow_normals: voxel size %g", (double)voxel);
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_normals: %ld voxels of %ld points", n_voxels, M);
+  const gr_layout L = gr_make_layout(M);
+  hipLaunchKernelGGL(r3d_scene_grow_normals_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (int)n_voxels, nx, ny, nz, voxel, ws + L.vkey, voxel_centroid, voxel_normal,
+                     voxel_support);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_normals");
+  return R3D_OK;
+}
+
+// ---- union (G4, G5)
+// parent[] is changed inside this launch by agent-scope atomics only and read by relaxed agent-scope atomic loads: the
+// L2s of the XCDs are not coherent for plain accesses within a launch.  Invariants: parent[v] <= v, and a voxel that is
+// no root (parent[v] < v) never becomes one again.  A root's parent changes by one compare-and-swap (the hook); any other
+// parent only by atomicMin with one of its ancestors (path halving).  So whatever a thread reads is the voxel itself or
+// an ancestor of it, and the compare-and-swap decides.  No thread waits for another: every loop below counts down.
+static __device__ __forceinline__ int gr_load(const int* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of v, halving the path; a chain descends strictly, so it has at most V links.  -1: it had more (a corrupted
+// table), bit 0 of the error word is set.
+static __device__ __forceinline__ int gr_find(int* __restrict__ parent, int v, int V, int* __restrict__ err) {
+  for (int step = 0; step <= V; ++step) {
+    const int p = gr_load(parent + v);
+    if (p == v) return v;
+    if (p < 0 || p > v) break;
+    const int gp = gr_load(parent + p);
+    if (gp < 0 || gp > p) break;
+    if (gp != p) atomicMin(parent + v, gp);
+    v = gp;
+  }
+  atomicOr(err, 1);
+  return -1;
+}
+
+// Unites the components of a and b.  A compare-and-swap on hi fails only when another thread gave hi a parent; hi is no
+// root from then on, so no later find returns it and every failure of one unite is at another voxel: fewer than V
+// failures, V + 1 attempts bound the loop.  Past that (a corrupted table): bit 1 of the error word.
+static __device__ __forceinline__ void gr_unite(int* __restrict__ parent, int a, int b, int V, int* __restrict__ err) {
+  for (int attempt = 0; attempt <= V; ++attempt) {
+    a = gr_find(parent, a, V, err);
+    b = gr_find(parent, b, V, err);
+    if (a < 0 || b < 0 || a == b) return;
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    const int old = atomicCAS(parent + hi, hi, lo);
+    if (old == hi) return;
+    a = old;  // hi has a parent now: go on from it
+    b = lo;
+  }
+  atomicOr(err, 2);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_init_kernel(int V, int* __restrict__ parent) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v < V) parent[v] = v;
+}
+
+// One thread per voxel a, the forward half of the neighbourhood (the offsets whose key is larger): 3 of 6, 13 of 26.  The
+// neighbour's coordinates are checked against the grid, its key is looked up by binary search among the rows behind a.
+// NORMALS (r3d_scene_grow_union_normals): a pair is joined only when dot^2 >= (cos2 la) lb as well, la and lb the squared
+// lengths of the two normal rows; a NaN in either row makes the comparison false.
+static __device__ __forceinline__ float gr_dot3(const float* x, const float* y) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
+}
+
+template <bool NORMALS>
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_union_kernel(int V, int nx, int ny, int nz, int conn,
+                                                                          const int* __restrict__ vkey, int use_colour, float tol,
+                                                                          const float* __restrict__ mean,
+                                                                          const float* __restrict__ normal, float cos2,
+                                                                          int* __restrict__ parent, int* __restrict__ err) {
+  const int a = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (a >= V) return;
+  float na[3] = {0.0f, 0.0f, 0.0f}, la = 0.0f;
+  if (NORMALS) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) na[j] = normal[3L * a + j];
+    la = __fmul_rn(cos2, gr_dot3(na, na));
+  }
+  const int key = vkey[a];
+  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
+  float ma[3] = {0.0f, 0.0f, 0.0f};
+  if (use_colour) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ma[j] = mean[3L * a + j];
+  }
+  for (int o = 14; o < 27; ++o) {  // (dz, dy, dx) in lexicographic order behind (0, 0, 0)
+    const int dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1;
+    if (conn == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1) continue;
+    const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
+    if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    const int want = (jz * ny + jy) * nx + jx;
+    int lo = a + 1, hi = V;  // the first row in (a, V) whose key is not below `want`
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (vkey[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= V || vkey[lo] != want) continue;
+    if (use_colour) {
+      bool alike = true;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) alike = alike && fabsf(__fsub_rn(ma[j], mean[3L * lo + j])) <= tol;  // a NaN joins nothing
+      if (!alike) continue;
+    }
+    if (NORMALS) {
+      const float nb[3] = {normal[3L * lo], normal[3L * lo + 1], normal[3L * lo + 2]};
+      const float dot = gr_dot3(na, nb);
+      if (!(__fmul_rn(dot, dot) >= __fmul_rn(la, gr_dot3(nb, nb)))) continue;
+    }
+    gr_unite(parent, a, lo, V, err);
+  }
+}
+
+static int gr_union(const char* name, long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                    float colour_tol, const float* voxel_normal, float cos2, int32_t* ws, long ws_words, void* stream) {
+  const bool colour = voxel_mean != nullptr;
+  SC_TRY(gr_check(name, M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "%s: %ld voxels of %ld points", name, n_voxels, M);
+  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "%s: connectivity %d (6 or 26)", name, connectivity);
+  R3D_REQUIRE(!colour || (colour_tol >= 0.0f && colour_tol < INFINITY), "%s: colour_tol %g (finite, >= 0)", name,
+              (double)colour_tol);
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_layout L = gr_make_layout(M);
+  const int V = (int)n_voxels, gv = sc_grid_of(V);
+  hipLaunchKernelGGL(r3d_scene_grow_init_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.parent);
+  if (voxel_normal)
+    hipLaunchKernelGGL(r3d_scene_grow_union_kernel<true>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
+                       ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
+                       ws + L.rec + GR_R_ERROR);
+  else
+    hipLaunchKernelGGL(r3d_scene_grow_union_kernel<false>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
+                       ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
+                       ws + L.rec + GR_R_ERROR);
+  R3D_LAUNCH_CHECK(name);
+  return R3D_OK;
+}
+
+extern "C" int r3d_scene_grow_union(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                                    float colour_tol, int32_t* ws, long ws_words, void* stream) {
+  return gr_union("r3d_scene_grow_union", M, nx, ny, nz, n_voxels, connectivity, voxel_mean, colour_tol, nullptr, 0.0f, ws,
+                  ws_words, stream);
+}
+
+extern "C" int r3d_scene_grow_union_normals(long M, int nx, int ny, int nz, long n_voxels, int connectivity,
+                                            const float* voxel_mean, float colour_tol, const float* voxel_normal, float cos2,
+                                            int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(voxel_normal, "r3d_scene_grow_union_normals: null pointer (voxel_normal)");
+  R3D_REQUIRE(cos2 >= 0.0f && cos2 <= 1.0f, "r3d_scene_grow_union_normals: cos2 %g (0 .. 1)", (double)cos2);
+  return gr_union("r3d_scene_grow_union_normals", M, nx, ny, nz, n_voxels, connectivity, voxel_mean, colour_tol, voxel_normal,
+                  cos2, ws, ws_words, stream);
+}
+
+// ---- components (G5, G6): root[v] = find(v) in a launch of its own, into another array.  No hook happens here, so the
+// roots are final; the finds still halve the paths they walk, with the atomics of the union.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_flatten_kernel(int V, int* __restrict__ parent, int* __restrict__ root,
+                                                                            int* __restrict__ err) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int r = gr_find(parent, v, V, err);
+  root[v] = r < 0 ? v : r;  // (an overrun: an index inside the tables; the host raises on the error word)
+}
+
+// points per root: integer atomics, order-independent.  The lanes of a wave that share a root add their counts first and
+// send one atomic: neighbouring rows mostly share a root, and one atomic per voxel onto the root of a component that
+// holds most of the scan took 7.5 ms at 10^6 points (profiles/r22_scene_grow.md).
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_count_kernel(int V, int M, const int* __restrict__ root,
+                                                                          const int* __restrict__ vstart, int* __restrict__ cnt) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  const bool live = v < V;
+  int r = -1, n = 0;
+  if (live) {
+    const int a = sc_clamp(vstart[v], 0, M), b = sc_clamp(vstart[v + 1], a, M);
+    r = sc_clamp(root[v], 0, V - 1);
+    n = b - a;
+  }
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(live);
+  while (todo) {  // (uniform) one round per distinct root of the wave
+    const int leader = __ffsll((long long)todo) - 1;
+    const int r0 = __shfl(r, leader);
+    const bool mine = live && r == r0;
+    int sum = mine ? n : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == leader) atomicAdd(cnt + r0, sum);
+    todo &= ~__ballot(mine);
+  }
+}
+
+// row v: kept[v] = it is the root of a component with at least min_points points; word V is 0 for the scan's total
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_kept_kernel(int V, int min_points, const int* __restrict__ root,
+                                                                         const int* __restrict__ cnt, int* __restrict__ kept,
+                                                                         int* __restrict__ rec) {
+  __shared__ int red[SC_WAVES];
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  const bool is_root = v < V && root[v] == v;
+  if (v <= V) kept[v] = is_root && cnt[v] >= min_points;
+  const int n = sc_block_count(is_root ? 1 : 0, red);
+  if (threadIdx.x == 0 && n > 0) atomicAdd(rec + GR_R_NCOMP, n);
+}
+
+extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream) {
+  SC_TRY(gr_check("r3d_scene_grow_components", M, 1, 1, 1, ws, ws_words));
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_components: %ld voxels of %ld points", n_voxels, M);
+  R3D_REQUIRE(min_points >= 1, "r3d_scene_grow_components: min_points %d (at least 1)", min_points);
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_layout L = gr_make_layout(M);
+  const int V = (int)n_voxels, gv = sc_grid_of(V), gv1 = sc_grid_of(V + 1);
+  int* rec = ws + L.rec;
+  r3d_zero_words(rec + GR_R_NCOMP, 2, st);
+  r3d_zero_words(ws + L.cnt, V, st);
+  hipLaunchKernelGGL(r3d_scene_grow_flatten_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.parent, ws + L.root,
+                     rec + GR_R_ERROR);
+  hipLaunchKernelGGL(r3d_scene_grow_count_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, (int)M, ws + L.root, ws + L.vstart,
+                     ws + L.cnt);
+  hipLaunchKernelGGL(r3d_scene_grow_kept_kernel, dim3(gv1), dim3(SC_THREADS), 0, st, V, min_points, ws + L.root, ws + L.cnt,
+                     ws + L.kept, rec);
+  sc_excl_scan(ws + L.kept, V + 1L, ws + L.sort.part, st);
+  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, ws + L.kept + V, rec + GR_R_S);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_components");
+  return R3D_OK;
+}
+
+// ---- ids (G7): after the scan kept[v] = kept roots in front of row v, the id of a kept root
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_sizes_kernel(int V, int S, const int* __restrict__ kept,
+                                                                          const int* __restrict__ cnt, int* __restrict__ segment_points) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int s = kept[v];
+  if (kept[v + 1] != s && s >= 0 && s < S) segment_points[s] = cnt[v];
+}
+
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_spread_kernel(int M, int V, const int* __restrict__ voxel_index,
+                                                                           const int* __restrict__ root, const int* __restrict__ kept,
+                                                                           int* __restrict__ segments, int* __restrict__ rec) {
+  __shared__ int red[SC_WAVES];
+  int n_drop = 0;
+  for (long p = (long)blockIdx.x * SC_THREADS + threadIdx.x; p < M; p += (long)gridDim.x * SC_THREADS) {
+    const int v = voxel_index[p];
+    int s = -1;
+    if (v >= 0 && v < V) {
+      const int r = sc_clamp(root[v], 0, V - 1);
+      if (kept[r + 1] != kept[r]) s = kept[r];
+      n_drop += s < 0;
+    }
+    segments[p] = s;
+  }
+  n_drop = sc_block_count(n_drop, red);
+  if (threadIdx.x == 0 && n_drop > 0) atomicAdd(rec + GR_R_NDROPPED, n_drop);  // an integer count: order-independent
+}
+
+extern "C" int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
+                                  int32_t* segment_points, int32_t* ws, long ws_words, void* stream) {
+  SC_TRY(gr_check("r3d_scene_grow_ids", M, 1, 1, 1, ws, ws_words));
+  R3D_REQUIRE(voxel_index && segments, "r3d_scene_grow_ids: null pointer (voxel_index %p, segments %p)", (const void*)voxel_index,
+              (void*)segments);
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M && n_segments >= 0 && n_segments <= n_voxels,
+              "r3d_scene_grow_ids: %ld segments of %ld voxels of %ld points", n_segments, n_voxels, M);
+  R3D_REQUIRE(n_segments == 0 || segment_points, "r3d_scene_grow_ids: null pointer (segment_points)");
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_layout L = gr_make_layout(M);
+  const int V = (int)n_voxels;
+  r3d_zero_words(ws + L.rec + GR_R_NDROPPED, 1, st);
+  if (n_segments > 0)
+    hipLaunchKernelGGL(r3d_scene_grow_sizes_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V,
+                       (int)n_segments, ws + L.kept, ws + L.cnt, segment_points);
+  hipLaunchKernelGGL(r3d_scene_grow_spread_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, (int)M, V, voxel_index,
+                     ws + L.root, ws + L.kept, segments, ws + L.rec);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_ids");
+  return R3D_OK;
+}

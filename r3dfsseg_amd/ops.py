@@ -905,7 +905,7 @@ def scene_prepare_blocks(scan, ncx, ncy, r, N, chunk_cap, ws, blocks, out, rgb_c
 
 
 # ---- pool_segments: scores pooled over user-given segments (scene_segments.py)
-SCENE_SEG_TILE = 256   # SG_TILE of csrc/scene.hip: contributor ranks per tile
+SCENE_SEG_TILE = 256   # SG_TILE of csrc/scene_common.h: contributor ranks per tile
 SCENE_SEG_REC = 16     # words of the record in front of the workspace
 # the record's words (include/r3d.h, "pool_segments")
 SEG_R_MAX1, SEG_R_NNEG, SEG_R_NBAD, SEG_R_BADMAX, SEG_R_S, SEG_R_NCONTRIB, SEG_R_NTILES = 0, 1, 2, 4, 6, 7, 8
@@ -994,7 +994,7 @@ def scene_seg_spread(min_members, segment_index, seg_members, seg_fields, in_fie
 
 # ---- build_segments: segments grown from the scan (scene_grow.py)
 SCENE_GROW_REC = 16    # words of the record in front of the workspace
-SCENE_GROW_AXIS = 1024  # GR_AXIS_MAX of csrc/scene.hip: voxels per axis
+SCENE_GROW_AXIS = 1024  # GR_AXIS_MAX of csrc/scene_grow.hip: voxels per axis
 # the record's words (include/r3d.h, "build_segments")
 GROW_R_MIN, GROW_R_MAX, GROW_R_NVALID, GROW_R_V, GROW_R_NCOMP, GROW_R_S, GROW_R_NDROPPED, GROW_R_ERROR = 0, 3, 6, 7, 8, 9, 10, 11
 

@@ -28,7 +28,7 @@ support sets"): steps 1-6 once, per launch one encoder pass and the K heads on i
 transfer on logits of K * (n_way + 1) columns, and one merged class id per point (step 10, r3d_scene_merge_sets); per set
 the bits of predict_scene.
 
-This module holds the host logic; the kernels are csrc/scene.hip.  The logits of the chunks that run are kept ((n_chunks,
+This module holds the host logic; the kernels are csrc/scene.hip (the sort and the bounds: csrc/scene_sort.hip).  The logits of the chunks that run are kept ((n_chunks,
 n_way + 1, N) floats) and summed once at the end; accumulating launch by launch would give the same bits for less memory
 and one more pass over the scores per launch."""
 import numpy as np

@@ -23,7 +23,7 @@ alone, so the same scan gives the same bits.
   5. roots, points per root, the roots with at least min_points points            r3d_scene_grow_components  host read 3 of 4
   6. kept components numbered by ascending root, spread to the points             r3d_scene_grow_ids         host read 4 of 4
 
-This module holds the host logic; the kernels are in csrc/scene.hip, beside the sort they use."""
+This module holds the host logic; the kernels are in csrc/scene_grow.hip, on the sort and the bounds of csrc/scene_sort.hip."""
 import math
 
 import numpy as np

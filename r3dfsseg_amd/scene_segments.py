@@ -16,7 +16,7 @@ number and adds no float by an atomic: the same result and the same segments giv
   4. every point of a segment with at least min_members members takes the
      segment's row and label(s); any other point keeps the bits of res            r3d_scene_seg_spread host read 3 of 3
 
-This module holds the host logic; the kernels are in csrc/scene.hip, beside the sort they use."""
+This module holds the host logic; the kernels are in csrc/scene_segments.hip, on the sort of csrc/scene_sort.hip."""
 import numpy as np
 import torch
 

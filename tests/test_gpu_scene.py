@@ -1,4 +1,4 @@
-"""predict_scene on the device (r3dfsseg_amd/scene.py, csrc/scene.hip) against the numpy restatement tests/scene_ref.py.
+"""predict_scene on the device (r3dfsseg_amd/scene.py, csrc/scene.hip, csrc/scene_sort.hip) against the numpy restatement tests/scene_ref.py.
 
 Every comparison is torch.equal / np.array_equal: the definition ("Labelling a scan") fixes every operation
 and its order, so no tolerance is used in this file."""
@@ -261,3 +261,63 @@ def test_errors_on_the_device_path():
         next(learner.model.parameters()).add_(1e-3)  # one in-place weight update
     with pytest.raises(ValueError, match="stale fit"):
         learner.predict_scene(scan, stride=0.5)
+
+
+# ---- 7. the bounds alone, both records ------------------------------------------------------------------------------------
+BOUNDS_THREADS = 1024 * 256  # the bounds grid: a longer scan sends its threads through their stride loop a second time
+
+
+def _bounds_scan(M, ld, seed, all_invalid=False):
+    """A seeded scan whose extremes and invalid rows are placed: in a scan longer than the grid every extreme lies behind
+    BOUNDS_THREADS and invalid rows lie on both sides of it; one invalid row holds values beyond every extreme."""
+    rng = np.random.default_rng(seed)
+    scan = rng.uniform(-50.0, 50.0, (M, ld)).astype(np.float32)
+    lo = BOUNDS_THREADS if M > BOUNDS_THREADS else 0
+    if M - lo >= 6:
+        at = lo + rng.choice(M - lo, 6, replace=False)
+        for a in range(3):
+            scan[at[a], a] = -100.0 - a
+            scan[at[3 + a], a] = 200.0 + a
+    bad = np.zeros(M, bool)
+    if all_invalid:
+        bad[:] = True
+    elif M >= 63:
+        free = np.setdiff1d(np.arange(M), at)
+        sides = [free[free < lo], free[free >= lo]] if lo else [free]
+        for side in sides:
+            bad[rng.choice(side, 6, replace=False)] = True
+    rows = np.flatnonzero(bad)
+    for k, i in enumerate(rows):
+        scan[i, k % 3] = (np.nan, np.inf, -np.inf)[k % 3]
+    if len(rows):  # values that would move every other extreme, in a row that does not count
+        scan[rows[0], 1:3] = (-1e6, 1e6)
+        scan[rows[1], 0] = 1e6
+    return scan
+
+
+@pytest.mark.parametrize("M,ld,all_invalid", [(M, ld, False) for M in (1, 63, 257, BOUNDS_THREADS + 300) for ld in (3, 6)] +
+                         [(63, 3, True)])
+def test_bounds_of_both_records(M, ld, all_invalid):
+    """r3d_scene_bounds (xy) and r3d_scene_grow_bounds (xyz) against numpy's minima, maxima and count over the valid rows:
+    minima and maxima are exact and the count is an integer, so values are compared with == and nothing has a tolerance."""
+    from r3dfsseg_amd import ops
+    scan = _bounds_scan(M, ld, seed=1000 + M + ld, all_invalid=all_invalid)
+    valid = np.isfinite(scan[:, :3]).all(axis=1)
+    n = int(valid.sum())
+    assert n == (0 if all_invalid else M - (12 if M > BOUNDS_THREADS else 6 if M >= 63 else 0))
+    mn = scan[valid, :3].min(axis=0) if n else np.full(3, np.inf, np.float32)
+    mx = scan[valid, :3].max(axis=0) if n else np.full(3, -np.inf, np.float32)
+    if M > BOUNDS_THREADS:  # what the second trip has to find, and to skip
+        assert (~valid[:BOUNDS_THREADS]).sum() == 6 and (~valid[BOUNDS_THREADS:]).sum() == 6
+        for a in range(3):
+            col = np.where(valid, scan[:, a], np.nan)
+            assert np.nanargmin(col) >= BOUNDS_THREADS and np.nanargmax(col) >= BOUNDS_THREADS
+    dev = torch.from_numpy(scan).cuda()
+    rec = ops.scene_bounds(dev).cpu()
+    assert rec[:4].numpy().tolist() == [mn[0], mn[1], mx[0], mx[1]]
+    assert rec.view(torch.int32)[4:].tolist() == [n, 0, 0, 0]
+    ws = ops.scene_grow_workspace(M, "cuda")
+    ops.scene_grow_bounds(dev, ws)
+    rec = ws[:16].cpu()
+    assert rec[:6].view(torch.float32).numpy().tolist() == mn.tolist() + mx.tolist()
+    assert rec[6:].tolist() == [n] + [0] * 9

@@ -1,4 +1,4 @@
-"""build_segments on the device (r3dfsseg_amd/scene_grow.py, csrc/scene.hip) against the numpy restatement
+"""build_segments on the device (r3dfsseg_amd/scene_grow.py, csrc/scene_grow.hip) against the numpy restatement
 tests/scene_grow_ref.py (which tests/test_scene_grow_host.py checks against a breadth-first search).
 
 Every comparison is on integers, and bit for bit on the voxels' mean colours (a NaN mean: the NaN positions): the definition

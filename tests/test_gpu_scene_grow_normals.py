@@ -1,4 +1,4 @@
-"""grow_segments (build_segments with normal_tol) on the device (r3dfsseg_amd/scene_grow.py, csrc/scene.hip) against the numpy restatement
+"""grow_segments (build_segments with normal_tol) on the device (r3dfsseg_amd/scene_grow.py, csrc/scene_grow.hip) against the numpy restatement
 tests/scene_grow_normals_ref.py (which tests/test_scene_grow_normals_host.py checks against float64 eigenvectors and a
 breadth-first search).
 

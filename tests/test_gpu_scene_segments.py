@@ -1,4 +1,4 @@
-"""pool_segments on the device (r3dfsseg_amd/scene_segments.py, csrc/scene.hip) against the numpy restatement
+"""pool_segments on the device (r3dfsseg_amd/scene_segments.py, csrc/scene_segments.hip) against the numpy restatement
 tests/scene_segments_ref.py.
 
 Every comparison is bit for bit: the definition ("Pooling scores over segments") fixes every operation and
