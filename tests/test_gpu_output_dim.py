@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_ref import keep_mask as _keep_mask  # csrc/attention.hip::attn_keep for every (cloud, query, key)
 from oracle import r3d_oracle as O
 from r3dfsseg_amd import synthetic as S
 
@@ -21,20 +22,6 @@ WIDTHS = (32, 96, 128)
 def _rel(a, b):
     return ((a.double() - b).abs().max() / b.abs().max()).item()
 
-
-def _keep_mask(B, N, seed, p_drop):
-    """csrc/attention.hip::attn_keep for every (cloud, query, key): the stateless hash of (row = b N + query, key)."""
-    M32 = 0xFFFFFFFF
-    row = torch.arange(B * N, dtype=torch.int64).view(B, N, 1)
-    key = torch.arange(N, dtype=torch.int64).view(1, 1, N)
-    x = ((row * 0x9E3779B1) & M32) ^ ((key * 0x85EBCA77) & M32) ^ seed
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & M32
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & M32
-    x ^= x >> 16
-    thresh = int(float(np.float32(p_drop)) * 4294967296.0)
-    return x >= thresh
 
 
 def _ref(qkv, B, N, D, dO, keep=None, p_drop=0.0):

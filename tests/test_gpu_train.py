@@ -258,7 +258,7 @@ def test_attention_dropout_mask_and_backward():
     st = ops._st()
     # effective seed = immediate + device word (the word is what a captured episode graph bumps per replay)
     sdev = torch.tensor([1000], dtype=torch.int32, device="cuda")
-    aws = torch.empty(lib.r3d_attention_ws_words(B, N), device="cuda")  # enables the key-axis split (8 ranges here)
+    aws = torch.empty(lib.r3d_attention_ws_words(B, N), device="cuda")  # packed operands; no key-axis split by default
     _lib.check(lib.r3d_attention_fwd_train(ops._p(qg), 192, B, N, ops._p(out), 64, ops._p(lse), p, ctypes.c_uint(seed - 1000),
                                            ops._p(sdev), ops._p(aws), st))
     np.testing.assert_allclose(out.cpu().numpy(), y.detach().numpy(), atol=1e-4, rtol=1e-4)
