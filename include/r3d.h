@@ -740,10 +740,11 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  * (dataloaders/loader.py:339-349); the definition is this project's.  A VALID point has finite x y z.  Voxel of a valid
  * point: i_a = (int)floorf((v_a - v0_a) / voxel) per axis, v0 the minima read from the record, key = (iz * ny + iy) * nx +
  * ix, nx, ny, nz <= 1024 the host's counts from the same arithmetic at the maxima.  ws: ONE int32 scratch of
- * r3d_scene_grow_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the six calls of one build, which pass the same M
+ * r3d_scene_grow_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the calls of one build, which pass the same M
  * and nx, ny, nz; its first 16 words are the record the host reads:
  *   [0..2] min x y z, [3..5] max x y z (float bits)   [6] valid points   [7] occupied voxels V   [8] components
  *   [9] kept components S   [10] points of dropped components   [11] != 0: a bounded loop of the union-find ran out
+ *   [12] absorbed voxels   [13] absorbed points (r3d_scene_grow_absorb; 0 without it)
  *
  *   entry point                what it does                                                              host reads
  *   r3d_scene_grow_bounds      words 0 .. 6 of the record, zeros in the others (r3d_scene_bounds keeps no z
@@ -772,9 +773,23 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  *                              own; points per root by integer atomics (the lanes of a wave that share a root
  *                              add first); a root is KEPT when its component has at least min_points points;
  *                              the kept roots' scan.                                                     words 8, 9, 11
+ *   r3d_scene_grow_absorb      only with absorb > 0 (G6a), between components and ids; rings 1 .. 64, voxel_ring
+ *                              (V,) int32 the caller's.  owner[v] = root[v] where that root is kept, else -1 (v is
+ *                              FREE); voxel_ring[v] = 0, or -1 for a free voxel.  Then `rings` launches, one thread
+ *                              per voxel, each reading one owner table and writing the other (a voxel taken in
+ *                              round r is seen from round r + 1 on): a voxel with an owner copies it; a free one
+ *                              finds its occupied neighbours at all 6 or 26 offsets as r3d_scene_grow_normals does
+ *                              (coordinates checked against 0 .. n - 1 per axis, one binary search per (dz, dy)), no
+ *                              colour and no normal test, and takes the owner that most of the neighbours with an
+ *                              owner have, the smallest on a tie, voxel_ring[v] = the round; none: it stays free.
+ *                              A last launch sets root[v] = owner[v] for the absorbed voxels and adds their points
+ *                              to the owner's count by integer atomics (the lanes of a wave that share an owner add
+ *                              first).  The tables lie in the workspace (the index array of the pair the sort left
+ *                              free, and parent[], dead after components); no atomics touch them, no thread waits.
+ *                              S and the ids of r3d_scene_grow_ids are unchanged: only -1s become ids.        words 12, 13
  *   r3d_scene_grow_ids         n_segments: word 9 as read.  Kept components are numbered 0 .. S - 1 by
  *                              ascending root; segments (M,) int32: that number, -1 for an invalid point
- *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          word 10
+ *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          words 10, 12, 13
  * No float atomics: the component of a voxel depends on the joined pairs alone, so the same scan gives the same bits.
  *
  * With normal_tol (G3c, G3n and the normal test of G4) two launches go between voxels and the union, and the union is
@@ -821,6 +836,8 @@ int r3d_scene_grow_union_normals(long M, int nx, int ny, int nz, long n_voxels, 
                                  float colour_tol, const float* voxel_normal, float cos2, int32_t* ws, long ws_words,
                                  void* stream);
 int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_grow_absorb(long M, int nx, int ny, int nz, long n_voxels, int connectivity, int rings, int32_t* voxel_ring,
+                          int32_t* ws, long ws_words, void* stream);
 int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
                        int32_t* segment_points, int32_t* ws, long ws_words, void* stream);
 

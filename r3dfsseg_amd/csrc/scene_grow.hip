@@ -15,6 +15,8 @@
 //               (r3d_scene_grow_union_normals) the same kernel with the test on the squared cosine of two normals
 //   components  root[v] = find(v) in a launch of its own, points per root, kept roots as flags, their scan
 //                                                                                 -> components, S (read 3)
+//   absorb      with absorb > 0: the voxels of dropped components taken ring by ring into the kept component most of
+//               their neighbours belong to, one launch per ring over two owner tables; their points join its count
 //   ids         the kept components numbered in ascending root order, spread to the points   -> the counts (read 4)
 // The union-find holds integers only and the component of a voxel depends on the graph alone: whichever thread hooks
 // first, the root of a component ends as its smallest row.  Floats are added by __fadd_rn in the stated order.
@@ -30,6 +32,9 @@
 #define GR_R_S 9          // kept components
 #define GR_R_NDROPPED 10  // points of dropped components
 #define GR_R_ERROR 11     // != 0: a bounded loop of the union-find ran out (bit 0 a find, bit 1 a unite)
+#define GR_R_ABSORBED_VOXELS 12  // voxels of dropped components taken into a kept one (absorb)
+#define GR_R_ABSORBED_POINTS 13  // their points
+#define GR_RINGS_MAX 64   // rounds of absorb
 
 struct gr_layout {
   long rec;              // 16
@@ -618,6 +623,147 @@ extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, 
   sc_excl_scan(ws + L.kept, V + 1L, ws + L.sort.part, st);
   hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, ws + L.kept + V, rec + GR_R_S);
   R3D_LAUNCH_CHECK("r3d_scene_grow_components");
+  return R3D_OK;
+}
+
+// ---- absorb (G6a): the voxels of dropped components taken into the kept component most of their neighbours belong to,
+// ring by ring.  owner[v]: the root of the kept component v belongs to, -1 while v is free.  Two owner tables, one read
+// and one written per round (a Jacobi round): a voxel taken in round r is seen by its neighbours from round r + 1 on.  One
+// lies in the index array of the pair the sort leaves free, the other in parent[], which nothing reads after the flatten
+// launch.  Rounds are launches of their own, so what a round reads was written by an earlier launch: plain loads and
+// stores, no atomics on the owner tables.  No thread waits for another; a round's loops are the 27 offsets and the depth
+// of a binary search.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_start_kernel(int V, const int* __restrict__ root,
+                                                                                 const int* __restrict__ kept,
+                                                                                 int* __restrict__ owner, int* __restrict__ ring) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int r = sc_clamp(root[v], 0, V - 1);
+  const bool in = kept[r + 1] != kept[r];  // after the scan: r is a kept root
+  owner[v] = in ? r : -1;
+  ring[v] = in ? 0 : -1;
+}
+
+// One thread per voxel.  A voxel that has an owner copies it.  A free one looks its neighbours up as the normals kernel
+// does (per (dz, dy) one binary search for the first x-neighbour inside the grid, the next rows of the table checked by
+// key; an x outside the grid is never looked up), keeps the owners of those the connectivity allows in registers (every
+// loop over them is unrolled), and takes the owner most of them have, the smallest on a tie.  Its own row is free, so it
+// never counts.  The unrolled 27 x 27 tally takes 206 VGPRs; rolled over candidates picked by selects it takes 44 and the
+// absorb span was 5 to 15 % longer (profiles/r25_scene_grow_absorb.md): a ring is bound by the free lanes' latency.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_round_kernel(int V, int nx, int ny, int nz, int conn, int round,
+                                                                                 const int* __restrict__ vkey,
+                                                                                 const int* __restrict__ src, int* __restrict__ dst,
+                                                                                 int* __restrict__ ring) {
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const int mine = src[v];
+  if (mine >= 0) {
+    dst[v] = mine;
+    return;
+  }
+  const int key = vkey[v];
+  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
+  int own[27];
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int dy = r % 3 - 1, dz = r / 3 - 1;
+    const int jy = iy + dy, jz = iz + dz;
+    own[3 * r] = own[3 * r + 1] = own[3 * r + 2] = -1;
+    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    if (conn == 6 && dy != 0 && dz != 0) continue;
+    const int base = (jz * ny + jy) * nx;
+    const int first = base + (ix > 0 ? ix - 1 : 0);
+    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
+    if (r == 4) {
+      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
+    } else {
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int jx = ix + d - 1;
+      if (jx < 0 || jx >= nx) continue;
+      if (lo < V && vkey[lo] == base + jx) {
+        if (conn != 6 || (d != 1) + (dy != 0) + (dz != 0) == 1) own[3 * r + d] = sc_clamp(src[lo], -1, V - 1);
+        ++lo;
+      }
+    }
+  }
+  int best = -1, best_n = 0;
+#pragma unroll
+  for (int i = 0; i < 27; ++i) {
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < 27; ++j) n += own[j] == own[i];
+    if (own[i] >= 0 && (n > best_n || (n == best_n && own[i] < best))) {
+      best = own[i];
+      best_n = n;
+    }
+  }
+  dst[v] = best;
+  if (best >= 0) ring[v] = round;
+}
+
+// The absorbed voxels (ring > 0) get their owner as their root and add their points to the owner's count: as in the count
+// kernel, the lanes of a wave that share an owner add first.  Words 12 and 13 of the record: absorbed voxels and points.
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_end_kernel(int V, int M, const int* __restrict__ owner,
+                                                                               const int* __restrict__ ring,
+                                                                               const int* __restrict__ vstart, int* __restrict__ root,
+                                                                               int* __restrict__ cnt, int* __restrict__ rec) {
+  __shared__ int red[SC_WAVES];
+  const int v = blockIdx.x * SC_THREADS + threadIdx.x;
+  int r = -1, n = 0;
+  if (v < V && ring[v] > 0) r = sc_clamp(owner[v], -1, V - 1);
+  const bool live = r >= 0;
+  if (live) {
+    const int a = sc_clamp(vstart[v], 0, M), b = sc_clamp(vstart[v + 1], a, M);
+    n = b - a;
+    root[v] = r;
+  }
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(live);
+  while (todo) {  // (uniform) one round per distinct owner of the wave
+    const int leader = __ffsll((long long)todo) - 1;
+    const int r0 = __shfl(r, leader);
+    const bool mine = live && r == r0;
+    int sum = mine ? n : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == leader) atomicAdd(cnt + r0, sum);
+    todo &= ~__ballot(mine);
+  }
+  const int voxels = sc_block_count(live ? 1 : 0, red), points = sc_block_count(n, red);
+  if (threadIdx.x == 0 && voxels > 0) {
+    atomicAdd(rec + GR_R_ABSORBED_VOXELS, voxels);  // integer counts: order-independent
+    atomicAdd(rec + GR_R_ABSORBED_POINTS, points);
+  }
+}
+
+extern "C" int r3d_scene_grow_absorb(long M, int nx, int ny, int nz, long n_voxels, int connectivity, int rings,
+                                     int32_t* voxel_ring, int32_t* ws, long ws_words, void* stream) {
+  R3D_REQUIRE(voxel_ring, "r3d_scene_grow_absorb: null pointer (voxel_ring)");
+  SC_TRY(gr_check("r3d_scene_grow_absorb", M, nx, ny, nz, ws, ws_words));
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_absorb: %ld voxels of %ld points", n_voxels, M);
+  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "r3d_scene_grow_absorb: connectivity %d (6 or 26)", connectivity);
+  R3D_REQUIRE(rings >= 1 && rings <= GR_RINGS_MAX, "r3d_scene_grow_absorb: %d rings (1 .. %d)", rings, GR_RINGS_MAX);
+  const hipStream_t st = (hipStream_t)stream;
+  const gr_layout L = gr_make_layout(M);
+  const int sorted = sc_passes((long)nx * ny * nz) & 1;
+  const int V = (int)n_voxels, gv = sc_grid_of(V);
+  int* owner[2] = {ws + L.sort.idx[sorted ^ 1], ws + L.parent};  // M + 1 and V words: both hold V
+  int* rec = ws + L.rec;
+  r3d_zero_words(rec + GR_R_ABSORBED_VOXELS, 2, st);
+  hipLaunchKernelGGL(r3d_scene_grow_absorb_start_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.root, ws + L.kept, owner[0],
+                     voxel_ring);
+  for (int r = 1; r <= rings; ++r)
+    hipLaunchKernelGGL(r3d_scene_grow_absorb_round_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity, r,
+                       ws + L.vkey, owner[(r - 1) & 1], owner[r & 1], voxel_ring);
+  hipLaunchKernelGGL(r3d_scene_grow_absorb_end_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, (int)M, owner[rings & 1], voxel_ring,
+                     ws + L.vstart, ws + L.root, ws + L.cnt, rec);
+  R3D_LAUNCH_CHECK("r3d_scene_grow_absorb");
   return R3D_OK;
 }
 

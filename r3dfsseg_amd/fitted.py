@@ -275,6 +275,14 @@ class FittedLearner(object):
         from . import scene_grow
         return scene_grow.grow_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol)
 
+    def absorb_segments(self, scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
+        """grow_segments with one more step, absorb: the number of rings, 0 .. 64, by which the voxels that min_points
+        dropped -- with normal_tol the slivers along the edge between two planes -- are taken into the kept segment most
+        of their neighbours belong to.  The segments and their ids are those of grow_segments; only -1s become ids
+        (scene_grow.py; INTEGRATION.md, "Building segments", G6a)."""
+        from . import scene_grow
+        return scene_grow.absorb_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol, absorb)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

@@ -997,6 +997,8 @@ SCENE_GROW_REC = 16    # words of the record in front of the workspace
 SCENE_GROW_AXIS = 1024  # GR_AXIS_MAX of csrc/scene_grow.hip: voxels per axis
 # the record's words (include/r3d.h, "build_segments")
 GROW_R_MIN, GROW_R_MAX, GROW_R_NVALID, GROW_R_V, GROW_R_NCOMP, GROW_R_S, GROW_R_NDROPPED, GROW_R_ERROR = 0, 3, 6, 7, 8, 9, 10, 11
+GROW_R_ABSORBED_VOXELS, GROW_R_ABSORBED_POINTS = 12, 13  # written by scene_grow_absorb, 0 without it
+SCENE_GROW_RINGS = 64  # GR_RINGS_MAX of csrc/scene_grow.hip: rounds of absorb
 
 
 def scene_grow_workspace(M, device):
@@ -1089,6 +1091,17 @@ def scene_grow_components(M, n_voxels, min_points, ws):
     """Roots, points per root, kept roots and their scan, in ws -> words 8 (components), 9 (S) and 11 (error)."""
     assert _seg_ws_ok(ws)
     _lib.check(_lib.load().r3d_scene_grow_components(M, int(n_voxels), int(min(min_points, 2 ** 31 - 1)), _p(ws), ws.numel(), _st()))
+
+
+def scene_grow_absorb(M, grid, n_voxels, connectivity, rings, ws):
+    """With absorb > 0, after the read of S and before scene_grow_ids: `rings` rounds of G6a on the tables in ws -> voxel_ring
+    (V,) int32: 0 for a voxel of a kept component, the round that took an absorbed one, -1 for one still free; words 12
+    (absorbed voxels) and 13 (absorbed points)."""
+    assert _seg_ws_ok(ws)
+    ring = torch.empty(int(n_voxels), device=ws.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_grow_absorb(M, *(int(n) for n in grid), int(n_voxels), int(connectivity), int(rings),
+                                                 _p(ring), _p(ws), ws.numel(), _st()))
+    return ring
 
 
 def scene_grow_ids(voxel_index, n_voxels, n_segments, ws):

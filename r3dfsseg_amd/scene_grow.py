@@ -21,6 +21,8 @@ alone, so the same scan gives the same bits.
   4. every voxel united with the occupied neighbours in front of it               r3d_scene_grow_union, or with normal_tol
                                                                                   r3d_scene_grow_union_normals
   5. roots, points per root, the roots with at least min_points points            r3d_scene_grow_components  host read 3 of 4
+  5a. absorb_segments with absorb > 0: the voxels of dropped components taken, ring by ring, into
+      the kept component most of their neighbours belong to (G6a)                 r3d_scene_grow_absorb
   6. kept components numbered by ascending root, spread to the points             r3d_scene_grow_ids         host read 4 of 4
 
 This module holds the host logic; the kernels are in csrc/scene_grow.hip, on the sort and the bounds of csrc/scene_sort.hip."""
@@ -32,17 +34,20 @@ import torch
 from . import ops, scene
 
 MAX_AXIS = ops.SCENE_GROW_AXIS
+MAX_RINGS = ops.SCENE_GROW_RINGS
 AXES = "xyz"
 
 
 class GrownSegments:
-    """What build_segments returns.  On the device: segments (M,) int32, 0 .. S - 1, or -1 for an invalid point or a point
+    """What build_segments, grow_segments and absorb_segments return.  On the device: segments (M,) int32, 0 .. S - 1, or -1 for an invalid point or a point
     of a dropped component; segment_points (S,) int32; voxel_index (M,) int32, the row of the point's voxel in the voxel
     table (ascending key order), -1 for an invalid point; voxel_means (V, 3) fp32, the mean colour of every voxel, None
     without colour_tol.  With normal_tol, else None: voxel_centroids (V, 3) fp32, the mean position of a voxel's points
     measured from the voxel's lower corner; voxel_normals (V, 3) fp32, not of unit length, its largest component 1, a row of
-    NaNs where a voxel has no normal; voxel_support (V,) int32, the occupied voxels among the 27 around it.  Host ints: n_segments (S), n_voxels, n_components (before min_points), n_dropped_points, n_invalid;
-    grid (nx, ny, nz), (0, 0, 0) without a valid point."""
+    NaNs where a voxel has no normal; voxel_support (V,) int32, the occupied voxels among the 27 around it.  With absorb > 0,
+    else None: voxel_ring (V,) int32, 0 for a voxel of a kept component, r for one absorbed in round r, -1 for one still
+    free.  Host ints: n_segments (S), n_voxels, n_components (before min_points), n_dropped_points (after absorbing),
+    n_absorbed_voxels, n_absorbed_points (0 with absorb=0), n_invalid; grid (nx, ny, nz), (0, 0, 0) without a valid point."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -57,7 +62,7 @@ def cos2_of(normal_tol):
     return np.float32(math.cos(math.radians(float(normal_tol))) ** 2)
 
 
-def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None):
+def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
     """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
     if isinstance(scan, np.ndarray):
         scan = torch.from_numpy(scan)
@@ -85,6 +90,8 @@ def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
                              % (colour_tol, scan.shape[1]))
     if normal_tol is not None and not (_is_real(normal_tol) and np.isfinite(normal_tol) and 0 <= normal_tol <= 90):
         raise ValueError("grow_segments: normal_tol %r must be None or a finite real number of degrees in [0, 90]" % (normal_tol,))
+    if not scene._is_int(absorb) or not 0 <= absorb <= MAX_RINGS:
+        raise ValueError("absorb_segments: absorb %r must be an integer number of rings in 0 .. %d" % (absorb, MAX_RINGS))
     return scan, v32
 
 
@@ -118,13 +125,22 @@ def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points
 
 
 def grow_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None):
+    """absorb_segments without absorbing: build_segments and, with normal_tol, the normal test.  Its signature is kept as it
+    was (a test pins it); the rings are a keyword of absorb_segments."""
+    return absorb_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol)
+
+
+def absorb_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
     """scan (M, 3) or (M, >= 6) float32 rows x y z [r g b ...], host or device, M <= 2^27 -> GrownSegments.  voxel: the edge
     of a voxel, at most 1024 of them along an axis; connectivity 6 (faces) or 26 (faces, edges, corners); colour_tol: None,
     or the largest difference of two neighbouring voxels' mean colours, per channel, that still joins them; min_points: a
     component with fewer points is dropped, its points get -1; normal_tol: None, or the largest angle in degrees, 0 .. 90,
     between the normals of two neighbouring voxels that still joins them (both must have a normal; with colour_tol both
-    tests must hold; needs no colour).  See the module text and INTEGRATION.md, "Building segments"."""
-    scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points, normal_tol)
+    tests must hold; needs no colour); absorb: the number of rings, 0 .. 64, by which the voxels of dropped components are
+    taken into the kept segment most of their neighbours belong to (G6a: no colour or normal test; S and every id of
+    absorb=0 stay, only -1s become ids).  See the module text and INTEGRATION.md, "Building segments"."""
+    scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points, normal_tol, absorb)
+    absorb = int(absorb)
     if not torch.cuda.is_available():
         raise RuntimeError("build_segments: no device (there is no CPU path)")
     dev = scan.device if scan.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -143,7 +159,9 @@ def grow_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=
                              voxel_means=table(colour_tol is not None, 3), n_segments=0, n_voxels=0, n_components=0,
                              n_dropped_points=0, n_invalid=M, grid=(0, 0, 0), voxel_centroids=table(normal_tol is not None, 3),
                              voxel_normals=table(normal_tol is not None, 3),
-                             voxel_support=None if normal_tol is None else torch.empty(0, device=dev, dtype=torch.int32))
+                             voxel_support=None if normal_tol is None else torch.empty(0, device=dev, dtype=torch.int32),
+                             voxel_ring=torch.empty(0, device=dev, dtype=torch.int32) if absorb else None,
+                             n_absorbed_voxels=0, n_absorbed_points=0)
     ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
     lo, hi = ext[:3], ext[3:]
     grid = grid_of(lo, hi, voxel)
@@ -161,9 +179,12 @@ def grow_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=
     rec = read_record(ws)  # host read 3 of 4: the tables' sizes
     _raise_on_error(rec)
     n_components, S = rec[ops.GROW_R_NCOMP], rec[ops.GROW_R_S]
+    ring = ops.scene_grow_absorb(M, grid, V, connectivity, absorb, ws) if absorb else None
     segments, segment_points = ops.scene_grow_ids(voxel_index, V, S, ws)
     rec = read_record(ws)  # host read 4 of 4, after everything is queued
     _raise_on_error(rec)
     return GrownSegments(segments=segments, segment_points=segment_points, voxel_index=voxel_index, voxel_means=voxel_means,
                          n_segments=S, n_voxels=V, n_components=n_components, n_dropped_points=rec[ops.GROW_R_NDROPPED],
-                         n_invalid=M - n_valid, grid=grid, voxel_centroids=centroids, voxel_normals=normals, voxel_support=support)
+                         n_invalid=M - n_valid, grid=grid, voxel_centroids=centroids, voxel_normals=normals, voxel_support=support,
+                         voxel_ring=ring, n_absorbed_voxels=rec[ops.GROW_R_ABSORBED_VOXELS],
+                         n_absorbed_points=rec[ops.GROW_R_ABSORBED_POINTS])

@@ -3,7 +3,7 @@ calls it sits between and beside the numpy restatement on the CPU (the only base
 library).
 
     python tools/scene_grow_cost.py [--points 1000000] [--calls 7] [--voxel 0.05] [--colour-tol 64] [--baseline one]
-                                    [--scan scene|room] [--normal-tol DEGREES]
+                                    [--scan scene|room] [--normal-tol DEGREES] [--min-points N --absorb R [R ...]]
 
 --scan scene (the default): the seeded room of synthetic.make_scene, 8 m x 6 m x 3 m of uniform points with colours in
 0 .. 255 -- about one point per occupied voxel at 0.05 m, so the voxel graph is as large as the scan allows.  --scan room:
@@ -11,7 +11,9 @@ synthetic.make_room, the same extent as SURFACES (a floor, four walls, three box
 more points, the scan normal_tol is meant for.  Configurations: connectivity 6 and 26, without colour and with colour_tol;
 and both with colour_tol = 0, which joins next to nothing on the uniform scan: the union span is then the neighbour searches
 alone, and what the other configurations take beyond it is the hooking.  With --normal-tol the first four are run once
-more with that normal_tol, and their spans include the two launches it adds, centroids and normals.
+more with that normal_tol, and their spans include the two launches it adds, centroids and normals.  With --absorb (needs
+--normal-tol) connectivity 6 and 26 are run with that normal_tol and --min-points once more per ring count, 0 first: the
+absorb span (the start launch, one launch per ring, the end launch) and the share of the scan's points that are -1.
 
 Per configuration, after a warm-up call: `calls` calls each timed with one HIP event pair (the call's four host reads lie
 inside it) and with the host clock, reported as median, minimum and maximum; then `calls` more with event pairs THIS TOOL
@@ -39,7 +41,8 @@ from r3dfsseg_amd import ops, scene_grow as G, scene_segments as SS, synthetic a
 
 SPANS = {"scene_grow_bounds": "bounds", "scene_grow_sort": "sort", "scene_grow_voxels": "voxels",
          "scene_grow_centroids": "centroids", "scene_grow_normals": "normals", "scene_grow_union": "union",
-         "scene_grow_union_normals": "union", "scene_grow_components": "flatten", "scene_grow_ids": "ids"}
+         "scene_grow_union_normals": "union", "scene_grow_components": "flatten", "scene_grow_absorb": "absorb",
+         "scene_grow_ids": "ids"}
 
 
 def stats(ms):
@@ -112,7 +115,11 @@ def main():
     ap.add_argument("--baseline", choices=["none", "one", "all"], default="one")
     ap.add_argument("--scan", choices=["scene", "room"], default="scene")
     ap.add_argument("--normal-tol", type=float, default=None)
+    ap.add_argument("--min-points", type=int, default=1)
+    ap.add_argument("--absorb", type=int, nargs="*", default=[])
     args = ap.parse_args()
+    if args.absorb and args.normal_tol is None:
+        ap.error("--absorb needs --normal-tol")
     from r3dfsseg_amd.proto_learner import ProtoLearner
     cfg = S.workload_cfg("S")
     if args.scan == "room":
@@ -126,15 +133,19 @@ def main():
     out = {"points": args.points, "calls": args.calls, "voxel": args.voxel, "scan": args.scan,
            "predict_scene": timed_calls(predict, min(args.calls, 3)), "runs": []}
     res = predict()
-    configs = [(6, None, None), (26, None, None), (6, args.colour_tol, None), (26, args.colour_tol, None), (6, 0.0, None),
-               (26, 0.0, None)]
+    configs = [(6, None, None, None), (26, None, None, None), (6, args.colour_tol, None, None), (26, args.colour_tol, None, None),
+               (6, 0.0, None, None), (26, 0.0, None, None)]
     if args.normal_tol is not None:
-        configs += [(conn, tol, args.normal_tol) for conn, tol, _ in configs[:4]]
-    for n, (conn, tol, ntol) in enumerate(configs):
+        configs += [(conn, tol, args.normal_tol, None) for conn, tol, _, _ in configs[:4]]
+    configs += [(conn, None, args.normal_tol, rings) for conn in (6, 26) for rings in [0] + args.absorb if args.absorb]
+    for n, (conn, tol, ntol, rings) in enumerate(configs):
         if ntol is None:  # (the call of a tree that has no normal_tol, too)
             grow = lambda: G.build_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn)
-        else:
+        elif rings is None:  # (and of one that has no absorb)
             grow = lambda: G.grow_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn, normal_tol=ntol)
+        else:
+            grow = lambda: G.absorb_segments(scan, voxel=args.voxel, colour_tol=tol, connectivity=conn, normal_tol=ntol,
+                                             min_points=args.min_points, absorb=rings)
         rec = {"connectivity": conn, "colour_tol": tol, "normal_tol": ntol, "build_segments": timed_calls(grow, args.calls)}
         rec["span_ms"] = spans(grow, args.calls)
         sg = grow()
@@ -142,12 +153,19 @@ def main():
                    largest_segment_points=sorted(sg.segment_points.tolist(), reverse=True)[:6])
         if ntol is not None:
             rec["voxels_without_normal"] = int(torch.isnan(sg.voxel_normals[:, 0]).sum())
+        if rings is not None:
+            rec.update(min_points=args.min_points, absorb=rings, n_absorbed_voxels=sg.n_absorbed_voxels,
+                       n_absorbed_points=sg.n_absorbed_points, n_dropped_points=sg.n_dropped_points,
+                       share_unsegmented=round(float((sg.segments < 0).float().mean()), 6))
         rec["pool_segments"] = timed_calls(lambda: SS.pool_segments(res, sg.segments), args.calls)
         if (args.baseline == "all" and (n < 4 or ntol is not None)) or (args.baseline == "one" and n == 0):
             t0 = time.perf_counter()
             if ntol is None:
                 import scene_grow_ref
                 want = scene_grow_ref.grow(scan_host.numpy(), args.voxel, tol, conn)
+            elif rings is not None:
+                import scene_grow_absorb_ref
+                want = scene_grow_absorb_ref.grow(scan_host.numpy(), args.voxel, tol, conn, args.min_points, ntol, rings)
             else:
                 import scene_grow_normals_ref
                 want = scene_grow_normals_ref.grow(scan_host.numpy(), args.voxel, tol, conn, normal_tol=ntol)
@@ -156,7 +174,7 @@ def main():
                                              and np.array_equal(sg.voxel_index.cpu().numpy(), want["voxel_index"])
                                              and sg.n_components == want["n_components"])
         out["runs"].append(rec)
-        print("connectivity %d, colour_tol %s, normal_tol %s: done" % (conn, tol, ntol), file=sys.stderr, flush=True)
+        print("connectivity %d, colour_tol %s, normal_tol %s, absorb %s: done" % (conn, tol, ntol, rings), file=sys.stderr, flush=True)
     print(json.dumps(out))
 
 
