@@ -841,6 +841,63 @@ int r3d_scene_grow_absorb(long M, int nx, int ny, int nz, long n_voxels, int con
 int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
                        int32_t* segment_points, int32_t* ws, long ws_words, void* stream);
 
+/* ---- extract_objects: object instances from a labelled scan ("Objects from a labelled scan", O1-O8).
+ * Additive: no entry point above changes.  The reference has no such function; the definition is this project's.
+ * labels (M,): int32 (labels64 = 0) or int64 (labels64 = 1); ignore: n_ignore <= 64 int64 class ids on the device (NULL with
+ * n_ignore = 0).  A point TAKES PART when x y z are finite, its label is >= 0 and not in ignore.  The grid is the one of
+ * build_segments (origin: the minima over the finite points).  A UNIT is the set of participating points of one class in one
+ * cell; key = label * n_cells + cell, n_cells = nx ny nz, n_labels the largest participating label plus one, n_labels *
+ * n_cells <= 2^31 - 1 (the key of every other point; it sorts last).  ws: ONE int32 scratch of r3d_scene_obj_ws_words(M) words
+ * (-1: M outside 1 .. 2^27) shared by the calls of one extraction, laid out as that of build_segments; its first 16 words
+ * are the record the host reads:
+ *   [0..2] min x y z, [3..5] max x y z (float bits)   [6] finite points   [7] units U   [8] components   [9] kept components S
+ *   [10] points of dropped components   [11] != 0: a bounded loop of the union-find ran out   [12] n_labels
+ *   [13] finite points left out by their label   [14] finite points whose label is above 2^31 - 2 and not ignored (no key holds
+ *   them: the host raises)   [15] participating points
+ *
+ *   entry point                what it does                                                              host reads
+ *   r3d_scene_obj_bounds       r3d_scene_grow_bounds, then words 12 .. 15 by integer atomics               words 0 .. 6, 12 .. 15
+ *   r3d_scene_obj_sort         x0 y0 z0, the grid: from words 0 .. 5 as build_segments derives them; n_labels, n_points:
+ *                              words 12 and 15 as read.  Keys, the stable LSD radix sort on (key, scan index), 8 bits a
+ *                              pass up to the highest set bit of n_labels n_cells, the first sorted position of every
+ *                              unit as a flag, their scan, the unit table (rows in ascending key order, a row's points by
+ *                              ascending scan index); unit_index (M,) int32: the row of a point's unit, -1 for a point
+ *                              that takes no part.                                                       word 7
+ *   r3d_scene_obj_union        parent[u] = u, then one thread per unit a and the offsets (dx, dy, dz) with a larger cell
+ *                              key (3 for connectivity 6, 13 for 26): the neighbour's coordinates are checked against
+ *                              0 .. n - 1 per axis, then its key is formed with a's class and found by binary search among
+ *                              the rows behind a; a pair found is united as r3d_scene_grow_union unites (the same device
+ *                              functions; only agent-scope atomics touch parent[]; an overrun sets word 11).   -
+ *   r3d_scene_obj_components   the launches of r3d_scene_grow_components on the unit table.               words 8, 9, 11
+ *   r3d_scene_obj_stats        n_objects = S >= 1: word 9 as read.  Per object s (kept components by ascending root, so by
+ *                              ascending class, then smallest cell key): object_labels (S,) int64; object_points (S,)
+ *                              int32; object_units (S,) int32; object_lo, object_hi (S, 3) fp32: the minima and maxima of
+ *                              its points' coordinates, exact, -0.0 below +0.0; object_centroid (S, 3) fp32: per axis
+ *                              v0 + voxel * ((sum / n) + 0.5) / 256 in float64 in that order, rounded once, sum the int64
+ *                              sum over its points of u = (int)floorf(((v - v0) / voxel) * 256.0f) (fp32, each operation
+ *                              rounded, clamped to 0 .. 256 n_axis - 1).  object_sums (S, 3) int64: the caller's scratch.
+ *                              One thread per unit reduces its points; the units of a wave that share an object are
+ *                              combined by shuffles; per wave and object 6 atomic min / max on the order-preserving
+ *                              integer image of the float bits, 3 64-bit atomic adds and 1 atomic add.        -
+ *   r3d_scene_obj_ids          objects (M,) int32: the number of the point's object, -1 for a point that takes no part
+ *                              or a dropped component (r3d_scene_grow_ids' launch).                         words 10, 11
+ * No float goes through an atomic: the same scan and labels give the same bits. */
+long r3d_scene_obj_ws_words(long M);
+int r3d_scene_obj_bounds(const float* scan, int ld, long M, const void* labels, int labels64, const int64_t* ignore, int n_ignore,
+                         int32_t* ws, long ws_words, void* stream);
+int r3d_scene_obj_sort(const float* scan, int ld, long M, const void* labels, int labels64, const int64_t* ignore, int n_ignore,
+                       float x0, float y0, float z0, float voxel, int nx, int ny, int nz, int n_labels, long n_points,
+                       int32_t* unit_index, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_obj_union(long M, int nx, int ny, int nz, int n_labels, long n_units, int connectivity, int32_t* ws, long ws_words,
+                        void* stream);
+int r3d_scene_obj_components(long M, long n_units, int min_points, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_obj_stats(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny, int nz,
+                        int n_labels, long n_units, long n_objects, int64_t* object_labels, int32_t* object_points,
+                        int32_t* object_units, float* object_lo, float* object_hi, float* object_centroid, int64_t* object_sums,
+                        const int32_t* ws, long ws_words, void* stream);
+int r3d_scene_obj_ids(long M, long n_units, long n_objects, const int32_t* unit_index, int32_t* objects, int32_t* ws,
+                      long ws_words, void* stream);
+
 /* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.

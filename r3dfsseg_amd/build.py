@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libr3d_hip.so")
 SOURCES = ["error.hip", "knn.hip", "gemm.hip", "gemm_bx3.hip", "edgeconv.hip", "attention.hip", "head_proto.hip",
            "head_graph.hip", "aux_heads.hip", "protonet_train.hip", "train_ops.hip", "edgeconv_train.hip", "contrast.hip",
-           "augment.hip", "scene_sort.hip", "scene.hip", "scene_segments.hip", "scene_grow.hip", "episode_cut.hip"]
+           "augment.hip", "scene_sort.hip", "scene.hip", "scene_segments.hip", "scene_grow.hip", "scene_objects.hip",
+           "episode_cut.hip"]
 # No packed fp32 vector arithmetic (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32), neither from the SLP vectoriser nor from
 # float2 / float4 source arithmetic: measured on MI355X (profiles/r02_experiments.md, section 9), a wave executing them
 # beside waves of a bf16-MFMA-dense kernel on the same SIMD got wrong results in lanes 48-63 of one half of the pair --
@@ -36,7 +37,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdr = [os.path.join(CSRC, h) for h in ("common.h", "edge_tile.h", "edgeconv_bwd_bx3.h", "scene_common.h")] + [os.path.join(INCLUDE, "r3d.h")]
+    hdr = [os.path.join(CSRC, h) for h in ("common.h", "edge_tile.h", "edgeconv_bwd_bx3.h", "scene_common.h", "scene_components.h")] + [os.path.join(INCLUDE, "r3d.h")]
     objs = []
     procs = []
     for s in [x for x in SOURCES if os.path.exists(os.path.join(CSRC, x))]:

@@ -1,5 +1,6 @@
-// What the scene sources share: scene.hip (labelling and support), scene_segments.hip (pool_segments) and scene_grow.hip
-// (build_segments) all stand on the sort, the scan and the bounds of scene_sort.hip.  Here: the sizes they agree on, the
+// What the scene sources share: scene.hip (labelling and support), scene_segments.hip (pool_segments), scene_grow.hip
+// (build_segments) and scene_objects.hip (extract_objects; with scene_grow.hip through scene_components.h) all stand on the
+// sort, the scan and the bounds of scene_sort.hip.  Here: the sizes they agree on, the
 // device helpers more than one of them uses, the workspace of the sort, the argument checks they have in common and the
 // host launchers of scene_sort.hip.  A kernel is launched only from the file that defines it.
 #pragma once

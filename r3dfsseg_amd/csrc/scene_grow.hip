@@ -20,50 +20,11 @@
 //   ids         the kept components numbered in ascending root order, spread to the points   -> the counts (read 4)
 // The union-find holds integers only and the component of a voxel depends on the graph alone: whichever thread hooks
 // first, the root of a component ends as its smallest row.  Floats are added by __fadd_rn in the stated order.
-#include "scene_common.h"
+// scene_objects.hip grows the units of a labelled scan the same way: the heads, init, components and ids launches below are
+// gr_launch_* (scene_components.h), called here by the entry points and there by r3d_scene_obj_*.
+#include "scene_components.h"  // the record, the workspace and the union-find, shared with scene_objects.hip
 
-#define GR_AXIS_MAX 1024  // voxels per axis: keys stay below 2^30
-// the record, words of ws[0 .. 16)
-#define GR_R_MIN 0        // x0 y0 z0 (float bits)
-#define GR_R_MAX 3        // the maxima (float bits)
-#define GR_R_NVALID 6
-#define GR_R_V 7          // occupied voxels
-#define GR_R_NCOMP 8      // components
-#define GR_R_S 9          // kept components
-#define GR_R_NDROPPED 10  // points of dropped components
-#define GR_R_ERROR 11     // != 0: a bounded loop of the union-find ran out (bit 0 a find, bit 1 a unite)
-#define GR_R_ABSORBED_VOXELS 12  // voxels of dropped components taken into a kept one (absorb)
-#define GR_R_ABSORBED_POINTS 13  // their points
 #define GR_RINGS_MAX 64   // rounds of absorb
-
-struct gr_layout {
-  long rec;              // 16
-  long bpart;            // 7 * SC_BOUNDS_BLOCKS: partial bounds
-  sc_sort_ws sort;       // pairs of M + 1 words; key of the pair the sort leaves free: the voxel heads, scanned
-  long vkey;             // V: key of a voxel row
-  long vstart;           // V + 1: first sorted position of a voxel
-  long parent, root;     // V each
-  long cnt;              // V: points of the component, at its root
-  long kept;             // V + 1: kept roots in front of a voxel row
-  long total;
-};
-
-static gr_layout gr_make_layout(long M) {
-  gr_layout L;
-  const long Ma = sc_align(M + 1);
-  long o = 0;
-  L.rec = o; o += 16;
-  L.bpart = o; o += sc_align(7L * SC_BOUNDS_BLOCKS);
-  o = sc_sort_ws_append(L.sort, o, M, Ma, sc_sort_part_words(M, M + 1));
-  L.vkey = o; o += Ma;
-  L.vstart = o; o += Ma;
-  L.parent = o; o += Ma;
-  L.root = o; o += Ma;
-  L.cnt = o; o += Ma;
-  L.kept = o; o += Ma;
-  L.total = o;
-  return L;
-}
 
 extern "C" long r3d_scene_grow_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? gr_make_layout(M).total : -1; }
 
@@ -120,6 +81,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_heads_kernel(const 
 
 __global__ void r3d_scene_grow_word_kernel(const int* __restrict__ src, int* __restrict__ dst) { *dst = *src; }
 
+void gr_launch_heads(const int* skey, long M, int key_limit, int* heads, int32_t* ws, const gr_layout& L, hipStream_t st) {
+  hipLaunchKernelGGL(r3d_scene_grow_heads_kernel, dim3(sc_grid_of(M + 1)), dim3(SC_THREADS), 0, st, skey, (int)M, key_limit, heads);
+  sc_excl_scan(heads, M + 1, ws + L.sort.part, st);
+  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, heads + M, ws + L.rec + GR_R_V);
+}
+
 extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny,
                                    int nz, int32_t* ws, long ws_words, void* stream) {
   R3D_REQUIRE(scan, "r3d_scene_grow_sort: null pointer (scan)");
@@ -131,14 +98,10 @@ extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, 
   const gr_layout L = gr_make_layout(M);
   const int n_cells = nx * ny * nz;
   const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
-  const int gm = sc_grid_of(M), gm1 = sc_grid_of(M + 1);
-  hipLaunchKernelGGL(r3d_scene_grow_keys_kernel, dim3(gm), dim3(SC_THREADS), 0, st, scan, ld, (int)M, g, ws + L.sort.key[0],
-                     ws + L.sort.idx[0]);
+  hipLaunchKernelGGL(r3d_scene_grow_keys_kernel, dim3(sc_grid_of(M)), dim3(SC_THREADS), 0, st, scan, ld, (int)M, g,
+                     ws + L.sort.key[0], ws + L.sort.idx[0]);
   const int sorted = sc_sort_pairs(ws, L.sort, M, sc_passes(n_cells), st);  // keys run 0 .. n_cells (n_cells: invalid point)
-  int* heads = ws + L.sort.key[sorted ^ 1];
-  hipLaunchKernelGGL(r3d_scene_grow_heads_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, ws + L.sort.key[sorted], (int)M, n_cells, heads);
-  sc_excl_scan(heads, M + 1, ws + L.sort.part, st);
-  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, heads + M, ws + L.rec + GR_R_V);
+  gr_launch_heads(ws + L.sort.key[sorted], M, n_cells, ws + L.sort.key[sorted ^ 1], ws, L, st);
   R3D_LAUNCH_CHECK("r3d_scene_grow_sort");
   return R3D_OK;
 }
@@ -202,21 +165,6 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_mean_kernel(const f
   });
 }
 
-struct gr_view {
-  const int *skey, *order, *heads;
-  gr_layout L;
-};
-
-static gr_view gr_make_view(long M, int nx, int ny, int nz, const int32_t* ws) {
-  gr_view v;
-  v.L = gr_make_layout(M);
-  const int sorted = sc_passes((long)nx * ny * nz) & 1;
-  v.skey = ws + v.L.sort.key[sorted];
-  v.order = ws + v.L.sort.idx[sorted];
-  v.heads = ws + v.L.sort.key[sorted ^ 1];
-  return v;
-}
-
 extern "C" int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, int ny, int nz, long n_valid, long n_voxels,
                                      int32_t* voxel_index, float* voxel_mean, int32_t* ws, long ws_words, void* stream) {
   R3D_REQUIRE(scan && voxel_index, "r3d_scene_grow_voxels: null pointer (scan %p, voxel_index %p)", (const void*)scan,
@@ -228,7 +176,7 @@ extern "C" int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, 
               "r3d_scene_grow_voxels: %ld voxels of %ld valid points among %ld", n_voxels, n_valid, M);
   R3D_REQUIRE(!colour || ld >= 6, "r3d_scene_grow_voxels: a scan row of %d floats has no colour", ld);
   const hipStream_t st = (hipStream_t)stream;
-  const gr_view v = gr_make_view(M, nx, ny, nz, ws);
+  const gr_view v = gr_make_view(M, (long)nx * ny * nz, ws);
   const int gm1 = sc_grid_of(M + 1);
   hipLaunchKernelGGL(r3d_scene_grow_table_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, v.skey, v.order, (int)M, nx * ny * nz,
                      (int)n_voxels, (int)n_valid, v.heads, ws + v.L.vkey, ws + v.L.vstart, voxel_index);
@@ -269,7 +217,7 @@ extern "C" int r3d_scene_grow_centroids(const float* scan, int ld, long M, float
   R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
               "r3d_scene_grow_centroids: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
   R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_centroids: %ld voxels of %ld points", n_voxels, M);
-  const gr_view v = gr_make_view(M, nx, ny, nz, ws);
+  const gr_view v = gr_make_view(M, (long)nx * ny * nz, ws);
   const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
   hipLaunchKernelGGL(r3d_scene_grow_centroid_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0,
                      (hipStream_t)stream, scan, ld, (int)M, (int)n_voxels, g, v.order, ws + v.L.vstart, ws + v.L.vkey,
@@ -413,51 +361,15 @@ extern "C" int r3d_scene_grow_normals(long M, int nx, int ny, int nz, long n_vox
 }
 
 // ---- union (G4, G5)
-// parent[] is changed inside this launch by agent-scope atomics only and read by relaxed agent-scope atomic loads: the
-// L2s of the XCDs are not coherent for plain accesses within a launch.  Invariants: parent[v] <= v, and a voxel that is
-// no root (parent[v] < v) never becomes one again.  A root's parent changes by one compare-and-swap (the hook); any other
-// parent only by atomicMin with one of its ancestors (path halving).  So whatever a thread reads is the voxel itself or
-// an ancestor of it, and the compare-and-swap decides.  No thread waits for another: every loop below counts down.
-static __device__ __forceinline__ int gr_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of v, halving the path; a chain descends strictly, so it has at most V links.  -1: it had more (a corrupted
-// table), bit 0 of the error word is set.
-static __device__ __forceinline__ int gr_find(int* __restrict__ parent, int v, int V, int* __restrict__ err) {
-  for (int step = 0; step <= V; ++step) {
-    const int p = gr_load(parent + v);
-    if (p == v) return v;
-    if (p < 0 || p > v) break;
-    const int gp = gr_load(parent + p);
-    if (gp < 0 || gp > p) break;
-    if (gp != p) atomicMin(parent + v, gp);
-    v = gp;
-  }
-  atomicOr(err, 1);
-  return -1;
-}
-
-// Unites the components of a and b.  A compare-and-swap on hi fails only when another thread gave hi a parent; hi is no
-// root from then on, so no later find returns it and every failure of one unite is at another voxel: fewer than V
-// failures, V + 1 attempts bound the loop.  Past that (a corrupted table): bit 1 of the error word.
-static __device__ __forceinline__ void gr_unite(int* __restrict__ parent, int a, int b, int V, int* __restrict__ err) {
-  for (int attempt = 0; attempt <= V; ++attempt) {
-    a = gr_find(parent, a, V, err);
-    b = gr_find(parent, b, V, err);
-    if (a < 0 || b < 0 || a == b) return;
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    const int old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) return;
-    a = old;  // hi has a parent now: go on from it
-    b = lo;
-  }
-  atomicOr(err, 2);
-}
-
+// The union-find itself (gr_load, gr_find, gr_unite: parent[] touched by agent-scope atomics only, no thread waits) is in
+// scene_components.h.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_init_kernel(int V, int* __restrict__ parent) {
   const int v = blockIdx.x * SC_THREADS + threadIdx.x;
   if (v < V) parent[v] = v;
+}
+
+void gr_launch_init(int V, int32_t* ws, const gr_layout& L, hipStream_t st) {
+  hipLaunchKernelGGL(r3d_scene_grow_init_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V, ws + L.parent);
 }
 
 // One thread per voxel a, the forward half of the neighbourhood (the offsets whose key is larger): 3 of 6, 13 of 26.  The
@@ -527,7 +439,7 @@ static int gr_union(const char* name, long M, int nx, int ny, int nz, long n_vox
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int V = (int)n_voxels, gv = sc_grid_of(V);
-  hipLaunchKernelGGL(r3d_scene_grow_init_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.parent);
+  gr_launch_init(V, ws, L, st);
   if (voxel_normal)
     hipLaunchKernelGGL(r3d_scene_grow_union_kernel<true>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
                        ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
@@ -604,13 +516,8 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_kept_kernel(int V, 
   if (threadIdx.x == 0 && n > 0) atomicAdd(rec + GR_R_NCOMP, n);
 }
 
-extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream) {
-  SC_TRY(gr_check("r3d_scene_grow_components", M, 1, 1, 1, ws, ws_words));
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_components: %ld voxels of %ld points", n_voxels, M);
-  R3D_REQUIRE(min_points >= 1, "r3d_scene_grow_components: min_points %d (at least 1)", min_points);
-  const hipStream_t st = (hipStream_t)stream;
-  const gr_layout L = gr_make_layout(M);
-  const int V = (int)n_voxels, gv = sc_grid_of(V), gv1 = sc_grid_of(V + 1);
+void gr_launch_components(long M, int V, int min_points, int32_t* ws, const gr_layout& L, hipStream_t st) {
+  const int gv = sc_grid_of(V), gv1 = sc_grid_of(V + 1);
   int* rec = ws + L.rec;
   r3d_zero_words(rec + GR_R_NCOMP, 2, st);
   r3d_zero_words(ws + L.cnt, V, st);
@@ -622,6 +529,13 @@ extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, 
                      ws + L.kept, rec);
   sc_excl_scan(ws + L.kept, V + 1L, ws + L.sort.part, st);
   hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, ws + L.kept + V, rec + GR_R_S);
+}
+
+extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream) {
+  SC_TRY(gr_check("r3d_scene_grow_components", M, 1, 1, 1, ws, ws_words));
+  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_components: %ld voxels of %ld points", n_voxels, M);
+  R3D_REQUIRE(min_points >= 1, "r3d_scene_grow_components: min_points %d (at least 1)", min_points);
+  gr_launch_components(M, (int)n_voxels, min_points, ws, gr_make_layout(M), (hipStream_t)stream);
   R3D_LAUNCH_CHECK("r3d_scene_grow_components");
   return R3D_OK;
 }
@@ -795,6 +709,16 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_spread_kernel(int M
   if (threadIdx.x == 0 && n_drop > 0) atomicAdd(rec + GR_R_NDROPPED, n_drop);  // an integer count: order-independent
 }
 
+void gr_launch_ids(long M, int V, int S, const int32_t* voxel_index, int32_t* segments, int32_t* segment_points, int32_t* ws,
+                   const gr_layout& L, hipStream_t st) {
+  r3d_zero_words(ws + L.rec + GR_R_NDROPPED, 1, st);
+  if (S > 0 && segment_points)
+    hipLaunchKernelGGL(r3d_scene_grow_sizes_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V, S, ws + L.kept, ws + L.cnt,
+                       segment_points);
+  hipLaunchKernelGGL(r3d_scene_grow_spread_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, (int)M, V, voxel_index,
+                     ws + L.root, ws + L.kept, segments, ws + L.rec);
+}
+
 extern "C" int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* voxel_index, int32_t* segments,
                                   int32_t* segment_points, int32_t* ws, long ws_words, void* stream) {
   SC_TRY(gr_check("r3d_scene_grow_ids", M, 1, 1, 1, ws, ws_words));
@@ -803,15 +727,8 @@ extern "C" int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const 
   R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M && n_segments >= 0 && n_segments <= n_voxels,
               "r3d_scene_grow_ids: %ld segments of %ld voxels of %ld points", n_segments, n_voxels, M);
   R3D_REQUIRE(n_segments == 0 || segment_points, "r3d_scene_grow_ids: null pointer (segment_points)");
-  const hipStream_t st = (hipStream_t)stream;
-  const gr_layout L = gr_make_layout(M);
-  const int V = (int)n_voxels;
-  r3d_zero_words(ws + L.rec + GR_R_NDROPPED, 1, st);
-  if (n_segments > 0)
-    hipLaunchKernelGGL(r3d_scene_grow_sizes_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V,
-                       (int)n_segments, ws + L.kept, ws + L.cnt, segment_points);
-  hipLaunchKernelGGL(r3d_scene_grow_spread_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, (int)M, V, voxel_index,
-                     ws + L.root, ws + L.kept, segments, ws + L.rec);
+  gr_launch_ids(M, (int)n_voxels, (int)n_segments, voxel_index, segments, segment_points, ws, gr_make_layout(M),
+                (hipStream_t)stream);
   R3D_LAUNCH_CHECK("r3d_scene_grow_ids");
   return R3D_OK;
 }

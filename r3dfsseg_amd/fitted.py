@@ -283,6 +283,16 @@ class FittedLearner(object):
         from . import scene_grow
         return scene_grow.absorb_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol, absorb)
 
+    def extract_objects(self, scan, labels, voxel=0.05, connectivity=26, min_points=1, ignore=()):
+        """Object instances from a labelled scan: labels (M,) int32 or int64 are the .labels of what predict_scene,
+        predict_scene_sets or pool_segments returned, or ground truth (negative: no class; ignore: class ids that form no
+        objects).  The points of one class in cells of edge `voxel` that touch are one object: a scene_objects.SceneObjects
+        with the object of every point and, per object, its class, points, cells, box and centroid; its .objects goes to
+        pool_segments as it is (scene_objects.py; INTEGRATION.md, "Objects from a labelled scan").  Needs no fit and no
+        model."""
+        from . import scene_objects
+        return scene_objects.extract_objects(scan, labels, voxel, connectivity, min_points, ignore)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

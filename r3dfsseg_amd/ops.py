@@ -1115,6 +1115,92 @@ def scene_grow_ids(voxel_index, n_voxels, n_segments, ws):
     return segments, segment_points
 
 
+# ---- extract_objects: objects from a labelled scan (scene_objects.py)
+SCENE_OBJ_IGNORE = 64          # OB_IGNORE_MAX of csrc/scene_objects.hip: entries of the ignore table
+SCENE_OBJ_LABEL = 2 ** 31 - 2  # OB_LABEL_MAX: the largest label a key holds
+SCENE_OBJ_KEY = 2 ** 31 - 1    # OB_KEY_MAX: n_labels * n_cells
+# the record: the words of build_segments above (GROW_R_V: the units) and four of its own (include/r3d.h, "extract_objects")
+OBJ_R_NLABELS, OBJ_R_NUNLABELLED, OBJ_R_NOVER, OBJ_R_NPOINTS = 12, 13, 14, 15
+
+
+def scene_obj_workspace(M, device):
+    """-> ws, int32 of r3d_scene_obj_ws_words(M) words: the one scratch of an extract_objects call, its record in front."""
+    words = _lib.load().r3d_scene_obj_ws_words(M)
+    if words < 0:
+        raise ValueError("extract_objects: %d points (1 .. 2^27)" % M)
+    return torch.empty(words, device=device, dtype=torch.int32)
+
+
+def _obj_labels_args(scan, labels, ignore):
+    assert labels.dim() == 1 and labels.numel() == scan.shape[0] and labels.dtype in (torch.int32, torch.int64)
+    assert labels.is_cuda and labels.is_contiguous()
+    n = 0 if ignore is None else ignore.numel()
+    assert n == 0 or (ignore.dtype == torch.int64 and ignore.is_cuda and ignore.is_contiguous() and n <= SCENE_OBJ_IGNORE)
+    return _p(labels), int(labels.dtype == torch.int64), _p(ignore) if n else None, n
+
+
+def scene_obj_bounds(scan, labels, ignore, ws):
+    """scan (M, ld) fp32, labels (M,) int32 or int64, ignore (n,) int64 or None, all on the device -> words 0 .. 6 and
+    12 .. 15 of the record in ws (zeros in the others), on the device."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    _lib.check(_lib.load().r3d_scene_obj_bounds(_p(scan), ld, M, *_obj_labels_args(scan, labels, ignore), _p(ws), ws.numel(),
+                                                _st()))
+
+
+def scene_obj_sort(scan, labels, ignore, origin, voxel, grid, n_labels, n_points, ws):
+    """origin, n_labels, n_points as read from the record, grid (nx, ny, nz): keys, the sort, the unit heads, the unit table
+    -> unit_index (M,) int32, the row of a point's unit or -1; word 7 (the units)."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
+    M, ld = scan.shape
+    x0, y0, z0 = (float(v) for v in origin)
+    unit_index = torch.empty(M, device=scan.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_obj_sort(_p(scan), ld, M, *_obj_labels_args(scan, labels, ignore), x0, y0, z0, float(voxel),
+                                              *(int(n) for n in grid), int(n_labels), int(n_points), _p(unit_index), _p(ws),
+                                              ws.numel(), _st()))
+    return unit_index
+
+
+def scene_obj_union(M, grid, n_labels, n_units, connectivity, ws):
+    """The union-find over the units of one class in neighbouring cells, in ws."""
+    assert _seg_ws_ok(ws)
+    _lib.check(_lib.load().r3d_scene_obj_union(M, *(int(n) for n in grid), int(n_labels), int(n_units), int(connectivity), _p(ws),
+                                               ws.numel(), _st()))
+
+
+def scene_obj_components(M, n_units, min_points, ws):
+    """Roots, points per root, kept roots and their scan, in ws -> words 8 (components), 9 (S) and 11 (error)."""
+    assert _seg_ws_ok(ws)
+    _lib.check(_lib.load().r3d_scene_obj_components(M, int(n_units), int(min(min_points, 2 ** 31 - 1)), _p(ws), ws.numel(), _st()))
+
+
+def scene_obj_stats(scan, origin, voxel, grid, n_labels, n_units, n_objects, ws):
+    """After the read of S >= 1: the object table -> (object_labels (S,) int64, object_points (S,) int32, object_units (S,)
+    int32, object_lo, object_hi, object_centroid (S, 3) fp32)."""
+    assert _grow_scan_ok(scan) and _seg_ws_ok(ws) and n_objects >= 1
+    M, ld = scan.shape
+    S, dev = int(n_objects), scan.device
+    x0, y0, z0 = (float(v) for v in origin)
+    labels = torch.empty(S, device=dev, dtype=torch.int64)
+    points, units = (torch.empty(S, device=dev, dtype=torch.int32) for _ in range(2))
+    lo, hi, centroid = (torch.empty(S, 3, device=dev, dtype=torch.float32) for _ in range(3))
+    sums = torch.empty(S, 3, device=dev, dtype=torch.int64)  # the kernels' scratch
+    _lib.check(_lib.load().r3d_scene_obj_stats(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid), int(n_labels),
+                                               int(n_units), S, _p(labels), _p(points), _p(units), _p(lo), _p(hi), _p(centroid),
+                                               _p(sums), _p(ws), ws.numel(), _st()))
+    return labels, points, units, lo, hi, centroid
+
+
+def scene_obj_ids(unit_index, n_units, n_objects, ws):
+    """After the read of S -> objects (M,) int32; word 10 (points of dropped components)."""
+    assert _seg_ws_ok(ws) and unit_index.dtype == torch.int32 and unit_index.is_contiguous() and unit_index.is_cuda
+    M = unit_index.numel()
+    objects = torch.empty(M, device=unit_index.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_obj_ids(M, int(n_units), int(n_objects), _p(unit_index), _p(objects), _p(ws), ws.numel(),
+                                             _st()))
+    return objects
+
+
 # ---------------------------------------------------------------------------------------------- cutting episodes (block_pool.py)
 def _episode_cut_args(points, labels, offsets, desc, classes, S, Q, N, out, mask, gt_mask, query_y, gt_query_y, slot_map):
     E, n_way = classes.shape
