@@ -1,8 +1,10 @@
 // What the growers share: scene_grow.hip (build_segments: a unit is a voxel) and scene_objects.hip (extract_objects: a unit
 // is a voxel's points of one class) both sort (key, scan index) pairs, cut the sorted keys into rows of a unit table, unite
 // neighbouring rows in parent[] and number the kept components.  Here: the record and the workspace they agree on, the
-// union-find on integer atomics, and the launchers of the kernels of scene_grow.hip that scene_objects.hip needs as well (a
-// kernel is launched only from the file that defines it).
+// argument checks, the grid and its cell key, the two walks over a row's neighbours in the table (all 27 cells, and the
+// forward half), the loop that sends one set of atomics per wave and key, the union-find on integer atomics, and the
+// launchers of the kernels of scene_grow.hip that scene_objects.hip needs as well (a kernel is launched only from the file
+// that defines it).
 #pragma once
 #include "scene_common.h"
 
@@ -64,6 +66,127 @@ static inline gr_view gr_make_view(long M, long key_max, const int32_t* ws) {
   return v;
 }
 
+// ---- the argument checks of the entry points
+// the workspace pointer, the scan's size and the grid, whose cells the caller calls `noun` ("voxels", "cells")
+static inline int gr_check_grid(const char* name, long M, int nx, int ny, int nz, const char* noun, const int32_t* ws) {
+  R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
+  SC_TRY(sc_check_points(name, M));
+  R3D_REQUIRE(nx >= 1 && nx <= GR_AXIS_MAX && ny >= 1 && ny <= GR_AXIS_MAX && nz >= 1 && nz <= GR_AXIS_MAX,
+              "%s: %d x %d x %d %s (1 .. 1024 per axis)", name, nx, ny, nz, noun);
+  return R3D_OK;
+}
+
+static inline int gr_check_origin(const char* name, float x0, float y0, float z0, float voxel) {
+  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY, "%s: origin (%g, %g, %g), voxel size %g", name,
+              (double)x0, (double)y0, (double)z0, (double)voxel);
+  return R3D_OK;
+}
+
+// the rows of the unit table as read from the record: 1 .. M `noun` ("voxels", "units")
+static inline int gr_check_rows(const char* name, long M, long n_rows, const char* noun) {
+  R3D_REQUIRE(n_rows >= 1 && n_rows <= M, "%s: %ld %s of %ld points", name, n_rows, noun, M);
+  return R3D_OK;
+}
+
+static inline int gr_check_connectivity(const char* name, int connectivity) {
+  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "%s: connectivity %d (6 or 26)", name, connectivity);
+  return R3D_OK;
+}
+
+// ---- the grid (G2, O3) and the walks over the rows of the unit table, which is sorted by key
+struct gr_grid {
+  float x0, y0, z0, s;
+  int nx, ny, nz;
+};
+
+// the key of the cell of a finite point: x runs fastest
+static __device__ __forceinline__ int gr_cell_key(const gr_grid& g, float x, float y, float z) {
+  return (sc_cell(z, g.z0, g.s, g.nz) * g.ny + sc_cell(y, g.y0, g.s, g.ny)) * g.nx + sc_cell(x, g.x0, g.s, g.nx);
+}
+
+// The rows of the occupied cells among the 27 around row v's (its own included): hit(r, d, row) for the cell at dy = r % 3 - 1,
+// dz = r / 3 - 1, dx = d - 1, in ascending key order; skip(dy, dz) leaves a (dz, dy) row of the grid out.  The three
+// x-neighbours of one (dz, dy) row have consecutive keys: one binary search finds the first candidate row of the table (v's
+// own row of the grid needs none), the next two are checked by key, and an x outside the grid is never looked up, so a key
+// that belongs to the neighbouring row of the grid is no neighbour.  Both loops are unrolled: r and d are compile-time
+// constants in hit, so what it indexes by them stays in registers.
+template <class Skip, class Hit>
+static __device__ __forceinline__ void gr_around(int v, int V, int nx, int ny, int nz, const int* __restrict__ vkey, Skip skip,
+                                                 Hit hit) {
+  const int key = vkey[v];
+  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int dy = r % 3 - 1, dz = r / 3 - 1;
+    const int jy = iy + dy, jz = iz + dz;
+    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    if (skip(dy, dz)) continue;
+    const int base = (jz * ny + jy) * nx;
+    const int first = base + (ix > 0 ? ix - 1 : 0);
+    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
+    if (r == 4) {
+      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
+    } else {
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int jx = ix + d - 1;
+      if (jx < 0 || jx >= nx) continue;
+      if (lo < V && vkey[lo] == base + jx) {
+        hit(r, d, lo);
+        ++lo;
+      }
+    }
+  }
+}
+
+// The forward half of the neighbourhood of row a, whose cell is (ix, iy, iz) and whose key is base + that cell's (the offsets
+// whose cell key is larger: 3 of 6, 13 of 26): join(row) for every occupied neighbour.  The caller decodes the cell, in
+// front of its other loads (decoded here, behind them, the grow union measured 2 % longer).  The neighbour's coordinates are
+// checked against the grid BEFORE its key
+// is formed from `base` (extract_objects: a's class times the cells; build_segments: 0), so the last cell of one class and
+// the first of the next, whose keys are consecutive, are never neighbours; the key is looked up by binary search among the
+// rows behind a.
+template <class Join>
+static __device__ __forceinline__ void gr_ahead(int a, int V, int nx, int ny, int nz, int conn, int ix, int iy, int iz, int base,
+                                                const int* __restrict__ vkey, Join join) {
+  for (int o = 14; o < 27; ++o) {  // (dz, dy, dx) in lexicographic order behind (0, 0, 0)
+    const int dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1;
+    if (conn == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1) continue;
+    const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
+    if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
+    const int want = base + (jz * ny + jy) * nx + jx;
+    int lo = a + 1, hi = V;  // the first row in (a, V) whose key is not below `want`
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (vkey[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    if (lo < V && vkey[lo] == want) join(lo);
+  }
+}
+
+// One round per distinct key among the live lanes of a wave (neighbouring rows mostly share one): body(key0, mine, is_leader)
+// with mine = this lane is live and holds key0, is_leader = it is the first such lane.  The lanes that share a key combine
+// their values by shuffles in the body and the leader sends one set of atomics: not one per row (profiles/r22_scene_grow.md:
+// 7.5 ms at 10^6 points for one atomic per voxel onto the root of a component that holds most of the scan).  The loop and
+// the body's shuffles are wave-uniform: every lane of the wave must get here, so no caller returns early in front of it.
+template <class Body>
+static __device__ __forceinline__ void gr_per_key(bool live, int key, Body body) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(live);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int key0 = __shfl(key, leader);
+    const bool mine = live && key == key0;
+    body(key0, mine, lane == leader);
+    todo &= ~__ballot(mine);
+  }
+}
+
 // ---- the union-find (G4, G5; O5)
 // parent[] is changed inside a union launch by agent-scope atomics only and read by relaxed agent-scope atomic loads: the
 // L2s of the XCDs are not coherent for plain accesses within a launch.  Invariants: parent[v] <= v, and a voxel that is
@@ -113,6 +236,11 @@ static __device__ __forceinline__ void gr_unite(int* __restrict__ parent, int a,
 // in front), their exclusive scan in place, its total (the rows) into rec[GR_R_V]
 R3D_INTERNAL void gr_launch_heads(const int* skey, long M, int key_limit, int* heads, int32_t* ws, const gr_layout& L,
                                   hipStream_t st);
+// after gr_launch_heads: the unit table (vkey: the keys in ascending order, vstart: a unit's first sorted position; row
+// heads[M] of vstart is n_in, the points that lie in a unit: they are sorted first) and index[p] = the row of scan point
+// p's unit, -1 for a point in none
+R3D_INTERNAL void gr_launch_table(const int* skey, const int* order, long M, int key_limit, long n_in, const int* heads,
+                                  int32_t* index, int32_t* ws, const gr_layout& L, hipStream_t st);
 // parent[v] = v
 R3D_INTERNAL void gr_launch_init(int V, int32_t* ws, const gr_layout& L, hipStream_t st);
 // root[], the points per root, the kept roots and their scan: words GR_R_NCOMP, GR_R_S (and GR_R_ERROR) of the record

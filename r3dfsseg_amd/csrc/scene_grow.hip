@@ -20,9 +20,11 @@
 //   ids         the kept components numbered in ascending root order, spread to the points   -> the counts (read 4)
 // The union-find holds integers only and the component of a voxel depends on the graph alone: whichever thread hooks
 // first, the root of a component ends as its smallest row.  Floats are added by __fadd_rn in the stated order.
-// scene_objects.hip grows the units of a labelled scan the same way: the heads, init, components and ids launches below are
-// gr_launch_* (scene_components.h), called here by the entry points and there by r3d_scene_obj_*.
-#include "scene_components.h"  // the record, the workspace and the union-find, shared with scene_objects.hip
+// scene_objects.hip grows the units of a labelled scan the same way: the heads, table, init, components and ids launches
+// below are gr_launch_* (scene_components.h), called here by the entry points and there by r3d_scene_obj_*.  The walks over
+// a voxel's neighbours (gr_around, gr_ahead), the per-key loop of a wave (gr_per_key), the cell key and the argument checks
+// are defined there too, once.
+#include "scene_components.h"
 
 #define GR_RINGS_MAX 64   // rounds of absorb
 
@@ -30,10 +32,7 @@ extern "C" long r3d_scene_grow_ws_words(long M) { return M > 0 && M <= SC_MAX_PO
 
 // what every entry point after the bounds has: the scan's size, the grid and the workspace
 static int gr_check(const char* name, long M, int nx, int ny, int nz, const int32_t* ws, long ws_words) {
-  R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
-  SC_TRY(sc_check_points(name, M));
-  R3D_REQUIRE(nx >= 1 && nx <= GR_AXIS_MAX && ny >= 1 && ny <= GR_AXIS_MAX && nz >= 1 && nz <= GR_AXIS_MAX,
-              "%s: %d x %d x %d voxels (1 .. 1024 per axis)", name, nx, ny, nz);
+  SC_TRY(gr_check_grid(name, M, nx, ny, nz, "voxels", ws));
   return sc_check_ws(name, ws_words, r3d_scene_grow_ws_words(M));
 }
 
@@ -49,11 +48,6 @@ extern "C" int r3d_scene_grow_bounds(const float* scan, int ld, long M, int32_t*
 }
 
 // ---- sort: keys (G2), the sort, the voxel heads and their scan
-struct gr_grid {
-  float x0, y0, z0, s;
-  int nx, ny, nz;
-};
-
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_keys_kernel(const float* __restrict__ scan, int ld, int M, gr_grid g,
                                                                          int* __restrict__ key, int* __restrict__ idx) {
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_keys_kernel(const f
   const float* p = scan + (long)i * ld;
   const float x = p[0], y = p[1], z = p[2];
   int k = g.nx * g.ny * g.nz;  // invalid points sort behind every voxel
-  if (sc_finite3(x, y, z)) k = (sc_cell(z, g.z0, g.s, g.nz) * g.ny + sc_cell(y, g.y0, g.s, g.ny)) * g.nx + sc_cell(x, g.x0, g.s, g.nx);
+  if (sc_finite3(x, y, z)) k = gr_cell_key(g, x, y, z);
   key[i] = k;
   idx[i] = i;
 }
@@ -92,8 +86,7 @@ extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, 
   R3D_REQUIRE(scan, "r3d_scene_grow_sort: null pointer (scan)");
   SC_TRY(sc_check_ld("r3d_scene_grow_sort", ld));
   SC_TRY(gr_check("r3d_scene_grow_sort", M, nx, ny, nz, ws, ws_words));
-  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
-              "r3d_scene_grow_sort: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
+  SC_TRY(gr_check_origin("r3d_scene_grow_sort", x0, y0, z0, voxel));
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int n_cells = nx * ny * nz;
@@ -107,26 +100,34 @@ extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, 
 }
 
 // ---- voxels: the table (G3)
-// after the scan: heads[i] = voxels opened in front of i.  A voxel's row is written by the thread of its first sorted
-// position, row V of vstart by the thread of position M.
+// After the scan: heads[i] = rows opened in front of sorted position i, heads[M] = V (r3d_scene_obj_sort has no host read
+// between the scan and this launch, so V is read here).  A row is written by the thread of its first sorted position, row
+// V of vstart by the thread of position M: the points that lie in a row are the first n_in of the sorted order.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_table_kernel(const int* __restrict__ skey, const int* __restrict__ order,
-                                                                          int M, int n_cells, int V, int n_valid,
+                                                                          int M, int key_limit, int n_in,
                                                                           const int* __restrict__ heads, int* __restrict__ vkey,
-                                                                          int* __restrict__ vstart, int* __restrict__ voxel_index) {
+                                                                          int* __restrict__ vstart, int* __restrict__ index) {
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
   if (i > M) return;
+  const int V = sc_clamp(heads[M], 0, M);
   if (i == M) {
-    vstart[V] = n_valid;
+    vstart[V] = n_in;
     return;
   }
   const int k = skey[i], v = heads[i + 1] - 1;
-  const bool in = k >= 0 && k < n_cells && v >= 0 && v < V;
+  const bool in = k >= 0 && k < key_limit && v >= 0 && v < V;
   const int p = sc_clamp(order[i], 0, M - 1);
-  voxel_index[p] = in ? v : -1;
+  index[p] = in ? v : -1;
   if (in && heads[i + 1] != heads[i]) {
     vkey[v] = k;
     vstart[v] = i;
   }
+}
+
+void gr_launch_table(const int* skey, const int* order, long M, int key_limit, long n_in, const int* heads, int32_t* index,
+                     int32_t* ws, const gr_layout& L, hipStream_t st) {
+  hipLaunchKernelGGL(r3d_scene_grow_table_kernel, dim3(sc_grid_of(M + 1)), dim3(SC_THREADS), 0, st, skey, order, (int)M, key_limit,
+                     (int)n_in, heads, ws + L.vkey, ws + L.vstart, index);
 }
 
 // One thread per voxel: its points in sorted order (ascending scan index: the sort is stable), three values per point
@@ -177,9 +178,7 @@ extern "C" int r3d_scene_grow_voxels(const float* scan, int ld, long M, int nx, 
   R3D_REQUIRE(!colour || ld >= 6, "r3d_scene_grow_voxels: a scan row of %d floats has no colour", ld);
   const hipStream_t st = (hipStream_t)stream;
   const gr_view v = gr_make_view(M, (long)nx * ny * nz, ws);
-  const int gm1 = sc_grid_of(M + 1);
-  hipLaunchKernelGGL(r3d_scene_grow_table_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, v.skey, v.order, (int)M, nx * ny * nz,
-                     (int)n_voxels, (int)n_valid, v.heads, ws + v.L.vkey, ws + v.L.vstart, voxel_index);
+  gr_launch_table(v.skey, v.order, M, nx * ny * nz, n_valid, v.heads, voxel_index, ws, v.L, st);  // heads[M] is n_voxels
   if (colour && n_voxels > 0)
     hipLaunchKernelGGL(r3d_scene_grow_mean_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0, st,
                        scan, ld, (int)M, (int)n_voxels, v.order, ws + v.L.vstart, voxel_mean);
@@ -214,9 +213,8 @@ extern "C" int r3d_scene_grow_centroids(const float* scan, int ld, long M, float
               (void*)voxel_centroid);
   SC_TRY(sc_check_ld("r3d_scene_grow_centroids", ld));
   SC_TRY(gr_check("r3d_scene_grow_centroids", M, nx, ny, nz, ws, ws_words));
-  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY,
-              "r3d_scene_grow_centroids: origin (%g, %g, %g), voxel size %g", (double)x0, (double)y0, (double)z0, (double)voxel);
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_centroids: %ld voxels of %ld points", n_voxels, M);
+  SC_TRY(gr_check_origin("r3d_scene_grow_centroids", x0, y0, z0, voxel));
+  SC_TRY(gr_check_rows("r3d_scene_grow_centroids", M, n_voxels, "voxels"));
   const gr_view v = gr_make_view(M, (long)nx * ny * nz, ws);
   const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
   hipLaunchKernelGGL(r3d_scene_grow_centroid_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0,
@@ -236,48 +234,23 @@ static __device__ __forceinline__ void gr_q(int o, float s, const float* __restr
   q[2] = __fadd_rn(__fmul_rn((float)(o / 9 - 1), s), c[2]);
 }
 
-// One thread per voxel.  The three x-neighbours of one (dz, dy) row have consecutive keys: one binary search finds the
-// first candidate row of the table, the next two are checked by key, and an x outside the grid is never looked up, so a
-// key that belongs to the neighbouring row of the grid is no neighbour.  The 27 rows stay in registers (every loop over
-// them is unrolled, no index is a run-time value); the centroids are gathered once for the mean and once more for the
-// second moments.
+// One thread per voxel.  The rows of the occupied voxels among the 27 around it come from gr_around and stay in registers
+// (every loop over them is unrolled, no index is a run-time value); the centroids are gathered once for the mean and once
+// more for the second moments.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_normals_kernel(int V, int nx, int ny, int nz, float s,
                                                                             const int* __restrict__ vkey,
                                                                             const float* __restrict__ centroid,
                                                                             float* __restrict__ normal, int* __restrict__ support) {
   const int v = blockIdx.x * SC_THREADS + threadIdx.x;
   if (v >= V) return;
-  const int key = vkey[v];
-  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
   int nb[27];
   int k = 0;
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int jy = iy + r % 3 - 1, jz = iz + r / 3 - 1;
-    nb[3 * r] = nb[3 * r + 1] = nb[3 * r + 2] = -1;
-    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
-    const int base = (jz * ny + jy) * nx;
-    const int first = base + (ix > 0 ? ix - 1 : 0);
-    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
-    if (r == 4) {
-      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
-    } else {
-      while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const int jx = ix + d - 1;
-      if (jx < 0 || jx >= nx) continue;
-      if (lo < V && vkey[lo] == base + jx) {
-        nb[3 * r + d] = lo;
-        ++lo;
-        ++k;
-      }
-    }
-  }
+  for (int o = 0; o < 27; ++o) nb[o] = -1;
+  gr_around(v, V, nx, ny, nz, vkey, [](int, int) { return false; }, [&](int r, int d, int row) {
+    nb[3 * r + d] = row;
+    ++k;
+  });
   float m[3] = {0.0f, 0.0f, 0.0f};
   bool first = true;
 #pragma unroll
@@ -351,7 +324,7 @@ extern "C" int r3d_scene_grow_normals(long M, int nx, int ny, int nz, long n_vox
               (const void*)voxel_centroid, (void*)voxel_normal, (void*)voxel_support);
   SC_TRY(gr_check("r3d_scene_grow_normals", M, nx, ny, nz, ws, ws_words));
   R3D_REQUIRE(voxel > 0.0f && voxel < INFINITY, "r3d_scene_grow_normals: voxel size %g", (double)voxel);
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_normals: %ld voxels of %ld points", n_voxels, M);
+  SC_TRY(gr_check_rows("r3d_scene_grow_normals", M, n_voxels, "voxels"));
   const gr_layout L = gr_make_layout(M);
   hipLaunchKernelGGL(r3d_scene_grow_normals_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0,
                      (hipStream_t)stream, (int)n_voxels, nx, ny, nz, voxel, ws + L.vkey, voxel_centroid, voxel_normal,
@@ -372,10 +345,9 @@ void gr_launch_init(int V, int32_t* ws, const gr_layout& L, hipStream_t st) {
   hipLaunchKernelGGL(r3d_scene_grow_init_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V, ws + L.parent);
 }
 
-// One thread per voxel a, the forward half of the neighbourhood (the offsets whose key is larger): 3 of 6, 13 of 26.  The
-// neighbour's coordinates are checked against the grid, its key is looked up by binary search among the rows behind a.
-// NORMALS (r3d_scene_grow_union_normals): a pair is joined only when dot^2 >= (cos2 la) lb as well, la and lb the squared
-// lengths of the two normal rows; a NaN in either row makes the comparison false.
+// One thread per voxel a and the occupied voxels of the forward half of its neighbourhood (gr_ahead).  NORMALS
+// (r3d_scene_grow_union_normals): a pair is joined only when dot^2 >= (cos2 la) lb as well, la and lb the squared lengths of
+// the two normal rows; a NaN in either row makes the comparison false.
 static __device__ __forceinline__ float gr_dot3(const float* x, const float* y) {
   return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
 }
@@ -401,39 +373,28 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_union_kernel(int V,
 #pragma unroll
     for (int j = 0; j < 3; ++j) ma[j] = mean[3L * a + j];
   }
-  for (int o = 14; o < 27; ++o) {  // (dz, dy, dx) in lexicographic order behind (0, 0, 0)
-    const int dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1;
-    if (conn == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1) continue;
-    const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
-    if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
-    const int want = (jz * ny + jy) * nx + jx;
-    int lo = a + 1, hi = V;  // the first row in (a, V) whose key is not below `want`
-    while (lo < hi) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (vkey[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= V || vkey[lo] != want) continue;
+  gr_ahead(a, V, nx, ny, nz, conn, ix, iy, iz, 0, vkey, [&](int b) {
     if (use_colour) {
       bool alike = true;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) alike = alike && fabsf(__fsub_rn(ma[j], mean[3L * lo + j])) <= tol;  // a NaN joins nothing
-      if (!alike) continue;
+      for (int j = 0; j < 3; ++j) alike = alike && fabsf(__fsub_rn(ma[j], mean[3L * b + j])) <= tol;  // a NaN joins nothing
+      if (!alike) return;
     }
     if (NORMALS) {
-      const float nb[3] = {normal[3L * lo], normal[3L * lo + 1], normal[3L * lo + 2]};
+      const float nb[3] = {normal[3L * b], normal[3L * b + 1], normal[3L * b + 2]};
       const float dot = gr_dot3(na, nb);
-      if (!(__fmul_rn(dot, dot) >= __fmul_rn(la, gr_dot3(nb, nb)))) continue;
+      if (!(__fmul_rn(dot, dot) >= __fmul_rn(la, gr_dot3(nb, nb)))) return;
     }
-    gr_unite(parent, a, lo, V, err);
-  }
+    gr_unite(parent, a, b, V, err);
+  });
 }
 
 static int gr_union(const char* name, long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
                     float colour_tol, const float* voxel_normal, float cos2, int32_t* ws, long ws_words, void* stream) {
   const bool colour = voxel_mean != nullptr;
   SC_TRY(gr_check(name, M, nx, ny, nz, ws, ws_words));
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "%s: %ld voxels of %ld points", name, n_voxels, M);
-  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "%s: connectivity %d (6 or 26)", name, connectivity);
+  SC_TRY(gr_check_rows(name, M, n_voxels, "voxels"));
+  SC_TRY(gr_check_connectivity(name, connectivity));
   R3D_REQUIRE(!colour || (colour_tol >= 0.0f && colour_tol < INFINITY), "%s: colour_tol %g (finite, >= 0)", name,
               (double)colour_tol);
   const hipStream_t st = (hipStream_t)stream;
@@ -477,9 +438,18 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_flatten_kernel(int 
   root[v] = r < 0 ? v : r;  // (an overrun: an index inside the tables; the host raises on the error word)
 }
 
-// points per root: integer atomics, order-independent.  The lanes of a wave that share a root add their counts first and
-// send one atomic: neighbouring rows mostly share a root, and one atomic per voxel onto the root of a component that
-// holds most of the scan took 7.5 ms at 10^6 points (profiles/r22_scene_grow.md).
+// cnt[r] += n over the live lanes: integer atomics, order-independent.  The lanes of a wave that share r add their n first
+// and send one atomic (gr_per_key: every lane of the wave calls this).
+static __device__ __forceinline__ void gr_add_points(bool live, int r, int n, int* __restrict__ cnt) {
+  gr_per_key(live, r, [&](int r0, bool mine, bool is_leader) {
+    int sum = mine ? n : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (is_leader) atomicAdd(cnt + r0, sum);
+  });
+}
+
+// points per root
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_count_kernel(int V, int M, const int* __restrict__ root,
                                                                           const int* __restrict__ vstart, int* __restrict__ cnt) {
   const int v = blockIdx.x * SC_THREADS + threadIdx.x;
@@ -490,18 +460,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_count_kernel(int V,
     r = sc_clamp(root[v], 0, V - 1);
     n = b - a;
   }
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(live);
-  while (todo) {  // (uniform) one round per distinct root of the wave
-    const int leader = __ffsll((long long)todo) - 1;
-    const int r0 = __shfl(r, leader);
-    const bool mine = live && r == r0;
-    int sum = mine ? n : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == leader) atomicAdd(cnt + r0, sum);
-    todo &= ~__ballot(mine);
-  }
+  gr_add_points(live, r, n, cnt);
 }
 
 // row v: kept[v] = it is the root of a component with at least min_points points; word V is 0 for the scan's total
@@ -533,7 +492,7 @@ void gr_launch_components(long M, int V, int min_points, int32_t* ws, const gr_l
 
 extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream) {
   SC_TRY(gr_check("r3d_scene_grow_components", M, 1, 1, 1, ws, ws_words));
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_components: %ld voxels of %ld points", n_voxels, M);
+  SC_TRY(gr_check_rows("r3d_scene_grow_components", M, n_voxels, "voxels"));
   R3D_REQUIRE(min_points >= 1, "r3d_scene_grow_components: min_points %d (at least 1)", min_points);
   gr_launch_components(M, (int)n_voxels, min_points, ws, gr_make_layout(M), (hipStream_t)stream);
   R3D_LAUNCH_CHECK("r3d_scene_grow_components");
@@ -559,11 +518,11 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_start_kernel
 }
 
 // One thread per voxel.  A voxel that has an owner copies it.  A free one looks its neighbours up as the normals kernel
-// does (per (dz, dy) one binary search for the first x-neighbour inside the grid, the next rows of the table checked by
-// key; an x outside the grid is never looked up), keeps the owners of those the connectivity allows in registers (every
-// loop over them is unrolled), and takes the owner most of them have, the smallest on a tie.  Its own row is free, so it
-// never counts.  The unrolled 27 x 27 tally takes 206 VGPRs; rolled over candidates picked by selects it takes 44 and the
-// absorb span was 5 to 15 % longer (profiles/r25_scene_grow_absorb.md): a ring is bound by the free lanes' latency.
+// does (gr_around; with connectivity 6 the (dz, dy) rows of the grid that hold no face neighbour are not searched), keeps
+// the owners of those the connectivity allows in registers (every loop over them is unrolled), and takes the owner most of
+// them have, the smallest on a tie.  Its own row is free, so it never counts.  The unrolled 27 x 27 tally takes 206 VGPRs;
+// rolled over candidates picked by selects it takes 44 and the absorb span was 5 to 15 % longer
+// (profiles/r25_scene_grow_absorb.md): a ring is bound by the free lanes' latency.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_round_kernel(int V, int nx, int ny, int nz, int conn, int round,
                                                                                  const int* __restrict__ vkey,
                                                                                  const int* __restrict__ src, int* __restrict__ dst,
@@ -575,37 +534,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_round_kernel
     dst[v] = mine;
     return;
   }
-  const int key = vkey[v];
-  const int ix = key % nx, iy = (key / nx) % ny, iz = key / (nx * ny);
   int own[27];
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const int dy = r % 3 - 1, dz = r / 3 - 1;
-    const int jy = iy + dy, jz = iz + dz;
-    own[3 * r] = own[3 * r + 1] = own[3 * r + 2] = -1;
-    if (jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
-    if (conn == 6 && dy != 0 && dz != 0) continue;
-    const int base = (jz * ny + jy) * nx;
-    const int first = base + (ix > 0 ? ix - 1 : 0);
-    int lo = r < 4 ? 0 : v, hi = r < 4 ? v : V;  // rows in front of v hold smaller keys, rows behind it larger ones
-    if (r == 4) {
-      lo = v > 0 && vkey[v - 1] == first ? v - 1 : v;  // v's own row of the grid: no search
-    } else {
-      while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (vkey[mid] < first) lo = mid + 1; else hi = mid;
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const int jx = ix + d - 1;
-      if (jx < 0 || jx >= nx) continue;
-      if (lo < V && vkey[lo] == base + jx) {
-        if (conn != 6 || (d != 1) + (dy != 0) + (dz != 0) == 1) own[3 * r + d] = sc_clamp(src[lo], -1, V - 1);
-        ++lo;
-      }
-    }
-  }
+  for (int o = 0; o < 27; ++o) own[o] = -1;
+  gr_around(v, V, nx, ny, nz, vkey, [&](int dy, int dz) { return conn == 6 && dy != 0 && dz != 0; }, [&](int r, int d, int row) {
+    if (conn != 6 || (d != 1) + (r % 3 != 1) + (r / 3 != 1) == 1) own[3 * r + d] = sc_clamp(src[row], -1, V - 1);
+  });
   int best = -1, best_n = 0;
 #pragma unroll
   for (int i = 0; i < 27; ++i) {
@@ -637,18 +571,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_end_kernel(i
     n = b - a;
     root[v] = r;
   }
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(live);
-  while (todo) {  // (uniform) one round per distinct owner of the wave
-    const int leader = __ffsll((long long)todo) - 1;
-    const int r0 = __shfl(r, leader);
-    const bool mine = live && r == r0;
-    int sum = mine ? n : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if (lane == leader) atomicAdd(cnt + r0, sum);
-    todo &= ~__ballot(mine);
-  }
+  gr_add_points(live, r, n, cnt);
   const int voxels = sc_block_count(live ? 1 : 0, red), points = sc_block_count(n, red);
   if (threadIdx.x == 0 && voxels > 0) {
     atomicAdd(rec + GR_R_ABSORBED_VOXELS, voxels);  // integer counts: order-independent
@@ -660,8 +583,8 @@ extern "C" int r3d_scene_grow_absorb(long M, int nx, int ny, int nz, long n_voxe
                                      int32_t* voxel_ring, int32_t* ws, long ws_words, void* stream) {
   R3D_REQUIRE(voxel_ring, "r3d_scene_grow_absorb: null pointer (voxel_ring)");
   SC_TRY(gr_check("r3d_scene_grow_absorb", M, nx, ny, nz, ws, ws_words));
-  R3D_REQUIRE(n_voxels >= 1 && n_voxels <= M, "r3d_scene_grow_absorb: %ld voxels of %ld points", n_voxels, M);
-  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "r3d_scene_grow_absorb: connectivity %d (6 or 26)", connectivity);
+  SC_TRY(gr_check_rows("r3d_scene_grow_absorb", M, n_voxels, "voxels"));
+  SC_TRY(gr_check_connectivity("r3d_scene_grow_absorb", connectivity));
   R3D_REQUIRE(rings >= 1 && rings <= GR_RINGS_MAX, "r3d_scene_grow_absorb: %d rings (1 .. %d)", rings, GR_RINGS_MAX);
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);

@@ -6,9 +6,11 @@
 //   bounds      the bounds of scene_sort.hip over the finite points, then the labels of those points: the largest
 //               participating label, the points left out by their label, labels that fit no key     -> the record (read 1)
 //   sort        keys label * n_cells + cell, the stable radix sort of scene_sort.hip on (key, scan index), unit heads as
-//               flags, their scan, the unit table and the unit of every point                        -> U (read 2)
-//   union       one thread per unit and the forward half of its neighbourhood: the neighbour's cell is checked against
-//               the grid, its key (same class) found by binary search; joined pairs united by gr_unite
+//               flags, their scan, the unit table and the unit of every point (the heads and table launches of
+//               build_segments)                                                                      -> U (read 2)
+//   union       one thread per unit and the forward half of its neighbourhood (gr_ahead, the walk of build_segments, with
+//               the class base of the unit's key): the neighbour's cell is checked against the grid, its key (same class)
+//               found by binary search; joined pairs united by gr_unite
 //   components  the launches of build_segments: roots, points per root, kept roots, their scan       -> components, S (read 3)
 //   stats       per unit the minima, maxima and sub-voxel sums of its points; the units of a wave that share an object are
 //               combined by shuffles and sent as one set of integer atomics per wave and object; then per object the box
@@ -30,16 +32,8 @@
 
 extern "C" long r3d_scene_obj_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? gr_make_layout(M).total : -1; }
 
-struct ob_grid {
-  float x0, y0, z0, s;
-  int nx, ny, nz, n_labels;
-};
-
 static int ob_check(const char* name, long M, int nx, int ny, int nz, long n_labels, const int32_t* ws, long ws_words) {
-  R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
-  SC_TRY(sc_check_points(name, M));
-  R3D_REQUIRE(nx >= 1 && nx <= GR_AXIS_MAX && ny >= 1 && ny <= GR_AXIS_MAX && nz >= 1 && nz <= GR_AXIS_MAX,
-              "%s: %d x %d x %d cells (1 .. 1024 per axis)", name, nx, ny, nz);
+  SC_TRY(gr_check_grid(name, M, nx, ny, nz, "cells", ws));
   R3D_REQUIRE(n_labels >= 1 && n_labels * ((long)nx * ny * nz) <= OB_KEY_MAX, "%s: %ld labels times %ld cells (at most 2^31 - 1)",
               name, n_labels, (long)nx * ny * nz);
   return sc_check_ws(name, ws_words, r3d_scene_obj_ws_words(M));
@@ -126,8 +120,8 @@ extern "C" int r3d_scene_obj_bounds(const float* scan, int ld, long M, const voi
 
 // ---- sort: keys (O3), the sort, the unit heads, their scan, the unit table
 template <class T>
-__global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_keys_kernel(const float* __restrict__ scan, int ld, int M, ob_grid g,
-                                                                       const T* __restrict__ labels,
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_keys_kernel(const float* __restrict__ scan, int ld, int M, gr_grid g,
+                                                                       int n_labels, const T* __restrict__ labels,
                                                                        const long long* __restrict__ ignore, int n_ignore,
                                                                        int* __restrict__ key, int* __restrict__ idx) {
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
@@ -135,44 +129,13 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_keys_kernel(const fl
   const float* p = scan + (long)i * ld;
   const float x = p[0], y = p[1], z = p[2];
   const int n_cells = g.nx * g.ny * g.nz;
-  int k = g.n_labels * n_cells;  // a point that takes no part sorts behind every unit
+  int k = n_labels * n_cells;  // a point that takes no part sorts behind every unit
   if (sc_finite3(x, y, z)) {
     const int c = ob_class(labels, i, ignore, n_ignore);
-    if (c >= 0 && c < g.n_labels)
-      k = c * n_cells + (sc_cell(z, g.z0, g.s, g.nz) * g.ny + sc_cell(y, g.y0, g.s, g.ny)) * g.nx + sc_cell(x, g.x0, g.s, g.nx);
+    if (c >= 0 && c < n_labels) k = c * n_cells + gr_cell_key(g, x, y, z);
   }
   key[i] = k;
   idx[i] = i;
-}
-
-// After the scan: heads[i] = units opened in front of sorted position i, heads[M] = U (no host read lies between the scan
-// and this launch, so U is read here).  A unit's row is written by the thread of its first sorted position, row U of
-// ustart by the thread of position M: the participating points are the first n_points of the sorted order.
-__global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_table_kernel(const int* __restrict__ skey, const int* __restrict__ order,
-                                                                        int M, int key_limit, int n_points,
-                                                                        const int* __restrict__ heads, int* __restrict__ ukey,
-                                                                        int* __restrict__ ustart, int* __restrict__ unit_index) {
-  const int i = blockIdx.x * SC_THREADS + threadIdx.x;
-  if (i > M) return;
-  const int U = sc_clamp(heads[M], 0, M);
-  if (i == M) {
-    ustart[U] = n_points;
-    return;
-  }
-  const int k = skey[i], u = heads[i + 1] - 1;
-  const bool in = k >= 0 && k < key_limit && u >= 0 && u < U;
-  const int p = sc_clamp(order[i], 0, M - 1);
-  unit_index[p] = in ? u : -1;
-  if (in && heads[i + 1] != heads[i]) {
-    ukey[u] = k;
-    ustart[u] = i;
-  }
-}
-
-static int ob_check_grid(const char* name, float x0, float y0, float z0, float voxel) {
-  R3D_REQUIRE(x0 == x0 && y0 == y0 && z0 == z0 && voxel > 0.0f && voxel < INFINITY, "%s: origin (%g, %g, %g), voxel size %g", name,
-              (double)x0, (double)y0, (double)z0, (double)voxel);
-  return R3D_OK;
 }
 
 extern "C" int r3d_scene_obj_sort(const float* scan, int ld, long M, const void* labels, int labels64, const int64_t* ignore,
@@ -182,33 +145,31 @@ extern "C" int r3d_scene_obj_sort(const float* scan, int ld, long M, const void*
   SC_TRY(sc_check_ld("r3d_scene_obj_sort", ld));
   SC_TRY(ob_check_labels("r3d_scene_obj_sort", labels, labels64, ignore, n_ignore));
   SC_TRY(ob_check("r3d_scene_obj_sort", M, nx, ny, nz, n_labels, ws, ws_words));
-  SC_TRY(ob_check_grid("r3d_scene_obj_sort", x0, y0, z0, voxel));
+  SC_TRY(gr_check_origin("r3d_scene_obj_sort", x0, y0, z0, voxel));
   R3D_REQUIRE(n_points >= 1 && n_points <= M, "r3d_scene_obj_sort: %ld participating points of %ld", n_points, M);
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int key_limit = n_labels * (nx * ny * nz);
-  const ob_grid g = {x0, y0, z0, voxel, nx, ny, nz, n_labels};
+  const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
   const dim3 grid(sc_grid_of(M)), block(SC_THREADS);
   if (labels64)
-    hipLaunchKernelGGL(r3d_scene_obj_keys_kernel<long long>, grid, block, 0, st, scan, ld, (int)M, g, (const long long*)labels,
-                       (const long long*)ignore, n_ignore, ws + L.sort.key[0], ws + L.sort.idx[0]);
+    hipLaunchKernelGGL(r3d_scene_obj_keys_kernel<long long>, grid, block, 0, st, scan, ld, (int)M, g, n_labels,
+                       (const long long*)labels, (const long long*)ignore, n_ignore, ws + L.sort.key[0], ws + L.sort.idx[0]);
   else
-    hipLaunchKernelGGL(r3d_scene_obj_keys_kernel<int>, grid, block, 0, st, scan, ld, (int)M, g, (const int*)labels,
+    hipLaunchKernelGGL(r3d_scene_obj_keys_kernel<int>, grid, block, 0, st, scan, ld, (int)M, g, n_labels, (const int*)labels,
                        (const long long*)ignore, n_ignore, ws + L.sort.key[0], ws + L.sort.idx[0]);
   const int sorted = sc_sort_pairs(ws, L.sort, M, sc_passes(key_limit), st);  // keys run 0 .. key_limit (key_limit: no part)
   int* heads = ws + L.sort.key[sorted ^ 1];
   gr_launch_heads(ws + L.sort.key[sorted], M, key_limit, heads, ws, L, st);
-  hipLaunchKernelGGL(r3d_scene_obj_table_kernel, dim3(sc_grid_of(M + 1)), block, 0, st, ws + L.sort.key[sorted],
-                     ws + L.sort.idx[sorted], (int)M, key_limit, (int)n_points, heads, ws + L.vkey, ws + L.vstart, unit_index);
+  gr_launch_table(ws + L.sort.key[sorted], ws + L.sort.idx[sorted], M, key_limit, n_points, heads, unit_index, ws, L, st);
   R3D_LAUNCH_CHECK("r3d_scene_obj_sort");
   return R3D_OK;
 }
 
 // ---- union (O4, O5)
-// One thread per unit a, the forward half of the neighbourhood (the offsets whose cell key is larger): 3 of 6, 13 of 26.  The
-// neighbour's coordinates are checked against the grid BEFORE its key is formed from a's own class, so the last cell of one
-// class and the first of the next, whose keys are consecutive, are never neighbours; the key is looked up by binary search
-// among the rows behind a.  parent[] only through gr_unite (agent-scope atomics, scene_components.h).
+// One thread per unit a and the units of its class in the forward half of its neighbourhood (gr_ahead with the class base
+// of a's key: the last cell of one class and the first of the next are never neighbours).  parent[] only through gr_unite
+// (agent-scope atomics, scene_components.h).
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_union_kernel(int U, int nx, int ny, int nz, int conn,
                                                                         const int* __restrict__ ukey, int* __restrict__ parent,
                                                                         int* __restrict__ err) {
@@ -218,32 +179,16 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_union_kernel(int U, 
   const int key = ukey[a];
   const int base = (key / n_cells) * n_cells, cell = key % n_cells;
   const int ix = cell % nx, iy = (cell / nx) % ny, iz = cell / (nx * ny);
-  for (int o = 14; o < 27; ++o) {  // (dz, dy, dx) in lexicographic order behind (0, 0, 0)
-    const int dx = o % 3 - 1, dy = (o / 3) % 3 - 1, dz = o / 9 - 1;
-    if (conn == 6 && (dx != 0) + (dy != 0) + (dz != 0) != 1) continue;
-    const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
-    if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || jz < 0 || jz >= nz) continue;
-    const int want = base + (jz * ny + jy) * nx + jx;
-    int lo = a + 1, hi = U;  // the first row in (a, U) whose key is not below `want`
-    while (lo < hi) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (ukey[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= U || ukey[lo] != want) continue;
-    gr_unite(parent, a, lo, U, err);
-  }
+  gr_ahead(a, U, nx, ny, nz, conn, ix, iy, iz, base, ukey, [&](int b) { gr_unite(parent, a, b, U, err); });
 }
 
-static int ob_check_units(const char* name, long M, long n_units) {
-  R3D_REQUIRE(n_units >= 1 && n_units <= M, "%s: %ld units of %ld points", name, n_units, M);
-  return R3D_OK;
-}
+static int ob_check_units(const char* name, long M, long n_units) { return gr_check_rows(name, M, n_units, "units"); }
 
 extern "C" int r3d_scene_obj_union(long M, int nx, int ny, int nz, int n_labels, long n_units, int connectivity, int32_t* ws,
                                    long ws_words, void* stream) {
   SC_TRY(ob_check("r3d_scene_obj_union", M, nx, ny, nz, n_labels, ws, ws_words));
   SC_TRY(ob_check_units("r3d_scene_obj_union", M, n_units));
-  R3D_REQUIRE(connectivity == 6 || connectivity == 26, "r3d_scene_obj_union: connectivity %d (6 or 26)", connectivity);
+  SC_TRY(gr_check_connectivity("r3d_scene_obj_union", connectivity));
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int U = (int)n_units;
@@ -289,7 +234,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_fill_kernel(int S, i
 // let alone per point (profiles/r22_scene_grow.md: 7.5 ms for one atomic per voxel onto the root of a component that holds
 // most of the scan).  Integers only, so the order does not matter.  The root's thread writes the object's class and points.
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_stats_kernel(const float* __restrict__ scan, int ld, int M, int U, int S,
-                                                                        ob_grid g, const int* __restrict__ order,
+                                                                        gr_grid g, const int* __restrict__ order,
                                                                         const int* __restrict__ ustart, const int* __restrict__ ukey,
                                                                         const int* __restrict__ root, const int* __restrict__ kept,
                                                                         const int* __restrict__ cnt, long long* __restrict__ labels,
@@ -326,12 +271,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_stats_kernel(const f
       }
     }
   }
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(live);
-  while (todo) {  // (uniform) one round per distinct object of the wave
-    const int leader = __ffsll((long long)todo) - 1;
-    const int s0 = __shfl(s, leader);
-    const bool mine = live && s == s0;
+  gr_per_key(live, s, [&](int s0, bool mine, bool is_leader) {  // one round per distinct object of the wave
     int rmn[3], rmx[3], n = mine ? 1 : 0;
     unsigned long long rsm[3];
 #pragma unroll
@@ -351,7 +291,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_stats_kernel(const f
       }
       n += __shfl_xor(n, o);
     }
-    if (lane == leader) {
+    if (is_leader) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         atomicMin(lo + 3L * s0 + j, rmn[j]);
@@ -360,13 +300,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_stats_kernel(const f
       }
       atomicAdd(units + s0, n);
     }
-    todo &= ~__ballot(mine);
-  }
+  });
 }
 
 // One thread per object: the box back from its images, in place, and the centroid (O8) in float64, v0 + voxel * ((sum / n) +
 // 0.5) / 256 in that order, every operation rounded on its own, rounded once to fp32.
-__global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_finish_kernel(int S, ob_grid g, const int* __restrict__ points,
+__global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_finish_kernel(int S, gr_grid g, const int* __restrict__ points,
                                                                          const long long* __restrict__ sums, int* __restrict__ lo,
                                                                          int* __restrict__ hi, float* __restrict__ centroid) {
   const int s = blockIdx.x * SC_THREADS + threadIdx.x;
@@ -392,12 +331,12 @@ extern "C" int r3d_scene_obj_stats(const float* scan, int ld, long M, float x0, 
               (void*)object_hi, (void*)object_centroid, (void*)object_sums);
   SC_TRY(sc_check_ld("r3d_scene_obj_stats", ld));
   SC_TRY(ob_check("r3d_scene_obj_stats", M, nx, ny, nz, n_labels, ws, ws_words));
-  SC_TRY(ob_check_grid("r3d_scene_obj_stats", x0, y0, z0, voxel));
+  SC_TRY(gr_check_origin("r3d_scene_obj_stats", x0, y0, z0, voxel));
   SC_TRY(ob_check_units("r3d_scene_obj_stats", M, n_units));
   R3D_REQUIRE(n_objects >= 1 && n_objects <= n_units, "r3d_scene_obj_stats: %ld objects of %ld units", n_objects, n_units);
   const hipStream_t st = (hipStream_t)stream;
   const gr_view v = gr_make_view(M, (long)n_labels * ((long)nx * ny * nz), ws);
-  const ob_grid g = {x0, y0, z0, voxel, nx, ny, nz, n_labels};
+  const gr_grid g = {x0, y0, z0, voxel, nx, ny, nz};
   const int U = (int)n_units, S = (int)n_objects;
   int *lo = (int*)object_lo, *hi = (int*)object_hi;  // integer images until the last launch
   hipLaunchKernelGGL(r3d_scene_obj_fill_kernel, dim3(sc_grid_of(S)), dim3(SC_THREADS), 0, st, S, lo, hi, (long long*)object_sums,

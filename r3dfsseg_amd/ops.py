@@ -912,12 +912,22 @@ SEG_R_MAX1, SEG_R_NNEG, SEG_R_NBAD, SEG_R_BADMAX, SEG_R_S, SEG_R_NCONTRIB, SEG_R
 SEG_R_NPOOLED, SEG_R_NFILLED, SEG_R_NUNLAB = 9, 10, 11
 
 
-def scene_seg_workspace(M, device):
-    """-> ws, int32 of r3d_scene_seg_ws_words(M) words: the one scratch of a pool_segments call, its record in front."""
-    words = _lib.load().r3d_scene_seg_ws_words(M)
+def _scene_workspace(what, name, M, device):
+    """-> ws, int32 of r3d_scene_<what>_ws_words(M) words: the one scratch of a call of `name`, its record in front."""
+    words = getattr(_lib.load(), "r3d_scene_%s_ws_words" % what)(M)
     if words < 0:
-        raise ValueError("pool_segments: %d points (1 .. 2^27)" % M)
+        raise ValueError("%s: %d points (1 .. 2^27)" % (name, M))
     return torch.empty(words, device=device, dtype=torch.int32)
+
+
+def _grid_args(grid, origin=None, voxel=None):
+    """-> (nx, ny, nz) as the entry points take them; with an origin, (x0, y0, z0, voxel) in front."""
+    cells = tuple(int(n) for n in grid)
+    return cells if origin is None else tuple(float(v) for v in origin) + (float(voxel),) + cells
+
+
+def scene_seg_workspace(M, device):
+    return _scene_workspace("seg", "pool_segments", M, device)
 
 
 def _seg_ws_ok(ws):
@@ -1002,11 +1012,7 @@ SCENE_GROW_RINGS = 64  # GR_RINGS_MAX of csrc/scene_grow.hip: rounds of absorb
 
 
 def scene_grow_workspace(M, device):
-    """-> ws, int32 of r3d_scene_grow_ws_words(M) words: the one scratch of a build_segments call, its record in front."""
-    words = _lib.load().r3d_scene_grow_ws_words(M)
-    if words < 0:
-        raise ValueError("build_segments: %d points (1 .. 2^27)" % M)
-    return torch.empty(words, device=device, dtype=torch.int32)
+    return _scene_workspace("grow", "build_segments", M, device)
 
 
 def _grow_scan_ok(scan):
@@ -1024,9 +1030,7 @@ def scene_grow_sort(scan, origin, voxel, grid, ws):
     """origin (x0, y0, z0) as read from the record, grid (nx, ny, nz): keys, the sort, the voxel heads -> word 7 (V)."""
     assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
     M, ld = scan.shape
-    x0, y0, z0 = (float(v) for v in origin)
-    _lib.check(_lib.load().r3d_scene_grow_sort(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid), _p(ws),
-                                               ws.numel(), _st()))
+    _lib.check(_lib.load().r3d_scene_grow_sort(_p(scan), ld, M, *_grid_args(grid, origin, voxel), _p(ws), ws.numel(), _st()))
 
 
 def scene_grow_voxels(scan, grid, n_valid, n_voxels, colour, ws):
@@ -1036,7 +1040,7 @@ def scene_grow_voxels(scan, grid, n_valid, n_voxels, colour, ws):
     M, ld = scan.shape
     voxel_index = torch.empty(M, device=scan.device, dtype=torch.int32)
     voxel_mean = torch.empty(int(n_voxels), 3, device=scan.device, dtype=torch.float32) if colour else None
-    _lib.check(_lib.load().r3d_scene_grow_voxels(_p(scan), ld, M, *(int(n) for n in grid), int(n_valid), int(n_voxels),
+    _lib.check(_lib.load().r3d_scene_grow_voxels(_p(scan), ld, M, *_grid_args(grid), int(n_valid), int(n_voxels),
                                                  _p(voxel_index), _p(voxel_mean), _p(ws), ws.numel(), _st()))
     return voxel_index, voxel_mean
 
@@ -1046,7 +1050,7 @@ def scene_grow_union(M, grid, n_voxels, connectivity, voxel_mean, colour_tol, ws
     assert _seg_ws_ok(ws)
     assert voxel_mean is None or (tuple(voxel_mean.shape) == (int(n_voxels), 3) and voxel_mean.dtype == torch.float32
                                   and voxel_mean.is_contiguous() and voxel_mean.is_cuda and colour_tol is not None)
-    _lib.check(_lib.load().r3d_scene_grow_union(M, *(int(n) for n in grid), int(n_voxels), int(connectivity), _p(voxel_mean),
+    _lib.check(_lib.load().r3d_scene_grow_union(M, *_grid_args(grid), int(n_voxels), int(connectivity), _p(voxel_mean),
                                                 0.0 if voxel_mean is None else float(colour_tol), _p(ws), ws.numel(), _st()))
 
 
@@ -1059,10 +1063,9 @@ def scene_grow_centroids(scan, origin, voxel, grid, n_voxels, ws):
     the mean offset of a voxel's points inside the voxel (G3c)."""
     assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
     M, ld = scan.shape
-    x0, y0, z0 = (float(v) for v in origin)
     centroid = torch.empty(int(n_voxels), 3, device=scan.device, dtype=torch.float32)
-    _lib.check(_lib.load().r3d_scene_grow_centroids(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid),
-                                                    int(n_voxels), _p(centroid), _p(ws), ws.numel(), _st()))
+    _lib.check(_lib.load().r3d_scene_grow_centroids(_p(scan), ld, M, *_grid_args(grid, origin, voxel), int(n_voxels), _p(centroid),
+                                                    _p(ws), ws.numel(), _st()))
     return centroid
 
 
@@ -1072,7 +1075,7 @@ def scene_grow_normals(M, grid, n_voxels, voxel, voxel_centroid, ws):
     assert _seg_ws_ok(ws) and _grow_table_ok(voxel_centroid, n_voxels)
     normal = torch.empty_like(voxel_centroid)
     support = torch.empty(int(n_voxels), device=voxel_centroid.device, dtype=torch.int32)
-    _lib.check(_lib.load().r3d_scene_grow_normals(M, *(int(n) for n in grid), int(n_voxels), float(voxel), _p(voxel_centroid),
+    _lib.check(_lib.load().r3d_scene_grow_normals(M, *_grid_args(grid), int(n_voxels), float(voxel), _p(voxel_centroid),
                                                   _p(normal), _p(support), _p(ws), ws.numel(), _st()))
     return normal, support
 
@@ -1082,7 +1085,7 @@ def scene_grow_union_normals(M, grid, n_voxels, connectivity, voxel_mean, colour
     tolerance; voxel_mean None: no colour test."""
     assert _seg_ws_ok(ws) and _grow_table_ok(voxel_normal, n_voxels)
     assert voxel_mean is None or (_grow_table_ok(voxel_mean, n_voxels) and colour_tol is not None)
-    _lib.check(_lib.load().r3d_scene_grow_union_normals(M, *(int(n) for n in grid), int(n_voxels), int(connectivity),
+    _lib.check(_lib.load().r3d_scene_grow_union_normals(M, *_grid_args(grid), int(n_voxels), int(connectivity),
                                                         _p(voxel_mean), 0.0 if voxel_mean is None else float(colour_tol),
                                                         _p(voxel_normal), float(cos2), _p(ws), ws.numel(), _st()))
 
@@ -1099,7 +1102,7 @@ def scene_grow_absorb(M, grid, n_voxels, connectivity, rings, ws):
     (absorbed voxels) and 13 (absorbed points)."""
     assert _seg_ws_ok(ws)
     ring = torch.empty(int(n_voxels), device=ws.device, dtype=torch.int32)
-    _lib.check(_lib.load().r3d_scene_grow_absorb(M, *(int(n) for n in grid), int(n_voxels), int(connectivity), int(rings),
+    _lib.check(_lib.load().r3d_scene_grow_absorb(M, *_grid_args(grid), int(n_voxels), int(connectivity), int(rings),
                                                  _p(ring), _p(ws), ws.numel(), _st()))
     return ring
 
@@ -1124,11 +1127,7 @@ OBJ_R_NLABELS, OBJ_R_NUNLABELLED, OBJ_R_NOVER, OBJ_R_NPOINTS = 12, 13, 14, 15
 
 
 def scene_obj_workspace(M, device):
-    """-> ws, int32 of r3d_scene_obj_ws_words(M) words: the one scratch of an extract_objects call, its record in front."""
-    words = _lib.load().r3d_scene_obj_ws_words(M)
-    if words < 0:
-        raise ValueError("extract_objects: %d points (1 .. 2^27)" % M)
-    return torch.empty(words, device=device, dtype=torch.int32)
+    return _scene_workspace("obj", "extract_objects", M, device)
 
 
 def _obj_labels_args(scan, labels, ignore):
@@ -1153,10 +1152,9 @@ def scene_obj_sort(scan, labels, ignore, origin, voxel, grid, n_labels, n_points
     -> unit_index (M,) int32, the row of a point's unit or -1; word 7 (the units)."""
     assert _grow_scan_ok(scan) and _seg_ws_ok(ws)
     M, ld = scan.shape
-    x0, y0, z0 = (float(v) for v in origin)
     unit_index = torch.empty(M, device=scan.device, dtype=torch.int32)
-    _lib.check(_lib.load().r3d_scene_obj_sort(_p(scan), ld, M, *_obj_labels_args(scan, labels, ignore), x0, y0, z0, float(voxel),
-                                              *(int(n) for n in grid), int(n_labels), int(n_points), _p(unit_index), _p(ws),
+    _lib.check(_lib.load().r3d_scene_obj_sort(_p(scan), ld, M, *_obj_labels_args(scan, labels, ignore),
+                                              *_grid_args(grid, origin, voxel), int(n_labels), int(n_points), _p(unit_index), _p(ws),
                                               ws.numel(), _st()))
     return unit_index
 
@@ -1164,7 +1162,7 @@ def scene_obj_sort(scan, labels, ignore, origin, voxel, grid, n_labels, n_points
 def scene_obj_union(M, grid, n_labels, n_units, connectivity, ws):
     """The union-find over the units of one class in neighbouring cells, in ws."""
     assert _seg_ws_ok(ws)
-    _lib.check(_lib.load().r3d_scene_obj_union(M, *(int(n) for n in grid), int(n_labels), int(n_units), int(connectivity), _p(ws),
+    _lib.check(_lib.load().r3d_scene_obj_union(M, *_grid_args(grid), int(n_labels), int(n_units), int(connectivity), _p(ws),
                                                ws.numel(), _st()))
 
 
@@ -1180,14 +1178,13 @@ def scene_obj_stats(scan, origin, voxel, grid, n_labels, n_units, n_objects, ws)
     assert _grow_scan_ok(scan) and _seg_ws_ok(ws) and n_objects >= 1
     M, ld = scan.shape
     S, dev = int(n_objects), scan.device
-    x0, y0, z0 = (float(v) for v in origin)
     labels = torch.empty(S, device=dev, dtype=torch.int64)
     points, units = (torch.empty(S, device=dev, dtype=torch.int32) for _ in range(2))
     lo, hi, centroid = (torch.empty(S, 3, device=dev, dtype=torch.float32) for _ in range(3))
     sums = torch.empty(S, 3, device=dev, dtype=torch.int64)  # the kernels' scratch
-    _lib.check(_lib.load().r3d_scene_obj_stats(_p(scan), ld, M, x0, y0, z0, float(voxel), *(int(n) for n in grid), int(n_labels),
-                                               int(n_units), S, _p(labels), _p(points), _p(units), _p(lo), _p(hi), _p(centroid),
-                                               _p(sums), _p(ws), ws.numel(), _st()))
+    _lib.check(_lib.load().r3d_scene_obj_stats(_p(scan), ld, M, *_grid_args(grid, origin, voxel), int(n_labels), int(n_units), S,
+                                               _p(labels), _p(points), _p(units), _p(lo), _p(hi), _p(centroid), _p(sums), _p(ws),
+                                               ws.numel(), _st()))
     return labels, points, units, lo, hi, centroid
 
 

@@ -62,26 +62,40 @@ def cos2_of(normal_tol):
     return np.float32(math.cos(math.radians(float(normal_tol))) ** 2)
 
 
-def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
-    """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
+def _check_scan(what, scan, min_columns):
+    """The scan of `what` (the function named in the messages): (M, 3) or (M, >= min_columns) float32, M <= 2^27 -> a tensor."""
     if isinstance(scan, np.ndarray):
         scan = torch.from_numpy(scan)
-    if not isinstance(scan, torch.Tensor) or scan.dim() != 2 or scan.shape[0] < 1 or not (scan.shape[1] == 3 or scan.shape[1] >= 6):
-        raise ValueError("build_segments: scan must be (M, 3) rows `x y z` or (M, >= 6) rows `x y z r g b ...`, got %s" % (
-            tuple(scan.shape) if isinstance(scan, torch.Tensor) else type(scan).__name__,))
+    is_tensor = isinstance(scan, torch.Tensor)
+    if not is_tensor or scan.dim() != 2 or scan.shape[0] < 1 or not (scan.shape[1] == 3 or scan.shape[1] >= min_columns):
+        rows = "(M, >= 3) rows `x y z ...`" if min_columns == 3 else "(M, 3) rows `x y z` or (M, >= 6) rows `x y z r g b ...`"
+        raise ValueError("%s: scan must be %s, got %s" % (what, rows, tuple(scan.shape) if is_tensor else type(scan).__name__))
     if scan.dtype != torch.float32:
-        raise ValueError("build_segments: scan must be float32, got %s" % scan.dtype)
+        raise ValueError("%s: scan must be float32, got %s" % (what, scan.dtype))
     if scan.shape[0] > scene.MAX_POINTS:
-        raise ValueError("build_segments: %d points (at most 2^27)" % scan.shape[0])
+        raise ValueError("%s: %d points (at most 2^27)" % (what, scan.shape[0]))
+    return scan
+
+
+def _check_voxel(what, voxel, connectivity, min_points):
+    """-> voxel as float32."""
     with np.errstate(over="ignore", under="ignore"):
         v32 = np.float32(voxel) if _is_real(voxel) else np.float32(np.nan)
-        t32 = np.float32(colour_tol) if _is_real(colour_tol) else np.float32(np.nan)
     if not (_is_real(voxel) and np.isfinite(voxel) and voxel > 0 and np.isfinite(v32) and v32 > 0):
-        raise ValueError("build_segments: voxel %r must be a finite float > 0 (in float32 too)" % (voxel,))
+        raise ValueError("%s: voxel %r must be a finite float > 0 (in float32 too)" % (what, voxel))
     if not scene._is_int(connectivity) or int(connectivity) not in (6, 26):
-        raise ValueError("build_segments: connectivity %r must be 6 or 26" % (connectivity,))
+        raise ValueError("%s: connectivity %r must be 6 or 26" % (what, connectivity))
     if not scene._is_int(min_points) or min_points < 1:
-        raise ValueError("build_segments: min_points %r must be an integer >= 1" % (min_points,))
+        raise ValueError("%s: min_points %r must be an integer >= 1" % (what, min_points))
+    return v32
+
+
+def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
+    """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
+    scan = _check_scan("build_segments", scan, 6)
+    v32 = _check_voxel("build_segments", voxel, connectivity, min_points)
+    with np.errstate(over="ignore", under="ignore"):
+        t32 = np.float32(colour_tol) if _is_real(colour_tol) else np.float32(np.nan)
     if colour_tol is not None:
         if not (_is_real(colour_tol) and np.isfinite(colour_tol) and colour_tol >= 0 and np.isfinite(t32)):
             raise ValueError("build_segments: colour_tol %r must be None or a finite float >= 0" % (colour_tol,))
@@ -112,10 +126,26 @@ def read_record(ws):
     return ws[:ops.SCENE_GROW_REC].tolist()
 
 
-def _raise_on_error(rec):
+def _raise_on_error(what, rec):
     if rec[ops.GROW_R_ERROR]:
-        raise RuntimeError("build_segments: the union-find ran out of its bounded loops (error word %d: bit 0 a find, bit 1 a "
-                           "unite): its table is corrupted, no result" % rec[ops.GROW_R_ERROR])
+        raise RuntimeError("%s: the union-find ran out of its bounded loops (error word %d: bit 0 a find, bit 1 a "
+                           "unite): its table is corrupted, no result" % (what, rec[ops.GROW_R_ERROR]))
+
+
+def extent_of(rec):
+    """-> (lo, hi), (3,) float32 each: the minima and maxima of the valid points, from the float bits in the record."""
+    ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
+    return ext[:3], ext[3:]
+
+
+def _on_device(what, scan, columns, *others):
+    """-> (the device of the first of scan and `others` that is on one, else the current one; the scan there, contiguous).
+    The kernels take rows of up to 64 floats and only ever read the first `columns`.  There is no CPU path."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s: no device (there is no CPU path)" % what)
+    on = [t.device for t in (scan,) + others if t.is_cuda]
+    dev = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+    return dev, (scan[:, :columns] if scan.shape[1] > 64 else scan).to(dev).contiguous()
 
 
 def build_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1):
@@ -141,12 +171,7 @@ def absorb_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
     absorb=0 stay, only -1s become ids).  See the module text and INTEGRATION.md, "Building segments"."""
     scan, voxel = check_grow_args(scan, voxel, colour_tol, connectivity, min_points, normal_tol, absorb)
     absorb = int(absorb)
-    if not torch.cuda.is_available():
-        raise RuntimeError("build_segments: no device (there is no CPU path)")
-    dev = scan.device if scan.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if scan.shape[1] > 64:  # the kernels take rows of up to 64 floats; only the first six are ever read
-        scan = scan[:, :6]
-    scan = scan.to(dev).contiguous()
+    dev, scan = _on_device("build_segments", scan, 6)
     M = scan.shape[0]
     ws = ops.scene_grow_workspace(M, dev)
     ops.scene_grow_bounds(scan, ws)
@@ -162,8 +187,7 @@ def absorb_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
                              voxel_support=None if normal_tol is None else torch.empty(0, device=dev, dtype=torch.int32),
                              voxel_ring=torch.empty(0, device=dev, dtype=torch.int32) if absorb else None,
                              n_absorbed_voxels=0, n_absorbed_points=0)
-    ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
-    lo, hi = ext[:3], ext[3:]
+    lo, hi = extent_of(rec)
     grid = grid_of(lo, hi, voxel)
     ops.scene_grow_sort(scan, lo, voxel, grid, ws)
     V = read_record(ws)[ops.GROW_R_V]  # host read 2 of 4
@@ -177,12 +201,12 @@ def absorb_segments(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
         ops.scene_grow_union_normals(M, grid, V, connectivity, voxel_means, colour_tol, normals, cos2_of(normal_tol), ws)
     ops.scene_grow_components(M, V, min_points, ws)
     rec = read_record(ws)  # host read 3 of 4: the tables' sizes
-    _raise_on_error(rec)
+    _raise_on_error("build_segments", rec)
     n_components, S = rec[ops.GROW_R_NCOMP], rec[ops.GROW_R_S]
     ring = ops.scene_grow_absorb(M, grid, V, connectivity, absorb, ws) if absorb else None
     segments, segment_points = ops.scene_grow_ids(voxel_index, V, S, ws)
     rec = read_record(ws)  # host read 4 of 4, after everything is queued
-    _raise_on_error(rec)
+    _raise_on_error("build_segments", rec)
     return GrownSegments(segments=segments, segment_points=segment_points, voxel_index=voxel_index, voxel_means=voxel_means,
                          n_segments=S, n_voxels=V, n_components=n_components, n_dropped_points=rec[ops.GROW_R_NDROPPED],
                          n_invalid=M - n_valid, grid=grid, voxel_centroids=centroids, voxel_normals=normals, voxel_support=support,

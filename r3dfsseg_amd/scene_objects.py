@@ -28,7 +28,9 @@ csrc/scene_sort.hip and the union-find and component launches that csrc/scene_gr
 import numpy as np
 import torch
 
-from . import ops, scene, scene_grow
+from . import ops, scene
+# read_record is looked up in this module at every call: tools/scene_objects_cost.py times the reads by replacing it here
+from .scene_grow import _check_scan, _check_voxel, _on_device, _raise_on_error, extent_of, grid_of, read_record
 
 MAX_IGNORE = ops.SCENE_OBJ_IGNORE
 MAX_KEY = ops.SCENE_OBJ_KEY
@@ -51,15 +53,7 @@ class SceneObjects:
 def check_object_args(scan, labels, voxel=0.05, connectivity=26, min_points=1, ignore=()):
     """Raises ValueError before anything needs a device.  -> (scan, labels as tensors, voxel as float32, ignore as a sorted
     tuple of distinct ints)."""
-    if isinstance(scan, np.ndarray):
-        scan = torch.from_numpy(scan)
-    if not isinstance(scan, torch.Tensor) or scan.dim() != 2 or scan.shape[0] < 1 or scan.shape[1] < 3:
-        raise ValueError("extract_objects: scan must be (M, >= 3) rows `x y z ...`, got %s" % (
-            tuple(scan.shape) if isinstance(scan, torch.Tensor) else type(scan).__name__,))
-    if scan.dtype != torch.float32:
-        raise ValueError("extract_objects: scan must be float32, got %s" % scan.dtype)
-    if scan.shape[0] > scene.MAX_POINTS:
-        raise ValueError("extract_objects: %d points (at most 2^27)" % scan.shape[0])
+    scan = _check_scan("extract_objects", scan, 3)
     if isinstance(labels, np.ndarray):
         labels = torch.from_numpy(labels)
     if not isinstance(labels, torch.Tensor) or labels.dim() != 1:
@@ -69,14 +63,7 @@ def check_object_args(scan, labels, voxel=0.05, connectivity=26, min_points=1, i
         raise ValueError("extract_objects: labels must be int32 or int64, got %s" % labels.dtype)
     if labels.shape[0] != scan.shape[0]:
         raise ValueError("extract_objects: %d labels for %d points" % (labels.shape[0], scan.shape[0]))
-    with np.errstate(over="ignore", under="ignore"):
-        v32 = np.float32(voxel) if scene_grow._is_real(voxel) else np.float32(np.nan)
-    if not (scene_grow._is_real(voxel) and np.isfinite(voxel) and voxel > 0 and np.isfinite(v32) and v32 > 0):
-        raise ValueError("extract_objects: voxel %r must be a finite float > 0 (in float32 too)" % (voxel,))
-    if not scene._is_int(connectivity) or int(connectivity) not in (6, 26):
-        raise ValueError("extract_objects: connectivity %r must be 6 or 26" % (connectivity,))
-    if not scene._is_int(min_points) or min_points < 1:
-        raise ValueError("extract_objects: min_points %r must be an integer >= 1" % (min_points,))
+    v32 = _check_voxel("extract_objects", voxel, connectivity, min_points)
     if not isinstance(ignore, (list, tuple, np.ndarray)) or not all(scene._is_int(c) and 0 <= int(c) < 2 ** 63 for c in ignore):
         raise ValueError("extract_objects: ignore %r must be a sequence of integer class ids >= 0" % (ignore,))
     ignore = tuple(sorted(set(int(c) for c in ignore)))
@@ -94,17 +81,6 @@ def check_key_range(n_labels, grid):
                          "exceed 2^31 - 1 keys; use a larger voxel or renumber the classes" % (
                              int(n_labels), n_cells, grid[0], grid[1], grid[2]))
     return int(n_labels) * n_cells
-
-
-def read_record(ws):
-    """The record in front of the workspace as host ints: a host read (the call has at most four)."""
-    return ws[:ops.SCENE_GROW_REC].tolist()
-
-
-def _raise_on_error(rec):
-    if rec[ops.GROW_R_ERROR]:
-        raise RuntimeError("extract_objects: the union-find ran out of its bounded loops (error word %d: bit 0 a find, bit 1 a "
-                           "unite): its table is corrupted, no result" % rec[ops.GROW_R_ERROR])
 
 
 def _empty(M, dev, n_invalid, n_unlabelled, grid):
@@ -125,12 +101,7 @@ def extract_objects(scan, labels, voxel=0.05, connectivity=26, min_points=1, ign
     objs.objects) gives the mean logits per object.  There is no CPU path.  See the module text and INTEGRATION.md, "Objects
     from a labelled scan"."""
     scan, labels, voxel, ignore = check_object_args(scan, labels, voxel, connectivity, min_points, ignore)
-    if not torch.cuda.is_available():
-        raise RuntimeError("extract_objects: no device (there is no CPU path)")
-    dev = scan.device if scan.is_cuda else (labels.device if labels.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    if scan.shape[1] > 64:  # the kernels take rows of up to 64 floats; only the first three are ever read
-        scan = scan[:, :3]
-    scan = scan.to(dev).contiguous()
+    dev, scan = _on_device("extract_objects", scan, 3, labels)
     labels = labels.to(dev).contiguous()
     ignored = torch.tensor(ignore, device=dev, dtype=torch.int64) if ignore else None
     M = scan.shape[0]
@@ -144,9 +115,8 @@ def extract_objects(scan, labels, voxel=0.05, connectivity=26, min_points=1, ign
                          % (rec[ops.OBJ_R_NOVER], ops.SCENE_OBJ_LABEL))
     if n_valid == 0:
         return _empty(M, dev, M, 0, (0, 0, 0))
-    ext = np.array(rec[ops.GROW_R_MIN:ops.GROW_R_MIN + 6], np.int32).view(np.float32)
-    lo, hi = ext[:3], ext[3:]
-    grid = scene_grow.grid_of(lo, hi, voxel)
+    lo, hi = extent_of(rec)
+    grid = grid_of(lo, hi, voxel)
     if n_points == 0:  # O1: no point takes part, nothing else is launched
         return _empty(M, dev, M - n_valid, n_unlabelled, grid)
     check_key_range(n_labels, grid)
@@ -155,7 +125,7 @@ def extract_objects(scan, labels, voxel=0.05, connectivity=26, min_points=1, ign
     ops.scene_obj_union(M, grid, n_labels, U, connectivity, ws)
     ops.scene_obj_components(M, U, min_points, ws)
     rec = read_record(ws)  # host read 3 of 4: the tables' sizes
-    _raise_on_error(rec)
+    _raise_on_error("extract_objects", rec)
     n_components, S = rec[ops.GROW_R_NCOMP], rec[ops.GROW_R_S]
     if S:
         o_labels, o_points, o_units, o_lo, o_hi, o_centroid = ops.scene_obj_stats(scan, lo, voxel, grid, n_labels, U, S, ws)
@@ -165,7 +135,7 @@ def extract_objects(scan, labels, voxel=0.05, connectivity=26, min_points=1, ign
         o_lo, o_hi, o_centroid = e.object_lo, e.object_hi, e.object_centroid
     objects = ops.scene_obj_ids(unit_index, U, S, ws)
     rec = read_record(ws)  # host read 4 of 4, after everything is queued
-    _raise_on_error(rec)
+    _raise_on_error("extract_objects", rec)
     return SceneObjects(objects=objects, unit_index=unit_index, object_labels=o_labels, object_points=o_points,
                         object_units=o_units, object_lo=o_lo, object_hi=o_hi, object_centroid=o_centroid, n_objects=S, n_units=U,
                         n_components=n_components, n_dropped_points=rec[ops.GROW_R_NDROPPED], n_unlabelled=n_unlabelled,

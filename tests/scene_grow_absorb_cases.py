@@ -122,7 +122,27 @@ def island_case():
     return cells_case([((0, 0, 0), 2, 0.0), ((1, 0, 0), 1, 10.0)] + [(v, 1, 20.0 + i) for i, v in enumerate(ISLAND)], 57)
 
 
-# ---- 8. big voxels.  min_points 2601
+# ---- 8. a comb: many owners in one wave.  min_points 2
+COMB_N = 130
+
+
+def comb_case():
+    """Kept voxels (x, 0, 0) of 2 points and colour x, each a segment of its own, and free voxels (x, 1, 0) of 1 point,
+    x = 0 .. 129: the 130 free rows follow the 130 kept ones in the table, so the two full waves of free rows hold 64
+    distinct owners each."""
+    cells = [((x, 0, 0), 2, float(x)) for x in range(COMB_N)] + [((x, 1, 0), 1, 200.0 + x) for x in range(COMB_N)]
+    return cells_case(cells, 59)
+
+
+def comb_expected(connectivity):
+    """One ring -> (the segment of free voxel (x, 1, 0) for every x, segment_points).  6: the kept voxel below it.  26: the
+    kept voxels at x - 1, x and x + 1 tie with one neighbour each, the smallest root wins."""
+    if connectivity == 6:
+        return list(range(COMB_N)), [3] * COMB_N
+    return [max(x - 1, 0) for x in range(COMB_N)], [4] + [3] * (COMB_N - 2) + [2]
+
+
+# ---- 9. big voxels.  min_points 2601
 BIG_MIN = 2601
 
 

@@ -161,6 +161,21 @@ def test_an_island_that_touches_nothing_kept_stays_free(connectivity):
     assert got.n_absorbed_points == 0 and got.n_dropped_points == len(scan) and got.segment_points.shape == (0,)
 
 
+@pytest.mark.parametrize("connectivity", [6, 26])
+def test_many_owners_in_one_wave(connectivity):
+    """130 kept voxels, a segment each, and 130 free ones above them: the free rows fill two waves of the end kernel with 64
+    distinct owners each, every one of which gets its own points and nobody else's.  With 26 a free voxel has one neighbour
+    in each of three segments and the smallest root wins."""
+    scan, coords = _cached("comb", AC.comb_case)
+    along = lambda got, y: [_seg_at(got, coords, (x, y, 0)) for x in range(AC.COMB_N)]
+    got, _ = _check("comb", scan, 0, connectivity)
+    assert got.n_segments == AC.COMB_N and along(got, 0) == list(range(AC.COMB_N)) and along(got, 1) == [-1] * AC.COMB_N
+    got, _ = _check("comb", scan, 1, connectivity)
+    owner, points = AC.comb_expected(connectivity)
+    assert along(got, 0) == list(range(AC.COMB_N)) and along(got, 1) == owner and got.segment_points.tolist() == points
+    assert (got.n_absorbed_voxels, got.n_absorbed_points, got.n_dropped_points) == (AC.COMB_N, AC.COMB_N, 0)
+
+
 def test_64_rings_on_a_free_chain_of_70():
     scan, coords = _cached("open", AC.open_chain_case)
     got, _ = _check("open", scan, 64, 6)

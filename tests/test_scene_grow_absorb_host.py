@@ -55,6 +55,7 @@ CASES = {
     "ends": (AC.ends_case, dict(voxel=C.VOX, colour_tol=AC.TOL, min_points=2)),
     "full grid": (AC.full_grid_case, dict(voxel=C.VOX, colour_tol=AC.TOL, min_points=AC.FULL_MIN)),
     "island": (AC.island_case, dict(voxel=C.VOX, colour_tol=AC.TOL, min_points=2)),
+    "comb": (AC.comb_case, dict(voxel=C.VOX, colour_tol=AC.TOL, min_points=2)),
     "random": (lambda: C.random_case(1), dict(voxel=0.05, colour_tol=0.25, min_points=30)),
 }
 
@@ -145,6 +146,15 @@ def test_the_crafted_cases_of_the_restatement():
             key = lambda v: (v[2] * 6 + v[1]) * 5 + v[0]
             assert abs(key(free) - key(kept)) == 1 and abs(keys.index(key(free)) - keys.index(key(kept))) == 1
             assert got["voxel_ring"][keys.index(key(free))] == -1
+    scan, coords = AC.comb_case()  # 130 kept voxels, a segment each, and 130 free ones: 64 distinct owners in a wave of rows
+    for conn in (6, 26):
+        base = R.grow(scan, C.VOX, AC.TOL, conn, 2)
+        seg = lambda got, y: [int(got["segments"][np.flatnonzero((coords == (x, y, 0)).all(1))[0]]) for x in range(AC.COMB_N)]
+        assert base["n_segments"] == AC.COMB_N and seg(base, 0) == list(range(AC.COMB_N)) and seg(base, 1) == [-1] * AC.COMB_N
+        got = A.absorb(base, conn, 1)
+        owner, points = AC.comb_expected(conn)
+        assert seg(got, 0) == list(range(AC.COMB_N)) and seg(got, 1) == owner and got["segment_points"].tolist() == points
+        assert (got["n_absorbed_voxels"], got["n_absorbed_points"], got["n_dropped_points"]) == (AC.COMB_N, AC.COMB_N, 0)
 
 
 def test_argument_errors_are_raised_without_a_device():
