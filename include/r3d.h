@@ -129,6 +129,15 @@ int r3d_set_wpack_in_capture(int on);
  * scale/shift may be NULL (1 / 0). */
 int r3d_pointwise_conv(const float* X, long ldx, const float* W /*(Co,K)*/, long M, int K, int Co,
                        const float* scale, const float* shift, int act, float* Out, long ldo, void* stream);
+/* test utility: the kernel r3d_pointwise_conv / _acc / _stats / _stats_seg launch for these operands, as the launcher itself
+ * decides it (one host function serves both), under r3d_get_matrix_arith() and the r3d_debug_set_gemm_bx3 mask as they are
+ * set: 0 = r3d_pointwise_gemm_kernel (fp32 core), 1 = r3d_pointwise_gemm_bx3_kernel (bf16 x 3, W cut per tile),
+ * 2 = r3d_pointwise_gemm_bx3p_kernel (bf16 x 3, W packed once per call; mask bit 2 and M >= 256).  The bf16 forms need
+ * K % 32 == 0, Co >= 32, Co % 4 == 0, M >= 64, ldx % 4 == 0, ldo % 4 == 0 and X, W, Out 16-byte aligned (*_misalign_bytes:
+ * the address modulo 16).  no_scratch != 0: the stream can have no packed-W scratch (a capturing stream without
+ * r3d_set_wpack_in_capture), where 1 stands in for 2 with the same bits.  Launches nothing, needs no device. */
+int r3d_debug_pointwise_path(long M, int K, int Co, long ldx, long ldo, int x_misalign_bytes, int w_misalign_bytes,
+                             int out_misalign_bytes, int no_scratch);
 
 /* ---- fused EdgeConv: gather + 2-layer edge MLP + max over K --------------------------
  * models/dgcnn.py:26-61,117-118.  PQ (B*N,128) = [s1*Wa x | s1*(Wb-Wa) x + t1] per point
@@ -329,6 +338,11 @@ int r3d_bn_running_update(const float* rec, int n_records, long rec_stride, int 
 long r3d_gemm_tn_ws_words(long M, int Ca, int Cb);
 int r3d_gemm_tn(const float* A, long lda, const float* B, long ldb, long M, int Ca, int Cb, float alpha, float* out,
                 int accumulate, float* ws, void* stream);
+/* test utility: the plan of r3d_gemm_tn for this shape, as the launcher itself decides it (one host function serves both),
+ * under r3d_get_matrix_arith() and the r3d_debug_set_gemm_bx3 mask as they are set.  Returns bit 0 = bf16 x 3 (Ca >= 32 and
+ * Cb >= 32), bit 1 = its 256 x 64 tiles (Cb <= 64; 128 x 128 otherwise); *rows = rows per chunk of the M axis, *chunks =
+ * their number (host ints, either may be NULL).  Launches nothing, needs no device. */
+int r3d_debug_gemm_tn_plan(long M, int Ca, int Cb, int* rows, int* chunks);
 int r3d_add_cols(const float* src, long ld_src, float* dst, long ld_dst, long M, int C, void* stream);
 
 /* EdgeConv with batch statistics over the edges of every segment of clouds (models/dgcnn.py:53-57 in train mode; segments

@@ -142,8 +142,9 @@ static int pointwise_launch(const float* X, long ldx, const float* W, long M, in
                             const float* shift, int act, float* Out, long ldo, int accumulate, float* stats_part,
                             void* stream);
 // gemm_bx3.hip: the same GEMM on the bf16 matrix core in three-piece arithmetic
-bool r3d_pointwise_bx3_ok(const float* X, long ldx, const float* W, long M, int K, int Co);
-int r3d_pointwise_bx3_launch(const float* X, long ldx, const float* W, long M, int K, int Co, const float* scale,
+// (r3d_debug_pointwise_path, declared in r3d.h, is the one decision between the three kernels: the launcher below and the
+// tests read the same function)
+int r3d_pointwise_bx3_launch(int path, const float* X, long ldx, const float* W, long M, int K, int Co, const float* scale,
                              const float* shift, int act, float* Out, long ldo, int accumulate, float* stats_part,
                              hipStream_t st);
 
@@ -197,14 +198,14 @@ static int pointwise_launch(const float* X, long ldx, const float* W, long M, in
   R3D_REQUIRE(M > 0 && K > 0 && Co > 0 && ldx >= K && ldo >= Co,
               "r3d_pointwise_conv: bad shape M=%ld K=%d Co=%d ldx=%ld ldo=%ld", M, K, Co, ldx, ldo);
   R3D_REQUIRE(act >= 0 && act <= 2, "r3d_pointwise_conv: unknown activation %d", act);
-  if (r3d_pointwise_bx3_ok(X, ldx, W, M, K, Co)) {  // (a function of the layer's shape only: never of the batch)
-    const int rc = r3d_pointwise_bx3_launch(X, ldx, W, M, K, Co, scale, shift, act, Out, ldo, accumulate, stats_part,
+  const int path = r3d_debug_pointwise_path(M, K, Co, ldx, ldo, (int)((uintptr_t)X & 15), (int)((uintptr_t)W & 15),
+                                            (int)((uintptr_t)Out & 15), 0);
+  if (path != 0) {  // bf16 x 3 (gemm_bx3.hip)
+    const int rc = r3d_pointwise_bx3_launch(path, X, ldx, W, M, K, Co, scale, shift, act, Out, ldo, accumulate, stats_part,
                                             (hipStream_t)stream);
-    if (rc > 0) return rc;
-    if (rc == 0) {
-      R3D_LAUNCH_CHECK("r3d_pointwise_conv");
-      return R3D_OK;
-    }
+    if (rc) return rc;
+    R3D_LAUNCH_CHECK("r3d_pointwise_conv");
+    return R3D_OK;
   }
   const long tiles = (long)r3d_cdiv(M, G_BM) * r3d_cdiv(Co, G_BN);
   R3D_REQUIRE(tiles < 0x7fffffffL, "r3d_pointwise_conv: too many tiles");

@@ -592,9 +592,19 @@ static int gb_lds_attr(KernelT k, size_t bytes) {
   return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : 1;
 }
 
-bool r3d_pointwise_bx3_ok(const float* X, long ldx, const float* W, long M, int K, int Co) {
-  return g_r3d_matrix_arith == 1 && (g_r3d_gemm_bx3 & 1) && K >= 32 && K % 32 == 0 && (ldx & 3) == 0 &&
-         ((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0 && Co >= 32 && Co % 4 == 0 && M >= 64;
+// The ONE decision between the three point-wise kernels (r3d.h): 0 = r3d_pointwise_gemm_kernel (fp32 core, gemm.hip),
+// 1 = r3d_pointwise_gemm_bx3_kernel (W cut per tile), 2 = r3d_pointwise_gemm_bx3p_kernel (packed W).  A function of the
+// layer's shape and of the operands' alignment only, never of the batch -- but for the M >= 256 that the packed kernel
+// wants, and for a stream that can have no scratch (no_scratch), where 1 stands in for 2 with the same bits.
+// pointwise_launch (gemm.hip) branches on it, so the tests that read it cannot disagree with the launch.
+extern "C" int r3d_debug_pointwise_path(long M, int K, int Co, long ldx, long ldo, int x_misalign_bytes, int w_misalign_bytes,
+                                        int out_misalign_bytes, int no_scratch) {
+  const bool bx3 = g_r3d_matrix_arith == 1 && (g_r3d_gemm_bx3 & 1) && K >= 32 && K % 32 == 0 && (ldx & 3) == 0 &&
+                   (x_misalign_bytes & 15) == 0 && (w_misalign_bytes & 15) == 0 && Co >= 32 && Co % 4 == 0 && M >= 64 &&
+                   (ldo & 3) == 0 && (out_misalign_bytes & 15) == 0;
+  if (!bx3) return 0;
+  // W cut once per call, 32-row wave tiles, 3 workgroups per CU
+  return (!(GB_ABL & 128) && (g_r3d_gemm_bx3 & 4) && M >= 256 && !no_scratch) ? 2 : 1;
 }
 
 // Scratch for the packed W of r3d_pointwise_gemm_bx3p_kernel: one buffer per stream (launches of one stream are
@@ -641,11 +651,11 @@ static unsigned short* wpack_scratch(hipStream_t st, size_t bytes) {
   return (unsigned short*)p;
 }
 
-int r3d_pointwise_bx3_launch(const float* X, long ldx, const float* W, long M, int K, int Co, const float* scale,
+// path: r3d_debug_pointwise_path's 1 or 2; a stream without scratch turns 2 into 1 (its no_scratch)
+int r3d_pointwise_bx3_launch(int path, const float* X, long ldx, const float* W, long M, int K, int Co, const float* scale,
                              const float* shift, int act, float* Out, long ldo, int accumulate, float* stats_part,
                              hipStream_t st) {
-  if ((ldo & 3) != 0 || ((uintptr_t)Out & 15) != 0) return -1;  // (the caller takes the fp32 kernel)
-  if (!(GB_ABL & 128) && (g_r3d_gemm_bx3 & 4) && M >= 256) {  // W cut once per call, 32-row wave tiles, 3 workgroups per CU
+  if (path == 2) {
     const int bnp = Co > 64 ? 128 : 64;
     const int Cop = r3d_cdiv(Co, bnp) * bnp;
     unsigned short* wp = wpack_scratch(st, (size_t)Cop * K * 6);

@@ -731,13 +731,22 @@ extern "C" long r3d_gemm_tn_ws_words(long M, int Ca, int Cb) {
   return ((M + rows - 1) / rows) * (long)Ca * Cb + 16;
 }
 
+// The plan of r3d_gemm_tn (r3d.h): bit 0 = bf16 x 3, bit 1 = its 256 x 64 tiles (Cb <= 64; else 128 x 128); *rows, *chunks:
+// the height and the number of the row chunks.  r3d_gemm_tn launches what this says.
+extern "C" int r3d_debug_gemm_tn_plan(long M, int Ca, int Cb, int* rows, int* chunks) {
+  const bool bx3 = r3d_gemm_tn_bx3_ok(Ca, Cb);
+  const int r = tn_rows(M, Ca, Cb, bx3);
+  if (rows) *rows = r;
+  if (chunks) *chunks = r3d_cdiv(M, r);
+  return (bx3 ? 1 : 0) | (bx3 && Cb <= 64 ? 2 : 0);
+}
+
 // out (Ca, Cb) = alpha * A^T B  (+ out if accumulate)
 extern "C" int r3d_gemm_tn(const float* A, long lda, const float* B, long ldb, long M, int Ca, int Cb, float alpha,
                            float* out, int accumulate, float* ws, void* stream) {
   R3D_REQUIRE(A && B && out && ws && M > 0 && Ca > 0 && Cb > 0 && lda >= Ca && ldb >= Cb, "r3d_gemm_tn: bad arguments");
-  const bool bx3 = r3d_gemm_tn_bx3_ok(Ca, Cb);
-  const int rows = tn_rows(M, Ca, Cb, bx3);
-  const int chunks = r3d_cdiv(M, rows);
+  int rows = 0, chunks = 0;
+  const bool bx3 = r3d_debug_gemm_tn_plan(M, Ca, Cb, &rows, &chunks) & 1;
   hipStream_t st = (hipStream_t)stream;
   if (bx3) {
     const int rc = r3d_gemm_tn_bx3_launch(A, lda, B, ldb, M, Ca, Cb, rows, chunks, ws, st);

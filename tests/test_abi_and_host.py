@@ -209,6 +209,72 @@ def test_edgeconv_bwd_path_states_the_three_fallbacks_without_gpu():
     assert "r3d_debug_edgeconv_bwd_path" in _lib._SIGS and _lib._SIGS["r3d_debug_edgeconv_bwd_path"] == (_lib.c_i, [_lib.c_i, _lib.c_l, _lib.c_i, _lib.c_i])
 
 
+def test_pointwise_path_states_every_fallback_and_threshold_without_gpu():
+    """r3d_debug_pointwise_path (the host function pointwise_launch branches on): 0 = fp32 kernel, 1 = bf16 x 3 with W cut
+    per tile, 2 = bf16 x 3 with packed W.  A bf16 form needs arithmetic 1, mask bit 0, K a multiple of 32, Co >= 32 and a
+    multiple of 4, M >= 64, ldx and ldo multiples of 4 and X, W, Out 16-byte aligned; the packed one mask bit 2, M >= 256
+    and a stream that can have a scratch."""
+    lib = _lib.load()
+    path = lib.r3d_debug_pointwise_path
+    arith, mask = lib.r3d_get_matrix_arith(), int(os.environ.get("R3D_GEMM_BX3", 7))  # (the mask has no getter: _lib.load's)
+    _lib.check(lib.r3d_debug_set_gemm_bx3(7))
+    try:
+        _lib.check(lib.r3d_set_matrix_arith(1))
+        assert [path(M, 64, 64, 64, 64, 0, 0, 0, 0) for M in (63, 64, 255, 256)] == [0, 1, 1, 2]   # the M thresholds
+        assert [path(M, 64, 64, 64, 64, 0, 0, 0, 1) for M in (63, 64, 255, 256)] == [0, 1, 1, 1]   # no scratch: never 2
+        assert path(4096, 512, 512, 512, 704, 0, 0, 0, 0) == 2 and path(1 << 33, 32, 32, 32, 32, 0, 0, 0, 0) == 2
+        assert path(256, 48, 64, 64, 64, 0, 0, 0, 0) == 0 and path(256, 16, 64, 64, 64, 0, 0, 0, 0) == 0   # K % 32 != 0
+        assert path(256, 64, 28, 64, 64, 0, 0, 0, 0) == 0 and path(256, 64, 32, 64, 64, 0, 0, 0, 0) == 2   # Co < 32
+        assert path(256, 64, 66, 64, 68, 0, 0, 0, 0) == 0 and path(256, 64, 68, 64, 68, 0, 0, 0, 0) == 2   # Co % 4 != 0
+        assert path(256, 64, 64, 65, 64, 0, 0, 0, 0) == 0 and path(256, 64, 64, 68, 64, 0, 0, 0, 0) == 2   # ldx % 4 != 0
+        assert path(256, 64, 64, 64, 65, 0, 0, 0, 0) == 0 and path(256, 64, 64, 64, 68, 0, 0, 0, 0) == 2   # ldo % 4 != 0
+        for off in (4, 8, 12):                                                                             # 4 bytes off 16, ..
+            assert path(256, 64, 64, 64, 64, off, 0, 0, 0) == 0 and path(256, 64, 64, 64, 64, 0, off, 0, 0) == 0
+            assert path(256, 64, 64, 64, 64, 0, 0, off, 0) == 0
+        assert path(256, 64, 64, 64, 64, 16, 32, 48, 0) == 2
+        lib.r3d_debug_set_gemm_bx3(3)   # no packed kernel
+        assert [path(M, 64, 64, 64, 64, 0, 0, 0, 0) for M in (63, 64, 255, 256)] == [0, 1, 1, 1]
+        lib.r3d_debug_set_gemm_bx3(6)   # the point-wise GEMM stays on the fp32 core
+        assert [path(M, 64, 64, 64, 64, 0, 0, 0, 0) for M in (63, 64, 255, 256)] == [0, 0, 0, 0]
+        lib.r3d_debug_set_gemm_bx3(7)
+        _lib.check(lib.r3d_set_matrix_arith(0))
+        assert [path(M, 64, 64, 64, 64, 0, 0, 0, 0) for M in (63, 64, 255, 256)] == [0, 0, 0, 0]
+    finally:
+        _lib.check(lib.r3d_debug_set_gemm_bx3(mask))
+        _lib.check(lib.r3d_set_matrix_arith(arith))
+    c_i, c_l = _lib.c_i, _lib.c_l
+    assert _lib._SIGS["r3d_debug_pointwise_path"] == (c_i, [c_l, c_i, c_i, c_l, c_l, c_i, c_i, c_i, c_i])
+
+
+def test_gemm_tn_plan_states_arithmetic_tiles_and_chunks_without_gpu():
+    """r3d_debug_gemm_tn_plan (the host function r3d_gemm_tn launches by): bit 0 = bf16 x 3 (arithmetic 1, mask bit 1, Ca and
+    Cb >= 32), bit 1 = its 256 x 64 tiles (Cb <= 64); chunks of at least 128 and at most 4096 rows, multiples of 32."""
+    lib = _lib.load()
+
+    def plan(M, Ca, Cb):
+        rows, chunks = ctypes.c_int(-1), ctypes.c_int(-1)
+        bits = lib.r3d_debug_gemm_tn_plan(M, Ca, Cb, ctypes.byref(rows), ctypes.byref(chunks))
+        assert chunks.value == -(-M // rows.value) and bits == lib.r3d_debug_gemm_tn_plan(M, Ca, Cb, None, None)
+        return bits, rows.value, chunks.value
+
+    arith, mask = lib.r3d_get_matrix_arith(), int(os.environ.get("R3D_GEMM_BX3", 7))  # (the mask has no getter: _lib.load's)
+    _lib.check(lib.r3d_debug_set_gemm_bx3(7))
+    try:
+        _lib.check(lib.r3d_set_matrix_arith(1))
+        assert plan(161, 33, 65) == (1, 128, 2) and plan(161, 257, 64) == (3, 128, 2) and plan(128, 32, 32) == (3, 128, 1)
+        assert plan(161, 31, 64) == (0, 128, 2) and plan(161, 128, 9) == (0, 128, 2)
+        assert plan(786432, 512, 192) == (1, 4096, 192) and plan(100000, 64, 64) == (3, 224, 447)
+        lib.r3d_debug_set_gemm_bx3(5)
+        assert plan(161, 33, 65) == (0, 128, 2)
+        lib.r3d_debug_set_gemm_bx3(7)
+        _lib.check(lib.r3d_set_matrix_arith(0))
+        assert plan(161, 33, 65) == (0, 128, 2) and plan(100000, 64, 64) == (0, 128, 782)
+    finally:
+        _lib.check(lib.r3d_debug_set_gemm_bx3(mask))
+        _lib.check(lib.r3d_set_matrix_arith(arith))
+    assert _lib._SIGS["r3d_debug_gemm_tn_plan"] == (_lib.c_i, [_lib.c_l, _lib.c_i, _lib.c_i, _lib.c_f, _lib.c_f])
+
+
 def test_state_dict_names_match_reference_contract():
     """Key names and shapes of SURVEY.md 8b (verified there against the reference DGCNN)."""
     from r3dfsseg_amd.mpti import MPTI_SelfAtten

@@ -17,9 +17,9 @@ int main(int argc, char** argv) {
   printf("GB_ABL=%d:", GB_ABL);
   for (auto& s : shapes) {
     const int K = s[0], Co = s[1];
-    for (int it = 0; it < 2; ++it) r3d_pointwise_bx3_launch(X, K, W, M, K, Co, nullptr, nullptr, 0, Out, Co, 0, nullptr, 0);
+    for (int it = 0; it < 2; ++it) r3d_pointwise_bx3_launch(r3d_debug_pointwise_path(M, K, Co, K, Co, 0, 0, 0, 0), X, K, W, M, K, Co, nullptr, nullptr, 0, Out, Co, 0, nullptr, 0);
     hipEventRecord(a, 0);
-    for (int it = 0; it < 10; ++it) r3d_pointwise_bx3_launch(X, K, W, M, K, Co, nullptr, nullptr, 0, Out, Co, 0, nullptr, 0);
+    for (int it = 0; it < 10; ++it) r3d_pointwise_bx3_launch(r3d_debug_pointwise_path(M, K, Co, K, Co, 0, 0, 0, 0), X, K, W, M, K, Co, nullptr, nullptr, 0, Out, Co, 0, nullptr, 0);
     hipEventRecord(b, 0); hipEventSynchronize(b);
     float ms; hipEventElapsedTime(&ms, a, b);
     printf("  %d->%d %.1f us", K, Co, ms * 100);
