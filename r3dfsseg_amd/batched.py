@@ -39,17 +39,9 @@ class EpisodeBatchRunner:
 
     # ------------------------------------------------------------------ status
     def _count(self, backward):
-        hb = self.model._head[1]
-        E = hb.E
-        c = self.counters
-        st = hb.stats.view(E, 2)
-        bad = (st[:, 0] == 0).sum() + (hb.desc.view(E, 32)[:, ops.HD_FPS_TIMEOUT] != 0).sum()
-        if backward:
-            bad = bad + (hb.stats_bwd.view(E, 2)[:, 0] == 0).sum()
-        c[0] += bad
-        c[1] += hb.knn_status[0].clamp(max=1)
-        c[2] += st[:, 1].sum()
-        torch.maximum(c[3], st[:, 1].max().to(torch.int64), out=c[3])
+        c, s = self.counters, self.model._head[1].status(backward)
+        c[:3].add_(s[:3])  # bad, 201-NN overflow, CG iterations
+        torch.maximum(c[3], s[3], out=c[3])
 
     def begin_step(self):
         self.counters.zero_()

@@ -94,20 +94,15 @@ class EpisodeGraphs:
             sl.parts[0].copy_(lp); sl.parts[1].copy_(con)
             for i in range(4):
                 sl.parts[2 + i].copy_(metrics[i])
-            hb = model._slot.last[1]
-            ok = hb.stats[0] * hb.stats_bwd[0].clamp(max=1)
         else:
             sx, sy, qx, qy = sl.inputs[:4]
             with torch.no_grad():
                 logits, loss = model(sx, sy, qx, qy, eval=self.eval_flag)
             sl.loss_sum += loss
-            hb = model._slot.last[1]
-            ok = hb.stats[0]
             sl.logits = logits
-        sl.bad += 1 - ok + hb.desc[ops.HD_FPS_TIMEOUT].clamp(max=1)
-        sl.knn_overflow += hb.knn_status[0].clamp(max=1)
-        sl.cg_iters += hb.stats[1]
-        torch.maximum(sl.cg_max, hb.stats[1], out=sl.cg_max)
+        s = model._slot.last[1].status(backward=self.train)
+        sl.counters[:3].add_(s[:3])  # bad, 201-NN overflow, CG iterations
+        torch.maximum(sl.counters[3], s[3], out=sl.counters[3])
 
     def _capture(self, s, example, dev):
         model = self.model
@@ -117,7 +112,7 @@ class EpisodeGraphs:
         sl.inputs = [t.to(dev).clone() for t in example]
         sl.loss_sum = torch.zeros((), device=dev)
         sl.parts = torch.zeros(6, device=dev)  # lp_loss, contrast loss, the four debug metrics of the last replay
-        sl.bad, sl.knn_overflow, sl.cg_iters, sl.cg_max = (self.counters[s, i] for i in range(4))
+        sl.counters = self.counters[s]
         st = EpisodeSlot(s)
         st.fixed_budget = self.lp_budget
         sl.ep2 = torch.zeros(1, device=dev, dtype=torch.int32)  # 2 x (index of the episode inside its run())

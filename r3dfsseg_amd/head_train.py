@@ -25,18 +25,12 @@ def lp_forward(model, sfeat, qfeat, support_y, query_y, E=1, ep_rows=0):
     if model._lp_force:  # the conservative re-run (see MPTILearner_V3.train): one FPS launch per round as well
         hb.fps_one_launch = False
     ops.head_prototypes(hb, sy, None, sfeat, qfeat, ep_rows)
-    nbr = ops.knn_nodes(hb, exact=model._lp_force)
-    if model.nbr_patch is not None:  # parity tests only (mpti.MPTI_SelfAtten.nbr_patch)
-        nbr = model.nbr_patch(nbr)
-    if model._trace is not None:
-        model._trace["nbr"] = nbr
-    # same launch-budget policy as eval (mpti.py: _lp_next_budget); MPTILearner_V3.train / DPTrainer.step check
-    # lp_converged(backward=True) before the optimiser step and redo the episode on this conservative schedule
-    budget = model._lp_next_budget()
-    ops.label_propagate(hb, nbr, model.sigma, 0.99, budget, model.lp_tol)
-    model._lp_post(hb)
+    # eval's graph and solve on eval's launch-budget policy (mpti.py: _propagate, _lp_next_budget); MPTILearner_V3.train /
+    # DPTrainer.step check lp_converged(backward=True) before the optimiser step and redo the episode on this conservative
+    # schedule
+    budget = model._propagate(hb, exact=model._lp_force)
     labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous()
-    logits, loss, pred = ops.logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), 32, E, n_q, N, model.n_classes, labels)
+    logits, loss, pred = ops.query_logits_ce(hb, n_q, model.n_classes, labels)
     return loss, logits, pred, LPSaved(model, hb, labels, n_q, E, ep_rows, budget)
 
 
@@ -63,9 +57,8 @@ def lp_backward(saved, gscale):
                 D, _p(hb.lp_ws), hb.lp_words, hb.lp_stride, _p(stats), 2, _st()))
             if plane:
                 dnodes.add_(dn)
-                sb = hb.stats_bwd.view(E, 2)
-                sb[:, 0] = torch.minimum(sb[:, 0], stats[:, 0])
-                sb[:, 1] = torch.maximum(sb[:, 1], stats[:, 1])
+                hb.stats_bwd[:, 0] = torch.minimum(hb.stats_bwd[:, 0], stats[:, 0])
+                hb.stats_bwd[:, 1] = torch.maximum(hb.stats_bwd[:, 1], stats[:, 1])
     assert E == 1 or ep_rows == (S + n_q) * N
     rows = E * (S + n_q) * N
     dfeat = torch.empty(rows, D, device=dev, dtype=torch.float32)

@@ -89,14 +89,8 @@ class MPTI_SelfAtten(FewShotFeatures):
         201-NN append kernel stay inside its survivor buffer AND did the one-launch FPS finish?  False -> call
         forward again with lp_iters=self.lp_max_iter (which also selects the always-exact insertion kNN kernel).
         backward=True: the adjoint solve of the last backward pass must have converged as well."""
-        hb = self._head[1]
-        E = hb.E
-        words = [hb.stats.view(E, 2)[:, 0], hb.knn_status, hb.desc.view(E, 32)[:, ops.HD_FPS_TIMEOUT]]
-        if backward:
-            words.append(hb.stats_bwd.view(E, 2)[:, 0])
-        w = torch.cat(words).tolist()  # one device-to-host copy
-        ok = all(v != 0 for v in w[:E]) and w[E] == 0 and all(v == 0 for v in w[E + 1:2 * E + 1])
-        return ok and (not backward or all(v != 0 for v in w[2 * E + 1:]))
+        bad, overflow = self._head[1].status(backward)[:2].tolist()  # one device-to-host copy
+        return bad == 0 and overflow == 0
 
     # ------------------------------------------------------------------ forward (mpti.py:414-577)
     def forward(self, support_x, support_y, query_x, query_y, gt_support_y=None, gt_query_y=None, train=False,
@@ -147,11 +141,11 @@ class MPTI_SelfAtten(FewShotFeatures):
         hb.fps_one_launch = self._slot.fps_one_launch and not lp_iters
         sy = support_y.reshape(1, S, N).to(torch.int32).contiguous()
         ops.head_prototypes(hb, sy, shot_keep, feat, feat)
-        if int(hb.desc[ops.HD_FPS_TIMEOUT].item()) != 0:  # (the fit's host read)
+        if int(hb.desc[0, ops.HD_FPS_TIMEOUT].item()) != 0:  # (the fit's host read)
             hb.fps_one_launch = False
             ops.head_prototypes(hb, sy, shot_keep, feat, feat)
         cap = hb.n_cap - 1
-        head = F.FittedHead(hb.nodes[:cap], hb.Y, hb.n_cap, hb.desc, hb.cluster_count, cap)
+        head = F.FittedHead(hb.nodes[:cap], hb.Y, hb.n_cap, hb.desc[0], hb.cluster_count[0], cap)
         return F.FittedSupport(self, head=head, shot_keep=shot_keep, eval=eval,
                                schedule="conservative" if lp_iters else "default", n_queries=n_queries)
 
@@ -168,17 +162,28 @@ class MPTI_SelfAtten(FewShotFeatures):
         logits, loss, pred = self._attached_head(hb, n_q, labels, lp_iters)
         return logits.reshape(G, n_q, self.n_classes, N), loss.reshape(G), pred.reshape(G, n_q, N)
 
-    def _attached_head(self, hb, n_q, labels, lp_iters):
-        """What follows the attach in _predict_groups and _predict_groups_sets: the 201-NN graph, the label propagation and
-        the logits of hb's E systems, one launch sequence -> query_logits_ce's (logits, loss, pred)."""
-        nbr = ops.knn_nodes(hb, exact=bool(lp_iters))
+    def _propagate(self, hb, exact, lp_iters=None):
+        """From the node matrices of hb's E systems to their Z, in eval, predict and training (head_train.lp_forward) alike:
+        the 201-NN graph (exact: the insertion kernel), then the label propagation on lp_iters or the budgeted number of
+        CG iterations -> the budget used (the adjoint solve sizes its own from it)."""
+        nbr = ops.knn_nodes(hb, exact=exact)
         if self.nbr_patch is not None:
             nbr = self.nbr_patch(nbr)
-        ops.label_propagate(hb, nbr, self.sigma, 0.99, lp_iters or self._lp_next_budget(), self.lp_tol)
+        if self._trace is not None:
+            self._trace["nbr"] = nbr
+        budget = lp_iters or self._lp_next_budget()
+        ops.label_propagate(hb, nbr, self.sigma, 0.99, budget, self.lp_tol)
         self._lp_post(hb)
-        out = ops.query_logits_ce(hb, n_q, self.n_classes, labels)
-        self.num_prototypes_dev = hb.desc.view(hb.E, 32)[:, ops.HD_N_PROTO]
-        return out
+        return budget
+
+    def _attached_head(self, hb, n_q, query_y, lp_iters):
+        """What follows the node matrices in _forward_eval, _predict_groups and _predict_groups_sets: the graph, the label
+        propagation and the logits of hb's E systems, one launch sequence -> query_logits_ce's (logits, loss, pred).
+        query_y: (E, n_q, N) labels or None."""
+        self._propagate(hb, bool(lp_iters), lp_iters)
+        labels = query_y.reshape(hb.E, n_q, hb.N).to(torch.int64).contiguous() if query_y is not None else None
+        self.num_prototypes_dev = hb.desc[:, ops.HD_N_PROTO]
+        return ops.query_logits_ce(hb, n_q, self.n_classes, labels)
 
     def _predict_groups_sets(self, fits, query_x, lp_iters=None):
         """_predict_groups against K fitted systems with ONE encoder pass and ONE head sequence: fits: fitted.FittedSets (or
@@ -238,15 +243,6 @@ class MPTI_SelfAtten(FewShotFeatures):
             hb.fps_one_launch = False
         sy = support_y.reshape(E, S, N).to(torch.int32).contiguous()
         ops.head_prototypes(hb, sy, shot_keep, sfeat, qfeat, ep_rows)
-        nbr = ops.knn_nodes(hb, exact=bool(lp_iters))
-        if self.nbr_patch is not None:
-            nbr = self.nbr_patch(nbr)
-        ops.label_propagate(hb, nbr, self.sigma, 0.99, lp_iters or self._lp_next_budget(), self.lp_tol)
-        self._lp_post(hb)
-        labels = query_y.reshape(E, n_q, N).to(torch.int64).contiguous() if query_y is not None else None
-        logits, loss, _ = ops.query_logits_ce(hb, n_q, self.n_classes, labels)
-        logits, loss = logits.reshape(E, n_q, self.n_classes, N), loss.reshape(E)
-        self.num_prototypes_dev = hb.desc.view(E, 32)[:, ops.HD_N_PROTO]
         if self._trace is not None:
-            self._trace.update(sfeat=feat[:S * N], qfeat=feat[S * N:ep_rows], feat=feat, shot_keep=shot_keep, nbr=nbr)
-        return logits, loss
+            self._trace.update(sfeat=feat[:S * N], qfeat=feat[S * N:ep_rows], feat=feat, shot_keep=shot_keep)
+        return self._attached_head(hb, n_q, query_y, lp_iters)[:2]

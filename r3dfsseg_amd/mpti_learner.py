@@ -192,34 +192,30 @@ class MPTILearner_V3(FittedLearner):
         query_x = query_x.cuda()
         query_y = query_y.cuda() if query_y is not None else None
         with torch.no_grad():
-            pred, loss, correct = self._predict_once(fitted, query_x, query_y)
-            if not self.model.lp_converged():
-                pred, loss, correct = self._predict_once(fitted, query_x, query_y, lp_iters=self.model.lp_max_iter)
-                if not self.model.lp_converged():
-                    raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
+            pred, loss, correct = self._exact(lambda lp_iters: self._predict_once(fitted, query_x, query_y, lp_iters))[0]
         return self._predict_result(query_x, pred, loss, correct)
 
-    def _scene_launch(self, fitted, query_x):
-        """One launch of predict_scene under predict()'s rule: a launch that did not converge is redone as a whole."""
-        logits = self.model._predict_groups(fitted, query_x, None)[0]
+    def _exact(self, run):
+        """The redo rule of every inference launch: run(lp_iters=None), the budgeted schedule; a launch that did not
+        converge (or overflowed the 201-NN survivor buffer, or timed out in the FPS) is redone as a whole on the
+        conservative one, run(model.lp_max_iter); it raises if that misses too.  -> (what run returned, redone)."""
+        out = run(None)
         if self.model.lp_converged():
-            return logits, False
-        logits = self.model._predict_groups(fitted, query_x, None, lp_iters=self.model.lp_max_iter)[0]
+            return out, False
+        out = run(self.model.lp_max_iter)
         if not self.model.lp_converged():
             raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
-        return logits, True
+        return out, True
+
+    def _scene_launch(self, fitted, query_x):
+        """One launch of predict_scene under predict()'s rule (_exact) -> (logits, redone)."""
+        return self._exact(lambda lp_iters: self.model._predict_groups(fitted, query_x, None, lp_iters=lp_iters)[0])
 
     def _scene_launch_sets(self, fits, query_x):
         """_scene_launch for K support sets: lp_converged() speaks for the K * G systems of the launch, and a miss redoes
         all of them."""
-        flat = lambda z: z.reshape(query_x.shape[0], -1, query_x.shape[-1])
-        logits = self.model._predict_groups_sets(fits, query_x)
-        if self.model.lp_converged():
-            return flat(logits), False
-        logits = self.model._predict_groups_sets(fits, query_x, lp_iters=self.model.lp_max_iter)
-        if not self.model.lp_converged():
-            raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
-        return flat(logits), True
+        return self._exact(lambda lp_iters: self.model._predict_groups_sets(fits, query_x, lp_iters=lp_iters).reshape(
+            query_x.shape[0], -1, query_x.shape[-1]))
 
     def _test_graph(self, data, eval):
         from .episode_graph import EpisodeGraphs
@@ -247,18 +243,13 @@ class MPTILearner_V3(FittedLearner):
         self.model.eval()
         from . import dist as D
         D.warn_rank_local_stats(self.model, 'evaluation')
-        with torch.no_grad():
+
+        def run(lp_iters):
             logits, loss = self.model(support_x, support_y, query_x, query_y, gt_support_y=gt_support_y,
                                       sampled_classes=sampled_classes, step=step, path=path, support_flag=None,
-                                      eval=eval)
+                                      eval=eval, lp_iters=lp_iters)
             pred = logits.argmax(dim=1)
-            accuracy = point_accuracy(pred, query_y)
-            if not self.model.lp_converged():  # CG launch budget too small for this episode: redo in full
-                logits, loss = self.model(support_x, support_y, query_x, query_y, gt_support_y=gt_support_y,
-                                          sampled_classes=sampled_classes, step=step, path=path,
-                                          support_flag=None, eval=eval, lp_iters=self.model.lp_max_iter)
-                pred = logits.argmax(dim=1)
-                accuracy = point_accuracy(pred, query_y)
-                if not self.model.lp_converged():
-                    raise RuntimeError("label propagation did not converge in %d CG iterations" % self.model.lp_max_iter)
-        return pred, loss, accuracy
+            return pred, loss, point_accuracy(pred, query_y)
+
+        with torch.no_grad():
+            return self._exact(run)[0]  # (a CG launch budget too small for this episode: redone in full)

@@ -270,9 +270,9 @@ def attention(qkv, B, N, out, want_lse=False, group=0):
 
 
 class HeadBuffers:
-    """Device buffers of the transductive heads of E episodes (capacity sized, no host sync).  E > 1: every array has a
-    leading episode axis, episode e's system lives at [e] (nodes / Y / Z: rows [e n_cap, (e + 1) n_cap)).  E = 1, the
-    single-episode head of the reference's schedule, keeps the plain shapes (desc (32,), stats (2,), ...)."""
+    """Device buffers of the transductive heads of E episodes (capacity sized, no host sync).  Every array has a leading
+    episode axis for every E, episode e's system lives at [e] (nodes / Y / Z: rows [e n_cap, (e + 1) n_cap)); the
+    single-episode head of the reference's schedule is E = 1: desc (1, 32), stats (1, 2), ..."""
 
     def __init__(self, n_way, k_shot, N, n_q_pts, k_sub, k_connect, D, device, E=1):
         lib = _lib.load()
@@ -285,8 +285,7 @@ class HeadBuffers:
         assert lib.r3d_head_desc_words() == 32
         i32 = dict(device=device, dtype=torch.int32)
         f32 = dict(device=device, dtype=torch.float32)
-        one = (lambda t: t[0]) if E == 1 else (lambda t: t)
-        self.desc = one(torch.zeros(E, 32, **i32))
+        self.desc = torch.zeros(E, 32, **i32)
         self.nodes = torch.empty(E * self.n_cap, D, **f32)
         # label columns travel as float4 per node.  More than 3 ways (5..8 classes): TWO planes of 4 columns, plane 1
         # (classes 4..7) behind the E systems of plane 0 -- the label propagation is column-wise independent and solves
@@ -296,16 +295,16 @@ class HeadBuffers:
         self.Z = torch.empty(self.planes * E * self.n_cap, 4, **f32)
         self.proto_words = lib.r3d_head_proto_ws_words(n_way, k_shot, N)
         self.proto_stride = (self.proto_words + 3) // 4 * 4      # even (64-bit words inside), 16-byte rows
-        self.proto_ws = one(torch.empty(E, self.proto_stride, **i32))
+        self.proto_ws = torch.empty(E, self.proto_stride, **i32)
         self.lp_words = lib.r3d_lp_ws_words(self.n_cap, self.kp1)
         self.lp_stride = (self.lp_words + 3) // 4 * 4             # float4 arrays inside
-        self.lp_ws = one(torch.empty(E, self.lp_stride, **i32))
-        self.assign = one(torch.empty(E, 2 * n_way * k_shot * N, **i32))
-        self.cluster_count = one(torch.zeros(E, self.n_cap, **i32))
-        self.stats = one(torch.zeros(E, 2, **i32))                # per system: {converged, CG iterations}
+        self.lp_ws = torch.empty(E, self.lp_stride, **i32)
+        self.assign = torch.empty(E, 2 * n_way * k_shot * N, **i32)
+        self.cluster_count = torch.zeros(E, self.n_cap, **i32)
+        self.stats = torch.zeros(E, 2, **i32)                # per system: {converged, CG iterations}
         self.stats2 = torch.zeros(E, 2, **i32) if self.planes == 2 else None   # ... of the second plane's solves
         self.knn_status = torch.zeros(1, **i32)                   # ONE word for the batch (bit 0: survivor overflow)
-        self.stats_bwd = one(torch.zeros(E, 2, **i32))
+        self.stats_bwd = torch.zeros(E, 2, **i32)
         # all FPS rounds in one persistent launch: its workgroups that hold points must be co-resident (~500 slots of
         # this kernel at D <= 192, 250 above); fps_group episodes share a launch, fps_slots caps what may be resident
         # (the library clamps the group to the kernel's real occupancy as well: csrc/head_proto.hip::fps_slots_clamp)
@@ -323,22 +322,38 @@ class HeadBuffers:
         return max(1, self.fps_slots // self.fps_blocks)
 
     def n_nodes_ptr(self):
-        return self.desc.view(-1)[HD_N_NODES:]   # episode e's count 32 words further on
+        return self.desc[0, HD_N_NODES:]   # episode e's count 32 words further on
 
     def n_proto_ptr(self):
-        return self.desc.view(-1)[HD_N_PROTO:]
+        return self.desc[0, HD_N_PROTO:]
+
+    def status(self, backward=False):
+        """head_status of the last launch through these buffers (backward: of its adjoint solve as well)."""
+        return head_status(self.stats, self.desc, self.knn_status, self.stats_bwd if backward else None)
 
     def csr(self, e=0):
         """(n, row_ptr (n+1) int64, col (nnz) int64, val (nnz) fp32) of the normalised graph S the last
         r3d_label_propagate left in episode e's workspace (synchronises; tests, tools and bench.py's byte counts)."""
-        n = int(self.desc.view(-1, 32)[e, HD_N_NODES].item())
+        n = int(self.desc[e, HD_N_NODES].item())
         o = self.lp_off
-        ws = self.lp_ws.view(-1, self.lp_stride)[e]
+        ws = self.lp_ws[e]
         row_ptr = ws[o["row_ptr"]:o["row_ptr"] + n + 1].to(torch.int64)
         nnz = int(row_ptr[-1].item())
         col = ws[o["col"]:o["col"] + (nnz + 1) // 2].view(torch.int16)[:nnz].to(torch.int64) & 0xffff
         val = ws[o["val"]:o["val"] + nnz].view(torch.float32)
         return n, row_ptr, col, val
+
+
+def head_status(stats, desc, knn_status, stats_bwd=None):
+    """The one reading of a head launch's status words -> (4,) int32 on their device: [bad, overflow, iters_sum, iters_max].
+    bad: systems whose CG did not converge (stats[e, 0] == 0), plus systems whose one-launch FPS timed out
+    (desc[e, HD_FPS_TIMEOUT] != 0), plus -- stats_bwd given -- systems whose adjoint CG did not converge; overflow: 1 if
+    the launch's 201-NN survivor buffer overflowed (knn_status[0] != 0); the sum and the maximum of the forward CG
+    iteration counts stats[:, 1].  A launch was exact iff bad == 0 and overflow == 0.  Torch ops on (E, .) tensors
+    only, no host read, no data-dependent shape: the same on CPU tensors and inside a stream capture."""
+    miss = [stats[:, 0] == 0, desc[:, HD_FPS_TIMEOUT] != 0] + ([stats_bwd[:, 0] == 0] if stats_bwd is not None else [])
+    bad, iters = torch.cat(miss).sum(dtype=torch.int32), stats[:, 1].to(torch.int32)
+    return torch.stack((bad, knn_status[0] != 0, iters.sum(dtype=torch.int32), iters.max()))  # (the flag is promoted)
 
 
 def head_prototypes(hb, support_y, shot_keep, sfeat_pm, qfeat_pm, feat_ep_rows=0):
@@ -383,9 +398,8 @@ def label_propagate(hb, nbr, sigma, alpha=0.99, max_iter=200, tol=1e-6):
                 hb.E, _p(hb.Y[pl:]), _p(hb.n_nodes_ptr()), 32, hb.n_cap, hb.kp1, float(alpha), int(max_iter), float(tol),
                 _p(hb.Z[pl:]), _p(hb.lp_ws), hb.lp_words, hb.lp_stride, _p(hb.stats2), 2, _st()))
             # one {converged, iterations} pair per system for the callers: converged = both, iterations = the larger
-            st1 = hb.stats.view(hb.E, 2)
-            st1[:, 0] = torch.minimum(st1[:, 0], hb.stats2[:, 0])
-            st1[:, 1] = torch.maximum(st1[:, 1], hb.stats2[:, 1])
+            hb.stats[:, 0] = torch.minimum(hb.stats[:, 0], hb.stats2[:, 0])
+            hb.stats[:, 1] = torch.maximum(hb.stats[:, 1], hb.stats2[:, 1])
     return hb.Z
 
 
@@ -418,9 +432,8 @@ def logits_ce(Z, z_ep_rows, n_proto_ptr, desc_stride, E, n_q, N, n_classes, labe
 
 
 def query_logits_ce(hb, n_q, n_classes, labels):
-    """logits_ce of the label-propagation result in hb (E = 1: without the episode axis, the loss 0-d)."""
-    out = logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), 32, hb.E, n_q, hb.N, n_classes, labels)
-    return tuple(t[0] for t in out) if hb.E == 1 else out
+    """logits_ce of the label-propagation result in hb."""
+    return logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), 32, hb.E, n_q, hb.N, n_classes, labels)
 
 
 def logits_ce_from_rows(Z, E, n_q, N, n_classes, labels):

@@ -80,11 +80,11 @@ def test_short_workspace_is_an_error_not_an_overrun():
     assert lib.r3d_edge_reverse(ops._p(idx), 2, 64, 8, ops._p(ws), ws.numel(), ops._st()) != 0
     assert b"workspace" in lib.r3d_last_error_string()
     hb = ops.HeadBuffers(2, 1, 256, 512, 100, 200, 192, "cuda")
-    hb.desc[ops.HD_N_PROTO] = 10
-    hb.desc[ops.HD_N_NODES] = 522
+    hb.desc[0, ops.HD_N_PROTO] = 10
+    hb.desc[0, ops.HD_N_NODES] = 522
     nbr = torch.zeros(hb.n_cap, hb.kp1, device="cuda", dtype=torch.int32)
-    short = hb.lp_ws[:hb.lp_ws.numel() - 64]
+    short = hb.lp_ws[0, :hb.lp_ws.numel() - 64]
     rc = lib.r3d_label_propagate(ops._p(hb.nodes), hb.nodes.stride(0), hb.D, ops._p(nbr), hb.kp1, ops._p(hb.Y),
-                                 ops._p(hb.desc[ops.HD_N_NODES:]), ops._p(hb.desc[ops.HD_N_PROTO:]), hb.n_cap, 1.0, 0.99, 10, 1e-6,
+                                 ops._p(hb.n_nodes_ptr()), ops._p(hb.n_proto_ptr()), hb.n_cap, 1.0, 0.99, 10, 1e-6,
                                  ops._p(hb.Z), ops._p(short), short.numel(), ops._p(hb.stats), ops._st())
     assert rc != 0 and b"workspace" in lib.r3d_last_error_string()

@@ -51,10 +51,10 @@ def test_prototypes_bitexact_indices(ops, n_way, k_shot, N, k_sub, seed):
     sy = support_y.reshape(Sx, N).to(torch.int32).contiguous().cuda()
     ops.head_prototypes(hb, sy, None, sfeat, qfeat.cuda())
     torch.cuda.synchronize()
-    desc = hb.desc.cpu().numpy()
-    ws = hb.proto_ws.cpu().numpy()
+    desc = hb.desc[0].cpu().numpy()
+    ws = hb.proto_ws[0].cpu().numpy()
     comp_off, _, _, _, sel_off, seeds_off = hb.ws_off
-    assign = hb.assign.cpu().numpy()
+    assign = hb.assign[0].cpu().numpy()
     nodes = hb.nodes.cpu()
     Y = torch.cat([hb.Y[p * hb.n_cap:(p + 1) * hb.n_cap] for p in range(hb.planes)], 1).cpu()  # (n_cap, 4 or 8) one-hot
     segs = _segments(support_y)
@@ -104,7 +104,7 @@ def test_prototype_count_follows_torch_cluster(ops, fg_counts):
         hb.desc.zero_()
         ops.head_prototypes(hb, support_y.reshape(n_way, N).contiguous().cuda(), None, feat.cuda(), qfeat.cuda())
         torch.cuda.synchronize()
-        desc = hb.desc.cpu().numpy()
+        desc = hb.desc[0].cpu().numpy()
         nodes = hb.nodes.cpu()
         row = 0
         for s, ids in enumerate(_segments(support_y)):
@@ -140,15 +140,15 @@ def test_label_propagation_vs_closed_form(ops, n_proto, n_q_pts, cap_extra):
     hb.nodes[n:] = 7.0  # garbage beyond n must be ignored
     hb.Y.zero_()
     hb.Y[:n] = Y.cuda()
-    hb.desc[ops.HD_N_PROTO] = n_proto
-    hb.desc[ops.HD_N_NODES] = n
-    nbr = ops.knn(hb.nodes, 1, hb.n_cap, 201, mode=ops.SCORE_L2, n_valid=hb.desc[ops.HD_N_NODES:], status=hb.knn_status)
+    hb.desc[0, ops.HD_N_PROTO] = n_proto
+    hb.desc[0, ops.HD_N_NODES] = n
+    nbr = ops.knn(hb.nodes, 1, hb.n_cap, 201, mode=ops.SCORE_L2, n_valid=hb.n_nodes_ptr(), status=hb.knn_status)
     assert int(hb.knn_status.item()) == 0
     want_nbr = O.knn_l2(x, 201)
     assert np.array_equal(nbr.cpu().numpy()[0, :n].astype(np.int64), want_nbr.numpy()), "201-NN indices differ"
     Z = ops.label_propagate(hb, nbr, 1.0, 0.99, 300, 1e-6)
     torch.cuda.synchronize()
-    conv, iters = hb.stats.cpu().tolist()
+    conv, iters = hb.stats[0].cpu().tolist()
     assert conv == 1, "CG did not converge in 300 iterations"
     A = O.affinity(x, 200, 1.0)
     Zw = O.label_propagate(A, Y[:, :3])
@@ -180,12 +180,12 @@ def test_label_propagation_on_clustered_features(ops, sep, n_proto):
     hb.nodes[:n] = x.cuda()
     hb.Y.zero_()
     hb.Y[:n] = Y.cuda()
-    hb.desc[ops.HD_N_PROTO] = n_proto
-    hb.desc[ops.HD_N_NODES] = n
-    nbr = ops.knn(hb.nodes, 1, hb.n_cap, 201, mode=ops.SCORE_L2, n_valid=hb.desc[ops.HD_N_NODES:], status=None)
+    hb.desc[0, ops.HD_N_PROTO] = n_proto
+    hb.desc[0, ops.HD_N_NODES] = n
+    nbr = ops.knn(hb.nodes, 1, hb.n_cap, 201, mode=ops.SCORE_L2, n_valid=hb.n_nodes_ptr(), status=None)
     Z = ops.label_propagate(hb, nbr, 1.0, 0.99, 300, 1e-6)
     torch.cuda.synchronize()
-    conv, iters = hb.stats.cpu().tolist()
+    conv, iters = hb.stats[0].cpu().tolist()
     A = O.affinity(x, 200, 1.0)
     Z64 = O.label_propagate(A, Y[:, :3], dtype=torch.float64)
     scale = Z64.abs().max().item()
@@ -215,11 +215,11 @@ def test_logits_and_cross_entropy(ops):
     n_q, N = 2, 512
     hb = ops.HeadBuffers(2, 1, N, n_q * N, 100, 200, 192, "cuda")
     n_proto = 287
-    hb.desc[ops.HD_N_PROTO] = n_proto
+    hb.desc[0, ops.HD_N_PROTO] = n_proto
     Z = torch.from_numpy(np.random.RandomState(9).randn(hb.n_cap, 4).astype(np.float32))
     hb.Z.copy_(Z)
     labels = torch.from_numpy(np.random.RandomState(10).randint(0, 3, (n_q, N)).astype(np.int64))
-    logits, loss, pred = ops.query_logits_ce(hb, n_q, 3, labels.cuda())
+    logits, loss, pred = (t[0] for t in ops.query_logits_ce(hb, n_q, 3, labels.cuda()))
     want_logits = Z[n_proto:n_proto + n_q * N, :3].view(n_q, N, 3).transpose(1, 2)
     assert torch.equal(logits.cpu(), want_logits.contiguous())
     want_loss = torch.nn.functional.cross_entropy(want_logits, labels)

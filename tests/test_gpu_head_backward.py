@@ -236,8 +236,8 @@ def test_the_adjoint_refuses_a_width_that_is_no_multiple_of_4(ops):
     lib = _lib.load()
     hb = ops.HeadBuffers(2, 1, 64, 64, 4, 8, 132, "cuda")
     hb.nodes.zero_(); hb.Y.zero_(); hb.Z.zero_()
-    hb.desc[ops.HD_N_PROTO] = 10
-    hb.desc[ops.HD_N_NODES] = 74
+    hb.desc[0, ops.HD_N_PROTO] = 10
+    hb.desc[0, ops.HD_N_NODES] = 74
     nbr = torch.zeros(hb.n_cap, hb.kp1, device="cuda", dtype=torch.int32)
     G = torch.zeros(hb.n_cap, 4, device="cuda")
     lam = torch.full((hb.n_cap, 4), 3.0, device="cuda")

@@ -188,8 +188,8 @@ def test_mpti_eval_logits_against_the_oracle(D):
     assert feat_hip.shape[1] == 64 + D + 64
     assert _close(feat_hip.double(), feat_ref) <= TOL, _close(feat_hip.double(), feat_ref)
     from r3dfsseg_amd import ops
-    n_proto = int(hb.desc[ops.HD_N_PROTO].item())
-    n = int(hb.desc[ops.HD_N_NODES].item())
+    n_proto = int(hb.desc[0, ops.HD_N_PROTO].item())
+    n = int(hb.desc[0, ops.HD_N_NODES].item())
     nodes = hb.nodes[:n].cpu()
     A = O.affinity(nodes, cfg["k_connect"], cfg["sigma"])
     Zo = O.label_propagate(A, hb.Y[:n, :n_way + 1].cpu(), dtype=torch.float64)

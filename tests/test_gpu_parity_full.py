@@ -121,8 +121,8 @@ def test_full_size_eval_chain_of_custody(workload, ev):
     bg_p, bg_l, _, _ = O.get_background_prototypes(sf4, torch.logical_not(sy), cfg["n_subprototypes"], n_way + 1)
     aux = dict(prototypes=torch.cat((bg_p, fg_p), 0), n_proto=bg_p.shape[0] + fg_p.shape[0],
                query_feat=qfeat_cm.transpose(1, 2).reshape(-1, sfeat_cm.shape[1]))
-    n_proto = int(hb.desc[ops.HD_N_PROTO].item())
-    n = int(hb.desc[ops.HD_N_NODES].item())
+    n_proto = int(hb.desc[0, ops.HD_N_PROTO].item())
+    n = int(hb.desc[0, ops.HD_N_NODES].item())
     assert n_proto == aux["n_proto"] and n == n_proto + qx.shape[0] * N
     nodes = hb.nodes[:n].cpu()
     # equal prototypes to 1e-5 mean: same FPS seeds, same nearest-seed assignment, same cluster means
@@ -190,7 +190,7 @@ def test_config2_full_size_training_episode_gradients():
     # would otherwise put one different edge into the graph the gradient flows through
     from r3dfsseg_amd import ops
     hb = m._head_buffers(qx.shape[0], ep[0].device)
-    n_proto, n = int(hb.desc[ops.HD_N_PROTO].item()), int(hb.desc[ops.HD_N_NODES].item())
+    n_proto, n = int(hb.desc[0, ops.HD_N_PROTO].item()), int(hb.desc[0, ops.HD_N_NODES].item())
     nodes = hb.nodes[:n].cpu()
     nbr_hip = tr["nbr"].reshape(hb.n_cap, hb.kp1)[:n].cpu().to(torch.int64)
     assert torch.equal(nbr_hip, O.knn_l2(nodes, hb.kp1))

@@ -300,7 +300,7 @@ def test_head_losses_and_feature_gradients(n_way, k_shot):
     closs = contrast.per_way_contrast_loss(m, sg, sy.cuda(), flag.cuda())
     lploss = head_train.HeadLPFn.apply(sg, qg, m, sy.cuda(), qy.cuda())
     (lploss + 0.1 * closs).backward()
-    assert m._head[1].stats.cpu().tolist()[0] == 1 and m._head[1].stats_bwd.cpu().tolist()[0] == 1
+    assert m._head[1].stats[0].cpu().tolist()[0] == 1 and m._head[1].stats_bwd[0].cpu().tolist()[0] == 1
     # --- oracle (torch-CPU autograd through the restated head)
     so, qo = sfeat.clone().requires_grad_(), qfeat.clone().requires_grad_()
     sdr = {k: v.clone() for k, v in sd.items()}
@@ -349,7 +349,7 @@ def test_training_episode_with_more_than_three_ways(n_way, k_shot):
     sdh = {k_: v.clone() for k_, v in sd.items()}
     sdh["proj.weight"].requires_grad_(); sdh["proj.bias"].requires_grad_()
     hb = m._head[1]
-    n_proto, n = int(hb.desc[ops.HD_N_PROTO].item()), int(hb.desc[ops.HD_N_NODES].item())
+    n_proto, n = int(hb.desc[0, ops.HD_N_PROTO].item()), int(hb.desc[0, ops.HD_N_NODES].item())
     nbr_hip = tr["nbr"].reshape(hb.n_cap, hb.kp1)[:n].cpu().to(torch.int64)
     assert torch.equal(nbr_hip, O.knn_l2(hb.nodes[:n].cpu(), hb.kp1))
     ref, aux = O.mpti_head(sdh, cfg, so, qo, sx, sy, qy, gt_support_y=gsy, gt_query_y=gqy, train=True, support_flag=flag,

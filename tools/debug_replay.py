@@ -44,20 +44,20 @@ for trial in range(300):
         if c[k][0] == 0:
             continue
         hb = sl.state.last[1]
-        n = int(hb.desc[ops.HD_N_NODES])
+        n = int(hb.desc[0, ops.HD_N_NODES])
         print("trial %d slot %d: replay bad, fwd %s adjoint %s FPS time-out %d 201-NN %s | nodes finite %s" % (
-            trial, k, hb.stats.tolist(), hb.stats_bwd.tolist(), int(hb.desc[ops.HD_FPS_TIMEOUT]), hb.knn_status.tolist(),
+            trial, k, hb.stats[0].tolist(), hb.stats_bwd[0].tolist(), int(hb.desc[0, ops.HD_FPS_TIMEOUT]), hb.knn_status.tolist(),
             bool(torch.isfinite(hb.nodes[:n]).all())), flush=True)
         # 1. the same solve again, alone on the device, from the node matrix the replay left behind
         Z_replay, stats_replay = hb.Z[:n].clone(), hb.stats.clone()
         n_, rp, col, val = hb.csr()
         rp0, col0, val0 = rp.clone(), col.clone(), val.clone()
         Y0 = hb.Y[:n].clone()
-        nbr = ops.knn(hb.nodes, 1, hb.n_cap, hb.kp1, mode=ops.SCORE_L2, n_valid=hb.desc[ops.HD_N_NODES:], status=hb.knn_status)
+        nbr = ops.knn(hb.nodes, 1, hb.n_cap, hb.kp1, mode=ops.SCORE_L2, n_valid=hb.n_nodes_ptr(), status=hb.knn_status)
         ops.label_propagate(hb, nbr, model.sigma, 0.99, 200, model.lp_tol)
         torch.cuda.synchronize()
         print("   same node matrix solved again alone: %s ; Z vs the replay's: max diff %.3e" % (
-            hb.stats.tolist(), (hb.Z[:n] - Z_replay).abs().max().item()), flush=True)
+            hb.stats[0].tolist(), (hb.Z[:n] - Z_replay).abs().max().item()), flush=True)
         n_, rp1, col1, val1 = hb.csr()
         nnz0, nnz1 = int(rp0[n]), int(rp1[n])
         same_rp = torch.equal(rp0[:n + 1], rp1[:n + 1])
@@ -80,7 +80,7 @@ for trial in range(300):
             hb2 = model._slot.last[1]
             d = (hb2.nodes[:n] - nodes_replay).abs()
             print("   eager arith %d, same seed: fwd %s | nodes vs replay: max diff %.3e (max |.| %.3g), rows differing > 1e-4: %d" % (
-                mode, hb2.stats.tolist(), d.max().item(), nodes_replay.abs().max().item(), int((d.amax(1) > 1e-4).sum())), flush=True)
+                mode, hb2.stats[0].tolist(), d.max().item(), nodes_replay.abs().max().item(), int((d.amax(1) > 1e-4).sum())), flush=True)
             sl.state.fixed_budget = saved_budget
         _lib.check(lib.r3d_set_matrix_arith(1))
         model._slot = default_slot

@@ -43,10 +43,10 @@ for i in range(steps):
         from r3dfsseg_amd import ops
         for k, sl in enumerate(trainer.graphs.slots):
             hb = sl.state.last[1]
-            n = int(hb.desc[ops.HD_N_NODES])
+            n = int(hb.desc[0, ops.HD_N_NODES])
             print("  slot %d: fwd (converged, its) %s  adjoint %s  FPS time-out %d  201-NN status %s  n_nodes %d n_proto %d  nodes finite %s max %.3g  Z finite %s" % (
-                k, hb.stats.tolist(), hb.stats_bwd.tolist(), int(hb.desc[ops.HD_FPS_TIMEOUT]), hb.knn_status.tolist(), n,
-                int(hb.desc[ops.HD_N_PROTO]), bool(torch.isfinite(hb.nodes[:n]).all()), hb.nodes[:n].abs().max().item(),
+                k, hb.stats[0].tolist(), hb.stats_bwd[0].tolist(), int(hb.desc[0, ops.HD_FPS_TIMEOUT]), hb.knn_status.tolist(), n,
+                int(hb.desc[0, ops.HD_N_PROTO]), bool(torch.isfinite(hb.nodes[:n]).all()), hb.nodes[:n].abs().max().item(),
                 bool(torch.isfinite(hb.Z[:n]).all())), flush=True)
         print("  counters of that run:", trainer.graphs.counters.tolist(), "active budget", trainer.graphs.active_budget)
         break
@@ -68,7 +68,7 @@ for mode in (1, 0):
         sf, qf = model._trace["sfeat"], model._trace["qfeat"]
         hb = model._head_buffers(ep[2].shape[0], dev)
         rows.append((bool(torch.isfinite(sf).all() and torch.isfinite(qf).all()), sf.abs().max().item(), qf[:, 64:128].abs().max().item(),
-                     hb.stats.tolist(), float(out[1])))
+                     hb.stats[0].tolist(), float(out[1])))
     print("arith %d:" % mode)
     for r in rows:
         print("   features finite %s  max |sfeat| %.3g  max |att part of qfeat| %.3g  LP (converged, iterations) %s  lp_loss %.4f" % r)

@@ -36,7 +36,7 @@ n, row_ptr, col, val = hb.csr()
 row_ptr, col, val = row_ptr.cpu().numpy(), col.cpu().numpy().astype(np.int32), val.cpu().numpy()
 nnz = int(row_ptr[n])
 np.savez_compressed(out, n=n, row_ptr=row_ptr[:n + 1].copy(), col=col[:nnz].copy(), val=val[:nnz].copy(),
-                    Y=hb.Y.cpu().numpy()[:n], Z=hb.Z.cpu().numpy()[:n], stats=hb.stats.cpu().numpy(),
-                    nodes=hb.nodes.cpu().numpy()[:n].astype(np.float16), n_proto=int(hb.desc[ops.HD_N_PROTO].item()),
+                    Y=hb.Y.cpu().numpy()[:n], Z=hb.Z.cpu().numpy()[:n], stats=hb.stats[0].cpu().numpy(),
+                    nodes=hb.nodes.cpu().numpy()[:n].astype(np.float16), n_proto=int(hb.desc[0, ops.HD_N_PROTO].item()),
                     query_y=pool[3][3].cpu().numpy())
-print("dumped n", n, "nnz", nnz, "stats (converged, iterations)", hb.stats.cpu().numpy())
+print("dumped n", n, "nnz", nnz, "stats (converged, iterations)", hb.stats[0].cpu().numpy())
