@@ -912,6 +912,60 @@ int r3d_scene_obj_stats(const float* scan, int ld, long M, float x0, float y0, f
 int r3d_scene_obj_ids(long M, long n_units, long n_objects, const int32_t* unit_index, int32_t* objects, int32_t* ws,
                       long ws_words, void* stream);
 
+/* ---- match_objects: a scan's objects against ground-truth instances ("Matching objects against ground
+ * truth", M1-M8).  Additive: no entry point above changes.  The reference scores points only (eval_noise.py:23-72); the
+ * definition is this project's.  pred, truth: M object ids each, int32 (bytes 4) or int64 (8), read as they are; g < 0: the
+ * point is in no object; legal ids are 0 .. 2^31 - 2.  With ignore_unannotated a point whose truth id is negative takes part in
+ * nothing (M1).  The labels, for both columns or for none (NULL): M classes each, int32 or int64.  ws: ONE int32 scratch of
+ * r3d_scene_match_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the four calls of one matching; its first 32 words are
+ * the record the host reads (column 0 is pred, 1 truth):
+ *   [0] [1] per column the largest legal id of a participating point + 1 (0: none)   [2] [3] per column the participating
+ *   points with a negative id   [4] points M1 took out   [5] ids >= 2^31 - 1, both columns   [6..7] the largest of those (uint64)
+ *   [8] pred rows P   [9] truth rows T   [10] [11] per column the rows in which some point carries another label than the
+ *   row's first   [12] points with a row in both columns   [13] pairs
+ *
+ *   entry point            what it does                                                                  host reads
+ *   r3d_scene_match_ids    zeroes the record, then words 0 .. 7 of it (integer maxima and counts, one atomic per word
+ *                          and workgroup)                                                                words 0 .. 7
+ *   r3d_scene_match_rows   max_pred, max_truth: words 0 and 1 as read, less one (both >= 0); n_pred_in, n_truth_in: M less
+ *                          word 4 less word 2 / 3.  Per column the stable LSD radix sort of (id, scan index), 1 .. 4 passes
+ *                          by the largest key (a point without a row sorts under the largest id + 1), run heads, their
+ *                          exclusive scan, the row tables in ws (rows in ascending id order, a row's points by ascending
+ *                          scan index); pred_index, truth_index (M,) int32: the row of the point, -1 without one.  With
+ *                          labels: every point of a run against the label of the run's head.            words 8 .. 11
+ *   r3d_scene_match_pairs  n_pred, n_truth: words 8 and 9 as read (both >= 1).  pred_ids (P,) int64, pred_points (P,) int32
+ *                          and, with labels, pred_classes (P,) int64, the label of the row's point with the lowest scan
+ *                          index; the same for truth.  Then two stable sorts of 32-bit keys: by truth row, then by the pred
+ *                          row gathered through the first order (a point without both rows: the keys T and P, last); heads
+ *                          where (p, t) changes, their scan, the pair tables in ws in ascending (p, t).   words 12, 13
+ *   r3d_scene_match_best   n_pairs: word 13 as read.  thresholds: n_iou <= 8 floats in HOST memory, ascending, each in
+ *                          (0, 1].  pair_pred, pair_truth, pair_points (n_pairs,) int32; pair_iou (n_pairs,) fp32 =
+ *                          (float)inter / (float)(pred_points[p] + truth_points[t] - inter), one IEEE division; a pair is
+ *                          ELIGIBLE without classes, or when the two classes are equal.  truth_best (T,) int32: per eligible
+ *                          pair one 64-bit integer atomicMax on (iou bits << 32) | (0xFFFFFFFF - p), then the pair whose
+ *                          value won; pred_best (P,) int32: a segmented maximum over the contiguous pairs of p on
+ *                          (iou bits << 32) | (0xFFFFFFFF - pair row), one integer atomicMax per run and workgroup; -1
+ *                          without an eligible pair.  pair_match (n_pairs,) bytes, written last: for a pair that is the
+ *                          best of both its rows the number of thresholds its IoU meets, else 0.  best_words: n_pred +
+ *                          n_truth int64 of the caller's scratch.                                         -
+ * No float goes through an atomic: the same columns give the same bits. */
+long r3d_scene_match_ws_words(long M);
+int r3d_scene_match_ids(const void* pred, int pred_bytes, const void* truth, int truth_bytes, long M, int ignore_unannotated,
+                        int32_t* ws, long ws_words, void* stream);
+int r3d_scene_match_rows(const void* pred, int pred_bytes, const void* truth, int truth_bytes, const void* pred_labels,
+                         int pred_label_bytes, const void* truth_labels, int truth_label_bytes, long M, int ignore_unannotated,
+                         long max_pred, long max_truth, long n_pred_in, long n_truth_in, int32_t* pred_index,
+                         int32_t* truth_index, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_match_pairs(long M, long n_pred, long n_truth, const int32_t* pred_index, const int32_t* truth_index,
+                          const void* pred_labels, int pred_label_bytes, const void* truth_labels, int truth_label_bytes,
+                          int64_t* pred_ids, int32_t* pred_points, int64_t* pred_classes, int64_t* truth_ids,
+                          int32_t* truth_points, int64_t* truth_classes, int32_t* ws, long ws_words, void* stream);
+int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pairs, const int32_t* pred_points, const int32_t* truth_points,
+                         const int64_t* pred_classes, const int64_t* truth_classes, const float* thresholds, int n_iou,
+                         int32_t* pair_pred, int32_t* pair_truth, int32_t* pair_points, float* pair_iou, int32_t* pred_best,
+                         int32_t* truth_best, uint8_t* pair_match, int64_t* best_words, const int32_t* ws, long ws_words,
+                         void* stream);
+
 /* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.

@@ -293,6 +293,16 @@ class FittedLearner(object):
         from . import scene_objects
         return scene_objects.extract_objects(scan, labels, voxel, connectivity, min_points, ignore)
 
+    def match_objects(self, pred, truth, pred_labels=None, truth_labels=None, iou=(0.25, 0.5, 0.75), ignore_unannotated=False):
+        """How good the objects are: pred, truth (M,) int32 or int64 object ids of the same points (negative: in no object),
+        e.g. the .objects of extract_objects on predicted and on true labels; with pred_labels and truth_labels (both or
+        neither) only objects of one class are paired.  Pairs of objects that share a point, their IoU, every object's best
+        partner and the mutual bests at the thresholds `iou`: a scene_match.ObjectMatch whose .summary holds precision,
+        recall, F1 and panoptic quality per threshold and class (scene_match.py; INTEGRATION.md, "Matching objects against
+        ground truth").  Needs no fit and no model."""
+        from . import scene_match
+        return scene_match.match_objects(pred, truth, pred_labels, truth_labels, iou, ignore_unannotated)
+
     def fit_scene(self, scan, labels, classes, block_size=1.0, stride=None, min_points=100, min_ratio=0.05, min_fg=100,
                   eval=False):
         """fit() from an annotated scan instead of cut-out clouds: scan as for predict_scene, labels (M,) int32 or int64

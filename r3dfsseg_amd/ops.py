@@ -1211,6 +1211,86 @@ def scene_obj_ids(unit_index, n_units, n_objects, ws):
     return objects
 
 
+# ---- match_objects: a scan's objects against ground-truth instances (scene_match.py)
+SCENE_MATCH_REC = 32   # MT_REC of csrc/scene_match.hip: words of the record in front of the workspace
+SCENE_MATCH_IOU = 8    # MT_MAX_IOU: thresholds of one call
+# the record's words (include/r3d.h, "match_objects"); the first four come per column, pred then truth
+MATCH_R_MAX1, MATCH_R_NNEG, MATCH_R_NIGNORED, MATCH_R_NBAD, MATCH_R_BADMAX = 0, 2, 4, 5, 6
+MATCH_R_ROWS, MATCH_R_MIXED, MATCH_R_NBOTH, MATCH_R_NPAIRS = 8, 10, 12, 13
+
+
+def scene_match_workspace(M, device):
+    return _scene_workspace("match", "match_objects", M, device)
+
+
+def _match_labels_args(pred_labels, truth_labels, M):
+    """-> (pred_labels, bytes, truth_labels, bytes) as the entry points take them; both columns or neither."""
+    assert (pred_labels is None) == (truth_labels is None)
+    if pred_labels is None:
+        return None, 0, None, 0
+    return _p(pred_labels), _label_bytes(pred_labels, M), _p(truth_labels), _label_bytes(truth_labels, M)
+
+
+def scene_match_ids(pred, truth, ignore_unannotated, ws):
+    """pred, truth (M,) int32 or int64 on the device, read as they are -> words 0 .. 7 of the record in ws, on the device."""
+    M = pred.numel()
+    assert _seg_ws_ok(ws)
+    _lib.check(_lib.load().r3d_scene_match_ids(_p(pred), _label_bytes(pred, M), _p(truth), _label_bytes(truth, M), M,
+                                               int(bool(ignore_unannotated)), _p(ws), ws.numel(), _st()))
+
+
+def scene_match_rows(pred, truth, pred_labels, truth_labels, ignore_unannotated, max_ids, n_in, ws):
+    """After scene_match_ids and the read of its record: max_ids, n_in: per column the largest id and the points with a row.
+    Per column the sort by (id, scan index) and the row tables into ws -> (pred_index, truth_index) (M,) int32; words
+    8 .. 11 of the record."""
+    M = pred.numel()
+    assert _seg_ws_ok(ws)
+    pred_index, truth_index = (torch.empty(M, device=pred.device, dtype=torch.int32) for _ in range(2))
+    _lib.check(_lib.load().r3d_scene_match_rows(_p(pred), _label_bytes(pred, M), _p(truth), _label_bytes(truth, M),
+                                                *_match_labels_args(pred_labels, truth_labels, M), M, int(bool(ignore_unannotated)),
+                                                int(max_ids[0]), int(max_ids[1]), int(n_in[0]), int(n_in[1]), _p(pred_index),
+                                                _p(truth_index), _p(ws), ws.numel(), _st()))
+    return pred_index, truth_index
+
+
+def scene_match_pairs(pred_index, truth_index, pred_labels, truth_labels, n_pred, n_truth, ws):
+    """After the read of P and T (both >= 1): the row tables -> ((pred_ids (P,) int64, pred_points (P,) int32, pred_classes
+    (P,) int64 or None), the same for truth); the two sorts and the pair tables into ws; words 12 and 13 of the record."""
+    M = pred_index.numel()
+    ok = lambda t: tuple(t.shape) == (M,) and t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert _seg_ws_ok(ws) and ok(pred_index) and ok(truth_index) and n_pred >= 1 and n_truth >= 1
+    dev = pred_index.device
+
+    def tables(n):
+        return (torch.empty(n, device=dev, dtype=torch.int64), torch.empty(n, device=dev, dtype=torch.int32),
+                torch.empty(n, device=dev, dtype=torch.int64) if pred_labels is not None else None)
+    pt, tt = tables(int(n_pred)), tables(int(n_truth))
+    _lib.check(_lib.load().r3d_scene_match_pairs(M, int(n_pred), int(n_truth), _p(pred_index), _p(truth_index),
+                                                 *_match_labels_args(pred_labels, truth_labels, M), _p(pt[0]), _p(pt[1]), _p(pt[2]),
+                                                 _p(tt[0]), _p(tt[1]), _p(tt[2]), _p(ws), ws.numel(), _st()))
+    return pt, tt
+
+
+def scene_match_best(M, pred_tables, truth_tables, n_pairs, thresholds, ws):
+    """After the read of n_pairs: pred_tables, truth_tables as scene_match_pairs returned them; thresholds: 1 .. 8 floats,
+    ascending -> (pair_pred, pair_truth, pair_points (n_pairs,) int32, pair_iou (n_pairs,) fp32, pred_best (P,) int32,
+    truth_best (T,) int32, pair_match (n_pairs,) uint8)."""
+    (_, p_points, p_classes), (_, t_points, t_classes) = pred_tables, truth_tables
+    P, T, K, dev = p_points.numel(), t_points.numel(), int(n_pairs), p_points.device
+    assert _seg_ws_ok(ws) and 1 <= len(thresholds) <= SCENE_MATCH_IOU and (p_classes is None) == (t_classes is None)
+    pair_pred, pair_truth, pair_points = (torch.empty(K, device=dev, dtype=torch.int32) for _ in range(3))
+    pair_iou = torch.empty(K, device=dev, dtype=torch.float32)
+    pair_match = torch.empty(K, device=dev, dtype=torch.uint8)
+    pred_best, truth_best = torch.empty(P, device=dev, dtype=torch.int32), torch.empty(T, device=dev, dtype=torch.int32)
+    words = torch.empty(P + T, device=dev, dtype=torch.int64)  # the kernels' scratch
+    th = (ctypes.c_float * len(thresholds))(*[float(v) for v in thresholds])  # read on the host by the entry point
+    nz = lambda t: _p(t) if t.numel() else None
+    _lib.check(_lib.load().r3d_scene_match_best(M, P, T, K, _p(p_points), _p(t_points), _p(p_classes), _p(t_classes), th,
+                                                len(thresholds), nz(pair_pred), nz(pair_truth), nz(pair_points), nz(pair_iou),
+                                                _p(pred_best), _p(truth_best), nz(pair_match), _p(words), _p(ws), ws.numel(), _st()))
+    return pair_pred, pair_truth, pair_points, pair_iou, pred_best, truth_best, pair_match
+
+
 # ---------------------------------------------------------------------------------------------- cutting episodes (block_pool.py)
 def _episode_cut_args(points, labels, offsets, desc, classes, S, Q, N, out, mask, gt_mask, query_y, gt_query_y, slot_map):
     E, n_way = classes.shape
