@@ -966,6 +966,51 @@ int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pairs, const 
                          int32_t* truth_best, uint8_t* pair_match, int64_t* best_words, const int32_t* ws, long ws_words,
                          void* stream);
 
+/* ---- smooth_scene: the scores of a labelled scan propagated over the voxel graph ("Smoothing a labelled
+ * scan", S1-S7).  Additive: no entry point above changes.  The reference has no such function; the definition is this
+ * project's.  The grid, the sort and the voxel table are those of build_segments: r3d_scene_grow_bounds, _sort and _voxels
+ * run first, as they are, and ws, M, nx, ny, nz below are theirs.  V = n_voxels (word 7 as read), C = n_cols <= 64.  Every
+ * float operation is fp32 and rounded on its own (__fadd_rn, __fmul_rn, __fdiv_rn); none goes through an atomic.
+ *
+ *   r3d_scene_smooth_evidence  scores (M, C) fp32, votes (M,) int32: those of the result.  A CONTRIBUTOR is a valid point
+ *                              with votes > 0, its row scores[p] / (float)votes[p].  voxel_evidence (V, C) fp32: per voxel
+ *                              the contributors' rows by ascending scan index, summed as r3d_scene_seg_pool sums a segment
+ *                              (ranks in tiles of 256, part = the first row, += the next, tot = the first tile's part, +=
+ *                              the next), tot / (float)members; zeros without a member.  voxel_members (V,) int32;
+ *                              voxel_ring (V,) int32: 0 with a member, else -1.
+ *   r3d_scene_smooth_graph     voxel_neighbours (26, V) int32, slot-major: column v holds the rows of the occupied voxels
+ *                              among the 6 or 26 cells around voxel v, found by their coordinates as r3d_scene_grow_absorb
+ *                              finds them, in ascending key order, packed to the front, -1 behind them.  With voxel_mean
+ *                              (V, 3) (else NULL) a neighbour must pass the colour test of r3d_scene_grow_union as well: a
+ *                              NaN mean joins nothing.
+ *   r3d_scene_smooth_sweep     `iterations` (0 .. 64) launches, sweep t = 0, 1, ...: sweep t reads Z_t (t = 0: voxel_evidence,
+ *                              else z[(t - 1) & 1]) and writes z[t & 1]; z0, z1 (V, C) fp32, two arrays (z1 may be NULL below
+ *                              two sweeps, z0 below one).  The result lies in z[(iterations - 1) & 1].  A neighbour u is LIVE
+ *                              at t when 0 <= ring[u] <= t.  With n >= 1 live neighbours u_0 < u_1 < ...: s = Z_t[u_0],
+ *                              s += Z_t[u_1], ..., m = s / (float)n; a voxel with a member (ring 0) gets b * Y + a * m, a =
+ *                              alpha, b = 1.0f - a, two multiplications and one addition; one without gets m and, while its
+ *                              ring is -1, ring = t + 1.  With n == 0 the voxel keeps Z_t and its ring.  voxel_ring is ONE
+ *                              array written in place: a reader of the same launch sees -1 or t + 1, and neither is live.
+ *   r3d_scene_smooth_spread    voxel_scores: the last sweep's Z (voxel_evidence without a sweep).  voxel_labels (V,) int64:
+ *                              the arg-max of the row (the lowest column wins a tie, a NaN never replaces a value) where ring
+ *                              >= 0, else -1.  A point whose voxel_index is a row with ring >= 0 is SMOOTHED: scores, labels
+ *                              = the voxel's, votes = 1, smoothed = 1; any other point copies in_scores, in_labels, in_votes,
+ *                              smoothed = 0.  counts: 8 int32 words, zeroed here, by integer atomics aggregated per
+ *                              workgroup: [0] voxels with a member  [1] filled voxels (ring > 0)  [2] smoothed points
+ *                              [3] of them: in_labels >= 0 and the label differs  [4] of them: in_labels == -1
+ *                              [5] labels that are -1 in the result. */
+int r3d_scene_smooth_evidence(long M, int nx, int ny, int nz, int n_cols, const float* scores, const int32_t* votes, long n_voxels,
+                              float* voxel_evidence, int32_t* voxel_members, int32_t* voxel_ring, const int32_t* ws, long ws_words,
+                              void* stream);
+int r3d_scene_smooth_graph(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
+                           float colour_tol, int32_t* voxel_neighbours, const int32_t* ws, long ws_words, void* stream);
+int r3d_scene_smooth_sweep(long M, long n_voxels, int n_cols, int iterations, float alpha, const float* voxel_evidence,
+                           const int32_t* voxel_neighbours, float* z0, float* z1, int32_t* voxel_ring, void* stream);
+int r3d_scene_smooth_spread(long M, int n_cols, long n_voxels, const int32_t* voxel_index, const int32_t* voxel_ring,
+                            const float* voxel_scores, const float* in_scores, const int64_t* in_labels, const int32_t* in_votes,
+                            int64_t* voxel_labels, float* scores, int64_t* labels, int32_t* votes, uint8_t* smoothed,
+                            int32_t* counts, void* stream);
+
 /* ---- Cutting episode clouds from a block pool resident on the device (dataloaders/loader.py:219-237: the per-cloud point
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.

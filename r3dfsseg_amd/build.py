@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libr3d_hip.so")
 SOURCES = ["error.hip", "knn.hip", "gemm.hip", "gemm_bx3.hip", "edgeconv.hip", "attention.hip", "head_proto.hip",
            "head_graph.hip", "aux_heads.hip", "protonet_train.hip", "train_ops.hip", "edgeconv_train.hip", "contrast.hip",
            "augment.hip", "scene_sort.hip", "scene.hip", "scene_segments.hip", "scene_grow.hip", "scene_objects.hip",
-           "scene_match.hip", "episode_cut.hip"]
+           "scene_match.hip", "scene_smooth.hip", "episode_cut.hip"]
 # No packed fp32 vector arithmetic (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32), neither from the SLP vectoriser nor from
 # float2 / float4 source arithmetic: measured on MI355X (profiles/r02_experiments.md, section 9), a wave executing them
 # beside waves of a bf16-MFMA-dense kernel on the same SIMD got wrong results in lanes 48-63 of one half of the pair --

@@ -283,6 +283,17 @@ class FittedLearner(object):
         from . import scene_grow
         return scene_grow.absorb_segments(scan, voxel, colour_tol, connectivity, min_points, normal_tol, absorb)
 
+    def smooth_scene(self, res, scan, voxel=0.05, connectivity=26, alpha=0.8, iterations=10, colour_tol=None):
+        """The scores of a labelled scan propagated over its voxel graph, between predict_scene and extract_objects: res is
+        what predict_scene returned, scan the scan it labels.  The voted logits are pooled per voxel of edge `voxel`, swept
+        `iterations` times over the voxel adjacency graph (Z <- (1 - alpha) Y + alpha (mean of the neighbours' Z); a voxel
+        without a voted point is filled from its neighbours, one ring a sweep) and spread back: a scene_smooth.SmoothResult,
+        which is a SceneResult, so its .labels go to extract_objects and it goes to pool_segments as it is
+        (scene_smooth.py; INTEGRATION.md, "Smoothing a labelled scan").  Needs no fit and no model and changes neither res
+        nor the learner."""
+        from . import scene_smooth
+        return scene_smooth.smooth_scene(res, scan, voxel, connectivity, alpha, iterations, colour_tol)
+
     def extract_objects(self, scan, labels, voxel=0.05, connectivity=26, min_points=1, ignore=()):
         """Object instances from a labelled scan: labels (M,) int32 or int64 are the .labels of what predict_scene,
         predict_scene_sets or pool_segments returned, or ground truth (negative: no class; ignore: class ids that form no

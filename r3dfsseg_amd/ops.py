@@ -1131,6 +1131,76 @@ def scene_grow_ids(voxel_index, n_voxels, n_segments, ws):
     return segments, segment_points
 
 
+# ---- smooth_scene: scores propagated over the voxel graph (scene_smooth.py), on the workspace of build_segments
+SCENE_SMOOTH_SLOTS = 26    # SM_SLOTS of csrc/scene_smooth.hip: neighbour slots of a voxel
+SCENE_SMOOTH_SWEEPS = 64   # SM_SWEEPS_MAX
+SCENE_SMOOTH_COUNTS = 8    # words of the counts (include/r3d.h, "smooth_scene")
+(SMOOTH_R_MEMBER_VOXELS, SMOOTH_R_FILLED_VOXELS, SMOOTH_R_NSMOOTHED, SMOOTH_R_NCHANGED, SMOOTH_R_NFILLED,
+ SMOOTH_R_NUNLAB) = range(6)
+
+
+def _smooth_ok(t, shape, dtype):
+    return tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.is_contiguous() and t.is_cuda
+
+
+def scene_smooth_evidence(scores, votes, grid, n_voxels, ws):
+    """After scene_grow_voxels: scores (M, C) fp32, votes (M,) int32 of the result -> (voxel_evidence (V, C) fp32,
+    voxel_members (V,) int32, voxel_ring (V,) int32: 0 with a member, else -1) by S2."""
+    M, C = scores.shape
+    V, dev = int(n_voxels), scores.device
+    assert _smooth_ok(scores, (M, C), torch.float32) and _smooth_ok(votes, (M,), torch.int32) and _seg_ws_ok(ws)
+    evidence = torch.empty(V, C, device=dev, dtype=torch.float32)
+    members = torch.empty(V, device=dev, dtype=torch.int32)
+    ring = torch.empty(V, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_smooth_evidence(M, *_grid_args(grid), C, _p(scores), _p(votes), V, _p(evidence), _p(members),
+                                                     _p(ring), _p(ws), ws.numel(), _st()))
+    return evidence, members, ring
+
+
+def scene_smooth_graph(M, grid, n_voxels, connectivity, voxel_mean, colour_tol, ws):
+    """-> voxel_neighbours (26, V) int32 by S3: per voxel the rows of its neighbours in ascending key order, -1 behind them;
+    voxel_mean None: adjacency alone."""
+    V = int(n_voxels)
+    assert _seg_ws_ok(ws) and (voxel_mean is None or (_grow_table_ok(voxel_mean, V) and colour_tol is not None))
+    nbr = torch.empty(SCENE_SMOOTH_SLOTS, V, device=ws.device, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_smooth_graph(M, *_grid_args(grid), V, int(connectivity), _p(voxel_mean),
+                                                  0.0 if voxel_mean is None else float(colour_tol), _p(nbr), _p(ws), ws.numel(), _st()))
+    return nbr
+
+
+def scene_smooth_sweep(M, iterations, alpha, evidence, nbr, ring):
+    """`iterations` sweeps of S4, queued without a host read; ring is updated in place -> voxel_scores (V, C) fp32, a tensor
+    of its own (without a sweep: a copy of evidence)."""
+    V, C = evidence.shape
+    n = int(iterations)
+    assert _smooth_ok(evidence, (V, C), torch.float32) and _smooth_ok(nbr, (SCENE_SMOOTH_SLOTS, V), torch.int32)
+    assert _smooth_ok(ring, (V,), torch.int32)
+    if n == 0:
+        return evidence.clone()
+    z = [torch.empty_like(evidence), torch.empty_like(evidence) if n > 1 else None]
+    _lib.check(_lib.load().r3d_scene_smooth_sweep(M, V, C, n, float(alpha), _p(evidence), _p(nbr), _p(z[0]), _p(z[1]), _p(ring),
+                                                  _st()))
+    return z[(n - 1) & 1]
+
+
+def scene_smooth_spread(voxel_index, ring, voxel_scores, in_scores, in_labels, in_votes):
+    """S5, S6 -> (voxel_labels (V,) int64, scores (M, C) fp32, labels (M,) int64, votes (M,) int32, smoothed (M,) bool, counts
+    (8,) int32 on the device: SMOOTH_R_*)."""
+    M, C = in_scores.shape
+    V, dev = voxel_scores.shape[0], in_scores.device
+    assert _smooth_ok(voxel_index, (M,), torch.int32) and _smooth_ok(ring, (V,), torch.int32)
+    assert _smooth_ok(voxel_scores, (V, C), torch.float32) and _smooth_ok(in_scores, (M, C), torch.float32)
+    assert _smooth_ok(in_labels, (M,), torch.int64) and _smooth_ok(in_votes, (M,), torch.int32)
+    voxel_labels = torch.empty(V, device=dev, dtype=torch.int64)
+    scores, labels, votes = torch.empty_like(in_scores), torch.empty_like(in_labels), torch.empty_like(in_votes)
+    smoothed = torch.empty(M, device=dev, dtype=torch.bool)
+    counts = torch.empty(SCENE_SMOOTH_COUNTS, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().r3d_scene_smooth_spread(M, C, V, _p(voxel_index), _p(ring), _p(voxel_scores), _p(in_scores),
+                                                   _p(in_labels), _p(in_votes), _p(voxel_labels), _p(scores), _p(labels), _p(votes),
+                                                   _p(smoothed), _p(counts), _st()))
+    return voxel_labels, scores, labels, votes, smoothed, counts
+
+
 # ---- extract_objects: objects from a labelled scan (scene_objects.py)
 SCENE_OBJ_IGNORE = 64          # OB_IGNORE_MAX of csrc/scene_objects.hip: entries of the ignore table
 SCENE_OBJ_LABEL = 2 ** 31 - 2  # OB_LABEL_MAX: the largest label a key holds

@@ -90,18 +90,24 @@ def _check_voxel(what, voxel, connectivity, min_points):
     return v32
 
 
+def _check_colour(what, colour_tol, scan):
+    """colour_tol: None, or finite and >= 0 (in float32 too), and then the scan has colour columns."""
+    if colour_tol is None:
+        return
+    with np.errstate(over="ignore", under="ignore"):
+        t32 = np.float32(colour_tol) if _is_real(colour_tol) else np.float32(np.nan)
+    if not (_is_real(colour_tol) and np.isfinite(colour_tol) and colour_tol >= 0 and np.isfinite(t32)):
+        raise ValueError("%s: colour_tol %r must be None or a finite float >= 0" % (what, colour_tol))
+    if scan.shape[1] < 6:
+        raise ValueError("%s: colour_tol %r given, but a scan of %d columns has no colour (x y z r g b)"
+                         % (what, colour_tol, scan.shape[1]))
+
+
 def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_points=1, normal_tol=None, absorb=0):
     """Raises ValueError before anything needs a device.  -> (scan as a tensor, voxel as float32)."""
     scan = _check_scan("build_segments", scan, 6)
     v32 = _check_voxel("build_segments", voxel, connectivity, min_points)
-    with np.errstate(over="ignore", under="ignore"):
-        t32 = np.float32(colour_tol) if _is_real(colour_tol) else np.float32(np.nan)
-    if colour_tol is not None:
-        if not (_is_real(colour_tol) and np.isfinite(colour_tol) and colour_tol >= 0 and np.isfinite(t32)):
-            raise ValueError("build_segments: colour_tol %r must be None or a finite float >= 0" % (colour_tol,))
-        if scan.shape[1] < 6:
-            raise ValueError("build_segments: colour_tol %r given, but a scan of %d columns has no colour (x y z r g b)"
-                             % (colour_tol, scan.shape[1]))
+    _check_colour("build_segments", colour_tol, scan)
     if normal_tol is not None and not (_is_real(normal_tol) and np.isfinite(normal_tol) and 0 <= normal_tol <= 90):
         raise ValueError("grow_segments: normal_tol %r must be None or a finite real number of degrees in [0, 90]" % (normal_tol,))
     if not scene._is_int(absorb) or not 0 <= absorb <= MAX_RINGS:
