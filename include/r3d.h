@@ -41,6 +41,19 @@
 extern "C" {
 #endif
 
+/* The NUMBERS of the contract -- the words of the records and descriptors the host reads back, their sizes, the flag and
+ * enum values passed in or returned, the limits an entry point refuses beyond -- are the `#define R3D_<NAME> <value>`
+ * lines of this header, each next to the entry points it belongs to, and are written nowhere else: the kernels include
+ * this header, r3dfsseg_amd/_lib.py parses it (parse_constants) and r3dfsseg_amd/ops.py exports every one without its
+ * prefix.  A value is an integer expression over literals and constants defined above it: decimal, hex, an L suffix,
+ * + - * << |, parentheses.  No function-like macros. */
+#define R3D_ABI_VERSION 6 /* what r3d_abi_version() returns; its history is beside that entry point */
+/* what an entry point that returns int returns */
+#define R3D_OK 0
+#define R3D_ERR_ARG 1
+#define R3D_ERR_LAUNCH 2
+#define R3D_ERR_UNSUPPORTED 3
+
 const char* r3d_last_error_string(void);
 int r3d_abi_version(void); /* 6: r3d_scene_prepare / _vote take the optional sws, r3d_scene_transfer the optional idw outputs */
 /* Arithmetic of the GEMM-shaped kernels that decide no index (self-attention forward / backward, r3d_pointwise_conv*,
@@ -67,8 +80,8 @@ long r3d_cm_pitch(int N); /* row pitch (floats) of internal channel-major copies
 int r3d_copy_cols(const float* src, long ld_src, float* dst, long ld_dst, long M, int C, void* stream);
 
 /* ---- k nearest neighbours ----------------------------------------------------------
- * mode 0: models/dgcnn.py:17-23 knn(x,k): score = -xx[j] + 2<xi,xj> - xx[i], k largest.
- * mode 1: models/mpti.py:733-735 faiss.IndexFlatL2.search: score = -max(0,|xi|^2+|xj|^2-2<xi,xj>).
+ * mode R3D_SCORE_DGCNN: models/dgcnn.py:17-23 knn(x,k): score = -xx[j] + 2<xi,xj> - xx[i], k largest.
+ * mode R3D_SCORE_L2: models/mpti.py:733-735 faiss.IndexFlatL2.search: score = -max(0,|xi|^2+|xj|^2-2<xi,xj>).
  * Inner products are channel-ascending fp32 fma chains (bit-exact vs oracle/r3d_oracle.c);
  * ties resolve to the lower index; columns are sorted best first.
  * x (B*N, ldx); norm_ws (B*N) scratch; idx_out (B,N,k) int32; score_out optional (B,N,k);
@@ -79,14 +92,16 @@ int r3d_copy_cols(const float* src, long ld_src, float* dst, long ld_dst, long M
  * status: optional device int32.  For k > 32 a non-NULL status selects the two-pass
  * append-and-rank kernel; bit 0 set afterwards means its survivor buffer overflowed and the
  * call must be repeated with status == NULL (insertion kernel, always exact). */
+#define R3D_SCORE_DGCNN 0
+#define R3D_SCORE_L2 1
 long r3d_knn_norm_ws_words(int B, int N);  /* floats of norm_ws: B*N norms + per-tile overflow flags */
 int r3d_knn_topk(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
                  const int32_t* n_valid_dev, float* norm_ws, float* cm_ws, int32_t* idx_out, float* score_out,
                  int32_t* status, void* stream);
 /* B point sets with their own valid counts: set b has n_valid_dev[b * n_valid_stride] rows (the graph nodes of B episodes'
  * label-propagation systems, each at its capacity N).  status: ONE word for the batch.
- * ws: one scratch of r3d_knn_ws_words(B, N, C, k, flags) floats, 16-byte aligned; flags bit 0 = status is given, bit 1 =
- * x_cm is given.  The library places in it what the path it selects needs: the squared norms, per-tile overflow flags,
+ * ws: one scratch of r3d_knn_ws_words(B, N, C, k, flags) floats, 16-byte aligned; flags: R3D_KNN_FLAG_STATUS = status is
+ * given, R3D_KNN_FLAG_X_CM = x_cm is given.  The library places in it what the path it selects needs: the squared norms, per-tile overflow flags,
  * the channel-major copy, the two partial lists per row when the large-k kernel splits its candidate axis (so few query
  * tiles that even twice as many workgroups fit the chip in one round), and the bf16 pieces of the points (C % 64 == 0,
  * needs x): the streamed kernels then run their THRESHOLD pass -- which only needs a lower bound of every score -- on the
@@ -94,6 +109,10 @@ int r3d_knn_topk(const float* x, long ldx, const float* x_cm, int B, int N, int 
  * whose score's upper bound reaches the threshold is kept, and only the kept ones (~k + 10 per query) get their exact
  * score -- the fp32 fmaf chain in channel order, bit for bit the accumulation of the all-pairs fp32 pass it replaces.
  * Indices and scores are the same bits on every path. */
+#define R3D_KNN_FLAG_STATUS 1
+#define R3D_KNN_FLAG_X_CM 2
+#define R3D_KNN_FLAG_NO_X 4          /* r3d_debug_knn_path only */
+#define R3D_KNN_FLAG_FIXED_SCRATCH 8 /* r3d_debug_knn_path only */
 long r3d_knn_ws_words(int B, int N, int C, int k, int flags);
 int r3d_knn_topk_batched(const float* x, long ldx, const float* x_cm, int B, int N, int C, int k, int mode,
                          const int32_t* n_valid_dev, int n_valid_stride, float* ws, long ws_words, int32_t* idx_out,
@@ -105,17 +124,36 @@ int r3d_debug_set_knn_bf16_threshold(int on);
 int r3d_debug_set_knn_bf16_filter(int on);
 /* test utility: the kernel configuration r3d_knn_topk[_batched] would launch for this call, as the launcher itself decides
  * it (one host function serves both), under the two switches above as they are set.  Launches nothing, needs no device.
- * flags: bit 0 status given, bit 1 x_cm given (as r3d_knn_ws_words), bit 2 x is NULL, bit 3 the call is r3d_knn_topk
- * (fixed scratch: no bf16 pieces, no split lists).  ldx: row pitch of x; x_misalign_bytes: address of x modulo 16.
- * Returns a bit mask, or -1 for a shape the calls refuse:
- *   bits 0-1  path: 0 = k <= 32 append-and-rank (overflowed tiles redone exactly), 1 = large-k append-and-rank
- *             (overflow -> status bit 0), 2 = sorted insertion
- *   bit 2     few: (path 0) 8 waves per query tile instead of 4
- *   bit 3     split: (path 1) the candidate axis dealt to two workgroups per tile, lists merged
- *   bit 4     bfa: the threshold pass runs on the bf16 matrix core
- *   bit 5     filter: (path 0) pass B is the bf16 filter + exact scores of the survivors
- *   bits 6-7  channel configuration: 0 = chunks of 64 with a padded tail, 1 = (path 0) C <= 16, 2 = C % 64 == 0
- *   bits 8-9  (path 2) list registers per lane: 1 -> 1, 2 -> 2, 3 -> 4 (k <= 64, <= 128, <= 256) */
+ * flags: R3D_KNN_FLAG_STATUS status given, _X_CM x_cm given (as r3d_knn_ws_words), _NO_X x is NULL, _FIXED_SCRATCH the call
+ * is r3d_knn_topk (fixed scratch: no bf16 pieces, no split lists).  ldx: row pitch of x; x_misalign_bytes: address of x
+ * modulo 16.  Returns a bit mask, or -1 for a shape the calls refuse:
+ *   R3D_KNN_PATH_MASK       path: _SMALL = k <= 32 append-and-rank (overflowed tiles redone exactly), _LARGE = large-k
+ *                           append-and-rank (overflow -> status bit 0), _INSERTION = sorted insertion
+ *   R3D_KNN_PATH_FEW        (path _SMALL) 8 waves per query tile instead of 4
+ *   R3D_KNN_PATH_SPLIT      (path _LARGE) the candidate axis dealt to two workgroups per tile, lists merged
+ *   R3D_KNN_PATH_BFA        the threshold pass runs on the bf16 matrix core
+ *   R3D_KNN_PATH_FILTER     (path _SMALL) pass B is the bf16 filter + exact scores of the survivors
+ *   R3D_KNN_PATH_CHAN_MASK  channel configuration: R3D_KNN_CHAN_ANY = chunks of 64 with a padded tail, _LE16 = (path
+ *                           _SMALL) C <= 16, _FULL = C % 64 == 0
+ *   R3D_KNN_PATH_REGS_MASK  (path _INSERTION) list registers per lane: R3D_KNN_REGS_1, _2, _4 (k <= 64, <= 128, <= 256) */
+#define R3D_KNN_PATH_MASK 0x3
+#define R3D_KNN_PATH_SMALL 0
+#define R3D_KNN_PATH_LARGE 1
+#define R3D_KNN_PATH_INSERTION 2
+#define R3D_KNN_PATH_FEW 0x4
+#define R3D_KNN_PATH_SPLIT 0x8
+#define R3D_KNN_PATH_BFA 0x10
+#define R3D_KNN_PATH_FILTER 0x20
+#define R3D_KNN_PATH_CHAN_SHIFT 6
+#define R3D_KNN_PATH_CHAN_MASK 0xC0
+#define R3D_KNN_CHAN_ANY (0 << R3D_KNN_PATH_CHAN_SHIFT)
+#define R3D_KNN_CHAN_LE16 (1 << R3D_KNN_PATH_CHAN_SHIFT)
+#define R3D_KNN_CHAN_FULL (2 << R3D_KNN_PATH_CHAN_SHIFT)
+#define R3D_KNN_PATH_REGS_SHIFT 8
+#define R3D_KNN_PATH_REGS_MASK 0x300
+#define R3D_KNN_REGS_1 (1 << R3D_KNN_PATH_REGS_SHIFT)
+#define R3D_KNN_REGS_2 (2 << R3D_KNN_PATH_REGS_SHIFT)
+#define R3D_KNN_REGS_4 (3 << R3D_KNN_PATH_REGS_SHIFT)
 int r3d_debug_knn_path(int B, int N, int C, int k, int flags, long ldx, int x_misalign_bytes);
 /* 1: launches captured into a hipGraph may use their stream's packed-weight scratch of the bf16 x 3 point-wise GEMM (it
  * must exist already: run the sequence eagerly on that stream first).  The caller promises that the captured graph is the
@@ -125,8 +163,11 @@ int r3d_set_wpack_in_capture(int on);
 
 /* ---- 1x1 convolution + folded BatchNorm/bias + activation ---------------------------
  * models/dgcnn.py:64-80 conv1d, models/mpti.py:18-40 BaseLearner, models/attention.py:39-41.
- * Out[m][j] = act(scale[j] * sum_k X[m][k] W[j][k] + shift[j]); act 0 none, 1 ReLU, 2 LeakyReLU(0.2).
+ * Out[m][j] = act(scale[j] * sum_k X[m][k] W[j][k] + shift[j]); act R3D_ACT_NONE, _RELU, _LRELU = LeakyReLU(0.2).
  * scale/shift may be NULL (1 / 0). */
+#define R3D_ACT_NONE 0
+#define R3D_ACT_RELU 1
+#define R3D_ACT_LRELU 2
 int r3d_pointwise_conv(const float* X, long ldx, const float* W /*(Co,K)*/, long M, int K, int Co,
                        const float* scale, const float* shift, int act, float* Out, long ldo, void* stream);
 /* test utility: the kernel r3d_pointwise_conv / _acc / _stats / _stats_seg launch for these operands, as the launcher itself
@@ -184,10 +225,18 @@ int r3d_attention_bwd_ws(const float* qkv, long ld, int B, int N, const float* O
  * FPS (start index 0, ties lowest index) -> sorted unique seeds -> nearest-seed assignment ->
  * cluster means, for background + each way, then query rows appended: fills node rows
  * [0, n_proto) and [n_proto, n_proto + n_query_pts) of `nodes` and the label matrix Y.
- * desc: device int32[r3d_head_desc_words()] = {seg_count[8], seg_m[8], seg_poff[8], n_proto, n_nodes,..}.
+ * desc: device int32[r3d_head_desc_words() = R3D_HD_WORDS], the words below; a segment is the background or one way.
  * Seeds per segment of n > k points: what torch_cluster.fps(feat, None, ratio = k / n) draws at the call site
  * models/mpti.py:612-613, ceil(float32(n) * float32(k / n)) = k or k + 1 (101 for 5.8 % of the n <= 20480 at k = 100),
  * so a segment can hold k + 1 prototypes: nodes / node_labels need (n_way + 1) * (k + 1) + n_query_pts rows, k < 128. */
+#define R3D_HD_MAXSEG 8                         /* segments: n_way + 1 <= R3D_HD_MAXSEG */
+#define R3D_HD_SEG_COUNT 0                      /* [R3D_HD_MAXSEG] points per segment */
+#define R3D_HD_SEG_M R3D_HD_MAXSEG              /* [R3D_HD_MAXSEG] prototypes per segment */
+#define R3D_HD_SEG_POFF (2 * R3D_HD_MAXSEG)     /* [R3D_HD_MAXSEG] first node row of the segment's prototypes */
+#define R3D_HD_N_PROTO (3 * R3D_HD_MAXSEG)
+#define R3D_HD_N_NODES (3 * R3D_HD_MAXSEG + 1)
+#define R3D_HD_FPS_TIMEOUT (3 * R3D_HD_MAXSEG + 2) /* != 0: a workgroup of the one-launch FPS gave up waiting for its peers */
+#define R3D_HD_WORDS (3 * R3D_HD_MAXSEG + 8)
 int r3d_head_desc_words(void);
 /* out[n], n in [0, n_max): the seeds a segment of n points gets at k (n <= k: n), as the device evaluates the count above
  * (device int32 out; for tests that hold it to the host arithmetic over every n). */
@@ -195,7 +244,7 @@ int r3d_fps_sample_count_table(int k, int n_max, int32_t* out, void* stream);
 long r3d_head_proto_ws_words(int n_way, int k_shot, int N);
 int r3d_head_proto_ws_offsets(int n_way, int k_shot, int N, long* out6 /* comp,mind,assign,cand,sel,seeds */);
 /* flags: R3D_HEAD_FPS_ONE_LAUNCH = all FPS rounds in one persistent launch (points stay in registers; needs the
- * grid co-resident: episodes in flight x support points / 256 <= ~384 workgroups; desc word 26 (HD_FPS_TIMEOUT) reports
+ * grid co-resident: episodes in flight x support points / 256 <= ~384 workgroups; desc word R3D_HD_FPS_TIMEOUT reports
  * a wait time-out); 0 = one launch per round. */
 #define R3D_HEAD_FPS_ONE_LAUNCH 1
 /* n_ep episodes in one launch sequence (every pointer addresses episode 0).  Per episode: support_y (n_way*k_shot, N),
@@ -561,7 +610,7 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
 
 /* ---- Labelling a whole scan against a fitted support set (no reference counterpart: the reference scores clouds its
  * loader cut on the host, dataloaders/loader.py:100-119; definition in INTEGRATION.md, "Labelling a scan", steps 1-9') ----
- * scan: M rows of ld floats, x y z first (r g b behind them when ld >= 6); M <= 2^27.  A point is VALID when x, y and z
+ * scan: M rows of ld floats, x y z first (r g b behind them when ld >= 6); M <= R3D_SCENE_MAX_POINTS.  A point is VALID when x, y and z
  * are finite.  Nothing here draws a random number or sums floats in an order that depends on scheduling.
  *
  *   entry point          what it does                                                         host reads afterwards
@@ -603,8 +652,9 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
  *                        point, -1 for an invalid point or one that found no candidate, which is
  *                        left as the vote left it.  Voted points go, in sorted order, into packed
  *                        rows {x, y, z, index}; the others into a list per cell, cut into tiles of
- *                        256 queries; one workgroup per tile stages the candidate runs of the three
- *                        cell rows through LDS, 1024 rows at a time, one thread per query keeping the
+ *                        256 queries (R3D_SCENE_TRANSFER_QUERY_TILE); one workgroup per tile stages the
+ *                        candidate runs of the three cell rows through LDS, 1024 rows at a time
+ *                        (R3D_SCENE_TRANSFER_CAND_TILE), one thread per query keeping the
  *                        lexicographic minimum of (d, index): no float is summed across threads, the
  *                        one atomic is an integer count.
  *
@@ -624,7 +674,7 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
  * third, the insertion sits behind that branch.  One of the two without the other is refused.
  *
  * Blocks: r x r cells (1 <= r <= 4), block (bx, by) covers cells bx .. min(bx + r, ncx) - 1 by by .. min(by + r, ncy) - 1,
- * nbx = max(ncx - r + 1, 1); its point list is its cells' lists by (cy, cx), never materialised.  ncx * ncy <= 65536.
+ * nbx = max(ncx - r + 1, 1); its point list is its cells' lists by (cy, cx), never materialised.  ncx * ncy <= R3D_SCENE_MAX_CELLS.
  * ws: ONE int32 scratch of r3d_scene_ws_words(M, ncx, ncy, chunk_cap) words (-1: shape out of range) shared by all of
  * them, which must be called with the same (M, ncx, ncy, r, N, chunk_cap); chunk_cap bounds the chunk table
  * (r * r * n_valid / N + blocks is always enough).  r3d_scene_ws_offsets fills 8 HOST words (the one host pointer of this
@@ -635,6 +685,10 @@ int r3d_augment_clouds(const float* x, long x_sb, long x_sc, long x_sn, float* o
  * r3d_scene_sparse_ws_offsets fills 8 HOST words with the word offsets of {first run chunk of a block (blocks + 1), block
  * of a run chunk, voted points in front of a sorted position (M + 1), scan indices of the points without a vote, first
  * query tile of a cell (ncx * ncy + 1), candidate rows (4 * M), sparse record (8), scan partials}. */
+#define R3D_SCENE_MAX_POINTS (1L << 27) /* rows of a scan, for every entry point that takes one */
+#define R3D_SCENE_MAX_CELLS 65536
+#define R3D_SCENE_TRANSFER_QUERY_TILE 256
+#define R3D_SCENE_TRANSFER_CAND_TILE 1024
 long r3d_scene_bounds_ws_words(long M);
 int r3d_scene_bounds(const float* scan, int ld, long M, float* rec /* 8 words */, float* ws, long ws_words, void* stream);
 long r3d_scene_ws_words(long M, int ncx, int ncy, long chunk_cap);
@@ -680,7 +734,7 @@ int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const float* scores,
  *
  *   entry point               what it does
  *   r3d_scene_support_counts  fg (blocks, n_way) int32: fg[b][w] = the members of block b's cloud whose label equals
- *                             classes[w] (a device array of n_way <= 7 int32 ids), every member once; 0 for a dropped
+ *                             classes[w] (a device array of n_way <= R3D_SCENE_SUPPORT_MAX_WAYS int32 ids), every member once; 0 for a dropped
  *                             block.  One workgroup per block, a ballot and a population count per wave and way, the
  *                             waves' integer counts summed in LDS.
  *   r3d_scene_support_pick    thr[b] = max((int)floorf((float)len * min_ratio), min_fg), one IEEE fp32 multiplication;
@@ -692,6 +746,7 @@ int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const float* scores,
  *                             that entry point's bits, strides and slot_map; a block id outside the grid or a dropped
  *                             block leaves its cloud unwritten.  With labels, cloud_class (G int32 ids) and mask (G, N)
  *                             int32 -- all three or none --: mask[g][t] = (labels[slot_map[g][t]] == cloud_class[g]). */
+#define R3D_SCENE_SUPPORT_MAX_WAYS 7
 int r3d_scene_support_counts(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws, long ws_words,
                              const void* labels, int label_bytes, const int32_t* classes, int n_way, int32_t* fg,
                              void* stream);
@@ -707,22 +762,22 @@ int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy
  * Replaces what a caller would write in torch as a sort plus index_add_ -- floating-point atomics, a summation order that
  * changes from run to run -- with sums in a defined order: the reference has no such step, the definition is this project's.
  * segments: M ids, int32 (seg_bytes 4) or int64 (8), read as they are; g < 0: the point is in no segment; legal ids are
- * 0 .. 2^31 - 2.  ws: ONE int32 scratch of r3d_scene_seg_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the four
- * calls of one pooling; its first 16 words are the record the host reads:
- *   [0] largest legal id + 1 (0: none)   [1] negative ids   [2] ids >= 2^31 - 1   [4..5] the largest of those (uint64)
- *   [6] segments S   [7] contributors   [8] tiles   [9] pooled points   [10] pooled points whose label was -1
- *   [11] labels that are -1 in the result
+ * 0 .. 2^31 - 2.  ws: ONE int32 scratch of r3d_scene_seg_ws_words(M) words (-1: M outside 1 .. R3D_SCENE_MAX_POINTS) shared
+ * by the four calls of one pooling; its first R3D_SCENE_SEG_REC words are the record the host reads, R3D_SEG_R_*:
+ *   MAX1 largest legal id + 1 (0: none)   NNEG negative ids   NBAD ids >= 2^31 - 1   BADMAX the largest of those (uint64, two
+ *   words)   S segments   NCONTRIB contributors   NTILES tiles   NPOOLED pooled points   NFILLED pooled points whose label
+ *   was -1   NUNLAB labels that are -1 in the result
  *
  *   entry point           what it does                                                                   host reads
- *   r3d_scene_seg_ids     zeroes the record, then words 0 .. 5 of it (integer maxima and counts)          words 0 .. 5
- *   r3d_scene_seg_group   max_id, n_negative: words 0 (less one) and 1 as read.  Stable LSD radix sort of
+ *   r3d_scene_seg_ids     zeroes the record, then MAX1 .. BADMAX of it (integer maxima and counts)        MAX1 .. BADMAX
+ *   r3d_scene_seg_group   max_id, n_negative: MAX1 (less one) and NNEG as read.  Stable LSD radix sort of
  *                         (id, scan index), the kernels of r3d_scene_plan, 8 bits a pass up to the highest
  *                         set bit of the largest key (1 .. 4 passes); a negative id sorts under the key
  *                         max_id + 1.  CONTRIBUTOR: a point in a segment with votes > 0.  Segment rows are in
  *                         ascending id order; segment_index (M,) int32: the row of a point's segment, -1
  *                         without one.  Contributors of a segment by ascending scan index, cut into TILES
- *                         of 256 ranks; tiles never span two segments.                                   words 6 .. 8
- *   r3d_scene_seg_pool    n_segments, n_tiles: words 6 and 8 as read; part: n_tiles * n_cols floats of
+ *                         of R3D_SCENE_SEG_TILE ranks; tiles never span two segments.                    S .. NTILES
+ *   r3d_scene_seg_pool    n_segments, n_tiles: S and NTILES as read; part: n_tiles * n_cols floats of
  *                         scratch.  Row of contributor p: c[j] = scores[p][j] / (float)votes[p].  Tile:
  *                         part = c of its first rank, then += the next, one fp32 addition at a time; segment:
  *                         tot = its first tile's part, then += the next; seg_scores = tot / (float)members,
@@ -734,7 +789,21 @@ int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int ncx, int ncy
  *                         takes seg_scores[s], seg_labels[s] and, with n_sets > 0 (then the set fields are
  *                         needed, else NULL), seg_set_labels / seg_set_of / seg_margin; any other point the
  *                         in_* fields of its own row.  pooled (M,) bytes 0 / 1.  One thread per point decides,
- *                         the workgroup copies the rows; one integer atomic per count and workgroup.    words 9 .. 11 */
+ *                         the workgroup copies the rows; one integer atomic per count and workgroup.    NPOOLED .. NUNLAB
+ * n_cols <= R3D_SCENE_SCORE_COLS_MAX wherever a call takes score rows. */
+#define R3D_SCENE_SEG_REC 16
+#define R3D_SEG_R_MAX1 0
+#define R3D_SEG_R_NNEG 1
+#define R3D_SEG_R_NBAD 2
+#define R3D_SEG_R_BADMAX 4
+#define R3D_SEG_R_S 6
+#define R3D_SEG_R_NCONTRIB 7
+#define R3D_SEG_R_NTILES 8
+#define R3D_SEG_R_NPOOLED 9
+#define R3D_SEG_R_NFILLED 10
+#define R3D_SEG_R_NUNLAB 11
+#define R3D_SCENE_SEG_TILE 256
+#define R3D_SCENE_SCORE_COLS_MAX 64
 long r3d_scene_seg_ws_words(long M);
 int r3d_scene_seg_ids(const void* segments, int seg_bytes, long M, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_seg_group(const void* segments, int seg_bytes, long M, const int32_t* votes, long max_id, long n_negative,
@@ -753,20 +822,20 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  * G1-G7).  Additive: no entry point above changes.  The reference reads segment ids that an offline script wrote
  * (dataloaders/loader.py:339-349); the definition is this project's.  A VALID point has finite x y z.  Voxel of a valid
  * point: i_a = (int)floorf((v_a - v0_a) / voxel) per axis, v0 the minima read from the record, key = (iz * ny + iy) * nx +
- * ix, nx, ny, nz <= 1024 the host's counts from the same arithmetic at the maxima.  ws: ONE int32 scratch of
- * r3d_scene_grow_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the calls of one build, which pass the same M
- * and nx, ny, nz; its first 16 words are the record the host reads:
- *   [0..2] min x y z, [3..5] max x y z (float bits)   [6] valid points   [7] occupied voxels V   [8] components
- *   [9] kept components S   [10] points of dropped components   [11] != 0: a bounded loop of the union-find ran out
- *   [12] absorbed voxels   [13] absorbed points (r3d_scene_grow_absorb; 0 without it)
+ * ix, nx, ny, nz <= R3D_SCENE_GROW_AXIS the host's counts from the same arithmetic at the maxima.  ws: ONE int32 scratch of
+ * r3d_scene_grow_ws_words(M) words (-1: M outside 1 .. R3D_SCENE_MAX_POINTS) shared by the calls of one build, which pass the
+ * same M and nx, ny, nz; its first R3D_SCENE_GROW_REC words are the record the host reads, R3D_GROW_R_*:
+ *   MIN min x y z, MAX max x y z (three words of float bits each)   NVALID valid points   V occupied voxels   NCOMP components
+ *   S kept components   NDROPPED points of dropped components   ERROR != 0: a bounded loop of the union-find ran out
+ *   ABSORBED_VOXELS, ABSORBED_POINTS (r3d_scene_grow_absorb; 0 without it)
  *
  *   entry point                what it does                                                              host reads
- *   r3d_scene_grow_bounds      words 0 .. 6 of the record, zeros in the others (r3d_scene_bounds keeps no z
- *                              and stays as it is)                                                       words 0 .. 6
+ *   r3d_scene_grow_bounds      MIN .. NVALID of the record, zeros in the others (r3d_scene_bounds keeps no z
+ *                              and stays as it is)                                                       MIN .. NVALID
  *   r3d_scene_grow_sort        keys (an invalid point: nx ny nz), the stable LSD radix sort of
  *                              r3d_scene_plan on (key, scan index), 8 bits a pass up to the highest set bit
- *                              of nx ny nz; the first sorted position of every voxel as a flag, their scan   word 7
- *   r3d_scene_grow_voxels      n_valid, n_voxels: words 6 and 7 as read.  The voxel table: rows in ascending
+ *                              of nx ny nz; the first sorted position of every voxel as a flag, their scan   V
+ *   r3d_scene_grow_voxels      n_valid, n_voxels: NVALID and V as read.  The voxel table: rows in ascending
  *                              key order, a row's points by ascending scan index; voxel_index (M,) int32: the
  *                              row of a point's voxel, -1 for an invalid point.  voxel_mean (V, 3) fp32 or
  *                              NULL (no colour; else ld >= 6): the mean of columns 3 .. 5 per voxel, summed as
@@ -782,12 +851,12 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  *                              (path halving by atomicMin), the larger root compare-and-swapped onto the
  *                              smaller, a failed swap goes on from the value it returned.  parent[v] <= v throughout; only agent-scope atomics
  *                              touch parent[]; no thread waits; a find is bounded by V links and a unite by
- *                              V + 1 attempts, an overrun sets word 11 and returns.                          -
+ *                              V + 1 attempts, an overrun sets ERROR and returns.                            -
  *   r3d_scene_grow_components  root[v] = the root of v (the smallest row of its component), a launch of its
  *                              own; points per root by integer atomics (the lanes of a wave that share a root
  *                              add first); a root is KEPT when its component has at least min_points points;
- *                              the kept roots' scan.                                                     words 8, 9, 11
- *   r3d_scene_grow_absorb      only with absorb > 0 (G6a), between components and ids; rings 1 .. 64, voxel_ring
+ *                              the kept roots' scan.                                                     NCOMP, S, ERROR
+ *   r3d_scene_grow_absorb      only with absorb > 0 (G6a), between components and ids; rings 1 .. R3D_SCENE_GROW_RINGS, voxel_ring
  *                              (V,) int32 the caller's.  owner[v] = root[v] where that root is kept, else -1 (v is
  *                              FREE); voxel_ring[v] = 0, or -1 for a free voxel.  Then `rings` launches, one thread
  *                              per voxel, each reading one owner table and writing the other (a voxel taken in
@@ -800,10 +869,10 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  *                              to the owner's count by integer atomics (the lanes of a wave that share an owner add
  *                              first).  The tables lie in the workspace (the index array of the pair the sort left
  *                              free, and parent[], dead after components); no atomics touch them, no thread waits.
- *                              S and the ids of r3d_scene_grow_ids are unchanged: only -1s become ids.        words 12, 13
- *   r3d_scene_grow_ids         n_segments: word 9 as read.  Kept components are numbered 0 .. S - 1 by
+ *                              S and the ids of r3d_scene_grow_ids are unchanged: only -1s become ids.        ABSORBED_*
+ *   r3d_scene_grow_ids         n_segments: S as read.  Kept components are numbered 0 .. S - 1 by
  *                              ascending root; segments (M,) int32: that number, -1 for an invalid point
- *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          words 10, 12, 13
+ *                              or a dropped component; segment_points (S,) int32 (NULL with S = 0).          NDROPPED, ABSORBED_*
  * No float atomics: the component of a voxel depends on the joined pairs alone, so the same scan gives the same bits.
  *
  * With normal_tol (G3c, G3n and the normal test of G4) two launches go between voxels and the union, and the union is
@@ -834,6 +903,19 @@ int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segments, int mi
  *                              square root, no normalisation, the sign of a row does not matter; a NaN makes the
  *                              comparison false, so a voxel without a normal joins nothing; a row of zeros reads
  *                              0 >= 0 and joins (r3d_scene_grow_normals writes none). */
+#define R3D_SCENE_GROW_REC 16
+#define R3D_SCENE_GROW_AXIS 1024 /* voxels per axis: keys stay below 2^30 */
+#define R3D_SCENE_GROW_RINGS 64
+#define R3D_GROW_R_MIN 0
+#define R3D_GROW_R_MAX 3
+#define R3D_GROW_R_NVALID 6
+#define R3D_GROW_R_V 7
+#define R3D_GROW_R_NCOMP 8
+#define R3D_GROW_R_S 9
+#define R3D_GROW_R_NDROPPED 10
+#define R3D_GROW_R_ERROR 11 /* bit 0 a find, bit 1 a unite */
+#define R3D_GROW_R_ABSORBED_VOXELS 12
+#define R3D_GROW_R_ABSORBED_POINTS 13
 long r3d_scene_grow_ws_words(long M);
 int r3d_scene_grow_bounds(const float* scan, int ld, long M, int32_t* ws, long ws_words, void* stream);
 int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny, int nz,
@@ -857,33 +939,32 @@ int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* vo
 
 /* ---- extract_objects: object instances from a labelled scan ("Objects from a labelled scan", O1-O8).
  * Additive: no entry point above changes.  The reference has no such function; the definition is this project's.
- * labels (M,): int32 (labels64 = 0) or int64 (labels64 = 1); ignore: n_ignore <= 64 int64 class ids on the device (NULL with
- * n_ignore = 0).  A point TAKES PART when x y z are finite, its label is >= 0 and not in ignore.  The grid is the one of
- * build_segments (origin: the minima over the finite points).  A UNIT is the set of participating points of one class in one
- * cell; key = label * n_cells + cell, n_cells = nx ny nz, n_labels the largest participating label plus one, n_labels *
- * n_cells <= 2^31 - 1 (the key of every other point; it sorts last).  ws: ONE int32 scratch of r3d_scene_obj_ws_words(M) words
- * (-1: M outside 1 .. 2^27) shared by the calls of one extraction, laid out as that of build_segments; its first 16 words
- * are the record the host reads:
- *   [0..2] min x y z, [3..5] max x y z (float bits)   [6] finite points   [7] units U   [8] components   [9] kept components S
- *   [10] points of dropped components   [11] != 0: a bounded loop of the union-find ran out   [12] n_labels
- *   [13] finite points left out by their label   [14] finite points whose label is above 2^31 - 2 and not ignored (no key holds
- *   them: the host raises)   [15] participating points
+ * labels (M,): int32 (labels64 = 0) or int64 (labels64 = 1); ignore: n_ignore <= R3D_SCENE_OBJ_IGNORE int64 class ids on the
+ * device (NULL with n_ignore = 0).  A point TAKES PART when x y z are finite, its label is >= 0 and not in ignore.  The grid is
+ * the one of build_segments (origin: the minima over the finite points).  A UNIT is the set of participating points of one
+ * class in one cell; key = label * n_cells + cell, n_cells = nx ny nz, n_labels the largest participating label plus one (a
+ * label <= R3D_SCENE_OBJ_LABEL), n_labels * n_cells <= R3D_SCENE_OBJ_KEY (the key of every other point; it sorts last).  ws:
+ * ONE int32 scratch of r3d_scene_obj_ws_words(M) words (-1: M outside 1 .. R3D_SCENE_MAX_POINTS) shared by the calls of one
+ * extraction, laid out as that of build_segments; its first R3D_SCENE_GROW_REC words are the record the host reads: the words
+ * R3D_GROW_R_MIN .. ERROR of build_segments (NVALID finite points, V units U) and four of its own, R3D_OBJ_R_*:
+ *   NLABELS n_labels   NUNLABELLED finite points left out by their label   NOVER finite points whose label is above
+ *   R3D_SCENE_OBJ_LABEL and not ignored (no key holds them: the host raises)   NPOINTS participating points
  *
  *   entry point                what it does                                                              host reads
- *   r3d_scene_obj_bounds       r3d_scene_grow_bounds, then words 12 .. 15 by integer atomics               words 0 .. 6, 12 .. 15
- *   r3d_scene_obj_sort         x0 y0 z0, the grid: from words 0 .. 5 as build_segments derives them; n_labels, n_points:
- *                              words 12 and 15 as read.  Keys, the stable LSD radix sort on (key, scan index), 8 bits a
+ *   r3d_scene_obj_bounds       r3d_scene_grow_bounds, then the four R3D_OBJ_R_* by integer atomics         MIN .. NVALID, OBJ_R_*
+ *   r3d_scene_obj_sort         x0 y0 z0, the grid: from MIN and MAX as build_segments derives them; n_labels, n_points:
+ *                              NLABELS and NPOINTS as read.  Keys, the stable LSD radix sort on (key, scan index), 8 bits a
  *                              pass up to the highest set bit of n_labels n_cells, the first sorted position of every
  *                              unit as a flag, their scan, the unit table (rows in ascending key order, a row's points by
  *                              ascending scan index); unit_index (M,) int32: the row of a point's unit, -1 for a point
- *                              that takes no part.                                                       word 7
+ *                              that takes no part.                                                       V
  *   r3d_scene_obj_union        parent[u] = u, then one thread per unit a and the offsets (dx, dy, dz) with a larger cell
  *                              key (3 for connectivity 6, 13 for 26): the neighbour's coordinates are checked against
  *                              0 .. n - 1 per axis, then its key is formed with a's class and found by binary search among
  *                              the rows behind a; a pair found is united as r3d_scene_grow_union unites (the same device
- *                              functions; only agent-scope atomics touch parent[]; an overrun sets word 11).   -
- *   r3d_scene_obj_components   the launches of r3d_scene_grow_components on the unit table.               words 8, 9, 11
- *   r3d_scene_obj_stats        n_objects = S >= 1: word 9 as read.  Per object s (kept components by ascending root, so by
+ *                              functions; only agent-scope atomics touch parent[]; an overrun sets ERROR).     -
+ *   r3d_scene_obj_components   the launches of r3d_scene_grow_components on the unit table.               NCOMP, S, ERROR
+ *   r3d_scene_obj_stats        n_objects = S >= 1: S as read.  Per object s (kept components by ascending root, so by
  *                              ascending class, then smallest cell key): object_labels (S,) int64; object_points (S,)
  *                              int32; object_units (S,) int32; object_lo, object_hi (S, 3) fp32: the minima and maxima of
  *                              its points' coordinates, exact, -0.0 below +0.0; object_centroid (S, 3) fp32: per axis
@@ -894,8 +975,15 @@ int r3d_scene_grow_ids(long M, long n_voxels, long n_segments, const int32_t* vo
  *                              combined by shuffles; per wave and object 6 atomic min / max on the order-preserving
  *                              integer image of the float bits, 3 64-bit atomic adds and 1 atomic add.        -
  *   r3d_scene_obj_ids          objects (M,) int32: the number of the point's object, -1 for a point that takes no part
- *                              or a dropped component (r3d_scene_grow_ids' launch).                         words 10, 11
+ *                              or a dropped component (r3d_scene_grow_ids' launch).                         NDROPPED, ERROR
  * No float goes through an atomic: the same scan and labels give the same bits. */
+#define R3D_SCENE_OBJ_IGNORE 64
+#define R3D_SCENE_OBJ_LABEL 2147483646L /* n_labels = label + 1 fits an int */
+#define R3D_SCENE_OBJ_KEY 2147483647L
+#define R3D_OBJ_R_NLABELS 12
+#define R3D_OBJ_R_NUNLABELLED 13
+#define R3D_OBJ_R_NOVER 14
+#define R3D_OBJ_R_NPOINTS 15
 long r3d_scene_obj_ws_words(long M);
 int r3d_scene_obj_bounds(const float* scan, int ld, long M, const void* labels, int labels64, const int64_t* ignore, int n_ignore,
                          int32_t* ws, long ws_words, void* stream);
@@ -917,28 +1005,28 @@ int r3d_scene_obj_ids(long M, long n_units, long n_objects, const int32_t* unit_
  * definition is this project's.  pred, truth: M object ids each, int32 (bytes 4) or int64 (8), read as they are; g < 0: the
  * point is in no object; legal ids are 0 .. 2^31 - 2.  With ignore_unannotated a point whose truth id is negative takes part in
  * nothing (M1).  The labels, for both columns or for none (NULL): M classes each, int32 or int64.  ws: ONE int32 scratch of
- * r3d_scene_match_ws_words(M) words (-1: M outside 1 .. 2^27) shared by the four calls of one matching; its first 32 words are
- * the record the host reads (column 0 is pred, 1 truth):
- *   [0] [1] per column the largest legal id of a participating point + 1 (0: none)   [2] [3] per column the participating
- *   points with a negative id   [4] points M1 took out   [5] ids >= 2^31 - 1, both columns   [6..7] the largest of those (uint64)
- *   [8] pred rows P   [9] truth rows T   [10] [11] per column the rows in which some point carries another label than the
- *   row's first   [12] points with a row in both columns   [13] pairs
+ * r3d_scene_match_ws_words(M) words (-1: M outside 1 .. R3D_SCENE_MAX_POINTS) shared by the four calls of one matching; its
+ * first R3D_SCENE_MATCH_REC words are the record the host reads, R3D_MATCH_R_* (`+ column`: the word of pred, then of truth):
+ *   MAX1 + column the largest legal id of a participating point + 1 (0: none)   NNEG + column the participating points with
+ *   a negative id   NIGNORED points M1 took out   NBAD ids >= 2^31 - 1, both columns   BADMAX the largest of those (uint64, two
+ *   words)   ROWS + column pred rows P, truth rows T   MIXED + column the rows in which some point carries another label than
+ *   the row's first   NBOTH points with a row in both columns   NPAIRS pairs
  *
  *   entry point            what it does                                                                  host reads
- *   r3d_scene_match_ids    zeroes the record, then words 0 .. 7 of it (integer maxima and counts, one atomic per word
- *                          and workgroup)                                                                words 0 .. 7
- *   r3d_scene_match_rows   max_pred, max_truth: words 0 and 1 as read, less one (both >= 0); n_pred_in, n_truth_in: M less
- *                          word 4 less word 2 / 3.  Per column the stable LSD radix sort of (id, scan index), 1 .. 4 passes
+ *   r3d_scene_match_ids    zeroes the record, then MAX1 .. BADMAX of it (integer maxima and counts, one atomic per word
+ *                          and workgroup)                                                                MAX1 .. BADMAX
+ *   r3d_scene_match_rows   max_pred, max_truth: the two MAX1 as read, less one (both >= 0); n_pred_in, n_truth_in: M less
+ *                          NIGNORED less the column's NNEG.  Per column the stable LSD radix sort of (id, scan index), 1 .. 4 passes
  *                          by the largest key (a point without a row sorts under the largest id + 1), run heads, their
  *                          exclusive scan, the row tables in ws (rows in ascending id order, a row's points by ascending
  *                          scan index); pred_index, truth_index (M,) int32: the row of the point, -1 without one.  With
- *                          labels: every point of a run against the label of the run's head.            words 8 .. 11
- *   r3d_scene_match_pairs  n_pred, n_truth: words 8 and 9 as read (both >= 1).  pred_ids (P,) int64, pred_points (P,) int32
+ *                          labels: every point of a run against the label of the run's head.            ROWS, MIXED
+ *   r3d_scene_match_pairs  n_pred, n_truth: the two ROWS as read (both >= 1).  pred_ids (P,) int64, pred_points (P,) int32
  *                          and, with labels, pred_classes (P,) int64, the label of the row's point with the lowest scan
  *                          index; the same for truth.  Then two stable sorts of 32-bit keys: by truth row, then by the pred
  *                          row gathered through the first order (a point without both rows: the keys T and P, last); heads
- *                          where (p, t) changes, their scan, the pair tables in ws in ascending (p, t).   words 12, 13
- *   r3d_scene_match_best   n_pairs: word 13 as read.  thresholds: n_iou <= 8 floats in HOST memory, ascending, each in
+ *                          where (p, t) changes, their scan, the pair tables in ws in ascending (p, t).   NBOTH, NPAIRS
+ *   r3d_scene_match_best   n_pairs: NPAIRS as read.  thresholds: n_iou <= R3D_SCENE_MATCH_IOU floats in HOST memory, ascending, each in
  *                          (0, 1].  pair_pred, pair_truth, pair_points (n_pairs,) int32; pair_iou (n_pairs,) fp32 =
  *                          (float)inter / (float)(pred_points[p] + truth_points[t] - inter), one IEEE division; a pair is
  *                          ELIGIBLE without classes, or when the two classes are equal.  truth_best (T,) int32: per eligible
@@ -949,6 +1037,17 @@ int r3d_scene_obj_ids(long M, long n_units, long n_objects, const int32_t* unit_
  *                          best of both its rows the number of thresholds its IoU meets, else 0.  best_words: n_pred +
  *                          n_truth int64 of the caller's scratch.                                         -
  * No float goes through an atomic: the same columns give the same bits. */
+#define R3D_SCENE_MATCH_REC 32
+#define R3D_SCENE_MATCH_IOU 8
+#define R3D_MATCH_R_MAX1 0
+#define R3D_MATCH_R_NNEG 2
+#define R3D_MATCH_R_NIGNORED 4
+#define R3D_MATCH_R_NBAD 5
+#define R3D_MATCH_R_BADMAX 6
+#define R3D_MATCH_R_ROWS 8
+#define R3D_MATCH_R_MIXED 10
+#define R3D_MATCH_R_NBOTH 12
+#define R3D_MATCH_R_NPAIRS 13
 long r3d_scene_match_ws_words(long M);
 int r3d_scene_match_ids(const void* pred, int pred_bytes, const void* truth, int truth_bytes, long M, int ignore_unannotated,
                         int32_t* ws, long ws_words, void* stream);
@@ -969,7 +1068,7 @@ int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pairs, const 
 /* ---- smooth_scene: the scores of a labelled scan propagated over the voxel graph ("Smoothing a labelled
  * scan", S1-S7).  Additive: no entry point above changes.  The reference has no such function; the definition is this
  * project's.  The grid, the sort and the voxel table are those of build_segments: r3d_scene_grow_bounds, _sort and _voxels
- * run first, as they are, and ws, M, nx, ny, nz below are theirs.  V = n_voxels (word 7 as read), C = n_cols <= 64.  Every
+ * run first, as they are, and ws, M, nx, ny, nz below are theirs.  V = n_voxels (R3D_GROW_R_V as read), C = n_cols <= R3D_SCENE_SCORE_COLS_MAX.  Every
  * float operation is fp32 and rounded on its own (__fadd_rn, __fmul_rn, __fdiv_rn); none goes through an atomic.
  *
  *   r3d_scene_smooth_evidence  scores (M, C) fp32, votes (M,) int32: those of the result.  A CONTRIBUTOR is a valid point
@@ -978,12 +1077,12 @@ int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pairs, const 
  *                              (ranks in tiles of 256, part = the first row, += the next, tot = the first tile's part, +=
  *                              the next), tot / (float)members; zeros without a member.  voxel_members (V,) int32;
  *                              voxel_ring (V,) int32: 0 with a member, else -1.
- *   r3d_scene_smooth_graph     voxel_neighbours (26, V) int32, slot-major: column v holds the rows of the occupied voxels
+ *   r3d_scene_smooth_graph     voxel_neighbours (R3D_SCENE_SMOOTH_SLOTS, V) int32, slot-major: column v holds the rows of the occupied voxels
  *                              among the 6 or 26 cells around voxel v, found by their coordinates as r3d_scene_grow_absorb
  *                              finds them, in ascending key order, packed to the front, -1 behind them.  With voxel_mean
  *                              (V, 3) (else NULL) a neighbour must pass the colour test of r3d_scene_grow_union as well: a
  *                              NaN mean joins nothing.
- *   r3d_scene_smooth_sweep     `iterations` (0 .. 64) launches, sweep t = 0, 1, ...: sweep t reads Z_t (t = 0: voxel_evidence,
+ *   r3d_scene_smooth_sweep     `iterations` (0 .. R3D_SCENE_SMOOTH_SWEEPS) launches, sweep t = 0, 1, ...: sweep t reads Z_t (t = 0: voxel_evidence,
  *                              else z[(t - 1) & 1]) and writes z[t & 1]; z0, z1 (V, C) fp32, two arrays (z1 may be NULL below
  *                              two sweeps, z0 below one).  The result lies in z[(iterations - 1) & 1].  A neighbour u is LIVE
  *                              at t when 0 <= ring[u] <= t.  With n >= 1 live neighbours u_0 < u_1 < ...: s = Z_t[u_0],
@@ -995,10 +1094,19 @@ int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pairs, const 
  *                              the arg-max of the row (the lowest column wins a tie, a NaN never replaces a value) where ring
  *                              >= 0, else -1.  A point whose voxel_index is a row with ring >= 0 is SMOOTHED: scores, labels
  *                              = the voxel's, votes = 1, smoothed = 1; any other point copies in_scores, in_labels, in_votes,
- *                              smoothed = 0.  counts: 8 int32 words, zeroed here, by integer atomics aggregated per
- *                              workgroup: [0] voxels with a member  [1] filled voxels (ring > 0)  [2] smoothed points
- *                              [3] of them: in_labels >= 0 and the label differs  [4] of them: in_labels == -1
- *                              [5] labels that are -1 in the result. */
+ *                              smoothed = 0.  counts: R3D_SCENE_SMOOTH_COUNTS int32 words, zeroed here, by integer atomics
+ *                              aggregated per workgroup, R3D_SMOOTH_R_*: MEMBER_VOXELS voxels with a member  FILLED_VOXELS
+ *                              filled voxels (ring > 0)  NSMOOTHED smoothed points  NCHANGED of them: in_labels >= 0 and the
+ *                              label differs  NFILLED of them: in_labels == -1  NUNLAB labels that are -1 in the result. */
+#define R3D_SCENE_SMOOTH_SLOTS 26
+#define R3D_SCENE_SMOOTH_SWEEPS 64
+#define R3D_SCENE_SMOOTH_COUNTS 8
+#define R3D_SMOOTH_R_MEMBER_VOXELS 0
+#define R3D_SMOOTH_R_FILLED_VOXELS 1
+#define R3D_SMOOTH_R_NSMOOTHED 2
+#define R3D_SMOOTH_R_NCHANGED 3
+#define R3D_SMOOTH_R_NFILLED 4
+#define R3D_SMOOTH_R_NUNLAB 5
 int r3d_scene_smooth_evidence(long M, int nx, int ny, int nz, int n_cols, const float* scores, const int32_t* votes, long n_voxels,
                               float* voxel_evidence, int32_t* voxel_members, int32_t* voxel_ring, const int32_t* ws, long ws_words,
                               void* stream);
@@ -1015,10 +1123,10 @@ int r3d_scene_smooth_spread(long M, int n_cols, long n_voxels, const int32_t* vo
  * draw of sample_pointcloud_universal; :258-276: its channels; :302-350: its labels.  Definition: INTEGRATION.md, "Cutting
  * episodes on the device").  Additive: the entry points above and what they compute are as they were.
  * Pool: points (T, 6) fp32 rows x y z r g b, labels (T,) int32, offsets (n_blocks + 1,) int64: block k is rows
- * offsets[k] .. offsets[k + 1] - 1, 1 .. 2^20 of them; T < 2^31.
+ * offsets[k] .. offsets[k + 1] - 1, 1 .. R3D_CUT_MAX_BLOCK_POINTS of them; T < 2^31.
  * desc: (E (S + Q), 5) int32, one row {block, share_class, m_A, flags, key} per cloud, per episode the S support clouds then
- * the Q query clouds (x_all order); flags bit 0: 0 support / 1 query (must agree with the position), bit 1: the ground-truth
- * mask is zero.  classes: (E, n_way) int32, the sampled classes of every episode (n_way <= 32).
+ * the Q query clouds (x_all order); flags: R3D_CUT_FLAG_QUERY 0 support / 1 query (must agree with the position),
+ * R3D_CUT_FLAG_GT_ZERO the ground-truth mask is zero (R3D_CUT_FLAG_PARTIAL: r3d_episode_cut_partial below).  classes: (E, n_way) int32, the sampled classes of every episode (n_way <= 32).
  * With n the block's points, N <= 8192 the cloud's, c = share_class, mix / stream / draw the hash of r3d_augment_clouds,
  * hA = stream(seed, 2 key), hB = stream(seed, 2 key + 1):
  *   A   slots 0 .. m_A - 1: the m_A points of class c with the smallest (draw(hA, i), i), by ascending local index i;
@@ -1026,7 +1134,7 @@ int r3d_scene_smooth_spread(long M, int n_cols, long n_voxels, const int32_t* vo
  *   B'  n <  N: slot m_A + j = (uint64(draw(hB, j)) * n) >> 32;
  *   C   over the N slots the prepared cloud of r3d_scene_prepare (the same device function): xyz - min, rgb / 255.0f at
  *       rgb_ch, xyz' / max at XYZ_ch (a flat axis gives 0), written at out[b * o_sb + ch * o_sc + t * o_sn];
- *   D   support cloud (e, i): mask[e S + i][t] = (label of slot t == c), gt_mask = mask, or zeros under flags bit 1;
+ *   D   support cloud (e, i): mask[e S + i][t] = (label of slot t == c), gt_mask = mask, or zeros under R3D_CUT_FLAG_GT_ZERO;
  *       query cloud (e, j): query_y[e Q + j][t] = gt_query_y = 1 + the first position of the label in classes[e], 0 if absent;
  *       slot_map (E (S + Q), N) int32: the pool row of every slot.
  * rec: 2 int32 words the caller zeroes.  A cloud whose descriptor cannot be cut (block outside the pool, m_A outside
@@ -1035,6 +1143,10 @@ int r3d_scene_smooth_spread(long M, int n_cols, long n_voxels, const int32_t* vo
  * One 256-thread workgroup per cloud; the m smallest by a radix select over the draw (four 256-bin histograms in LDS,
  * draws recomputed), ties by index, survivors compacted in index order by ballot and prefix count.  Integer counts and
  * min / max only: the same descriptors and seed give the same bits, whatever else is in the launch. */
+#define R3D_CUT_MAX_BLOCK_POINTS (1 << 20)
+#define R3D_CUT_FLAG_QUERY 1
+#define R3D_CUT_FLAG_GT_ZERO 2
+#define R3D_CUT_FLAG_PARTIAL 4
 int r3d_episode_cut(const float* points, const int32_t* labels, const int64_t* offsets, int n_blocks, long T,
                     const int32_t* desc, const int32_t* classes, int E, int n_way, int S, int Q, int N, unsigned seed, int C,
                     int rgb_ch, int XYZ_ch, float* out, long o_sb, long o_sc, long o_sn, int32_t* mask, int32_t* gt_mask,
@@ -1043,19 +1155,19 @@ int r3d_episode_cut(const float* points, const int32_t* labels, const int64_t* o
 /* ---- Partial noise in a cut episode (dataloaders/loader.py:239-322: one wrong object is flipped into a support mask and,
  * with probability 0.3, one right object is taken out; :741-779: the shots it is applied to.  Definition: INTEGRATION.md,
  * "Cutting episodes on the device", steps P0-P7).  Additive: r3d_episode_cut keeps its arguments and results and still
- * refuses flags bit 2.
+ * refuses R3D_CUT_FLAG_PARTIAL.
  * r3d_episode_cut_partial takes r3d_episode_cut's arguments, then instances (T,) int32 -- the object id of every pool row,
- * may be null -- and info (E (S + Q), 8) int32; rec has 4 words the caller zeroes.  A descriptor without flags bit 2 is cut
- * with the bits of r3d_episode_cut and gets info = 0.  Bit 2 is legal on a support cloud with m_A == 0 when instances is
+ * may be null -- and info (E (S + Q), 8) int32; rec has 4 words the caller zeroes.  A descriptor without R3D_CUT_FLAG_PARTIAL is cut
+ * with the bits of r3d_episode_cut and gets info = 0.  The flag is legal on a support cloud with m_A == 0 when instances is
  * given; otherwise the cloud is refused as any bad descriptor (rec[0], rec[1], nothing else written, info included).
- * With bit 2, over the N slots of steps B / B' (m_A = 0: a uniform sample), lab / inst read through the slot:
+ * With the flag, over the N slots of steps B / B' (m_A = 0: a uniform sample), lab / inst read through the slot:
  *   mask0[t] = (lab[t] == c);  objects o_0 < .. < o_{K-1}: the distinct inst, ascending as signed;  first(o): the lowest
  *   slot holding o;  eligible(o) = lab[first(o)] != c;  fg(o): some slot of o has mask0;  e, f: how many are eligible, fg;
  *   multi = K > 1 and some lab[t] != lab[0];
  *   flip, if multi and e > 0: the r-th eligible object, r = (uint64(draw(hA, 0)) * e) >> 32, joins the mask;
  *   drop, if draw(hA, 1) > 0xB3333333 and f > 0: the r2-th fg object, r2 = (uint64(draw(hA, 2)) * f) >> 32, leaves it
  *   (after the flip) -- unless that leaves no point, then it is not applied;
- *   mask = the result, gt_mask = zeros under bit 1, else mask0.  A final mask without a point: rec[2] += 1,
+ *   mask = the result, gt_mask = zeros under R3D_CUT_FLAG_GT_ZERO, else mask0.  A final mask without a point: rec[2] += 1,
  *   rec[3] = max(rec[3], 1 + the cloud's index); the cloud is written in full.
  *   info[cloud] = {K, e, f, did, o_flip, n_flip, o_drop, n_drop}: did bit 0 flipped, bit 1 dropped, bit 2 drop drawn but
  *   skipped; n_*: slots holding the object; ids and counts 0 where nothing happened.

@@ -59,8 +59,80 @@ def parse_header(txt):
     return names, sigs
 
 
+_TOKEN = re.compile(r"\s*(?:(0[xX][0-9a-fA-F]+|[0-9]+)[lL]?(?![0-9A-Za-z_.])|([A-Za-z_][A-Za-z0-9_]*)|(<<|[-+*|()]))")
+_BINARY = (("|",), ("<<",), ("+", "-"), ("*",))  # loosest first, as C ranks them
+
+
+def _const_value(expr, known, name):
+    """Value of `expr`, the right-hand side of `#define name`: integer literals (decimal, hex, an L suffix), constants
+    already in `known`, + - * << |, unary + and -, parentheses.  Anything else raises and names the constant."""
+    def bad(why):
+        return RuntimeError("r3dfsseg_amd: cannot evaluate %s: %s in %r" % (name, why, expr))
+
+    toks, at = [], 0
+    while expr[at:].strip():
+        m = _TOKEN.match(expr, at)
+        if not m:
+            raise bad("unrecognised text")
+        toks.append(m.group(1, 2, 3))
+        at = m.end()
+    toks.reverse()  # a stack: the next token is toks[-1]
+
+    def atom():
+        if not toks:
+            raise bad("an operand is missing")
+        num, ident, op = toks.pop()
+        if num is not None:
+            return int(num, 0)
+        if ident is not None:
+            if ident not in known:
+                raise bad("%s is not defined above it" % ident)
+            return known[ident]
+        if op in "+-":
+            return atom() if op == "+" else -atom()
+        if op == "(":
+            v = binary(0)
+            if not toks or toks.pop()[2] != ")":
+                raise bad("an unclosed parenthesis")
+            return v
+        raise bad("a misplaced %r" % op)
+
+    def binary(level):
+        if level == len(_BINARY):
+            return atom()
+        v = binary(level + 1)
+        while toks and toks[-1][2] in _BINARY[level]:
+            op, w = toks.pop()[2], binary(level + 1)
+            v = v | w if op == "|" else v << w if op == "<<" else v + w if op == "+" else v - w if op == "-" else v * w
+        return v
+
+    v = binary(0)
+    if toks:
+        raise bad("text behind the expression")
+    return v
+
+
+def parse_constants(txt):
+    """{name: int} of the `#define R3D_<NAME> <value>` lines of a C header, comments removed, in the order of the text.  A
+    define without a value (the include guard) is skipped.  A value is what _const_value takes; a float, a function-like
+    macro, a name used before its definition or a second definition of a name raises and names the constant."""
+    txt = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", txt, flags=re.S))
+    consts = {}
+    for name, params, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(R3D_[A-Za-z0-9_]*)(\()?([^\n]*)$", txt, flags=re.M):
+        if params:
+            raise RuntimeError("r3dfsseg_amd: cannot evaluate %s: a function-like macro" % name)
+        if not expr.strip():
+            continue
+        if name in consts:
+            raise RuntimeError("r3dfsseg_amd: %s is defined twice" % name)
+        consts[name] = _const_value(expr, consts, name)
+    return consts
+
+
 # the binding IS the header: read once, at import
-_SYMBOLS, _SIGS = parse_header(open(HEADER_PATH).read())
+_HEADER = open(HEADER_PATH).read()
+_SYMBOLS, _SIGS = parse_header(_HEADER)
+CONSTANTS = parse_constants(_HEADER)  # every number of the contract: ops exports them without the prefix
 
 
 def header_symbols():
@@ -71,7 +143,7 @@ def header_symbols():
 _lib = None
 
 
-ABI_VERSION = 6  # include/r3d.h; 6: one scene entry point per step (prepare / vote take the optional sws, transfer the idw outputs)
+ABI_VERSION = CONSTANTS["R3D_ABI_VERSION"]
 
 
 def load():

@@ -18,10 +18,11 @@ Not here: the four background clouds of the train layout (no model here reads th
 import numpy as np
 import torch
 
+from . import ops
 from .episode_sampler import episode_rules
 
-MAX_BLOCK_POINTS = 1 << 20
-FLAG_QUERY, FLAG_GT_ZERO, FLAG_PARTIAL = 1, 2, 4
+MAX_BLOCK_POINTS = ops.CUT_MAX_BLOCK_POINTS
+FLAG_QUERY, FLAG_GT_ZERO, FLAG_PARTIAL = ops.CUT_FLAG_QUERY, ops.CUT_FLAG_GT_ZERO, ops.CUT_FLAG_PARTIAL
 ATTRIB_SETS = {"xyz": (3, -1, -1), "xyzrgb": (6, 3, -1), "xyzXYZ": (6, -1, 3), "xyzrgbXYZ": (9, 3, 6)}  # C, rgb_ch, XYZ_ch
 
 
@@ -233,7 +234,6 @@ class DeviceEpisodeSampler:
                                  % (i, m_A, N, pool.count(b, c), c, pool.names[b]))
 
     def cut(self, plans, counter=None):
-        from . import ops
         from .batch import EpisodeBatch
         if counter is None:
             counter = self.counter

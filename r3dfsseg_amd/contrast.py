@@ -5,7 +5,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _p, _st
 
 ContrastSaved = namedtuple("ContrastSaved", "model ws words E ep_rows")
@@ -74,7 +74,7 @@ def train_debug_metrics(model, hb, pred, support_y, gt_support_y, query_y, gt_qu
     qy = query_y.to(torch.int64).contiguous()
     gq = (gt_query_y if gt_query_y is not None else query_y).to(torch.int64).contiguous()
     gs = (gt_support_y if gt_support_y is not None else support_y).reshape(-1).to(torch.int32).contiguous()
-    _lib.check(lib.r3d_train_metrics_batched(n_ep, _p(pred), _p(qy), _p(gq), n_qpts, _p(hb.Z), hb.n_cap, _p(hb.desc), 32,
+    _lib.check(lib.r3d_train_metrics_batched(n_ep, _p(pred), _p(qy), _p(gq), n_qpts, _p(hb.Z), hb.n_cap, _p(hb.desc), ops.HD_WORDS,
                                              _p(hb.proto_ws), hb.proto_stride, _p(hb.assign), 2 * S * N, _p(gs), model.n_way,
                                              model.k_shot, N, _p(out), _st()))
     if logger is not None:  # the reference prints these every step (mpti.py:546,568): a host sync, as there

@@ -6,10 +6,6 @@
 
 #include "r3d.h"  // the C ABI: every definition is compiled against its prototype
 
-#define R3D_OK 0
-#define R3D_ERR_ARG 1
-#define R3D_ERR_LAUNCH 2
-#define R3D_ERR_UNSUPPORTED 3
 
 void r3d_set_error(const char* fmt, ...);
 

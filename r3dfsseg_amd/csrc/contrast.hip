@@ -450,8 +450,8 @@ __global__ __launch_bounds__(256) void r3d_train_metrics_kernel(
   const long SN = (long)n_way * k_shot * N;
   for (int wy = 0; wy < n_way; ++wy) {
     const int seg = 1 + wy;
-    const int count = desc[seg];                 // HD_SEG_COUNT
-    const int poff = desc[16 + seg];             // HD_SEG_POFF
+    const int count = desc[R3D_HD_SEG_COUNT + seg];
+    const int poff = desc[R3D_HD_SEG_POFF + seg];
     const long off = SN + (long)wy * k_shot * N;  // SegGeom::off(seg)
     if (tid == 0) { acc[2] = 0; acc[3] = 0; }
     __syncthreads();

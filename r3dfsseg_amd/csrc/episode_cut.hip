@@ -25,7 +25,6 @@
 #define EC_THREADS 256
 #define EC_WAVES (EC_THREADS / R3D_WAVE)
 #define EC_MAX_N 8192          // slots of a cloud live in LDS (32 KiB at most)
-#define EC_MAX_BLOCK (1 << 20)  // points of a block
 #define EC_MAX_WAY 32
 
 struct ec_shared {
@@ -284,18 +283,19 @@ __global__ __launch_bounds__(EC_THREADS) void r3d_episode_cut_kernel(
   const int* d = desc + 5L * b;
   const int block = d[0], c = d[1], mA = d[2], flags = d[3];
   const unsigned key = (unsigned)d[4];
+  constexpr int kFlags = R3D_CUT_FLAG_QUERY | R3D_CUT_FLAG_GT_ZERO | (PARTIAL ? R3D_CUT_FLAG_PARTIAL : 0);  // the legal ones
   // every index below is bounded here, whatever the descriptor and the offsets hold (all of it uniform)
-  if (block < 0 || block >= n_blocks || mA < 0 || mA > N || (flags & ~(PARTIAL ? 7 : 3)) != 0 || ((flags & 1) != 0) != query) {
+  if (block < 0 || block >= n_blocks || mA < 0 || mA > N || (flags & ~kFlags) != 0 || ((flags & R3D_CUT_FLAG_QUERY) != 0) != query) {
     ec_refuse(rec, b);
     return;
   }
-  const bool partial = PARTIAL && (flags & 4) != 0;
+  const bool partial = PARTIAL && (flags & R3D_CUT_FLAG_PARTIAL) != 0;
   if (partial && (query || mA != 0 || !instances)) {  // P0
     ec_refuse(rec, b);
     return;
   }
   const long long off0 = offsets[block], off1 = offsets[block + 1];
-  if (off0 < 0 || off1 > T || off1 <= off0 || off1 - off0 > EC_MAX_BLOCK) {
+  if (off0 < 0 || off1 > T || off1 <= off0 || off1 - off0 > R3D_CUT_MAX_BLOCK_POINTS) {
     ec_refuse(rec, b);
     return;
   }
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(EC_THREADS) void r3d_episode_cut_kernel(
         if (ed.drop && i == ed.o_drop) me = 0;
       }
       mask[sup * N + t] = me;
-      gt_mask[sup * N + t] = (flags & 2) ? 0 : m;
+      gt_mask[sup * N + t] = (flags & R3D_CUT_FLAG_GT_ZERO) ? 0 : m;
     } else {
       int y = 0;
       for (int k = n_way - 1; k >= 0; --k)

@@ -22,7 +22,6 @@
 #define G_BK 32
 #define G_LD (G_BK + 1)
 
-enum { R3D_ACT_NONE = 0, R3D_ACT_RELU = 1, R3D_ACT_LRELU02 = 2 };
 
 __global__ __launch_bounds__(256) void r3d_pointwise_gemm_kernel(
     const float* __restrict__ X, long ldx, const float* __restrict__ W, int M, int K, int Co,
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(256) void r3d_pointwise_gemm_kernel(
     if (m >= M || !jok) continue;
     float v = sc * acc[r] + sh;
     if (act == R3D_ACT_RELU) v = fmaxf(v, 0.f);
-    else if (act == R3D_ACT_LRELU02) v = v > 0.f ? v : 0.2f * v;
+    else if (act == R3D_ACT_LRELU) v = v > 0.f ? v : 0.2f * v;
     Out[m * ldo + j] = accumulate ? Out[m * ldo + j] + v : v;
     s1 += v;
     s2 += v * v;

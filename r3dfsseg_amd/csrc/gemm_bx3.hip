@@ -24,7 +24,6 @@
 
 #define GB_RS 40  // LDS row stride in bf16 units (64 B of data + 16 B: consecutive rows start 20 banks apart)
 
-enum { GB_ACT_NONE = 0, GB_ACT_RELU = 1, GB_ACT_LRELU02 = 2 };
 
 // one staged chunk: 8 consecutive k of a row, as three 16-byte piece vectors
 static __device__ __forceinline__ void gb_store_chunk(unsigned short* __restrict__ planes, int rows, int row, int kc,
@@ -243,8 +242,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float v = sc[tn] * acc[tm][tn][4 * q + i] + sh[tn];
-          if (act == GB_ACT_RELU) v = fmaxf(v, 0.f);
-          else if (act == GB_ACT_LRELU02) v = fmaxf(v, 0.2f * v);
+          if (act == R3D_ACT_RELU) v = fmaxf(v, 0.f);
+          else if (act == R3D_ACT_LRELU) v = fmaxf(v, 0.2f * v);
           es[(4 * g + i) * ER + 32 * tn + j] = v;
           {  // column sums of the values written (training: batch statistics of z); rows beyond M add zeros
             const float u = r3d_keep(v, mrow0 + 4 * g + i < M);
@@ -430,8 +429,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
           float v = acc[tn][4 * q + i];
           if (!PLAIN) {
             v = sc[tn] * v + sh[tn];
-            if (act == GB_ACT_RELU) v = fmaxf(v, 0.f);
-            else if (act == GB_ACT_LRELU02) v = fmaxf(v, 0.2f * v);
+            if (act == R3D_ACT_RELU) v = fmaxf(v, 0.f);
+            else if (act == R3D_ACT_LRELU) v = fmaxf(v, 0.2f * v);
           }
           es[(4 * g + i) * ER + 32 * tn + j] = v;
           if (STATS) {
@@ -460,7 +459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
   {
     using T_ = std::integral_constant<bool, true>;
     using F_ = std::integral_constant<bool, false>;
-    const bool plain = !scale && !shift && act == GB_ACT_NONE, full = mw + 32 <= M && n0 + BN <= Co, stats = stats_part != nullptr;
+    const bool plain = !scale && !shift && act == R3D_ACT_NONE, full = mw + 32 <= M && n0 + BN <= Co, stats = stats_part != nullptr;
     if (plain) {
       if (stats) { if (full) epilogue(T_{}, T_{}, T_{}); else epilogue(T_{}, T_{}, F_{}); }
       else       { if (full) epilogue(T_{}, F_{}, T_{}); else epilogue(T_{}, F_{}, F_{}); }

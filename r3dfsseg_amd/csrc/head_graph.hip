@@ -14,7 +14,7 @@
 //      [1-alpha, 1+alpha]); all n_way+1 right-hand sides share every SpMV.  The reference's
 //      "+ eps" on every matrix element (2.2e-16) is below fp32 resolution of the diagonal
 //      and perturbs Z by < 1e-9; it is dropped (tests/test_oracle_props.py shows the bound).
-// Node count n lives in device memory (descriptor word HD_N_NODES); grids are sized by
+// Node count n lives in device memory (descriptor word R3D_HD_N_NODES); grids are sized by
 // the capacity n_cap.
 #include "common.h"
 

@@ -16,21 +16,12 @@
 // channel-ascending fmaf chains evaluated by ONE thread per point.
 #include "common.h"
 
-#define HP_MAXSEG 8
 #define HP_BLOCK 256
 #define HP_MAXK 128
 #define HP_DP 256      // row pitch (floats) of the compacted point-major copy
 
-// int32 words of the device-side descriptor
-enum {
-  HD_SEG_COUNT = 0,                     // [HP_MAXSEG] points per segment
-  HD_SEG_M = HP_MAXSEG,                 // [HP_MAXSEG] prototypes per segment
-  HD_SEG_POFF = 2 * HP_MAXSEG,          // [HP_MAXSEG] first node row of the segment's prototypes
-  HD_N_PROTO = 3 * HP_MAXSEG,
-  HD_N_NODES = 3 * HP_MAXSEG + 1,
-  HD_FPS_TIMEOUT = 3 * HP_MAXSEG + 2,   // != 0: a workgroup of the one-launch FPS gave up waiting for its peers
-  HD_WORDS = 3 * HP_MAXSEG + 8
-};
+// the device-side descriptor: R3D_HD_WORDS int32 words, R3D_HD_* (r3d.h)
+static_assert(R3D_HD_WORDS == 32 && R3D_HD_FPS_TIMEOUT < R3D_HD_WORDS, "the descriptor is 32 words");
 
 // Batches of episodes (round 3): every kernel below takes the episode from a grid dimension and shifts its per-episode
 // pointers by the strides of HpEp (elements of each array between consecutive episodes; all capacity sized, so episode e
@@ -116,8 +107,8 @@ __global__ __launch_bounds__(1024) void r3d_head_compact_kernel(const int* __res
     if (tid == 0) base_s = base + tot;
     __syncthreads();
   }
-  if (tid == 0) desc[HD_SEG_COUNT + seg] = base_s;
-  if (tid == 0 && seg == 0) desc[HD_FPS_TIMEOUT] = 0;
+  if (tid == 0) desc[R3D_HD_SEG_COUNT + seg] = base_s;
+  if (tid == 0 && seg == 0) desc[R3D_HD_FPS_TIMEOUT] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_head_gather_kernel(const float* 
   HP_SHIFT(featP, st.ws);
   int blk0;
   const int seg = g.seg_of_block(blockIdx.x, &blk0);
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   const int bis = blockIdx.x - blk0;
   if ((long)bis * HP_BLOCK >= count) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -214,7 +205,7 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_fps_round_kernel(
   int blk0;
   const int seg = g.seg_of_block(blockIdx.x, &blk0);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   if (count <= k) return;  // identity case (mpti.py:631-634): no sampling
   const int bis = blockIdx.x - blk0;  // block index inside the segment
   if ((long)bis * HP_BLOCK >= count) return;
@@ -315,7 +306,7 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_fps_round_kernel(
 //     Co-residency: all workgroups of a grid that hold points must be resident together (one workgroup waits
 //     for its peers).  A workgroup needs ~200 VGPRs, i.e. 2 workgroups fit a CU, 512 on the chip; the caller
 //     groups the episodes of a batch into launches that stay below that (fps_group).  A waiter that sees
-//     nothing for ~2 s sets desc[HD_FPS_TIMEOUT] and proceeds, so a mis-sized launch ends with an error flag
+//     nothing for ~2 s sets desc[R3D_HD_FPS_TIMEOUT] and proceeds, so a mis-sized launch ends with an error flag
 //     instead of a hung GPU.
 // ---------------------------------------------------------------------------
 #define FPS_SPIN_LIMIT (1 << 22)
@@ -384,7 +375,7 @@ __global__ __launch_bounds__(HP_BLOCK) __attribute__((amdgpu_waves_per_eu(LC ? 3
   {
     int first = 0;
     for (int s = 0; s < g.nseg(); ++s) {
-      const int cnt = desc[HD_SEG_COUNT + s];
+      const int cnt = desc[R3D_HD_SEG_COUNT + s];
       const int nb = cnt > k ? (cnt + HP_BLOCK - 1) / HP_BLOCK : 0;  // count <= k: identity case (mpti.py:631-634), no sampling
       if (seg < 0 && (int)blockIdx.x < first + nb) { seg = s; bis = blockIdx.x - first; count = cnt; blk0 = first; }
       first += nb;
@@ -470,7 +461,7 @@ __global__ __launch_bounds__(HP_BLOCK) __attribute__((amdgpu_waves_per_eu(LC ? 3
           word = __hip_atomic_load(&cw[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           ++spins;
         }
-        if (word == 0ull) desc[HD_FPS_TIMEOUT] = 1;
+        if (word == 0ull) desc[R3D_HD_FPS_TIMEOUT] = 1;
         win = word > win ? word : win;
       }
 #pragma unroll
@@ -496,7 +487,7 @@ __global__ __launch_bounds__(HP_BLOCK) __attribute__((amdgpu_waves_per_eu(LC ? 3
         win = __hip_atomic_load(&res[round], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ++spins;
       }
-      if (win == 0ull) desc[HD_FPS_TIMEOUT] = 1;
+      if (win == 0ull) desc[R3D_HD_FPS_TIMEOUT] = 1;
     }
     if (tid == 0) {
       const unsigned wp = 0xffffffffu - (unsigned)(win & 0xffffffffull);
@@ -519,10 +510,10 @@ __global__ __launch_bounds__(HP_MAXK) void r3d_fps_finalize_kernel(SegGeom g, in
   const int ep = blockIdx.x;
   HP_SHIFT(sel, st.ws); HP_SHIFT(seeds, st.ws); HP_SHIFT(desc, st.desc);
   __shared__ int a[HP_MAXK];
-  __shared__ int m_s[HP_MAXSEG];
+  __shared__ int m_s[R3D_HD_MAXSEG];
   const int tid = threadIdx.x;
   for (int seg = 0; seg < g.nseg(); ++seg) {
-    const int count = desc[HD_SEG_COUNT + seg];
+    const int count = desc[R3D_HD_SEG_COUNT + seg];
     int m;
     if (count <= k) {  // identity: every point is its own prototype
       m = count;
@@ -563,12 +554,12 @@ __global__ __launch_bounds__(HP_MAXK) void r3d_fps_finalize_kernel(SegGeom g, in
   if (tid == 0) {
     int off = 0;
     for (int seg = 0; seg < g.nseg(); ++seg) {
-      desc[HD_SEG_M + seg] = m_s[seg];
-      desc[HD_SEG_POFF + seg] = off;
+      desc[R3D_HD_SEG_M + seg] = m_s[seg];
+      desc[R3D_HD_SEG_POFF + seg] = off;
       off += m_s[seg];
     }
-    desc[HD_N_PROTO] = off;
-    desc[HD_N_NODES] = off + n_query_pts;
+    desc[R3D_HD_N_PROTO] = off;
+    desc[R3D_HD_N_NODES] = off + n_query_pts;
   }
 }
 
@@ -593,10 +584,10 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_assign_kernel(const float* __res
   int blk0;
   const int seg = g.seg_of_block(blockIdx.x, &blk0);
   const int tid = threadIdx.x;
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   const int bis = blockIdx.x - blk0;
   if ((long)bis * HP_BLOCK >= count) return;
-  const int m = desc[HD_SEG_M + seg];
+  const int m = desc[R3D_HD_SEG_M + seg];
   const int s0 = blockIdx.y * AS_TILE;
   if (s0 >= m) return;
   const int pos = bis * HP_BLOCK + tid;
@@ -672,8 +663,8 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_cluster_partial_kernel(
   const int seg = blockIdx.z - ep * g.nseg(), s = blockIdx.x, chunk = blockIdx.y;
   feat += (long)ep * st.feat * ldf; HP_SHIFT(comp, st.ws); HP_SHIFT(desc, st.desc); HP_SHIFT(assign, st.assign);
   HP_SHIFT(part, st.ws); HP_SHIFT(part_cnt, st.ws);
-  const int m = desc[HD_SEG_M + seg];
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int m = desc[R3D_HD_SEG_M + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   if (s >= m || (long)chunk * CM_CHUNK >= count) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -730,9 +721,9 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_cluster_reduce_kernel(
   nodes += (long)ep * st.nodes * ldn; node_labels += (long)ep * st.labels * 4;
   if (node_labels2) node_labels2 += (long)ep * st.labels * 4;
   if (cluster_count) HP_SHIFT(cluster_count, st.ccount);
-  const int m = desc[HD_SEG_M + seg];
+  const int m = desc[R3D_HD_SEG_M + seg];
   if (s >= m) return;
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   const int nchunks = (count + CM_CHUNK - 1) / CM_CHUNK;
   const int tid = threadIdx.x;
   float sum = 0.f;
@@ -742,7 +733,7 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_cluster_reduce_kernel(
     sum += part[slot * 256 + tid];
     total += part_cnt[slot];
   }
-  const int row = desc[HD_SEG_POFF + seg] + s;
+  const int row = desc[R3D_HD_SEG_POFF + seg] + s;
   if (tid < D) nodes[(long)row * ldn + tid] = sum / (float)total;  // 0/0 = NaN for an empty cluster, as torch
   if (tid < 4) node_labels[(long)row * 4 + tid] = (tid == seg) ? 1.f : 0.f;
   if (tid < 4 && node_labels2) node_labels2[(long)row * 4 + tid] = (tid + 4 == seg) ? 1.f : 0.f;
@@ -760,7 +751,7 @@ __global__ void r3d_nodes_append_query_kernel(const float* __restrict__ qfeat, l
   qfeat += (long)ep * st.qfeat * ldq; HP_SHIFT(desc, st.desc);
   nodes += (long)ep * st.nodes * ldn; node_labels += (long)ep * st.labels * 4;
   if (node_labels2) node_labels2 += (long)ep * st.labels * 4;
-  const int n_proto = desc[HD_N_PROTO];
+  const int n_proto = desc[R3D_HD_N_PROTO];
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)nq_pts * D) return;
   const long r = (long)((unsigned)i / (unsigned)D);  // (n_query_pts D < 2^31, checked by the entry point: a 32-bit division)
@@ -774,7 +765,7 @@ __global__ void r3d_nodes_append_query_kernel(const float* __restrict__ qfeat, l
 // C ABI
 // ===========================================================================
 static int check_geom(const char* fn, int n_way, int k_shot, int N, int D) {
-  if (n_way < 1 || n_way + 1 > HP_MAXSEG || k_shot < 1 || N < 1 || D < 1 || D > 256) {
+  if (n_way < 1 || n_way + 1 > R3D_HD_MAXSEG || k_shot < 1 || N < 1 || D < 1 || D > 256) {
     r3d_set_error("%s: unsupported geometry n_way=%d k_shot=%d N=%d D=%d (n_way<=7, D<=256)", fn, n_way,
                   k_shot, N, D);
     return R3D_ERR_ARG;
@@ -793,7 +784,7 @@ static int check_query_rows(const char* fn, int n_query_pts, int D) {  // (the q
   return 0;
 }
 
-extern "C" int r3d_head_desc_words(void) { return HD_WORDS; }
+extern "C" int r3d_head_desc_words(void) { return R3D_HD_WORDS; }
 
 // out[n] = the seeds a segment of n points gets at k (n in [0, n_max)): the device's evaluation of hp_fps_count, so that
 // a test can hold it to numpy's float32 arithmetic for EVERY point count (tests/test_gpu_head.py)
@@ -824,14 +815,14 @@ static HpWs hp_carve(const SegGeom& g) {
   L.mind = o; o += cap;
   L.assign = o; o += cap;
   L.cand = o; o += 4L * g.total_blocks();                          // 2 x blocks x (value, position)
-  L.sel = o; o += (long)HP_MAXSEG * HP_MAXK;
-  L.seeds = o; o += (long)HP_MAXSEG * HP_MAXK + 64;
+  L.sel = o; o += (long)R3D_HD_MAXSEG * HP_MAXK;
+  L.seeds = o; o += (long)R3D_HD_MAXSEG * HP_MAXK + 64;
   L.part = o; o += (long)g.nseg() * HP_MAXK * L.max_chunks * 256;  // cluster partial sums
   L.part_cnt = o; o += (long)g.nseg() * HP_MAXK * L.max_chunks;
   L.featC = o; o += 256L * (cap + 64);                             // compacted channel-major copy (D <= 256 rows)
   o = (o + 3) & ~3L;
   // one-launch FPS: a candidate word per (round, workgroup) and a result word per (segment, round), 64 bit each
-  L.xch = o; o += 2L * HP_MAXK * ((g.cap(0) + HP_BLOCK - 1) / HP_BLOCK + g.nseg()) + 2L * HP_MAXSEG * HP_MAXK;
+  L.xch = o; o += 2L * HP_MAXK * ((g.cap(0) + HP_BLOCK - 1) / HP_BLOCK + g.nseg()) + 2L * R3D_HD_MAXSEG * HP_MAXK;
   L.best = o; o += 2L * cap + 2;                                   // 64-bit (distance, seed) minimum per point
   o = (o + 3) & ~3L;
   L.featP = o; o += cap * HP_DP;                                   // compacted point-major copy
@@ -932,7 +923,7 @@ extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_
                      featP, e2);
   if (flags & R3D_HEAD_FPS_ONE_LAUNCH) {
     const int tb_dense = (int)((g.cap(0) + HP_BLOCK - 1) / HP_BLOCK) + g.nseg();  // the segments' counts add up to cap(0)
-    r3d_fill_words_ep(xch, 0u, 2L * kr * tb_dense + 2L * HP_MAXSEG * HP_MAXK, n_ep, e2.ws, st);
+    r3d_fill_words_ep(xch, 0u, 2L * kr * tb_dense + 2L * R3D_HD_MAXSEG * HP_MAXK, n_ep, e2.ws, st);
     // the launch's workgroups wait for each other: never more of them than the chip holds at once, whatever the caller asks
     const int grp = fps_slots_clamp(D, tb_dense, fps_group);
     for (int e0 = 0; e0 < n_ep; e0 += grp) {
@@ -1001,10 +992,10 @@ static __device__ __forceinline__ void at_attach_system(
     float4* __restrict__ labels2 /* or null */, int* __restrict__ desc, long desc_stride, int* __restrict__ ccount /* or null */,
     long ccount_stride) {
   const int tid = threadIdx.x;
-  int n_proto = fit_desc[HD_N_PROTO];
+  int n_proto = fit_desc[R3D_HD_N_PROTO];
   n_proto = n_proto < 0 ? 0 : (n_proto > proto_cap ? proto_cap : n_proto);
-  if (blockIdx.x == 0 && tid < HD_WORDS)
-    desc[sys * desc_stride + tid] = tid == HD_N_PROTO ? n_proto : tid == HD_N_NODES ? n_proto + nq_pts : fit_desc[tid];
+  if (blockIdx.x == 0 && tid < R3D_HD_WORDS)
+    desc[sys * desc_stride + tid] = tid == R3D_HD_N_PROTO ? n_proto : tid == R3D_HD_N_NODES ? n_proto + nq_pts : fit_desc[tid];
   qfeat += grp * qfeat_sys_rows * ldq4;
   nodes += sys * n_cap * ldn4;
   labels += sys * n_cap;
@@ -1085,7 +1076,7 @@ extern "C" int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes
                                                void* stream) {
   const char* fn = "r3d_head_attach_queries_batched";
   R3D_REQUIRE(fit_nodes && fit_labels && fit_desc && qfeat && nodes && node_labels && desc, "%s: null pointer", fn);
-  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= HP_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
+  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= R3D_HD_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
               "%s: unsupported geometry n_way=%d D=%d (n_way <= 7, D <= 256 and a multiple of 4)", fn, n_way, D);
   R3D_REQUIRE(n_sys >= 1 && n_sys <= 65535 && n_query_pts >= 1 && proto_cap >= 1 && (n_sys == 1 || qfeat_sys_rows >= n_query_pts),
               "%s: %d systems of %d query rows (%ld rows between them), %d prototype slots", fn, n_sys, n_query_pts,
@@ -1101,7 +1092,7 @@ extern "C" int r3d_head_attach_queries_batched(int n_sys, const float* fit_nodes
               "%s: row pitches %ld / %ld / %ld must be multiples of 4 floats >= D = %d", fn, fit_ldn, ldq, ldn, D);
   R3D_REQUIRE((((uintptr_t)fit_nodes | (uintptr_t)fit_labels | (uintptr_t)qfeat | (uintptr_t)nodes | (uintptr_t)node_labels) & 15) == 0,
               "%s: node, label and query rows must be 16-byte aligned", fn);
-  R3D_REQUIRE(desc_stride >= HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)HD_WORDS);
+  R3D_REQUIRE(desc_stride >= R3D_HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)R3D_HD_WORDS);
   R3D_REQUIRE(!cluster_count || n_sys == 1 || ccount_stride >= n_cap, "%s: cluster_count stride %ld < n_cap = %d", fn,
               ccount_stride, n_cap);
   const int d4 = D / 4;
@@ -1124,7 +1115,7 @@ extern "C" int r3d_head_attach_queries_sets(int n_groups, int n_sets, const uint
                                             void* stream) {
   const char* fn = "r3d_head_attach_queries_sets";
   R3D_REQUIRE(fits && qfeat && nodes && node_labels && desc, "%s: null pointer", fn);
-  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= HP_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
+  R3D_REQUIRE(n_way >= 1 && n_way + 1 <= R3D_HD_MAXSEG && D >= 4 && D <= 256 && D % 4 == 0,
               "%s: unsupported geometry n_way=%d D=%d (n_way <= 7, D <= 256 and a multiple of 4)", fn, n_way, D);
   R3D_REQUIRE(n_groups >= 1 && n_sets >= 1 && (long)n_groups * n_sets <= 65535 && n_query_pts >= 1 && proto_cap >= 1 &&
                   (n_groups == 1 || qfeat_sys_rows >= n_query_pts),
@@ -1142,7 +1133,7 @@ extern "C" int r3d_head_attach_queries_sets(int n_groups, int n_sets, const uint
   R3D_REQUIRE((((uintptr_t)fits & 7) | (((uintptr_t)qfeat | (uintptr_t)nodes | (uintptr_t)node_labels) & 15)) == 0,
               "%s: the fit table must be 8-byte, node, label and query rows 16-byte aligned", fn);
   const long n_sys = (long)n_groups * n_sets;
-  R3D_REQUIRE(desc_stride >= HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)HD_WORDS);
+  R3D_REQUIRE(desc_stride >= R3D_HD_WORDS || n_sys == 1, "%s: desc stride %ld < %d words", fn, desc_stride, (int)R3D_HD_WORDS);
   R3D_REQUIRE(!cluster_count || n_sys == 1 || ccount_stride >= n_cap, "%s: cluster_count stride %ld < n_cap = %d", fn,
               ccount_stride, n_cap);
   const int d4 = D / 4;
@@ -1171,11 +1162,11 @@ __global__ __launch_bounds__(HP_BLOCK) void r3d_proto_bwd_kernel(const float* __
   HP_SHIFT(cluster_count, st.ccount); dsfeat += (long)ep * st.feat * lds_;
   int blk0;
   const int seg = g.seg_of_block(blockIdx.x, &blk0);
-  const int count = desc[HD_SEG_COUNT + seg];
+  const int count = desc[R3D_HD_SEG_COUNT + seg];
   const int bis = blockIdx.x - blk0;
   if ((long)bis * HP_BLOCK >= count) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int poff = desc[HD_SEG_POFF + seg];
+  const int poff = desc[R3D_HD_SEG_POFF + seg];
   for (int pos = bis * HP_BLOCK + w; pos < min(count, (bis + 1) * HP_BLOCK); pos += 4) {
     const int gp = comp[g.off(seg) + pos];
     const int row = poff + assign[g.off(seg) + pos];
@@ -1188,7 +1179,7 @@ __global__ void r3d_query_bwd_kernel(const float* __restrict__ dnodes, long ldd,
                                      const int* __restrict__ desc, float* __restrict__ dqfeat, long ldq, HpEp st) {
   const int ep = blockIdx.y;
   dnodes += (long)ep * st.nodes * ldd; HP_SHIFT(desc, st.desc); dqfeat += (long)ep * st.qfeat * ldq;
-  const int n_proto = desc[HD_N_PROTO];
+  const int n_proto = desc[R3D_HD_N_PROTO];
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)nq_pts * D) return;
   const long r = (long)((unsigned)i / (unsigned)D);  // (n_query_pts D < 2^31, checked by the entry point: a 32-bit division)

@@ -24,7 +24,6 @@
 #define KNN_SLAB 64
 #define KNN_ROWS_PER_WAVE 8
 
-enum { R3D_SCORE_DGCNN = 0, R3D_SCORE_L2 = 1 };
 
 // ---- squared norms: channel-ascending fmaf chain (== diagonal of the MFMA product)
 __global__ void r3d_sqnorm_kernel(const float* __restrict__ x, long ldx, int rows, int C,
@@ -1530,10 +1529,10 @@ extern "C" long r3d_cm_pitch(int N) { return (long)((N + 31) / 32) * 32 + 32; }
 // floats of r3d_knn_topk's norm_ws: the squared norms (B*N) + one overflow flag per 32-row tile (k <= 32 path) + padding
 extern "C" long r3d_knn_norm_ws_words(int B, int N) { return (long)B * N + (long)B * ((N + 31) / 32) + 64; }
 
-enum KnnPath {
-  KNN_STREAMED_SMALL,  // k <= 32, C <= 64: append-and-rank, mid configuration; overflowed tiles redone by the two-pass kernel
-  KNN_STREAMED_LARGE,  // k > 32 with a status word: append-and-rank, big configuration; overflow -> *status bit 0
-  KNN_INSERTION,       // everything else: the sorted-insertion kernel
+enum KnnPath {  // the values r3d_debug_knn_path reports under R3D_KNN_PATH_MASK
+  KNN_STREAMED_SMALL = R3D_KNN_PATH_SMALL,  // k <= 32, C <= 64: append-and-rank, mid configuration; overflowed tiles redone by the two-pass kernel
+  KNN_STREAMED_LARGE = R3D_KNN_PATH_LARGE,  // k > 32 with a status word: append-and-rank, big configuration; overflow -> *status bit 0
+  KNN_INSERTION = R3D_KNN_PATH_INSERTION,   // everything else: the sorted-insertion kernel
 };
 struct KnnPlan {
   KnnPath path;
@@ -1587,23 +1586,19 @@ static KnnPlan knn_plan(int B, int N, int C, int k, bool status, bool x_cm, bool
 }
 
 extern "C" long r3d_knn_ws_words(int B, int N, int C, int k, int flags) {
-  return knn_plan(B, N, C, k, flags & 1, flags & 2, true).words;
+  return knn_plan(B, N, C, k, flags & R3D_KNN_FLAG_STATUS, flags & R3D_KNN_FLAG_X_CM, true).words;
 }
 
 // What one call launches: the ONE place that decides it.  knn_choose is a pure host function of the plan, the two A/B
 // switches and what the caller handed over; knn_topk_impl branches on its result and on nothing else, and
 // r3d_debug_knn_path returns the same result as a bit mask (tests assert the path a case claims to reach).
-enum KnnChan {
-  KNN_CHAN_ANY,   // channel chunks of 64, the last one padded (FULLC = false)
-  KNN_CHAN_LE16,  // (small path) C <= 16: one chunk of 16 channels
-  KNN_CHAN_FULL,  // C % 64 == 0: every chunk is whole (FULLC)
-};
 struct KnnChoice {
   KnnPath path;
   bool few, split;  // as planned
   bool bfa;         // the threshold pass runs on the bf16 pieces
   bool filter;      // (small) ... and pass B is the bf16 filter + exact scores of the survivors
-  KnnChan chan;
+  int chan;         // R3D_KNN_CHAN_ANY: channel chunks of 64, the last one padded (FULLC = false); _LE16: (small path) C <= 16, one
+                    // chunk of 16 channels; _FULL: C % 64 == 0, every chunk is whole (FULLC)
   int regs;         // (insertion) list registers per lane: 1, 2 or 4
 };
 static KnnChoice knn_choose(const KnnPlan& p, bool bf16_threshold, bool bf16_filter, bool has_x, int ldx_mod4,
@@ -1616,21 +1611,24 @@ static KnnChoice knn_choose(const KnnPlan& p, bool bf16_threshold, bool bf16_fil
   }
   ch.few = p.few;
   ch.split = p.split;
-  ch.chan = p.path == KNN_STREAMED_SMALL && p.C <= 16 ? KNN_CHAN_LE16 : p.C % 64 == 0 ? KNN_CHAN_FULL : KNN_CHAN_ANY;
+  ch.chan = p.path == KNN_STREAMED_SMALL && p.C <= 16 ? R3D_KNN_CHAN_LE16 : p.C % 64 == 0 ? R3D_KNN_CHAN_FULL : R3D_KNN_CHAN_ANY;
   ch.bfa = p.bf && bf16_threshold && has_x;  // the pieces are cut from the point-major rows (p.bf: C % 64 == 0)
   // the filter reads the point-major rows as 16-byte vectors, and its survivor bitmap, 32 words per sub-tile, sits in
   // the index buffer's 32 KM_CAP words
   ch.filter = p.path == KNN_STREAMED_SMALL && ch.bfa && bf16_filter && ldx_mod4 == 0 && x_aligned16 && p.tiles <= KM_CAP;
   return ch;
 }
-// flags: bit 0 status given, bit 1 x_cm given (as r3d_knn_ws_words), bit 2 x is NULL, bit 3 the call is r3d_knn_topk
-// (two fixed scratch buffers: no bf16 pieces, no split lists).  Launches nothing, needs no device.
+// flags: R3D_KNN_FLAG_* (r3d.h; _FIXED_SCRATCH: r3d_knn_topk's two fixed scratch buffers, no bf16 pieces, no split lists).
+// Launches nothing, needs no device.
 extern "C" int r3d_debug_knn_path(int B, int N, int C, int k, int flags, long ldx, int x_misalign_bytes) {
   if (B <= 0 || N <= 0 || C <= 0 || k <= 0 || k > N || k > 256) return -1;
-  const KnnChoice ch = knn_choose(knn_plan(B, N, C, k, flags & 1, flags & 2, !(flags & 8)), g_knn_bf16_threshold,
-                                  g_knn_bf16_filter, !(flags & 4), (int)(ldx & 3), (x_misalign_bytes & 15) == 0);
-  return (int)ch.path | ch.few << 2 | ch.split << 3 | ch.bfa << 4 | ch.filter << 5 | (int)ch.chan << 6 |
-         (ch.regs == 4 ? 3 : ch.regs) << 8;
+  const KnnChoice ch = knn_choose(knn_plan(B, N, C, k, flags & R3D_KNN_FLAG_STATUS, flags & R3D_KNN_FLAG_X_CM,
+                                           !(flags & R3D_KNN_FLAG_FIXED_SCRATCH)),
+                                  g_knn_bf16_threshold, g_knn_bf16_filter, !(flags & R3D_KNN_FLAG_NO_X), (int)(ldx & 3),
+                                  (x_misalign_bytes & 15) == 0);
+  return (int)ch.path | (ch.few ? R3D_KNN_PATH_FEW : 0) | (ch.split ? R3D_KNN_PATH_SPLIT : 0) | (ch.bfa ? R3D_KNN_PATH_BFA : 0) |
+         (ch.filter ? R3D_KNN_PATH_FILTER : 0) | ch.chan |
+         (ch.regs == 4 ? R3D_KNN_REGS_4 : ch.regs == 2 ? R3D_KNN_REGS_2 : ch.regs == 1 ? R3D_KNN_REGS_1 : 0);
 }
 
 // one call's operands and scratch, as the kernels take them (xT: the streamed kernels' channel-major operand)
@@ -1749,7 +1747,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
     // append-and-rank (mid configuration); tiles whose survivor buffer overflowed are redone by the exact
     // two-pass kernel in the same stream -- no host round trip, never a wrong result
     r3d_zero_words(c.tile_flags, (long)c.B * grid.x, c.st);
-    if (ch.chan == KNN_CHAN_LE16) {
+    if (ch.chan == R3D_KNN_CHAN_LE16) {
       rc = ch.few ? knn_append_launch<8, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags)
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 8, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
     } else if (ch.bfa) {
@@ -1759,7 +1757,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
       // half pass saved -- 3.30 against 3.63 ms per 384 clouds.)
       rc = ch.filter ? knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, 1, true, true, true>(c, grid, nullptr, c.tile_flags)
                      : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true, true>(c, grid, nullptr, c.tile_flags);
-    } else if (ch.chan == KNN_CHAN_FULL) {
+    } else if (ch.chan == R3D_KNN_CHAN_FULL) {
       rc = ch.few ? knn_append_launch<8, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags)
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, true>(c, grid, nullptr, c.tile_flags);
     } else {
@@ -1767,7 +1765,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
                  : knn_append_launch<KM_WAVES, KM_CAP, KM_TOP, 32, KM_SAMPLE, false>(c, grid, nullptr, c.tile_flags);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(ch.chan == KNN_CHAN_LE16 ? r3d_knn_small_kernel<8> : r3d_knn_small_kernel<32>, grid, dim3(256), 0, c.st,
+    hipLaunchKernelGGL(ch.chan == R3D_KNN_CHAN_LE16 ? r3d_knn_small_kernel<8> : r3d_knn_small_kernel<32>, grid, dim3(256), 0, c.st,
                        c.xT, c.ldT, c.N, c.C, c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, (const int*)c.tile_flags);
     R3D_LAUNCH_CHECK("r3d_knn_topk(small)");
     return R3D_OK;
@@ -1779,7 +1777,7 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
   if (ch.bfa) {
     knn_pack_bf(c);
     rc = knn_append_launch<8, 384, 2, 32, 1, true, true>(c, gb, status, nullptr);
-  } else if (ch.chan == KNN_CHAN_FULL) {
+  } else if (ch.chan == R3D_KNN_CHAN_FULL) {
     rc = knn_append_launch<8, 384, 2, 32, 1, true>(c, gb, status, nullptr);
   } else {
     rc = knn_append_launch<8, 384, 2, 32, 1, false>(c, gb, status, nullptr);

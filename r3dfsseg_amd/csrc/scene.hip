@@ -18,8 +18,6 @@
 // the only floating-point sums are the vote's, one running sum per (point, class) in a fixed order.
 #include "scene_common.h"
 
-#define SC_MAX_CELLS 65536
-
 // record of r3d_scene_plan (ints)
 #define SC_P_NCHUNKS 0
 #define SC_P_NBLOCKS 1
@@ -28,9 +26,8 @@
 #define SC_P_NRUN 4
 #define SC_P_NSKIPPED 5
 #define SC_P_NVOTED_RUN 6
-// transfer: queries per workgroup (one thread each), candidate rows staged through LDS at a time (16 KiB)
-#define SC_Q_TILE 256
-#define SC_C_TILE 1024
+// transfer: R3D_SCENE_TRANSFER_QUERY_TILE queries per workgroup (one thread each), R3D_SCENE_TRANSFER_CAND_TILE candidate
+// rows staged through LDS at a time (16 KiB)
 // record of r3d_scene_transfer (ints, in the sparse workspace)
 #define SC_T_NTRANSFERRED 0
 #define SC_T_NTILES 1
@@ -65,7 +62,7 @@ static sc_layout sc_make_layout(long M, long n_cells, long chunk_cap) {
 }
 
 static bool sc_shape_ok(long M, int ncx, int ncy, int r, long chunk_cap) {
-  return M > 0 && M <= SC_MAX_POINTS && ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS && r >= 1 && r <= 4 &&
+  return M > 0 && M <= R3D_SCENE_MAX_POINTS && ncx > 0 && ncy > 0 && (long)ncx * ncy <= R3D_SCENE_MAX_CELLS && r >= 1 && r <= 4 &&
          chunk_cap >= 0 && chunk_cap < (1L << 30);
 }
 
@@ -240,7 +237,7 @@ extern "C" int r3d_scene_ws_offsets(long M, int ncx, int ncy, long chunk_cap, lo
 // what every entry point that works on a plan has: the scan's size, the cells and the workspace
 static int sc_check_plan(const char* name, long M, int ncx, int ncy, long chunk_cap, long ws_words) {
   SC_TRY(sc_check_points(name, M));
-  R3D_REQUIRE(ncx > 0 && ncy > 0 && (long)ncx * ncy <= SC_MAX_CELLS, "%s: %d x %d cells (1 .. 65536)", name, ncx, ncy);
+  R3D_REQUIRE(ncx > 0 && ncy > 0 && (long)ncx * ncy <= R3D_SCENE_MAX_CELLS, "%s: %d x %d cells (1 .. 65536)", name, ncx, ncy);
   R3D_REQUIRE(chunk_cap > 0 && chunk_cap < (1L << 30), "%s: chunk_cap %ld", name, chunk_cap);
   return sc_check_ws(name, ws_words, r3d_scene_ws_words(M, ncx, ncy, chunk_cap));
 }
@@ -605,7 +602,7 @@ extern "C" int r3d_scene_run_tables(long M, int ncx, int ncy, int r, int N, long
 //   flags    voff[i] = 1 when the point at sorted position i is voted; source = the point itself, or -1
 //   scan     voff in place, exclusive (the three scan kernels of the sort)
 //   compact  voted points -> cand rows {x, y, z, index} at voff; the others -> uq at i - voff[i]
-//   tiles    per cell ceil(points without a vote / SC_Q_TILE) query tiles, their exclusive scan
+//   tiles    per cell ceil(points without a vote / R3D_SCENE_TRANSFER_QUERY_TILE) query tiles, their exclusive scan
 //   transfer one workgroup per query tile; the candidate runs of the three cell rows go through LDS
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_transfer_flags_kernel(int M, const int* __restrict__ order,
                                                                               const int* __restrict__ votes,
@@ -661,7 +658,7 @@ __global__ __launch_bounds__(SC_PLAN_THREADS) void r3d_scene_transfer_tiles_kern
     if (c < n_cells) {
       const int s = sc_clamp(cell[c], 0, M), e = sc_clamp(cell[c + 1], s, M);
       const int u = (e - s) - (voff[e] - voff[s]);
-      t = u > 0 ? (u + SC_Q_TILE - 1) / SC_Q_TILE : 0;
+      t = u > 0 ? (u + R3D_SCENE_TRANSFER_QUERY_TILE - 1) / R3D_SCENE_TRANSFER_QUERY_TILE : 0;
     }
     int total;
     const int ex = r3d_block_excl_scan<SC_PLAN_THREADS>(t, wsum, total);
@@ -684,12 +681,12 @@ static __device__ __forceinline__ bool sc_closer(float d, int i, float bd, int b
 // the means scores[q] / votes[q] of the three, weighted by w = 1 / (d + 1e-8), every operation rounded on its own.  Voted
 // rows are only read and a receiver's row is written by its own thread.
 template <int NN>
-__global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
+__global__ __launch_bounds__(R3D_SCENE_TRANSFER_QUERY_TILE) void r3d_scene_transfer_kernel(
     const float* __restrict__ scan, int ld, int M, const int* __restrict__ cell, const int* __restrict__ voff,
     const int* __restrict__ uq, const int* __restrict__ tile0, const float4* __restrict__ cand, int ncx, int ncy, int K,
     float* __restrict__ scores, long long* __restrict__ labels, long long* __restrict__ source, int* __restrict__ rec,
     const int* __restrict__ votes, long long* __restrict__ neighbours, float* __restrict__ weights) {
-  __shared__ float4 rows[SC_C_TILE];
+  __shared__ float4 rows[R3D_SCENE_TRANSFER_CAND_TILE];
   const int n_cells = ncx * ncy, t = blockIdx.x, tid = threadIdx.x;
   if (t >= tile0[n_cells]) return;  // (uniform) the grid is an upper bound of the tiles
   int lo = 0, hi = n_cells;         // tile0[lo] <= t < tile0[hi]
@@ -699,7 +696,7 @@ __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
   }
   const int c = lo, cx = c % ncx, cy = c / ncx;
   const int s = sc_clamp(cell[c], 0, M), e = sc_clamp(cell[c + 1], s, M);
-  const int u = (s - voff[s]) + (t - tile0[c]) * SC_Q_TILE + tid;
+  const int u = (s - voff[s]) + (t - tile0[c]) * R3D_SCENE_TRANSFER_QUERY_TILE + tid;
   const bool live = u >= 0 && u < e - voff[e] && u < M;
   int p = live ? uq[u] : 0;
   p = sc_clamp(p, 0, M - 1);
@@ -717,10 +714,10 @@ __global__ __launch_bounds__(SC_Q_TILE) void r3d_scene_transfer_kernel(
     // cells (cx0 .. cx1, row) are neighbours in the sorted order: one run of candidate rows
     const int a = sc_clamp(voff[sc_clamp(cell[row * ncx + cx0], 0, M)], 0, M);
     const int b = sc_clamp(voff[sc_clamp(cell[row * ncx + cx1 + 1], 0, M)], a, M);
-    for (int base = a; base < b; base += SC_C_TILE) {
-      const int n = b - base < SC_C_TILE ? b - base : SC_C_TILE;
+    for (int base = a; base < b; base += R3D_SCENE_TRANSFER_CAND_TILE) {
+      const int n = b - base < R3D_SCENE_TRANSFER_CAND_TILE ? b - base : R3D_SCENE_TRANSFER_CAND_TILE;
       __syncthreads();  // the previous tile has been read
-      for (int k = tid; k < n; k += SC_Q_TILE) rows[k] = cand[base + k];
+      for (int k = tid; k < n; k += R3D_SCENE_TRANSFER_QUERY_TILE) rows[k] = cand[base + k];
       __syncthreads();
       if (live) {
 #pragma unroll 4
@@ -820,10 +817,10 @@ extern "C" int r3d_scene_transfer(const float* scan, int ld, long M, int ncx, in
                      sws + S.voff, cand, sws + S.uq);
   hipLaunchKernelGGL(r3d_scene_transfer_tiles_kernel, dim3(1), dim3(SC_PLAN_THREADS), 0, st, v.cell, sws + S.voff, v.n_cells,
                      (int)M, sws + S.tile0, sws + S.rec);
-  // sum over the cells of ceil(u / SC_Q_TILE) <= U / SC_Q_TILE + cells that hold such a point
-  const long tiles = M / SC_Q_TILE + (v.n_cells < M ? v.n_cells : M) + 1;
+  // sum over the cells of ceil(u / R3D_SCENE_TRANSFER_QUERY_TILE) <= U / R3D_SCENE_TRANSFER_QUERY_TILE + cells that hold such a point
+  const long tiles = M / R3D_SCENE_TRANSFER_QUERY_TILE + (v.n_cells < M ? v.n_cells : M) + 1;
   const auto kernel = neighbours ? r3d_scene_transfer_kernel<3> : r3d_scene_transfer_kernel<1>;
-  hipLaunchKernelGGL(kernel, dim3((int)tiles), dim3(SC_Q_TILE), 0, st, scan, ld, (int)M, v.cell, sws + S.voff, sws + S.uq,
+  hipLaunchKernelGGL(kernel, dim3((int)tiles), dim3(R3D_SCENE_TRANSFER_QUERY_TILE), 0, st, scan, ld, (int)M, v.cell, sws + S.voff, sws + S.uq,
                      sws + S.tile0, cand, ncx, ncy, n_classes, scores, (long long*)labels, (long long*)source, sws + S.rec, votes,
                      (long long*)neighbours, weights);
   R3D_LAUNCH_CHECK("r3d_scene_transfer");
@@ -893,8 +890,6 @@ extern "C" int r3d_scene_merge_sets(long M, int n_sets, int n_classes, const flo
 // fit_scene ("Fitting from an annotated scan"): the cloud of a block is its chunk 0 -- list positions
 // 0, nc, 2 nc, ..., len = ceil(n / nc) members --; fg[b][w] counts the members labelled classes[w]; way w's shots are
 // its eligible blocks (fg > max((int)floorf(len * min_ratio), min_fg)) by fg descending, block id ascending.
-#define SC_MAX_WAYS 7
-
 // One workgroup per block: threads stride over the len members, per way a ballot and a population count per wave, then
 // the integer sum of the waves in LDS.  Every member counts once (wrap-around slots are not visited); dropped blocks get 0.
 template <typename L>
@@ -902,7 +897,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_counts_kernel(
     const L* __restrict__ labels, int M, const int* __restrict__ order, const int* __restrict__ cell,
     const int* __restrict__ blk_n, const int* __restrict__ chunk0, sc_grid g, const int* __restrict__ classes, int n_way,
     int* __restrict__ fg) {
-  __shared__ int wcnt[SC_THREADS / R3D_WAVE][SC_MAX_WAYS + 1];
+  __shared__ int wcnt[SC_THREADS / R3D_WAVE][R3D_SCENE_SUPPORT_MAX_WAYS + 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = blk_n[b], nc = chunk0[b + 1] - chunk0[b];
   if (nc <= 0 || n <= 0) {  // (uniform) a dropped block
@@ -910,10 +905,10 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_counts_kernel(
     return;
   }
   const int bx = b % g.nbx, by = b / g.nbx, len = (n + nc - 1) / nc;
-  long long cls[SC_MAX_WAYS];
-  int acc[SC_MAX_WAYS];
+  long long cls[R3D_SCENE_SUPPORT_MAX_WAYS];
+  int acc[R3D_SCENE_SUPPORT_MAX_WAYS];
 #pragma unroll
-  for (int k = 0; k < SC_MAX_WAYS; ++k) {
+  for (int k = 0; k < R3D_SCENE_SUPPORT_MAX_WAYS; ++k) {
     cls[k] = k < n_way ? (long long)classes[k] : 0;
     acc[k] = 0;
   }
@@ -927,12 +922,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_counts_kernel(
       lab = (long long)labels[p];
     }
 #pragma unroll
-    for (int k = 0; k < SC_MAX_WAYS; ++k)
+    for (int k = 0; k < R3D_SCENE_SUPPORT_MAX_WAYS; ++k)
       if (k < n_way) acc[k] += __popcll(__ballot(live && lab == cls[k]));  // the wave's count, the same in every lane
   }
   if ((tid & 63) == 0) {
 #pragma unroll
-    for (int k = 0; k < SC_MAX_WAYS; ++k) wcnt[tid >> 6][k] = acc[k];
+    for (int k = 0; k < R3D_SCENE_SUPPORT_MAX_WAYS; ++k) wcnt[tid >> 6][k] = acc[k];
   }
   __syncthreads();
   if (tid < n_way) {
@@ -999,7 +994,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_support_pick_kernel(
 }
 
 #define SC_REQUIRE_SUPPORT_ARGS(name)                                                                                     \
-  R3D_REQUIRE(n_way >= 1 && n_way <= SC_MAX_WAYS, name ": n_way %d (1 .. 7)", n_way)
+  R3D_REQUIRE(n_way >= 1 && n_way <= R3D_SCENE_SUPPORT_MAX_WAYS, name ": n_way %d (1 .. 7)", n_way)
 
 extern "C" int r3d_scene_support_counts(long M, int ncx, int ncy, int r, int N, long chunk_cap, const int32_t* ws,
                                         long ws_words, const void* labels, int label_bytes, const int32_t* classes, int n_way,
@@ -1046,7 +1041,7 @@ extern "C" int r3d_scene_prepare_blocks(const float* scan, int ld, long M, int n
                                         const void* labels, int label_bytes, const int32_t* cloud_class, int32_t* mask,
                                         void* stream) {
   R3D_REQUIRE(blocks, "r3d_scene_prepare_blocks: null pointer (blocks)");
-  R3D_REQUIRE(G > 0 && G <= SC_MAX_CELLS, "r3d_scene_prepare_blocks: G %d (1 .. 65536 block ids)", G);
+  R3D_REQUIRE(G > 0 && G <= R3D_SCENE_MAX_CELLS, "r3d_scene_prepare_blocks: G %d (1 .. 65536 block ids)", G);
   R3D_REQUIRE((labels && cloud_class && mask) || (!labels && !cloud_class && !mask),
               "r3d_scene_prepare_blocks: labels %p, cloud_class %p and mask %p go together", labels, (const void*)cloud_class,
               (void*)mask);

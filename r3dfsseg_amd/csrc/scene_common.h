@@ -11,9 +11,7 @@
 #define SC_TILE 2048                 // points per sort tile, elements per scan block (8 per thread)
 #define SC_PLAN_THREADS 1024         // the one-workgroup kernels that scan a table
 #define SC_BOUNDS_BLOCKS 1024
-#define SC_MAX_POINTS (1L << 27)
 #define SC_COUNT_BLOCKS 1024         // workgroups of the kernels that end in atomics on a record
-#define SG_TILE 256                  // rows summed one at a time before their partial joins the total (pool, voxel means)
 
 // ------------------------------------------------------------------------------------------------ device helpers
 static __device__ __forceinline__ bool sc_finite3(float x, float y, float z) {
@@ -115,7 +113,7 @@ static inline int sc_check_ld(const char* name, int ld) {
 }
 
 static inline int sc_check_points(const char* name, long M) {
-  R3D_REQUIRE(M > 0 && M <= SC_MAX_POINTS, "%s: M %ld (1 .. 2^27 points)", name, M);
+  R3D_REQUIRE(M > 0 && M <= R3D_SCENE_MAX_POINTS, "%s: M %ld (1 .. 2^27 points)", name, M);
   return R3D_OK;
 }
 

@@ -8,21 +8,10 @@
 #pragma once
 #include "scene_common.h"
 
-#define GR_AXIS_MAX 1024  // voxels per axis: keys stay below 2^30
-// the record, words of ws[0 .. 16)
-#define GR_R_MIN 0        // x0 y0 z0 (float bits)
-#define GR_R_MAX 3        // the maxima (float bits)
-#define GR_R_NVALID 6
-#define GR_R_V 7          // occupied voxels (rows of the unit table)
-#define GR_R_NCOMP 8      // components
-#define GR_R_S 9          // kept components
-#define GR_R_NDROPPED 10  // points of dropped components
-#define GR_R_ERROR 11     // != 0: a bounded loop of the union-find ran out (bit 0 a find, bit 1 a unite)
-#define GR_R_ABSORBED_VOXELS 12  // voxels of dropped components taken into a kept one (absorb)
-#define GR_R_ABSORBED_POINTS 13  // their points
+static_assert(R3D_GROW_R_MAX + 3 <= R3D_SCENE_GROW_REC && R3D_GROW_R_ABSORBED_POINTS < R3D_SCENE_GROW_REC, "a word beyond the record");
 
 struct gr_layout {
-  long rec;              // 16
+  long rec;              // R3D_SCENE_GROW_REC words, R3D_GROW_R_* (r3d.h)
   long bpart;            // 7 * SC_BOUNDS_BLOCKS: partial bounds
   sc_sort_ws sort;       // pairs of M + 1 words; key of the pair the sort leaves free: the voxel heads, scanned
   long vkey;             // V: key of a voxel row
@@ -37,7 +26,7 @@ static inline gr_layout gr_make_layout(long M) {
   gr_layout L;
   const long Ma = sc_align(M + 1);
   long o = 0;
-  L.rec = o; o += 16;
+  L.rec = o; o += R3D_SCENE_GROW_REC;
   L.bpart = o; o += sc_align(7L * SC_BOUNDS_BLOCKS);
   o = sc_sort_ws_append(L.sort, o, M, Ma, sc_sort_part_words(M, M + 1));
   L.vkey = o; o += Ma;
@@ -71,7 +60,7 @@ static inline gr_view gr_make_view(long M, long key_max, const int32_t* ws) {
 static inline int gr_check_grid(const char* name, long M, int nx, int ny, int nz, const char* noun, const int32_t* ws) {
   R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
   SC_TRY(sc_check_points(name, M));
-  R3D_REQUIRE(nx >= 1 && nx <= GR_AXIS_MAX && ny >= 1 && ny <= GR_AXIS_MAX && nz >= 1 && nz <= GR_AXIS_MAX,
+  R3D_REQUIRE(nx >= 1 && nx <= R3D_SCENE_GROW_AXIS && ny >= 1 && ny <= R3D_SCENE_GROW_AXIS && nz >= 1 && nz <= R3D_SCENE_GROW_AXIS,
               "%s: %d x %d x %d %s (1 .. 1024 per axis)", name, nx, ny, nz, noun);
   return R3D_OK;
 }
@@ -233,7 +222,7 @@ static __device__ __forceinline__ void gr_unite(int* __restrict__ parent, int a,
 // ---- scene_grow.hip: the launches a second grower repeats.  ws and L: the workspace and its layout; every launcher only
 // queues work on st.
 // the sorted keys -> heads[i] = sorted position i opens a row (its key lies in 0 .. key_limit - 1 and differs from the one
-// in front), their exclusive scan in place, its total (the rows) into rec[GR_R_V]
+// in front), their exclusive scan in place, its total (the rows) into rec[R3D_GROW_R_V]
 R3D_INTERNAL void gr_launch_heads(const int* skey, long M, int key_limit, int* heads, int32_t* ws, const gr_layout& L,
                                   hipStream_t st);
 // after gr_launch_heads: the unit table (vkey: the keys in ascending order, vstart: a unit's first sorted position; row
@@ -243,9 +232,9 @@ R3D_INTERNAL void gr_launch_table(const int* skey, const int* order, long M, int
                                   int32_t* index, int32_t* ws, const gr_layout& L, hipStream_t st);
 // parent[v] = v
 R3D_INTERNAL void gr_launch_init(int V, int32_t* ws, const gr_layout& L, hipStream_t st);
-// root[], the points per root, the kept roots and their scan: words GR_R_NCOMP, GR_R_S (and GR_R_ERROR) of the record
+// root[], the points per root, the kept roots and their scan: words R3D_GROW_R_NCOMP, R3D_GROW_R_S (and R3D_GROW_R_ERROR) of the record
 R3D_INTERNAL void gr_launch_components(long M, int V, int min_points, int32_t* ws, const gr_layout& L, hipStream_t st);
 // the kept components numbered by ascending root: segment_points (S,) (skipped when null) and the id of every point from
-// the row of its unit; word GR_R_NDROPPED
+// the row of its unit; word R3D_GROW_R_NDROPPED
 R3D_INTERNAL void gr_launch_ids(long M, int V, int S, const int32_t* voxel_index, int32_t* segments, int32_t* segment_points,
                                 int32_t* ws, const gr_layout& L, hipStream_t st);

@@ -26,9 +26,7 @@
 // are defined there too, once.
 #include "scene_components.h"
 
-#define GR_RINGS_MAX 64   // rounds of absorb
-
-extern "C" long r3d_scene_grow_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? gr_make_layout(M).total : -1; }
+extern "C" long r3d_scene_grow_ws_words(long M) { return M > 0 && M <= R3D_SCENE_MAX_POINTS ? gr_make_layout(M).total : -1; }
 
 // what every entry point after the bounds has: the scan's size, the grid and the workspace
 static int gr_check(const char* name, long M, int nx, int ny, int nz, const int32_t* ws, long ws_words) {
@@ -78,7 +76,7 @@ __global__ void r3d_scene_grow_word_kernel(const int* __restrict__ src, int* __r
 void gr_launch_heads(const int* skey, long M, int key_limit, int* heads, int32_t* ws, const gr_layout& L, hipStream_t st) {
   hipLaunchKernelGGL(r3d_scene_grow_heads_kernel, dim3(sc_grid_of(M + 1)), dim3(SC_THREADS), 0, st, skey, (int)M, key_limit, heads);
   sc_excl_scan(heads, M + 1, ws + L.sort.part, st);
-  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, heads + M, ws + L.rec + GR_R_V);
+  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, heads + M, ws + L.rec + R3D_GROW_R_V);
 }
 
 extern "C" int r3d_scene_grow_sort(const float* scan, int ld, long M, float x0, float y0, float z0, float voxel, int nx, int ny,
@@ -137,8 +135,8 @@ static __device__ __forceinline__ void gr_voxel_mean(int v, int M, const int* __
                                                      float* __restrict__ mean, Row row) {
   const int a = sc_clamp(vstart[v], 0, M), b = sc_clamp(vstart[v + 1], a, M);
   float tot[3] = {0.0f, 0.0f, 0.0f};
-  for (int t0 = a; t0 < b; t0 += SG_TILE) {
-    const int t1 = t0 + SG_TILE < b ? t0 + SG_TILE : b;
+  for (int t0 = a; t0 < b; t0 += R3D_SCENE_SEG_TILE) {
+    const int t1 = t0 + R3D_SCENE_SEG_TILE < b ? t0 + R3D_SCENE_SEG_TILE : b;
     float part[3] = {0.0f, 0.0f, 0.0f};
     for (int i = t0; i < t1; ++i) {
       float c[3];
@@ -404,11 +402,11 @@ static int gr_union(const char* name, long M, int nx, int ny, int nz, long n_vox
   if (voxel_normal)
     hipLaunchKernelGGL(r3d_scene_grow_union_kernel<true>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
                        ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
-                       ws + L.rec + GR_R_ERROR);
+                       ws + L.rec + R3D_GROW_R_ERROR);
   else
     hipLaunchKernelGGL(r3d_scene_grow_union_kernel<false>, dim3(gv), dim3(SC_THREADS), 0, st, V, nx, ny, nz, connectivity,
                        ws + L.vkey, colour ? 1 : 0, colour_tol, voxel_mean, voxel_normal, cos2, ws + L.parent,
-                       ws + L.rec + GR_R_ERROR);
+                       ws + L.rec + R3D_GROW_R_ERROR);
   R3D_LAUNCH_CHECK(name);
   return R3D_OK;
 }
@@ -472,22 +470,22 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_kept_kernel(int V, 
   const bool is_root = v < V && root[v] == v;
   if (v <= V) kept[v] = is_root && cnt[v] >= min_points;
   const int n = sc_block_count(is_root ? 1 : 0, red);
-  if (threadIdx.x == 0 && n > 0) atomicAdd(rec + GR_R_NCOMP, n);
+  if (threadIdx.x == 0 && n > 0) atomicAdd(rec + R3D_GROW_R_NCOMP, n);
 }
 
 void gr_launch_components(long M, int V, int min_points, int32_t* ws, const gr_layout& L, hipStream_t st) {
   const int gv = sc_grid_of(V), gv1 = sc_grid_of(V + 1);
   int* rec = ws + L.rec;
-  r3d_zero_words(rec + GR_R_NCOMP, 2, st);
+  r3d_zero_words(rec + R3D_GROW_R_NCOMP, 2, st);
   r3d_zero_words(ws + L.cnt, V, st);
   hipLaunchKernelGGL(r3d_scene_grow_flatten_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.parent, ws + L.root,
-                     rec + GR_R_ERROR);
+                     rec + R3D_GROW_R_ERROR);
   hipLaunchKernelGGL(r3d_scene_grow_count_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, (int)M, ws + L.root, ws + L.vstart,
                      ws + L.cnt);
   hipLaunchKernelGGL(r3d_scene_grow_kept_kernel, dim3(gv1), dim3(SC_THREADS), 0, st, V, min_points, ws + L.root, ws + L.cnt,
                      ws + L.kept, rec);
   sc_excl_scan(ws + L.kept, V + 1L, ws + L.sort.part, st);
-  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, ws + L.kept + V, rec + GR_R_S);
+  hipLaunchKernelGGL(r3d_scene_grow_word_kernel, dim3(1), dim3(1), 0, st, ws + L.kept + V, rec + R3D_GROW_R_S);
 }
 
 extern "C" int r3d_scene_grow_components(long M, long n_voxels, int min_points, int32_t* ws, long ws_words, void* stream) {
@@ -574,8 +572,8 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_absorb_end_kernel(i
   gr_add_points(live, r, n, cnt);
   const int voxels = sc_block_count(live ? 1 : 0, red), points = sc_block_count(n, red);
   if (threadIdx.x == 0 && voxels > 0) {
-    atomicAdd(rec + GR_R_ABSORBED_VOXELS, voxels);  // integer counts: order-independent
-    atomicAdd(rec + GR_R_ABSORBED_POINTS, points);
+    atomicAdd(rec + R3D_GROW_R_ABSORBED_VOXELS, voxels);  // integer counts: order-independent
+    atomicAdd(rec + R3D_GROW_R_ABSORBED_POINTS, points);
   }
 }
 
@@ -585,14 +583,14 @@ extern "C" int r3d_scene_grow_absorb(long M, int nx, int ny, int nz, long n_voxe
   SC_TRY(gr_check("r3d_scene_grow_absorb", M, nx, ny, nz, ws, ws_words));
   SC_TRY(gr_check_rows("r3d_scene_grow_absorb", M, n_voxels, "voxels"));
   SC_TRY(gr_check_connectivity("r3d_scene_grow_absorb", connectivity));
-  R3D_REQUIRE(rings >= 1 && rings <= GR_RINGS_MAX, "r3d_scene_grow_absorb: %d rings (1 .. %d)", rings, GR_RINGS_MAX);
+  R3D_REQUIRE(rings >= 1 && rings <= R3D_SCENE_GROW_RINGS, "r3d_scene_grow_absorb: %d rings (1 .. %d)", rings, R3D_SCENE_GROW_RINGS);
   const hipStream_t st = (hipStream_t)stream;
   const gr_layout L = gr_make_layout(M);
   const int sorted = sc_passes((long)nx * ny * nz) & 1;
   const int V = (int)n_voxels, gv = sc_grid_of(V);
   int* owner[2] = {ws + L.sort.idx[sorted ^ 1], ws + L.parent};  // M + 1 and V words: both hold V
   int* rec = ws + L.rec;
-  r3d_zero_words(rec + GR_R_ABSORBED_VOXELS, 2, st);
+  r3d_zero_words(rec + R3D_GROW_R_ABSORBED_VOXELS, 2, st);
   hipLaunchKernelGGL(r3d_scene_grow_absorb_start_kernel, dim3(gv), dim3(SC_THREADS), 0, st, V, ws + L.root, ws + L.kept, owner[0],
                      voxel_ring);
   for (int r = 1; r <= rings; ++r)
@@ -629,12 +627,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_grow_spread_kernel(int M
     segments[p] = s;
   }
   n_drop = sc_block_count(n_drop, red);
-  if (threadIdx.x == 0 && n_drop > 0) atomicAdd(rec + GR_R_NDROPPED, n_drop);  // an integer count: order-independent
+  if (threadIdx.x == 0 && n_drop > 0) atomicAdd(rec + R3D_GROW_R_NDROPPED, n_drop);  // an integer count: order-independent
 }
 
 void gr_launch_ids(long M, int V, int S, const int32_t* voxel_index, int32_t* segments, int32_t* segment_points, int32_t* ws,
                    const gr_layout& L, hipStream_t st) {
-  r3d_zero_words(ws + L.rec + GR_R_NDROPPED, 1, st);
+  r3d_zero_words(ws + L.rec + R3D_GROW_R_NDROPPED, 1, st);
   if (S > 0 && segment_points)
     hipLaunchKernelGGL(r3d_scene_grow_sizes_kernel, dim3(sc_grid_of(V)), dim3(SC_THREADS), 0, st, V, S, ws + L.kept, ws + L.cnt,
                        segment_points);

@@ -13,21 +13,11 @@
 // atomic, whose result does not depend on the order: no float goes through an atomic.
 #include "scene_common.h"
 
-#define MT_REC 32        // words of the record, ws[0 .. 32)
-#define MT_R_MAX1 0      // + column (0 pred, 1 truth): largest legal id of a participating point + 1, 0 without one
-#define MT_R_NNEG 2      // + column: participating points with a negative id
-#define MT_R_NIGN 4      // points M1 takes out
-#define MT_R_NBAD 5      // ids >= 2^31 - 1, both columns
-#define MT_R_BADMAX 6    // the largest of them (two words)
-#define MT_R_ROWS 8      // + column: P, T
-#define MT_R_MIXED 10    // + column: rows in which some point carries another label than the first
-#define MT_R_NBOTH 12    // points with a row in both columns
-#define MT_R_NPAIRS 13
 #define MT_ID_LIMIT 2147483647LL
-#define MT_MAX_IOU 8
+static_assert(R3D_MATCH_R_NPAIRS < R3D_SCENE_MATCH_REC, "a word beyond the record");
 
 struct mt_layout {
-  long rec;
+  long rec;            // R3D_SCENE_MATCH_REC words, R3D_MATCH_R_* (r3d.h; `+ column`: 0 pred, 1 truth)
   sc_sort_ws sort;     // pairs of M + 1 words; the pair a sort leaves free holds the head scan and the mixed flags
   long row_start[2];   // R + 1: first sorted position of a row
   long row_id[2];      // R
@@ -41,7 +31,7 @@ static mt_layout mt_make_layout(long M) {
   mt_layout L;
   const long Ma = sc_align(M + 1);
   long o = 0;
-  L.rec = o; o += MT_REC;
+  L.rec = o; o += R3D_SCENE_MATCH_REC;
   o = sc_sort_ws_append(L.sort, o, M, Ma, sc_sort_part_words(M, M + 1));
   for (int c = 0; c < 2; ++c) {
     L.row_start[c] = o; o += Ma;
@@ -55,7 +45,7 @@ static mt_layout mt_make_layout(long M) {
   return L;
 }
 
-extern "C" long r3d_scene_match_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? mt_make_layout(M).total : -1; }
+extern "C" long r3d_scene_match_ws_words(long M) { return M > 0 && M <= R3D_SCENE_MAX_POINTS ? mt_make_layout(M).total : -1; }
 
 // what every entry point has: the scan's size and the workspace
 static int mt_check(const char* name, long M, long ws_words) {
@@ -130,14 +120,14 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_ids_kernel(const v
   n_ign = sc_block_count(n_ign, red);
   n_bad = sc_block_count(n_bad, red);
   if (threadIdx.x == 0) {  // integer maxima and counts: order-independent
-    if (m0 > 0) atomicMax(&rec[MT_R_MAX1], (int)m0);
-    if (m1 > 0) atomicMax(&rec[MT_R_MAX1 + 1], (int)m1);
-    if (nn0 > 0) atomicAdd(&rec[MT_R_NNEG], nn0);
-    if (nn1 > 0) atomicAdd(&rec[MT_R_NNEG + 1], nn1);
-    if (n_ign > 0) atomicAdd(&rec[MT_R_NIGN], n_ign);
+    if (m0 > 0) atomicMax(&rec[R3D_MATCH_R_MAX1], (int)m0);
+    if (m1 > 0) atomicMax(&rec[R3D_MATCH_R_MAX1 + 1], (int)m1);
+    if (nn0 > 0) atomicAdd(&rec[R3D_MATCH_R_NNEG], nn0);
+    if (nn1 > 0) atomicAdd(&rec[R3D_MATCH_R_NNEG + 1], nn1);
+    if (n_ign > 0) atomicAdd(&rec[R3D_MATCH_R_NIGNORED], n_ign);
     if (n_bad > 0) {
-      atomicAdd(&rec[MT_R_NBAD], n_bad);
-      atomicMax((unsigned long long*)(rec + MT_R_BADMAX), bmax);
+      atomicAdd(&rec[R3D_MATCH_R_NBAD], n_bad);
+      atomicMax((unsigned long long*)(rec + R3D_MATCH_R_BADMAX), bmax);
     }
   }
 }
@@ -150,7 +140,7 @@ extern "C" int r3d_scene_match_ids(const void* pred, int pred_bytes, const void*
   SC_TRY(mt_check_bytes("r3d_scene_match_ids", "truth", truth_bytes));
   const hipStream_t st = (hipStream_t)stream;
   const mt_layout L = mt_make_layout(M);
-  r3d_zero_words(ws + L.rec, MT_REC, st);
+  r3d_zero_words(ws + L.rec, R3D_SCENE_MATCH_REC, st);
   hipLaunchKernelGGL(r3d_scene_match_ids_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, pred, pred_bytes, truth,
                      truth_bytes, (int)M, ignore_unannotated ? 1 : 0, ws + L.rec);
   R3D_LAUNCH_CHECK("r3d_scene_match_ids");
@@ -249,12 +239,12 @@ static void mt_rows_of(int c, const void* ids, int bytes, const void* gate, int 
   hipLaunchKernelGGL(r3d_scene_match_row_flags_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, skey, (int)M, none, heads, mixed);
   sc_excl_scan(heads, M + 1, ws + L.sort.part, st);
   hipLaunchKernelGGL(r3d_scene_match_row_tables_kernel, dim3(gm1), dim3(SC_THREADS), 0, st, skey, order, (int)M, (int)n_in, heads,
-                     ws + L.row_start[c], ws + L.row_id[c], ws + L.row_head[c], index, ws + L.rec + MT_R_ROWS + c);
+                     ws + L.row_start[c], ws + L.row_id[c], ws + L.row_head[c], index, ws + L.rec + R3D_MATCH_R_ROWS + c);
   if (labels) {
     hipLaunchKernelGGL(r3d_scene_match_row_mixed_kernel, dim3(gm), dim3(SC_THREADS), 0, st, order, (int)M, (int)n_in, heads,
                        ws + L.row_head[c], labels, label_bytes, mixed);
     hipLaunchKernelGGL(r3d_scene_match_row_mixed_count_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, heads, (int)M, mixed,
-                       ws + L.rec + MT_R_MIXED + c);
+                       ws + L.rec + R3D_MATCH_R_MIXED + c);
   }
 }
 
@@ -334,7 +324,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_pair_flags_kernel(
   if (i > M) return;
   if (i == M) {
     heads[M] = 0;
-    if (skey[0] < 0 || skey[0] >= P) rec[MT_R_NBOTH] = 0;
+    if (skey[0] < 0 || skey[0] >= P) rec[R3D_MATCH_R_NBOTH] = 0;
     return;
   }
   const int k = skey[i];
@@ -342,7 +332,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_pair_flags_kernel(
   if (k >= 0 && k < P) {
     const int t = truth_index[sc_clamp(order[i], 0, M - 1)];
     h = i == 0 || skey[i - 1] != k || truth_index[sc_clamp(order[i - 1], 0, M - 1)] != t;
-    if (i == M - 1 || skey[i + 1] < 0 || skey[i + 1] >= P) rec[MT_R_NBOTH] = i + 1;  // one writer: the prefix's last position
+    if (i == M - 1 || skey[i + 1] < 0 || skey[i + 1] >= P) rec[R3D_MATCH_R_NBOTH] = i + 1;  // one writer: the prefix's last position
   }
   heads[i] = h;
 }
@@ -357,8 +347,8 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_pair_tables_kernel
   if (i > M) return;
   if (i == M) {
     const int K = sc_clamp(heads[M], 0, M);
-    pair_start[K] = rec[MT_R_NBOTH];  // (written by the launch before)
-    rec[MT_R_NPAIRS] = K;
+    pair_start[K] = rec[R3D_MATCH_R_NBOTH];  // (written by the launch before)
+    rec[R3D_MATCH_R_NPAIRS] = K;
     return;
   }
   if (heads[i + 1] != heads[i]) {
@@ -505,7 +495,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_best_rows_kernel(i
 }
 
 struct mt_thresholds {
-  float v[MT_MAX_IOU];
+  float v[R3D_SCENE_MATCH_IOU];
 };
 
 // M7, written last: over eligible[]
@@ -522,7 +512,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_match_pair_match_kernel(
   if (pred_best[p] == k && truth_best[t] == k) {
     const float iou = pair_iou[k];
 #pragma unroll
-    for (int j = 0; j < MT_MAX_IOU; ++j) m += j < n_iou && iou >= th.v[j];
+    for (int j = 0; j < R3D_SCENE_MATCH_IOU; ++j) m += j < n_iou && iou >= th.v[j];
   }
   pair_match[k] = (unsigned char)m;
 }
@@ -539,14 +529,14 @@ extern "C" int r3d_scene_match_best(long M, long n_pred, long n_truth, long n_pa
   SC_TRY(mt_check("r3d_scene_match_best", M, ws_words));
   R3D_REQUIRE(n_pred >= 1 && n_pred <= M && n_truth >= 1 && n_truth <= M && n_pairs >= 0 && n_pairs <= M,
               "r3d_scene_match_best: %ld and %ld rows, %ld pairs of %ld points", n_pred, n_truth, n_pairs, M);
-  R3D_REQUIRE(n_iou >= 1 && n_iou <= MT_MAX_IOU, "r3d_scene_match_best: %d thresholds (1 .. %d)", n_iou, MT_MAX_IOU);
+  R3D_REQUIRE(n_iou >= 1 && n_iou <= R3D_SCENE_MATCH_IOU, "r3d_scene_match_best: %d thresholds (1 .. %d)", n_iou, R3D_SCENE_MATCH_IOU);
   R3D_REQUIRE((pred_classes != nullptr) == (truth_classes != nullptr), "r3d_scene_match_best: classes for one column only "
               "(pred_classes %p, truth_classes %p)", (const void*)pred_classes, (const void*)truth_classes);
   R3D_REQUIRE(n_pairs == 0 || (pair_pred && pair_truth && pair_points && pair_iou && pair_match),
               "r3d_scene_match_best: null pointer (pair_pred %p, pair_truth %p, pair_points %p, pair_iou %p, pair_match %p)",
               (void*)pair_pred, (void*)pair_truth, (void*)pair_points, (void*)pair_iou, (void*)pair_match);
   mt_thresholds th;
-  for (int j = 0; j < MT_MAX_IOU; ++j) th.v[j] = j < n_iou ? thresholds[j] : 2.0f;  // thresholds: host memory
+  for (int j = 0; j < R3D_SCENE_MATCH_IOU; ++j) th.v[j] = j < n_iou ? thresholds[j] : 2.0f;  // thresholds: host memory
   for (int j = 0; j < n_iou; ++j)
     R3D_REQUIRE(th.v[j] > 0.0f && th.v[j] <= 1.0f && (j == 0 || th.v[j] >= th.v[j - 1]),
                 "r3d_scene_match_best: threshold %d is %g (ascending, each in (0, 1])", j, (double)th.v[j]);

@@ -20,21 +20,15 @@
 // centroid's sums are 64-bit integers.  The same scan and labels give the same bits.
 #include "scene_components.h"
 
-#define OB_IGNORE_MAX 64            // entries of the ignore table
-#define OB_LABEL_MAX 2147483646L    // n_labels = label + 1 fits an int
-#define OB_KEY_MAX 2147483647L      // n_labels * n_cells: the key of a point that takes no part
 #define OB_SUB 256                  // sub-voxel steps per cell (O8)
-// the record: the words of build_segments (GR_R_*), 12 and 13 reused, 14 and 15 new
-#define OB_R_NLABELS 12      // the largest participating label, plus one
-#define OB_R_NUNLABELLED 13  // finite points left out by their label (negative or ignored)
-#define OB_R_NOVER 14        // finite points whose label is above OB_LABEL_MAX and not ignored
-#define OB_R_NPOINTS 15      // participating points
+// the record: the words of build_segments (R3D_GROW_R_*), the two of absorb reused (R3D_OBJ_R_*, r3d.h)
+static_assert(R3D_OBJ_R_NPOINTS < R3D_SCENE_GROW_REC, "a word beyond the record");
 
-extern "C" long r3d_scene_obj_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? gr_make_layout(M).total : -1; }
+extern "C" long r3d_scene_obj_ws_words(long M) { return M > 0 && M <= R3D_SCENE_MAX_POINTS ? gr_make_layout(M).total : -1; }
 
 static int ob_check(const char* name, long M, int nx, int ny, int nz, long n_labels, const int32_t* ws, long ws_words) {
   SC_TRY(gr_check_grid(name, M, nx, ny, nz, "cells", ws));
-  R3D_REQUIRE(n_labels >= 1 && n_labels * ((long)nx * ny * nz) <= OB_KEY_MAX, "%s: %ld labels times %ld cells (at most 2^31 - 1)",
+  R3D_REQUIRE(n_labels >= 1 && n_labels * ((long)nx * ny * nz) <= R3D_SCENE_OBJ_KEY, "%s: %ld labels times %ld cells (at most 2^31 - 1)",
               name, n_labels, (long)nx * ny * nz);
   return sc_check_ws(name, ws_words, r3d_scene_obj_ws_words(M));
 }
@@ -42,8 +36,8 @@ static int ob_check(const char* name, long M, int nx, int ny, int nz, long n_lab
 static int ob_check_labels(const char* name, const void* labels, int labels64, const int64_t* ignore, int n_ignore) {
   R3D_REQUIRE(labels, "%s: null pointer (labels)", name);
   R3D_REQUIRE(labels64 == 0 || labels64 == 1, "%s: labels64 %d (0: int32, 1: int64)", name, labels64);
-  R3D_REQUIRE(n_ignore >= 0 && n_ignore <= OB_IGNORE_MAX && (n_ignore == 0 || ignore), "%s: %d ignored classes at %p (0 .. %d)",
-              name, n_ignore, (const void*)ignore, OB_IGNORE_MAX);
+  R3D_REQUIRE(n_ignore >= 0 && n_ignore <= R3D_SCENE_OBJ_IGNORE && (n_ignore == 0 || ignore), "%s: %d ignored classes at %p (0 .. %d)",
+              name, n_ignore, (const void*)ignore, R3D_SCENE_OBJ_IGNORE);
   return R3D_OK;
 }
 
@@ -56,7 +50,7 @@ static __device__ __forceinline__ int ob_class(const T* __restrict__ labels, int
   if (l < 0) return -1;
   for (int j = 0; j < n_ignore; ++j)
     if (ignore[j] == l) return -1;
-  return l > OB_LABEL_MAX ? -2 : (int)l;
+  return l > R3D_SCENE_OBJ_LABEL ? -2 : (int)l;
 }
 
 // ---- bounds: r3d_scene_grow_bounds' launches, then the labels of the finite points into words 12 .. 15
@@ -86,15 +80,15 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_obj_labels_kernel(const 
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int w = 1; w < SC_WAVES; ++w) top = red[w] > top ? red[w] : top;
-    if (top > 0) atomicMax(rec + OB_R_NLABELS, top);  // integer maxima and counts: order-independent
+    if (top > 0) atomicMax(rec + R3D_OBJ_R_NLABELS, top);  // integer maxima and counts: order-independent
   }
   n_out = sc_block_count(n_out, red);
   n_over = sc_block_count(n_over, red);
   n_in = sc_block_count(n_in, red);
   if (threadIdx.x == 0) {
-    if (n_out > 0) atomicAdd(rec + OB_R_NUNLABELLED, n_out);
-    if (n_over > 0) atomicAdd(rec + OB_R_NOVER, n_over);
-    if (n_in > 0) atomicAdd(rec + OB_R_NPOINTS, n_in);
+    if (n_out > 0) atomicAdd(rec + R3D_OBJ_R_NUNLABELLED, n_out);
+    if (n_over > 0) atomicAdd(rec + R3D_OBJ_R_NOVER, n_over);
+    if (n_in > 0) atomicAdd(rec + R3D_OBJ_R_NPOINTS, n_in);
   }
 }
 
@@ -194,7 +188,7 @@ extern "C" int r3d_scene_obj_union(long M, int nx, int ny, int nz, int n_labels,
   const int U = (int)n_units;
   gr_launch_init(U, ws, L, st);
   hipLaunchKernelGGL(r3d_scene_obj_union_kernel, dim3(sc_grid_of(U)), dim3(SC_THREADS), 0, st, U, nx, ny, nz, connectivity,
-                     ws + L.vkey, ws + L.parent, ws + L.rec + GR_R_ERROR);
+                     ws + L.vkey, ws + L.parent, ws + L.rec + R3D_GROW_R_ERROR);
   R3D_LAUNCH_CHECK("r3d_scene_obj_union");
   return R3D_OK;
 }

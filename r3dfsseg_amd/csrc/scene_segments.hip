@@ -11,24 +11,14 @@
 // Floats are added by __fadd_rn in the stated order and divided by __fdiv_rn; counts are integer scans and integer atomics.
 #include "scene_common.h"
 
-// a tile: SG_TILE contributor ranks
+// a tile: R3D_SCENE_SEG_TILE contributor ranks
 #define SG_BATCH 32    // rows of a tile staged in LDS at a time: 32 * 64 floats per wave, 32 KiB per workgroup
 #define SG_UNROLL 8    // element loads of a lane in flight while a batch is staged; partials loaded ahead of their additions
-// the record, words of ws[0 .. 16)
-#define SG_R_MAX1 0      // largest legal id + 1, 0 without one
-#define SG_R_NNEG 1      // points with a negative id
-#define SG_R_NBAD 2      // ids >= 2^31 - 1
-#define SG_R_BADMAX 4    // the largest of them (two words)
-#define SG_R_S 6         // segments
-#define SG_R_NCONTRIB 7  // contributors
-#define SG_R_NTILES 8    // tiles
-#define SG_R_NPOOLED 9
-#define SG_R_NFILLED 10
-#define SG_R_NUNLAB 11
 #define SG_ID_LIMIT 2147483647LL
+static_assert(R3D_SEG_R_BADMAX + 2 <= R3D_SCENE_SEG_REC && R3D_SEG_R_NUNLAB < R3D_SCENE_SEG_REC, "a word beyond the record");
 
 struct sg_layout {
-  long rec;              // 16
+  long rec;              // R3D_SCENE_SEG_REC words, R3D_SEG_R_* (r3d.h)
   sc_sort_ws sort;       // pairs of M + 1 words; the pair the sort leaves free holds the two scans, part their partials too
   long tiles;            // M + 1: tile heads in front of a sorted position
   long clist;            // contributors' scan indices, segment after segment, ascending scan index inside one
@@ -43,7 +33,7 @@ static sg_layout sg_make_layout(long M) {
   sg_layout L;
   const long Ma = sc_align(M + 1);
   long o = 0;
-  L.rec = o; o += 16;
+  L.rec = o; o += R3D_SCENE_SEG_REC;
   o = sc_sort_ws_append(L.sort, o, M, Ma, sc_sort_part_words(M, M + 1));
   L.tiles = o; o += Ma;
   L.clist = o; o += Ma;
@@ -55,7 +45,7 @@ static sg_layout sg_make_layout(long M) {
   return L;
 }
 
-extern "C" long r3d_scene_seg_ws_words(long M) { return M > 0 && M <= SC_MAX_POINTS ? sg_make_layout(M).total : -1; }
+extern "C" long r3d_scene_seg_ws_words(long M) { return M > 0 && M <= R3D_SCENE_MAX_POINTS ? sg_make_layout(M).total : -1; }
 
 // what every entry point has: the scan's size and the workspace
 static int sg_check(const char* name, long M, long ws_words) {
@@ -102,11 +92,11 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_ids_kernel(const L* 
   n_neg = sc_block_count(n_neg, red);
   n_bad = sc_block_count(n_bad, red);
   if (threadIdx.x == 0) {  // integer maxima and counts: order-independent
-    if (mx > 0) atomicMax(&rec[SG_R_MAX1], mx);
-    if (n_neg > 0) atomicAdd(&rec[SG_R_NNEG], n_neg);
+    if (mx > 0) atomicMax(&rec[R3D_SEG_R_MAX1], mx);
+    if (n_neg > 0) atomicAdd(&rec[R3D_SEG_R_NNEG], n_neg);
     if (n_bad > 0) {
-      atomicAdd(&rec[SG_R_NBAD], n_bad);
-      atomicMax((unsigned long long*)(rec + SG_R_BADMAX), bmax);
+      atomicAdd(&rec[R3D_SEG_R_NBAD], n_bad);
+      atomicMax((unsigned long long*)(rec + R3D_SEG_R_BADMAX), bmax);
     }
   }
 }
@@ -118,7 +108,7 @@ extern "C" int r3d_scene_seg_ids(const void* segments, int seg_bytes, long M, in
   const hipStream_t st = (hipStream_t)stream;
   const sg_layout L = sg_make_layout(M);
   const int gm = sc_count_grid(M);
-  r3d_zero_words(ws + L.rec, 16, st);
+  r3d_zero_words(ws + L.rec, R3D_SCENE_SEG_REC, st);
   if (seg_bytes == 8)
     hipLaunchKernelGGL(r3d_scene_seg_ids_kernel<long long>, dim3(gm), dim3(SC_THREADS), 0, st, (const long long*)segments, (int)M,
                        ws + L.rec);
@@ -184,7 +174,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_tables_kernel(
   if (contrib[i + 1] != c) clist[c] = p;
 }
 
-// tile heads: the contributors whose rank inside their segment is a multiple of SG_TILE
+// tile heads: the contributors whose rank inside their segment is a multiple of R3D_SCENE_SEG_TILE
 __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_tile_flags_kernel(int M, int n_in_seg, const int* __restrict__ heads,
                                                                               const int* __restrict__ contrib,
                                                                               const int* __restrict__ cstart,
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_tile_flags_kernel(in
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
   if (i > M) return;
   int f = 0;
-  if (i < n_in_seg && contrib[i + 1] != contrib[i]) f = ((contrib[i] - cstart[heads[i + 1] - 1]) % SG_TILE) == 0;
+  if (i < n_in_seg && contrib[i + 1] != contrib[i]) f = ((contrib[i] - cstart[heads[i + 1] - 1]) % R3D_SCENE_SEG_TILE) == 0;
   tiles[i] = f;
 }
 
@@ -203,9 +193,9 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_tile_table_kernel(in
   const int i = blockIdx.x * SC_THREADS + threadIdx.x;
   if (i > M) return;
   if (i == M) {
-    rec[SG_R_S] = heads[M];
-    rec[SG_R_NCONTRIB] = contrib[M];
-    rec[SG_R_NTILES] = tiles[M];
+    rec[R3D_SEG_R_S] = heads[M];
+    rec[R3D_SEG_R_NCONTRIB] = contrib[M];
+    rec[R3D_SEG_R_NTILES] = tiles[M];
     return;
   }
   if (i < n_in_seg && tiles[i + 1] != tiles[i]) tile_seg[tiles[i]] = heads[i + 1] - 1;
@@ -259,37 +249,37 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_pool_tiles_kernel(
     const int* __restrict__ cstart, const int* __restrict__ seg_start, const int* __restrict__ tiles,
     const int* __restrict__ tile_seg, float* __restrict__ part) {
   __shared__ float stage[SC_WAVES][SG_BATCH * 64];
-  __shared__ int row_p[SC_WAVES][SG_TILE];    // the tile's rows: scan index
-  __shared__ float row_v[SC_WAVES][SG_TILE];  // and votes as a float
+  __shared__ int row_p[SC_WAVES][R3D_SCENE_SEG_TILE];    // the tile's rows: scan index
+  __shared__ float row_v[SC_WAVES][R3D_SCENE_SEG_TILE];  // and votes as a float
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int t = blockIdx.x * SC_WAVES + w;
   int first = 0, n = 0;
   if (t < n_tiles) {
     int s = tile_seg[t];
     s = s < 0 ? 0 : (s >= M ? M - 1 : s);
-    first = cstart[s] + SG_TILE * (t - tiles[sc_clamp(seg_start[s], 0, M)]);
+    first = cstart[s] + R3D_SCENE_SEG_TILE * (t - tiles[sc_clamp(seg_start[s], 0, M)]);
     n = cstart[s + 1] - first;
-    n = n > SG_TILE ? SG_TILE : n;
+    n = n > R3D_SCENE_SEG_TILE ? R3D_SCENE_SEG_TILE : n;
     // the tables come from counts of these very points, so the rows lie inside clist; the guard only matters for a
     // workspace that r3d_scene_seg_group did not fill
     if (first < 0 || n < 0 || (long)first + n > M) first = n = 0;
   }
   // the tile's scan indices and votes first, four independent loads a lane: the element loads below then depend on LDS
   // only and go out eight at a time (one load per element, each waiting for its index, took ten times as long)
-  int pr[SG_TILE / R3D_WAVE];
+  int pr[R3D_SCENE_SEG_TILE / R3D_WAVE];
 #pragma unroll
-  for (int k = 0; k < SG_TILE / R3D_WAVE; ++k) {
+  for (int k = 0; k < R3D_SCENE_SEG_TILE / R3D_WAVE; ++k) {
     const int r = k * R3D_WAVE + lane;
     pr[k] = sc_clamp(clist[first + (r < n ? r : 0)], 0, M - 1);
   }
 #pragma unroll
-  for (int k = 0; k < SG_TILE / R3D_WAVE; ++k) {
+  for (int k = 0; k < R3D_SCENE_SEG_TILE / R3D_WAVE; ++k) {
     row_p[w][k * R3D_WAVE + lane] = pr[k];
     row_v[w][k * R3D_WAVE + lane] = (float)votes[pr[k]];
   }
   __syncthreads();
   float acc = 0.0f;
-  for (int r0 = 0; r0 < SG_TILE; r0 += SG_BATCH) {
+  for (int r0 = 0; r0 < R3D_SCENE_SEG_TILE; r0 += SG_BATCH) {
     const int nb = n - r0 < SG_BATCH ? n - r0 : SG_BATCH;  // <= 0: nothing left
     const int n_el = nb * C;
     for (int e0 = lane; e0 < n_el + lane; e0 += SG_UNROLL * R3D_WAVE) {  // (uniform trip count)
@@ -365,7 +355,7 @@ extern "C" int r3d_scene_seg_pool(long M, int n_cols, const float* scores, const
   R3D_REQUIRE(scores && votes && ws, "r3d_scene_seg_pool: null pointer (scores %p, votes %p, ws %p)", (const void*)scores,
               (const void*)votes, (const void*)ws);
   SC_TRY(sg_check("r3d_scene_seg_pool", M, ws_words));
-  R3D_REQUIRE(n_cols >= 1 && n_cols <= 64, "r3d_scene_seg_pool: %d score columns (1 .. 64)", n_cols);
+  R3D_REQUIRE(n_cols >= 1 && n_cols <= R3D_SCENE_SCORE_COLS_MAX, "r3d_scene_seg_pool: %d score columns (1 .. 64)", n_cols);
   R3D_REQUIRE(n_segments >= 0 && n_segments <= M && n_tiles >= 0 && n_tiles <= M,
               "r3d_scene_seg_pool: %ld segments, %ld tiles of %ld points", n_segments, n_tiles, M);
   R3D_REQUIRE(n_segments == 0 || (seg_ids && seg_points && seg_members && seg_scores),
@@ -442,9 +432,9 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_seg_spread_kernel(
   n_fi = sc_block_count(n_fi, red);
   n_un = sc_block_count(n_un, red);
   if (threadIdx.x == 0) {  // integer counts: order-independent
-    if (n_pl > 0) atomicAdd(&rec[SG_R_NPOOLED], n_pl);
-    if (n_fi > 0) atomicAdd(&rec[SG_R_NFILLED], n_fi);
-    if (n_un > 0) atomicAdd(&rec[SG_R_NUNLAB], n_un);
+    if (n_pl > 0) atomicAdd(&rec[R3D_SEG_R_NPOOLED], n_pl);
+    if (n_fi > 0) atomicAdd(&rec[R3D_SEG_R_NFILLED], n_fi);
+    if (n_un > 0) atomicAdd(&rec[R3D_SEG_R_NUNLAB], n_un);
   }
 }
 
@@ -460,7 +450,7 @@ extern "C" int r3d_scene_seg_spread(long M, int n_cols, int n_sets, long n_segme
               "ws %p)", (const void*)segment_index, (const void*)in_scores, (const void*)in_labels, (void*)scores, (void*)labels,
               (void*)pooled, (void*)ws);
   SC_TRY(sg_check("r3d_scene_seg_spread", M, ws_words));
-  R3D_REQUIRE(n_cols >= 1 && n_cols <= 64, "r3d_scene_seg_spread: %d score columns (1 .. 64)", n_cols);
+  R3D_REQUIRE(n_cols >= 1 && n_cols <= R3D_SCENE_SCORE_COLS_MAX, "r3d_scene_seg_spread: %d score columns (1 .. 64)", n_cols);
   R3D_REQUIRE(n_sets >= 0 && n_sets <= 32 && (n_sets == 0 || n_cols % n_sets == 0),
               "r3d_scene_seg_spread: %d sets over %d score columns", n_sets, n_cols);
   R3D_REQUIRE(min_members >= 1, "r3d_scene_seg_spread: min_members %d (at least 1)", min_members);

@@ -15,23 +15,15 @@
 // atomic.  Counts are integer atomics, one per workgroup and word.
 #include "scene_components.h"
 
-#define SM_SLOTS 26       // neighbour slots of a voxel
 #define SM_CHUNK 9        // slots whose loads a lane of the sweep has in flight together
-#define SM_SWEEPS_MAX 64
-// the counts, words of counts[0 .. 8)
-#define SM_R_MEMBER_VOXELS 0  // voxels with a contributor
-#define SM_R_FILLED_VOXELS 1  // voxels without one that a sweep reached
-#define SM_R_NSMOOTHED 2      // points of a reached voxel
-#define SM_R_NCHANGED 3       // of them: the label in res was >= 0 and differs
-#define SM_R_NFILLED 4        // of them: the label in res was -1
-#define SM_R_NUNLAB 5         // labels that are -1 in the result
+static_assert(R3D_SMOOTH_R_NUNLAB < R3D_SCENE_SMOOTH_COUNTS, "a word beyond the counts");
 
 static int sm_check(const char* name, long M, long n_voxels, int n_cols, const int32_t* ws, long ws_words) {
   R3D_REQUIRE(ws, "%s: null pointer (ws)", name);
   SC_TRY(sc_check_points(name, M));
   SC_TRY(sc_check_ws(name, ws_words, gr_make_layout(M).total));
   SC_TRY(gr_check_rows(name, M, n_voxels, "voxels"));
-  R3D_REQUIRE(n_cols >= 1 && n_cols <= 64, "%s: %d score columns (1 .. 64)", name, n_cols);
+  R3D_REQUIRE(n_cols >= 1 && n_cols <= R3D_SCENE_SCORE_COLS_MAX, "%s: %d score columns (1 .. 64)", name, n_cols);
   return R3D_OK;
 }
 
@@ -57,15 +49,15 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_smooth_evidence_kernel(i
     const int w = votes[p];
     if (w <= 0) continue;
     const float c = __fdiv_rn(scores[(long)p * C + j], (float)w);
-    if (n % SG_TILE == 0) {  // a tile opens: the one before joins the total
-      if (n > 0) tot = n == SG_TILE ? part : __fadd_rn(tot, part);
+    if (n % R3D_SCENE_SEG_TILE == 0) {  // a tile opens: the one before joins the total
+      if (n > 0) tot = n == R3D_SCENE_SEG_TILE ? part : __fadd_rn(tot, part);
       part = c;
     } else {
       part = __fadd_rn(part, c);
     }
     ++n;
   }
-  if (n > 0) tot = n <= SG_TILE ? part : __fadd_rn(tot, part);
+  if (n > 0) tot = n <= R3D_SCENE_SEG_TILE ? part : __fadd_rn(tot, part);
   evidence[e] = n > 0 ? __fdiv_rn(tot, (float)n) : 0.0f;
   if (j == 0) {
     members[v] = n;
@@ -111,10 +103,10 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_smooth_graph_kernel(int 
       for (int j = 0; j < 3; ++j) alike = alike && fabsf(__fsub_rn(mv[j], mean[3L * row + j])) <= tol;
       if (!alike) return;
     }
-    if (k < SM_SLOTS) nbr[(long)k * V + v] = row;
+    if (k < R3D_SCENE_SMOOTH_SLOTS) nbr[(long)k * V + v] = row;
     ++k;
   });
-  for (; k < SM_SLOTS; ++k) nbr[(long)k * V + v] = -1;
+  for (; k < R3D_SCENE_SMOOTH_SLOTS; ++k) nbr[(long)k * V + v] = -1;
 }
 
 extern "C" int r3d_scene_smooth_graph(long M, int nx, int ny, int nz, long n_voxels, int connectivity, const float* voxel_mean,
@@ -149,12 +141,12 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_smooth_sweep_kernel(int 
   const int v = (int)(e / C), j = (int)(e - (long)v * C);
   float s = 0.0f;
   int n = 0;
-  for (int k0 = 0; k0 < SM_SLOTS; k0 += SM_CHUNK) {
+  for (int k0 = 0; k0 < R3D_SCENE_SMOOTH_SLOTS; k0 += SM_CHUNK) {
     int u[SM_CHUNK], ru[SM_CHUNK];
     float val[SM_CHUNK];
 #pragma unroll
     for (int i = 0; i < SM_CHUNK; ++i) {
-      const int x = k0 + i < SM_SLOTS ? nbr[(long)(k0 + i) * V + v] : -1;
+      const int x = k0 + i < R3D_SCENE_SMOOTH_SLOTS ? nbr[(long)(k0 + i) * V + v] : -1;
       u[i] = x < V ? x : -1;
     }
     if (u[0] < 0) break;  // the slots are packed: none behind the first empty one
@@ -190,9 +182,9 @@ extern "C" int r3d_scene_smooth_sweep(long M, long n_voxels, int n_cols, int ite
               (const void*)voxel_evidence, (const void*)voxel_neighbours, (void*)voxel_ring);
   SC_TRY(sc_check_points("r3d_scene_smooth_sweep", M));
   SC_TRY(gr_check_rows("r3d_scene_smooth_sweep", M, n_voxels, "voxels"));
-  R3D_REQUIRE(n_cols >= 1 && n_cols <= 64, "r3d_scene_smooth_sweep: %d score columns (1 .. 64)", n_cols);
-  R3D_REQUIRE(iterations >= 0 && iterations <= SM_SWEEPS_MAX, "r3d_scene_smooth_sweep: %d sweeps (0 .. %d)", iterations,
-              SM_SWEEPS_MAX);
+  R3D_REQUIRE(n_cols >= 1 && n_cols <= R3D_SCENE_SCORE_COLS_MAX, "r3d_scene_smooth_sweep: %d score columns (1 .. 64)", n_cols);
+  R3D_REQUIRE(iterations >= 0 && iterations <= R3D_SCENE_SMOOTH_SWEEPS, "r3d_scene_smooth_sweep: %d sweeps (0 .. %d)", iterations,
+              R3D_SCENE_SMOOTH_SWEEPS);
   R3D_REQUIRE(alpha >= 0.0f && alpha < 1.0f, "r3d_scene_smooth_sweep: alpha %g (0 <= alpha < 1)", (double)alpha);
   R3D_REQUIRE((iterations < 1 || z0) && (iterations < 2 || z1) && (!z0 || z0 != z1),
               "r3d_scene_smooth_sweep: %d sweeps need z0 %p and, from the second on, z1 %p, two arrays", iterations, (void*)z0,
@@ -225,8 +217,8 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_smooth_labels_kernel(int
   }
   const int n_member = sc_block_count(rv == 0 ? 1 : 0, red), n_filled = sc_block_count(rv > 0 ? 1 : 0, red);
   if (threadIdx.x == 0) {  // integer counts: order-independent
-    if (n_member > 0) atomicAdd(&counts[SM_R_MEMBER_VOXELS], n_member);
-    if (n_filled > 0) atomicAdd(&counts[SM_R_FILLED_VOXELS], n_filled);
+    if (n_member > 0) atomicAdd(&counts[R3D_SMOOTH_R_MEMBER_VOXELS], n_member);
+    if (n_filled > 0) atomicAdd(&counts[R3D_SMOOTH_R_FILLED_VOXELS], n_filled);
   }
 }
 
@@ -272,10 +264,10 @@ __global__ __launch_bounds__(SC_THREADS) void r3d_scene_smooth_spread_kernel(
   n_fi = sc_block_count(n_fi, red);
   n_un = sc_block_count(n_un, red);
   if (threadIdx.x == 0) {  // integer counts: order-independent
-    if (n_sm > 0) atomicAdd(&counts[SM_R_NSMOOTHED], n_sm);
-    if (n_ch > 0) atomicAdd(&counts[SM_R_NCHANGED], n_ch);
-    if (n_fi > 0) atomicAdd(&counts[SM_R_NFILLED], n_fi);
-    if (n_un > 0) atomicAdd(&counts[SM_R_NUNLAB], n_un);
+    if (n_sm > 0) atomicAdd(&counts[R3D_SMOOTH_R_NSMOOTHED], n_sm);
+    if (n_ch > 0) atomicAdd(&counts[R3D_SMOOTH_R_NCHANGED], n_ch);
+    if (n_fi > 0) atomicAdd(&counts[R3D_SMOOTH_R_NFILLED], n_fi);
+    if (n_un > 0) atomicAdd(&counts[R3D_SMOOTH_R_NUNLAB], n_un);
   }
 }
 
@@ -292,9 +284,9 @@ extern "C" int r3d_scene_smooth_spread(long M, int n_cols, long n_voxels, const 
               (void*)smoothed, (void*)counts);
   SC_TRY(sc_check_points("r3d_scene_smooth_spread", M));
   SC_TRY(gr_check_rows("r3d_scene_smooth_spread", M, n_voxels, "voxels"));
-  R3D_REQUIRE(n_cols >= 1 && n_cols <= 64, "r3d_scene_smooth_spread: %d score columns (1 .. 64)", n_cols);
+  R3D_REQUIRE(n_cols >= 1 && n_cols <= R3D_SCENE_SCORE_COLS_MAX, "r3d_scene_smooth_spread: %d score columns (1 .. 64)", n_cols);
   const hipStream_t st = (hipStream_t)stream;
-  r3d_zero_words(counts, 8, st);
+  r3d_zero_words(counts, R3D_SCENE_SMOOTH_COUNTS, st);
   hipLaunchKernelGGL(r3d_scene_smooth_labels_kernel, dim3(sc_grid_of(n_voxels)), dim3(SC_THREADS), 0, st, (int)n_voxels, n_cols,
                      voxel_scores, voxel_ring, (long long*)voxel_labels, counts);
   hipLaunchKernelGGL(r3d_scene_smooth_spread_kernel, dim3(sc_count_grid(M)), dim3(SC_THREADS), 0, st, (int)M, n_cols, (int)n_voxels,

@@ -43,7 +43,7 @@ def lp_backward(saved, gscale):
     N, D = model.n_points, model.feat_dim
     S = model.n_way * model.k_shot
     pl = E * hb.n_cap  # rows of one plane of label columns (ops.HeadBuffers: two planes for more than 3 ways)
-    G = ops.ce_grad(hb.Z, hb.n_proto_ptr(), 32, E, hb.n_cap, n_q * N, model.n_classes, labels, gscale)
+    G = ops.ce_grad(hb.Z, hb.n_proto_ptr(), ops.HD_WORDS, E, hb.n_cap, n_q * N, model.n_classes, labels, gscale)
     lam = torch.empty(pl, 4, device=dev, dtype=torch.float32)
     dnodes = torch.empty(pl, D, device=dev, dtype=torch.float32)
     budget = int(min(model.lp_max_iter, fwd_budget + max(4, fwd_budget // 4)))
@@ -53,7 +53,7 @@ def lp_backward(saved, gscale):
             stats = hb.stats_bwd if plane == 0 else torch.zeros(E, 2, device=dev, dtype=torch.int32)
             _lib.check(lib.r3d_label_propagate_bwd_batched(
                 E, _p(hb.nodes), hb.nodes.stride(0), D, hb.kp1, _p(hb.Z[plane * pl:]), _p(G[plane * pl:]),
-                _p(hb.n_nodes_ptr()), 32, hb.n_cap, float(model.sigma), 0.99, budget, float(model.lp_tol), _p(lam), _p(dn),
+                _p(hb.n_nodes_ptr()), ops.HD_WORDS, hb.n_cap, float(model.sigma), 0.99, budget, float(model.lp_tol), _p(lam), _p(dn),
                 D, _p(hb.lp_ws), hb.lp_words, hb.lp_stride, _p(stats), 2, _st()))
             if plane:
                 dnodes.add_(dn)
@@ -65,7 +65,7 @@ def lp_backward(saved, gscale):
     dfeat.view(E, (S + n_q) * N, D)[:, :S * N].zero_()
     dsfeat, dqfeat = dfeat, dfeat[S * N:]
     _lib.check(lib.r3d_head_prototypes_bwd_batched(E, _p(dnodes), D, hb.n_cap, model.n_way, model.k_shot, N, D, n_q * N,
-                                                   _p(hb.desc), 32, _p(hb.assign), 2 * S * N, _p(hb.cluster_count), hb.n_cap,
+                                                   _p(hb.desc), ops.HD_WORDS, _p(hb.assign), 2 * S * N, _p(hb.cluster_count), hb.n_cap,
                                                    _p(hb.proto_ws), hb.proto_stride, _p(dsfeat), D, ep_rows, _p(dqfeat), D,
                                                    ep_rows, _st()))
     return dfeat

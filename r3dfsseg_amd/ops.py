@@ -9,17 +9,10 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
-SCORE_DGCNN, SCORE_L2 = 0, 1
-HD_SEG_COUNT, HD_SEG_M, HD_SEG_POFF, HD_N_PROTO, HD_N_NODES, HD_FPS_TIMEOUT = 0, 8, 16, 24, 25, 26
-HEAD_FPS_ONE_LAUNCH = 1
-# r3d_debug_knn_path: fields of the bit mask (include/r3d.h) and the values of the two enumerated ones
-KNN_PATH_MASK, KNN_PATH_FEW, KNN_PATH_SPLIT, KNN_PATH_BFA, KNN_PATH_FILTER = 0x3, 0x4, 0x8, 0x10, 0x20
-KNN_PATH_CHAN_SHIFT, KNN_PATH_CHAN_MASK, KNN_PATH_REGS_SHIFT, KNN_PATH_REGS_MASK = 6, 0xC0, 8, 0x300
-KNN_PATH_SMALL, KNN_PATH_LARGE, KNN_PATH_INSERTION = 0, 1, 2
-KNN_CHAN_ANY, KNN_CHAN_LE16, KNN_CHAN_FULL = 0 << 6, 1 << 6, 2 << 6
-KNN_REGS_1, KNN_REGS_2, KNN_REGS_4 = 1 << 8, 2 << 8, 3 << 8
-KNN_FLAG_STATUS, KNN_FLAG_X_CM, KNN_FLAG_NO_X, KNN_FLAG_FIXED_SCRATCH = 1, 2, 4, 8
+# Every number of the C ABI -- record words (GROW_R_V, HD_N_PROTO, ...), sizes, flag and enum values (ACT_LRELU, SCORE_L2,
+# KNN_PATH_FEW, ...), limits (SCENE_GROW_AXIS, ...) -- is a `#define R3D_<NAME>` of include/r3d.h, declared and explained
+# there next to its entry point, and is a name of this module without the prefix.  None is written here.
+globals().update({name[len("R3D_"):]: value for name, value in _lib.CONSTANTS.items()})
 
 
 def _p(t):
@@ -272,7 +265,7 @@ def attention(qkv, B, N, out, want_lse=False, group=0):
 class HeadBuffers:
     """Device buffers of the transductive heads of E episodes (capacity sized, no host sync).  Every array has a leading
     episode axis for every E, episode e's system lives at [e] (nodes / Y / Z: rows [e n_cap, (e + 1) n_cap)); the
-    single-episode head of the reference's schedule is E = 1: desc (1, 32), stats (1, 2), ..."""
+    single-episode head of the reference's schedule is E = 1: desc (1, HD_WORDS), stats (1, 2), ..."""
 
     def __init__(self, n_way, k_shot, N, n_q_pts, k_sub, k_connect, D, device, E=1):
         lib = _lib.load()
@@ -282,10 +275,10 @@ class HeadBuffers:
         # k_sub + 1 prototype slots per class: torch_cluster's float-rounded sample count gives k or k + 1 seeds
         # (csrc/head_proto.hip::hp_fps_count, models/mpti.py:612-613)
         self.n_cap = (n_way + 1) * (k_sub + 1) + n_q_pts
-        assert lib.r3d_head_desc_words() == 32
+        assert lib.r3d_head_desc_words() == HD_WORDS
         i32 = dict(device=device, dtype=torch.int32)
         f32 = dict(device=device, dtype=torch.float32)
-        self.desc = torch.zeros(E, 32, **i32)
+        self.desc = torch.zeros(E, HD_WORDS, **i32)
         self.nodes = torch.empty(E * self.n_cap, D, **f32)
         # label columns travel as float4 per node.  More than 3 ways (5..8 classes): TWO planes of 4 columns, plane 1
         # (classes 4..7) behind the E systems of plane 0 -- the label propagation is column-wise independent and solves
@@ -322,7 +315,7 @@ class HeadBuffers:
         return max(1, self.fps_slots // self.fps_blocks)
 
     def n_nodes_ptr(self):
-        return self.desc[0, HD_N_NODES:]   # episode e's count 32 words further on
+        return self.desc[0, HD_N_NODES:]   # episode e's count HD_WORDS words further on
 
     def n_proto_ptr(self):
         return self.desc[0, HD_N_PROTO:]
@@ -371,14 +364,14 @@ def head_prototypes(hb, support_y, shot_keep, sfeat_pm, qfeat_pm, feat_ep_rows=0
         _lib.check(_lib.load().r3d_head_prototypes_batched(
             E, hb.fps_group, _p(support_y), S * hb.N, _p(shot_keep), S, _p(sfeat_pm), ldf, feat_ep_rows, _p(qfeat_pm), ldq,
             feat_ep_rows, hb.n_way, hb.k_shot, hb.N, hb.D, hb.n_q_pts, hb.k_sub, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap,
-            _p(hb.Y), _p(hb.desc), 32, _p(hb.assign), 2 * S * hb.N, _p(hb.cluster_count), hb.n_cap, _p(hb.proto_ws),
+            _p(hb.Y), _p(hb.desc), HD_WORDS, _p(hb.assign), 2 * S * hb.N, _p(hb.cluster_count), hb.n_cap, _p(hb.proto_ws),
             hb.proto_words, hb.proto_stride, HEAD_FPS_ONE_LAUNCH if hb.fps_one_launch else 0, _st()))
 
 
 def knn_nodes(hb, exact=False):
     """201-NN lists (E, n_cap, kp1) of every episode's graph nodes (mpti.py:731-736).  exact: the insertion kernel
     (always exact); otherwise the append-and-rank kernel, whose survivor-buffer overflow sets hb.knn_status."""
-    nbr = knn(hb.nodes, hb.E, hb.n_cap, hb.kp1, mode=SCORE_L2, n_valid=hb.n_nodes_ptr(), n_valid_stride=32,
+    nbr = knn(hb.nodes, hb.E, hb.n_cap, hb.kp1, mode=SCORE_L2, n_valid=hb.n_nodes_ptr(), n_valid_stride=HD_WORDS,
               status=None if exact else hb.knn_status)
     if exact:
         hb.knn_status.zero_()
@@ -390,12 +383,12 @@ def label_propagate(hb, nbr, sigma, alpha=0.99, max_iter=200, tol=1e-6):
     with _timed("label_propagate"):
         _lib.check(_lib.load().r3d_label_propagate_batched(
             hb.E, _p(hb.nodes), hb.nodes.stride(0), hb.D, _p(nbr), hb.kp1, _p(hb.Y), _p(hb.n_nodes_ptr()),
-            _p(hb.n_proto_ptr()), 32, hb.n_cap, float(sigma), float(alpha), int(max_iter), float(tol), _p(hb.Z), _p(hb.lp_ws),
+            _p(hb.n_proto_ptr()), HD_WORDS, hb.n_cap, float(sigma), float(alpha), int(max_iter), float(tol), _p(hb.Z), _p(hb.lp_ws),
             hb.lp_words, hb.lp_stride, _p(hb.stats), 2, _st()))
         if hb.planes == 2:  # label columns 4..7: the same systems, further right-hand sides
             pl = hb.E * hb.n_cap
             _lib.check(_lib.load().r3d_label_propagate_solve_batched(
-                hb.E, _p(hb.Y[pl:]), _p(hb.n_nodes_ptr()), 32, hb.n_cap, hb.kp1, float(alpha), int(max_iter), float(tol),
+                hb.E, _p(hb.Y[pl:]), _p(hb.n_nodes_ptr()), HD_WORDS, hb.n_cap, hb.kp1, float(alpha), int(max_iter), float(tol),
                 _p(hb.Z[pl:]), _p(hb.lp_ws), hb.lp_words, hb.lp_stride, _p(hb.stats2), 2, _st()))
             # one {converged, iterations} pair per system for the callers: converged = both, iterations = the larger
             hb.stats[:, 0] = torch.minimum(hb.stats[:, 0], hb.stats2[:, 0])
@@ -410,7 +403,7 @@ def graph_weights_verify(hb, sigma):
     dev = hb.nodes.device
     scratch = torch.empty(hb.E * lib.r3d_graph_weights_verify_words(hb.n_cap, hb.kp1), device=dev, dtype=torch.float32)
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
-    _lib.check(lib.r3d_graph_weights_verify(hb.E, _p(hb.nodes), hb.nodes.stride(0), hb.D, _p(hb.n_nodes_ptr()), 32, hb.n_cap,
+    _lib.check(lib.r3d_graph_weights_verify(hb.E, _p(hb.nodes), hb.nodes.stride(0), hb.D, _p(hb.n_nodes_ptr()), HD_WORDS, hb.n_cap,
                                             hb.kp1, float(sigma), _p(hb.lp_ws), hb.lp_words, hb.lp_stride, _p(scratch), _p(bad),
                                             _st()))
     return bad
@@ -433,7 +426,7 @@ def logits_ce(Z, z_ep_rows, n_proto_ptr, desc_stride, E, n_q, N, n_classes, labe
 
 def query_logits_ce(hb, n_q, n_classes, labels):
     """logits_ce of the label-propagation result in hb."""
-    return logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), 32, hb.E, n_q, hb.N, n_classes, labels)
+    return logits_ce(hb.Z, hb.n_cap, hb.n_proto_ptr(), HD_WORDS, hb.E, n_q, hb.N, n_classes, labels)
 
 
 def logits_ce_from_rows(Z, E, n_q, N, n_classes, labels):
@@ -589,7 +582,7 @@ def head_attach_queries(hb, fit, qfeat_pm, q_sys_rows=None):
         _lib.check(_lib.load().r3d_head_attach_queries_batched(
             hb.E, _p(fit.nodes), fit.nodes.stride(0), _p(fit.Y), fit.label_rows, _p(fit.desc), _p(fit.cluster_count),
             fit.proto_cap, _p(qfeat_pm), ldq, step, hb.n_way, hb.D, hb.n_q_pts, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap,
-            _p(hb.Y), _p(hb.desc), 32, _p(hb.cluster_count), hb.n_cap, _st()))
+            _p(hb.Y), _p(hb.desc), HD_WORDS, _p(hb.cluster_count), hb.n_cap, _st()))
 
 
 def protonet_similarity_sets(qfeat_pm, tables, n_way, method, n_groups, n_query_pts, q_sys_rows=None, scaler=10.0):
@@ -622,7 +615,7 @@ def head_fit_table(fits, device):
             (f0.nodes.stride(0), f0.nodes.shape[1], f0.label_rows, f0.proto_cap), "fits of different geometry"
         assert f.nodes.dtype == torch.float32 and f.Y.dtype == torch.float32 and f.desc.dtype == torch.int32
         assert f.nodes.data_ptr() % 16 == 0 and f.Y.data_ptr() % 16 == 0 and f.nodes.stride(0) % 4 == 0
-        assert f.Y.numel() >= 4 * f.label_rows and f.desc.numel() >= 32 and f.cluster_count.numel() >= f.proto_cap
+        assert f.Y.numel() >= 4 * f.label_rows and f.desc.numel() >= HD_WORDS and f.cluster_count.numel() >= f.proto_cap
         rows.append([f.nodes.data_ptr(), f.Y.data_ptr(), f.desc.data_ptr(), f.cluster_count.data_ptr()])
     return torch.tensor(rows, dtype=torch.int64).to(device)
 
@@ -640,7 +633,7 @@ def head_attach_queries_sets(hb, fits, table, qfeat_pm, q_sys_rows=None):
     with _timed("head_attach_queries"):
         _lib.check(_lib.load().r3d_head_attach_queries_sets(
             G, K, _p(table), f0.nodes.stride(0), f0.label_rows, f0.proto_cap, _p(qfeat_pm), ldq, step, hb.n_way, hb.D,
-            hb.n_q_pts, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap, _p(hb.Y), _p(hb.desc), 32, _p(hb.cluster_count), hb.n_cap,
+            hb.n_q_pts, _p(hb.nodes), hb.nodes.stride(0), hb.n_cap, _p(hb.Y), _p(hb.desc), HD_WORDS, _p(hb.cluster_count), hb.n_cap,
             _st()))
 
 
@@ -794,8 +787,6 @@ def scene_vote(M, ncx, ncy, r, N, chunk_cap, ws, logits, sws=None):
 
 # ---- predict_scene on a subsample: a cap on the chunks of a block, the transfer to the points without a vote
 SCENE_SPARSE_WS_NAMES = ("run_chunk0", "run_block", "voted_before", "unvoted", "tile0", "cand", "rec", "part")
-SCENE_TRANSFER_QUERY_TILE = 256   # SC_Q_TILE of csrc/scene.hip: queries of one cell per workgroup
-SCENE_TRANSFER_CAND_TILE = 1024   # SC_C_TILE: candidate rows staged through LDS at a time
 
 
 def scene_sparse_workspace(M, ncx, ncy, chunk_cap, device):
@@ -862,7 +853,6 @@ def scene_merge_sets(scores, votes, source, classes, background):
 
 
 # ---- fit_scene: the support set from an annotated scan (scene_support.py)
-SCENE_SUPPORT_MAX_WAYS = 7  # SC_MAX_WAYS of csrc/scene.hip
 
 
 def _label_bytes(labels, M):
@@ -918,11 +908,6 @@ def scene_prepare_blocks(scan, ncx, ncy, r, N, chunk_cap, ws, blocks, out, rgb_c
 
 
 # ---- pool_segments: scores pooled over user-given segments (scene_segments.py)
-SCENE_SEG_TILE = 256   # SG_TILE of csrc/scene_common.h: contributor ranks per tile
-SCENE_SEG_REC = 16     # words of the record in front of the workspace
-# the record's words (include/r3d.h, "pool_segments")
-SEG_R_MAX1, SEG_R_NNEG, SEG_R_NBAD, SEG_R_BADMAX, SEG_R_S, SEG_R_NCONTRIB, SEG_R_NTILES = 0, 1, 2, 4, 6, 7, 8
-SEG_R_NPOOLED, SEG_R_NFILLED, SEG_R_NUNLAB = 9, 10, 11
 
 
 def _scene_workspace(what, name, M, device):
@@ -1016,12 +1001,6 @@ def scene_seg_spread(min_members, segment_index, seg_members, seg_fields, in_fie
 
 
 # ---- build_segments: segments grown from the scan (scene_grow.py)
-SCENE_GROW_REC = 16    # words of the record in front of the workspace
-SCENE_GROW_AXIS = 1024  # GR_AXIS_MAX of csrc/scene_grow.hip: voxels per axis
-# the record's words (include/r3d.h, "build_segments")
-GROW_R_MIN, GROW_R_MAX, GROW_R_NVALID, GROW_R_V, GROW_R_NCOMP, GROW_R_S, GROW_R_NDROPPED, GROW_R_ERROR = 0, 3, 6, 7, 8, 9, 10, 11
-GROW_R_ABSORBED_VOXELS, GROW_R_ABSORBED_POINTS = 12, 13  # written by scene_grow_absorb, 0 without it
-SCENE_GROW_RINGS = 64  # GR_RINGS_MAX of csrc/scene_grow.hip: rounds of absorb
 
 
 def scene_grow_workspace(M, device):
@@ -1132,11 +1111,6 @@ def scene_grow_ids(voxel_index, n_voxels, n_segments, ws):
 
 
 # ---- smooth_scene: scores propagated over the voxel graph (scene_smooth.py), on the workspace of build_segments
-SCENE_SMOOTH_SLOTS = 26    # SM_SLOTS of csrc/scene_smooth.hip: neighbour slots of a voxel
-SCENE_SMOOTH_SWEEPS = 64   # SM_SWEEPS_MAX
-SCENE_SMOOTH_COUNTS = 8    # words of the counts (include/r3d.h, "smooth_scene")
-(SMOOTH_R_MEMBER_VOXELS, SMOOTH_R_FILLED_VOXELS, SMOOTH_R_NSMOOTHED, SMOOTH_R_NCHANGED, SMOOTH_R_NFILLED,
- SMOOTH_R_NUNLAB) = range(6)
 
 
 def _smooth_ok(t, shape, dtype):
@@ -1202,11 +1176,6 @@ def scene_smooth_spread(voxel_index, ring, voxel_scores, in_scores, in_labels, i
 
 
 # ---- extract_objects: objects from a labelled scan (scene_objects.py)
-SCENE_OBJ_IGNORE = 64          # OB_IGNORE_MAX of csrc/scene_objects.hip: entries of the ignore table
-SCENE_OBJ_LABEL = 2 ** 31 - 2  # OB_LABEL_MAX: the largest label a key holds
-SCENE_OBJ_KEY = 2 ** 31 - 1    # OB_KEY_MAX: n_labels * n_cells
-# the record: the words of build_segments above (GROW_R_V: the units) and four of its own (include/r3d.h, "extract_objects")
-OBJ_R_NLABELS, OBJ_R_NUNLABELLED, OBJ_R_NOVER, OBJ_R_NPOINTS = 12, 13, 14, 15
 
 
 def scene_obj_workspace(M, device):
@@ -1282,11 +1251,6 @@ def scene_obj_ids(unit_index, n_units, n_objects, ws):
 
 
 # ---- match_objects: a scan's objects against ground-truth instances (scene_match.py)
-SCENE_MATCH_REC = 32   # MT_REC of csrc/scene_match.hip: words of the record in front of the workspace
-SCENE_MATCH_IOU = 8    # MT_MAX_IOU: thresholds of one call
-# the record's words (include/r3d.h, "match_objects"); the first four come per column, pred then truth
-MATCH_R_MAX1, MATCH_R_NNEG, MATCH_R_NIGNORED, MATCH_R_NBAD, MATCH_R_BADMAX = 0, 2, 4, 5, 6
-MATCH_R_ROWS, MATCH_R_MIXED, MATCH_R_NBOTH, MATCH_R_NPAIRS = 8, 10, 12, 13
 
 
 def scene_match_workspace(M, device):

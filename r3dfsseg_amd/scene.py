@@ -36,8 +36,8 @@ import torch
 
 from . import ops
 
-MAX_CELLS = 65536
-MAX_POINTS = 2 ** 27
+MAX_CELLS = ops.SCENE_MAX_CELLS
+MAX_POINTS = ops.SCENE_MAX_POINTS
 TRANSFERS = ("nearest", "idw")
 ATTRIBS = {"xyz": (-1, -1), "xyzrgb": (3, -1), "xyzXYZ": (-1, 3), "xyzrgbXYZ": (3, 6)}  # -> (rgb_ch, XYZ_ch)
 

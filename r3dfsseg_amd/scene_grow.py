@@ -115,15 +115,15 @@ def check_grow_args(scan, voxel=0.05, colour_tol=None, connectivity=6, min_point
     return scan, v32
 
 
-def grid_of(lo, hi, voxel):
+def grid_of(lo, hi, voxel, what="build_segments"):
     """lo, hi (3,) float32 minima and maxima of the valid points -> (nx, ny, nz) by G2: the keys kernel's arithmetic at the
-    maximum, plus one.  Raises ValueError, naming the axis, when one of them exceeds 1024."""
+    maximum, plus one.  Raises ValueError in the name of `what`, naming the axis, when one of them exceeds MAX_AXIS."""
     grid = tuple(scene.n_cells_along(lo[a], hi[a], voxel) for a in range(3))
     for a, n in enumerate(grid):
         if n > MAX_AXIS:
             extent = float(np.float32(hi[a]) - np.float32(lo[a]))
-            raise ValueError("build_segments: %d voxels of %g along %s (at most %d per axis); the extent %g fits with any voxel "
-                             "above %.9g" % (n, float(voxel), AXES[a], MAX_AXIS, extent, extent / MAX_AXIS))
+            raise ValueError("%s: %d voxels of %g along %s (at most %d per axis); the extent %g fits with any voxel "
+                             "above %.9g" % (what, n, float(voxel), AXES[a], MAX_AXIS, extent, extent / MAX_AXIS))
     return grid
 
 

@@ -22,7 +22,7 @@ import torch
 
 from . import ops, scene
 
-MAX_COLS = 64
+MAX_COLS = ops.SCENE_SCORE_COLS_MAX
 
 
 class SegmentResult:

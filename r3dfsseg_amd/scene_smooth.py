@@ -30,7 +30,7 @@ import torch
 
 from . import ops, scene, scene_grow, scene_segments
 
-MAX_COLS = 64
+MAX_COLS = ops.SCENE_SCORE_COLS_MAX
 MAX_ITERATIONS = ops.SCENE_SMOOTH_SWEEPS
 
 
@@ -120,10 +120,7 @@ def smooth_scene(res, scan, voxel=0.05, connectivity=26, alpha=0.8, iterations=1
                             n_voxels=0, n_member_voxels=0, n_filled_voxels=0, n_smoothed=0, n_changed=0, n_filled=0,
                             n_unlabelled=int((labels == -1).sum()), n_invalid=M, grid=(0, 0, 0))
     lo, hi = scene_grow.extent_of(rec)
-    try:
-        grid = scene_grow.grid_of(lo, hi, voxel)
-    except ValueError as e:
-        raise ValueError(str(e).replace("build_segments:", "smooth_scene:", 1)) from None
+    grid = scene_grow.grid_of(lo, hi, voxel, "smooth_scene")
     ops.scene_grow_sort(scan, lo, voxel, grid, ws)
     V = scene_grow.read_record(ws)[ops.GROW_R_V]  # host read 2 of 3
     voxel_index, voxel_means = ops.scene_grow_voxels(scan, grid, n_valid, V, colour_tol is not None, ws)

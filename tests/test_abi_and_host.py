@@ -133,6 +133,121 @@ def test_binding_spot_pins_on_the_real_header():
     assert fn(1, 2, (ctypes.c_long * 6)()) == 0 and fn(1, 2, ctypes.byref(ctypes.c_int(0))) == 0
 
 
+def test_constant_parser_on_small_headers():
+    """The parser the constants are read with (_lib.parse_constants), on text written here: the grammar include/r3d.h uses
+    and what must be refused rather than guessed."""
+    consts = _lib.parse_constants("""
+        #ifndef R3D_GUARD_H
+        #define R3D_GUARD_H            /* no value: skipped */
+        /* #define R3D_IN_A_COMMENT 1 */
+        #define R3D_DEC 26
+        #define R3D_HEX 0xC0           // a trailing comment
+        #define R3D_LONG 2147483646L   /* n + 1 fits an int */
+        #define R3D_SHIFT (1L << 27)
+        #define R3D_PRODUCT (3 * R3D_DEC)
+        #define R3D_NESTED ((R3D_PRODUCT + 8) * 2 - (1 << 2) | 0x1)
+        #define R3D_ALIAS R3D_HEX
+        #  define  R3D_SPACED   7
+        #define OTHER_PREFIX 5
+        int r3d_fn(int R3D_NOT_A_DEFINE);
+    """)
+    assert consts == {"R3D_DEC": 26, "R3D_HEX": 192, "R3D_LONG": 2147483646, "R3D_SHIFT": 1 << 27, "R3D_PRODUCT": 78,
+                      "R3D_NESTED": 169, "R3D_ALIAS": 192, "R3D_SPACED": 7}
+    assert all(type(v) is int for v in consts.values())
+    for bad, named in (("#define R3D_A (2 * R3D_B)\n#define R3D_B 1", "R3D_A.*R3D_B"),   # used before its definition
+                       ("#define R3D_OK 0\n#define R3D_A 0.5", "R3D_A"),                    # a float
+                       ("#define R3D_A 1e3", "R3D_A"),
+                       ("#define R3D_A(x) 1", "R3D_A"),                                     # a function-like macro
+                       ("#define R3D_A 1\n#define R3D_B 2\n#define R3D_A 1", "R3D_A.*twice"),
+                       ("#define R3D_A 8 / 2", "R3D_A"),                                    # an operator outside the grammar
+                       ("#define R3D_A (1 << 3", "R3D_A"),
+                       ("#define R3D_A 1 2", "R3D_A"),
+                       ("#define R3D_A sizeof(int)", "R3D_A")):
+        with pytest.raises(RuntimeError, match=named):
+            _lib.parse_constants(bad)
+
+
+# Every constant of ABI 6 and its value: the one deliberate repetition of include/r3d.h, like a golden file.  Changing a
+# value or adding a constant fails here until this pin -- and, where callers are affected, R3D_ABI_VERSION -- is touched
+# on purpose.
+ABI_6_CONSTANTS = {
+    "R3D_ABI_VERSION": 6, "R3D_OK": 0, "R3D_ERR_ARG": 1, "R3D_ERR_LAUNCH": 2, "R3D_ERR_UNSUPPORTED": 3,
+    "R3D_SCORE_DGCNN": 0, "R3D_SCORE_L2": 1,
+    "R3D_KNN_FLAG_STATUS": 1, "R3D_KNN_FLAG_X_CM": 2, "R3D_KNN_FLAG_NO_X": 4, "R3D_KNN_FLAG_FIXED_SCRATCH": 8,
+    "R3D_KNN_PATH_MASK": 0x3, "R3D_KNN_PATH_SMALL": 0, "R3D_KNN_PATH_LARGE": 1, "R3D_KNN_PATH_INSERTION": 2,
+    "R3D_KNN_PATH_FEW": 0x4, "R3D_KNN_PATH_SPLIT": 0x8, "R3D_KNN_PATH_BFA": 0x10, "R3D_KNN_PATH_FILTER": 0x20,
+    "R3D_KNN_PATH_CHAN_SHIFT": 6, "R3D_KNN_PATH_CHAN_MASK": 0xC0, "R3D_KNN_CHAN_ANY": 0, "R3D_KNN_CHAN_LE16": 64,
+    "R3D_KNN_CHAN_FULL": 128, "R3D_KNN_PATH_REGS_SHIFT": 8, "R3D_KNN_PATH_REGS_MASK": 0x300, "R3D_KNN_REGS_1": 256,
+    "R3D_KNN_REGS_2": 512, "R3D_KNN_REGS_4": 768,
+    "R3D_ACT_NONE": 0, "R3D_ACT_RELU": 1, "R3D_ACT_LRELU": 2,
+    "R3D_HD_MAXSEG": 8, "R3D_HD_SEG_COUNT": 0, "R3D_HD_SEG_M": 8, "R3D_HD_SEG_POFF": 16, "R3D_HD_N_PROTO": 24,
+    "R3D_HD_N_NODES": 25, "R3D_HD_FPS_TIMEOUT": 26, "R3D_HD_WORDS": 32, "R3D_HEAD_FPS_ONE_LAUNCH": 1,
+    "R3D_SCENE_MAX_POINTS": 2 ** 27, "R3D_SCENE_MAX_CELLS": 65536, "R3D_SCENE_TRANSFER_QUERY_TILE": 256,
+    "R3D_SCENE_TRANSFER_CAND_TILE": 1024, "R3D_SCENE_SUPPORT_MAX_WAYS": 7,
+    "R3D_SCENE_SEG_REC": 16, "R3D_SCENE_SEG_TILE": 256, "R3D_SCENE_SCORE_COLS_MAX": 64,
+    "R3D_SEG_R_MAX1": 0, "R3D_SEG_R_NNEG": 1, "R3D_SEG_R_NBAD": 2, "R3D_SEG_R_BADMAX": 4, "R3D_SEG_R_S": 6,
+    "R3D_SEG_R_NCONTRIB": 7, "R3D_SEG_R_NTILES": 8, "R3D_SEG_R_NPOOLED": 9, "R3D_SEG_R_NFILLED": 10, "R3D_SEG_R_NUNLAB": 11,
+    "R3D_SCENE_GROW_REC": 16, "R3D_SCENE_GROW_AXIS": 1024, "R3D_SCENE_GROW_RINGS": 64,
+    "R3D_GROW_R_MIN": 0, "R3D_GROW_R_MAX": 3, "R3D_GROW_R_NVALID": 6, "R3D_GROW_R_V": 7, "R3D_GROW_R_NCOMP": 8,
+    "R3D_GROW_R_S": 9, "R3D_GROW_R_NDROPPED": 10, "R3D_GROW_R_ERROR": 11, "R3D_GROW_R_ABSORBED_VOXELS": 12,
+    "R3D_GROW_R_ABSORBED_POINTS": 13,
+    "R3D_SCENE_OBJ_IGNORE": 64, "R3D_SCENE_OBJ_LABEL": 2 ** 31 - 2, "R3D_SCENE_OBJ_KEY": 2 ** 31 - 1,
+    "R3D_OBJ_R_NLABELS": 12, "R3D_OBJ_R_NUNLABELLED": 13, "R3D_OBJ_R_NOVER": 14, "R3D_OBJ_R_NPOINTS": 15,
+    "R3D_SCENE_MATCH_REC": 32, "R3D_SCENE_MATCH_IOU": 8,
+    "R3D_MATCH_R_MAX1": 0, "R3D_MATCH_R_NNEG": 2, "R3D_MATCH_R_NIGNORED": 4, "R3D_MATCH_R_NBAD": 5, "R3D_MATCH_R_BADMAX": 6,
+    "R3D_MATCH_R_ROWS": 8, "R3D_MATCH_R_MIXED": 10, "R3D_MATCH_R_NBOTH": 12, "R3D_MATCH_R_NPAIRS": 13,
+    "R3D_SCENE_SMOOTH_SLOTS": 26, "R3D_SCENE_SMOOTH_SWEEPS": 64, "R3D_SCENE_SMOOTH_COUNTS": 8,
+    "R3D_SMOOTH_R_MEMBER_VOXELS": 0, "R3D_SMOOTH_R_FILLED_VOXELS": 1, "R3D_SMOOTH_R_NSMOOTHED": 2, "R3D_SMOOTH_R_NCHANGED": 3,
+    "R3D_SMOOTH_R_NFILLED": 4, "R3D_SMOOTH_R_NUNLAB": 5,
+    "R3D_CUT_MAX_BLOCK_POINTS": 1 << 20, "R3D_CUT_FLAG_QUERY": 1, "R3D_CUT_FLAG_GT_ZERO": 2, "R3D_CUT_FLAG_PARTIAL": 4,
+}
+# the names some modules keep for a constant of theirs
+CONSTANT_ALIASES = {
+    "ABI_VERSION": "R3D_ABI_VERSION", "MAX_AXIS": "R3D_SCENE_GROW_AXIS", "MAX_RINGS": "R3D_SCENE_GROW_RINGS",
+    "MAX_CELLS": "R3D_SCENE_MAX_CELLS", "MAX_POINTS": "R3D_SCENE_MAX_POINTS", "MAX_COLS": "R3D_SCENE_SCORE_COLS_MAX",
+    "MAX_ITERATIONS": "R3D_SCENE_SMOOTH_SWEEPS", "MAX_IGNORE": "R3D_SCENE_OBJ_IGNORE", "MAX_KEY": "R3D_SCENE_OBJ_KEY",
+    "MAX_IOU": "R3D_SCENE_MATCH_IOU", "MAX_BLOCK_POINTS": "R3D_CUT_MAX_BLOCK_POINTS", "FLAG_QUERY": "R3D_CUT_FLAG_QUERY",
+    "FLAG_GT_ZERO": "R3D_CUT_FLAG_GT_ZERO", "FLAG_PARTIAL": "R3D_CUT_FLAG_PARTIAL",
+}
+
+
+def test_the_constants_of_abi_6_are_pinned_and_exported_by_ops():
+    from r3dfsseg_amd import ops
+    got = _lib.CONSTANTS
+    assert sorted(got) == sorted(ABI_6_CONSTANTS), set(got) ^ set(ABI_6_CONSTANTS)
+    assert got == ABI_6_CONSTANTS, {k: (v, ABI_6_CONSTANTS[k]) for k, v in got.items() if v != ABI_6_CONSTANTS[k]}
+    for name, value in ABI_6_CONSTANTS.items():
+        assert getattr(ops, name[len("R3D_"):]) == value, name
+    assert got == _lib.parse_constants(open(_lib.HEADER_PATH).read())
+
+
+def test_parsed_abi_version_is_the_built_library_s():
+    from r3dfsseg_amd import build
+    lib = ctypes.CDLL(build.build())
+    lib.r3d_abi_version.restype = ctypes.c_int
+    assert lib.r3d_abi_version() == _lib.CONSTANTS["R3D_ABI_VERSION"] == _lib.ABI_VERSION == 6
+
+
+def test_no_module_keeps_a_value_of_its_own_for_an_abi_constant():
+    """Every global of the package's modules that carries the name of a constant -- without the prefix, or one of the
+    aliases above -- holds the header's value (values, not source text: a module may rename, never restate)."""
+    import importlib
+    import pkgutil
+    import r3dfsseg_amd
+    names = {name[len("R3D_"):]: name for name in ABI_6_CONSTANTS}
+    names.update(CONSTANT_ALIASES)
+    seen = set()
+    for info in pkgutil.iter_modules(r3dfsseg_amd.__path__):
+        if not os.path.exists(os.path.join(r3dfsseg_amd.__path__[0], info.name + ".py")):
+            continue  # the built library lies in the package too
+        mod = importlib.import_module("r3dfsseg_amd." + info.name)
+        for name, value in vars(mod).items():
+            if name in names:
+                assert type(value) is int and value == _lib.CONSTANTS[names[name]], (info.name, name, value)
+                seen.add(name)
+    assert seen == set(names), set(names) - seen
+
+
 REMOVED_WITHIN_ABI_5 = (
     "r3d_sqnorm", "r3d_pm_to_cm_pitched", "r3d_attention_fwd", "r3d_head_max_k", "r3d_head_prototypes",
     "r3d_head_prototypes_bwd", "r3d_pointwise_conv_stats2", "r3d_colreduce", "r3d_colreduce_seg", "r3d_colstats",
