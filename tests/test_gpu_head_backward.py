@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import head_ref as R
+from proto_cases import masks as _masks  # exact foreground counts per (way, shot)
 from oracle import r3d_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -289,17 +290,6 @@ def test_ce_grad(ops, n_classes):
 # ----------------------------------------------------------------------------------------------------------------------
 # E: prototypes, forward and backward
 # ----------------------------------------------------------------------------------------------------------------------
-def _masks(n_way, k_shot, N, seg_counts, seed):
-    """support_y (n_way, k_shot, N) int64 whose way w has seg_counts[w] foreground points, split over its shots."""
-    rs = np.random.RandomState(seed)
-    y = torch.zeros(n_way, k_shot, N, dtype=torch.int64)
-    for w, c in enumerate(seg_counts):
-        per = [c // k_shot + (1 if k < c % k_shot else 0) for k in range(k_shot)]
-        for k in range(k_shot):
-            y[w, k, torch.from_numpy(rs.permutation(N)[:per[k]])] = 1
-    return y
-
-
 @pytest.mark.parametrize("one_launch", [True, False])
 @pytest.mark.parametrize("n_way,k_shot,seg_counts", [(2, 2, ((3, 10), (11, 40))), (4, 1, ((3, 10, 11, 40), (40, 11, 10, 3)))])
 @pytest.mark.parametrize("D", [64, 132, 256])
