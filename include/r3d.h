@@ -297,9 +297,11 @@ int r3d_head_attach_queries_sets(int n_groups, int n_sets, const uint64_t* fits,
  * ws: r3d_lp_ws_words(n_cap, kp1) int32 words, 16-byte aligned; it keeps the graph, the coarse space and the
  * directed weights for r3d_label_propagate_bwd_batched.  stats_out optional device int32[2] = {converged, iterations}.
  * r3d_lp_ws_offsets: int32-word offsets inside ws of {row_ptr, col (uint16 entries), val, dinv, aggregate ids,
- * solver state} for tests and tools that read the system back. */
+ * solver state} for tests and tools that read the system back; r3d_lp_ws_offsets_coarse: those of {M W (n_cap, 64) fp32,
+ * the 16 partial matrices of E (16, 64, 64), E^-1 (64, 64) fp32, the CG residual r (n_cap, 4) fp32}. */
 long r3d_lp_ws_words(int n_cap, int kp1);
 int r3d_lp_ws_offsets(int n_cap, int kp1, long* out6);
+int r3d_lp_ws_offsets_coarse(int n_cap, int kp1, long* out4);
 int r3d_label_propagate(const float* nodes, long ldn, int D, const int32_t* nbr, int kp1, const float* Y,
                         const int32_t* n_dev, const int32_t* n_proto_dev, int n_cap, float sigma, float alpha,
                         int max_iter, float tol, float* Z, int32_t* ws, long ws_words, int32_t* stats_out, void* stream);

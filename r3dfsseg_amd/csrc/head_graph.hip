@@ -1641,6 +1641,17 @@ extern "C" int r3d_lp_ws_offsets(int n_cap, int kp1, long* out6) {
   return R3D_OK;
 }
 
+// ... and of the coarse space and the residual: M W ((n_cap, 64) fp32, rows >= n zero), the 16 partial matrices of E,
+// E^-1 ((64, 64) fp32) and the CG residual r ((n_cap, 4) fp32)
+extern "C" int r3d_lp_ws_offsets_coarse(int n_cap, int kp1, long* out4) {
+  R3D_REQUIRE(out4 && n_cap > 0 && kp1 >= 2, "r3d_lp_ws_offsets_coarse: bad arguments");
+  const LpWs L = lp_carve(nullptr, n_cap, kp1);
+  const int32_t* base = nullptr;
+  out4[0] = (const int32_t*)L.MW - base; out4[1] = (const int32_t*)L.Epart - base; out4[2] = (const int32_t*)L.Einv - base;
+  out4[3] = (const int32_t*)L.r - base;
+  return R3D_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Runtime guard of the multi-stream schedule (packed fp32 arithmetic beside bf16-MFMA-dense waves computed
 // wrong graph weights on this chip; the library is built without those instructions and tests/test_gpu_concurrency.py

@@ -309,6 +309,9 @@ class HeadBuffers:
         self.ws_off = list(off)
         lib.r3d_lp_ws_offsets(self.n_cap, self.kp1, off)
         self.lp_off = dict(zip(("row_ptr", "col", "val", "dinv", "agg", "cg"), off))
+        off4 = (ctypes.c_long * 4)()
+        lib.r3d_lp_ws_offsets_coarse(self.n_cap, self.kp1, off4)
+        self.lp_off.update(zip(("MW", "Epart", "Einv", "r"), off4))
 
     @property
     def fps_group(self):
@@ -335,6 +338,19 @@ class HeadBuffers:
         col = ws[o["col"]:o["col"] + (nnz + 1) // 2].view(torch.int16)[:nnz].to(torch.int64) & 0xffff
         val = ws[o["val"]:o["val"] + nnz].view(torch.float32)
         return n, row_ptr, col, val
+
+    def coarse(self, e=0):
+        """(agg (n,) int64, MW (n_cap, 64) fp32, Einv (64, 64) fp32, r (n_cap, 4) fp32): the coarse space of the CG's
+        preconditioner and the residual the last solve left in episode e's workspace (views; synchronises; tests and
+        tools)."""
+        n = int(self.desc[e, HD_N_NODES].item())
+        o, nc = self.lp_off, self.n_cap
+        ws = self.lp_ws[e]
+        agg = ws[o["agg"]:o["agg"] + n].to(torch.int64)
+        MW = ws[o["MW"]:o["MW"] + nc * 64].view(torch.float32).view(nc, 64)
+        Einv = ws[o["Einv"]:o["Einv"] + 64 * 64].view(torch.float32).view(64, 64)
+        r = ws[o["r"]:o["r"] + nc * 4].view(torch.float32).view(nc, 4)
+        return agg, MW, Einv, r
 
 
 def head_status(stats, desc, knn_status, stats_bwd=None):

@@ -126,6 +126,7 @@ def test_binding_spot_pins_on_the_real_header():
     assert args.count(_lib.c_u) == 2
     assert sigs["r3d_last_error_string"] == (ctypes.c_char_p, [])
     assert sigs["r3d_lp_ws_offsets"] == (_lib.c_i, [_lib.c_i, _lib.c_i, _lib.c_f])
+    assert sigs["r3d_lp_ws_offsets_coarse"] == (_lib.c_i, [_lib.c_i, _lib.c_i, _lib.c_f])
     assert sigs["r3d_graph_set_lp_budget"][1][-1] is _lib.c_f  # (host out-pointers travel as void* too)
     assert sigs["r3d_cm_pitch"] == (_lib.c_l, [_lib.c_i])
     # as void* the host out-pointers still take what callers pass: ctypes arrays and byref objects
@@ -291,6 +292,28 @@ def test_entry_points_removed_within_abi_5_are_gone():
         assert name not in words, name
         assert name not in _lib._SIGS and name not in _lib.header_symbols(), name
         assert exported is None or name not in exported, name
+
+
+def test_coarse_space_offsets_are_declared_bound_and_inside_the_workspace():
+    """r3d_lp_ws_offsets_coarse (an additive entry point of ABI 6, beside r3d_lp_ws_offsets): declared, bound, exported, and
+    on the host -- the layout needs no GPU -- its four arrays lie in carving order behind the aggregate ids and in front of
+    the solver state, the float4-read ones on 16-byte boundaries, none overlapping the next, all inside r3d_lp_ws_words."""
+    name = "r3d_lp_ws_offsets_coarse"
+    assert name in _lib._SIGS and name in _lib.header_symbols() and _lib.ABI_VERSION == 6
+    exported = _exported_r3d_symbols()
+    assert exported is None or name in exported
+    lib = _lib.load()
+    for n_cap, kp1 in ((1, 2), (193, 9), (640, 9), (4396, 201), (32768, 201)):
+        o6, o4 = (ctypes.c_long * 6)(), (ctypes.c_long * 4)()
+        assert lib.r3d_lp_ws_offsets(n_cap, kp1, o6) == 0 and lib.r3d_lp_ws_offsets_coarse(n_cap, kp1, o4) == 0
+        agg, cg = o6[4], o6[5]
+        MW, Epart, Einv, r = list(o4)
+        assert agg + n_cap <= MW and MW + 64 * n_cap <= Epart and Epart + 16 * 64 * 64 <= Einv and Einv + 64 * 64 <= r
+        assert r + 3 * 4 * n_cap <= cg < lib.r3d_lp_ws_words(n_cap, kp1)   # r, p, q in front of the state
+        assert MW % 4 == 0 and Einv % 4 == 0 and r % 4 == 0
+    assert lib.r3d_lp_ws_offsets_coarse(0, 9, o4) != 0 and b"bad arguments" in lib.r3d_last_error_string()
+    assert lib.r3d_lp_ws_offsets_coarse(64, 9, None) != 0
+    assert lib.r3d_lp_ws_offsets_coarse(64, 1, o4) != 0
 
 
 def test_abi_argument_validation_without_gpu():
