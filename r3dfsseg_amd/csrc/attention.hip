@@ -1376,23 +1376,13 @@ extern "C" int r3d_attention_bwd(const float* qkv, long ld, int B, int N, const 
 // device to ask (host-only sizing calls)
 template <int D>
 static int attention_slots(int which) {
-  static int cache[ATT_N] = {0, 0, 0, 0, 0, 0};
-  if (cache[which]) return cache[which];
   const int fallback[ATT_N] = {512, 256, 512, 768, 512, 512};
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  hipError_t e = hipErrorUnknown;
-  if (which == ATT_FWD) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_fwd_kernel<D>, 256, 0);
-  else if (which == ATT_FWD_BX3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_fwd_bx3_kernel<D, false>, 256, 0);
-  else if (which == ATT_BWD_KV_BX3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_bwd_kv_bx3_kernel<D, false>, 256, 0);
-  else if (which == ATT_BWD_Q_BX3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_bwd_q_bx3_kernel<D, false>, 256, 0);
-  else if (which == ATT_BWD_KV) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_bwd_kv_kernel<D>, 256, 0);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_attention_bwd_q_kernel<D>, 256, 0);
-  if (e == hipSuccess && per_cu > 0 && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-    cache[which] = per_cu * prop.multiProcessorCount;
-  else {
-    (void)hipGetLastError();
-    cache[which] = fallback[which];
-  }
-  return cache[which];
+  const void* const kernel = which == ATT_FWD          ? (const void*)r3d_attention_fwd_kernel<D>
+                             : which == ATT_FWD_BX3    ? (const void*)r3d_attention_fwd_bx3_kernel<D, false>
+                             : which == ATT_BWD_KV_BX3 ? (const void*)r3d_attention_bwd_kv_bx3_kernel<D, false>
+                             : which == ATT_BWD_Q_BX3  ? (const void*)r3d_attention_bwd_q_bx3_kernel<D, false>
+                             : which == ATT_BWD_KV     ? (const void*)r3d_attention_bwd_kv_kernel<D>
+                                                       : (const void*)r3d_attention_bwd_q_kernel<D>;
+  const int slots = r3d_kernel_resident(kernel, 256, 0);
+  return slots > 0 ? slots : fallback[which];
 }

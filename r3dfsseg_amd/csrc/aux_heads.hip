@@ -669,12 +669,7 @@ extern "C" int r3d_protonet_similarity_sets(int n_groups, int n_sets, const floa
   R3D_REQUIRE(((uintptr_t)Z & 15) == 0, "%s: Z must be 16-byte aligned", who);
   const int R = n_sets * (n_way + 1);
   const size_t lds = sizeof(float) * ((size_t)R * (D | 1) + R);
-  static size_t reserved = 64 * 1024;  // what a kernel may ask for without the attribute
-  if (lds > reserved) {
-    hipError_t e = hipFuncSetAttribute((const void*)r3d_proto_sim_sets_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    R3D_REQUIRE(e == hipSuccess, "%s: cannot reserve %zu B of LDS", who, lds);
-    reserved = lds;
-  }
+  R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_proto_sim_sets_kernel, lds) == 0, "%s: cannot reserve %zu B of LDS", who, lds);
   // the tiling of r3d_protonet_similarity_batched over the groups (a point's arithmetic does not depend on the grid)
   const int gx = min(r3d_cdiv(n_query_pts, 4), max(32, min(256, 2048 / n_groups)));
   const long plane = (long)n_groups * n_sets * n_query_pts;

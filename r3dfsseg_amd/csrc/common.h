@@ -15,6 +15,12 @@ void r3d_set_error(const char* fmt, ...);
 R3D_INTERNAL int r3d_pm_to_cm_pitched_launch(const float* in, long ld, int B, int C, int N, float* out, long pitch, void* stream);
 // train_ops.hip: [chunks][2][C] partial column sums -> sums_out [seg][2][C]
 R3D_INTERNAL int r3d_colreduce_launch(const float* part, int count_a, int count_b, int n_seg, int C, float* sums_out, void* stream);
+// error.hip: what the runtime says about a kernel on the CURRENT device, remembered per (device, kernel).
+// dynamic LDS: make sure `kernel` may be launched with `bytes` of it.  0 = ok, else the runtime's hipError_t.
+R3D_INTERNAL int r3d_kernel_lds(const void* kernel, size_t bytes);
+// workgroups of `kernel` (block threads, lds bytes of dynamic LDS, which it makes sure of first) the device holds at
+// once: occupancy x CUs.  0 when the runtime cannot be asked (no device, query failed); the caller decides what then.
+R3D_INTERNAL int r3d_kernel_resident(const void* kernel, int block, size_t lds);
 
 #define R3D_REQUIRE(cond, ...)          \
   do {                                  \

@@ -528,12 +528,7 @@ static int contrast_fwd_impl(int n_ep, const CtEp& ep, const float* feat, long l
   hipLaunchKernelGGL(r3d_contrast_protos_kernel, dim3(n_way * k_shot, n_ep), dim3(256), 0, st, feat, ldf, D, support_y, N, c.protos,
                      c.cnt, c.m, c.assign, ep);
   const size_t lds = sizeof(float) * CT_MAXV * (CT_DMAX + 1 + 2 * (CT_PD + 1) + CT_MAXV + 1);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)r3d_contrast_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    R3D_REQUIRE(e == hipSuccess, "r3d_contrast_fwd: cannot reserve %zu B of LDS", lds);
-    attr = true;
-  }
+  R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_contrast_loss_kernel, lds) == 0, "r3d_contrast_fwd: cannot reserve %zu B of LDS", lds);
   hipLaunchKernelGGL(r3d_contrast_loss_kernel, dim3(n_way, n_ep), dim3(256), lds, st, c.protos, c.m, support_flag, n_way, k_shot, D,
                      W, bias, temp, c.loss_way, c.dW_way, c.db_way, c.dp_way, c.vec_src, ep);
   hipLaunchKernelGGL(r3d_contrast_mean_kernel, dim3(n_ep), dim3(64), 0, st, c.loss_way, n_way, loss_out, ep);

@@ -42,17 +42,3 @@ static __device__ __forceinline__ void e2_rowgemm(const float* __restrict__ A, c
     }
   }
 }
-
-// workgroups of `kernel` (256 threads, `lds` bytes of dynamic LDS) the chip holds at once, capped: the grid of a
-// persistent loop over the units.  Sets the dynamic-LDS attribute.  0 on failure.
-template <typename KernelT>
-static int e2_resident_blocks(KernelT kernel, size_t lds, int cap) {
-  if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
-  int per_cu = 0, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
-      hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu <= 0)
-    return 0;
-  const int r = per_cu * prop.multiProcessorCount;
-  return r < cap ? r : cap;
-}

@@ -84,11 +84,9 @@ template <int RT>
 static int edgeconv_launch_rt(const float* PQ, const int32_t* idx, const float* W2, const float* s2, const float* t2, float* out,
                               long ldo, int N, long total_points, int32_t* argmax_out, hipStream_t st) {
   const size_t lds = sizeof(float) * ((size_t)2 * 16 * RT * E2_LD);
-  static int resident = 0;  // workgroups the chip holds at once
-  if (!resident) {
-    resident = e2_resident_blocks(r3d_edgeconv_kernel<RT>, lds, 1024);
-    R3D_REQUIRE(resident > 0, "r3d_edgeconv_fwd: cannot reserve %zu B of LDS", lds);
-  }
+  // workgroups the chip holds at once
+  const int resident = std::min(r3d_kernel_resident((const void*)r3d_edgeconv_kernel<RT>, 256, lds), 1024);
+  R3D_REQUIRE(resident > 0, "r3d_edgeconv_fwd: cannot reserve %zu B of LDS", lds);
   const long units = total_points / E2_PTS;
   const int grid = (int)(units <= resident ? units : (resident & ~7));  // several units per workgroup: keep their XCD label
   hipLaunchKernelGGL(r3d_edgeconv_kernel<RT>, dim3(grid), dim3(256), lds, st, PQ, idx, W2, s2, t2, out, ldo, N, total_points,

@@ -728,11 +728,8 @@ static int fwd2_launch_rt(int n_chunks, hipStream_t st, const float* PQ, const i
                           long bn_stride, const float* W2, EcGeom gm, r3d_segmap cs, int32_t* argmax, float* zmax, float* zmin,
                           int32_t* argmin, float* ws) {
   const size_t lds = sizeof(float) * ((size_t)2 * 16 * RT * E2_LD);
-  static int resident = 0;
-  if (!resident) {
-    resident = e2_resident_blocks(r3d_edgeconv_train_fwd2_kernel<RT>, lds, ET_MAXBLK);
-    R3D_REQUIRE(resident > 0, "r3d_edgeconv_train_fwd_minmax: cannot reserve %zu B of LDS", lds);
-  }
+  const int resident = std::min(r3d_kernel_resident((const void*)r3d_edgeconv_train_fwd2_kernel<RT>, 256, lds), ET_MAXBLK);
+  R3D_REQUIRE(resident > 0, "r3d_edgeconv_train_fwd_minmax: cannot reserve %zu B of LDS", lds);
   const int grid = et_grid8(n_chunks, resident);
   hipLaunchKernelGGL(r3d_edgeconv_train_fwd2_kernel<RT>, dim3(grid), dim3(256), lds, st, PQ, idx, s1, t1, bn_stride, W2, gm, cs,
                      n_chunks, argmax, zmax, zmin, argmin, ws);
@@ -805,11 +802,9 @@ static int bwd1_launch_rt(int n_chunks, hipStream_t st, const float* PQ, const i
                           const float* bn2_sums, const float* dout, long lddo, const int32_t* argmax, EcGeom gm, r3d_segmap cs,
                           float* DY1, float* BE, float* part_dw, float* part_bn, int* grid_out) {
   const size_t lds = sizeof(float) * ((size_t)2 * 16 * RT * E2_LD + 2 * E2_PTS * 64 + 6 * 64);
-  static int resident = 0;  // workgroups the chip holds at once (persistent loop over the chunks)
-  if (!resident) {
-    resident = e2_resident_blocks(r3d_edgeconv_bwd1_kernel<RT>, lds, ET_MAXBLK);
-    R3D_REQUIRE(resident > 0, "r3d_edgeconv_bwd: cannot reserve %zu B of LDS", lds);
-  }
+  // workgroups the chip holds at once (persistent loop over the chunks)
+  const int resident = std::min(r3d_kernel_resident((const void*)r3d_edgeconv_bwd1_kernel<RT>, 256, lds), ET_MAXBLK);
+  R3D_REQUIRE(resident > 0, "r3d_edgeconv_bwd: cannot reserve %zu B of LDS", lds);
   const int grid = et_grid8(n_chunks, resident);
   hipLaunchKernelGGL(r3d_edgeconv_bwd1_kernel<RT>, dim3(grid), dim3(256), lds, st, PQ, idx, bn, W2, bn2_sums, dout, lddo, argmax,
                      gm, cs, n_chunks, DY1, BE, part_dw, part_bn);
@@ -821,11 +816,10 @@ template <int RT>
 static int bwd1_bx3_launch_rt(int n_chunks, hipStream_t st, const float* PQ, const int32_t* idx, EcBn bn, const float* W2,
                               const float* bn2_sums, const float* dout, long lddo, const int32_t* argmax, const float* zwin,
                               EcGeom gm, r3d_segmap cs, float* DY1, float* BE, float* part_dw, float* part_bn, int* grid_out) {
-  static int resident = 0;  // workgroups the chip holds at once (persistent loop over the chunks); two dW2 partials each
-  if (!resident) {
-    resident = e2_resident_blocks(r3d_edgeconv_bwd1_bx3_kernel<RT>, EB_LDS_BYTES, ET_MAXBLK / 2);
-    R3D_REQUIRE(resident > 0, "r3d_edgeconv_bwd: cannot reserve %d B of LDS", (int)EB_LDS_BYTES);
-  }
+  // workgroups the chip holds at once (persistent loop over the chunks); two dW2 partials each
+  const int resident =
+      std::min(r3d_kernel_resident((const void*)r3d_edgeconv_bwd1_bx3_kernel<RT>, 256, EB_LDS_BYTES), ET_MAXBLK / 2);
+  R3D_REQUIRE(resident > 0, "r3d_edgeconv_bwd: cannot reserve %d B of LDS", (int)EB_LDS_BYTES);
   const int grid = et_grid8(n_chunks, resident);
   hipLaunchKernelGGL(r3d_edgeconv_bwd1_bx3_kernel<RT>, dim3(grid), dim3(256), EB_LDS_BYTES, st, PQ, idx, bn, W2, bn2_sums, dout,
                      lddo, argmax, zwin, gm, cs, n_chunks, DY1, BE, part_dw, part_bn);
@@ -845,12 +839,8 @@ extern "C" int r3d_edge_reverse(const int32_t* idx, int B, int N, int K, int32_t
   const size_t ro_lds = sizeof(int) * (size_t)RO_WAVES * N;
   static const bool ro_off = getenv("R3D_EDGE_REVERSE_SORT") != nullptr;  // A/B switch: the sorting kernel
   if (!ro_off && ro_lds <= 144 * 1024 && (long)N * K >= 64 * RO_WAVES) {
-    static size_t attr = 0;
-    if (ro_lds > attr) {
-      R3D_REQUIRE(hipFuncSetAttribute((const void*)r3d_edge_reverse_ordered_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)ro_lds) == hipSuccess, "r3d_edge_reverse: cannot reserve %zu B of LDS", ro_lds);
-      attr = ro_lds;
-    }
+    R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_edge_reverse_ordered_kernel, ro_lds) == 0,
+                "r3d_edge_reverse: cannot reserve %zu B of LDS", ro_lds);
     hipLaunchKernelGGL(r3d_edge_reverse_ordered_kernel, dim3(B), dim3(64 * RO_WAVES), ro_lds, (hipStream_t)stream, idx, N, K, B,
                        rev_ws, rev_ws + (long)B * N + 1);
   } else {

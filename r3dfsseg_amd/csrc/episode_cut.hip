@@ -406,10 +406,9 @@ static int ec_launch(const char* name, const float* points, const int32_t* label
   // LDS from N: the slots; PARTIAL: the sort keys in front of them, the run words behind (128 KiB at N = 8192)
   const size_t lds = (size_t)N * sizeof(int) + (PARTIAL ? (size_t)ec_pow2(N) * 8 + (size_t)N * sizeof(int) : 0);
   if (lds > 64 * 1024) {  // above the default ceiling of dynamic LDS the kernel's attribute is raised first
-    hipError_t e_ = hipFuncSetAttribute((const void*)r3d_episode_cut_kernel<PARTIAL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds);
-    if (e_ != hipSuccess) {
-      r3d_set_error("%s: %zu bytes of LDS for N %d refused: %s", name, lds, N, hipGetErrorString(e_));
+    const int e_ = r3d_kernel_lds((const void*)r3d_episode_cut_kernel<PARTIAL>, lds);
+    if (e_ != 0) {
+      r3d_set_error("%s: %zu bytes of LDS for N %d refused: %s", name, lds, N, hipGetErrorString((hipError_t)e_));
       return R3D_ERR_LAUNCH;
     }
   }

@@ -586,11 +586,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 static const size_t GB_LDS_22 = sizeof(unsigned short) * 3 * (128 + 128) * GB_RS;
 static const size_t GB_LDS_41 = sizeof(unsigned short) * 3 * (256 + 64) * GB_RS;
 
-template <typename KernelT>
-static int gb_lds_attr(KernelT k, size_t bytes) {
-  return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : 1;
-}
-
 // The ONE decision between the three point-wise kernels (r3d.h): 0 = r3d_pointwise_gemm_kernel (fp32 core, gemm.hip),
 // 1 = r3d_pointwise_gemm_bx3_kernel (W cut per tile), 2 = r3d_pointwise_gemm_bx3p_kernel (packed W).  A function of the
 // layer's shape and of the operands' alignment only, never of the batch -- but for the M >= 256 that the packed kernel
@@ -693,11 +688,7 @@ int r3d_gemm_tn_bx3_tiles(int Ca, int Cb) {
 template <int WM, int WN>
 static int gemm_tn_bx3_go(size_t lds, int blocks, hipStream_t st, const float* A, long lda, const float* B, long ldb, long M,
                           int Ca, int Cb, int rows, float* part) {
-  static bool attr = false;
-  if (!attr) {
-    R3D_REQUIRE(gb_lds_attr(r3d_gemm_tn_bx3_kernel<WM, WN>, lds) == 0, "r3d_gemm_tn: cannot reserve %zu B of LDS", lds);
-    attr = true;
-  }
+  R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_gemm_tn_bx3_kernel<WM, WN>, lds) == 0, "r3d_gemm_tn: cannot reserve %zu B of LDS", lds);
   hipLaunchKernelGGL((r3d_gemm_tn_bx3_kernel<WM, WN>), dim3(blocks), dim3(256), lds, st, A, lda, B, ldb, M, Ca, Cb, rows, part);
   return R3D_OK;
 }

@@ -1719,11 +1719,9 @@ static int lp_coarse_space(const LpWs& L, const float* nodes, long ldn, int D, c
                            int n_cap, float alpha, int n_ep, const HgEp& ep, hipStream_t st) {
   const int agg_rpw = 4;  // 16 nodes per workgroup: the 64 seed rows are staged once per workgroup
   const size_t agg_lds = ((size_t)HG_M * (D | 1) + 4 * D) * sizeof(float);
-  static bool lds_opt_in = false;
-  if (!lds_opt_in) {  // 69 KB of dynamic LDS at D = 256 (64 KB is the default ceiling)
-    hipFuncSetAttribute((const void*)r3d_cg_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    lds_opt_in = true;
-  }
+  // 69 KB of dynamic LDS at D = 256 (64 KB is the default ceiling)
+  R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_cg_aggregate_kernel, 96 * 1024) == 0,
+              "r3d_label_propagate: cannot reserve %d B of LDS", 96 * 1024);
   hipLaunchKernelGGL(r3d_cg_aggregate_kernel, dim3(r3d_cdiv(n_cap, 4 * agg_rpw), n_ep), dim3(256), agg_lds, st, nodes, ldn, D,
                      n_dev, n_proto_dev, n_cap, agg_rpw, L.agg, ep);
   hipLaunchKernelGGL(r3d_cg_mw_kernel, dim3(r3d_cdiv(n_cap, 4), n_ep), dim3(256), 0, st, L.row_ptr, L.col, L.val, L.dinv, L.agg,
@@ -1743,23 +1741,10 @@ extern "C" int r3d_debug_set_cg_spmv_lds_min_blocks(int min_blocks) {
 }
 
 // Workgroups of r3d_cg_spmv_lds_kernel the chip holds at once with lds_r bytes of residual each (occupancy x CUs; asked
-// once per size).
+// once per device and size).
 static int cg_lds_slots(size_t lds_r) {
-  static size_t asked = 0;
-  static int slots = 0;
-  if (lds_r != asked || !slots) {
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_cg_spmv_lds_kernel, 64 * SL_WAVES, lds_r) == hipSuccess &&
-        per_cu > 0 && hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-      slots = per_cu * cus;
-    else {
-      (void)hipGetLastError();
-      slots = 256;  // one workgroup per CU: always resident
-    }
-    asked = lds_r;
-  }
-  return slots;
+  const int slots = r3d_kernel_resident((const void*)r3d_cg_spmv_lds_kernel, 64 * SL_WAVES, lds_r);
+  return slots > 0 ? slots : 256;  // one workgroup per CU: always resident
 }
 
 // two-level CG on the already built graphs and coarse spaces: X = (I - alpha S)^-1 RHS for every system of the batch.
@@ -1786,12 +1771,8 @@ static int lp_solve(const LpWs& L, const float* RHS, long rhs_stride, const int3
   const size_t lds_r = (size_t)n_cap * sizeof(float4);
   const bool use_lds = lds_r <= SL_MAX_LDS && rpb == HG_ROWS_PER_BLOCK_MIN && (long)n_ep * r3d_cdiv(n_cap, SL_ROWS) >= g_cg_lds_min_blocks;
   if (use_lds) {
-    static size_t attr = 0;
-    if (lds_r > attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)r3d_cg_spmv_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-      R3D_REQUIRE(e == hipSuccess, "r3d_label_propagate: cannot reserve %zu B of LDS: %s", lds_r, hipGetErrorString(e));
-      attr = lds_r;
-    }
+    const int e = r3d_kernel_lds((const void*)r3d_cg_spmv_lds_kernel, lds_r);
+    R3D_REQUIRE(e == 0, "r3d_label_propagate: cannot reserve %zu B of LDS: %s", lds_r, hipGetErrorString((hipError_t)e));
   }
   // one resident round: the workgroups the chip holds at once, shared out among the systems (a system never takes more
   // than one per 128 rows, and a batch of more systems than slots runs one workgroup per system in several rounds)

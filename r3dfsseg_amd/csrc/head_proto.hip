@@ -842,26 +842,13 @@ extern "C" long r3d_head_proto_ws_words(int n_way, int k_shot, int N) { return h
 // fps_group: episodes whose farthest-point samplings share ONE persistent launch (flags & R3D_HEAD_FPS_ONE_LAUNCH): all
 // their workgroups that hold points must be co-resident, so the caller sizes it to the chip (~500 workgroup slots at
 // D <= 192, 250 above; an episode needs ceil(S N / 256) + n_way + 1); the batch takes ceil(n_ep / fps_group) such launches.
-// Workgroups of the persistent FPS kernel the chip holds at once (occupancy of the instantiation x CUs; asked once per
-// shape class) -> episodes per launch: what the caller asked for, clamped to that.
-static int fps_slots_clamp(int D, int tb_dense, int fps_group) {
-  static int slots[4] = {0, 0, 0, 0};
-  const int cls = D <= 64 ? 0 : D <= 128 ? 1 : D <= 192 ? 2 : 3;
-  if (!slots[cls]) {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    hipError_t e = cls == 0   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_fps_persistent_kernel<64, true, 0>, HP_BLOCK, 0)
-                   : cls == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_fps_persistent_kernel<128, true, 0>, HP_BLOCK, 0)
-                   : cls == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_fps_persistent_kernel<192, true, 0>, HP_BLOCK, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, r3d_fps_persistent_kernel<256, true, 0>, HP_BLOCK, 0);
-    if (e == hipSuccess && per_cu > 0 && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      slots[cls] = per_cu * prop.multiProcessorCount;
-    else {
-      (void)hipGetLastError();
-      slots[cls] = 256;  // one workgroup per CU: always resident
-    }
-  }
-  const int fit = slots[cls] / tb_dense;
+// Workgroups of `kernel`, the instantiation of the persistent FPS kernel that is about to be launched, the chip holds at
+// once (occupancy x CUs; asked once per device and instantiation) -> episodes per launch: what the caller asked for,
+// clamped to that.
+static int fps_slots_clamp(const void* kernel, int tb_dense, int fps_group) {
+  int slots = r3d_kernel_resident(kernel, HP_BLOCK, 0);
+  if (slots <= 0) slots = 256;  // one workgroup per CU: always resident
+  const int fit = slots / tb_dense;
   return fps_group < 1 ? 1 : (fit < 1 ? 1 : (fps_group < fit ? fps_group : fit));
 }
 
@@ -924,25 +911,23 @@ extern "C" int r3d_head_prototypes_batched(int n_ep, int fps_group, const int32_
   if (flags & R3D_HEAD_FPS_ONE_LAUNCH) {
     const int tb_dense = (int)((g.cap(0) + HP_BLOCK - 1) / HP_BLOCK) + g.nseg();  // the segments' counts add up to cap(0)
     r3d_fill_words_ep(xch, 0u, 2L * kr * tb_dense + 2L * R3D_HD_MAXSEG * HP_MAXK, n_ep, e2.ws, st);
-    // the launch's workgroups wait for each other: never more of them than the chip holds at once, whatever the caller asks
-    const int grp = fps_slots_clamp(D, tb_dense, fps_group);
-    for (int e0 = 0; e0 < n_ep; e0 += grp) {
-      const int ne = n_ep - e0 < grp ? n_ep - e0 : grp;
-#define FPS_ONE(DPAD, LC)                                                                                               \
-      do {                                                                                                              \
-        if (D == DPAD)                                                                                                  \
-          hipLaunchKernelGGL((r3d_fps_persistent_kernel<DPAD, true, LC>), dim3(tb_dense, ne), dim3(HP_BLOCK), 0, st, featC, pitch, \
-                             featP, D, g, desc, k, kr, xch, tb_dense, sel, e2, e0);                                         \
-        else                                                                                                            \
-          hipLaunchKernelGGL((r3d_fps_persistent_kernel<DPAD, false, LC>), dim3(tb_dense, ne), dim3(HP_BLOCK), 0, st, featC, pitch, \
-                             featP, D, g, desc, k, kr, xch, tb_dense, sel, e2, e0);                                         \
-      } while (0)
-      if (D <= 64) FPS_ONE(64, 0);
-      else if (D <= 128) FPS_ONE(128, 0);
-      else if (D <= 192) FPS_ONE(192, 0);
-      else FPS_ONE(256, 0);
+    // the launch's workgroups wait for each other: never more of them than the chip holds at once, whatever the caller
+    // asks -- and the kernel asked about is the one launched
+    auto fps_one = [&](auto kernel) {
+      const int grp = fps_slots_clamp((const void*)kernel, tb_dense, fps_group);
+      for (int e0 = 0; e0 < n_ep; e0 += grp) {
+        const int ne = n_ep - e0 < grp ? n_ep - e0 : grp;
+        hipLaunchKernelGGL(kernel, dim3(tb_dense, ne), dim3(HP_BLOCK), 0, st, featC, pitch, featP, D, g, desc, k, kr, xch, tb_dense,
+                           sel, e2, e0);
+      }
+    };
+    // (FULL: D fills the padded width, no channel masks; LC = 0, see the kernel)
+#define FPS_ONE(DPAD) (D == DPAD ? fps_one(r3d_fps_persistent_kernel<DPAD, true, 0>) : fps_one(r3d_fps_persistent_kernel<DPAD, false, 0>))
+    if (D <= 64) FPS_ONE(64);
+    else if (D <= 128) FPS_ONE(128);
+    else if (D <= 192) FPS_ONE(192);
+    else FPS_ONE(256);
 #undef FPS_ONE
-    }
   } else {
     for (int t = 0; t < kr; ++t) {
   #define FPS_LAUNCH(DPAD)                                                                                          \

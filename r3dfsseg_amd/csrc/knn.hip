@@ -1638,20 +1638,15 @@ struct KnnCall {
   float *norms; int* tile_flags; float* cm; unsigned short* pieces; float *mean, *cnorm; int* split_idx; float* split_sc;
 };
 
-// launch one configuration of the append-and-rank kernel (raising its dynamic-LDS limit once per instantiation);
+// launch one configuration of the append-and-rank kernel (raising its dynamic-LDS limit where this size needs it);
 // nsplit = grid.z
 template <int WAVES, int CAP, int TOP, int KCH, int SAMPLE, bool FULLC, bool BFA = false, bool BFB = false>
 static int knn_append_launch(const KnnCall& c, dim3 grid, int* status, int* tile_flags) {
   const size_t lds = knn_append_lds_bytes(c.C, WAVES, CAP, TOP, KCH, BFA);
   auto go = [&](auto smode) {
     constexpr int SM = decltype(smode)::value;
-    static size_t attr = 0;
-    if (lds > attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SM, BFA, BFB>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      R3D_REQUIRE(e == hipSuccess, "r3d_knn_topk: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-      attr = lds;
-    }
+    const int e = r3d_kernel_lds((const void*)r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SM, BFA, BFB>, lds);
+    R3D_REQUIRE(e == 0, "r3d_knn_topk: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString((hipError_t)e));
     hipLaunchKernelGGL((r3d_knn_append_kernel<WAVES, CAP, TOP, KCH, SAMPLE, FULLC, SM, BFA, BFB>), grid, dim3(64 * WAVES), lds,
                        c.st, c.xT, c.ldT, c.N, c.C, c.k, SM, c.n_dev, c.n_stride, c.norms, c.idx, c.sc, status, tile_flags,
                        (int)grid.z, c.split_idx, c.split_sc, BFA ? c.pieces : nullptr, BFA ? c.cnorm : nullptr,
@@ -1664,14 +1659,12 @@ static int knn_append_launch(const KnnCall& c, dim3 grid, int* status, int* tile
 
 // launch the sorted-insertion kernel
 template <int R>
-static void knn_insertion_launch(const KnnCall& c, size_t lds) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)r3d_knn_topk_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+static int knn_insertion_launch(const KnnCall& c, size_t lds) {
+  R3D_REQUIRE(r3d_kernel_lds((const void*)r3d_knn_topk_kernel<R>, 160 * 1024) == 0, "r3d_knn_topk: cannot reserve %d B of LDS",
+              160 * 1024);
   hipLaunchKernelGGL(r3d_knn_topk_kernel<R>, dim3(r3d_cdiv(c.N, KNN_Q), c.B), dim3(256), lds, c.st, c.x, c.ldx, c.N, c.C,
                      c.k, c.mode, c.n_dev, c.n_stride, c.norms, c.idx, c.sc);
+  return R3D_OK;
 }
 
 // the streamed kernels' channel-major operand (x_cm as given, or a copy of x into c.cm) and its squared norms
@@ -1734,9 +1727,9 @@ static int knn_topk_impl(const float* x, long ldx, const float* x_cm, int B, int
     R3D_REQUIRE(lds <= 160 * 1024, "r3d_knn_topk: C=%d needs %zu B of LDS (> 160 KiB)", c.C, lds);
     int rc = knn_sqnorm_launch(c.x, c.ldx, (long)c.B * c.N, c.C, c.norms, c.st);
     if (rc) return rc;
-    if (ch.regs == 1) knn_insertion_launch<1>(c, lds);
-    else if (ch.regs == 2) knn_insertion_launch<2>(c, lds);
-    else knn_insertion_launch<4>(c, lds);
+    rc = ch.regs == 1 ? knn_insertion_launch<1>(c, lds) : ch.regs == 2 ? knn_insertion_launch<2>(c, lds)
+                                                                        : knn_insertion_launch<4>(c, lds);
+    if (rc) return rc;
     R3D_LAUNCH_CHECK("r3d_knn_topk");
     return R3D_OK;
   }
